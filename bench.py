@@ -18,12 +18,15 @@ shared decode runs (include/fwamd.h).  N > 1: one process per GPU; rank 0 packs 
 over RCCL/xGMI, every rank processes its own batches (weak scaling, no data-path collective), per-step results
 are gathered to rank 0.
 
-Besides the metric the line carries (rank 0): `roofline` (dominant kernel family, HIP events on the engine's
-streams during a profiled round of the same workload), `cpu_baseline` (oracle port on the host cores, N = 1),
-and secondary measurements of the other SURVEY.md section 8 configurations: `pipeline` (section 8d wall-time
-definition: ndarray in host memory -> last Segment of a 1 h recording), `cap_case` (224 new tokens per chunk),
-`single_utterance` (C2: one 30 s chunk), and at N > 1 `sharded_recording` (C4: the 1 h recording sharded over
-the ranks — strong scaling).
+A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR` then also writes what
+the last timed step returned (DIR/<name>.npy, float64), so that two builds can be compared output for output.
+
+With `--full` the line also carries (rank 0): `verified` (the last timed batch decoded again alone, bit for bit),
+`roofline` (dominant kernel family, HIP events on the engine's streams during a profiled round of the same
+workload), `cpu_baseline` (oracle port on the host cores, N = 1), and secondary measurements of the other SURVEY.md
+section 8 configurations: `pipeline` (section 8d wall-time definition: ndarray in host memory -> last Segment of a
+1 h recording), `cap_case` (224 new tokens per chunk), `single_utterance` (C2: one 30 s chunk), and at N > 1
+`sharded_recording` (C4: the 1 h recording sharded over the ranks — strong scaling).
 """
 import argparse
 import datetime
@@ -258,11 +261,29 @@ def oracle_rev():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(path, res):
+    """--dump-outputs: what a caller of the timed path receives from one step — per chunk the hypothesis' token ids, its
+    score and the no-speech probability — as float64 arrays (ids and fp32 scores exactly): sequences_ids
+    [batch, hypotheses, new_tokens], scores [batch, hypotheses], no_speech_prob [batch]"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"sequences_ids": [r.sequences_ids for r in res], "scores": [r.scores for r in res],
+              "no_speech_prob": [r.no_speech_prob for r in res]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=64, help="timed steps (one 16-chunk batch each)")
+    ap.add_argument("--warmup", type=int, default=1,
+                    help="warm-up steps before the timed region, rounded up to whole rounds of the worker pool: every "
+                         "worker runs at least one (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the timed results, profile the kernels and take the cpu_baseline and the secondary "
+                         "measurements (several minutes); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned to DIR/<name>.npy (float64)")
     ap.add_argument("--model", default="large-v3")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--beam", type=int, default=5)
@@ -288,10 +309,11 @@ def parse_args(argv=None):
                     help="the pipeline measurement runs with vad_filter=True on the native device VAD (config C5: the recording "
                          "has digital silences, the Silero network — synthetic weights, calibrated to separate them — runs "
                          "INSIDE the timed wall, its spans are collected into chunks and the times restored)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile-pass", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
+    ap.add_argument("--no-profile-pass", action="store_true", help="--full without the profiled round (roofline)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (pipeline, cap_case, single_utterance, sharded_recording)")
+                    help="--full without the secondary measurements (pipeline, cap_case, single_utterance, "
+                         "sharded_recording)")
     ap.add_argument("--pipeline-chunks", type=int, default=960,
                     help="30 s chunks of the end-to-end recording (960 = 8 h: >= 10 s of wall, a steady state)")
     ap.add_argument("--dry-dist", action="store_true",
@@ -355,6 +377,12 @@ def main(argv=None, backend_factory=None, dist_backend=None):
     from faster_whisper_amd.sharding import gather_results
 
     cfg = get_config(args.model)
+    # every worker slot gets its OWN 16 chunks of PCM (set w: seed 1000 + rank + 7919 w), made while the model loads
+    # (the weight packer is native code that runs outside the GIL)
+    from concurrent.futures import ThreadPoolExecutor
+    n_sets = 1 if getattr(args, "dry_dist", False) else max(1, args.workers)
+    pcm_pool = ThreadPoolExecutor(max_workers=4)
+    pcm_sets = [pcm_pool.submit(synth_chunks, args.batch, 1000 + rank + 7919 * w) for w in range(n_sets)]
     t0 = time.time()
     model, weights = (backend_factory or build_backend)(args, cfg, rank, world, local_rank)
     load_s = time.time() - t0
@@ -368,14 +396,13 @@ def main(argv=None, backend_factory=None, dist_backend=None):
     lanes = getattr(args, "decode_lanes", 2)
     if lanes != 2 and hasattr(model, "set_decode_lanes"):
         model.set_decode_lanes(lanes)
-    chunks = synth_chunks(args.batch, seed=1000 + rank)
-    staged = model.stage_pcm(chunks)
-    # every worker slot of the pool its OWN 16 chunks of PCM (resident in HBM like `staged`): the batches in flight are
-    # different audio, as the batches of a recording are (step i takes set i mod W; set 0 = `staged`)
-    staged_sets = [staged]
-    if hasattr(model, "stage_pcm") and not getattr(args, "dry_dist", False):
-        for w in range(1, max(1, args.workers)):
-            staged_sets.append(model.stage_pcm(synth_chunks(args.batch, seed=1000 + rank + 7919 * w)))
+    chunks = pcm_sets[0].result()
+    # the PCM sets resident in HBM: the batches in flight are different audio, as the batches of a recording are
+    # (step i takes set i mod W; set 0 = `staged`)
+    staged_sets = [model.stage_pcm(f.result()) for f in pcm_sets]
+    staged = staged_sets[0]
+    pcm_pool.shutdown()
+    del pcm_sets
     prompt = list(cfg.sot_sequence) + [cfg.no_timestamps]
     L = args.new_tokens
     sup = [cfg.sot, cfg.sot_prev, cfg.sot_lm, cfg.no_speech, cfg.translate, cfg.transcribe]
@@ -396,15 +423,15 @@ def main(argv=None, backend_factory=None, dist_backend=None):
 
     # W host threads, one worker replica (encoder stream + workspaces, shared weights) each: the batches of a long
     # recording are independent, so several are kept in flight on the GPU at once.
-    from concurrent.futures import ThreadPoolExecutor
     import threading
     W = max(1, args.workers)
     pool = ThreadPoolExecutor(max_workers=W)
     sync = threading.Barrier(W)
+    warm_rounds = -(-args.warmup // W) if args.warmup > 0 else 0
 
     def warm(_):
         sync.wait()                      # every pool thread takes exactly one of these tasks
-        for _ in range(max(1, args.warmup)):
+        for _ in range(warm_rounds):
             r = step()
         return r
 
@@ -455,20 +482,24 @@ def main(argv=None, backend_factory=None, dist_backend=None):
         dist.barrier()
         dist.destroy_process_group()
         return {"dry_dist": True}
-    if args.warmup > 0:
+    if warm_rounds:
         list(pool.map(warm, range(W)))
     phase("warmup")
     stats0 = model.decode_stats()
     elapsed = timed(args.steps)
     stats1 = model.decode_stats()
-    # ---- the timed configuration checks itself: the last batch of the timed region (decoded inside a merged run of
-    #      many batches) against the same batch decoded ALONE afterwards — ids, scores and no-speech probabilities
-    #      must be identical bit for bit (every kernel works per row / per chunk; tests/test_gpu_full_size.py checks
-    #      the same geometry against the oracle) ----
-    merged_res = last["res"]
-    solo_res = step(which=last["which"])
-    verified = all(a.sequences_ids == b.sequences_ids and a.scores == b.scores and a.no_speech_prob == b.no_speech_prob
-                   for a, b in zip(merged_res, solo_res)) and len(merged_res) == len(solo_res) == args.batch
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["res"])
+    verified = None
+    if args.full:
+        # ---- the timed configuration checks itself: the last batch of the timed region (decoded inside a merged run of
+        #      many batches) against the same batch decoded ALONE afterwards — ids, scores and no-speech probabilities
+        #      must be identical bit for bit (every kernel works per row / per chunk; tests/test_gpu_full_size.py checks
+        #      the same geometry against the oracle) ----
+        merged_res = last["res"]
+        solo_res = step(which=last["which"])
+        verified = all(a.sequences_ids == b.sequences_ids and a.scores == b.scores and a.no_speech_prob == b.no_speech_prob
+                       for a, b in zip(merged_res, solo_res)) and len(merged_res) == len(solo_res) == args.batch
 
     audio_s = 30.0 * args.batch * args.steps * world
     value = audio_s / elapsed
@@ -476,12 +507,13 @@ def main(argv=None, backend_factory=None, dist_backend=None):
     out = {
         "metric": "audio-sec/sec (RTF) large-v3 fp16 beam=5 batch=16", "value": round(value, 2),
         "unit": "audio-seconds per wall-second", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "warmup_steps": warm_rounds * W,
         "ms_per_step": round(1000.0 * elapsed / max(1, args.steps), 3), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f16" if args.compute_type == "float16" else "i8/f16",
         "data": "synthetic",
-        "verified": bool(verified),
-        "verified_what": "last batch of the timed region (decoded in a merged run) == the same batch decoded alone "
-                         "afterwards: ids, scores, no_speech_prob bit-identical",
+        **({"verified": bool(verified),
+            "verified_what": "last batch of the timed region (decoded in a merged run) == the same batch decoded alone "
+                             "afterwards: ids, scores, no_speech_prob bit-identical"} if args.full else {}),
         "value_definition": "step = one 16-chunk batch, PCM resident in HBM -> ids / scores on the host (the task's bench "
                             "contract); `pipeline` is the SURVEY section 8d wall (ndarray in host memory -> last Segment)",
         "config": {"workload": f"{args.model} {args.compute_type} BatchedInferencePipeline hot path: {args.batch} x 30 s "
@@ -495,7 +527,7 @@ def main(argv=None, backend_factory=None, dist_backend=None):
                    "steady_state": args.steps >= 2 * W,
                    "steady_state_note": ("the timed region is at least two rounds of the worker pool" if args.steps >= 2 * W else
                                          f"{args.steps} steps < 2 x {W} workers: the timed region is ONE burst of the pool; "
-                                         "`steady` holds the same measurement over 4 rounds"),
+                                         "with --full, `steady` holds the same measurement over 4 rounds"),
                    "model_load_s": round(load_s, 1),
                    **({"blob_broadcast_s": TIMES["blob_broadcast_s"],
                        "blob_broadcast_what": "RCCL broadcast of the packed weight blob from rank 0's device memory (no host "
@@ -516,7 +548,7 @@ def main(argv=None, backend_factory=None, dist_backend=None):
                                                        "5 500x with the two roofs ADDED (SURVEY's method), 7 450x if they "
                                                        "overlapped perfectly — the fraction over 4 525x flatters the gap"}
         out["roofline_combined"]["value_over_merged_run_ceiling"] = round(value / (5500.0 * world), 4)
-    secondary = not args.no_secondary
+    secondary = args.full and not args.no_secondary
     # ---- secondary, all ranks take part: steady state, the cap case and (N > 1) the sharded recording ----
     if secondary and args.steps < 2 * W:
         ns = 4 * W
@@ -539,7 +571,7 @@ def main(argv=None, backend_factory=None, dist_backend=None):
     if rank == 0:
         # ---- roofline of the dominant kernel family: one profiled round of the same workload (HIP events on the
         #      engine's streams; the decode step runs eagerly instead of as a graph replay while profiling) ----
-        if not args.no_profile_pass:
+        if args.full and not args.no_profile_pass:
             # ONE decode run at a time while profiling: with two lanes a kernel's event-to-event time would include the
             # other lane's kernels running beside it; the roofline is a statement about the kernel
             if hasattr(model, "set_decode_lanes"):
@@ -649,7 +681,7 @@ def main(argv=None, backend_factory=None, dist_backend=None):
             out["one_batch_at_a_time"] = one_batch(model, staged, chunks, prompt, gen_kw(L), L, args.batch)
         # ---- CPU baseline: the oracle (torch fp32 port) on a bounded sample of the same workload ----
         # (reported at N = 1 only: at N > 1 the other ranks would idle at the final barrier while it runs)
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             out["cpu_baseline"] = cpu_baseline(cfg, weights, chunks, prompt, args.beam, L, gen_kw(L))
         print(json.dumps(out), flush=True)
     for st_ in staged_sets:
@@ -658,7 +690,7 @@ def main(argv=None, backend_factory=None, dist_backend=None):
     if multi:
         dist.barrier()
         dist.destroy_process_group()
-    if not verified:
+    if verified is False:
         # a merged run that does not reproduce the solo run bit for bit is a wrong result, not a slow one
         raise SystemExit("bench.py: the last batch of the timed region differs from the same batch decoded alone "
                          "(`verified`: false) — the line above must not be used")

@@ -16,7 +16,9 @@ Tensor names / shapes (PyTorch [out, in] convention, biases 1-D):
   dec.{i}.cross.out.w/.b  dec.{i}.ln3.g/b  dec.{i}.ffn1.w/.b  dec.{i}.ffn2.w/.b
   dec.ln.g/b
 """
+import os
 import zlib
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict
 
 import numpy as np
@@ -78,8 +80,9 @@ def synthetic_weights(cfg: WhisperConfig, seed: int = 1234, dtype=np.float16, pe
     it differs from step to step; the audio moves the margins, not the winner (random weights attend nearly uniformly
     over the 1 500 frames, so the cross-attention output hardly depends on the audio — measured)."""
     d = cfg.d_model
-    out = {}
-    for name, shape in weight_shapes(cfg).items():
+
+    def make(item):
+        name, shape = item
         rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
         if name == "enc.pos":
             w = sinusoids(cfg.n_audio_ctx, d)
@@ -109,7 +112,12 @@ def synthetic_weights(cfg: WhisperConfig, seed: int = 1234, dtype=np.float16, pe
                 scale *= 0.5  # residual branches: keep the stream from growing
             w = rng.standard_normal(shape, dtype=np.float32)
             w *= scale
-        out[name] = np.ascontiguousarray(w.astype(dtype))
+        return name, np.ascontiguousarray(w.astype(dtype))
+
+    # the streams are independent and numpy fills arrays without the GIL: large-v3's 1.5 G values take seconds on a
+    # thread pool instead of most of the benchmark's start-up on one core; the result does not depend on the pool
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        out = dict(pool.map(make, weight_shapes(cfg).items()))
     return make_peaked(cfg, out, seed) if peaked else out
 
 

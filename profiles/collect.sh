@@ -4,7 +4,7 @@
 #   gpurun --timeout 1200 -- 'timeout 1100 bash profiles/collect.sh r03'
 #
 # Writes under gpurun_out/<tag>/ and copies what is to be judged into profiles/<tag>_*:
-#   bench.json                  python bench.py (the bench line: roofline + cpu_baseline + secondary measurements)
+#   bench.json                  python bench.py --full (the bench line: roofline + cpu_baseline + secondary measurements)
 #   kernel_stats_w1.csv         rocprofv3 --kernel-trace --stats, ONE batch at a time (16-chunk decode runs), eager decode
 #   kernel_stats_w32.csv        the same with the bench's 32 workers: merged decode runs next to the encoders (durations
 #                               of concurrent kernels overlap in this one: read it for the decode stream)
@@ -50,7 +50,7 @@ pmc fetch_w32 --steps 32 --warmup 1 -- FETCH_SIZE
 pmc sq --workers 1 --steps 1 --warmup 1 -- SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS
 cd "$R"
 cp "$OUT/pmc_fetch.json" "$R/profiles/${TAG}_pmc_fetch.json" 2>/dev/null
-timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench.json"
+timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench.json"
 timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_cmd.json" 2> "$OUT/bench_driver_cmd.err"; echo "driver-cmd bench rc=$?"; cut -c1-300 "$OUT/bench_driver_cmd.json"
 head -12 "$OUT/kernel_stats_w1.csv" | cut -c1-150
 head -8 "$OUT/kernel_stats_w32.csv" | cut -c1-150

@@ -24,7 +24,7 @@ for n in sys.argv[1:]:
     print("   ms", j.get("families_ms_per_step"))
 PY
 }
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 timeout 400 $B --steps 32 > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "== bench rc=$?"; cut -c1-300 "$OUT/bench.json"; tail -2 "$OUT/bench.err"
 if [ -n "${AB_ENV:-}" ]; then   # A/B of an experiment knob: AB_ENV="FWAMD_X=1"
   env $AB_ENV timeout 400 $B --steps 32 --no-secondary > "$OUT/bench_ab.json" 2> "$OUT/bench_ab.err"; echo "== bench with $AB_ENV rc=$? $(cut -c1-160 $OUT/bench_ab.json)"

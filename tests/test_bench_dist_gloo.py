@@ -109,7 +109,7 @@ n_shard, batch = os.environ.get("FW_SHARDED_CHUNKS", "11"), os.environ.get("FW_B
 out = bench.main(["--gpus", os.environ["WORLD_SIZE"], "--model", "micro", "--batch", batch, "--beam", "5",
                   "--steps", os.environ.get("FW_STEPS", "6"),
                   "--warmup", "1", "--workers", "2", "--new-tokens", "12", "--pipeline-chunks", "11", "--sharded-chunks", n_shard,
-                  "--no-cpu-baseline"] + os.environ.get("FW_EXTRA_ARGS", "").split(), backend_factory=factory, dist_backend="gloo")
+                  "--full", "--no-cpu-baseline"] + os.environ.get("FW_EXTRA_ARGS", "").split(), backend_factory=factory, dist_backend="gloo")
 if int(os.environ["RANK"]) != 0:
     print("RANK_DONE", flush=True)
 if os.environ.get("FW_SERIAL_DIGEST"):
@@ -196,7 +196,7 @@ def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
                         "--model", "micro", "--batch", "4", "--beam", "5", "--workers", "2", "--new-tokens", "12",
-                        "--pipeline-chunks", "11", "--sharded-chunks", "11", "--no-cpu-baseline"],
+                        "--pipeline-chunks", "11", "--sharded-chunks", "11", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -55,3 +55,44 @@ def test_cpu_baseline_all_cores_form(monkeypatch):
         assert abs(out["value"] - sum(out["all_cores"]["per_stream_value"])) < 1e-2 * out["value"]   # (each rounded to 4 digits)
     else:
         assert out["cores"] == 2 and out["value"] == out["one_stream"]["value"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, monkeypatch):
+    """a plain run sets up, warms up, times --steps steps and prints the line, nothing of --full; --dump-outputs writes
+    what the last timed step returned, the same from run to run; --full adds the checks and secondary figures"""
+    from faster_whisper_amd import get_config
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "FWAMD_DIST_AT_WORLD_1", "FWAMD_BENCH_SEAM"):
+        monkeypatch.delenv(k, raising=False)
+    made = []
+
+    def factory(args, cfg, rank, world, local_rank):
+        made.append(_fake_backend(cfg, args.workers))
+        return made[-1], None
+
+    argv = ["--model", "micro", "--batch", "4", "--beam", "5", "--steps", "5", "--warmup", "3", "--workers", "2",
+            "--new-tokens", "12"]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        j = bench.main(argv + ["--dump-outputs", str(d)], backend_factory=factory)
+        assert j["steps"] == 5 and j["warmup_steps"] == 4 and j["ms_per_step"] > 0 and j["value"] > 0
+        for key in ("verified", "roofline", "cpu_baseline", "pipeline", "cap_case", "steady", "single_utterance",
+                    "one_batch_at_a_time"):
+            assert key not in j, key
+        # two rounds of the pool warm up (3 steps rounded up to whole rounds of 2 workers), then the 5 timed steps
+        assert made[-1].calls["generate"] == 4 + 5
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("sequences_ids", "scores", "no_speech_prob")})
+    a, b = dumps
+    assert a["sequences_ids"].shape == (4, 1, 12) and a["scores"].shape == (4, 1) and a["no_speech_prob"].shape == (4,)
+    assert all(v.dtype == np.float64 and np.array_equal(v, b[n]) for n, v in a.items())
+    # the last timed step (index 4) took PCM set 4 mod 2 = 0: what the backend returns for that batch
+    cfg = get_config("micro")
+    fake = _fake_backend(cfg)
+    prompt = list(cfg.sot_sequence) + [cfg.no_timestamps]
+    res = fake.generate(fake.encode_pcm(bench.synth_chunks(4, seed=1000)), [prompt] * 4, max_length=len(prompt) + 12)
+    assert np.array_equal(a["sequences_ids"], np.asarray([r.sequences_ids for r in res], dtype=np.float64))
+    assert np.array_equal(a["scores"], np.asarray([r.scores for r in res], dtype=np.float64))
+
+    j = bench.main(argv + ["--full", "--no-cpu-baseline", "--pipeline-chunks", "6"], backend_factory=factory)
+    assert j["verified"] is True and j["cap_case"]["value"] > 0 and "error" not in j["pipeline"]
+    assert j["roofline"]["kernel"] == "dec_cross_attn" and j["single_utterance"]["value"] > 0

@@ -21,7 +21,7 @@ sys.path.insert(0, os.environ["FW_ROOT"])
 import numpy as np
 import bench
 out = bench.main(["--gpus", "1", "--model", "micro", "--batch", "4", "--beam", "5", "--steps", "6", "--warmup", "1",
-                  "--workers", "2", "--new-tokens", "12", "--sharded-chunks", "11", "--no-profile-pass"])
+                  "--workers", "2", "--new-tokens", "12", "--sharded-chunks", "11", "--full", "--no-profile-pass"])
 import torch.distributed as dist
 assert not dist.is_initialized()          # bench tore its process group down
 # the same recording, same model geometry and weights, no process group: the serial result
