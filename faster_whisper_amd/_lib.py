@@ -77,7 +77,8 @@ SYMBOLS = [
     "fw_generate", "fw_detect_language", "fw_align",
     "fw_prof_enable", "fw_prof_reset", "fw_prof_count", "fw_prof_name", "fw_prof_get", "fw_synchronize",
     "fw_dev_alloc", "fw_dev_free", "fw_dev_upload",
-    "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules", "fw_bench_gemm", "fw_bench_dec_linear", "fw_bench_attention",
+    "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules",
+    "fw_test_dec_self_attn", "fw_test_dec_cross_attn", "fw_test_dec_cross_probs", "fw_test_dec_softmax_pick", "fw_bench_gemm", "fw_bench_dec_linear", "fw_bench_attention",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_flac_info", "fw_flac_decode",
 ]
@@ -164,6 +165,11 @@ def load():
     lib.fw_test_dec_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.fw_test_dec_logits.argtypes = [vp, vp, i32, vp]
     lib.fw_test_logits_rules.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp]
+    if hasattr(lib, "fw_test_dec_self_attn"):   # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_test_dec_self_attn.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.fw_test_dec_cross_attn.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, C.c_float, vp]
+        lib.fw_test_dec_cross_probs.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp]
+        lib.fw_test_dec_softmax_pick.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.fw_bench_attention.argtypes = [vp, i32, i32, i32, i32, i32, f32p]
     lib.fw_bench_gemm.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, f32p]
     lib.fw_bench_dec_linear.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32p]

@@ -1690,6 +1690,17 @@ static int download_f16(Model* m, const half_t* src, size_t n, float* dst) {
   return FW_OK;
 }
 
+// fragment-major position of key mm, column n (head n / 64) inside one encoder chunk's cross-attention K (vt = false) or
+// V^T (vt = true) block of [H][kvp * 64] halves: the layout the projection GEMM's epilogue writes (gemm.hip) and
+// dec_cross_attn_kernel / dec_cross_probs_kernel read (dec_kernels.hip, K14).  The one host statement of it: the gemm
+// hook un-permutes through it, the cross-attention hooks permute through it.
+static inline size_t cross_kv_frag_pos(bool vt, int kvp, int mm, int n) {
+  const int c = n & 63, r = mm & 31;
+  const size_t head = (size_t)(n >> 6) * kvp * 64;
+  return vt ? head + ((size_t)((mm >> 5) * 4 + (c >> 4)) * 64 + ((mm >> 3) & 3) * 16 + (c & 15)) * 8 + (mm & 7)
+            : head + ((size_t)((mm >> 5) * 4 + 2 * ((r >> 2) & 1) + (c >> 5)) * 64 + ((c >> 3) & 3) * 16 + (((r >> 3) << 2) | (r & 3))) * 8 + (c & 7);
+}
+
 int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* bias, const float* residual,
                      int32_t M, int32_t N, int32_t K, int32_t act_gelu, int32_t use_int8, float* out) {
   FW_CHECK_ARG(fm && A && W && out, "null argument");
@@ -1749,9 +1760,7 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
     if (!rc) {
       for (int mm = 0; mm < kvp && !rc; ++mm)
         for (int n = 0; n < N; ++n) {
-          const int c = n & 63, r = mm & 31;
-          const size_t off = vt ? (size_t)(n >> 6) * kvp * 64 + ((size_t)((mm >> 5) * 4 + (c >> 4)) * 64 + ((mm >> 3) & 3) * 16 + (c & 15)) * 8 + (mm & 7)
-                                : (size_t)(n >> 6) * kvp * 64 + ((size_t)((mm >> 5) * 4 + 2 * ((r >> 2) & 1) + (c >> 5)) * 64 + ((c >> 3) & 3) * 16 + (((r >> 3) << 2) | (r & 3))) * 8 + (c & 7);
+          const size_t off = cross_kv_frag_pos(vt, kvp, mm, n);
           if (mm < M) out[(size_t)mm * N + n] = hf[off];
           else if (hf[off] != 0.f) { set_error("fragment-major epilogue wrote the padded key %d", mm); rc = FW_ERUNTIME; break; }
         }
@@ -2175,6 +2184,181 @@ int32_t fw_bench_attention(fw_model* fm, int32_t B, int32_t H, int32_t T, int32_
   cleanup();
   if (he != hipSuccess) { set_error("attention bench failed: %s", hipGetErrorString(he)); return FW_ERUNTIME; }
   *ms_out = ms / (float)iters;
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- decoder attention hooks (tests/test_gpu_dec_attention.py)
+// Each one uploads host buffers, runs the product's own launcher on m->stream (the form / register cap a decode step
+// would take under knobs 2 / 7) and downloads.  Every index the kernels turn into an address is checked here first.
+extern "C++" {
+namespace {
+struct DevBufs {   // device buffers of one hook call, freed on every return path
+  std::vector<void*> p;
+  template <typename T>
+  int alloc(T** dst, size_t n) {
+    int rc = dev_alloc_t(dst, n);
+    if (!rc) p.push_back(*dst);
+    return rc;
+  }
+  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
+};
+int upload_f16_to(const float* src, size_t n, half_t* dst) {
+  std::vector<uint16_t> tmp(n);
+  for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_f16_bits(src[i]);
+  FW_HIP(hipMemcpy(dst, tmp.data(), n * 2, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t fw_test_dec_self_attn(fw_model* fm, const float* qkv, float* kcache, float* vcache, const uint8_t* kvidx,
+                              int32_t n_chunks, int32_t kmul, int32_t Kbeam, int32_t H, int32_t n_ctx, int32_t cache_ctx,
+                              int32_t pos_fixed, int32_t P, int32_t step, int32_t blk_n, int32_t frag, float* out) {
+  FW_CHECK_ARG(fm && qkv && kcache && vcache && kvidx && out, "null argument");
+  FW_CHECK_ARG(n_chunks >= 1 && H >= 1 && kmul >= 1 && kmul <= 16 && Kbeam >= 1 && Kbeam <= 255, "bad geometry");
+  FW_CHECK_ARG(n_ctx >= 1 && n_ctx <= 448 && cache_ctx >= 1 && cache_ctx <= n_ctx, "need 1 <= cache_ctx <= n_ctx <= 448");
+  FW_CHECK_ARG(blk_n >= 0 && (blk_n == 0 ? kmul <= Kbeam : (kmul == blk_n && pos_fixed >= 0)),
+               "blk_n = 0: kmul <= Kbeam; blk_n > 0: kmul == blk_n and pos_fixed >= 0");
+  const int pos0 = pos_fixed >= 0 ? pos_fixed : P - 1 + step;
+  const int pos_last = pos0 + (blk_n > 0 ? blk_n - 1 : 0);
+  FW_CHECK_ARG(pos0 >= 0 && pos_last < cache_ctx, "positions %d..%d outside the cache (%d)", pos0, pos_last, cache_ctx);
+  const int d = H * 64, R = n_chunks * kmul, R16 = (R + 15) / 16 * 16, R_total = n_chunks * Kbeam;
+  FW_CHECK_ARG(blk_n == 0 || fwd::self_attn_block_ok(n_ctx, cache_ctx, d, R_total), "position blocks need n_ctx %% 4 == 0");
+  const size_t n_tab = (size_t)2 * R_total * n_ctx, n_cache = (size_t)R_total * H * cache_ctx * 64;
+  for (size_t i = 0; i < n_tab; ++i)
+    FW_CHECK_ARG(kvidx[i] < Kbeam, "kvidx[%zu] = %d is not a beam of %d", i, (int)kvidx[i], Kbeam);
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  DevBufs db;
+  half_t *d_qkv, *d_kc, *d_vc, *d_out;
+  uint8_t* d_idx;
+  int* d_step;
+  int rc;
+  if ((rc = db.alloc(&d_qkv, (size_t)R * 3 * d)) || (rc = db.alloc(&d_kc, n_cache)) || (rc = db.alloc(&d_vc, n_cache)) ||
+      (rc = db.alloc(&d_out, (size_t)R16 * d)) || (rc = db.alloc(&d_idx, n_tab)) || (rc = db.alloc(&d_step, 1)))
+    return rc;
+  if ((rc = upload_f16_to(qkv, (size_t)R * 3 * d, d_qkv)) || (rc = upload_f16_to(kcache, n_cache, d_kc)) ||
+      (rc = upload_f16_to(vcache, n_cache, d_vc)))
+    return rc;
+  FW_HIP(hipMemcpy(d_idx, kvidx, n_tab, hipMemcpyHostToDevice));
+  FW_HIP(hipMemcpy(d_step, &step, sizeof(int), hipMemcpyHostToDevice));
+  FW_HIP(hipMemset(d_out, 0, (size_t)R16 * d * 2));
+  fwd::launch_self_attn(m->stream, d_qkv, d, d_kc, d_vc, n_ctx, cache_ctx, H, d_idx, Kbeam, kmul, d_out, R, d_step,
+                        pos_fixed, P, R_total, frag ? 1 : 0, blk_n);
+  FW_HIP(hipGetLastError());
+  if ((rc = download_f16(m, d_kc, n_cache, kcache)) || (rc = download_f16(m, d_vc, n_cache, vcache))) return rc;
+  if (!frag) return download_f16(m, d_out, (size_t)R * d, out);
+  std::vector<float> of((size_t)R16 * d);
+  if ((rc = download_f16(m, d_out, of.size(), of.data()))) return rc;
+  for (int r = 0; r < R; ++r)
+    for (int n = 0; n < d; ++n) out[(size_t)r * d + n] = of[frag_pos(r, n, d, 32)];
+  return FW_OK;
+}
+
+int32_t fw_test_dec_cross_attn(fw_model* fm, const float* q, const float* k, const float* v, int32_t n_enc, int32_t T,
+                               int32_t H, int32_t B, int32_t kmul, int32_t kv_div, const int32_t* slot_map,
+                               const int32_t* done, int32_t frag, float k_pad, float* out) {
+  FW_CHECK_ARG(fm && q && k && v && slot_map && out, "null argument");
+  FW_CHECK_ARG(n_enc >= 1 && T >= 1 && H >= 1 && B >= 1 && kmul >= 1 && kmul <= 16 && kv_div >= 1, "bad geometry");
+  const int n_map = (B + kv_div - 1) / kv_div;
+  for (int i = 0; i < n_map; ++i)
+    FW_CHECK_ARG(slot_map[i] >= 0 && slot_map[i] < n_enc, "slot_map[%d] = %d outside [0, %d)", i, slot_map[i], n_enc);
+  const int d = H * 64, kvp = (T + 31) / 32 * 32, R = B * kmul, R16 = (R + 15) / 16 * 16;
+  const size_t blk = (size_t)d * kvp;   // one encoder chunk's K (or V^T)
+  // the pool's layout and contract (decoder.hip: CrossPool): padded keys of K hold whatever (k_pad), of V^T zeros
+  std::vector<float> kf((size_t)n_enc * blk), vf((size_t)n_enc * blk, 0.f);
+  for (int e = 0; e < n_enc; ++e)
+    for (int t = 0; t < kvp; ++t)
+      for (int n = 0; n < d; ++n) {
+        const size_t src = ((size_t)e * T + t) * d + n;
+        kf[e * blk + cross_kv_frag_pos(false, kvp, t, n)] = t < T ? k[src] : k_pad;
+        if (t < T) vf[e * blk + cross_kv_frag_pos(true, kvp, t, n)] = v[src];
+      }
+  std::vector<float> of((size_t)R16 * d, 0.f);
+  if (frag)
+    for (int r = 0; r < R; ++r)
+      for (int n = 0; n < d; ++n) of[frag_pos(r, n, d, 32)] = out[(size_t)r * d + n];
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  DevBufs db;
+  half_t *d_q, *d_k, *d_vt, *d_out;
+  int *d_map, *d_done = nullptr;
+  int rc;
+  if ((rc = db.alloc(&d_q, (size_t)R * d)) || (rc = db.alloc(&d_k, kf.size())) || (rc = db.alloc(&d_vt, vf.size())) ||
+      (rc = db.alloc(&d_out, (size_t)R16 * d)) || (rc = db.alloc(&d_map, (size_t)n_map)) || (done && (rc = db.alloc(&d_done, (size_t)B))))
+    return rc;
+  if ((rc = upload_f16_to(q, (size_t)R * d, d_q)) || (rc = upload_f16_to(kf.data(), kf.size(), d_k)) ||
+      (rc = upload_f16_to(vf.data(), vf.size(), d_vt)) || (rc = upload_f16_to(frag ? of.data() : out, frag ? of.size() : (size_t)R * d, d_out)))
+    return rc;
+  FW_HIP(hipMemcpy(d_map, slot_map, (size_t)n_map * sizeof(int), hipMemcpyHostToDevice));
+  if (done) FW_HIP(hipMemcpy(d_done, done, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  fwd::launch_cross_attn(m->stream, d_q, d, d_k, d_vt, T, kvp, kmul, d_out, B, H, d_done, kv_div, frag ? 1 : 0, d_map);
+  FW_HIP(hipGetLastError());
+  if (!frag) return download_f16(m, d_out, (size_t)R * d, out);
+  if ((rc = download_f16(m, d_out, of.size(), of.data()))) return rc;
+  for (int r = 0; r < R; ++r)
+    for (int n = 0; n < d; ++n) out[(size_t)r * d + n] = of[frag_pos(r, n, d, 32)];
+  return FW_OK;
+}
+
+int32_t fw_test_dec_cross_probs(fw_model* fm, const float* q, const float* k, int32_t B, int32_t T, int32_t H,
+                                const int32_t* heads, int32_t n_sel, int32_t n_tok, int32_t tok_idx, int32_t blk_n,
+                                float* probs) {
+  FW_CHECK_ARG(fm && q && k && heads && probs, "null argument");
+  const int blk = blk_n > 0 ? blk_n : 1;
+  FW_CHECK_ARG(B >= 1 && T >= 1 && H >= 1 && n_sel >= 1 && blk_n >= 0 && blk <= 16, "bad geometry");
+  FW_CHECK_ARG(tok_idx >= 0 && tok_idx + blk <= n_tok, "tokens %d..%d outside [0, %d)", tok_idx, tok_idx + blk - 1, n_tok);
+  for (int i = 0; i < n_sel; ++i) FW_CHECK_ARG(heads[i] >= 0 && heads[i] < H, "heads[%d] = %d outside [0, %d)", i, heads[i], H);
+  const int d = H * 64, kvp = (T + 31) / 32 * 32;
+  const size_t blkk = (size_t)d * kvp, n_probs = (size_t)B * n_sel * n_tok * T;
+  std::vector<float> kf((size_t)B * blkk, 0.f);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < T; ++t)
+      for (int n = 0; n < d; ++n) kf[b * blkk + cross_kv_frag_pos(false, kvp, t, n)] = k[((size_t)b * T + t) * d + n];
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  DevBufs db;
+  half_t *d_q, *d_k;
+  int* d_heads;
+  float* d_p;
+  int rc;
+  if ((rc = db.alloc(&d_q, (size_t)B * blk * d)) || (rc = db.alloc(&d_k, kf.size())) || (rc = db.alloc(&d_heads, (size_t)n_sel)) ||
+      (rc = db.alloc(&d_p, n_probs)))
+    return rc;
+  if ((rc = upload_f16_to(q, (size_t)B * blk * d, d_q)) || (rc = upload_f16_to(kf.data(), kf.size(), d_k))) return rc;
+  FW_HIP(hipMemcpy(d_heads, heads, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice));
+  FW_HIP(hipMemcpy(d_p, probs, n_probs * sizeof(float), hipMemcpyHostToDevice));
+  fwd::launch_cross_probs(m->stream, d_q, d, d_k, T, kvp, d_heads, n_sel, n_sel, d_p, n_tok, tok_idx, B, blk_n);
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipStreamSynchronize(m->stream));
+  FW_HIP(hipMemcpy(probs, d_p, n_probs * sizeof(float), hipMemcpyDeviceToHost));
+  return FW_OK;
+}
+
+int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows, int32_t V, int32_t row_mul,
+                                 const int32_t* target, int32_t nospeech, float* out) {
+  FW_CHECK_ARG(fm && logits && target && out, "null argument");
+  FW_CHECK_ARG(rows >= 1 && V >= 1 && row_mul >= 1, "bad geometry");
+  FW_CHECK_ARG(!nospeech || (target[0] >= 0 && target[0] < V), "no-speech id %d outside [0, %d)", target[0], V);
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  DevBufs db;
+  const size_t n_lg = (size_t)rows * row_mul * V;
+  float *d_lg, *d_out;
+  int* d_t;
+  int rc;
+  if ((rc = db.alloc(&d_lg, n_lg)) || (rc = db.alloc(&d_out, (size_t)rows)) || (rc = db.alloc(&d_t, (size_t)rows))) return rc;
+  FW_HIP(hipMemcpy(d_lg, logits, n_lg * sizeof(float), hipMemcpyHostToDevice));
+  FW_HIP(hipMemcpy(d_t, target, (size_t)(nospeech ? 1 : rows) * sizeof(int), hipMemcpyHostToDevice));
+  if (nospeech) fwd::launch_nospeech(m->stream, d_lg, V, row_mul, target[0], d_out, rows);
+  else fwd::launch_token_prob(m->stream, d_lg, V, d_t, d_out, 1, 0, rows, row_mul);
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipStreamSynchronize(m->stream));
+  FW_HIP(hipMemcpy(out, d_out, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
   return FW_OK;
 }
 

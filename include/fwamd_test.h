@@ -49,6 +49,36 @@ int32_t fw_test_layernorm(fw_model* m, const float* x, const float* g, const flo
                           int32_t rows, int32_t d, float* out);
 int32_t fw_test_attention(fw_model* m, const float* q, const float* k, const float* v,
                           int32_t B, int32_t H, int32_t T, float* out);
+/* decoder self-attention, one launch exactly as a decode step makes it (dec_kernels.hip: launch_self_attn; the form
+ * follows knob 2): qkv [R][3 d] (d = H * 64, R = n_chunks * kmul), K / V cache kcache / vcache
+ * [n_chunks * Kbeam][H][cache_ctx][64] IN / OUT (returned as the launch leaves it: the new K / V of each row written at
+ * its position of its own slot), slot table kvidx [2][n_chunks * Kbeam][n_ctx] (every byte < Kbeam: checked) ->
+ * out [R][d].  Position pos_fixed, or with pos_fixed < 0 the step counter route: the device step counter holds `step`,
+ * pos = P - 1 + step and the slot table half step & 1 is read.  blk_n > 0 (needs kmul == blk_n, pos_fixed >= 0):
+ * position blocks, row c * blk_n + j = position pos_fixed + j of chunk c's beam slot 0.  frag = 1: the fragment-major
+ * output of the fp16 path, un-permuted on the host; 0: the row-major output of the int8 path (the same values). */
+int32_t fw_test_dec_self_attn(fw_model* m, const float* qkv, float* kcache, float* vcache, const uint8_t* kvidx,
+                              int32_t n_chunks, int32_t kmul, int32_t Kbeam, int32_t H, int32_t n_ctx, int32_t cache_ctx,
+                              int32_t pos_fixed, int32_t P, int32_t step, int32_t blk_n, int32_t frag, float* out);
+/* decoder cross-attention, one launch of launch_cross_attn (register cap: knob 7): q [B * kmul][d] (kmul <= 16),
+ * k / v [n_enc][T][d] plain row-major, laid out by the hook in the pool's fragment-major K / V^T (kvp = T rounded up
+ * to 32 keys; K's padded keys hold k_pad, V^T's zeros: the pool's contract).  Decode chunk c attends to encoder chunk
+ * slot_map[c / kv_div] (slot_map [ceil(B / kv_div)], values < n_enc: checked); chunks with done[c] != 0 (done [B] or
+ * NULL) are skipped.  out [B * kmul][d] IN / OUT: the device output starts as the caller's values. */
+int32_t fw_test_dec_cross_attn(fw_model* m, const float* q, const float* k, const float* v, int32_t n_enc, int32_t T,
+                               int32_t H, int32_t B, int32_t kmul, int32_t kv_div, const int32_t* slot_map,
+                               const int32_t* done, int32_t frag, float k_pad, float* out);
+/* the cross-attention probabilities of align (launch_cross_probs): q [B * blk][d] (blk = max(blk_n, 1) <= 16: row
+ * b * blk + j is token tok_idx + j of chunk b), k [B][T][d] (laid out as the pool's K), heads [n_sel] (< H) ->
+ * probs [B][n_sel][n_tok][T] float32 IN / OUT: only token slots tok_idx .. tok_idx + blk - 1 are written. */
+int32_t fw_test_dec_cross_probs(fw_model* m, const float* q, const float* k, int32_t B, int32_t T, int32_t H,
+                                const int32_t* heads, int32_t n_sel, int32_t n_tok, int32_t tok_idx, int32_t blk_n,
+                                float* probs);
+/* fp32 softmax picks of a decode step on float32 logits [rows * row_mul][V] (row b reads logits row b * row_mul):
+ * nospeech = 1: dec_nospeech_kernel, out[b] = softmax(row)[target[0]] (target[0] < V: checked); 0:
+ * dec_token_prob_kernel, out[b] = softmax(row)[target[b]], 0 for a target outside [0, V). */
+int32_t fw_test_dec_softmax_pick(fw_model* m, const float* logits, int32_t rows, int32_t V, int32_t row_mul,
+                                 const int32_t* target, int32_t nospeech, float* out);
 /* measurement hook (profiles/attn_bench.py): mean milliseconds of one launch of the encoder self-attention kernel for
  * B chunks x H heads x T positions on device-resident pseudo-random operands; variant = the workgroup mapping
  * (0: XCD-aware, the product's; 1: query tile fastest over all XCDs, round 3's) */

@@ -11,6 +11,13 @@ independent derivation of the same outputs (tests/test_oracle_silero_graph.py co
 speech fixture and on noise, and pins a committed golden vector made by tests/golden/make_silero_graph_golden.py).
 It is NOT onnxruntime: the pin is "the asset's graph under the operator specification", stated as such in DESIGN.md.
 
+Every node is evaluated with torch's oneDNN (mkldnn) backend switched off, on ATen's plain float32 kernels: oneDNN
+picks its convolution and RNN implementations per CPU and per batch size (torch sends a 1-D convolution of one window to
+ATen, of several windows to oneDNN), and an implementation that computes a float32 convolution at reduced internal
+precision moves the speech probabilities by 1e-2 (a bfloat16 convolution: 8.7e-3 on the reference's speech fixture,
+against 5e-7 on ATen's kernels) — for batches of windows only.  The executor is a reference: its float32 arithmetic
+must not depend on the CPU it runs on.
+
 Operators (the 13 the asset uses; anything else raises): Pad (reflect / constant / edge), Unsqueeze, Squeeze, Reshape,
 Transpose, Slice, Conv (1-D), Pow, Add, Sqrt, Relu, Sigmoid, LSTM (forward, one direction, default activations).
 Only tests/ import this module.
@@ -111,6 +118,16 @@ def run(nodes: List[dict], inits: Dict[str, np.ndarray], feeds: Dict[str, np.nda
             raise KeyError(f"tensor '{name}' is read before it is produced")
         return env[name]
 
+    was = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False                  # plain float32 ATen kernels (module docstring)
+    try:
+        _run_nodes(nodes, env, get)
+    finally:
+        torch.backends.mkldnn.enabled = was
+    return [env[n] for n in outputs]
+
+
+def _run_nodes(nodes, env, get):
     for nd in nodes:
         op, a = nd["op"], nd["attrs"]
         i = [get(n) for n in nd["inputs"]]
@@ -156,4 +173,3 @@ def run(nodes: List[dict], inits: Dict[str, np.ndarray], feeds: Dict[str, np.nda
         for name, val in zip(nd["outputs"], out):
             if name:
                 env[name] = val
-    return [env[n] for n in outputs]
