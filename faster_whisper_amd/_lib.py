@@ -79,6 +79,7 @@ SYMBOLS = [
     "fw_dev_alloc", "fw_dev_free", "fw_dev_upload",
     "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules",
     "fw_test_dec_self_attn", "fw_test_dec_cross_attn", "fw_test_dec_cross_probs", "fw_test_dec_softmax_pick", "fw_bench_gemm", "fw_bench_dec_linear", "fw_bench_attention",
+    "fw_bench_gemm_epi", "fw_bench_dec_linear_epi",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_flac_info", "fw_flac_decode",
 ]
@@ -173,6 +174,9 @@ def load():
     lib.fw_bench_attention.argtypes = [vp, i32, i32, i32, i32, i32, f32p]
     lib.fw_bench_gemm.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, f32p]
     lib.fw_bench_dec_linear.argtypes = [vp, i32, i32, i32, i32, i32, i32, f32p]
+    if hasattr(lib, "fw_bench_gemm_epi"):       # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_bench_gemm_epi.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p]
+        lib.fw_bench_dec_linear_epi.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p]
     lib.fw_test_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     lib.fw_test_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

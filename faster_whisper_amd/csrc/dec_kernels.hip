@@ -60,6 +60,8 @@ __global__ void dec_embed_kernel(const int* __restrict__ tok, const half_t* __re
 //   LNF:  y = rstd * (v - mu * s1[n]) + cf[n]     (LayerNorm folded into the weights: s1 = rowsum(W o g), cf = W b + bias)
 //   else: y = v + bias[n]
 //   then  act == 1: exact-erf GELU;   then + residual;   ONE rounding to fp16
+// The column constants (s1 / cf of the lane's four columns, or their bias) and the residual arrive as VALUES: the
+// kernels request them ahead of their epilogues, together, so that no load is waited for on its own (dec_col_consts).
 // ------------------------------------------------------------------------------------
 static __device__ __forceinline__ void dec_ln_stats(float sa, float sb, int K, float& mu, float& rstd) {
 #pragma clang fp contract(off)
@@ -69,19 +71,27 @@ static __device__ __forceinline__ void dec_ln_stats(float sa, float sb, int K, f
   const float var = ex2 - mu * mu;
   rstd = rsqrtf(fmaxf(var, 0.f) + 1e-5f);
 }
+// the column constants of columns n .. n + 3 (n a multiple of 4, inside the matrix): LNF s1 -> a4, cf -> c4; else bias -> b4
+struct DecColConsts { floatx4 a4, c4; half4_t b4; };
 template <bool LNF>
-static __device__ __forceinline__ half4_t dec_epilogue4(const floatx4 v, float mu, float rstd,
-                                                        const float* __restrict__ s1, const float* __restrict__ cf,
-                                                        const half_t* __restrict__ bias, bool has_res, half4_t r4, int n, int act) {
-#pragma clang fp contract(off)
-  floatx4 a4 = {0.f, 0.f, 0.f, 0.f}, c4 = {0.f, 0.f, 0.f, 0.f};
-  half4_t b4 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+static __device__ __forceinline__ DecColConsts dec_col_consts(const float* __restrict__ s1, const float* __restrict__ cf,
+                                                              const half_t* __restrict__ bias, int n) {
+  DecColConsts k;
+  k.a4 = floatx4{0.f, 0.f, 0.f, 0.f}; k.c4 = k.a4;
+  k.b4 = half4_t{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
   if (LNF) {
-    a4 = *reinterpret_cast<const floatx4*>(s1 + n);
-    c4 = *reinterpret_cast<const floatx4*>(cf + n);
+    k.a4 = *reinterpret_cast<const floatx4*>(s1 + n);
+    k.c4 = *reinterpret_cast<const floatx4*>(cf + n);
   } else if (bias) {
-    b4 = *reinterpret_cast<const half4_t*>(bias + n);
+    k.b4 = *reinterpret_cast<const half4_t*>(bias + n);
   }
+  return k;
+}
+template <bool LNF>
+static __device__ __forceinline__ half4_t dec_epilogue4(const floatx4 v, float mu, float rstd, const floatx4 a4,
+                                                        const floatx4 c4, const half4_t b4, bool bias, bool has_res,
+                                                        half4_t r4, int act) {
+#pragma clang fp contract(off)
   half4_t o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -180,18 +190,28 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_frag_kernel(
   }
   // the residual values of the tiles THIS wave finishes in the epilogue, requested now: behind the barrier the load was
   // one more dependent round trip of a launch that is nothing but round trips (solo runs)
+  // (likewise the column constants — s1 / cf or the bias — of those tiles: the same round trip, one launch in 224 of a step.
+  //  The LayerNorm-folded forms with several tiles hold 126 registers through the K loop: 8 more for s1 / cf cost the fourth wave
+  //  per SIMD — measured, cross-q at 800 rows 11.2 -> 11.9 us — so they request the two behind the K loop instead, where the
+  //  fragment registers are free: still ahead of the reduction's LDS writes and its barrier, and one wait for the pair.)
+  constexpr bool CONSTS_EARLY = !(LNF && RT * NT > 1);
   half4_t resv[(RT * NT + WAVES - 1) / WAVES];
+  DecColConsts colk[(RT * NT + WAVES - 1) / WAVES];
 #pragma unroll
-  for (int q = 0; q < (RT * NT + WAVES - 1) / WAVES; ++q) resv[q] = half4_t{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
-  if (res) {
+  for (int q = 0; q < (RT * NT + WAVES - 1) / WAVES; ++q) {
+    resv[q] = half4_t{(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+    colk[q] = DecColConsts{floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}, resv[q]};
+  }
 #pragma unroll
-    for (int a = 0; a < RT; ++a) {
+  for (int a = 0; a < RT; ++a) {
 #pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        if ((a * NT + b) % WAVES != wave) continue;
-        const int row = (rt0 + a) * 16 + i, n = (ct0 + b) * 16 + 4 * g;
-        if (row < R && n < N) resv[(a * NT + b) / WAVES] = *reinterpret_cast<const half4_t*>(res + (size_t)row * ldr + n);
-      }
+    for (int b = 0; b < NT; ++b) {
+      if ((a * NT + b) % WAVES != wave) continue;
+      int row = (rt0 + a) * 16 + i, n = (ct0 + b) * 16 + 4 * g;
+      if (row > R - 1) row = R - 1;     // clamped rows / columns are never stored
+      if (n > N - 4) n = N - 4;
+      if (CONSTS_EARLY) colk[(a * NT + b) / WAVES] = dec_col_consts<LNF>(s1, cf, bias, n);
+      if (res) resv[(a * NT + b) / WAVES] = *reinterpret_cast<const half4_t*>(res + (size_t)row * ldr + n);
     }
   }
   if (nks > 0) {
@@ -241,6 +261,18 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_frag_kernel(
       }
     }
   }
+  if (!CONSTS_EARLY) {
+#pragma unroll
+    for (int a = 0; a < RT; ++a) {
+#pragma unroll
+      for (int b = 0; b < NT; ++b) {
+        if ((a * NT + b) % WAVES != wave) continue;
+        int n = (ct0 + b) * 16 + 4 * g;
+        if (n > N - 4) n = N - 4;       // clamped columns are never stored
+        colk[(a * NT + b) / WAVES] = dec_col_consts<LNF>(s1, cf, bias, n);
+      }
+    }
+  }
 #pragma unroll
   for (int a = 0; a < RT; ++a) {
     if (LNF) {   // row i's statistics: the 4 k-octet lanes of the row, then the waves
@@ -279,7 +311,8 @@ __global__ __launch_bounds__(WAVES * 64) void dec_gemm_frag_kernel(
       if (n >= N) continue;
       const floatx4 v4 = {v[0], v[1], v[2], v[3]};
       const half4_t r4 = resv[(a * NT + b) / WAVES];
-      const half4_t o = dec_epilogue4<LNF>(v4, mu, rstd, s1, cf, bias, res != nullptr, r4, n, act);
+      const DecColConsts& ck = colk[(a * NT + b) / WAVES];
+      const half4_t o = dec_epilogue4<LNF>(v4, mu, rstd, ck.a4, ck.c4, ck.b4, bias != nullptr, res != nullptr, r4, act);
       if (out) *reinterpret_cast<half4_t*>(out + (size_t)row * ldo + n) = o;
       if (out_frag) *reinterpret_cast<half4_t*>(out_frag + frag_off(row, n, N >> 5)) = o;
     }
@@ -512,6 +545,43 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void dec_gemm_big_kernel(
   }
   // tail: nothing left to issue; the queue is drained once
   wait_vmcnt<0>();
+  // The epilogue's operands are requested HERE, together — the column constants of the wave's FB column tiles (they depend
+  // on the column tile only: FB loads, not one per (row tile, column tile)) and the residual patch in whole row segments,
+  // clamped addresses instead of branches around the loads — so that their round trip runs under the remaining ring
+  // stages and ONE wait in front of the staging writes covers them (behind the last MFMA they were 12-24 dependent
+  // `load; s_waitcnt vmcnt(0)` round trips per wave).  The queue is empty from here on: no counted wait is disturbed.
+  // A residual linear of the decoder runs in place (res == out): this wave reads exactly the patch that it alone writes
+  // later, and every load of the patch is consumed before the patch's first store.
+  const int row0 = (rt0 + wm * 4) * 16;                    // first row / column of the wave's patch
+  const int col0 = (ct0 + wn * FB) * 16;
+  constexpr int CPR = FB * 2;                              // 16-byte chunks per patch row
+  constexpr int RPI = 64 / CPR;                            // patch rows one wave instruction covers
+  const int cr = lane / CPR, cc = lane % CPR;              // row-segment pass: this lane's row within the group, chunk
+  // (The LayerNorm-folded 256 x 128 form holds 207 registers through the tail: with all 8 residual segments on top it
+  //  spills 17.  That form requests RES_EARLY of them here and the rest behind the tail, where the stage's fragment
+  //  registers are free — still one group, under the last barrier and the exchange of the LayerNorm sums.)
+  constexpr int NSEG = 64 / RPI;                           // residual row segments per lane
+  constexpr int RES_EARLY = (LNF && NW == 8 && FB == 4) ? 2 : NSEG;
+  DecColConsts colk[FB];
+  intx4 resv[NSEG];
+  auto load_res = [&](int j0, int j1) {
+    if (!res) return;
+#pragma unroll
+    for (int j = 0; j < NSEG; ++j) {
+      if (j < j0 || j >= j1) continue;
+      int row = row0 + j * RPI + cr, n = col0 + cc * 8;
+      if (row > R - 1) row = R - 1;                        // clamped rows / columns are never stored
+      if (n > N - 8) n = N - 8;
+      resv[j] = *reinterpret_cast<const intx4*>(res + (size_t)row * ldr + n);
+    }
+  };
+#pragma unroll
+  for (int b = 0; b < FB; ++b) {
+    int n = col0 + b * 16 + 4 * g;                         // this lane: D[n + e][row], e = 0..3
+    if (n > N - 4) n = N - 4;                              // clamped columns are never stored
+    colk[b] = dec_col_consts<LNF>(s1, cf, bias, n);
+  }
+  load_res(0, RES_EARLY);
 #pragma unroll 1
   for (int c = n_steady; c < nch; ++c) {
     DGB_BARRIER();
@@ -519,6 +589,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void dec_gemm_big_kernel(
     if (--to_slice == 0) { to_slice = ch_per_slice; slice_end(); }
     slot = (slot + 1 == NST) ? 0 : slot + 1;
   }
+  load_res(RES_EARLY, NSEG);
   DGB_BARRIER();     // every wave is done with the ring: it becomes the epilogue's staging area
 
   if (LNF) {
@@ -543,19 +614,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void dec_gemm_big_kernel(
   }
   // ---------------------------------- epilogue ----------------------------------
   char* ep = dgb_smem + wave * (64 * DGB_EP_STRIDE);       // this wave's 64-row x (16 FB)-column patch, fp16
-  const int row0 = (rt0 + wm * 4) * 16;                    // first row / column of the wave's patch
-  const int col0 = (ct0 + wn * FB) * 16;
-  constexpr int CPR = FB * 2;                              // 16-byte chunks per patch row
-  constexpr int RPI = 64 / CPR;                            // patch rows one wave instruction covers
-  const int cr = lane / CPR, cc = lane % CPR;              // row-segment pass: this lane's row within the group, chunk
-  if (res) {   // residual patch -> LDS in whole row segments (a wave's LDS operations execute in order)
+  if (res) {   // residual patch (requested before the ring's tail) -> LDS in whole row segments (a wave's LDS operations execute in order)
 #pragma unroll
     for (int j = 0; j < 64 / RPI; ++j) {
       const int r = j * RPI + cr;
-      const int row = row0 + r, n = col0 + cc * 8;
-      intx4 v = {0, 0, 0, 0};
-      if (row < R && n < N) v = *reinterpret_cast<const intx4*>(res + (size_t)row * ldr + n);
-      *reinterpret_cast<intx4*>(ep + r * DGB_EP_STRIDE + cc * 16) = v;
+      *reinterpret_cast<intx4*>(ep + r * DGB_EP_STRIDE + cc * 16) = resv[j];
     }
   }
 #pragma unroll
@@ -564,12 +627,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void dec_gemm_big_kernel(
     if (LNF) dec_ln_stats(sa[a], sb[a], K, mu, rstd);
 #pragma unroll
     for (int b = 0; b < FB; ++b) {
-      int n = col0 + b * 16 + 4 * g;                       // this lane: D[n + e][row], e = 0..3
-      if (n > N - 4) n = N - 4;                            // clamped columns are never stored
       char* cell = ep + (a * 16 + i) * DGB_EP_STRIDE + (b * 16 + 4 * g) * 2;
       half4_t r4 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
       if (res) r4 = *reinterpret_cast<const half4_t*>(cell);
-      const half4_t o = dec_epilogue4<LNF>(tot[a][b], mu, rstd, s1, cf, bias, res != nullptr, r4, n, act);
+      const half4_t o = dec_epilogue4<LNF>(tot[a][b], mu, rstd, colk[b].a4, colk[b].c4, colk[b].b4, bias != nullptr,
+                                           res != nullptr, r4, act);
       *reinterpret_cast<half4_t*>(cell) = o;
     }
   }
@@ -728,6 +790,7 @@ __global__ __launch_bounds__(WM * WN * 64) void dec_gemm_wave_kernel(
   __shared__ float xst[SPLIT ? RT : 1][16][2];
   if (rt0 >= n_rt) return;                    // (the whole workgroup: WM = 1 when SPLIT)
   if (!SPLIT && ct0 >= n_ct) return;          // whole waves leave: there is no barrier in the un-split kernel
+  if (cgrp * WN * NT >= n_ct) return;         // a column group that is pure padding (the grid is padded to groups of 8): the whole workgroup
   const int KS = K / (I8 ? 64 : 32);
   const intx4* wp[NT];
   const intx4* xp[RT];
@@ -810,6 +873,23 @@ __global__ __launch_bounds__(WM * WN * 64) void dec_gemm_wave_kernel(
       }
     }
   };
+  // the column constants of this wave's NT tiles (s1 / cf, or the bias, or the int8 column scales), requested BEFORE the
+  // K loop: behind it every one of them was a dependent round trip of its own.  Element by element with the index
+  // clamped: N (51 866) is no multiple of 4, and a clamped column is computed but never stored.
+  float ks1[NT][4], kcf[NT][4], kws[NT][4];
+  half_t kb[NT][4];
+#pragma unroll
+  for (int b = 0; b < NT; ++b) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int n = (ct0 + b) * 16 + 4 * g + e;
+      const int ne = n < N ? n : N - 1;
+      ks1[b][e] = kcf[b][e] = 0.f; kws[b][e] = 1.f; kb[b][e] = (half_t)0.f;
+      if (I8) kws[b][e] = w_scale[ne];
+      if (LNF) { ks1[b][e] = s1[ne]; kcf[b][e] = cf[ne]; }
+      else if (bias) kb[b][e] = bias[ne];
+    }
+  }
   Set fa, fb;
   load(fa, 0);
   for (int ks0 = 0; ks0 < KS; ks0 += 2 * CH) {
@@ -855,10 +935,9 @@ __global__ __launch_bounds__(WM * WN * 64) void dec_gemm_wave_kernel(
       float t4[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int ne = n + e < N ? n + e : N - 1;   // (clamped: computed, never stored)
-        float tv = I8 ? (float)acci[a][b][e] * sx * w_scale[ne] : accf[a][b][e];
-        if (LNF) tv = rstd * (tv - mu * s1[ne]) + cf[ne];
-        else if (bias) tv += (float)bias[ne];
+        float tv = I8 ? (float)acci[a][b][e] * sx * kws[b][e] : accf[a][b][e];
+        if (LNF) tv = rstd * (tv - mu * ks1[b][e]) + kcf[b][e];
+        else if (bias) tv += (float)kb[b][e];
         t4[e] = tv;
       }
       if (F32 && pair_ok) {

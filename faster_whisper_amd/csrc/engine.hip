@@ -2097,6 +2097,161 @@ int32_t fw_bench_gemm(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t bat
   return FW_OK;
 }
 
+// pseudo-random fp16 fill in [-1, 1) of a device buffer of n halves, staged through `h` (constant fills clock the chip up)
+static int bench_fill(half_t* dst, size_t n, std::vector<uint16_t>& h, uint32_t seed) {
+  if (h.size() < n) h.resize(n);
+  for (size_t i = 0; i < n; ++i) { seed = seed * 1664525u + 1013904223u; h[i] = f32_to_f16_bits(((int)(seed >> 16) % 2001 - 1000) * 1e-3f); }
+  FW_HIP(hipMemcpy(dst, h.data(), n * 2, hipMemcpyHostToDevice));
+  return FW_OK;
+}
+
+// measurement hook (profiles/gemm_bench.py --epilogue): fw_bench_gemm with the epilogue the PRODUCT runs for the shape —
+// bias, GELU, residual as run_encoder passes them, or (n_layers > 1) the layered head-major cross-attention K / V^T
+// projection of ensure_cross_kv.  The residual is read from a set of buffers larger than L2 + MALL, rotated launch by
+// launch (res = 1), or from one [M][N] block shared by the chunks (res = 2: conv2's positional embedding).
+int32_t fw_bench_gemm_epi(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t lda_in, int32_t trans,
+                          int32_t bias, int32_t act, int32_t res, int32_t n_layers, int32_t iters, float* ms_out) {
+  FW_CHECK_ARG(fm && ms_out && M > 0 && N > 0 && K > 0 && batch > 0 && iters > 0 && n_layers >= 1, "bad argument");
+  FW_CHECK_ARG(res >= 0 && res <= 2 && !(res && (trans || n_layers > 1)), "residual: row-major single-layer output only");
+  Model* m = &fm->impl;
+  FW_CHECK_ARG(m->compute_type != FW_COMPUTE_INT8_FLOAT16, "float16 models only");
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  const int64_t lda = lda_in > 0 ? lda_in : K;
+  const bool layered = n_layers > 1;
+  const int64_t kvp = (M + 31) / 32 * 32;                  // keys of a head, padded to whole 32-key groups (the pool's kvp)
+  const int64_t ldct = layered ? kvp : (M + 63) / 64 * 64;
+  const int64_t c_bs = layered ? (int64_t)N * kvp : (trans ? (int64_t)N * ldct : (int64_t)M * N);
+  const int64_t c_ls = c_bs * batch;
+  const size_t na = (size_t)batch * ((size_t)M * lda + K), nw = (size_t)N * K * n_layers, nc = (size_t)c_ls * n_layers;
+  const size_t nr1 = res == 1 ? (size_t)batch * M * N : (size_t)M * N;
+  const int copies = res == 1 ? (int)std::max<size_t>(2, ((size_t)640 << 20) / (nr1 * 2)) : 1;
+  half_t *dA = nullptr, *dW = nullptr, *dC = nullptr, *dB = nullptr, *dR = nullptr;
+  int rc;
+  auto cleanup = [&]() { for (void* p : {(void*)dA, (void*)dW, (void*)dC, (void*)dB, (void*)dR}) if (p) (void)hipFree(p); };
+  if ((rc = dev_alloc_t(&dA, na)) || (rc = dev_alloc_t(&dW, nw)) || (rc = dev_alloc_t(&dC, nc)) ||
+      (rc = dev_alloc_t(&dB, (size_t)N * n_layers)) || (res && (rc = dev_alloc_t(&dR, nr1 * copies)))) {
+    cleanup();
+    return rc;
+  }
+  {
+    std::vector<uint16_t> h;
+    if ((rc = bench_fill(dA, na, h, 12345u)) || (rc = bench_fill(dW, nw, h, 12345u)) ||
+        (rc = bench_fill(dB, (size_t)N * n_layers, h, 777u))) { cleanup(); return rc; }
+    if (res) {
+      if ((rc = bench_fill(dR, nr1, h, 4242u))) { cleanup(); return rc; }
+      for (int c = 1; c < copies; ++c) FW_HIP(hipMemcpy(dR + (size_t)c * nr1, dR, nr1 * 2, hipMemcpyDeviceToDevice));
+    }
+    FW_HIP(hipMemset(dC, 0, nc * 2));
+  }
+  fwk::GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = dA; p.lda = lda; p.a_bstride = (int64_t)M * lda;
+  p.W = dW; p.ldw = K;
+  p.bias = bias ? dB : nullptr;
+  p.C = dC; p.ldc = layered ? (trans ? kvp : N) : (trans ? ldct : N); p.c_bstride = c_bs;
+  p.M = M; p.N = N; p.K = K;
+  p.act = act;
+  if (layered) {
+    p.head_rows = (int)kvp;
+    p.n_layers = n_layers; p.w_lstride = (int64_t)N * K; p.bias_lstride = N; p.c_lstride = c_ls;
+  }
+  p.ldr = N; p.r_bstride = res == 1 ? (int64_t)M * N : 0;
+  hipEvent_t e0, e1;
+  FW_HIP(hipEventCreate(&e0));
+  FW_HIP(hipEventCreate(&e1));
+  p.res = dR;
+  int lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);   // warm-up
+  FW_HIP(hipEventRecord(e0, m->stream));
+  for (int i = 0; i < iters && lr == 0; ++i) {
+    if (res) p.res = dR + (size_t)(i % copies) * nr1;
+    lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);
+  }
+  FW_HIP(hipEventRecord(e1, m->stream));
+  hipError_t he = hipEventSynchronize(e1);
+  float ms = 0.f;
+  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  cleanup();
+  if (lr != 0 || he != hipSuccess) {
+    set_error("gemm epilogue bench failed: %s", lr ? "unsupported shape" : hipGetErrorString(he));
+    return FW_ERUNTIME;
+  }
+  *ms_out = ms / (float)iters;
+  return FW_OK;
+}
+
+// measurement hook (profiles/dec_linear_bench.py --epilogue): fw_bench_dec_linear with the epilogue a decode step runs —
+// act, and with res = 1 the residual added IN PLACE (res == out, as run_step passes g->x), outs bit 0 / 1: the row-major
+// / the fragment-major copy written.  Weights AND the in-place residual / output rows rotate over sets larger than
+// L2 + MALL.  variant 0: what a decode step launches for this row count; 5: the register-streaming kernel; 10 + cfg:
+// the GEMM-shaped kernel of merged runs.
+int32_t fw_bench_dec_linear_epi(fw_model* fm, int32_t R, int32_t N, int32_t K, int32_t lnf, int32_t variant, int32_t act,
+                                int32_t res, int32_t outs, int32_t iters, float* us_out) {
+  FW_CHECK_ARG(fm && us_out && R > 0 && N > 0 && K > 0 && iters > 0, "bad argument");
+  FW_CHECK_ARG((outs & 3) != 0 && (!res || (outs & 1)), "needs an output; the residual is the row-major output in place");
+  FW_CHECK_ARG(variant == 0 || variant == 5 || (variant >= 10 && variant <= 12), "unknown variant %d", variant);
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  const size_t wn = (size_t)N * K;
+  const int copies = (int)std::max<size_t>(2, ((size_t)640 << 20) / (wn * 2));
+  const size_t rp = ((size_t)R + 15) / 16 * 16, on = rp * N;
+  const int ocopies = (int)std::max<size_t>(2, ((size_t)640 << 20) / (on * 2));
+  half_t *dW = nullptr, *dX = nullptr, *dO = nullptr, *dF = nullptr, *dB = nullptr;
+  float *dS = nullptr, *dC = nullptr;
+  int rc;
+  auto cleanup = [&]() { for (void* p : {(void*)dW, (void*)dX, (void*)dO, (void*)dF, (void*)dB, (void*)dS, (void*)dC}) if (p) (void)hipFree(p); };
+  if ((rc = dev_alloc_t(&dW, wn * copies)) || (rc = dev_alloc_t(&dX, rp * K)) || (rc = dev_alloc_t(&dO, on * ocopies)) ||
+      (rc = dev_alloc_t(&dF, on)) || (rc = dev_alloc_t(&dB, (size_t)N)) || (rc = dev_alloc_t(&dS, (size_t)N)) ||
+      (rc = dev_alloc_t(&dC, (size_t)N))) {
+    cleanup();
+    return rc;
+  }
+  {
+    std::vector<uint16_t> h;
+    if ((rc = bench_fill(dW, wn, h, 2463534242u)) || (rc = bench_fill(dX, rp * K, h, 2463534242u))) { cleanup(); return rc; }
+    for (int c = 1; c < copies; ++c) FW_HIP(hipMemcpy(dW + (size_t)c * wn, dW, wn * 2, hipMemcpyDeviceToDevice));
+  }
+  // (zero residual / bias / fold constants: an in-place residual that is re-read iters / ocopies times stays finite)
+  FW_HIP(hipMemset(dO, 0, on * ocopies * 2));
+  FW_HIP(hipMemset(dB, 0, (size_t)N * 2));
+  FW_HIP(hipMemset(dS, 0, (size_t)N * 4));
+  FW_HIP(hipMemset(dC, 0, (size_t)N * 4));
+  hipEvent_t e0, e1;
+  FW_HIP(hipEventCreate(&e0));
+  FW_HIP(hipEventCreate(&e1));
+  hipStream_t st = m->stream;
+  auto go = [&](int i) -> int {
+    const half_t* w = dW + (size_t)(i % copies) * wn;
+    half_t* o = dO + (size_t)(i % ocopies) * on;
+    half_t* op = (outs & 1) ? o : nullptr;
+    half_t* of = (outs & 2) ? dF : nullptr;
+    const half_t* r = res ? o : nullptr;
+    const half_t* b = lnf ? nullptr : dB;
+    const float *s1 = lnf ? dS : nullptr, *cf = lnf ? dC : nullptr;
+    if (variant >= 10) return fwd::launch_dec_gemm_big(st, variant - 10, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
+    if (variant == 5) return fwd::launch_dec_gemm_skinny(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
+    return fwd::launch_dec_gemm_frag(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
+  };
+  int lr = 0;
+  for (int i = 0; i < 4 && lr == 0; ++i) lr = go(i);
+  FW_HIP(hipEventRecord(e0, st));
+  for (int i = 0; i < iters && lr == 0; ++i) lr = go(i);
+  FW_HIP(hipEventRecord(e1, st));
+  hipError_t he = hipEventSynchronize(e1);
+  float ms = 0.f;
+  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  cleanup();
+  if (lr != 0) { set_error("fw_bench_dec_linear_epi: unsupported shape / variant"); return FW_EINVAL; }
+  if (he != hipSuccess) { set_error("fw_bench_dec_linear_epi: %s", hipGetErrorString(he)); return FW_ENODEV; }
+  *us_out = ms * 1000.f / (float)iters;
+  return FW_OK;
+}
+
 int32_t fw_test_layernorm(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
                           float* out) {
   FW_CHECK_ARG(fm && x && g && b && out, "null argument");

@@ -200,6 +200,48 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
 
+  // ---- epilogue operands, requested AHEAD of the epilogue: in the last K tile's last load segment, behind the wait that
+  // drains the DMA queue (ordinary loads must not be in flight while the counted vmcnt(8) protocol runs), so that their
+  // round trip runs under that phase's MFMAs.  A lane needs the same 8 bias half4 (2 with a transposed tile: one per column
+  // tile) for every (half, row tile) of its sub-tile: they are loaded once; and the 8 residual row segments of a half
+  // of the row-major epilogue are requested together — clamped addresses instead of branches around the loads, only the
+  // stores are predicated — so that ONE wait covers them.  Waited for one by one behind 184 `s_waitcnt vmcnt(0)` the
+  // loads were 48 dependent round trips per wave on a CU that this workgroup holds alone. ----
+  const int mw = m0 + wm * 128, nw = n0 + wn * 64;       // this wave's sub-tile
+  const bool rowmajor = !TRANS && p.head_rows == 0;
+  const half_t* const Rb = (rowmajor && p.res) ? p.res + (size_t)z * p.r_bstride : nullptr;
+  const int ep_rr = lane >> 3, ep_cc = (lane & 7) * 8;   // row-major store pass: 8 lanes per row segment, 8 columns each
+  const bool vec_ok = (p.ldc % 8 == 0) && (p.c_bstride % 8 == 0) && (!Rb || ((p.ldr % 8 == 0) && (p.r_bstride % 8 == 0)));
+  const half4_t hz4 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
+  half4_t bias4[2][4] = {{hz4, hz4, hz4, hz4}, {hz4, hz4, hz4, hz4}};   // !TRANS: columns nw + ni * 32 + 8 g + 4 hi + [0, 4)
+  half_t biasT[2] = {(half_t)0.f, (half_t)0.f};                         // TRANS: column nw + ni * 32 + l31
+  half8_t resv[8];                                                      // the residual row segments of one half
+  auto load_bias = [&]() {
+    if (!biasp) return;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      if (TRANS) {
+        int n = nw + ni * 32 + l31; if (n > p.N - 1) n = p.N - 1;       // clamped columns are never stored
+        biasT[ni] = biasp[n];
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          int n = nw + ni * 32 + 8 * g + 4 * hi; if (n > p.N - 4) n = p.N - 4;
+          bias4[ni][g] = *reinterpret_cast<const half4_t*>(biasp + n);
+        }
+      }
+    }
+  };
+  auto load_res = [&](int half) {
+    if (!Rb || !vec_ok || p.N < 8) return;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      int m = mw + half * 64 + j * 8 + ep_rr; if (m > p.M - 1) m = p.M - 1;   // clamped rows / columns are never stored
+      int n = nw + ep_cc; if (n + 8 > p.N) n = (p.N - 8) & ~7;
+      resv[j] = *reinterpret_cast<const half8_t*>(Rb + (size_t)m * p.ldr + n);
+    }
+  };
+
   // ---- prologue: tile 0 whole, tile 1's B0 / A0 (the issue order of the steady state) ----
   issue(2, 0); issue(0, 0); issue(3, 0); issue(1, 0);
   if (nk > 1) { issue(2, 1); issue(0, 1); }
@@ -250,6 +292,9 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
     GB_TL(12);
     if (n2) issue(0, kt + 2);
     seg_wait(n2);
+    // the last tile: the queue is drained, the epilogue's operands leave now (int8: the residual segments only in the
+    // epilogue itself — held across this phase's MFMAs they spill 29 registers of that instantiation)
+    if (!n1 && !n2) { load_bias(); if (!I8) load_res(0); }
     GB_TL(13);
     GB_BARRIER();
     GB_TL(14);
@@ -277,12 +322,10 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
     constexpr int EP_STRIDE = 272;                       // bytes per staged row: 64 floats + 16 (16-B aligned)
     char* ep = smem_raw + wave * (64 * EP_STRIDE);
     half_t* Cb = Cp + (size_t)z * p.c_bstride;
-    const half_t* Rb = p.res ? p.res + (size_t)z * p.r_bstride : nullptr;
-    const int mw = m0 + wm * 128, nw = n0 + wn * 64;     // this wave's sub-tile
-    const int rr = lane >> 3, cc = (lane & 7) * 8;       // store pass: 8 lanes per row segment, 8 columns each
-    const bool vec_ok = (p.ldc % 8 == 0) && (p.c_bstride % 8 == 0) && (!Rb || ((p.ldr % 8 == 0) && (p.r_bstride % 8 == 0)));
+    const int rr = ep_rr, cc = ep_cc;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
+      if (half == 1 || I8) load_res(half);               // (half 0's were requested in the last K tile)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -300,9 +343,8 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
             for (int e = 0; e < 4; ++e)
               v[e] = I8 ? (float)acci[mi][ni][g * 4 + e] * sam * p.w_scale[n + e] : accf[mi][ni][g * 4 + e];
             if (biasp) {
-              const half4_t bv = *reinterpret_cast<const half4_t*>(biasp + n);
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] += (float)bv[e];
+              for (int e = 0; e < 4; ++e) v[e] += (float)bias4[ni][g][e];
             }
             if (p.act == 1) {
 #pragma unroll
@@ -313,7 +355,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
         }
       // (a wave's LDS operations execute in order: its reads below see its writes above, and the next half's
       //  writes come after these reads)
-#pragma unroll 4
+#pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int r = j * 8 + rr;
         const int m = mw + half * 64 + r, n = nw + cc;
@@ -323,7 +365,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
         float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
         if (vec_ok && n + 8 <= p.N) {
           if (Rb) {
-            const half8_t rv = *reinterpret_cast<const half8_t*>(Rb + (size_t)m * p.ldr + n);
+            const half8_t rv = resv[j];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
           }
@@ -352,8 +394,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
     // as fp16 [key][dim] (K) or [dim][key] (V^T), and leaves as whole 1 KB runs, 16 B per lane.
     constexpr int FS = 144;                                  // bytes per staged row: 64 halves + 16
     char* ep = smem_raw + wave * (64 * FS);
-    half_t* Cb = Cp + (size_t)z * p.c_bstride;
-    const int mw = m0 + wm * 128, nw = n0 + wn * 64;         // this wave's keys / its head's 64 dims
+    half_t* Cb = Cp + (size_t)z * p.c_bstride;              // (mw / nw: this wave's keys / its head's 64 dims)
     if (nw < p.N) {
       half_t* Hb = Cb + (size_t)(nw >> 6) * p.head_rows * 64;
       const int g4 = lane >> 4, j = lane & 15;
@@ -376,7 +417,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                   float v = I8 ? (float)acci[mi][ni][g * 4 + e] * sam * p.w_scale[n + e] : accf[mi][ni][g * 4 + e];
-                  if (biasp) v += (float)biasp[n + e];
+                  if (biasp) v += (float)bias4[ni][g][e];
                   if (p.act == 1) v = gelu_erf(v);
                   o[e] = (half_t)v;
                 }
@@ -385,7 +426,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
             } else {
               const int c = ni * 32 + l31;                   // dim inside the head
               int n = nw + c; if (n > p.N - 1) n = p.N - 1;
-              const float bv = biasp ? (float)biasp[n] : 0.f;
+              const float bv = (float)biasT[ni];
               const float swn = I8 ? p.w_scale[n] : 1.f;
 #pragma unroll
               for (int g = 0; g < 4; ++g) {
@@ -445,12 +486,10 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
     constexpr int TS = 272;                                  // bytes per staged row: 128 halves + 16
     char* ep = smem_raw + wave * (64 * TS);
     half_t* Cb = Cp + (size_t)z * p.c_bstride;
-    const int mw = m0 + wm * 128, nw = n0 + wn * 64;
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
       const int c = ni * 32 + l31;                           // column of the sub-tile = row of the staged patch
-      int n = nw + c; if (n > p.N - 1) n = p.N - 1;          // clamped columns are never stored
-      const float bv = biasp ? (float)biasp[n] : 0.f;
+      const float bv = (float)biasT[ni];
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -492,7 +531,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
       for (int ni = 0; ni < 2; ++ni) {
         const int n = n0 + wn * 64 + ni * 32 + l31;
         if (n >= p.N) continue;
-        const float bv = biasp ? (float)biasp[n] : 0.f;
+        const float bv = (float)biasT[ni];
         const float swn = I8 ? p.w_scale[n] : 1.f;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {

@@ -45,6 +45,19 @@ int32_t fw_bench_gemm(fw_model* m, int32_t M, int32_t N, int32_t K, int32_t batc
  * mean microseconds per launch of a [R] x [N][K] linear (lnf = LayerNorm-folded form). */
 int32_t fw_bench_dec_linear(fw_model* m, int32_t R, int32_t N, int32_t K, int32_t lnf, int32_t variant, int32_t iters,
                             float* us_out);
+/* fw_bench_gemm with the epilogue the product runs for the shape (profiles/gemm_bench.py --epilogue; float16 models):
+ * bias != 0: a bias vector; act = 1: GELU; res = 1: a residual [batch][M][N] read from buffers larger than the caches,
+ * rotated launch by launch; res = 2: one [M][N] block shared by the chunks (conv2's positional embedding); lda: row
+ * stride of A in elements (0: K; conv2 reads overlapping rows, lda = 2 d, K = 3 d); n_layers > 1: the layered
+ * head-major cross-attention K (trans = 0) / V^T (trans = 1) projection, N = d_model per layer, no residual */
+int32_t fw_bench_gemm_epi(fw_model* m, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t lda, int32_t trans,
+                          int32_t bias, int32_t act, int32_t res, int32_t n_layers, int32_t iters, float* ms_out);
+/* fw_bench_dec_linear with the epilogue a decode step runs (profiles/dec_linear_bench.py --epilogue): act = 1: GELU;
+ * res = 1: the residual added in place (res == out, rows rotated over buffers larger than the caches); outs bit 0: the
+ * row-major copy is written, bit 1: the fragment-major copy.  variant 0: what a decode step launches for this row
+ * count, 5: the register-streaming kernel, 10 + cfg: the GEMM-shaped kernel of merged runs */
+int32_t fw_bench_dec_linear_epi(fw_model* m, int32_t R, int32_t N, int32_t K, int32_t lnf, int32_t variant, int32_t act,
+                                int32_t res, int32_t outs, int32_t iters, float* us_out);
 int32_t fw_test_layernorm(fw_model* m, const float* x, const float* g, const float* b,
                           int32_t rows, int32_t d, float* out);
 int32_t fw_test_attention(fw_model* m, const float* q, const float* k, const float* v,

@@ -19,6 +19,30 @@ SHAPES = [("qkv", 3840, 1280, 1), ("dxd", 1280, 1280, 0), ("ffn1", 5120, 1280, 1
 if os.environ.get("DLB_LNF") is not None:      # force the LayerNorm-folded form on / off for every shape (what the statistics cost)
     SHAPES = [(n, N, K, int(os.environ["DLB_LNF"])) for n, N, K, _ in SHAPES]
 
+# python profiles/dec_linear_bench.py --epilogue 80 800 1280: every linear of a layer with the epilogue a decode step runs
+# for it (fw_bench_dec_linear_epi), next to the bare launch; the kernel a step launches at that row count.
+# The linears of a decoder layer as run_step launches them: (name, N, K, lnf, act, res, outs: 1 row-major | 2 fragment-major)
+EPI_SHAPES = [("qkv", 3840, 1280, 1, 0, 0, 1), ("out", 1280, 1280, 0, 0, 1, 3), ("cross-q", 1280, 1280, 1, 0, 0, 1),
+              ("cross-out", 1280, 1280, 0, 0, 1, 3), ("ffn1", 5120, 1280, 1, 1, 0, 2), ("ffn2", 1280, 5120, 0, 0, 1, 3)]
+
+
+def epilogue_table(m, h, rows, reps=3, iters=400):
+    us = C.c_float()
+    for R in rows:
+        print(f"R = {R}   us per launch, min .. max of {reps} measurements (bare = no activation / residual, row-major output only)")
+        layer = {"bare": 0.0, "product": 0.0}
+        for name, N, K, lnf, act, res, outs in EPI_SHAPES:
+            t = {"bare": [], "product": []}
+            for _ in range(reps):
+                for key, (a_, r_, o_) in (("bare", (0, 0, 1)), ("product", (act, res, outs))):
+                    _lib.check(m._lib.fw_bench_dec_linear_epi(h, R, N, K, lnf, 0, a_, r_, o_, iters, C.byref(us)))
+                    t[key].append(us.value)
+            for key in t:
+                layer[key] += min(t[key])
+            print("  %-10s bare %7.2f .. %7.2f   product %7.2f .. %7.2f" %
+                  (name, min(t["bare"]), max(t["bare"]), min(t["product"]), max(t["product"])), flush=True)
+        print("  %-10s bare %7.2f              product %7.2f" % ("layer", layer["bare"], layer["product"]), flush=True)
+
 
 def main():
     cfg = get_config("micro")
@@ -26,6 +50,9 @@ def main():
                 max_batch_size=1, max_beam_size=1)
     h = m._replicas[0].handle
     us = C.c_float()
+    if "--epilogue" in sys.argv[1:]:
+        epilogue_table(m, h, [int(a) for a in sys.argv[1:] if a != "--epilogue"] or [80, 800, 1280])
+        return
     rows = [int(a) for a in sys.argv[1:]] or [80, 320, 640]
     for R in rows:
         print(f"R = {R}")
