@@ -82,6 +82,7 @@ SYMBOLS = [
     "fw_bench_gemm_epi", "fw_bench_dec_linear_epi",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_flac_info", "fw_flac_decode",
+    "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
 ]
 
 _lib = None
@@ -186,6 +187,11 @@ def load():
     if hasattr(lib, "fw_vad_forward_audio_dev"):
         lib.fw_vad_forward_audio_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
     lib.fw_vad_free.restype = None
+    if hasattr(lib, "fw_resample_dev"):           # (absent from an older build loaded through FWAMD_LIB)
+        f64 = C.c_double
+        lib.fw_resample_filter.argtypes = [i32, i32, i32, f64, vp, i64p, i32p, i32p]
+        lib.fw_resample_dev.argtypes = [i32, vp, i64, i32, i32, i32, f64, i32, vp, i64]
+        lib.fw_bench_resample.argtypes = [i32, vp, i64, i32, i32, i32, f64, i32, i32, f32p]
     _lib = lib
     return lib
 

@@ -9,14 +9,15 @@ the reference decodes with PyAV (bundled FFmpeg), resamples to signed 16-bit at 
     bit-exactly);
   * other containers (MP3, AAC, Ogg ...) are delegated to PyAV when it is importable, and fail loudly otherwise;
   * rate conversion is a Kaiser-windowed sinc polyphase filter in numpy (libswresample is not available, so the
-    resampled waveform is not bit-identical to the reference's — the s16 quantisation step and the interface are).
+    resampled waveform is not bit-identical to the reference's — the s16 quantisation step and the interface are);
+    `resample_device` / `decode_audio(..., device_index=)` run the same filter on the GPU (csrc/resample.hip), opt-in.
 `pad_or_trim` (audio.py:111-123) lives in transcribe.py.
 """
 import io
 import os
 import struct
 from math import gcd
-from typing import BinaryIO, Tuple, Union
+from typing import BinaryIO, Optional, Tuple, Union
 
 import numpy as np
 
@@ -122,6 +123,11 @@ def resample(x: np.ndarray, rate_in: int, rate_out: int, taps_per_phase: int = 3
     x = np.asarray(x, dtype=np.float32)
     if rate_in == rate_out or x.size == 0:
         return x
+    return _resample_f64(x, rate_in, rate_out, taps_per_phase, beta).astype(np.float32)
+
+
+def _resample_f64(x: np.ndarray, rate_in: int, rate_out: int, taps_per_phase: int, beta: float) -> np.ndarray:
+    """the fp64 sums of `resample`, before their rounding to float32 (x: non-empty float32, rate_in != rate_out)"""
     g = gcd(rate_in, rate_out)
     up, down = rate_out // g, rate_in // g
     big = max(up, down)
@@ -148,7 +154,29 @@ def resample(x: np.ndarray, rate_in: int, rate_out: int, taps_per_phase: int = 3
             win = np.lib.stride_tricks.sliding_window_view(xp, coef.size)
             valid = np.minimum(starts, win.shape[0] - 1)
             out[r] = win[valid] @ coef
-    return out.astype(np.float32)
+    return out
+
+
+def resample_device(x: np.ndarray, rate_in: int, rate_out: int, device_index: int = 0, taps_per_phase: int = 32,
+                    beta: float = 9.0, quantize_s16: bool = False) -> np.ndarray:
+    """`resample` on HIP device `device_index` (fw_resample_dev, csrc/resample.hip): the same filter and the same fp64
+    accumulation, host arrays in and out.  quantize_s16 fuses `_to_s16_float` into the kernel.  No host fallback: without
+    that device the call raises RuntimeError."""
+    import ctypes as C
+    from . import _lib
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1:
+        raise ValueError(f"resample_device takes a 1-D signal, got shape {x.shape}")
+    if (rate_in == rate_out and not quantize_s16) or x.size == 0:
+        return x
+    lib = _lib.load()
+    n_h, up, down = C.c_int64(), C.c_int32(), C.c_int32()
+    _lib.check(lib.fw_resample_filter(rate_in, rate_out, taps_per_phase, beta, None, C.byref(n_h), C.byref(up),
+                                      C.byref(down)))
+    out = np.empty(-(-x.size * up.value // down.value), dtype=np.float32)
+    _lib.check(lib.fw_resample_dev(device_index, _lib.ptr(x), x.size, rate_in, rate_out, taps_per_phase, beta,
+                                   int(bool(quantize_s16)), _lib.ptr(out), out.size))
+    return out
 
 
 def _to_s16_float(x: np.ndarray) -> np.ndarray:
@@ -173,8 +201,11 @@ def _decode_with_pyav(input_file, sampling_rate: int, split_stereo: bool):
     return (audio[0::2], audio[1::2]) if split_stereo else audio
 
 
-def decode_audio(input_file: Union[str, BinaryIO], sampling_rate: int = 16000, split_stereo: bool = False):
-    """-> float32 waveform at `sampling_rate` (mono), or (left, right) when split_stereo"""
+def decode_audio(input_file: Union[str, BinaryIO], sampling_rate: int = 16000, split_stereo: bool = False, *,
+                 device_index: Optional[int] = None):
+    """-> float32 waveform at `sampling_rate` (mono), or (left, right) when split_stereo.
+    device_index (not in the reference): the natively decoded formats (WAVE, FLAC) are rate-converted and quantised on
+    that HIP device (`resample_device`) instead of in numpy; the samples are the same."""
     if isinstance(input_file, (str, bytes)) and not isinstance(input_file, bytes):
         with open(input_file, "rb") as f:
             data = f.read()
@@ -189,6 +220,14 @@ def decode_audio(input_file: Union[str, BinaryIO], sampling_rate: int = 16000, s
         native = _read_flac(data)
     if native is not None:
         x, rate = native
+        if device_index is not None:
+            def convert(sig):
+                return resample_device(sig, rate, sampling_rate, device_index, quantize_s16=True)
+            if split_stereo:
+                if x.shape[1] < 2:
+                    x = np.repeat(x[:, :1], 2, axis=1)
+                return convert(x[:, 0]), convert(x[:, 1])
+            return convert(x.mean(axis=1) if x.shape[1] > 1 else x[:, 0])
         if split_stereo:
             if x.shape[1] < 2:
                 x = np.repeat(x[:, :1], 2, axis=1)

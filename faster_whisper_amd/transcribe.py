@@ -38,6 +38,16 @@ from .config import WhisperConfig
 _LOG = logging.getLogger("faster_whisper")
 
 
+def _resample_device_index(backend) -> Optional[int]:
+    """decode_audio's device_index for a transcribe(path) call: with FWAMD_RESAMPLE_DEVICE=1 in the environment file audio
+    is rate-converted on the model's (first) GPU (audio.resample_device: the same samples as the numpy filter); unset, on
+    the host"""
+    if os.environ.get("FWAMD_RESAMPLE_DEVICE") != "1":
+        return None
+    idx = backend.device_index
+    return idx if isinstance(idx, int) else idx[0]
+
+
 @dataclass
 class Word:
     start: float
@@ -367,7 +377,7 @@ class WhisperModel:
             multilingual = False
         if not isinstance(audio, np.ndarray):
             from .audio import decode_audio   # path / file object: WAVE and FLAC natively, other containers through PyAV
-            audio = decode_audio(audio, sampling_rate=sr)
+            audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(self.model))
         duration = audio.shape[0] / sr
         duration_after_vad = duration
         speech_chunks = None
@@ -863,7 +873,7 @@ class BatchedInferencePipeline:
             multilingual = False
         if not isinstance(audio, np.ndarray):
             from .audio import decode_audio   # path / file object: WAVE and FLAC natively, other containers through PyAV
-            audio = decode_audio(audio, sampling_rate=sr)
+            audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(m.model))
         audio = np.asarray(audio, dtype=np.float32)
         duration = audio.shape[0] / sr
         chunk_length = chunk_length or m.feature_extractor.chunk_length

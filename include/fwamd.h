@@ -50,7 +50,8 @@ extern "C" {
 
 /* 2: fw_model_set_encoder_cus / fw_model_encoder_cus removed, fw_model_set_merge_wait, fw_model_set_decode_lanes and
  *    fw_model_run_capacity added, test / bench hooks moved to fwamd_test.h; the cross-attention cache of a decode group
- *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run) */
+ *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run);
+ *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed) */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -340,6 +341,23 @@ int32_t fw_flac_info(const uint8_t* data, int64_t n_bytes, int32_t* sample_rate,
                      int32_t* bits_per_sample, int64_t* total_samples);
 int32_t fw_flac_decode(const uint8_t* data, int64_t n_bytes, int32_t* out, int64_t capacity_samples,
                        int64_t* n_decoded, int32_t* md5_status);
+
+/* ---- audio front: sample-rate conversion on the device (csrc/resample.hip) ---------------------------------------
+ * The Kaiser-windowed-sinc polyphase converter of faster_whisper_amd/audio.py::resample (the reference resamples inside
+ * PyAV / libswresample, faster_whisper/audio.py:42-62).  g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,
+ * big = max(up, down), half = taps_per_phase * big / 2; prototype h[t], t = -half .. half: 2c sinc(2c t) kaiser(beta) with
+ * c = 0.5 / big, scaled to sum up; y[m] = sum_k h[half + k up - m down] x[k], x zero outside [0, n).  float32 samples,
+ * fp64 coefficients and accumulation.  No fw_model is needed. */
+/* prototype filter of the rate converter (host code; needs no GPU).  h == NULL: only *n_h, *up, *down are written */
+int32_t fw_resample_filter(int32_t rate_in, int32_t rate_out, int32_t taps_per_phase, double beta,
+                           double* h, int64_t* n_h, int32_t* up, int32_t* down);
+/* x[n] float32 at rate_in -> out[n_out] float32 at rate_out on HIP device `device_index`;
+ * n_out must equal ceil(n * up / down); quantize_s16 != 0: the reference's s16 step (audio.py:62-66) fused:
+ * clip(rint(y * 32768), -32768, 32767) / 32768.  rate_in == rate_out copies (and quantises when asked to); n == 0
+ * writes nothing.  The recording passes through the device in blocks of FWAMD_RESAMPLE_BLOCK outputs (environment, read
+ * per call; default 2^20), so device memory does not grow with n.  FW_ENODEV without that device: no host fallback. */
+int32_t fw_resample_dev(int32_t device_index, const float* x, int64_t n, int32_t rate_in, int32_t rate_out,
+                        int32_t taps_per_phase, double beta, int32_t quantize_s16, float* out, int64_t n_out);
 
 #ifdef __cplusplus
 }

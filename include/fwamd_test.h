@@ -96,6 +96,10 @@ int32_t fw_test_dec_softmax_pick(fw_model* m, const float* logits, int32_t rows,
  * B chunks x H heads x T positions on device-resident pseudo-random operands; variant = the workgroup mapping
  * (0: XCD-aware, the product's; 1: query tile fastest over all XCDs, round 3's) */
 int32_t fw_bench_attention(fw_model* m, int32_t B, int32_t H, int32_t T, int32_t variant, int32_t iters, float* ms_out);
+/* measurement hook (profiles/resample_bench.py): mean milliseconds of the rate-conversion kernel of fw_resample_dev over
+ * the whole of x[n] (uploaded once, every output in one launch, `iters` launches between two HIP events after a warm-up) */
+int32_t fw_bench_resample(int32_t device_index, const float* x, int64_t n, int32_t rate_in, int32_t rate_out,
+                          int32_t taps_per_phase, double beta, int32_t quantize_s16, int32_t iters, float* ms_out);
 
 /* rows from which a decode run's per-layer linears take the GEMM-shaped kernel (dec_kernels.hip: DEC_BIG_MIN_ROWS);
  * bench.py prices the decoder linears against the MFMA roof from this row count on, against HBM below */
