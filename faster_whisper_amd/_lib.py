@@ -80,6 +80,7 @@ SYMBOLS = [
     "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules",
     "fw_test_dec_self_attn", "fw_test_dec_cross_attn", "fw_test_dec_cross_probs", "fw_test_dec_softmax_pick", "fw_bench_gemm", "fw_bench_dec_linear", "fw_bench_attention",
     "fw_bench_gemm_epi", "fw_bench_dec_linear_epi",
+    "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_flac_info", "fw_flac_decode",
     "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
@@ -180,6 +181,12 @@ def load():
         lib.fw_bench_dec_linear_epi.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p]
     lib.fw_test_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     lib.fw_test_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    if hasattr(lib, "fw_test_gemm_ex"):         # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_test_gemm_ex.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, i64, i64, i64, i64, i64,
+                                        i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+        lib.fw_test_cross_kv_frag_index.argtypes = [i32, i32, i32, vp]
+        lib.fw_test_quant_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp]
+        lib.fw_test_layernorm_frag.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]
     lib.fw_vad_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     lib.fw_vad_free.argtypes = [vp]

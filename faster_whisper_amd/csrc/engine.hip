@@ -1670,6 +1670,8 @@ int32_t fw_dev_upload(fw_model* fm, void* dst_dev, const void* src_host, int64_t
 }
 
 // ---------------------------------------------------------------- kernel test hooks
+// (the model's streams are non-blocking streams: a buffer a hook clears before a launch is cleared with hipMemsetAsync ON the
+//  launch's stream — a hipMemset on the null stream is not ordered against the kernel and may land after its stores)
 static int upload_f16(Model* m, const float* src, size_t n, half_t** dst) {
   int rc = dev_alloc_t(dst, n);
   if (rc) return rc;
@@ -1701,6 +1703,18 @@ static inline size_t cross_kv_frag_pos(bool vt, int kvp, int mm, int n) {
             : head + ((size_t)((mm >> 5) * 4 + 2 * ((r >> 2) & 1) + (c >> 5)) * 64 + ((c >> 3) & 3) * 16 + (((r >> 3) << 2) | (r & 3))) * 8 + (c & 7);
 }
 
+// per-output-row int8 quantisation of fp16-rounded W [N][K], exactly like the weight packer
+static void quant_w_rows_host(const float* W, int N, int K, int8_t* wq, float* ws) {
+  for (int n = 0; n < N; ++n) {
+    float amax = 0.f;
+    for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k]))));
+    const float sc = amax > 0.f ? 127.0f / amax : 0.f;
+    for (int k = 0; k < K; ++k)
+      wq[(size_t)n * K + k] = (int8_t)lrintf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k])) * sc);
+    ws[n] = amax > 0.f ? amax / 127.0f : 1.0f;
+  }
+}
+
 int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* bias, const float* residual,
                      int32_t M, int32_t N, int32_t K, int32_t act_gelu, int32_t use_int8, float* out) {
   FW_CHECK_ARG(fm && A && W && out, "null argument");
@@ -1726,14 +1740,7 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
     }
     std::vector<int8_t> wq((size_t)N * K);
     std::vector<float> ws(N);
-    for (int n = 0; n < N; ++n) {
-      float amax = 0.f;
-      for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k]))));
-      const float sc = amax > 0.f ? 127.0f / amax : 0.f;
-      for (int k = 0; k < K; ++k)
-        wq[(size_t)n * K + k] = (int8_t)lrintf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k])) * sc);
-      ws[n] = amax > 0.f ? amax / 127.0f : 1.0f;
-    }
+    quant_w_rows_host(W, N, K, wq.data(), ws.data());
     if ((rc = dev_alloc_t(&dWq, wq.size()))) return rc;
     if ((rc = dev_alloc_t(&dWs, ws.size()))) return rc;
     FW_HIP(hipMemcpy(dWq, wq.data(), wq.size(), hipMemcpyHostToDevice));
@@ -1751,7 +1758,7 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
     const int kvp = (M + 31) / 32 * 32, H = N / 64;
     half_t* dF = nullptr;
     if ((rc = dev_alloc_t(&dF, (size_t)H * kvp * 64))) return rc;
-    FW_HIP(hipMemset(dF, 0, (size_t)H * kvp * 64 * sizeof(half_t)));
+    FW_HIP(hipMemsetAsync(dF, 0, (size_t)H * kvp * 64 * sizeof(half_t), m->stream));
     rc = vt ? run_linear(m, L, dA, K, 0, dF, kvp, 0, nullptr, 0, 0, M, 1, 0, true, kvp)
             : run_linear(m, L, dA, K, 0, dF, N, 0, nullptr, 0, 0, M, 1, 0, false, kvp);
     std::vector<float> hf((size_t)H * kvp * 64);
@@ -1822,7 +1829,7 @@ int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const f
   owned.push_back(d_out);
   if ((rc = dev_alloc_t(&d_of, (size_t)R16 * N))) { cleanup(); return rc; }
   owned.push_back(d_of);
-  FW_HIP(hipMemset(d_of, 0, (size_t)R16 * N * 2));
+  FW_HIP(hipMemsetAsync(d_of, 0, (size_t)R16 * N * 2, st));
   if (use_int8 == 1) {
     if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || ln_g) {
       cleanup();
@@ -1854,7 +1861,7 @@ int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const f
     owned.push_back(d_xq);
     if ((rc = dev_alloc_t(&d_xs, (size_t)R16))) { cleanup(); return rc; }
     owned.push_back(d_xs);
-    FW_HIP(hipMemset(d_xq, 0, (size_t)R16 * K));
+    FW_HIP(hipMemsetAsync(d_xq, 0, (size_t)R16 * K, st));
     fwk::launch_quant_rows(st, d_x, K, nullptr, nullptr, d_xq, d_xs, R, K, 1);
     if (fwd::launch_dec_gemm_frag_i8(st, d_xq, d_xs, d_wq, d_ws, d_bias, d_res, N, d_out, N, R, N, K, act) != 0) {
       cleanup();
@@ -1964,7 +1971,7 @@ int32_t fw_test_dec_logits(fw_model* fm, const float* x, int32_t R, float* out) 
   int lr;
   if (i8) {
     if ((rc = dev_alloc_t(&d_xq, (size_t)R16 * d)) || (rc = dev_alloc_t(&d_xs, (size_t)R16))) { cleanup(); return rc; }
-    FW_HIP(hipMemset(d_xq, 0, (size_t)R16 * d));
+    FW_HIP(hipMemsetAsync(d_xq, 0, (size_t)R16 * d, st));
     fwk::launch_quant_rows(st, d_x, d, m->dec_ln.g, m->dec_ln.b, d_xq, d_xs, R, d, 1);
     lr = fwd::launch_dec_logits(st, true, d_xq, d_xs, m->logits.wq, m->logits.wscale, nullptr, nullptr, d_out, V, R, V, d);
   } else {
@@ -2252,23 +2259,173 @@ int32_t fw_bench_dec_linear_epi(fw_model* fm, int32_t R, int32_t N, int32_t K, i
   return FW_OK;
 }
 
-int32_t fw_test_layernorm(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
-                          float* out) {
-  FW_CHECK_ARG(fm && x && g && b && out, "null argument");
-  FW_CHECK_ARG(d % 128 == 0 && d <= 1280, "d must be a multiple of 128 and <= 1280");
+static int test_layernorm_impl(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
+                               int32_t frag, float* out) {
+  FW_CHECK_ARG(fm && x && g && b && out && rows >= 1, "null argument");
+  FW_CHECK_ARG(d % 128 == 0 && d >= 128 && d <= 1536, "d must be a multiple of 128 and <= 1536");
   Model* m = &fm->impl;
   std::lock_guard<std::mutex> lk(m->mu);
   FW_HIP(hipSetDevice(m->device));
   half_t *dx = nullptr, *dg = nullptr, *db = nullptr, *dy = nullptr;
+  const size_t ny = (size_t)(frag ? (rows + 15) / 16 * 16 : rows) * d;   // the fragment-major form is whole 16-row tiles
   int rc;
   if ((rc = upload_f16(m, x, (size_t)rows * d, &dx))) return rc;
   if ((rc = upload_f16(m, g, d, &dg))) return rc;
   if ((rc = upload_f16(m, b, d, &db))) return rc;
-  if ((rc = dev_alloc_t(&dy, (size_t)rows * d))) return rc;
-  fwk::launch_layernorm(m->stream, dx, dg, db, dy, rows, d);
-  rc = download_f16(m, dy, (size_t)rows * d, out);
+  if ((rc = dev_alloc_t(&dy, ny))) return rc;
+  FW_HIP(hipMemsetAsync(dy, 0, ny * sizeof(half_t), m->stream));   // (on the launch's stream: it is a non-blocking one)
+  fwk::launch_layernorm(m->stream, dx, dg, db, dy, rows, d, frag ? 1 : 0);
+  if (!frag) {
+    rc = download_f16(m, dy, (size_t)rows * d, out);
+  } else {
+    std::vector<float> yf(ny);
+    rc = download_f16(m, dy, ny, yf.data());
+    if (!rc)
+      for (int r = 0; r < rows; ++r)
+        for (int k = 0; k < d; ++k) out[(size_t)r * d + k] = yf[frag_pos(r, k, d, 32)];
+  }
   for (half_t* p : {dx, dg, db, dy})
     if (p) (void)hipFree(p);
+  return rc;
+}
+int32_t fw_test_layernorm(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
+                          float* out) {
+  return test_layernorm_impl(fm, x, g, b, rows, d, 0, out);
+}
+int32_t fw_test_layernorm_frag(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
+                               int32_t frag, float* out) {
+  return test_layernorm_impl(fm, x, g, b, rows, d, frag, out);
+}
+
+int32_t fw_test_quant_rows(fw_model* fm, const float* x, int32_t rows, int32_t d, int64_t ldx, const float* ln_g,
+                           const float* ln_b, int32_t frag, int8_t* xq, float* scale) {
+  FW_CHECK_ARG(fm && x && xq && scale && rows >= 1 && rows <= (1 << 20), "bad argument");
+  FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr), "ln_g and ln_b go together");
+  FW_CHECK_ARG(d >= 64 && d % 64 == 0 && d <= (ln_g ? 1536 : 5120), "d %% 64 == 0, d <= 1536 with LayerNorm, <= 5120 without");
+  FW_CHECK_ARG(ldx >= d && ldx % 8 == 0 && ldx <= (1 << 20), "ldx >= d, ldx %% 8 == 0");
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  FW_HIP(hipSetDevice(m->device));
+  const int R16 = (rows + 15) / 16 * 16;
+  half_t *dx = nullptr, *dg = nullptr, *db = nullptr;
+  int8_t* dq = nullptr;
+  float* ds = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)dx, (void*)dg, (void*)db, (void*)dq, (void*)ds}) if (p) (void)hipFree(p); };
+  int rc;
+  if ((rc = upload_f16(m, x, (size_t)(rows - 1) * ldx + d, &dx)) || (ln_g && (rc = upload_f16(m, ln_g, d, &dg))) ||
+      (ln_b && (rc = upload_f16(m, ln_b, d, &db))) || (rc = dev_alloc_t(&dq, (size_t)R16 * d)) ||
+      (rc = dev_alloc_t(&ds, (size_t)R16))) { cleanup(); return rc; }
+  std::vector<int8_t> hq((size_t)R16 * d);
+  hipError_t he = hipMemsetAsync(dq, 0, hq.size(), m->stream);     // (on the launch's stream: it is a non-blocking one)
+  if (he == hipSuccess) {
+    fwk::launch_quant_rows(m->stream, dx, ldx, dg, db, dq, ds, rows, d, frag ? 1 : 0);
+    he = hipStreamSynchronize(m->stream);
+  }
+  if (he == hipSuccess) he = hipMemcpy(hq.data(), dq, hq.size(), hipMemcpyDeviceToHost);
+  if (he == hipSuccess) he = hipMemcpy(scale, ds, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost);
+  cleanup();
+  if (he != hipSuccess) { set_error("fw_test_quant_rows: %s", hipGetErrorString(he)); return FW_ENODEV; }
+  for (int r = 0; r < rows; ++r)
+    for (int k = 0; k < d; ++k) xq[(size_t)r * d + k] = hq[frag ? frag_pos(r, k, d, 64) : (size_t)r * d + k];
+  return FW_OK;
+}
+
+int32_t fw_test_cross_kv_frag_index(int32_t vt, int32_t kvp, int32_t N, int64_t* idx) {
+  FW_CHECK_ARG(idx && kvp >= 32 && kvp % 32 == 0 && N >= 64 && N % 64 == 0, "need kvp %% 32 == 0, N %% 64 == 0");
+  for (int mm = 0; mm < kvp; ++mm)
+    for (int n = 0; n < N; ++n) idx[(size_t)mm * N + n] = (int64_t)cross_kv_frag_pos(vt != 0, kvp, mm, n);
+  return FW_OK;
+}
+
+int32_t fw_test_gemm_ex(fw_model* fm, const float* A, int64_t a_elems, int64_t lda, int64_t a_bstride, const float* W,
+                        const float* bias, const float* res, int64_t r_elems, int64_t ldr, int64_t r_bstride, float* C,
+                        int64_t c_elems, int64_t c_off, int64_t ldc, int64_t c_bstride, int64_t c_lstride, int32_t M,
+                        int32_t N, int32_t K, int32_t batch, int32_t n_layers, int32_t act, int32_t trans,
+                        int32_t head_rows, int32_t use_int8, const float* ln_g, const float* ln_b) {
+  FW_CHECK_ARG(fm && A && W && C, "null argument");
+  const int64_t dim_max = 1 << 20, cnt_max = 1 << 12, str_max = (int64_t)1 << 40;   // (no product below can overflow)
+  FW_CHECK_ARG(M >= 1 && N >= 1 && K >= 1 && M <= dim_max && N <= dim_max && K <= dim_max, "bad M / N / K");
+  FW_CHECK_ARG(batch >= 1 && n_layers >= 1 && batch <= cnt_max && n_layers <= cnt_max, "bad batch / n_layers");
+  for (int64_t v : {a_elems, lda, a_bstride, r_elems, ldr, r_bstride, c_elems, c_off, ldc, c_bstride, c_lstride})
+    FW_CHECK_ARG(v >= 0 && v <= str_max, "negative or oversized count / stride");
+  FW_CHECK_ARG(act == 0 || act == 1, "act is 0 or 1");
+  FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr) && (!ln_g || use_int8), "ln_g / ln_b: both, and only with use_int8");
+  const bool rowmajor = !trans && head_rows == 0;
+  FW_CHECK_ARG(!res || (rowmajor && n_layers == 1), "a residual needs the row-major single-layer form");
+  FW_CHECK_ARG(n_layers == 1 || (!use_int8 && act == 0), "the layered launch is fp16 without activation");
+  FW_CHECK_ARG(head_rows == 0 || (head_rows > 0 && head_rows % 32 == 0 && head_rows >= M && N % 64 == 0),
+               "fragment-major output: head_rows %% 32 == 0, head_rows >= M, N %% 64 == 0");
+  // 16-byte stores of the epilogues start from these offsets
+  FW_CHECK_ARG(c_off % 8 == 0 && c_lstride % 8 == 0, "c_off and c_lstride must be multiples of 8");
+  if (use_int8) FW_CHECK_ARG(lda == K && a_bstride == (int64_t)M * K, "int8: A is contiguous [batch * M][K]");
+  // ---- the furthest element the launch touches in each buffer (gemm.hip: rows are clamped to M - 1, every K tile is read
+  // whole, residual and output are touched only at m < M, n < N; a fragment-major key group is written as a whole) ----
+  const int64_t a_last = (int64_t)(batch - 1) * a_bstride + (int64_t)(M - 1) * lda + (K - 1);
+  FW_CHECK_ARG(a_last < a_elems, "the launch reads A[%lld], a_elems = %lld", (long long)a_last, (long long)a_elems);
+  if (res) {
+    const int64_t r_last = (int64_t)(batch - 1) * r_bstride + (int64_t)(M - 1) * ldr + (N - 1);
+    FW_CHECK_ARG(r_last < r_elems, "the launch reads res[%lld], r_elems = %lld", (long long)r_last, (long long)r_elems);
+  }
+  const int64_t chunk_last = head_rows > 0 ? (int64_t)(N / 64 - 1) * head_rows * 64 + (int64_t)((M - 1) / 32 + 1) * 2048 - 1
+                             : trans       ? (int64_t)(N - 1) * ldc + (M - 1)
+                                           : (int64_t)(M - 1) * ldc + (N - 1);
+  const int64_t c_last = c_off + (int64_t)(n_layers - 1) * c_lstride + (int64_t)(batch - 1) * c_bstride + chunk_last;
+  FW_CHECK_ARG(c_last < c_elems, "the launch writes C[%lld], c_elems = %lld", (long long)c_last, (long long)c_elems);
+
+  Model* m = &fm->impl;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (use_int8) {
+    const int64_t T = m->cfg.n_audio_ctx;
+    if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || (int64_t)batch * M * K > (int64_t)m->max_batch * T * 4 * m->cfg.d_model ||
+        (int64_t)batch * M > (int64_t)m->max_batch * T || (ln_g && K > 1536)) {
+      set_error("int8 gemm test needs an int8_float16 model, batch*M*K within its quantisation workspace, K <= 1536 with LayerNorm");
+      return FW_EINVAL;
+    }
+  }
+  FW_HIP(hipSetDevice(m->device));
+  std::vector<void*> owned;
+  auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
+  auto up16 = [&](const float* src, size_t n, half_t** dst) -> int {
+    int rc = upload_f16(m, src, n, dst);
+    if (*dst) owned.push_back(*dst);
+    return rc;
+  };
+  half_t *dA = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr, *dG = nullptr, *dLb = nullptr;
+  const size_t nw = (size_t)n_layers * N * K;
+  int rc;
+  if ((rc = up16(A, (size_t)a_elems, &dA)) || (rc = up16(W, nw, &dW)) || (bias && (rc = up16(bias, (size_t)n_layers * N, &dB))) ||
+      (res && (rc = up16(res, (size_t)r_elems, &dR))) || (rc = up16(C, (size_t)c_elems, &dC)) ||
+      (ln_g && ((rc = up16(ln_g, K, &dG)) || (rc = up16(ln_b, K, &dLb))))) { cleanup(); return rc; }
+  LinearW L{dW, dB, nullptr, nullptr, nullptr, nullptr, N, K};
+  if (use_int8) {
+    std::vector<int8_t> wq(nw);
+    std::vector<float> ws(N);
+    quant_w_rows_host(W, N, K, wq.data(), ws.data());
+    int8_t* dWq = nullptr;
+    float* dWs = nullptr;
+    if ((rc = dev_alloc_t(&dWq, wq.size()))) { cleanup(); return rc; }
+    owned.push_back(dWq);
+    if ((rc = dev_alloc_t(&dWs, ws.size()))) { cleanup(); return rc; }
+    owned.push_back(dWs);
+    if (hipMemcpy(dWq, wq.data(), wq.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dWs, ws.data(), ws.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      cleanup();
+      set_error("fw_test_gemm_ex: upload failed");
+      return FW_ENODEV;
+    }
+    L.wq = dWq; L.wscale = dWs;
+    LNW ln{dG, dLb};
+    rc = run_linear_i8(m, L, dA, ln_g ? &ln : nullptr, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act,
+                       trans != 0, head_rows);
+  } else if (n_layers > 1) {
+    rc = run_linear_layers(m, L, n_layers, (int64_t)N * K, bias ? N : 0, dA, lda, a_bstride, dC + c_off, ldc, c_bstride,
+                           c_lstride, M, batch, trans != 0, head_rows, nullptr);
+  } else {
+    rc = run_linear(m, L, dA, lda, a_bstride, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act, trans != 0,
+                    head_rows, nullptr);
+  }
+  if (!rc) rc = download_f16(m, dC, (size_t)c_elems, C);
+  cleanup();
   return rc;
 }
 
@@ -2398,7 +2555,7 @@ int32_t fw_test_dec_self_attn(fw_model* fm, const float* qkv, float* kcache, flo
     return rc;
   FW_HIP(hipMemcpy(d_idx, kvidx, n_tab, hipMemcpyHostToDevice));
   FW_HIP(hipMemcpy(d_step, &step, sizeof(int), hipMemcpyHostToDevice));
-  FW_HIP(hipMemset(d_out, 0, (size_t)R16 * d * 2));
+  FW_HIP(hipMemsetAsync(d_out, 0, (size_t)R16 * d * 2, m->stream));
   fwd::launch_self_attn(m->stream, d_qkv, d, d_kc, d_vc, n_ctx, cache_ctx, H, d_idx, Kbeam, kmul, d_out, R, d_step,
                         pos_fixed, P, R_total, frag ? 1 : 0, blk_n);
   FW_HIP(hipGetLastError());

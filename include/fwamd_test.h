@@ -60,6 +60,40 @@ int32_t fw_bench_dec_linear_epi(fw_model* m, int32_t R, int32_t N, int32_t K, in
                                 int32_t res, int32_t outs, int32_t iters, float* us_out);
 int32_t fw_test_layernorm(fw_model* m, const float* x, const float* g, const float* b,
                           int32_t rows, int32_t d, float* out);
+/* fw_test_layernorm with the output layout as an argument: frag = 1 is the MFMA-fragment-major form the decoder linears
+ * read (rowops.hip; d % 32 == 0), un-permuted on the host into out [rows][d]; frag = 0 is fw_test_layernorm */
+int32_t fw_test_layernorm_frag(fw_model* m, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
+                               int32_t frag, float* out);
+/* one launch of the row quantiser (rowops.hip: launch_quant_rows): x [rows][ldx] (the first d of every ldx elements are
+ * a row; ldx % 8 == 0, ldx >= d), LayerNorm in front when ln_g / ln_b are given -> int8 codes xq [rows][d] and
+ * de-quantisation scales scale [rows].  frag = 1: the int8 fragment-major destination, un-permuted on the host.
+ * d % 64 == 0; d <= 1536 with LayerNorm, <= 5120 without (the kernel's limits). */
+int32_t fw_test_quant_rows(fw_model* m, const float* x, int32_t rows, int32_t d, int64_t ldx, const float* ln_g,
+                           const float* ln_b, int32_t frag, int8_t* xq, float* scale);
+/* one launch of the encoder GEMM in any form the product launches, through the product's entry points (engine.hip:
+ * run_linear; run_linear_layers when n_layers > 1; run_linear_i8 when use_int8).  The caller describes the device buffers
+ * as they lie in memory (all counts in elements):
+ *   A    a_elems values; chunk z, row r starts at z * a_bstride + r * lda (rows may overlap: conv2 has lda < K).
+ *        use_int8: contiguous [batch * M][K] (lda = K, a_bstride = M * K: what run_linear_i8 takes), quantised by the
+ *        launch's own row quantiser, through LayerNorm(ln_g, ln_b [K]) when those are given
+ *   W    [n_layers][N][K], bias [n_layers][N] | NULL (use_int8: W quantised per row on the host like fw_test_gemm)
+ *   res  r_elems values | NULL; chunk z, row r at z * r_bstride + r * ldr (r_bstride = 0: one block shared by all
+ *        chunks); row-major output only
+ *   C    c_elems values IN / OUT: the WHOLE buffer is uploaded (rounded to fp16) before the launch and downloaded after
+ *        it, gaps and tail included, and nothing is un-permuted.  The launch gets C + c_off (c_off % 8 == 0); layer l,
+ *        chunk z start at l * c_lstride + z * c_bstride.  Row-major: row r at r * ldc; trans = 1: Ct, column n at
+ *        n * ldc; head_rows > 0 (% 32 == 0, >= M, N % 64 == 0): the fragment-major cross-attention K (trans = 0) / V^T
+ *        (trans = 1) block of [N / 64][head_rows * 64] per chunk (index it with fw_test_cross_kv_frag_index)
+ * Before anything is launched the furthest element the described launch reads or writes in A, res and C is computed:
+ * FW_EINVAL when it lies outside a_elems / r_elems / c_elems (a wrong test gets an error code, never a device fault). */
+int32_t fw_test_gemm_ex(fw_model* m, const float* A, int64_t a_elems, int64_t lda, int64_t a_bstride, const float* W,
+                        const float* bias, const float* res, int64_t r_elems, int64_t ldr, int64_t r_bstride, float* C,
+                        int64_t c_elems, int64_t c_off, int64_t ldc, int64_t c_bstride, int64_t c_lstride, int32_t M,
+                        int32_t N, int32_t K, int32_t batch, int32_t n_layers, int32_t act, int32_t trans,
+                        int32_t head_rows, int32_t use_int8, const float* ln_g, const float* ln_b);
+/* host-only: idx [kvp][N] = position of (key, column) inside one chunk's fragment-major cross-attention K (vt = 0) /
+ * V^T (vt = 1) block of [N / 64][kvp * 64] halves (kvp % 32 == 0, N % 64 == 0): the layout the projection GEMM writes */
+int32_t fw_test_cross_kv_frag_index(int32_t vt, int32_t kvp, int32_t N, int64_t* idx);
 int32_t fw_test_attention(fw_model* m, const float* q, const float* k, const float* v,
                           int32_t B, int32_t H, int32_t T, float* out);
 /* decoder self-attention, one launch exactly as a decode step makes it (dec_kernels.hip: launch_self_attn; the form

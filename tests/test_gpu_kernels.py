@@ -115,7 +115,7 @@ def test_gemm_transposed_output_staged_epilogue(model, M, N, K):
     assert np.array_equal(out[0], out[1])
 
 
-@pytest.mark.parametrize("d", [128, 384, 1280])
+@pytest.mark.parametrize("d", [128, 384, 1280, 1536])     # 1536: the kernel's limit (three 16-byte chunks per lane)
 def test_layernorm(model, d):
     from faster_whisper_amd import _lib
     lib = _lib.load()
