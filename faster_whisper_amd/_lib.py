@@ -81,6 +81,7 @@ SYMBOLS = [
     "fw_test_dec_self_attn", "fw_test_dec_cross_attn", "fw_test_dec_cross_probs", "fw_test_dec_softmax_pick", "fw_bench_gemm", "fw_bench_dec_linear", "fw_bench_attention",
     "fw_bench_gemm_epi", "fw_bench_dec_linear_epi",
     "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
+    "fw_test_dec_beam_update", "fw_test_dec_embed", "fw_test_align_post",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_flac_info", "fw_flac_decode",
     "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
@@ -187,6 +188,12 @@ def load():
         lib.fw_test_cross_kv_frag_index.argtypes = [i32, i32, i32, vp]
         lib.fw_test_quant_rows.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp]
         lib.fw_test_layernorm_frag.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    if hasattr(lib, "fw_test_dec_beam_update"):  # (absent from an older build loaded through FWAMD_LIB)
+        f32 = C.c_float
+        lib.fw_test_dec_beam_update.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp,
+                                                i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.fw_test_dec_embed.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
+        lib.fw_test_align_post.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]
     lib.fw_vad_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     lib.fw_vad_free.argtypes = [vp]

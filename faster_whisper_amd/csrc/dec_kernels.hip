@@ -1704,6 +1704,14 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
 // candidates (stable: value desc, flat index asc), walks the first K slots (EOS / last step ->
 // finished hypothesis, replaced by the next non-EOS secondary candidate), then rewrites
 // the per-row state (token history, KV-slot table, cum, next input token).
+// Contract (pinned by tests/decode_state_refs.py::beam_update_ref, tests/test_gpu_decode_state.py):
+//   * -inf candidates are never merged (rows arrive sorted, -inf at the tail); at step 0 only row 0 is a source;
+//   * an <eot> secondary is skipped when a finished slot is refilled, and is NOT recorded as a hypothesis;
+//   * nothing is recorded past FIN_CAP;
+//   * a chunk that finishes (last step, n_fin >= max_fin, no live beam) or was done on entry rewrites NO row state:
+//     only fin_*, n_fin, done and n_done change;
+//   * otherwise dead beams copy live beam 0 with cum = -inf, and history (+ token at `step`), slot table (+ parent byte
+//     at P - 1 + step), cum and cur_tok go to the OTHER parity half; the current half is left as it was.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, const float* __restrict__ cand_val,
                                                              const int* __restrict__ cand_tok, int* __restrict__ hist2,

@@ -35,6 +35,43 @@ int32_t fw_test_dec_logits(fw_model* m, const float* x, int32_t R, float* out);
 int32_t fw_test_logits_rules(fw_model* m, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                              const float* cum, const fw_gen_opts* opts, int32_t with_timestamps, float* cand_val,
                              int32_t* cand_tok);
+/* The three hooks of the decode-state kernels (tests/test_gpu_decode_state.py).  Geometry comes from the arguments, not
+ * from the model.  Every quantity a kernel uses as an index or extent is checked BEFORE anything is allocated or
+ * launched; a violation returns FW_EINVAL (a wrong test gets an error code, never a device fault).
+ *
+ * fw_test_dec_beam_update: one launch of the beam update (dec_kernels.hip K19/K20: launch_beam_update) for B chunks of K
+ * beams (R = B * K rows) at decode step `step` of a text context of NT positions and a vocabulary of V tokens.
+ *   in      cand_val / cand_tok [R][2 K] (each row sorted by value, descending, -inf at the tail: what the logits-rules
+ *           kernel leaves; the hook places them at the kernel's stride of 32 per row), hist [R][step], kvidx
+ *           [R][P - 1 + step], cum [R]
+ *   in/out  done [B], n_done [1], n_fin [B], fin_tok [B][FIN_CAP = 48][NT], fin_len / fin_score / fin_cum [B][48]: uploaded
+ *           and downloaded WHOLE
+ *   out     hist2 [2][R][NT], kvidx2 [2][R][NT] (bytes), cum2 [2][R], cur_tok [R]: both parity halves whole.  The hook put
+ *           hist / kvidx / cum into half step & 1 and filled everything else (the rest of that half, the other half,
+ *           cur_tok) with sentinel_i (its low byte in kvidx2) / sentinel_f (cum2) before the launch.
+ * Checked: 1 <= K <= 16, 1 <= B <= 4096, 1 <= NT <= 4096, P >= 1, 0 <= step < NT, P - 1 + step < NT, 0 <= eot < V,
+ * max_fin >= 1, budget >= 1, every cand_tok in [0, V), every kvidx byte < K, 0 <= n_fin[c] <= 48. */
+int32_t fw_test_dec_beam_update(fw_model* m, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                const int32_t* cand_tok, const int32_t* hist, const uint8_t* kvidx, const float* cum,
+                                int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
+                                int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
+                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok);
+/* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
+ * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
+ * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
+ * Position of row r: blk_n > 0 (<= 16, rows % blk_n == 0, pos_fixed >= 0, pos_fixed + blk_n <= NT): pos_fixed + r % blk_n;
+ * else pos_fixed >= 0 (< NT): pos_fixed; else the step-counter route, P - 1 + step (P >= 1, 0 <= step, < NT).
+ * d % 32 == 0. */
+int32_t fw_test_dec_embed(fw_model* m, const int32_t* tok, int32_t rows, const float* emb, int32_t V,
+                          const float* pos_emb, int32_t NT, int32_t d, int32_t pos_fixed, int32_t P, int32_t step,
+                          int32_t blk_n, float sentinel, float* x, float* x_frag);
+/* the device part of align's post-processing, align_stats_kernel then align_filter_kernel launched as fw_align does:
+ * probs [B][n_sel][n_tok_cap][T], n_tok [B] (1 .. n_tok_cap), nfr [B] (1 .. T), width odd and <= 15, n_sel >= 1 ->
+ * mat [B][n_tok_cap][T] IN / OUT (the device buffer starts as the caller's values; only tok < n_tok[b], t < nfr[b] are
+ * written).  A frame with zero variance over the tokens gives inf * 0 here and in the oracle alike: not pinned. */
+int32_t fw_test_align_post(fw_model* m, const float* probs, int32_t B, int32_t n_sel, int32_t n_tok_cap, int32_t T,
+                           const int32_t* n_tok, const int32_t* nfr, int32_t width, float* mat);
 /* measurement hook (profiles/gemm_bench.py): average milliseconds of one launch of the "many rows" GEMM
  * C[batch][M][N] = A[batch][M][K] W[N][K]^T on device-resident pseudo-random operands (fp16, or int8 on an
  * int8_float16 model); lda = K + a_pad, ldw = K + w_pad elements; trans: the transposed-output form */
