@@ -1115,251 +1115,6 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
   return req.rc;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Test hook: ONE launch of the logits-rules kernel (rules, log-softmax, top-2K / Gumbel arg-max) on caller-provided
-// logits and row state, outside any decode run: tests/test_gpu_logits_rules.py compares the candidates with the
-// oracle's rule restatement id for id.  rows = R (row r belongs to chunk r / beam_size), n = tokens generated so far
-// (the same for every row), hist [R][n], cum [R]; out: cand_val / cand_tok [R][2 * beam_size] (sampling: [R][1]).
-// ---------------------------------------------------------------------------------------------------
-int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
-                             const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
-                             int32_t* cand_tok) {
-  FW_CHECK_ARG(fm && logits && cum && o && cand_val && cand_tok && R >= 1 && n >= 0, "bad arguments");
-  Model* m = &fm->impl;
-  const fw_config& c = m->cfg;
-  const int K = o->beam_size;
-  const bool sampling = K == 1 && o->sampling_topk != 1;
-  FW_CHECK_ARG(K >= 1 && K <= 16 && R % K == 0 && n < c.n_text_ctx && (n == 0 || hist), "bad geometry");
-  FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64, "vocabulary too large for the rules kernel");
-  FW_HIP(hipSetDevice(m->device));
-  GenDev gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.B = R / K; gp.K = K; gp.R = R; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx;
-  gp.sample = sampling ? 1 : 0;
-  gp.inv_temp = sampling ? 1.0f / o->sampling_temperature : 1.0f;
-  gp.seed_lo = (unsigned)(o->seed & 0xffffffffu);
-  gp.seed_hi = (unsigned)(o->seed >> 32);
-  gp.with_ts = with_timestamps ? 1 : 0;
-  gp.suppress_blank = o->suppress_blank ? 1 : 0;
-  gp.min_new = o->min_new_tokens;
-  gp.mits = o->max_initial_timestamp_index;
-  gp.ngram = o->no_repeat_ngram_size;
-  gp.rep_pen = o->repetition_penalty;
-  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
-  gp.n_sup_begin = c.n_suppress_begin;
-  for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
-  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
-  for (int i = 0; i < o->n_suppress_tokens; ++i) {
-    const int t = o->suppress_tokens[i];
-    if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
-  }
-  const size_t NT = (size_t)c.n_text_ctx;
-  std::vector<int> h2(2 * (size_t)R * NT, 0);
-  std::vector<float> c2(2 * (size_t)R, 0.f);
-  const int cur = n & 1;   // the kernel reads the half selected by the step's parity
-  for (int r = 0; r < R; ++r) {
-    for (int i = 0; i < n; ++i) h2[((size_t)cur * R + r) * NT + i] = hist[(size_t)r * n + i];
-    c2[(size_t)cur * R + r] = cum[r];
-  }
-  float *d_lg = nullptr, *d_cum = nullptr, *d_cv = nullptr;
-  int *d_hist = nullptr, *d_step = nullptr, *d_done = nullptr, *d_ct = nullptr;
-  unsigned long long* d_bits = nullptr;
-  int rc = FW_OK;
-  auto cleanup = [&]() {
-    (void)hipFree(d_lg); (void)hipFree(d_cum); (void)hipFree(d_cv); (void)hipFree(d_hist); (void)hipFree(d_step);
-    (void)hipFree(d_done); (void)hipFree(d_ct); (void)hipFree(d_bits);
-  };
-#define TH(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s: %s", #call, hipGetErrorString(e_)); cleanup(); return FW_ENODEV; } } while (0)
-  const size_t lg_bytes = (size_t)R * c.n_vocab * sizeof(float);
-  TH(hipMalloc(&d_lg, lg_bytes));
-  TH(hipMalloc(&d_cum, c2.size() * sizeof(float)));
-  TH(hipMalloc(&d_cv, (size_t)R * 32 * sizeof(float)));
-  TH(hipMalloc(&d_ct, (size_t)R * 32 * sizeof(int)));
-  TH(hipMalloc(&d_hist, h2.size() * sizeof(int)));
-  TH(hipMalloc(&d_step, sizeof(int)));
-  TH(hipMalloc(&d_done, (size_t)R * sizeof(int)));
-  TH(hipMalloc(&d_bits, mask.size() * sizeof(mask[0])));
-  TH(hipMemcpy(d_lg, logits, lg_bytes, hipMemcpyHostToDevice));
-  TH(hipMemcpy(d_cum, c2.data(), c2.size() * sizeof(float), hipMemcpyHostToDevice));
-  TH(hipMemcpy(d_hist, h2.data(), h2.size() * sizeof(int), hipMemcpyHostToDevice));
-  TH(hipMemcpy(d_step, &n, sizeof(int), hipMemcpyHostToDevice));
-  TH(hipMemset(d_done, 0, (size_t)R * sizeof(int)));
-  TH(hipMemset(d_cv, 0, (size_t)R * 32 * sizeof(float)));
-  TH(hipMemset(d_ct, 0, (size_t)R * 32 * sizeof(int)));
-  TH(hipMemcpy(d_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice));
-  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct);
-  TH(hipGetLastError());
-  TH(hipDeviceSynchronize());
-  const int C = sampling ? 1 : 2 * K;
-  std::vector<float> hv((size_t)R * 32);
-  std::vector<int> ht((size_t)R * 32);
-  TH(hipMemcpy(hv.data(), d_cv, hv.size() * sizeof(float), hipMemcpyDeviceToHost));
-  TH(hipMemcpy(ht.data(), d_ct, ht.size() * sizeof(int), hipMemcpyDeviceToHost));
-#undef TH
-  for (int r = 0; r < R; ++r)
-    for (int j = 0; j < C; ++j) {
-      cand_val[(size_t)r * C + j] = hv[(size_t)r * 32 + j];
-      cand_tok[(size_t)r * C + j] = ht[(size_t)r * 32 + j];
-    }
-  cleanup();
-  return rc;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Test hooks of the decode-state kernels (tests/test_gpu_decode_state.py).  Each owns its device buffers, takes its
-// geometry from arguments (not from the model) and calls the product's launcher unchanged.  EVERY quantity a kernel
-// turns into an index or an extent is checked before anything is allocated or launched: a mistaken test gets
-// FW_EINVAL, never an out-of-bounds access.
-// ---------------------------------------------------------------------------------------------------
-extern "C++" {
-namespace {
-struct HookBufs {   // device buffers of one hook call, freed on every return path
-  std::vector<void*> p;
-  template <typename T>
-  int alloc(T** dst, size_t n) {
-    int rc = dev_alloc_t(dst, n);
-    if (!rc) p.push_back(*dst);
-    return rc;
-  }
-  template <typename T>
-  int upload(T** dst, const T* src, size_t n) {
-    int rc = alloc(dst, n);
-    if (rc) return rc;
-    FW_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return FW_OK;
-  }
-  ~HookBufs() { for (void* q : p) (void)hipFree(q); }
-};
-template <typename T>
-int hook_download(T* dst, const T* src, size_t n) {
-  FW_HIP(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-  return FW_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-// ONE launch of dec_beam_update_kernel (fwd::launch_beam_update) for B chunks of K beams at decode step `step`.
-int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
-                                int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
-                                const int32_t* cand_tok, const int32_t* hist, const uint8_t* kvidx, const float* cum,
-                                int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
-                                int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
-                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok) {
-  FW_CHECK_ARG(fm && cand_val && cand_tok && cum && done && n_done && n_fin && fin_tok && fin_len && fin_score &&
-                   fin_cum && hist2 && kvidx2 && cum2 && cur_tok, "null argument");
-  FW_CHECK_ARG(K >= 1 && K <= 16, "need 1 <= K <= 16 (K = %d)", K);
-  FW_CHECK_ARG(B >= 1 && B <= 4096, "need 1 <= B <= 4096 (B = %d)", B);
-  FW_CHECK_ARG(NT >= 1 && NT <= 4096 && V >= 1, "need 1 <= NT <= 4096 and V >= 1");
-  FW_CHECK_ARG(P >= 1 && step >= 0 && step < NT && (int64_t)P - 1 + step < NT,
-               "need P >= 1, 0 <= step < NT and P - 1 + step < NT (P = %d, step = %d, NT = %d)", P, step, NT);
-  FW_CHECK_ARG(eot >= 0 && eot < V && max_fin >= 1 && budget >= 1 && lp_pow == lp_pow, "bad eot / max_fin / budget / lp_pow");
-  const int R = B * K, C = 2 * K, pos = P - 1 + step;
-  FW_CHECK_ARG((step == 0 || hist) && (pos == 0 || kvidx), "null history / slot table");
-  for (int i = 0; i < R * C; ++i)
-    FW_CHECK_ARG(cand_tok[i] >= 0 && cand_tok[i] < V, "cand_tok[%d] = %d outside [0, %d)", i, cand_tok[i], V);
-  for (int64_t i = 0; i < (int64_t)R * pos; ++i)
-    FW_CHECK_ARG(kvidx[i] < K, "kvidx[%lld] = %d is not a beam of %d", (long long)i, (int)kvidx[i], K);
-  for (int c = 0; c < B; ++c)
-    FW_CHECK_ARG(n_fin[c] >= 0 && n_fin[c] <= FIN_CAP, "n_fin[%d] = %d outside [0, %d]", c, n_fin[c], FIN_CAP);
-  GenDev gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.B = B; gp.K = K; gp.R = R; gp.P = P; gp.budget = budget; gp.max_fin = max_fin; gp.V = V; gp.n_text_ctx = NT;
-  gp.lp_pow = lp_pow; gp.eot = eot; gp.kv_div = 1;
-  // both parity halves: the inputs go to half step & 1, everything else holds the caller's sentinel
-  const int cur = step & 1;
-  const size_t n_state = 2 * (size_t)R * NT;
-  std::vector<int> h2(n_state, sentinel_i), ct(R, sentinel_i);
-  std::vector<uint8_t> k2(n_state, (uint8_t)sentinel_i);
-  std::vector<float> c2(2 * (size_t)R, sentinel_f), cv((size_t)R * 32, -INFINITY);
-  std::vector<int> ctk((size_t)R * 32, 0);
-  for (int r = 0; r < R; ++r) {
-    for (int q = 0; q < step; ++q) h2[((size_t)cur * R + r) * NT + q] = hist[(size_t)r * step + q];
-    for (int q = 0; q < pos; ++q) k2[((size_t)cur * R + r) * NT + q] = kvidx[(size_t)r * pos + q];
-    c2[(size_t)cur * R + r] = cum[r];
-    for (int j = 0; j < C; ++j) {   // the kernel's row stride of 32 candidates
-      cv[(size_t)r * 32 + j] = cand_val[(size_t)r * C + j];
-      ctk[(size_t)r * 32 + j] = cand_tok[(size_t)r * C + j];
-    }
-  }
-  Model* m = &fm->impl;
-  FW_HIP(hipSetDevice(m->device));
-  HookBufs db;
-  float *d_cv, *d_c2, *d_fs, *d_fc;
-  int *d_ct, *d_h2, *d_cur, *d_step, *d_done, *d_ndone, *d_nfin, *d_ft, *d_fl;
-  uint8_t* d_k2;
-  const size_t n_f = (size_t)B * FIN_CAP;
-  int rc;
-  if ((rc = db.upload(&d_cv, (const float*)cv.data(), cv.size())) || (rc = db.upload(&d_ct, (const int*)ctk.data(), ctk.size())) ||
-      (rc = db.upload(&d_h2, (const int*)h2.data(), n_state)) || (rc = db.upload(&d_k2, (const uint8_t*)k2.data(), n_state)) ||
-      (rc = db.upload(&d_c2, (const float*)c2.data(), c2.size())) || (rc = db.upload(&d_cur, (const int*)ct.data(), ct.size())) ||
-      (rc = db.upload(&d_step, (const int*)&step, 1)) || (rc = db.upload(&d_done, (const int*)done, (size_t)B)) ||
-      (rc = db.upload(&d_ndone, (const int*)n_done, 1)) || (rc = db.upload(&d_nfin, (const int*)n_fin, (size_t)B)) ||
-      (rc = db.upload(&d_ft, (const int*)fin_tok, n_f * NT)) || (rc = db.upload(&d_fl, (const int*)fin_len, n_f)) ||
-      (rc = db.upload(&d_fs, (const float*)fin_score, n_f)) || (rc = db.upload(&d_fc, (const float*)fin_cum, n_f)))
-    return rc;
-  fwd::launch_beam_update(nullptr, gp, d_cv, d_ct, d_h2, d_c2, d_k2, d_cur, d_step, d_done, d_ndone, d_nfin, d_ft, d_fl,
-                          d_fs, d_fc);
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipDeviceSynchronize());
-  if ((rc = hook_download(hist2, d_h2, n_state)) || (rc = hook_download(kvidx2, d_k2, n_state)) ||
-      (rc = hook_download(cum2, d_c2, c2.size())) || (rc = hook_download(cur_tok, d_cur, (size_t)R)) ||
-      (rc = hook_download(done, d_done, (size_t)B)) || (rc = hook_download(n_done, d_ndone, 1)) ||
-      (rc = hook_download(n_fin, d_nfin, (size_t)B)) || (rc = hook_download(fin_tok, d_ft, n_f * NT)) ||
-      (rc = hook_download(fin_len, d_fl, n_f)) || (rc = hook_download(fin_score, d_fs, n_f)) ||
-      (rc = hook_download(fin_cum, d_fc, n_f)))
-    return rc;
-  return FW_OK;
-}
-
-// ONE launch of dec_embed_kernel (fwd::launch_embed): x [rows][d] and the fragment-major copy, un-permuted on the host
-// into x_frag [ceil(rows / 16) * 16][d] (the device buffer starts as `sentinel`, so the padding rows of the last 16-row
-// tile show whether they were touched).  Position: blk_n > 0: pos_fixed + r % blk_n; else pos_fixed >= 0: pos_fixed;
-// else P - 1 + the device step counter (= step).
-int32_t fw_test_dec_embed(fw_model* fm, const int32_t* tok, int32_t rows, const float* emb, int32_t V,
-                          const float* pos_emb, int32_t NT, int32_t d, int32_t pos_fixed, int32_t P, int32_t step,
-                          int32_t blk_n, float sentinel, float* x, float* x_frag) {
-  FW_CHECK_ARG(fm && tok && emb && pos_emb && x && x_frag, "null argument");
-  FW_CHECK_ARG(rows >= 1 && rows <= 65536 && V >= 1 && NT >= 1 && NT <= 65536, "bad geometry");
-  FW_CHECK_ARG(d >= 32 && d % 32 == 0 && d <= 16384, "need d %% 32 == 0, 32 <= d <= 16384 (d = %d)", d);
-  FW_CHECK_ARG(blk_n >= 0 && blk_n <= 16, "need 0 <= blk_n <= 16 (blk_n = %d)", blk_n);
-  if (blk_n > 0) {
-    FW_CHECK_ARG(rows % blk_n == 0, "rows (%d) must be a multiple of blk_n (%d)", rows, blk_n);
-    FW_CHECK_ARG(pos_fixed >= 0 && pos_fixed + blk_n <= NT, "positions %d..%d outside [0, %d)", pos_fixed,
-                 pos_fixed + blk_n - 1, NT);
-  } else if (pos_fixed >= 0) {
-    FW_CHECK_ARG(pos_fixed < NT, "position %d outside [0, %d)", pos_fixed, NT);
-  } else {
-    FW_CHECK_ARG(P >= 1 && step >= 0 && step < NT && (int64_t)P - 1 + step < NT,
-                 "need P >= 1, 0 <= step < NT and P - 1 + step < NT (P = %d, step = %d, NT = %d)", P, step, NT);
-  }
-  for (int r = 0; r < rows; ++r) FW_CHECK_ARG(tok[r] >= 0 && tok[r] < V, "tok[%d] = %d outside [0, %d)", r, tok[r], V);
-  const int R16 = (rows + 15) / 16 * 16, KS = d / 32;
-  std::vector<half_t> he((size_t)V * d), hp((size_t)NT * d), hx((size_t)rows * d, (half_t)sentinel),
-      hf((size_t)R16 * d, (half_t)sentinel);
-  for (size_t i = 0; i < he.size(); ++i) he[i] = (half_t)emb[i];
-  for (size_t i = 0; i < hp.size(); ++i) hp[i] = (half_t)pos_emb[i];
-  Model* m = &fm->impl;
-  FW_HIP(hipSetDevice(m->device));
-  HookBufs db;
-  half_t *d_e, *d_p, *d_x, *d_f;
-  int *d_tok, *d_step;
-  int rc;
-  if ((rc = db.upload(&d_e, (const half_t*)he.data(), he.size())) || (rc = db.upload(&d_p, (const half_t*)hp.data(), hp.size())) ||
-      (rc = db.upload(&d_x, (const half_t*)hx.data(), hx.size())) || (rc = db.upload(&d_f, (const half_t*)hf.data(), hf.size())) ||
-      (rc = db.upload(&d_tok, (const int*)tok, (size_t)rows)) || (rc = db.upload(&d_step, (const int*)&step, 1)))
-    return rc;
-  fwd::launch_embed(nullptr, d_tok, d_e, d_p, d_x, d_f, rows, d, d_step, pos_fixed, P, blk_n);
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipDeviceSynchronize());
-  if ((rc = hook_download(hx.data(), d_x, hx.size())) || (rc = hook_download(hf.data(), d_f, hf.size()))) return rc;
-  for (size_t i = 0; i < hx.size(); ++i) x[i] = (float)hx[i];
-  for (int r = 0; r < R16; ++r)   // fragment-major -> row-major (dec_kernels.hip: frag_off)
-    for (int k = 0; k < d; ++k)
-      x_frag[(size_t)r * d + k] =
-          (float)hf[((size_t)((r >> 4) * KS + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + (r & 15)) * 8 + (k & 7)];
-  return FW_OK;
-}
-
 int32_t fw_detect_language(fw_model* fm, const fw_tensor* enc_t, int32_t B, int32_t* out_lang_ids,
                            float* out_probs) {
   FW_CHECK_ARG(fm && enc_t && out_lang_ids && out_probs, "null argument");
@@ -1485,6 +1240,14 @@ __global__ void align_filter_kernel(const float* __restrict__ probs, const float
 }
 
 namespace fw {
+void launch_align_post(hipStream_t st, const float* probs, float* stats, int n_sel, int n_tok_cap, int T, int B,
+                       const int* n_tok, const int* nfr, int width, float* mat) {
+  dim3 g1((T + 127) / 128, n_sel, B);
+  align_stats_kernel<<<g1, 128, 0, st>>>(probs, n_sel, n_tok_cap, T, n_tok, nfr, stats);
+  dim3 g2((T + 127) / 128, n_tok_cap, B);
+  align_filter_kernel<<<g2, 128, 0, st>>>(probs, stats, n_sel, n_tok_cap, T, n_tok, nfr, width, mat);
+}
+
 // openai-whisper timing.dtw_cpu on cost = -matrix (N text rows x M frames)
 static void dtw_path(const float* mat, int ld, int N, int M, std::vector<int>& ti, std::vector<int>& fi) {
   std::vector<double> D((size_t)(N + 1) * (M + 1), INFINITY);
@@ -1683,13 +1446,7 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
     }
     pos += nb;
   }
-  {
-    dim3 g1((T + 127) / 128, n_sel, B);
-    align_stats_kernel<<<g1, 128, 0, st>>>(probs, n_sel, max_tok, T, ntok_dev, nfr_dev, stats);
-    dim3 g2((T + 127) / 128, max_tok, B);
-    align_filter_kernel<<<g2, 128, 0, st>>>(probs, stats, n_sel, max_tok, T, ntok_dev, nfr_dev, median_filter_width,
-                                             mat);
-  }
+  launch_align_post(st, probs, stats, n_sel, max_tok, T, B, ntok_dev, nfr_dev, median_filter_width, mat);
   std::vector<float> hmat((size_t)B * max_tok * T), htprob((size_t)B * max_tok);
   he = hipMemcpyAsync(hmat.data(), mat, hmat.size() * sizeof(float), hipMemcpyDeviceToHost, st);
   if (he == hipSuccess) he = hipMemcpyAsync(htprob.data(), tprob, htprob.size() * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -1721,44 +1478,4 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
     out_n_pairs[b] = np;
   }
   return FW_OK;
-}
-
-// Test hook: align_stats_kernel then align_filter_kernel with the grid shapes fw_align uses, on caller-provided
-// probabilities probs [B][n_sel][n_tok_cap][T], per-chunk token and frame counts and the median width.  mat
-// [B][n_tok_cap][T] is IN / OUT: the device buffer starts as the caller's values, so entries with tok >= n_tok[b] or
-// t >= nfr[b] show whether they were touched.  A frame whose probabilities are equal over the tokens has zero variance:
-// 1 / sqrt(0) = inf times a zero difference is NaN, in the kernel and in the oracle alike; tests keep the variance
-// positive and do not pin that case.
-extern "C" int32_t fw_test_align_post(fw_model* fm, const float* probs, int32_t B, int32_t n_sel, int32_t n_tok_cap,
-                                      int32_t T, const int32_t* n_tok, const int32_t* nfr, int32_t width, float* mat) {
-  FW_CHECK_ARG(fm && probs && n_tok && nfr && mat, "null argument");
-  FW_CHECK_ARG(B >= 1 && B <= 65535 && n_sel >= 1 && n_sel <= 65535 && n_tok_cap >= 1 && n_tok_cap <= 65535 && T >= 1 &&
-                   T <= (1 << 20), "bad geometry (B, n_sel, n_tok_cap in 1..65535, T >= 1)");
-  FW_CHECK_ARG(width >= 1 && width <= 15 && (width & 1), "median_filter_width must be odd and <= 15");
-  for (int b = 0; b < B; ++b) {
-    FW_CHECK_ARG(n_tok[b] >= 1 && n_tok[b] <= n_tok_cap, "n_tok[%d] = %d outside [1, %d]", b, n_tok[b], n_tok_cap);
-    FW_CHECK_ARG(nfr[b] >= 1 && nfr[b] <= T, "nfr[%d] = %d outside [1, %d]", b, nfr[b], T);
-  }
-  Model* m = &fm->impl;
-  FW_HIP(hipSetDevice(m->device));
-  HookBufs db;
-  const size_t n_probs = (size_t)B * n_sel * n_tok_cap * T, n_stats = (size_t)B * n_sel * T * 2,
-               n_mat = (size_t)B * n_tok_cap * T;
-  float *d_p, *d_s, *d_m;
-  int *d_nt, *d_nf;
-  int rc;
-  if ((rc = db.upload(&d_p, probs, n_probs)) || (rc = db.alloc(&d_s, n_stats)) ||
-      (rc = db.upload(&d_m, (const float*)mat, n_mat)) || (rc = db.upload(&d_nt, (const int*)n_tok, (size_t)B)) ||
-      (rc = db.upload(&d_nf, (const int*)nfr, (size_t)B)))
-    return rc;
-  FW_HIP(hipMemset(d_s, 0, n_stats * sizeof(float)));
-  {
-    dim3 g1((T + 127) / 128, n_sel, B);
-    align_stats_kernel<<<g1, 128, 0, nullptr>>>(d_p, n_sel, n_tok_cap, T, d_nt, d_nf, d_s);
-    dim3 g2((T + 127) / 128, n_tok_cap, B);
-    align_filter_kernel<<<g2, 128, 0, nullptr>>>(d_p, d_s, n_sel, n_tok_cap, T, d_nt, d_nf, width, d_m);
-  }
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipDeviceSynchronize());
-  return hook_download(mat, d_m, n_mat);
 }

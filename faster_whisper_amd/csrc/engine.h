@@ -1,7 +1,10 @@
 // Engine-internal structures of libfwamd.so (host side, C++17).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -32,6 +35,32 @@ void set_error(const char* fmt, ...);
       return FW_EINVAL;                \
     }                                  \
   } while (0)
+
+// ---- fp16 helpers (host) ----------------------------------------------------------------
+inline uint16_t f32_to_f16_bits(float f) {
+  half_t h = (half_t)f;  // round-to-nearest-even, same as the device cast
+  uint16_t u;
+  memcpy(&u, &h, 2);
+  return u;
+}
+inline float f16_bits_to_f32(uint16_t u) {
+  half_t h;
+  memcpy(&h, &u, 2);
+  return (float)h;
+}
+
+// int8_float16 weight row (K25, [CT2-ext] CTranslate2 convention): scale = 127 / absmax(row), q = rint(row * scale)
+// (round-half-even).  `row` is K fp16-rounded values; code k goes to q[at(k)] (row-major for the blob and the encoder GEMM,
+// fragment-major for the decoder linears); returns the DE-quantisation factor absmax / 127 (1 for an all-zero row).
+// The one statement of it: the weight packer and the test hooks that quantise a caller's W both call it.
+template <typename At>
+inline float quant_row_i8(const float* row, int K, int8_t* q, At&& at) {
+  float amax = 0.f;
+  for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(row[k]));
+  const float sc = amax > 0.f ? 127.0f / amax : 0.f;
+  for (int k = 0; k < K; ++k) q[at(k)] = (int8_t)lrintf(row[k] * sc);
+  return amax > 0.f ? amax / 127.0f : 1.0f;
+}
 
 // ---- weight blob (what travels over RCCL at load time) --------------------------------
 #define FW_BLOB_MAGIC "FWAMDBL1"
@@ -268,6 +297,11 @@ void gen_workspace_free(Model* m);
 int64_t gen_workspace_bytes(const Model* m, int lane_chunks, int self_ctx);
 int64_t cross_pool_bytes(const Model* m, int pool_chunks);
 void cross_pool_free(Model* m);
+// align's device post-processing on stream st: align_stats_kernel (standardise over tokens) then align_filter_kernel
+// (median over frames, mean over the n_sel heads) on probs [B][n_sel][n_tok_cap][T] -> mat [B][n_tok_cap][T]; stats is
+// scratch of [B][n_sel][T][2] floats.  fw_align and its test hook launch the pair through here.
+void launch_align_post(hipStream_t st, const float* probs, float* stats, int n_sel, int n_tok_cap, int T, int B,
+                       const int* n_tok, const int* nfr, int width, float* mat);
 inline Model* decoder_of(Model* m) { return m->decoder ? m->decoder : m; }
 inline int n_lanes_of(const Model* m) {
   int n = 1;

@@ -1,6 +1,6 @@
 // libfwamd.so — host side of the MI355X Whisper engine: C ABI (include/fwamd.h), weight
-// packing/upload, workspaces, the log-mel + encoder pipeline and the kernel test hooks.
-// The decoder / generate / align side lives in decoder.hip.
+// packing/upload, workspaces and the log-mel + encoder pipeline.
+// The decoder / generate / align side lives in decoder.hip, the kernel test and bench hooks in hooks.hip.
 //
 // Reference interfaces replaced here (faster_whisper/transcribe.py): the
 // ctranslate2.models.Whisper constructor (:689-698), .encode (:1400), the
@@ -95,14 +95,6 @@ void prof_collect(Model* m) {
   }
 }
 
-// ---------------------------------------------------------------- fp16 helpers (host)
-static inline uint16_t f32_to_f16_bits(float f) {
-  half_t h = (half_t)f;  // round-to-nearest-even, same as the device cast
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-
 // ---------------------------------------------------------------- blob packing
 struct PackItem {
   std::string name;
@@ -119,12 +111,6 @@ struct PackItem {
     return dtype == 1 ? (int64_t)data.size() * 2 : dtype == 2 ? (int64_t)qdata.size() : (int64_t)fdata.size() * 4;
   }
 };
-
-static inline float f16_bits_to_f32(uint16_t u) {
-  half_t h;
-  memcpy(&h, &u, 2);
-  return (float)h;
-}
 
 static const fw_weight* find_w(const fw_weight* w, int n, const std::string& name) {
   for (int i = 0; i < n; ++i)
@@ -291,14 +277,8 @@ static int pack_blob(const fw_config* cfg, const fw_weight* w, int nw, int compu
     ws.fdata.resize(N);
     std::vector<float> row(K);
     for (int n = 0; n < N; ++n) {
-      float amax = 0.f;
-      for (int k = 0; k < K; ++k) {
-        row[k] = f16_bits_to_f32(f32_to_f16_bits(w_at(W, (int64_t)n * K + k)));
-        amax = std::max(amax, fabsf(row[k]));
-      }
-      const float sc = amax > 0.f ? 127.0f / amax : 0.f;
-      for (int k = 0; k < K; ++k) wq.qdata[(size_t)n * K + k] = (int8_t)lrintf(row[k] * sc);
-      ws.fdata[n] = amax > 0.f ? amax / 127.0f : 1.0f;
+      for (int k = 0; k < K; ++k) row[k] = f16_bits_to_f32(f32_to_f16_bits(w_at(W, (int64_t)n * K + k)));
+      ws.fdata[n] = quant_row_i8(row.data(), K, wq.qdata.data(), [&](int k) { return (size_t)n * K + k; });
     }
     items.push_back(std::move(wq)); items.push_back(std::move(ws));
     return FW_OK;
@@ -1666,1011 +1646,6 @@ int32_t fw_dev_upload(fw_model* fm, void* dst_dev, const void* src_host, int64_t
   FW_CHECK_ARG(fm && dst_dev && src_host && bytes >= 0, "bad argument");
   FW_HIP(hipSetDevice(fm->impl.device));
   FW_HIP(hipMemcpy(dst_dev, src_host, (size_t)bytes, hipMemcpyHostToDevice));
-  return FW_OK;
-}
-
-// ---------------------------------------------------------------- kernel test hooks
-// (the model's streams are non-blocking streams: a buffer a hook clears before a launch is cleared with hipMemsetAsync ON the
-//  launch's stream — a hipMemset on the null stream is not ordered against the kernel and may land after its stores)
-static int upload_f16(Model* m, const float* src, size_t n, half_t** dst) {
-  int rc = dev_alloc_t(dst, n);
-  if (rc) return rc;
-  std::vector<uint16_t> tmp(n);
-  for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_f16_bits(src[i]);
-  FW_HIP(hipMemcpy(*dst, tmp.data(), n * 2, hipMemcpyHostToDevice));
-  return FW_OK;
-}
-static int download_f16(Model* m, const half_t* src, size_t n, float* dst) {
-  std::vector<uint16_t> tmp(n);
-  FW_HIP(hipStreamSynchronize(m->stream));
-  FW_HIP(hipMemcpy(tmp.data(), src, n * 2, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i) {
-    half_t h;
-    memcpy(&h, &tmp[i], 2);
-    dst[i] = (float)h;
-  }
-  return FW_OK;
-}
-
-// fragment-major position of key mm, column n (head n / 64) inside one encoder chunk's cross-attention K (vt = false) or
-// V^T (vt = true) block of [H][kvp * 64] halves: the layout the projection GEMM's epilogue writes (gemm.hip) and
-// dec_cross_attn_kernel / dec_cross_probs_kernel read (dec_kernels.hip, K14).  The one host statement of it: the gemm
-// hook un-permutes through it, the cross-attention hooks permute through it.
-static inline size_t cross_kv_frag_pos(bool vt, int kvp, int mm, int n) {
-  const int c = n & 63, r = mm & 31;
-  const size_t head = (size_t)(n >> 6) * kvp * 64;
-  return vt ? head + ((size_t)((mm >> 5) * 4 + (c >> 4)) * 64 + ((mm >> 3) & 3) * 16 + (c & 15)) * 8 + (mm & 7)
-            : head + ((size_t)((mm >> 5) * 4 + 2 * ((r >> 2) & 1) + (c >> 5)) * 64 + ((c >> 3) & 3) * 16 + (((r >> 3) << 2) | (r & 3))) * 8 + (c & 7);
-}
-
-// per-output-row int8 quantisation of fp16-rounded W [N][K], exactly like the weight packer
-static void quant_w_rows_host(const float* W, int N, int K, int8_t* wq, float* ws) {
-  for (int n = 0; n < N; ++n) {
-    float amax = 0.f;
-    for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k]))));
-    const float sc = amax > 0.f ? 127.0f / amax : 0.f;
-    for (int k = 0; k < K; ++k)
-      wq[(size_t)n * K + k] = (int8_t)lrintf(f16_bits_to_f32(f32_to_f16_bits(W[(size_t)n * K + k])) * sc);
-    ws[n] = amax > 0.f ? amax / 127.0f : 1.0f;
-  }
-}
-
-int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* bias, const float* residual,
-                     int32_t M, int32_t N, int32_t K, int32_t act_gelu, int32_t use_int8, float* out) {
-  FW_CHECK_ARG(fm && A && W && out, "null argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  half_t *dA = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr;
-  int rc;
-  if ((rc = upload_f16(m, A, (size_t)M * K, &dA))) return rc;
-  if ((rc = upload_f16(m, W, (size_t)N * K, &dW))) return rc;
-  if (bias && (rc = upload_f16(m, bias, N, &dB))) return rc;
-  if (residual && (rc = upload_f16(m, residual, (size_t)M * N, &dR))) return rc;
-  if ((rc = dev_alloc_t(&dC, (size_t)M * N))) return rc;
-  LinearW L{dW, dB, nullptr, nullptr, nullptr, nullptr, N, K};
-  int8_t* dWq = nullptr;
-  float* dWs = nullptr;
-  if (use_int8) {
-    // quantise W per output row exactly like the weight packer, run the int8 path
-    if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || (int64_t)M * K > (int64_t)m->max_batch * 1500 * 4 * m->cfg.d_model ||
-        M > m->max_batch * 1500) {
-      set_error("int8 gemm test needs an int8_float16 model and M*K within its quantisation workspace");
-      return FW_EINVAL;
-    }
-    std::vector<int8_t> wq((size_t)N * K);
-    std::vector<float> ws(N);
-    quant_w_rows_host(W, N, K, wq.data(), ws.data());
-    if ((rc = dev_alloc_t(&dWq, wq.size()))) return rc;
-    if ((rc = dev_alloc_t(&dWs, ws.size()))) return rc;
-    FW_HIP(hipMemcpy(dWq, wq.data(), wq.size(), hipMemcpyHostToDevice));
-    FW_HIP(hipMemcpy(dWs, ws.data(), ws.size() * sizeof(float), hipMemcpyHostToDevice));
-    L.wq = dWq; L.wscale = dWs;
-    if (act_gelu >= 2)
-      rc = run_linear_i8(m, L, dA, nullptr, dC, M, 0, nullptr, 0, 0, M, 1, act_gelu - 2, true, 0);
-    else
-      rc = run_linear_i8(m, L, dA, nullptr, dC, N, 0, dR, N, 0, M, 1, act_gelu, false, 0);
-  } else if (act_gelu == 8 || act_gelu == 9) {
-    // the cross-attention K (8) / V^T (9) projection epilogues: output MFMA-fragment-major per 64-column head
-    // (gemm.hip), un-permuted here into out [M][N]; the padded keys of the last 32-key group must stay zero
-    const bool vt = act_gelu == 9;
-    if (N % 64 || residual) { set_error("fragment-major gemm test: N %% 64 == 0, no residual"); return FW_EINVAL; }
-    const int kvp = (M + 31) / 32 * 32, H = N / 64;
-    half_t* dF = nullptr;
-    if ((rc = dev_alloc_t(&dF, (size_t)H * kvp * 64))) return rc;
-    FW_HIP(hipMemsetAsync(dF, 0, (size_t)H * kvp * 64 * sizeof(half_t), m->stream));
-    rc = vt ? run_linear(m, L, dA, K, 0, dF, kvp, 0, nullptr, 0, 0, M, 1, 0, true, kvp)
-            : run_linear(m, L, dA, K, 0, dF, N, 0, nullptr, 0, 0, M, 1, 0, false, kvp);
-    std::vector<float> hf((size_t)H * kvp * 64);
-    if (!rc) rc = download_f16(m, dF, hf.size(), hf.data());
-    (void)hipFree(dF);
-    if (!rc) {
-      for (int mm = 0; mm < kvp && !rc; ++mm)
-        for (int n = 0; n < N; ++n) {
-          const size_t off = cross_kv_frag_pos(vt, kvp, mm, n);
-          if (mm < M) out[(size_t)mm * N + n] = hf[off];
-          else if (hf[off] != 0.f) { set_error("fragment-major epilogue wrote the padded key %d", mm); rc = FW_ERUNTIME; break; }
-        }
-    }
-    for (half_t* p : {dA, dW, dB, dR, dC})
-      if (p) (void)hipFree(p);
-    return rc;
-  } else if (act_gelu >= 2) {
-    // transposed-output mode: out is [N][M]
-    rc = run_linear(m, L, dA, K, 0, dC, M, 0, nullptr, 0, 0, M, 1, act_gelu - 2, true);
-  } else {
-    rc = run_linear(m, L, dA, K, 0, dC, N, 0, dR, N, 0, M, 1, act_gelu, false);
-  }
-  if (!rc) rc = download_f16(m, dC, (size_t)M * N, out);
-  for (half_t* p : {dA, dW, dB, dR, dC})
-    if (p) (void)hipFree(p);
-  if (dWq) (void)hipFree(dWq);
-  if (dWs) (void)hipFree(dWs);
-  return rc;
-}
-
-// fragment-major position of element (row, k) of a [rows][K] operand: 16-row tiles x k-steps of KE elements, the
-// 16 bytes of lane l = 16*((k / (KE/4)) % 4) + row % 16 contiguous (dec_kernels.hip)
-static inline size_t frag_pos(int64_t row, int64_t k, int64_t K, int KE) {
-  const int OCT = KE / 4;
-  return (size_t)((((row >> 4) * (K / KE) + k / KE) * 64 + ((k / OCT) & 3) * 16 + (row & 15)) * OCT + (k % OCT));
-}
-
-int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const float* bias, const float* ln_g,
-                           const float* ln_b, const float* res, int32_t R, int32_t N, int32_t K, int32_t act,
-                           int32_t use_int8, float* out, float* out_from_frag) {
-  FW_CHECK_ARG(fm && x && W && out && out_from_frag, "null argument");
-  FW_CHECK_ARG(R >= 1 && N % 32 == 0 && K % 64 == 0, "need R >= 1, N %% 32 == 0, K %% 64 == 0");
-  FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr), "ln_g and ln_b go together");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  hipStream_t st = m->stream;
-  const int R16 = (R + 15) / 16 * 16;
-  auto h = [](float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); };
-  std::vector<void*> owned;
-  auto up = [&](const void* src, size_t bytes, void** dst) -> int {
-    int rc = dev_alloc(dst, bytes);
-    if (rc) return rc;
-    owned.push_back(*dst);
-    FW_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return FW_OK;
-  };
-  auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-  int rc = FW_OK;
-  half_t *d_res = nullptr, *d_bias = nullptr, *d_out = nullptr, *d_of = nullptr;
-  std::vector<uint16_t> tmp;
-  if (res) {
-    tmp.resize((size_t)R * N);
-    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = f32_to_f16_bits(res[i]);
-    if ((rc = up(tmp.data(), tmp.size() * 2, (void**)&d_res))) { cleanup(); return rc; }
-  }
-  if ((rc = dev_alloc_t(&d_out, (size_t)R * N))) { cleanup(); return rc; }
-  owned.push_back(d_out);
-  if ((rc = dev_alloc_t(&d_of, (size_t)R16 * N))) { cleanup(); return rc; }
-  owned.push_back(d_of);
-  FW_HIP(hipMemsetAsync(d_of, 0, (size_t)R16 * N * 2, st));
-  if (use_int8 == 1) {
-    if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || ln_g) {
-      cleanup();
-      set_error("int8 decoder-linear test needs an int8_float16 model and no LayerNorm");
-      return FW_EINVAL;
-    }
-    std::vector<int8_t> wq((size_t)N * K);
-    std::vector<float> ws(N);
-    for (int n = 0; n < N; ++n) {
-      float amax = 0.f;
-      for (int k = 0; k < K; ++k) amax = std::max(amax, fabsf(h(W[(size_t)n * K + k])));
-      const float sc = amax > 0.f ? 127.0f / amax : 0.f;
-      for (int k = 0; k < K; ++k) wq[frag_pos(n, k, K, 64)] = (int8_t)lrintf(h(W[(size_t)n * K + k]) * sc);
-      ws[n] = amax > 0.f ? amax / 127.0f : 1.0f;
-    }
-    int8_t *d_wq = nullptr, *d_xq = nullptr;
-    float *d_ws = nullptr, *d_xs = nullptr;
-    half_t* d_x = nullptr;
-    tmp.resize((size_t)R * K);
-    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = f32_to_f16_bits(x[i]);
-    if ((rc = up(wq.data(), wq.size(), (void**)&d_wq)) || (rc = up(ws.data(), ws.size() * 4, (void**)&d_ws)) ||
-        (rc = up(tmp.data(), tmp.size() * 2, (void**)&d_x))) { cleanup(); return rc; }
-    if (bias) {
-      tmp.resize(N);
-      for (int n = 0; n < N; ++n) tmp[n] = f32_to_f16_bits(bias[n]);
-      if ((rc = up(tmp.data(), (size_t)N * 2, (void**)&d_bias))) { cleanup(); return rc; }
-    }
-    if ((rc = dev_alloc_t(&d_xq, (size_t)R16 * K))) { cleanup(); return rc; }
-    owned.push_back(d_xq);
-    if ((rc = dev_alloc_t(&d_xs, (size_t)R16))) { cleanup(); return rc; }
-    owned.push_back(d_xs);
-    FW_HIP(hipMemsetAsync(d_xq, 0, (size_t)R16 * K, st));
-    fwk::launch_quant_rows(st, d_x, K, nullptr, nullptr, d_xq, d_xs, R, K, 1);
-    if (fwd::launch_dec_gemm_frag_i8(st, d_xq, d_xs, d_wq, d_ws, d_bias, d_res, N, d_out, N, R, N, K, act) != 0) {
-      cleanup();
-      set_error("int8 decoder linear: unsupported shape R=%d N=%d K=%d", R, N, K);
-      return FW_ERUNTIME;
-    }
-    rc = download_f16(m, d_out, (size_t)R * N, out);
-    if (!rc) memcpy(out_from_frag, out, (size_t)R * N * sizeof(float));
-    cleanup();
-    return rc;
-  }
-  // fp16: fold the LayerNorm exactly like the weight packer (add_folded)
-  std::vector<uint16_t> wf((size_t)N * K), xf((size_t)R16 * K, 0);
-  std::vector<float> s1(N, 0.f), cf(N, 0.f);
-  for (int n = 0; n < N; ++n) {
-    double a1 = 0.0, ac = 0.0;
-    for (int k = 0; k < K; ++k) {
-      const float wv = h(W[(size_t)n * K + k]);
-      const uint16_t wg = ln_g ? f32_to_f16_bits(wv * h(ln_g[k])) : f32_to_f16_bits(wv);
-      wf[frag_pos(n, k, K, 32)] = wg;
-      a1 += (double)f16_bits_to_f32(wg);
-      if (ln_g) ac += (double)wv * (double)h(ln_b[k]);
-    }
-    if (bias) ac += (double)h(bias[n]);
-    s1[n] = (float)a1;
-    cf[n] = (float)ac;
-  }
-  for (int r = 0; r < R; ++r)
-    for (int k = 0; k < K; ++k) xf[frag_pos(r, k, K, 32)] = f32_to_f16_bits(x[(size_t)r * K + k]);
-  half_t *d_wf = nullptr, *d_xf = nullptr;
-  float *d_s1 = nullptr, *d_cf = nullptr;
-  if ((rc = up(wf.data(), wf.size() * 2, (void**)&d_wf)) || (rc = up(xf.data(), xf.size() * 2, (void**)&d_xf))) {
-    cleanup();
-    return rc;
-  }
-  if (ln_g) {
-    if ((rc = up(s1.data(), (size_t)N * 4, (void**)&d_s1)) || (rc = up(cf.data(), (size_t)N * 4, (void**)&d_cf))) {
-      cleanup();
-      return rc;
-    }
-  } else if (bias) {
-    tmp.resize(N);
-    for (int n = 0; n < N; ++n) tmp[n] = f32_to_f16_bits(bias[n]);
-    if ((rc = up(tmp.data(), (size_t)N * 2, (void**)&d_bias))) { cleanup(); return rc; }
-  }
-  // use_int8 >= 10: the GEMM-shaped kernel of merged runs (dec_gemm_big_kernel), workgroup shape use_int8 - 10,
-  // whatever the row count; 5: the skinny kernel whatever the row count (the reference of the bit-identity test).
-  const int lr =
-      use_int8 >= 10 ? fwd::launch_dec_gemm_big(st, use_int8 - 10, d_xf, d_wf, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-      : use_int8 == 5 ? fwd::launch_dec_gemm_skinny(st, d_xf, d_wf, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-      : (use_int8 == 6 || use_int8 == 7) ? fwd::launch_dec_gemm_skinny_tiles(st, use_int8 - 5, d_xf, d_wf, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-                      : fwd::launch_dec_gemm_frag(st, d_xf, d_wf, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act);
-  if (lr != 0) {
-    cleanup();
-    set_error("decoder linear: unsupported shape R=%d N=%d K=%d", R, N, K);
-    return FW_ERUNTIME;
-  }
-  rc = download_f16(m, d_out, (size_t)R * N, out);
-  std::vector<float> of((size_t)R16 * N);
-  if (!rc) rc = download_f16(m, d_of, (size_t)R16 * N, of.data());
-  if (!rc)
-    for (int r = 0; r < R; ++r)
-      for (int n = 0; n < N; ++n) out_from_frag[(size_t)r * N + n] = of[frag_pos(r, n, N, 32)];
-  cleanup();
-  return rc;
-}
-
-int32_t fw_dec_big_min_rows(void) { return fwd::dec_big_min_rows(); }
-int32_t fw_dec_big_min_rows_of(int32_t role, int32_t compute_type) { return fwd::dec_big_min_rows_of(role, compute_type); }
-
-// process-wide measurement knobs (A/B inside one process: profiles/gemm_bench.py); 1: encoder GEMM tile order
-int32_t fw_test_knob(int32_t id, int32_t value) {
-  FW_CHECK_ARG(id == 1 || id == 2 || id == 4 || id == 5 || id == 6 || id == 7, "unknown knob %d", id);
-  if (id == 6) { set_cross_kv_layered(value); return FW_OK; }
-  if (id == 7) { fwd::set_cross_attn_regs(value); return FW_OK; }
-  if (id == 1) fwk::g_gemm_order.store(value);
-  else if (id == 5) fwk::g_gemm_vt_stage.store(value);
-  else if (id == 2) fwd::set_self_attn_form(value);
-  else set_pos_blocks(value);
-  return FW_OK;
-}
-
-// host-only: the run size an idle two-lane decode group leads with (decoder.hip: idle_lead_chunks); needs no device
-int64_t fw_test_idle_lead_chunks(int64_t queued, int32_t n_queued, int32_t encoding, int64_t want, int32_t max_batch) {
-  return idle_lead_chunks(queued, n_queued, encoding, want, max_batch);
-}
-
-int32_t fw_test_dec_logits(fw_model* fm, const float* x, int32_t R, float* out) {
-  FW_CHECK_ARG(fm && x && out && R >= 1, "bad argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  hipStream_t st = m->stream;
-  const int d = m->cfg.d_model, V = m->cfg.n_vocab, R16 = (R + 15) / 16 * 16;
-  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
-  std::vector<uint16_t> xh((size_t)R16 * d, 0);
-  for (int r = 0; r < R; ++r)
-    for (int k = 0; k < d; ++k)
-      xh[i8 ? (size_t)r * d + k : frag_pos(r, k, d, 32)] = f32_to_f16_bits(x[(size_t)r * d + k]);
-  half_t* d_x = nullptr;
-  int8_t* d_xq = nullptr;
-  float *d_xs = nullptr, *d_out = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (void* p : {(void*)d_x, (void*)d_xq, (void*)d_xs, (void*)d_out}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc_t(&d_x, xh.size())) || (rc = dev_alloc_t(&d_out, (size_t)R * V))) { cleanup(); return rc; }
-  FW_HIP(hipMemcpy(d_x, xh.data(), xh.size() * 2, hipMemcpyHostToDevice));
-  int lr;
-  if (i8) {
-    if ((rc = dev_alloc_t(&d_xq, (size_t)R16 * d)) || (rc = dev_alloc_t(&d_xs, (size_t)R16))) { cleanup(); return rc; }
-    FW_HIP(hipMemsetAsync(d_xq, 0, (size_t)R16 * d, st));
-    fwk::launch_quant_rows(st, d_x, d, m->dec_ln.g, m->dec_ln.b, d_xq, d_xs, R, d, 1);
-    lr = fwd::launch_dec_logits(st, true, d_xq, d_xs, m->logits.wq, m->logits.wscale, nullptr, nullptr, d_out, V, R, V, d);
-  } else {
-    lr = fwd::launch_dec_logits(st, false, d_x, nullptr, m->logits.w, nullptr, m->logits.s1, m->logits.cf, d_out, V, R, V,
-                                d);
-  }
-  hipError_t he = hipSuccess;
-  if (lr == 0) he = hipMemcpyAsync(out, d_out, (size_t)R * V * sizeof(float), hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess) he = hipStreamSynchronize(st);
-  cleanup();
-  if (lr != 0 || he != hipSuccess) {
-    set_error("logits projection test failed: %s", lr ? "unsupported shape" : hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  return FW_OK;
-}
-
-// Micro-benchmark of the decoder linear kernel's tile shapes (profiles/dec_linear_bench.py): `iters` back-to-back
-// launches on one stream over a ROTATING set of weight matrices larger than L2 + MALL (as in a decode step, where
-// 1.5 GB of weights pass between two uses of the same matrix); us_out = mean microseconds per launch.
-int32_t fw_bench_dec_linear(fw_model* fm, int32_t R, int32_t N, int32_t K, int32_t lnf, int32_t variant, int32_t iters,
-                            float* us_out) {
-  FW_CHECK_ARG(fm && us_out && R > 0 && N > 0 && K > 0 && iters > 0, "bad argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const size_t wn = (size_t)N * K;
-  const int copies = (int)std::max<size_t>(2, ((size_t)640 << 20) / (wn * 2));
-  const size_t rp = ((size_t)R + 15) / 16 * 16;
-  half_t *dW = nullptr, *dX = nullptr, *dO = nullptr, *dB = nullptr;
-  float *dS = nullptr, *dC = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (void* p : {(void*)dW, (void*)dX, (void*)dO, (void*)dB, (void*)dS, (void*)dC}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc_t(&dW, wn * copies)) || (rc = dev_alloc_t(&dX, rp * K)) || (rc = dev_alloc_t(&dO, rp * N)) ||
-      (rc = dev_alloc_t(&dB, (size_t)N)) || (rc = dev_alloc_t(&dS, (size_t)N)) || (rc = dev_alloc_t(&dC, (size_t)N))) {
-    cleanup();
-    return rc;
-  }
-  {   // pseudo-random operands in [-1, 1) (constant fills clock the chip up: MI355X_MICROARCH.md, DVFS)
-    std::vector<uint16_t> h(std::max(wn, rp * (size_t)K));
-    uint32_t sd = 2463534242u;
-    for (auto& v : h) { sd = sd * 1664525u + 1013904223u; v = f32_to_f16_bits(((int)(sd >> 16) % 2001 - 1000) * 1e-3f); }
-    for (int c = 0; c < copies; ++c) FW_HIP(hipMemcpy(dW + (size_t)c * wn, h.data(), wn * 2, hipMemcpyHostToDevice));
-    FW_HIP(hipMemcpy(dX, h.data(), rp * K * 2, hipMemcpyHostToDevice));
-  }
-  FW_HIP(hipMemset(dB, 0, (size_t)N * 2));
-  FW_HIP(hipMemset(dS, 0, (size_t)N * 4));
-  FW_HIP(hipMemset(dC, 0, (size_t)N * 4));
-  hipEvent_t e0, e1;
-  FW_HIP(hipEventCreate(&e0));
-  FW_HIP(hipEventCreate(&e1));
-  hipStream_t st = m->stream;
-  int lr = 0;
-  for (int i = 0; i < 4 && lr == 0; ++i)
-    lr = fwd::launch_dec_gemm_frag_variant(st, variant, lnf != 0, dX, dW + (size_t)(i % copies) * wn, dB, dS, dC, dO, R, N, K);
-  FW_HIP(hipEventRecord(e0, st));
-  for (int i = 0; i < iters && lr == 0; ++i)
-    lr = fwd::launch_dec_gemm_frag_variant(st, variant, lnf != 0, dX, dW + (size_t)(i % copies) * wn, dB, dS, dC, dO, R, N, K);
-  FW_HIP(hipEventRecord(e1, st));
-  hipError_t he = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  cleanup();
-  if (lr != 0) { set_error("fw_bench_dec_linear: unsupported shape / variant"); return FW_EINVAL; }
-  if (he != hipSuccess) { set_error("fw_bench_dec_linear: %s", hipGetErrorString(he)); return FW_ENODEV; }
-  *us_out = ms * 1000.f / (float)iters;
-  return FW_OK;
-}
-
-// measurement hook (profiles/gemm_bench.py): the encoder GEMM on device-resident pseudo-random operands,
-// `iters` launches between two events.  lda = K + a_pad, ldw = K + w_pad elements (stride experiments).
-int32_t fw_bench_gemm(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t a_pad, int32_t w_pad,
-                      int32_t trans, int32_t iters, float* ms_out) {
-  FW_CHECK_ARG(fm && ms_out && M > 0 && N > 0 && K > 0 && batch > 0 && iters > 0, "bad argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
-  const int64_t lda = K + a_pad, ldw = K + w_pad;
-  const size_t es = i8 ? 1 : 2;
-  // transposed output: Ct[z][n][m] with the row stride the encoder's V^T has (keys padded to a multiple of 64: t_pad)
-  const int64_t ldct = (M + 63) / 64 * 64;
-  const size_t na = (size_t)batch * M * lda, nw = (size_t)N * ldw,
-               nc = trans ? (size_t)batch * N * ldct : (size_t)batch * M * N;
-  void *dA = nullptr, *dW = nullptr;
-  half_t* dC = nullptr;
-  float *dsa = nullptr, *dsw = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (void* p : {dA, dW, (void*)dC, (void*)dsa, (void*)dsw}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc(&dA, na * es)) || (rc = dev_alloc(&dW, nw * es)) || (rc = dev_alloc_t(&dC, nc))) { cleanup(); return rc; }
-  {
-    std::vector<uint16_t> h(std::max(na, nw));
-    uint32_t st = 12345u;
-    for (auto& v : h) { st = st * 1664525u + 1013904223u; v = f32_to_f16_bits(((int)(st >> 16) % 2001 - 1000) * 1e-3f); }
-    FW_HIP(hipMemcpy(dA, h.data(), na * es, hipMemcpyHostToDevice));
-    FW_HIP(hipMemcpy(dW, h.data(), nw * es, hipMemcpyHostToDevice));
-  }
-  if (i8) {
-    if ((rc = dev_alloc_t(&dsa, (size_t)batch * M)) || (rc = dev_alloc_t(&dsw, (size_t)N))) { cleanup(); return rc; }
-    FW_HIP(hipMemset(dsa, 0, (size_t)batch * M * 4));
-    FW_HIP(hipMemset(dsw, 0, (size_t)N * 4));
-  }
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = (const half_t*)dA; p.lda = lda; p.a_bstride = (int64_t)M * lda;
-  p.W = (const half_t*)dW; p.ldw = ldw;
-  p.C = dC; p.ldc = trans ? ldct : N; p.c_bstride = trans ? (int64_t)N * ldct : (int64_t)M * N;
-  p.M = M; p.N = N; p.K = K;
-  p.a_scale = dsa; p.as_bstride = M; p.w_scale = dsw;
-  hipEvent_t e0, e1;
-  FW_HIP(hipEventCreate(&e0));
-  FW_HIP(hipEventCreate(&e1));
-  int lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);   // warm-up
-  FW_HIP(hipEventRecord(e0, m->stream));
-  for (int i = 0; i < iters && lr == 0; ++i) lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);
-  FW_HIP(hipEventRecord(e1, m->stream));
-  hipError_t he = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  cleanup();
-  if (lr != 0 || he != hipSuccess) {
-    set_error("gemm bench failed: %s", lr ? "unsupported shape" : hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  *ms_out = ms / (float)iters;
-  return FW_OK;
-}
-
-// pseudo-random fp16 fill in [-1, 1) of a device buffer of n halves, staged through `h` (constant fills clock the chip up)
-static int bench_fill(half_t* dst, size_t n, std::vector<uint16_t>& h, uint32_t seed) {
-  if (h.size() < n) h.resize(n);
-  for (size_t i = 0; i < n; ++i) { seed = seed * 1664525u + 1013904223u; h[i] = f32_to_f16_bits(((int)(seed >> 16) % 2001 - 1000) * 1e-3f); }
-  FW_HIP(hipMemcpy(dst, h.data(), n * 2, hipMemcpyHostToDevice));
-  return FW_OK;
-}
-
-// measurement hook (profiles/gemm_bench.py --epilogue): fw_bench_gemm with the epilogue the PRODUCT runs for the shape —
-// bias, GELU, residual as run_encoder passes them, or (n_layers > 1) the layered head-major cross-attention K / V^T
-// projection of ensure_cross_kv.  The residual is read from a set of buffers larger than L2 + MALL, rotated launch by
-// launch (res = 1), or from one [M][N] block shared by the chunks (res = 2: conv2's positional embedding).
-int32_t fw_bench_gemm_epi(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t lda_in, int32_t trans,
-                          int32_t bias, int32_t act, int32_t res, int32_t n_layers, int32_t iters, float* ms_out) {
-  FW_CHECK_ARG(fm && ms_out && M > 0 && N > 0 && K > 0 && batch > 0 && iters > 0 && n_layers >= 1, "bad argument");
-  FW_CHECK_ARG(res >= 0 && res <= 2 && !(res && (trans || n_layers > 1)), "residual: row-major single-layer output only");
-  Model* m = &fm->impl;
-  FW_CHECK_ARG(m->compute_type != FW_COMPUTE_INT8_FLOAT16, "float16 models only");
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const int64_t lda = lda_in > 0 ? lda_in : K;
-  const bool layered = n_layers > 1;
-  const int64_t kvp = (M + 31) / 32 * 32;                  // keys of a head, padded to whole 32-key groups (the pool's kvp)
-  const int64_t ldct = layered ? kvp : (M + 63) / 64 * 64;
-  const int64_t c_bs = layered ? (int64_t)N * kvp : (trans ? (int64_t)N * ldct : (int64_t)M * N);
-  const int64_t c_ls = c_bs * batch;
-  const size_t na = (size_t)batch * ((size_t)M * lda + K), nw = (size_t)N * K * n_layers, nc = (size_t)c_ls * n_layers;
-  const size_t nr1 = res == 1 ? (size_t)batch * M * N : (size_t)M * N;
-  const int copies = res == 1 ? (int)std::max<size_t>(2, ((size_t)640 << 20) / (nr1 * 2)) : 1;
-  half_t *dA = nullptr, *dW = nullptr, *dC = nullptr, *dB = nullptr, *dR = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (void* p : {(void*)dA, (void*)dW, (void*)dC, (void*)dB, (void*)dR}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc_t(&dA, na)) || (rc = dev_alloc_t(&dW, nw)) || (rc = dev_alloc_t(&dC, nc)) ||
-      (rc = dev_alloc_t(&dB, (size_t)N * n_layers)) || (res && (rc = dev_alloc_t(&dR, nr1 * copies)))) {
-    cleanup();
-    return rc;
-  }
-  {
-    std::vector<uint16_t> h;
-    if ((rc = bench_fill(dA, na, h, 12345u)) || (rc = bench_fill(dW, nw, h, 12345u)) ||
-        (rc = bench_fill(dB, (size_t)N * n_layers, h, 777u))) { cleanup(); return rc; }
-    if (res) {
-      if ((rc = bench_fill(dR, nr1, h, 4242u))) { cleanup(); return rc; }
-      for (int c = 1; c < copies; ++c) FW_HIP(hipMemcpy(dR + (size_t)c * nr1, dR, nr1 * 2, hipMemcpyDeviceToDevice));
-    }
-    FW_HIP(hipMemset(dC, 0, nc * 2));
-  }
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = dA; p.lda = lda; p.a_bstride = (int64_t)M * lda;
-  p.W = dW; p.ldw = K;
-  p.bias = bias ? dB : nullptr;
-  p.C = dC; p.ldc = layered ? (trans ? kvp : N) : (trans ? ldct : N); p.c_bstride = c_bs;
-  p.M = M; p.N = N; p.K = K;
-  p.act = act;
-  if (layered) {
-    p.head_rows = (int)kvp;
-    p.n_layers = n_layers; p.w_lstride = (int64_t)N * K; p.bias_lstride = N; p.c_lstride = c_ls;
-  }
-  p.ldr = N; p.r_bstride = res == 1 ? (int64_t)M * N : 0;
-  hipEvent_t e0, e1;
-  FW_HIP(hipEventCreate(&e0));
-  FW_HIP(hipEventCreate(&e1));
-  p.res = dR;
-  int lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);   // warm-up
-  FW_HIP(hipEventRecord(e0, m->stream));
-  for (int i = 0; i < iters && lr == 0; ++i) {
-    if (res) p.res = dR + (size_t)(i % copies) * nr1;
-    lr = fwk::launch_gemm(m->stream, p, batch, trans != 0);
-  }
-  FW_HIP(hipEventRecord(e1, m->stream));
-  hipError_t he = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  cleanup();
-  if (lr != 0 || he != hipSuccess) {
-    set_error("gemm epilogue bench failed: %s", lr ? "unsupported shape" : hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  *ms_out = ms / (float)iters;
-  return FW_OK;
-}
-
-// measurement hook (profiles/dec_linear_bench.py --epilogue): fw_bench_dec_linear with the epilogue a decode step runs —
-// act, and with res = 1 the residual added IN PLACE (res == out, as run_step passes g->x), outs bit 0 / 1: the row-major
-// / the fragment-major copy written.  Weights AND the in-place residual / output rows rotate over sets larger than
-// L2 + MALL.  variant 0: what a decode step launches for this row count; 5: the register-streaming kernel; 10 + cfg:
-// the GEMM-shaped kernel of merged runs.
-int32_t fw_bench_dec_linear_epi(fw_model* fm, int32_t R, int32_t N, int32_t K, int32_t lnf, int32_t variant, int32_t act,
-                                int32_t res, int32_t outs, int32_t iters, float* us_out) {
-  FW_CHECK_ARG(fm && us_out && R > 0 && N > 0 && K > 0 && iters > 0, "bad argument");
-  FW_CHECK_ARG((outs & 3) != 0 && (!res || (outs & 1)), "needs an output; the residual is the row-major output in place");
-  FW_CHECK_ARG(variant == 0 || variant == 5 || (variant >= 10 && variant <= 12), "unknown variant %d", variant);
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const size_t wn = (size_t)N * K;
-  const int copies = (int)std::max<size_t>(2, ((size_t)640 << 20) / (wn * 2));
-  const size_t rp = ((size_t)R + 15) / 16 * 16, on = rp * N;
-  const int ocopies = (int)std::max<size_t>(2, ((size_t)640 << 20) / (on * 2));
-  half_t *dW = nullptr, *dX = nullptr, *dO = nullptr, *dF = nullptr, *dB = nullptr;
-  float *dS = nullptr, *dC = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (void* p : {(void*)dW, (void*)dX, (void*)dO, (void*)dF, (void*)dB, (void*)dS, (void*)dC}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc_t(&dW, wn * copies)) || (rc = dev_alloc_t(&dX, rp * K)) || (rc = dev_alloc_t(&dO, on * ocopies)) ||
-      (rc = dev_alloc_t(&dF, on)) || (rc = dev_alloc_t(&dB, (size_t)N)) || (rc = dev_alloc_t(&dS, (size_t)N)) ||
-      (rc = dev_alloc_t(&dC, (size_t)N))) {
-    cleanup();
-    return rc;
-  }
-  {
-    std::vector<uint16_t> h;
-    if ((rc = bench_fill(dW, wn, h, 2463534242u)) || (rc = bench_fill(dX, rp * K, h, 2463534242u))) { cleanup(); return rc; }
-    for (int c = 1; c < copies; ++c) FW_HIP(hipMemcpy(dW + (size_t)c * wn, dW, wn * 2, hipMemcpyDeviceToDevice));
-  }
-  // (zero residual / bias / fold constants: an in-place residual that is re-read iters / ocopies times stays finite)
-  FW_HIP(hipMemset(dO, 0, on * ocopies * 2));
-  FW_HIP(hipMemset(dB, 0, (size_t)N * 2));
-  FW_HIP(hipMemset(dS, 0, (size_t)N * 4));
-  FW_HIP(hipMemset(dC, 0, (size_t)N * 4));
-  hipEvent_t e0, e1;
-  FW_HIP(hipEventCreate(&e0));
-  FW_HIP(hipEventCreate(&e1));
-  hipStream_t st = m->stream;
-  auto go = [&](int i) -> int {
-    const half_t* w = dW + (size_t)(i % copies) * wn;
-    half_t* o = dO + (size_t)(i % ocopies) * on;
-    half_t* op = (outs & 1) ? o : nullptr;
-    half_t* of = (outs & 2) ? dF : nullptr;
-    const half_t* r = res ? o : nullptr;
-    const half_t* b = lnf ? nullptr : dB;
-    const float *s1 = lnf ? dS : nullptr, *cf = lnf ? dC : nullptr;
-    if (variant >= 10) return fwd::launch_dec_gemm_big(st, variant - 10, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
-    if (variant == 5) return fwd::launch_dec_gemm_skinny(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
-    return fwd::launch_dec_gemm_frag(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
-  };
-  int lr = 0;
-  for (int i = 0; i < 4 && lr == 0; ++i) lr = go(i);
-  FW_HIP(hipEventRecord(e0, st));
-  for (int i = 0; i < iters && lr == 0; ++i) lr = go(i);
-  FW_HIP(hipEventRecord(e1, st));
-  hipError_t he = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  cleanup();
-  if (lr != 0) { set_error("fw_bench_dec_linear_epi: unsupported shape / variant"); return FW_EINVAL; }
-  if (he != hipSuccess) { set_error("fw_bench_dec_linear_epi: %s", hipGetErrorString(he)); return FW_ENODEV; }
-  *us_out = ms * 1000.f / (float)iters;
-  return FW_OK;
-}
-
-static int test_layernorm_impl(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
-                               int32_t frag, float* out) {
-  FW_CHECK_ARG(fm && x && g && b && out && rows >= 1, "null argument");
-  FW_CHECK_ARG(d % 128 == 0 && d >= 128 && d <= 1536, "d must be a multiple of 128 and <= 1536");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  half_t *dx = nullptr, *dg = nullptr, *db = nullptr, *dy = nullptr;
-  const size_t ny = (size_t)(frag ? (rows + 15) / 16 * 16 : rows) * d;   // the fragment-major form is whole 16-row tiles
-  int rc;
-  if ((rc = upload_f16(m, x, (size_t)rows * d, &dx))) return rc;
-  if ((rc = upload_f16(m, g, d, &dg))) return rc;
-  if ((rc = upload_f16(m, b, d, &db))) return rc;
-  if ((rc = dev_alloc_t(&dy, ny))) return rc;
-  FW_HIP(hipMemsetAsync(dy, 0, ny * sizeof(half_t), m->stream));   // (on the launch's stream: it is a non-blocking one)
-  fwk::launch_layernorm(m->stream, dx, dg, db, dy, rows, d, frag ? 1 : 0);
-  if (!frag) {
-    rc = download_f16(m, dy, (size_t)rows * d, out);
-  } else {
-    std::vector<float> yf(ny);
-    rc = download_f16(m, dy, ny, yf.data());
-    if (!rc)
-      for (int r = 0; r < rows; ++r)
-        for (int k = 0; k < d; ++k) out[(size_t)r * d + k] = yf[frag_pos(r, k, d, 32)];
-  }
-  for (half_t* p : {dx, dg, db, dy})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-int32_t fw_test_layernorm(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
-                          float* out) {
-  return test_layernorm_impl(fm, x, g, b, rows, d, 0, out);
-}
-int32_t fw_test_layernorm_frag(fw_model* fm, const float* x, const float* g, const float* b, int32_t rows, int32_t d,
-                               int32_t frag, float* out) {
-  return test_layernorm_impl(fm, x, g, b, rows, d, frag, out);
-}
-
-int32_t fw_test_quant_rows(fw_model* fm, const float* x, int32_t rows, int32_t d, int64_t ldx, const float* ln_g,
-                           const float* ln_b, int32_t frag, int8_t* xq, float* scale) {
-  FW_CHECK_ARG(fm && x && xq && scale && rows >= 1 && rows <= (1 << 20), "bad argument");
-  FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr), "ln_g and ln_b go together");
-  FW_CHECK_ARG(d >= 64 && d % 64 == 0 && d <= (ln_g ? 1536 : 5120), "d %% 64 == 0, d <= 1536 with LayerNorm, <= 5120 without");
-  FW_CHECK_ARG(ldx >= d && ldx % 8 == 0 && ldx <= (1 << 20), "ldx >= d, ldx %% 8 == 0");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const int R16 = (rows + 15) / 16 * 16;
-  half_t *dx = nullptr, *dg = nullptr, *db = nullptr;
-  int8_t* dq = nullptr;
-  float* ds = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)dx, (void*)dg, (void*)db, (void*)dq, (void*)ds}) if (p) (void)hipFree(p); };
-  int rc;
-  if ((rc = upload_f16(m, x, (size_t)(rows - 1) * ldx + d, &dx)) || (ln_g && (rc = upload_f16(m, ln_g, d, &dg))) ||
-      (ln_b && (rc = upload_f16(m, ln_b, d, &db))) || (rc = dev_alloc_t(&dq, (size_t)R16 * d)) ||
-      (rc = dev_alloc_t(&ds, (size_t)R16))) { cleanup(); return rc; }
-  std::vector<int8_t> hq((size_t)R16 * d);
-  hipError_t he = hipMemsetAsync(dq, 0, hq.size(), m->stream);     // (on the launch's stream: it is a non-blocking one)
-  if (he == hipSuccess) {
-    fwk::launch_quant_rows(m->stream, dx, ldx, dg, db, dq, ds, rows, d, frag ? 1 : 0);
-    he = hipStreamSynchronize(m->stream);
-  }
-  if (he == hipSuccess) he = hipMemcpy(hq.data(), dq, hq.size(), hipMemcpyDeviceToHost);
-  if (he == hipSuccess) he = hipMemcpy(scale, ds, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost);
-  cleanup();
-  if (he != hipSuccess) { set_error("fw_test_quant_rows: %s", hipGetErrorString(he)); return FW_ENODEV; }
-  for (int r = 0; r < rows; ++r)
-    for (int k = 0; k < d; ++k) xq[(size_t)r * d + k] = hq[frag ? frag_pos(r, k, d, 64) : (size_t)r * d + k];
-  return FW_OK;
-}
-
-int32_t fw_test_cross_kv_frag_index(int32_t vt, int32_t kvp, int32_t N, int64_t* idx) {
-  FW_CHECK_ARG(idx && kvp >= 32 && kvp % 32 == 0 && N >= 64 && N % 64 == 0, "need kvp %% 32 == 0, N %% 64 == 0");
-  for (int mm = 0; mm < kvp; ++mm)
-    for (int n = 0; n < N; ++n) idx[(size_t)mm * N + n] = (int64_t)cross_kv_frag_pos(vt != 0, kvp, mm, n);
-  return FW_OK;
-}
-
-int32_t fw_test_gemm_ex(fw_model* fm, const float* A, int64_t a_elems, int64_t lda, int64_t a_bstride, const float* W,
-                        const float* bias, const float* res, int64_t r_elems, int64_t ldr, int64_t r_bstride, float* C,
-                        int64_t c_elems, int64_t c_off, int64_t ldc, int64_t c_bstride, int64_t c_lstride, int32_t M,
-                        int32_t N, int32_t K, int32_t batch, int32_t n_layers, int32_t act, int32_t trans,
-                        int32_t head_rows, int32_t use_int8, const float* ln_g, const float* ln_b) {
-  FW_CHECK_ARG(fm && A && W && C, "null argument");
-  const int64_t dim_max = 1 << 20, cnt_max = 1 << 12, str_max = (int64_t)1 << 40;   // (no product below can overflow)
-  FW_CHECK_ARG(M >= 1 && N >= 1 && K >= 1 && M <= dim_max && N <= dim_max && K <= dim_max, "bad M / N / K");
-  FW_CHECK_ARG(batch >= 1 && n_layers >= 1 && batch <= cnt_max && n_layers <= cnt_max, "bad batch / n_layers");
-  for (int64_t v : {a_elems, lda, a_bstride, r_elems, ldr, r_bstride, c_elems, c_off, ldc, c_bstride, c_lstride})
-    FW_CHECK_ARG(v >= 0 && v <= str_max, "negative or oversized count / stride");
-  FW_CHECK_ARG(act == 0 || act == 1, "act is 0 or 1");
-  FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr) && (!ln_g || use_int8), "ln_g / ln_b: both, and only with use_int8");
-  const bool rowmajor = !trans && head_rows == 0;
-  FW_CHECK_ARG(!res || (rowmajor && n_layers == 1), "a residual needs the row-major single-layer form");
-  FW_CHECK_ARG(n_layers == 1 || (!use_int8 && act == 0), "the layered launch is fp16 without activation");
-  FW_CHECK_ARG(head_rows == 0 || (head_rows > 0 && head_rows % 32 == 0 && head_rows >= M && N % 64 == 0),
-               "fragment-major output: head_rows %% 32 == 0, head_rows >= M, N %% 64 == 0");
-  // 16-byte stores of the epilogues start from these offsets
-  FW_CHECK_ARG(c_off % 8 == 0 && c_lstride % 8 == 0, "c_off and c_lstride must be multiples of 8");
-  if (use_int8) FW_CHECK_ARG(lda == K && a_bstride == (int64_t)M * K, "int8: A is contiguous [batch * M][K]");
-  // ---- the furthest element the launch touches in each buffer (gemm.hip: rows are clamped to M - 1, every K tile is read
-  // whole, residual and output are touched only at m < M, n < N; a fragment-major key group is written as a whole) ----
-  const int64_t a_last = (int64_t)(batch - 1) * a_bstride + (int64_t)(M - 1) * lda + (K - 1);
-  FW_CHECK_ARG(a_last < a_elems, "the launch reads A[%lld], a_elems = %lld", (long long)a_last, (long long)a_elems);
-  if (res) {
-    const int64_t r_last = (int64_t)(batch - 1) * r_bstride + (int64_t)(M - 1) * ldr + (N - 1);
-    FW_CHECK_ARG(r_last < r_elems, "the launch reads res[%lld], r_elems = %lld", (long long)r_last, (long long)r_elems);
-  }
-  const int64_t chunk_last = head_rows > 0 ? (int64_t)(N / 64 - 1) * head_rows * 64 + (int64_t)((M - 1) / 32 + 1) * 2048 - 1
-                             : trans       ? (int64_t)(N - 1) * ldc + (M - 1)
-                                           : (int64_t)(M - 1) * ldc + (N - 1);
-  const int64_t c_last = c_off + (int64_t)(n_layers - 1) * c_lstride + (int64_t)(batch - 1) * c_bstride + chunk_last;
-  FW_CHECK_ARG(c_last < c_elems, "the launch writes C[%lld], c_elems = %lld", (long long)c_last, (long long)c_elems);
-
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  if (use_int8) {
-    const int64_t T = m->cfg.n_audio_ctx;
-    if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || (int64_t)batch * M * K > (int64_t)m->max_batch * T * 4 * m->cfg.d_model ||
-        (int64_t)batch * M > (int64_t)m->max_batch * T || (ln_g && K > 1536)) {
-      set_error("int8 gemm test needs an int8_float16 model, batch*M*K within its quantisation workspace, K <= 1536 with LayerNorm");
-      return FW_EINVAL;
-    }
-  }
-  FW_HIP(hipSetDevice(m->device));
-  std::vector<void*> owned;
-  auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-  auto up16 = [&](const float* src, size_t n, half_t** dst) -> int {
-    int rc = upload_f16(m, src, n, dst);
-    if (*dst) owned.push_back(*dst);
-    return rc;
-  };
-  half_t *dA = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr, *dG = nullptr, *dLb = nullptr;
-  const size_t nw = (size_t)n_layers * N * K;
-  int rc;
-  if ((rc = up16(A, (size_t)a_elems, &dA)) || (rc = up16(W, nw, &dW)) || (bias && (rc = up16(bias, (size_t)n_layers * N, &dB))) ||
-      (res && (rc = up16(res, (size_t)r_elems, &dR))) || (rc = up16(C, (size_t)c_elems, &dC)) ||
-      (ln_g && ((rc = up16(ln_g, K, &dG)) || (rc = up16(ln_b, K, &dLb))))) { cleanup(); return rc; }
-  LinearW L{dW, dB, nullptr, nullptr, nullptr, nullptr, N, K};
-  if (use_int8) {
-    std::vector<int8_t> wq(nw);
-    std::vector<float> ws(N);
-    quant_w_rows_host(W, N, K, wq.data(), ws.data());
-    int8_t* dWq = nullptr;
-    float* dWs = nullptr;
-    if ((rc = dev_alloc_t(&dWq, wq.size()))) { cleanup(); return rc; }
-    owned.push_back(dWq);
-    if ((rc = dev_alloc_t(&dWs, ws.size()))) { cleanup(); return rc; }
-    owned.push_back(dWs);
-    if (hipMemcpy(dWq, wq.data(), wq.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dWs, ws.data(), ws.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-      cleanup();
-      set_error("fw_test_gemm_ex: upload failed");
-      return FW_ENODEV;
-    }
-    L.wq = dWq; L.wscale = dWs;
-    LNW ln{dG, dLb};
-    rc = run_linear_i8(m, L, dA, ln_g ? &ln : nullptr, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act,
-                       trans != 0, head_rows);
-  } else if (n_layers > 1) {
-    rc = run_linear_layers(m, L, n_layers, (int64_t)N * K, bias ? N : 0, dA, lda, a_bstride, dC + c_off, ldc, c_bstride,
-                           c_lstride, M, batch, trans != 0, head_rows, nullptr);
-  } else {
-    rc = run_linear(m, L, dA, lda, a_bstride, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act, trans != 0,
-                    head_rows, nullptr);
-  }
-  if (!rc) rc = download_f16(m, dC, (size_t)c_elems, C);
-  cleanup();
-  return rc;
-}
-
-// q,k,v,out: float32 [B][T][H*64]
-int32_t fw_test_attention(fw_model* fm, const float* q, const float* k, const float* v, int32_t B, int32_t H,
-                          int32_t T, float* out) {
-  FW_CHECK_ARG(fm && q && k && v && out, "null argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const int d = H * 64, tp = (T + 63) / 64 * 64;
-  const size_t n = (size_t)B * T * d;
-  half_t *dq = nullptr, *dk = nullptr, *dvt = nullptr, *dout = nullptr;
-  int rc;
-  if ((rc = upload_f16(m, q, n, &dq))) return rc;
-  if ((rc = upload_f16(m, k, n, &dk))) return rc;
-  std::vector<float> vt((size_t)B * d * tp, 0.f);
-  for (int b = 0; b < B; ++b)
-    for (int t = 0; t < T; ++t)
-      for (int c = 0; c < d; ++c) vt[((size_t)b * d + c) * tp + t] = v[((size_t)b * T + t) * d + c];
-  if ((rc = upload_f16(m, vt.data(), vt.size(), &dvt))) return rc;
-  if ((rc = dev_alloc_t(&dout, n))) return rc;
-  fwk::launch_attn_enc(m->stream, dq, dk, d, (int64_t)T * d, dvt, tp, (int64_t)d * tp, dout, d, (int64_t)T * d, B, H,
-                       T);
-  rc = download_f16(m, dout, n, out);
-  for (half_t* p : {dq, dk, dvt, dout})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-
-// measurement hook (profiles/attn_bench.py): mean milliseconds of one launch of the encoder self-attention on
-// device-resident pseudo-random Q | K ([B][T][2d] as the fused projection leaves them) and V^T ([B][d][T padded]);
-// variant: reserved (0)
-int32_t fw_bench_attention(fw_model* fm, int32_t B, int32_t H, int32_t T, int32_t variant, int32_t iters, float* ms_out) {
-  FW_CHECK_ARG(fm && ms_out && B > 0 && H > 0 && T > 0 && iters > 0, "bad argument");
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  const int d = H * 64, tp = (T + 63) / 64 * 64;
-  const size_t nqk = (size_t)B * T * 2 * d, nvt = (size_t)B * d * tp, no = (size_t)B * T * d;
-  half_t *dqk = nullptr, *dvt = nullptr, *dout = nullptr;
-  int rc;
-  auto cleanup = [&]() { for (half_t* p : {dqk, dvt, dout}) if (p) (void)hipFree(p); };
-  if ((rc = dev_alloc_t(&dqk, nqk)) || (rc = dev_alloc_t(&dvt, nvt)) || (rc = dev_alloc_t(&dout, no))) { cleanup(); return rc; }
-  {
-    std::vector<uint16_t> h(std::max(nqk, nvt));
-    uint32_t sd = 777u;
-    for (auto& v : h) { sd = sd * 1664525u + 1013904223u; v = f32_to_f16_bits(((int)(sd >> 16) % 2001 - 1000) * 2e-3f); }
-    FW_HIP(hipMemcpy(dqk, h.data(), nqk * 2, hipMemcpyHostToDevice));
-    FW_HIP(hipMemcpy(dvt, h.data(), nvt * 2, hipMemcpyHostToDevice));
-  }
-  hipEvent_t e0, e1;
-  FW_HIP(hipEventCreate(&e0));
-  FW_HIP(hipEventCreate(&e1));
-  auto go = [&]() {   // variant: the workgroup -> (chunk, head, query tile) mapping (attn_enc.hip: 0 = XCD-aware, 1 = round 3's)
-    fwk::launch_attn_enc(m->stream, dqk, dqk + d, 2 * d, (int64_t)T * 2 * d, dvt, tp, (int64_t)d * tp, dout, d, (int64_t)T * d, B,
-                         H, T, variant);
-  };
-  go();
-  FW_HIP(hipEventRecord(e0, m->stream));
-  for (int i = 0; i < iters; ++i) go();
-  FW_HIP(hipEventRecord(e1, m->stream));
-  hipError_t he = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  cleanup();
-  if (he != hipSuccess) { set_error("attention bench failed: %s", hipGetErrorString(he)); return FW_ERUNTIME; }
-  *ms_out = ms / (float)iters;
-  return FW_OK;
-}
-
-// ---------------------------------------------------------------- decoder attention hooks (tests/test_gpu_dec_attention.py)
-// Each one uploads host buffers, runs the product's own launcher on m->stream (the form / register cap a decode step
-// would take under knobs 2 / 7) and downloads.  Every index the kernels turn into an address is checked here first.
-extern "C++" {
-namespace {
-struct DevBufs {   // device buffers of one hook call, freed on every return path
-  std::vector<void*> p;
-  template <typename T>
-  int alloc(T** dst, size_t n) {
-    int rc = dev_alloc_t(dst, n);
-    if (!rc) p.push_back(*dst);
-    return rc;
-  }
-  ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-};
-int upload_f16_to(const float* src, size_t n, half_t* dst) {
-  std::vector<uint16_t> tmp(n);
-  for (size_t i = 0; i < n; ++i) tmp[i] = f32_to_f16_bits(src[i]);
-  FW_HIP(hipMemcpy(dst, tmp.data(), n * 2, hipMemcpyHostToDevice));
-  return FW_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int32_t fw_test_dec_self_attn(fw_model* fm, const float* qkv, float* kcache, float* vcache, const uint8_t* kvidx,
-                              int32_t n_chunks, int32_t kmul, int32_t Kbeam, int32_t H, int32_t n_ctx, int32_t cache_ctx,
-                              int32_t pos_fixed, int32_t P, int32_t step, int32_t blk_n, int32_t frag, float* out) {
-  FW_CHECK_ARG(fm && qkv && kcache && vcache && kvidx && out, "null argument");
-  FW_CHECK_ARG(n_chunks >= 1 && H >= 1 && kmul >= 1 && kmul <= 16 && Kbeam >= 1 && Kbeam <= 255, "bad geometry");
-  FW_CHECK_ARG(n_ctx >= 1 && n_ctx <= 448 && cache_ctx >= 1 && cache_ctx <= n_ctx, "need 1 <= cache_ctx <= n_ctx <= 448");
-  FW_CHECK_ARG(blk_n >= 0 && (blk_n == 0 ? kmul <= Kbeam : (kmul == blk_n && pos_fixed >= 0)),
-               "blk_n = 0: kmul <= Kbeam; blk_n > 0: kmul == blk_n and pos_fixed >= 0");
-  const int pos0 = pos_fixed >= 0 ? pos_fixed : P - 1 + step;
-  const int pos_last = pos0 + (blk_n > 0 ? blk_n - 1 : 0);
-  FW_CHECK_ARG(pos0 >= 0 && pos_last < cache_ctx, "positions %d..%d outside the cache (%d)", pos0, pos_last, cache_ctx);
-  const int d = H * 64, R = n_chunks * kmul, R16 = (R + 15) / 16 * 16, R_total = n_chunks * Kbeam;
-  FW_CHECK_ARG(blk_n == 0 || fwd::self_attn_block_ok(n_ctx, cache_ctx, d, R_total), "position blocks need n_ctx %% 4 == 0");
-  const size_t n_tab = (size_t)2 * R_total * n_ctx, n_cache = (size_t)R_total * H * cache_ctx * 64;
-  for (size_t i = 0; i < n_tab; ++i)
-    FW_CHECK_ARG(kvidx[i] < Kbeam, "kvidx[%zu] = %d is not a beam of %d", i, (int)kvidx[i], Kbeam);
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  DevBufs db;
-  half_t *d_qkv, *d_kc, *d_vc, *d_out;
-  uint8_t* d_idx;
-  int* d_step;
-  int rc;
-  if ((rc = db.alloc(&d_qkv, (size_t)R * 3 * d)) || (rc = db.alloc(&d_kc, n_cache)) || (rc = db.alloc(&d_vc, n_cache)) ||
-      (rc = db.alloc(&d_out, (size_t)R16 * d)) || (rc = db.alloc(&d_idx, n_tab)) || (rc = db.alloc(&d_step, 1)))
-    return rc;
-  if ((rc = upload_f16_to(qkv, (size_t)R * 3 * d, d_qkv)) || (rc = upload_f16_to(kcache, n_cache, d_kc)) ||
-      (rc = upload_f16_to(vcache, n_cache, d_vc)))
-    return rc;
-  FW_HIP(hipMemcpy(d_idx, kvidx, n_tab, hipMemcpyHostToDevice));
-  FW_HIP(hipMemcpy(d_step, &step, sizeof(int), hipMemcpyHostToDevice));
-  FW_HIP(hipMemsetAsync(d_out, 0, (size_t)R16 * d * 2, m->stream));
-  fwd::launch_self_attn(m->stream, d_qkv, d, d_kc, d_vc, n_ctx, cache_ctx, H, d_idx, Kbeam, kmul, d_out, R, d_step,
-                        pos_fixed, P, R_total, frag ? 1 : 0, blk_n);
-  FW_HIP(hipGetLastError());
-  if ((rc = download_f16(m, d_kc, n_cache, kcache)) || (rc = download_f16(m, d_vc, n_cache, vcache))) return rc;
-  if (!frag) return download_f16(m, d_out, (size_t)R * d, out);
-  std::vector<float> of((size_t)R16 * d);
-  if ((rc = download_f16(m, d_out, of.size(), of.data()))) return rc;
-  for (int r = 0; r < R; ++r)
-    for (int n = 0; n < d; ++n) out[(size_t)r * d + n] = of[frag_pos(r, n, d, 32)];
-  return FW_OK;
-}
-
-int32_t fw_test_dec_cross_attn(fw_model* fm, const float* q, const float* k, const float* v, int32_t n_enc, int32_t T,
-                               int32_t H, int32_t B, int32_t kmul, int32_t kv_div, const int32_t* slot_map,
-                               const int32_t* done, int32_t frag, float k_pad, float* out) {
-  FW_CHECK_ARG(fm && q && k && v && slot_map && out, "null argument");
-  FW_CHECK_ARG(n_enc >= 1 && T >= 1 && H >= 1 && B >= 1 && kmul >= 1 && kmul <= 16 && kv_div >= 1, "bad geometry");
-  const int n_map = (B + kv_div - 1) / kv_div;
-  for (int i = 0; i < n_map; ++i)
-    FW_CHECK_ARG(slot_map[i] >= 0 && slot_map[i] < n_enc, "slot_map[%d] = %d outside [0, %d)", i, slot_map[i], n_enc);
-  const int d = H * 64, kvp = (T + 31) / 32 * 32, R = B * kmul, R16 = (R + 15) / 16 * 16;
-  const size_t blk = (size_t)d * kvp;   // one encoder chunk's K (or V^T)
-  // the pool's layout and contract (decoder.hip: CrossPool): padded keys of K hold whatever (k_pad), of V^T zeros
-  std::vector<float> kf((size_t)n_enc * blk), vf((size_t)n_enc * blk, 0.f);
-  for (int e = 0; e < n_enc; ++e)
-    for (int t = 0; t < kvp; ++t)
-      for (int n = 0; n < d; ++n) {
-        const size_t src = ((size_t)e * T + t) * d + n;
-        kf[e * blk + cross_kv_frag_pos(false, kvp, t, n)] = t < T ? k[src] : k_pad;
-        if (t < T) vf[e * blk + cross_kv_frag_pos(true, kvp, t, n)] = v[src];
-      }
-  std::vector<float> of((size_t)R16 * d, 0.f);
-  if (frag)
-    for (int r = 0; r < R; ++r)
-      for (int n = 0; n < d; ++n) of[frag_pos(r, n, d, 32)] = out[(size_t)r * d + n];
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  DevBufs db;
-  half_t *d_q, *d_k, *d_vt, *d_out;
-  int *d_map, *d_done = nullptr;
-  int rc;
-  if ((rc = db.alloc(&d_q, (size_t)R * d)) || (rc = db.alloc(&d_k, kf.size())) || (rc = db.alloc(&d_vt, vf.size())) ||
-      (rc = db.alloc(&d_out, (size_t)R16 * d)) || (rc = db.alloc(&d_map, (size_t)n_map)) || (done && (rc = db.alloc(&d_done, (size_t)B))))
-    return rc;
-  if ((rc = upload_f16_to(q, (size_t)R * d, d_q)) || (rc = upload_f16_to(kf.data(), kf.size(), d_k)) ||
-      (rc = upload_f16_to(vf.data(), vf.size(), d_vt)) || (rc = upload_f16_to(frag ? of.data() : out, frag ? of.size() : (size_t)R * d, d_out)))
-    return rc;
-  FW_HIP(hipMemcpy(d_map, slot_map, (size_t)n_map * sizeof(int), hipMemcpyHostToDevice));
-  if (done) FW_HIP(hipMemcpy(d_done, done, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-  fwd::launch_cross_attn(m->stream, d_q, d, d_k, d_vt, T, kvp, kmul, d_out, B, H, d_done, kv_div, frag ? 1 : 0, d_map);
-  FW_HIP(hipGetLastError());
-  if (!frag) return download_f16(m, d_out, (size_t)R * d, out);
-  if ((rc = download_f16(m, d_out, of.size(), of.data()))) return rc;
-  for (int r = 0; r < R; ++r)
-    for (int n = 0; n < d; ++n) out[(size_t)r * d + n] = of[frag_pos(r, n, d, 32)];
-  return FW_OK;
-}
-
-int32_t fw_test_dec_cross_probs(fw_model* fm, const float* q, const float* k, int32_t B, int32_t T, int32_t H,
-                                const int32_t* heads, int32_t n_sel, int32_t n_tok, int32_t tok_idx, int32_t blk_n,
-                                float* probs) {
-  FW_CHECK_ARG(fm && q && k && heads && probs, "null argument");
-  const int blk = blk_n > 0 ? blk_n : 1;
-  FW_CHECK_ARG(B >= 1 && T >= 1 && H >= 1 && n_sel >= 1 && blk_n >= 0 && blk <= 16, "bad geometry");
-  FW_CHECK_ARG(tok_idx >= 0 && tok_idx + blk <= n_tok, "tokens %d..%d outside [0, %d)", tok_idx, tok_idx + blk - 1, n_tok);
-  for (int i = 0; i < n_sel; ++i) FW_CHECK_ARG(heads[i] >= 0 && heads[i] < H, "heads[%d] = %d outside [0, %d)", i, heads[i], H);
-  const int d = H * 64, kvp = (T + 31) / 32 * 32;
-  const size_t blkk = (size_t)d * kvp, n_probs = (size_t)B * n_sel * n_tok * T;
-  std::vector<float> kf((size_t)B * blkk, 0.f);
-  for (int b = 0; b < B; ++b)
-    for (int t = 0; t < T; ++t)
-      for (int n = 0; n < d; ++n) kf[b * blkk + cross_kv_frag_pos(false, kvp, t, n)] = k[((size_t)b * T + t) * d + n];
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  DevBufs db;
-  half_t *d_q, *d_k;
-  int* d_heads;
-  float* d_p;
-  int rc;
-  if ((rc = db.alloc(&d_q, (size_t)B * blk * d)) || (rc = db.alloc(&d_k, kf.size())) || (rc = db.alloc(&d_heads, (size_t)n_sel)) ||
-      (rc = db.alloc(&d_p, n_probs)))
-    return rc;
-  if ((rc = upload_f16_to(q, (size_t)B * blk * d, d_q)) || (rc = upload_f16_to(kf.data(), kf.size(), d_k))) return rc;
-  FW_HIP(hipMemcpy(d_heads, heads, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice));
-  FW_HIP(hipMemcpy(d_p, probs, n_probs * sizeof(float), hipMemcpyHostToDevice));
-  fwd::launch_cross_probs(m->stream, d_q, d, d_k, T, kvp, d_heads, n_sel, n_sel, d_p, n_tok, tok_idx, B, blk_n);
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipStreamSynchronize(m->stream));
-  FW_HIP(hipMemcpy(probs, d_p, n_probs * sizeof(float), hipMemcpyDeviceToHost));
-  return FW_OK;
-}
-
-int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows, int32_t V, int32_t row_mul,
-                                 const int32_t* target, int32_t nospeech, float* out) {
-  FW_CHECK_ARG(fm && logits && target && out, "null argument");
-  FW_CHECK_ARG(rows >= 1 && V >= 1 && row_mul >= 1, "bad geometry");
-  FW_CHECK_ARG(!nospeech || (target[0] >= 0 && target[0] < V), "no-speech id %d outside [0, %d)", target[0], V);
-  Model* m = &fm->impl;
-  std::lock_guard<std::mutex> lk(m->mu);
-  FW_HIP(hipSetDevice(m->device));
-  DevBufs db;
-  const size_t n_lg = (size_t)rows * row_mul * V;
-  float *d_lg, *d_out;
-  int* d_t;
-  int rc;
-  if ((rc = db.alloc(&d_lg, n_lg)) || (rc = db.alloc(&d_out, (size_t)rows)) || (rc = db.alloc(&d_t, (size_t)rows))) return rc;
-  FW_HIP(hipMemcpy(d_lg, logits, n_lg * sizeof(float), hipMemcpyHostToDevice));
-  FW_HIP(hipMemcpy(d_t, target, (size_t)(nospeech ? 1 : rows) * sizeof(int), hipMemcpyHostToDevice));
-  if (nospeech) fwd::launch_nospeech(m->stream, d_lg, V, row_mul, target[0], d_out, rows);
-  else fwd::launch_token_prob(m->stream, d_lg, V, d_t, d_out, 1, 0, rows, row_mul);
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipStreamSynchronize(m->stream));
-  FW_HIP(hipMemcpy(out, d_out, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
   return FW_OK;
 }
 

@@ -2,6 +2,8 @@
  * fwamd_test.h — test and measurement hooks of libfwamd.so.  NOT part of the drop-in boundary (include/fwamd.h):
  * thin wrappers over single kernels on host buffers, so that tests/ can parity-test each kernel in isolation and
  * profiles/ can time one kernel outside the pipeline.  Nothing in faster_whisper_amd/ (the product) calls them.
+ * All of them are defined in csrc/hooks.hip (fw_bench_resample: csrc/resample.hip); file names in the comments below are
+ * those of the PRODUCT code a hook launches.
  */
 #ifndef FWAMD_TEST_H
 #define FWAMD_TEST_H
