@@ -83,6 +83,7 @@ SYMBOLS = [
     "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
     "fw_test_dec_beam_update", "fw_test_dec_embed", "fw_test_align_post",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
+    "fw_vad_forward_audio_batch_dev",
     "fw_flac_info", "fw_flac_decode",
     "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
 ]
@@ -200,6 +201,8 @@ def load():
     lib.fw_vad_forward_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
     if hasattr(lib, "fw_vad_forward_audio_dev"):
         lib.fw_vad_forward_audio_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
+    if hasattr(lib, "fw_vad_forward_audio_batch_dev"):   # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_vad_forward_audio_batch_dev.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
     lib.fw_vad_free.restype = None
     if hasattr(lib, "fw_resample_dev"):           # (absent from an older build loaded through FWAMD_LIB)
         f64 = C.c_double

@@ -11,6 +11,12 @@
 //   vad_lstm_kernel    ONE workgroup of 512 threads walks the windows sequentially: thread r keeps row r of the
 //                      recurrence matrix R[512][128] in 128 VGPRs, h[128] lives in LDS (broadcast reads), two
 //                      barriers per step; c stays in the registers of the first 128 threads.
+//
+// N recordings in one call (fw_vad_forward_audio_batch_dev): the same two bodies (vad_front_body, vad_lstm_body — the
+// arithmetic exists once) behind two ragged kernels.  vad_front_ragged_kernel is one launch over the windows of a group of
+// recordings, a workgroup finds its recording in a device table of first windows and frames within it;
+// vad_lstm_ragged_kernel is one workgroup PER RECORDING, all launched together: the recurrence is a latency chain of one
+// workgroup on one CU, so N recordings cost about the time of the longest one (more recordings than CUs queue behind).
 #include <math.h>
 #include <stdlib.h>
 
@@ -30,14 +36,16 @@ struct VadDev {
 
 __device__ __forceinline__ float sigmoid_dev(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
-__global__ __launch_bounds__(256) void vad_front_kernel(const float* __restrict__ win, const float* __restrict__ basis_t,
-                                                        const float* __restrict__ cw0, const float* __restrict__ cb0,
-                                                        const float* __restrict__ cw1, const float* __restrict__ cb1,
-                                                        const float* __restrict__ cw2, const float* __restrict__ cb2,
-                                                        const float* __restrict__ cw3, const float* __restrict__ cb3,
-                                                        const float* __restrict__ lw_t, const float* __restrict__ lb,
-                                                        float* __restrict__ gx, const float* __restrict__ audio,
-                                                        int64_t n_windows) {
+// one window of one recording: wi = its index in the recording, n_windows = the recording's windows, audio = the recording's
+// first sample (or win: the framed rows), gx_row = where the window's 512 gate pre-activations go
+__device__ __forceinline__ void vad_front_body(const float* __restrict__ win, const float* __restrict__ basis_t,
+                                               const float* __restrict__ cw0, const float* __restrict__ cb0,
+                                               const float* __restrict__ cw1, const float* __restrict__ cb1,
+                                               const float* __restrict__ cw2, const float* __restrict__ cb2,
+                                               const float* __restrict__ cw3, const float* __restrict__ cb3,
+                                               const float* __restrict__ lw_t, const float* __restrict__ lb,
+                                               float* __restrict__ gx_row, const float* __restrict__ audio,
+                                               const int64_t wi, const int64_t n_windows) {
   __shared__ float xp[kPadded];
   __shared__ float spec[kFrames][2 * kBins];
   __shared__ float mag[kFrames][kBins + 3];
@@ -50,7 +58,6 @@ __global__ __launch_bounds__(256) void vad_front_kernel(const float* __restrict_
   // reference's SileroVADModel.__call__ does on the host (vad.py:318-336): the context of window i is the tail of window
   // i - 1 (zeros for the first window) and the last 64 samples of the LAST window are zeroed (its in-place
   // `context[-1] = 0` on a view) — no [n][576] copy of the recording is built on the host or sent over PCIe
-  const int64_t wi = blockIdx.x;
   const float* w = win ? win + (size_t)wi * kWin : nullptr;
   auto sample = [&](int j) -> float {
     if (w) return w[j];
@@ -128,14 +135,46 @@ __global__ __launch_bounds__(256) void vad_front_kernel(const float* __restrict_
   for (int g = tid; g < kGates; g += 256) {
     float acc = lb[g];
     for (int c = 0; c < kHidden; ++c) acc += lw_t[(size_t)c * kGates + g] * feat[c];
-    gx[(size_t)blockIdx.x * kGates + g] = acc;
+    gx_row[g] = acc;
   }
 }
 
-__global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__ gx, const float* __restrict__ lr_t,
-                                                       const float* __restrict__ dw, float db, int64_t n,
-                                                       float* __restrict__ h_io, float* __restrict__ c_io,
-                                                       float* __restrict__ probs) {
+#define VAD_FRONT_WEIGHT_PARAMS                                                                                          \
+  const float *__restrict__ basis_t, const float *__restrict__ cw0, const float *__restrict__ cb0,                       \
+      const float *__restrict__ cw1, const float *__restrict__ cb1, const float *__restrict__ cw2,                       \
+      const float *__restrict__ cb2, const float *__restrict__ cw3, const float *__restrict__ cb3,                       \
+      const float *__restrict__ lw_t, const float *__restrict__ lb
+#define VAD_FRONT_WEIGHT_ARGS basis_t, cw0, cb0, cw1, cb1, cw2, cb2, cw3, cb3, lw_t, lb
+
+__global__ __launch_bounds__(256) void vad_front_kernel(const float* __restrict__ win, VAD_FRONT_WEIGHT_PARAMS,
+                                                        float* __restrict__ gx, const float* __restrict__ audio,
+                                                        int64_t n_windows) {
+  vad_front_body(win, VAD_FRONT_WEIGHT_ARGS, gx + (size_t)blockIdx.x * kGates, audio, blockIdx.x, n_windows);
+}
+
+// A group of recordings, one workgroup per window of the group.  first_win[0 .. n_rec]: first window of every recording of
+// the group (non-decreasing; first_win[n_rec] = the end), audio / gx: the group's first sample / first gate row.  The grid
+// is first_win[n_rec] - first_win[0] workgroups, so every workgroup's window lies in exactly one non-empty recording:
+// the one with first_win[r] <= window < first_win[r + 1] (an empty recording has no such window and is never picked).
+__global__ __launch_bounds__(256) void vad_front_ragged_kernel(VAD_FRONT_WEIGHT_PARAMS, float* __restrict__ gx,
+                                                               const float* __restrict__ audio,
+                                                               const int64_t* __restrict__ first_win, int n_rec) {
+  const int64_t base = first_win[0], g = base + blockIdx.x;
+  int lo = 0, hi = n_rec;                        // first_win[lo] <= g < first_win[hi] throughout
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (first_win[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t first = first_win[lo];
+  vad_front_body(nullptr, VAD_FRONT_WEIGHT_ARGS, gx + (size_t)blockIdx.x * kGates, audio + (first - base) * 512, g - first,
+                 first_win[lo + 1] - first);
+}
+
+// the recurrence over the n windows of ONE recording, by one workgroup of 512 threads
+__device__ __forceinline__ void vad_lstm_body(const float* __restrict__ gx, const float* __restrict__ lr_t,
+                                              const float* __restrict__ dw, float db, int64_t n,
+                                              float* __restrict__ h_io, float* __restrict__ c_io,
+                                              float* __restrict__ probs) {
   __shared__ float hs[kHidden];
   __shared__ float gs[kGates];
   __shared__ float part[2];
@@ -185,6 +224,26 @@ __global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__
     h_io[r] = hs[r];
     c_io[r] = cell;
   }
+}
+
+__global__ __launch_bounds__(512) void vad_lstm_kernel(const float* __restrict__ gx, const float* __restrict__ lr_t,
+                                                       const float* __restrict__ dw, float db, int64_t n,
+                                                       float* __restrict__ h_io, float* __restrict__ c_io,
+                                                       float* __restrict__ probs) {
+  vad_lstm_body(gx, lr_t, dw, db, n, h_io, c_io, probs);
+}
+
+// one workgroup per recording of a group (first_win as above; gx / probs: the group's first row / value; h_io, c_io:
+// [n_rec][128]).  A recording of no windows leaves its state as it is.
+__global__ __launch_bounds__(512) void vad_lstm_ragged_kernel(const float* __restrict__ gx, const float* __restrict__ lr_t,
+                                                              const float* __restrict__ dw, float db,
+                                                              const int64_t* __restrict__ first_win,
+                                                              float* __restrict__ h_io, float* __restrict__ c_io,
+                                                              float* __restrict__ probs) {
+  const int64_t first = first_win[blockIdx.x], n = first_win[blockIdx.x + 1] - first, at = first - first_win[0];
+  if (n == 0) return;
+  vad_lstm_body(gx + (size_t)at * kGates, lr_t, dw, db, n, h_io + (size_t)blockIdx.x * kHidden,
+                c_io + (size_t)blockIdx.x * kHidden, probs + at);
 }
 
 // (Round 6 measured a second form — four waves, two gate rows per lane, the four gates of a unit meeting by one cross-lane
@@ -299,4 +358,89 @@ extern "C" int32_t fw_vad_forward_audio_dev(fw_vad* v, int32_t device_index, con
                                             float* h, float* c, float* probs) {
   FW_CHECK_ARG(n_samples >= 0 && n_samples % 512 == 0, "the recording must be padded to a multiple of 512 samples");
   return vad_forward_dev_impl(v, device_index, nullptr, audio, n_samples / 512, h, c, probs);
+}
+
+extern "C" int32_t fw_vad_forward_audio_batch_dev(fw_vad* v, int32_t device_index, const float* audio,
+                                                  const int64_t* offsets, int32_t n_rec, float* h, float* c,
+                                                  float* probs) {
+  FW_CHECK_ARG(v && n_rec >= 0, "null model or negative recording count");
+  if (n_rec == 0) return FW_OK;
+  FW_CHECK_ARG(offsets && h && c, "null argument");
+  FW_CHECK_ARG(offsets[0] >= 0 && offsets[0] % 512 == 0, "offsets must be non-negative multiples of 512 samples");
+  std::vector<int64_t> first((size_t)n_rec + 1);           // first window of every recording, relative to offsets[0]
+  first[0] = 0;
+  for (int r = 0; r < n_rec; ++r) {
+    FW_CHECK_ARG(offsets[r + 1] >= offsets[r], "offsets must not decrease (recording %d)", r);
+    FW_CHECK_ARG(offsets[r + 1] % 512 == 0, "every recording must be padded to a multiple of 512 samples (recording %d)", r);
+    FW_CHECK_ARG(offsets[r + 1] - offsets[r] < ((int64_t)512 << 31), "window count out of range (recording %d)", r);
+    first[r + 1] = (offsets[r + 1] - offsets[0]) / 512;
+  }
+  const int64_t total = first[n_rec];
+  if (total == 0) return FW_OK;
+  FW_CHECK_ARG(audio && probs, "null argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device_index < 0 || device_index >= ndev) {
+    fw::set_error("fw_vad_forward_audio_batch_dev: no HIP device %d", device_index);
+    return FW_ENODEV;
+  }
+  // groups of consecutive recordings of at most FW_VAD_BATCH_MAX_WINDOWS windows (a longer recording: a group of its own)
+  std::vector<int> cut{0};
+  int64_t largest = 0;
+  for (int r = 0; r < n_rec;) {
+    int e = r + 1;
+    while (e < n_rec && first[e + 1] - first[r] <= FW_VAD_BATCH_MAX_WINDOWS) ++e;
+    largest = std::max(largest, first[e] - first[r]);
+    cut.push_back(e);
+    r = e;
+  }
+  int rc = ensure_dev(v, device_index);
+  if (rc) return rc;
+  VadDev* d = static_cast<VadDev*>(v->dev);
+  FW_HIP(hipSetDevice(d->device));
+  float *daudio = nullptr, *dgx = nullptr, *dh = nullptr, *dc = nullptr, *dp = nullptr;
+  int64_t* dfirst = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)daudio, (void*)dgx, (void*)dh, (void*)dc, (void*)dp, (void*)dfirst})
+      if (p) (void)hipFree(p);
+  };
+#define VAD_TRY(call)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (call);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      fw::set_error("%s failed: %s", #call, hipGetErrorString(e_));                          \
+      cleanup();                                                                             \
+      return e_ == hipErrorOutOfMemory ? FW_ENOMEM : FW_ERUNTIME;                            \
+    }                                                                                        \
+  } while (0)
+  const size_t state_bytes = (size_t)n_rec * kHidden * sizeof(float);
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&daudio), (size_t)largest * 512 * sizeof(float)));
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&dgx), (size_t)largest * kGates * sizeof(float)));
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&dh), state_bytes));
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&dc), state_bytes));
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&dp), (size_t)total * sizeof(float)));
+  VAD_TRY(hipMalloc(reinterpret_cast<void**>(&dfirst), first.size() * sizeof(int64_t)));
+  VAD_TRY(hipMemcpyAsync(dfirst, first.data(), first.size() * sizeof(int64_t), hipMemcpyHostToDevice, d->st));
+  VAD_TRY(hipMemcpyAsync(dh, h, state_bytes, hipMemcpyHostToDevice, d->st));
+  VAD_TRY(hipMemcpyAsync(dc, c, state_bytes, hipMemcpyHostToDevice, d->st));
+  for (size_t g = 0; g + 1 < cut.size(); ++g) {
+    const int r0 = cut[g], nr = cut[g + 1] - r0;
+    const int64_t w0 = first[r0], nw = first[r0 + nr] - w0;
+    if (nw == 0) continue;
+    // (the stream orders this upload behind the kernels of the group before, which read the same buffer)
+    VAD_TRY(hipMemcpyAsync(daudio, audio + offsets[0] + w0 * 512, (size_t)nw * 512 * sizeof(float), hipMemcpyHostToDevice,
+                           d->st));
+    vad_front_ragged_kernel<<<(unsigned)nw, 256, 0, d->st>>>(d->basis_t, d->cw_t[0], d->cb[0], d->cw_t[1], d->cb[1],
+                                                             d->cw_t[2], d->cb[2], d->cw_t[3], d->cb[3], d->lw_t, d->lb,
+                                                             dgx, daudio, dfirst + r0, nr);
+    vad_lstm_ragged_kernel<<<(unsigned)nr, 512, 0, d->st>>>(dgx, d->lr_t, d->dw, d->db, dfirst + r0,
+                                                            dh + (size_t)r0 * kHidden, dc + (size_t)r0 * kHidden, dp + w0);
+    VAD_TRY(hipGetLastError());
+  }
+  VAD_TRY(hipMemcpyAsync(probs, dp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, d->st));
+  VAD_TRY(hipMemcpyAsync(h, dh, state_bytes, hipMemcpyDeviceToHost, d->st));
+  VAD_TRY(hipMemcpyAsync(c, dc, state_bytes, hipMemcpyDeviceToHost, d->st));
+  VAD_TRY(hipStreamSynchronize(d->st));
+#undef VAD_TRY
+  cleanup();
+  return FW_OK;
 }

@@ -28,7 +28,7 @@ import os
 import zlib
 from dataclasses import dataclass
 from math import ceil
-from typing import Iterable, List, Optional, Tuple, Union
+from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -749,10 +749,20 @@ class WhisperModel:
                 audio = np.concatenate(collect_chunks(audio, speech_chunks)[0], axis=0)
             features = fe(audio[: language_detection_segments * fe.n_samples])
         features = features[..., : language_detection_segments * fe.nb_max_frames]
+        return self._detect_language_segments(features, language_detection_threshold)
+
+    def _detect_language_segments(self, features: np.ndarray, language_detection_threshold, first=None):
+        """the loop over the 30 s segments of `features` until one is confident; first: the backend's detect_language
+        result for segment 0 when the caller already has it (transcribe_many detects the first segments of many
+        recordings in one batch)"""
+        fe = self.feature_extractor
         seen = {}
         for i in range(0, features.shape[-1], fe.nb_max_frames):
-            enc = self.encode(pad_or_trim(features[..., i:i + fe.nb_max_frames]))
-            results = self.model.detect_language(enc)[0]
+            if i == 0 and first is not None:
+                results = first
+            else:
+                enc = self.encode(pad_or_trim(features[..., i:i + fe.nb_max_frames]))
+                results = self.model.detect_language(enc)[0]
             all_probs = [(tok[2:-2], p) for tok, p in results]
             language, prob = all_probs[0]
             if prob > language_detection_threshold:
@@ -877,20 +887,70 @@ class BatchedInferencePipeline:
         audio = np.asarray(audio, dtype=np.float32)
         duration = audio.shape[0] / sr
         chunk_length = chunk_length or m.feature_extractor.chunk_length
-        from .vad import VadOptions, collect_chunks, get_speech_timestamps
+        from .vad import get_speech_timestamps
         from .words import restore_speech_timestamps
         clips_given = bool(clip_timestamps)
+        speech_spans = None
+        if not clips_given and vad_filter:
+            vad_parameters = self._vad_options(vad_parameters, chunk_length)
+            speech_spans = get_speech_timestamps(audio, vad_parameters, speech_probs=vad_speech_probs)
+        clips, audio_chunks, chunks_metadata, duration_after_vad = self._split_recording(audio, clip_timestamps,
+                                                                                         speech_spans, chunk_length)
+
+        all_language_probs = None
+        if language is None:
+            if not m.model.is_multilingual:
+                language, language_probability = "en", 1
+            else:
+                feats = self._language_features(audio_chunks, language_detection_segments)
+                language, language_probability, all_language_probs = m.detect_language(
+                    features=feats, language_detection_segments=language_detection_segments,
+                    language_detection_threshold=language_detection_threshold)
+        else:
+            language, language_probability = self._given_language(language), 1
+        tokenizer = m.make_tokenizer(task=task, language=language)
+        options = self._batched_options(
+            tokenizer, clip_timestamps if clips_given else clips, beam_size=beam_size, best_of=best_of,
+            patience=patience, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+            no_repeat_ngram_size=no_repeat_ngram_size, log_prob_threshold=log_prob_threshold,
+            no_speech_threshold=no_speech_threshold, compression_ratio_threshold=compression_ratio_threshold,
+            temperature=temperature, initial_prompt=initial_prompt, prefix=prefix, suppress_blank=suppress_blank,
+            suppress_tokens=suppress_tokens, prepend_punctuations=prepend_punctuations,
+            append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, hotwords=hotwords,
+            word_timestamps=word_timestamps, multilingual=multilingual, without_timestamps=without_timestamps)
+        info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
+                                 duration_after_vad=duration_after_vad, transcription_options=options,
+                                 vad_options=vad_parameters, all_language_probs=all_language_probs)
+        gen = self._batched_segments_generator(audio_chunks, tokenizer, chunks_metadata, batch_size, options,
+                                               log_progress, shard, fused_features)
         if not clips_given:
+            gen = restore_speech_timestamps(gen, clips, sr)
+        return gen, info
+
+    # ---- the pieces of transcribe's front that transcribe_many runs per recording -----------------
+    @staticmethod
+    def _vad_options(vad_parameters, chunk_length):
+        """the VAD options of the batched path: spans of at most one chunk"""
+        from .vad import VadOptions
+        if vad_parameters is None:
+            return VadOptions(max_speech_duration_s=chunk_length, min_silence_duration_ms=160)
+        if isinstance(vad_parameters, dict):
+            return VadOptions(**{k: v for k, v in vad_parameters.items() if k != "max_speech_duration_s"},
+                              max_speech_duration_s=chunk_length)
+        return vad_parameters
+
+    def _split_recording(self, audio, clip_timestamps, speech_spans, chunk_length):
+        """-> (clips, audio_chunks, chunks_metadata, duration_after_vad) of one recording.  clip_timestamps: the caller's
+        split (wins); speech_spans: the VAD's spans of the recording (None: the VAD did not run)"""
+        from .vad import collect_chunks
+        m = self.model
+        sr = m.feature_extractor.sampling_rate
+        duration = audio.shape[0] / sr
+        if not clip_timestamps:
             # no split provided: speech spans from the VAD (merged into <= chunk_length chunks), or the whole
             # audio when it is shorter than one chunk
-            if vad_filter:
-                if vad_parameters is None:
-                    vad_parameters = VadOptions(max_speech_duration_s=chunk_length, min_silence_duration_ms=160)
-                elif isinstance(vad_parameters, dict):
-                    vad_parameters = VadOptions(**{k: v for k, v in vad_parameters.items()
-                                                   if k != "max_speech_duration_s"},
-                                                max_speech_duration_s=chunk_length)
-                clips = get_speech_timestamps(audio, vad_parameters, speech_probs=vad_speech_probs)
+            if speech_spans is not None:
+                clips = speech_spans
             elif duration < chunk_length:
                 clips = [{"start": 0, "end": audio.shape[0]}]
             else:
@@ -912,34 +972,37 @@ class BatchedInferencePipeline:
         assert duration - duration_after_vad >= 0, "non-negative timestamp expected"
         if not duration_after_vad:
             audio_chunks, chunks_metadata = [], []
+        return clips, audio_chunks, chunks_metadata, duration_after_vad
 
-        all_language_probs = None
-        if language is None:
-            if not m.model.is_multilingual:
-                language, language_probability = "en", 1
-            else:
-                # the reference concatenates the (unpadded) features of ALL chunks; detect_language only looks
-                # at the first language_detection_segments * 3000 frames, so stop once those are covered
-                need = language_detection_segments * m.feature_extractor.nb_max_frames
-                parts, have = [], 0
-                for chunk in audio_chunks:
-                    if have >= need:
-                        break
-                    parts.append(m.feature_extractor(chunk)[..., :-1])
-                    have += parts[-1].shape[-1]
-                # + one dummy frame so that empty audio still has a feature
-                feats = np.concatenate(parts + [np.full((m.model.n_mels, 1), -1.5, dtype="float32")], axis=1)
-                language, language_probability, all_language_probs = m.detect_language(
-                    features=feats, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold)
-        else:
-            if not m.model.is_multilingual and language != "en":
-                m.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
-                                 "using 'en' instead." % language)
-                language = "en"
-            language_probability = 1
-        tokenizer = m.make_tokenizer(task=task, language=language)
-        options = TranscriptionOptions(
+    def _language_features(self, audio_chunks, language_detection_segments):
+        """the features language detection looks at: the reference concatenates the (unpadded) features of ALL chunks;
+        detect_language only looks at the first language_detection_segments * 3000 frames, so stop once those are covered"""
+        m = self.model
+        need = language_detection_segments * m.feature_extractor.nb_max_frames
+        parts, have = [], 0
+        for chunk in audio_chunks:
+            if have >= need:
+                break
+            parts.append(m.feature_extractor(chunk)[..., :-1])
+            have += parts[-1].shape[-1]
+        # + one dummy frame so that empty audio still has a feature
+        return np.concatenate(parts + [np.full((m.model.n_mels, 1), -1.5, dtype="float32")], axis=1)
+
+    def _given_language(self, language):
+        m = self.model
+        if not m.model.is_multilingual and language != "en":
+            m.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
+                             "using 'en' instead." % language)
+            language = "en"
+        return language
+
+    @staticmethod
+    def _batched_options(tokenizer, clip_timestamps, *, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                         no_repeat_ngram_size, log_prob_threshold, no_speech_threshold, compression_ratio_threshold,
+                         temperature, initial_prompt, prefix, suppress_blank, suppress_tokens, prepend_punctuations,
+                         append_punctuations, max_new_tokens, hotwords, word_timestamps, multilingual,
+                         without_timestamps):
+        return TranscriptionOptions(
             beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
             log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
@@ -951,17 +1014,9 @@ class BatchedInferencePipeline:
             prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
             max_new_tokens=max_new_tokens, hotwords=hotwords, word_timestamps=word_timestamps,
             hallucination_silence_threshold=None, condition_on_previous_text=False,
-            clip_timestamps=(clip_timestamps if clips_given else clips), prompt_reset_on_temperature=0.5,
+            clip_timestamps=clip_timestamps, prompt_reset_on_temperature=0.5,
             multilingual=multilingual,
             without_timestamps=without_timestamps, max_initial_timestamp=0.0)
-        info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
-                                 duration_after_vad=duration_after_vad, transcription_options=options,
-                                 vad_options=vad_parameters, all_language_probs=all_language_probs)
-        gen = self._batched_segments_generator(audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                               log_progress, shard, fused_features)
-        if not clips_given:
-            gen = restore_speech_timestamps(gen, clips, sr)
-        return gen, info
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
                                     log_progress, shard=False, fused_features=True):
@@ -974,25 +1029,7 @@ class BatchedInferencePipeline:
             local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         n = len(audio_chunks)
         seg_idx = 0
-        # The batches of a recording are independent (`condition_on_previous_text=False`): with worker replicas
-        # (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
-        # encoders run side by side and their generate() calls share decode runs (backend decode groups).  Only
-        # the word-timestamp pause heuristics chain through last_speech_timestamp; those run in order, below.
-        workers = int(getattr(m.model, "inter_threads", 1) or 1)
-
-        def decode_batch(i0, i1):
-            chunks = audio_chunks[i0:i1]
-            feats = None if fused_features else m.model.log_mel(chunks)
-            enc, outs = self.generate_segment_batched(feats, tokenizer, options,
-                                                      audio_chunks=chunks if fused_features else None)
-            local = aligned = None
-            if not shard or options.word_timestamps:
-                local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata[i0:i1])
-                if options.word_timestamps:
-                    # the chunk-local half of the word timing runs where the encoder output lives
-                    aligned = m.align_words(local, tokenizer, enc, sizes, options.prepend_punctuations,
-                                            options.append_punctuations)
-            return outs, local, aligned
+        workers = self._workers()
 
         def batches(lo, hi):
             """(outs, local, aligned) per batch of the chunk range [lo, hi), in order, `workers` batches in flight"""
@@ -1004,31 +1041,14 @@ class BatchedInferencePipeline:
                 # kernel works per chunk); measured 315 -> 290 ms for 15 chunks (profiles/r06_bench_c4_halves.json)
                 mid = lo + (hi - lo + 1) // 2
                 spans = [(lo, mid), (mid, hi)]
-            if workers <= 1 or len(spans) <= 1:
-                for sp in spans:
-                    yield decode_batch(*sp)
-                return
-            from collections import deque
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=workers) as pool:
-                pending = deque()
-                for sp in spans:
-                    pending.append(pool.submit(decode_batch, *sp))
-                    if len(pending) >= workers:
-                        yield pending.popleft().result()
-                while pending:
-                    yield pending.popleft().result()
+            return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
+                                            for i0, i1 in spans], shard, fused_features)
 
         def emit(results):
             nonlocal seg_idx
-            for result in results:
-                for seg in result:
-                    seg_idx += 1
-                    yield Segment(seek=seg["seek"], id=seg_idx, text=seg["text"], start=round(seg["start"], 3),
-                                  end=round(seg["end"], 3), tokens=seg["tokens"], avg_logprob=seg["avg_logprob"],
-                                  words=(None if not options.word_timestamps else [Word(**w) for w in seg["words"]]),
-                                  no_speech_prob=seg["no_speech_prob"], compression_ratio=seg["compression_ratio"],
-                                  temperature=options.temperatures[0])
+            for seg in self._segments(results, options, seg_idx + 1):
+                seg_idx = seg.id
+                yield seg
 
         if not shard:
             # single process: segments are yielded as soon as their batch is decoded
@@ -1067,6 +1087,200 @@ class BatchedInferencePipeline:
             self.last_speech_timestamp = m.apply_word_alignments(results, ordered_aligned, self.last_speech_timestamp)
         yield from emit(results)
         self.last_speech_timestamp = 0.0
+
+
+    def _workers(self) -> int:
+        return int(getattr(self.model.model, "inter_threads", 1) or 1)
+
+    def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True):
+        """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
+        m = self.model
+        feats = None if fused_features else m.model.log_mel(chunks)
+        enc, outs = self.generate_segment_batched(feats, tokenizer, options,
+                                                  audio_chunks=chunks if fused_features else None)
+        local = aligned = None
+        if not shard or options.word_timestamps:
+            local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
+            if options.word_timestamps:
+                # the chunk-local half of the word timing runs where the encoder output lives
+                aligned = m.align_words(local, tokenizer, enc, sizes, options.prepend_punctuations,
+                                        options.append_punctuations)
+        return outs, local, aligned
+
+    def _batches_in_flight(self, jobs, shard=False, fused_features=True):
+        """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
+        The batches are independent (`condition_on_previous_text=False`): with worker replicas
+        (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
+        encoders run side by side and their generate() calls share decode runs (backend decode groups).  Only
+        the word-timestamp pause heuristics chain through last_speech_timestamp; those run in order, in the caller."""
+        workers = self._workers()
+        if workers <= 1 or len(jobs) <= 1:
+            for job in jobs:
+                yield self._decode_batch(*job, shard, fused_features)
+            return
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            pending = deque()
+            for job in jobs:
+                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features))
+                if len(pending) >= workers:
+                    yield pending.popleft().result()
+            while pending:
+                yield pending.popleft().result()
+
+    @staticmethod
+    def _segments(results, options, first_id):
+        """the Segment objects of decoded chunks (`results`: per chunk its sub-segment dicts), ids from first_id"""
+        idx = first_id
+        for result in results:
+            for seg in result:
+                yield Segment(seek=seg["seek"], id=idx, text=seg["text"], start=round(seg["start"], 3),
+                              end=round(seg["end"], 3), tokens=seg["tokens"], avg_logprob=seg["avg_logprob"],
+                              words=(None if not options.word_timestamps else [Word(**w) for w in seg["words"]]),
+                              no_speech_prob=seg["no_speech_prob"], compression_ratio=seg["compression_ratio"],
+                              temperature=options.temperatures[0])
+                idx += 1
+
+    # ---- many recordings in one call ------------------------------------------------------------
+    def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]], *, language=None, clip_timestamps=None,
+                        vad_speech_probs=None, vad_model=None, shard: bool = False,
+                        **kwargs) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+        """Transcribes several recordings in ONE call: result[i] = (list of segments, info) is what
+        `BatchedInferencePipeline(model).transcribe(audios[i], ...)` on a fresh pipeline yields, field for field (the
+        engine's result for a chunk does not depend on what shares its batch), but the work is shared: one VAD pass
+        over all recordings (`vad_model.forward_many`), first-segment language detection in batches, and the chunks of
+        ALL recordings pooled into batches of `batch_size` — cut across recording boundaries, `num_workers` batches in
+        flight — so a thousand 20 s clips run the encoder and the decoder as full batches, not a thousand batches of one.
+
+        language, clip_timestamps, vad_speech_probs: one value for all recordings, or a sequence with one entry per
+        recording.  vad_model: a SileroVADModel or a callable (default: get_vad_model()).  Every other keyword is
+        transcribe()'s, with its default.  A batch holds chunks of one language (the prompt is per language).  Returns
+        when every recording is done; shard=True is not offered here (ValueError)."""
+        import inspect
+        from .vad import get_speech_timestamps_many
+        from .words import restore_speech_timestamps
+        if shard:
+            raise ValueError("transcribe_many does not shard: call it per rank on that rank's recordings")
+        a = inspect.signature(self.transcribe).bind(None, **kwargs)     # transcribe's keywords and defaults
+        a.apply_defaults()
+        a = a.arguments
+        m = self.model
+        sr = m.feature_extractor.sampling_rate
+        n = len(audios)
+        if n == 0:
+            return []
+        multilingual = a["multilingual"]
+        if multilingual and not m.model.is_multilingual:
+            m.logger.warning("The current model is English-only but the multilingual parameter is set to"
+                             "True; setting to False instead.")
+            multilingual = False
+        languages = self._per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
+        clip_lists = self._per_recording(clip_timestamps, n, "clip_timestamps",
+                                         lambda v: v is None or all(isinstance(c, dict) for c in v))
+        probs = self._per_recording(vad_speech_probs, n, "vad_speech_probs",
+                                    lambda v: v is None or isinstance(v, np.ndarray)
+                                    or all(np.ndim(p) == 0 and p is not None for p in v))
+        recs = []
+        for audio in audios:
+            if not isinstance(audio, np.ndarray):
+                from .audio import decode_audio
+                audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(m.model))
+            recs.append(np.asarray(audio, dtype=np.float32))
+        chunk_length = a["chunk_length"] or m.feature_extractor.chunk_length
+
+        # ---- VAD: one pass over every recording that needs it ----
+        vad_options = [a["vad_parameters"]] * n
+        spans = [None] * n
+        need_vad = [r for r in range(n) if not clip_lists[r] and a["vad_filter"]]
+        if need_vad:
+            opts = self._vad_options(a["vad_parameters"], chunk_length)
+            found = get_speech_timestamps_many([recs[r] for r in need_vad], opts, vad_model=vad_model,
+                                               speech_probs=[probs[r] for r in need_vad])
+            for r, sp in zip(need_vad, found):
+                vad_options[r], spans[r] = opts, sp
+        split = [self._split_recording(recs[r], clip_lists[r], spans[r], chunk_length) for r in range(n)]
+
+        # ---- language: the first detection segment of all undecided recordings in batches ----
+        detected = {}
+        if m.model.is_multilingual:
+            undecided = [r for r in range(n) if languages[r] is None]
+            frames = m.feature_extractor.nb_max_frames
+            feats = {r: self._language_features(split[r][1], a["language_detection_segments"])
+                     [..., :a["language_detection_segments"] * frames] for r in undecided}
+            for i in range(0, len(undecided), a["batch_size"]):
+                part = undecided[i:i + a["batch_size"]]
+                enc = m.encode(np.stack([pad_or_trim(feats[r][..., :frames]) for r in part]))
+                for r, first in zip(part, m.model.detect_language(enc)):
+                    # (a recording whose first segment stays under the threshold goes on alone with its further segments)
+                    detected[r] = m._detect_language_segments(feats[r], a["language_detection_threshold"], first=first)
+
+        # ---- per recording: tokenizer (one per language), options, info ----
+        tokenizers, infos, all_options = {}, [], []
+        for r in range(n):
+            all_language_probs = None
+            if languages[r] is not None:
+                lang, lang_prob = self._given_language(languages[r]), 1
+            elif not m.model.is_multilingual:
+                lang, lang_prob = "en", 1
+            else:
+                lang, lang_prob, all_language_probs = detected[r]
+            languages[r] = lang
+            if lang not in tokenizers:
+                tokenizers[lang] = m.make_tokenizer(task=a["task"], language=lang)
+            clips = split[r][0]
+            options = self._batched_options(
+                tokenizers[lang], clip_lists[r] if clip_lists[r] else clips, multilingual=multilingual,
+                **{k: a[k] for k in ("beam_size", "best_of", "patience", "length_penalty", "repetition_penalty",
+                                     "no_repeat_ngram_size", "log_prob_threshold", "no_speech_threshold",
+                                     "compression_ratio_threshold", "temperature", "initial_prompt", "prefix",
+                                     "suppress_blank", "suppress_tokens", "prepend_punctuations", "append_punctuations",
+                                     "max_new_tokens", "hotwords", "word_timestamps", "without_timestamps")})
+            all_options.append(options)
+            infos.append(TranscriptionInfo(language=lang, language_probability=lang_prob,
+                                           duration=recs[r].shape[0] / sr, duration_after_vad=split[r][3],
+                                           transcription_options=options, vad_options=vad_options[r],
+                                           all_language_probs=all_language_probs))
+
+        # ---- pooling: the chunks of all recordings in recording order, per language; a batch every batch_size chunks ----
+        jobs, owners = [], []                                  # owners[j]: the recording of every chunk of job j
+        for lang, tokenizer in tokenizers.items():
+            pool = [(r, k) for r in range(n) if languages[r] == lang for k in range(len(split[r][1]))]
+            # (what a batch's decode reads of the options is the same for every recording of a language: they differ in
+            #  clip_timestamps alone)
+            options = next(all_options[r] for r in range(n) if languages[r] == lang)
+            for i in range(0, len(pool), a["batch_size"]):
+                part = pool[i:i + a["batch_size"]]
+                jobs.append(([split[r][1][k] for r, k in part], [split[r][2][k] for r, k in part], tokenizer, options))
+                owners.append([r for r, _ in part])
+
+        # ---- routing: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
+        results = [[] for _ in range(n)]
+        aligned = [[] for _ in range(n)]
+        for own, (_, local, al) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"])):
+            for j, r in enumerate(own):
+                results[r].append(local[j])
+                if al is not None:
+                    aligned[r].append(al[j])
+        out = []
+        for r in range(n):
+            if a["word_timestamps"]:
+                m.apply_word_alignments(results[r], aligned[r], 0.0)   # the pause heuristics chain within a recording
+            segments = self._segments(results[r], all_options[r], 1)
+            if not clip_lists[r]:
+                segments = restore_speech_timestamps(segments, split[r][0], sr)
+            out.append((list(segments), infos[r]))
+        return out
+
+    @staticmethod
+    def _per_recording(value, n, name, is_single):
+        """one value for all recordings, or a sequence with one entry per recording -> a list of n"""
+        if is_single(value):
+            return [value] * n
+        value = list(value)
+        if len(value) != n:
+            raise ValueError(f"{name} has {len(value)} entries for {n} recordings")
+        return value
 
 
 class _OutRec:

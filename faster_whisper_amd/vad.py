@@ -8,6 +8,9 @@ Mirrors the reference's `faster_whisper/vad.py` interface (same names, argument 
 
     SileroVADModel, get_vad_model   vad.py:288-351  the Silero VAD v6 network (row f-3)
 
+Not in the reference: get_speech_timestamps_many / SileroVADModel.forward_many — several recordings through ONE pass of
+the network (on the device one call, fw_vad_forward_audio_batch_dev), for BatchedInferencePipeline.transcribe_many.
+
 The network that produces the window probabilities is an ONNX asset the reference runs with onnxruntime on one
 CPU thread.  Here it is native host C++ behind the C ABI (`fw_vad_*`, csrc/vad_host.cpp: window-parallel front
 end on a thread pool, sequential LSTM recurrence); the ONNX file is only read for its weights (onnx_lite.py) and
@@ -149,6 +152,31 @@ def get_speech_timestamps(audio: np.ndarray, vad_options: Optional[VadOptions] =
         else:
             span["end"] = int(min(n_audio, span["end"] + pad))
     return spans
+
+
+def get_speech_timestamps_many(audios: Sequence[np.ndarray], vad_options: Optional[VadOptions] = None,
+                               sampling_rate: int = 16000, vad_model=None, speech_probs: Optional[Sequence] = None,
+                               **kwargs) -> List[List[dict]]:
+    """get_speech_timestamps for several recordings: the network runs ONCE over all of them (`vad_model.forward_many`:
+    one device call with SileroVADModel(device="cuda"); a plain callable is called per recording), the state machine per
+    recording.  speech_probs: one entry per recording (None: run the network for that one).  -> one span list per
+    recording, each what get_speech_timestamps returns for that recording."""
+    opts = vad_options if vad_options is not None else VadOptions(**kwargs)
+    audios = list(audios)
+    probs = list(speech_probs) if speech_probs is not None else [None] * len(audios)
+    if len(probs) != len(audios):
+        raise ValueError(f"speech_probs has {len(probs)} entries for {len(audios)} recordings")
+    todo = [i for i, p in enumerate(probs) if p is None]
+    if todo:
+        if vad_model is None:
+            vad_model = get_vad_model()
+        # the reference always appends 1..512 zero samples (a whole extra window when already aligned)
+        padded = [np.pad(audios[i], (0, WINDOW - len(audios[i]) % WINDOW)) for i in todo]
+        many = getattr(vad_model, "forward_many", None)
+        outs = many(padded) if many is not None else [vad_model(a) for a in padded]
+        for i, out in zip(todo, outs):
+            probs[i] = out
+    return [get_speech_timestamps(a, opts, sampling_rate, speech_probs=p) for a, p in zip(audios, probs)]
 
 
 def collect_chunks(audio: np.ndarray, chunks: List[dict], sampling_rate: int = 16000,
@@ -333,6 +361,33 @@ class SileroVADModel:
             _lib.check(self._lib.fw_vad_forward(self._handle, _lib.ptr(windows), n, self.n_threads, _lib.ptr(h),
                                                 _lib.ptr(c), _lib.ptr(probs)))
         return probs
+
+    def forward_many(self, padded_audios: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """`self(a)` for every recording of `padded_audios` (1-D, each a multiple of 512 samples; empty allowed).
+        device="cuda": ONE fw_vad_forward_audio_batch_dev call — one upload, one front-end launch over all windows, the
+        recurrences of all recordings side by side — with the same bits as the per-recording calls; device="cpu": a loop
+        over the host path."""
+        from . import _lib
+        for a in padded_audios:
+            assert a.ndim == 1, "Input should be a 1D array"
+            assert a.shape[0] % WINDOW == 0, "Input size should be a multiple of num_samples"
+        n_rec = len(padded_audios)
+        if self.device != "cuda":
+            return [self(a) if a.shape[0] else np.empty(0, dtype=np.float32) for a in padded_audios]
+        if n_rec == 0:
+            return []
+        offsets = np.zeros(n_rec + 1, dtype=np.int64)
+        np.cumsum([a.shape[0] for a in padded_audios], out=offsets[1:])
+        audio = np.empty(int(offsets[-1]), dtype=np.float32)
+        for a, o in zip(padded_audios, offsets):
+            audio[o:o + a.shape[0]] = a
+        h = np.zeros((n_rec, 128), dtype=np.float32)
+        c = np.zeros((n_rec, 128), dtype=np.float32)
+        probs = np.empty(int(offsets[-1]) // WINDOW, dtype=np.float32)
+        _lib.check(self._lib.fw_vad_forward_audio_batch_dev(self._handle, self.device_index, _lib.ptr(audio),
+                                                            _lib.ptr(offsets), n_rec, _lib.ptr(h), _lib.ptr(c),
+                                                            _lib.ptr(probs)))
+        return [probs[a // WINDOW:b // WINDOW].copy() for a, b in zip(offsets[:-1], offsets[1:])]
 
     def __del__(self):
         h = getattr(self, "_handle", None)

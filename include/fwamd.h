@@ -51,7 +51,8 @@ extern "C" {
 /* 2: fw_model_set_encoder_cus / fw_model_encoder_cus removed, fw_model_set_merge_wait, fw_model_set_decode_lanes and
  *    fw_model_run_capacity added, test / bench hooks moved to fwamd_test.h; the cross-attention cache of a decode group
  *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run);
- *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed) */
+ *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed),
+ *    fw_vad_forward_audio_batch_dev likewise */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -328,6 +329,24 @@ int32_t fw_vad_forward_dev(fw_vad* v, int32_t device_index, const float* windows
  * of the recording is built or transferred.  probs: n_samples / 512 values. */
 int32_t fw_vad_forward_audio_dev(fw_vad* v, int32_t device_index, const float* audio, int64_t n_samples, float* h, float* c,
                                  float* probs);
+/* N recordings in one device call.  audio: the recordings back to back, each padded to a multiple of 512 samples
+ * (as fw_vad_forward_audio_dev takes ONE); offsets[n_rec + 1]: sample offsets, non-decreasing, multiples of 512
+ * (an empty recording is allowed);  h, c: [n_rec][128] LSTM states, updated in place per recording;
+ * probs: offsets[n_rec] / 512 values, recording after recording.
+ * Recording r's probabilities and final h / c are bit for bit those of fw_vad_forward_audio_dev on that recording alone:
+ * the front end is ONE launch over the windows of all recordings (a workgroup finds its recording in a device table of
+ * first windows and frames per recording: zero context for a recording's first window, the last 64 samples of its last
+ * window zeroed), the recurrence one workgroup PER RECORDING, all launched together, so N recordings cost about the time
+ * of the longest one.  One set of device buffers per call.  The recordings are processed in groups of consecutive
+ * recordings of at most FW_VAD_BATCH_MAX_WINDOWS windows in total: the gate pre-activations of a group are 2 KB per
+ * window, so 131 072 windows (70 min of audio) bound that buffer at 256 MiB — no more than the single call allocates for
+ * a 70-minute recording — and a group of that size is already 131 072 front-end workgroups, far more than the device
+ * holds at once; a single recording above the bound forms a group of its own, as fw_vad_forward_audio_dev runs it.
+ * FW_EINVAL: n_rec < 0, a null pointer, offsets that decrease, are negative or are no multiple of 512 (nothing is started
+ * on the device); FW_ENODEV: no such device; n_rec == 0: FW_OK. */
+#define FW_VAD_BATCH_MAX_WINDOWS 131072
+int32_t fw_vad_forward_audio_batch_dev(fw_vad* v, int32_t device_index, const float* audio, const int64_t* offsets,
+                                       int32_t n_rec, float* h, float* c, float* probs);
 
 /* ---- audio front: native FLAC decoding --------------------------------------------
  * The reference decodes every container through PyAV / FFmpeg (faster_whisper/audio.py:19-76); its own test asset
