@@ -128,16 +128,12 @@ int64_t cross_pool_bytes(const Model* m, int pool_chunks) {
   return 2 * ((int64_t)c.n_dec_layers * pool_chunks * c.d_model * kvp) * 2;   // K and V^T, fp16
 }
 
-// the pool of the group m decodes for: m's own (primary) or the primary's (a lane)
-static CrossPool* pool_of(Model* m) { return (m->pool_owner ? m->pool_owner : m)->xpool; }
-
-static int cross_pool_ensure(Model* m) {
-  Model* owner = m->pool_owner ? m->pool_owner : m;
-  if (owner->xpool) return FW_OK;
-  const fw_config& c = owner->cfg;
+int cross_pool_ensure(Model* m, int pool_chunks) {
+  if (m->xpool) return FW_OK;
+  const fw_config& c = m->cfg;
   CrossPool* p = new CrossPool();
-  p->EB = owner->max_batch;
-  p->n_blocks = std::max(1, std::max(owner->decode_batch, owner->max_batch) / owner->max_batch);
+  p->EB = m->max_batch;
+  p->n_blocks = std::max(1, std::max(pool_chunks, m->max_batch) / m->max_batch);
   p->kvp = ((c.n_audio_ctx + 31) / 32) * 32;
   p->blocks.assign(p->n_blocks, CrossPool::Block());
   const size_t n = (size_t)c.n_dec_layers * p->n_slots() * c.d_model * p->kvp;
@@ -157,7 +153,7 @@ static int cross_pool_ensure(Model* m) {
     set_error("cross-attention pool setup failed: %s", hipGetErrorString(he));
     return FW_ENODEV;
   }
-  owner->xpool = p;
+  m->xpool = p;
   return FW_OK;
 }
 
@@ -225,23 +221,22 @@ struct PoolHold {   // releases its blocks when the decode run / detect_language
   }
 };
 
-static int gen_workspace_build(Model* m) {
+static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks, int self_ctx) {
   const fw_config& c = m->cfg;
   GenWorkspace* g = new GenWorkspace();
-  m->gen = g;   // gen_workspace_ensure frees it again when anything below fails
-  if (m->decode_batch < m->max_batch) m->decode_batch = m->max_batch;
-  g->B = lane_chunks_of(m);
+  lane->gen = g;   // gen_workspace_build frees it again when anything below fails
+  g->B = lane_chunks;
   g->EB = m->max_batch;
   g->K = m->max_beam;
   g->R = g->B * g->K;
   g->NT = c.n_text_ctx;
-  g->NTs = self_positions(m, g->B, m->decode_self_ctx > 0 ? m->decode_self_ctx : c.n_text_ctx);
+  g->NTs = self_positions(m, g->B, self_ctx > 0 ? self_ctx : c.n_text_ctx);
   g->self_cap = (int64_t)g->R * g->NTs;
   const size_t B = g->B, R = g->R, d = c.d_model, L = c.n_dec_layers, NT = g->NT;
   (void)B;
   FW_CHECK_ARG(R <= 2048, "decode_batch * max_beam must be <= 2048 (got %zu)", R);
   FW_HIP(hipSetDevice(m->device));
-  if (!m->dec_stream) FW_HIP(create_stream(&m->dec_stream, "DEC"));
+  if (!lane->stream) FW_HIP(create_stream(&lane->stream, "DEC"));
   int rc;
 #define A(p, n) do { if ((rc = dev_alloc_t(&(p), (n)))) return rc; } while (0)
   A(g->slot_map, R);
@@ -292,17 +287,20 @@ static int gen_workspace_build(Model* m) {
 
 // A workspace is installed whole or not at all: after a failed build (argument check, out of HBM) the next call
 // starts from scratch instead of launching kernels on a half-allocated one.
-int gen_workspace_ensure(Model* m) {
-  int rc = cross_pool_ensure(m);
-  if (rc) return rc;
-  if (m->gen) return FW_OK;
-  rc = gen_workspace_build(m);
-  if (rc) gen_workspace_free(m);
+int gen_workspace_build(const Model* m, DecodeLane* lane, int lane_chunks, int self_ctx) {
+  const int rc = gen_workspace_alloc(m, lane, lane_chunks, self_ctx);
+  if (rc) gen_workspace_free(lane);
   return rc;
 }
 
-void gen_workspace_free(Model* m) {
-  GenWorkspace* g = m->gen;
+int gen_workspace_ensure(Model* m, DecodeLane* lane) {
+  if (int rc = cross_pool_ensure(m, m->decode_batch)) return rc;
+  if (lane->gen) return FW_OK;
+  return gen_workspace_build(m, lane, lane_chunks_of(m), m->decode_self_ctx);
+}
+
+void gen_workspace_free(DecodeLane* lane) {
+  GenWorkspace* g = lane->gen;
   if (!g) return;
   for (GraphSlot& s : g->graphs)
     if (s.exec) (void)hipGraphExecDestroy(s.exec);
@@ -313,7 +311,14 @@ void gen_workspace_free(Model* m) {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete g;
-  m->gen = nullptr;
+  lane->gen = nullptr;
+}
+
+DecodeLane::~DecodeLane() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  gen_workspace_free(this);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (spare) (void)hipStreamDestroy(spare);
 }
 
 // K11: cross-attention K / V^T of every decoder layer for the chunks of one encoder output, written to the chunk
@@ -347,19 +352,19 @@ static bool cross_kv_strides(const Model* m, int64_t* ws, int64_t* bs) {
   return w1 > 0;
 }
 
-static int ensure_cross_kv(Model* m, const Tensor* enc, int blk, bool hit) {
+static int ensure_cross_kv(Model* m, DecodeLane* lane, const Tensor* enc, int blk, bool hit) {
   if (hit) return FW_OK;
-  GenWorkspace* g = m->gen;
-  CrossPool* pool = pool_of(m);
+  GenWorkspace* g = lane->gen;
+  CrossPool* pool = m->xpool;
   const int B = enc->B;
   const int b0 = blk * pool->EB;
   // (a failure half way leaves the block marked empty — pool_acquire did that — never pointing at partly overwritten K/V)
   const fw_config& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx;
   const int64_t xs = (int64_t)T * d;
-  hipStream_t st = m->dec_stream;
+  hipStream_t st = lane->stream;
   int rc;
-  ProfScope ps(m, PF_CROSS_KV_GEMM, 2.0 * c.n_dec_layers * B * (double)T * d * (2.0 * d), 0, st);
+  ProfScope ps(lane->prof, PF_CROSS_KV_GEMM, 2.0 * c.n_dec_layers * B * (double)T * d * (2.0 * d), 0, st);
   const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
   const int kvp = pool->kvp;
   const int64_t kvs = (int64_t)d * kvp;   // one chunk's K (or V^T): H heads x kvp keys x 64
@@ -457,17 +462,17 @@ static int pos_block_size(const Model* m, const GenWorkspace* g, const GenDev& g
 
 // One decoder forward over `rows` rows.  Everything that varies from step to step lives in HBM (d_step, beam
 // tables), and everything a captured graph bakes in by value is part of GenDev (the graph key).
-static int run_step(Model* m, const GenDev& gp, const StepCfg& s) {
-  GenWorkspace* g = m->gen;
+static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg& s) {
+  GenWorkspace* g = lane->gen;
   const fw_config& c = m->cfg;
   const int d = c.d_model, H = c.n_heads, T = c.n_audio_ctx, NT = g->NT;
-  CrossPool* pool = pool_of(m);
+  CrossPool* pool = m->xpool;
   const int kvp = pool->kvp;
-  hipStream_t st = m->dec_stream;
+  hipStream_t st = lane->stream;
   const int rows = s.rows;
   const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
   {
-    ProfScope ps(m, PF_DEC_MISC, 0, 0, st);
+    ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
     fwd::launch_embed(st, s.tok, m->tok_emb, m->dec_pos, g->x, i8 ? nullptr : g->x_frag, rows, d, g->d_step,
                       s.pos_fixed, s.P, s.blk_n);
   }
@@ -501,18 +506,18 @@ static int run_step(Model* m, const GenDev& gp, const StepCfg& s) {
     const half_t* ck = pool->ck + (size_t)l * pool->n_slots() * d * kvp;
     const half_t* cvt = pool->cvt + (size_t)l * pool->n_slots() * d * kvp;
     {
-      ProfScope ps(m, PF_DEC_GEMM_QKV, 2.0 * rows * 3.0 * d * d, 2.0 * 3.0 * d * d, st);
+      ProfScope ps(lane->prof, PF_DEC_GEMM_QKV, 2.0 * rows * 3.0 * d * d, 2.0 * 3.0 * d * d, st);
       if (i8) DG(lin_q(g->x, &L.ln1, L.qkv, nullptr, g->qkv, 0));
       else if (unf) DG(lin_u(L.ln1, L.qkv_p, g->qkv, nullptr, 0));
       else DG(lin_f(g->x_frag, L.qkv, nullptr, g->qkv, nullptr, 0));
     }
     {
-      ProfScope ps(m, PF_DEC_SELF_ATTN, 0, 0, st);
+      ProfScope ps(lane->prof, PF_DEC_SELF_ATTN, 0, 0, st);
       fwd::launch_self_attn(st, g->qkv, d, kc, vc, NT, gp.ctx, H, g->kvidx2, gp.K, s.kmul, frag ? g->att_frag : g->att, rows,
                             g->d_step, s.pos_fixed, s.P, gp.R, frag, s.blk_n);
     }
     {
-      ProfScope ps(m, PF_DEC_GEMM_DXD, 2.0 * rows * 2.0 * d * d, 2.0 * 2.0 * d * d, st);
+      ProfScope ps(lane->prof, PF_DEC_GEMM_DXD, 2.0 * rows * 2.0 * d * d, 2.0 * 2.0 * d * d, st);
       if (i8) {
         DG(lin_q(g->att, nullptr, L.out, g->x, g->x, 0));
         DG(lin_q(g->x, &L.ln2, L.cq, nullptr, g->qc, 0));
@@ -523,35 +528,36 @@ static int run_step(Model* m, const GenDev& gp, const StepCfg& s) {
       }
     }
     if (s.probs && s.sel_layer_off[l + 1] > s.sel_layer_off[l]) {
-      ProfScope ps(m, PF_DEC_MISC, 0, 0, st);
+      ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
       const int off = s.sel_layer_off[l], n = s.sel_layer_off[l + 1] - off;
       fwd::launch_cross_probs(st, g->qc, d, ck + (size_t)s.kv_slot0 * d * kvp, T, kvp, s.sel_heads_dev + off, n, s.n_sel_total,
                               s.probs + (size_t)off * s.n_tok * T, s.n_tok, s.tok_idx, s.B, s.blk_n);
     }
     {
-      ProfScope ps(m, PF_DEC_CROSS_ATTN, 4.0 * rows * (double)T * d, 4.0 * (s.B / gp.kv_div) * (double)T * d, st);
+      ProfScope ps(lane->prof, PF_DEC_CROSS_ATTN, 4.0 * rows * (double)T * d, 4.0 * (s.B / gp.kv_div) * (double)T * d,
+                   st);
       fwd::launch_cross_attn(st, g->qc, d, ck, cvt, T, kvp, s.kmul, frag ? g->att_frag : g->att, s.B, H, s.done,
                              gp.kv_div, frag, g->slot_map);
     }
     {
-      ProfScope ps(m, PF_DEC_GEMM_DXD, 2.0 * rows * 1.0 * d * d, 2.0 * 1.0 * d * d, st);
+      ProfScope ps(lane->prof, PF_DEC_GEMM_DXD, 2.0 * rows * 1.0 * d * d, 2.0 * 1.0 * d * d, st);
       if (i8) DG(lin_q(g->att, nullptr, L.cout, g->x, g->x, 0));
       else DG(lin_f(g->att_frag, L.cout, g->x, g->x, g->x_frag, 0));
     }
     {
-      ProfScope ps(m, PF_DEC_GEMM_FFN1, 2.0 * rows * 4.0 * d * d, 2.0 * 4.0 * d * d, st);
+      ProfScope ps(lane->prof, PF_DEC_GEMM_FFN1, 2.0 * rows * 4.0 * d * d, 2.0 * 4.0 * d * d, st);
       if (i8) DG(lin_q(g->x, &L.ln3, L.ffn1, nullptr, g->ffn, 1));
       else if (unf) DG(lin_u(L.ln3, L.ffn1_p, nullptr, g->ffn_frag, 1));
       else DG(lin_f(g->x_frag, L.ffn1, nullptr, nullptr, g->ffn_frag, 1));
     }
     {
-      ProfScope ps(m, PF_DEC_GEMM_FFN2, 2.0 * rows * 4.0 * d * d, 2.0 * 4.0 * d * d, st);
+      ProfScope ps(lane->prof, PF_DEC_GEMM_FFN2, 2.0 * rows * 4.0 * d * d, 2.0 * 4.0 * d * d, st);
       if (i8) DG(lin_q(g->ffn, nullptr, L.ffn2, g->x, g->x, 0));
       else DG(lin_f(g->ffn_frag, L.ffn2, g->x, g->x, g->x_frag, 0));
     }
   }
   if (s.need_logits || s.beam_tail) {
-    ProfScope ps(m, PF_DEC_LOGITS, 2.0 * rows * (double)c.n_vocab * d, 2.0 * c.n_vocab * d, st);
+    ProfScope ps(lane->prof, PF_DEC_LOGITS, 2.0 * rows * (double)c.n_vocab * d, 2.0 * c.n_vocab * d, st);
     if (i8) {
       fwk::launch_quant_rows(st, g->x, d, m->dec_ln.g, m->dec_ln.b, g->xq, g->xs, rows, d, 1);
       DG(fwd::launch_dec_logits(st, true, g->xq, g->xs, m->logits.wq, m->logits.wscale, nullptr, nullptr, g->logits,
@@ -566,12 +572,12 @@ static int run_step(Model* m, const GenDev& gp, const StepCfg& s) {
     }
   }
   if (s.nospeech_rowmul > 0) {
-    ProfScope ps(m, PF_DEC_MISC, 0, 0, st);
+    ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
     fwd::launch_nospeech(st, g->logits + (size_t)s.nospeech_off * c.n_vocab, c.n_vocab, s.nospeech_rowmul,
                          c.tok_no_speech, g->no_speech, s.B);
   }
   if (s.beam_tail) {
-    ProfScope ps(m, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
+    ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
@@ -671,11 +677,11 @@ static int64_t self_chunk_capacity(Model* dm, const GenRequest& r) {
   return planned_self_cap(dm) / (rows_per_chunk * run_ctx(dm->cfg, r.o->max_length, r.P));
 }
 
-// Decode run over the concatenated chunks of `reqs` (all mergeable with reqs[0]).  Caller holds m->dec_mu.
-static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
-  int rc = gen_workspace_ensure(m);
+// Decode run over the concatenated chunks of `reqs` (all mergeable with reqs[0]).  Caller holds lane->mu.
+static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest*>& reqs) {
+  int rc = gen_workspace_ensure(m, lane);
   if (rc) return rc;
-  GenWorkspace* g = m->gen;
+  GenWorkspace* g = lane->gen;
   const fw_config& c = m->cfg;
   const GenRequest& r0 = *reqs[0];
   const fw_gen_opts* o = r0.o;
@@ -692,10 +698,10 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
   const int ctx = run_ctx(c, o->max_length, P);
   FW_CHECK_ARG((int64_t)Bx * K * ctx <= g->self_cap, "decode run of %d rows x %d positions exceeds the self-attention cache", Bx * K, ctx);
   FW_HIP(hipSetDevice(m->device));
-  hipStream_t st = m->dec_stream;
+  hipStream_t st = lane->stream;
   // ---- the run's blocks of the cross-attention pool (all at once), the projection of those that are not there yet,
   //      and the run's chunk -> pool slot table ----
-  CrossPool* pool = pool_of(m);
+  CrossPool* pool = m->xpool;
   PoolHold hold{pool, {}, st};
   std::vector<int> slot_host((size_t)Bx);
   {
@@ -708,7 +714,7 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
     pool_acquire(pool, ids, ns, hold.blk, hit);
     int bx = 0;
     for (size_t i = 0; i < reqs.size(); ++i) {
-      if ((rc = ensure_cross_kv(m, reqs[i]->enc, hold.blk[i], hit[i] != 0))) return rc;
+      if ((rc = ensure_cross_kv(m, lane, reqs[i]->enc, hold.blk[i], hit[i] != 0))) return rc;
       for (int b = 0; b < reqs[i]->B; ++b)
         for (int j = 0; j < kv_div; ++j) slot_host[bx++] = hold.blk[i] * pool->EB + b;
     }
@@ -810,7 +816,7 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
         s.rows = Bx; s.kmul = 1; s.tok = blk_tok.empty() ? g->prompt_dev + (size_t)pos * Bx : g->prompt_blk + (size_t)pos * Bx;
         s.nospeech_rowmul = s.need_logits ? 1 : 0;
       }
-      if ((rc = run_step(m, gp, s))) return rc;
+      if ((rc = run_step(m, lane, gp, s))) return rc;
       pos += nb;
     }
   }
@@ -825,14 +831,14 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
     s.nospeech_rowmul = (sot_pos == P - 1 && want_nsp) ? K : 0;
     s.beam_tail = true;
     s.done = g->done;
-    if ((rc = run_step(m, gp, s))) return rc;
+    if ((rc = run_step(m, lane, gp, s))) return rc;
     steps_done = 1;
     s.nospeech_rowmul = 0;
 
     // ---- steps 1.. : one hipGraph replay per step; graphs are cached per GenDev (everything the captured
     //      kernels take by value, kv_div included) ----
     hipGraphExec_t exec = nullptr;
-    if (g->graphs_enabled && !m->prof_on) {
+    if (g->graphs_enabled && !lane->prof.on) {
       for (GraphSlot& gs : g->graphs)
         if (gs.exec && gs.forms == fwd::kernel_forms_epoch() && memcmp(&gs.key, &gp, sizeof(gp)) == 0) {
           exec = gs.exec; gs.stamp = ++g->graph_clock;
@@ -840,7 +846,7 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
       if (!exec) {
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int rc2 = run_step(m, gp, s);
+          const int rc2 = run_step(m, lane, gp, s);
           const hipError_t e2 = hipStreamEndCapture(st, &graph);
           hipGraphExec_t ne = nullptr;
           if (rc2 == FW_OK && e2 == hipSuccess && graph && hipGraphInstantiate(&ne, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -871,7 +877,7 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
             set_error("hipGraphLaunch failed: %s", hipGetErrorString(he));
             return FW_ERUNTIME;
           }
-        } else if ((rc = run_step(m, gp, s))) {
+        } else if ((rc = run_step(m, lane, gp, s))) {
           return rc;
         }
       }
@@ -883,7 +889,7 @@ static int generate_run(Model* m, const std::vector<GenRequest*>& reqs) {
   }
   FW_HIP(hipStreamSynchronize(st));
   if ((rc = check_launch("decode loop"))) return rc;
-  prof_collect(m);
+  prof_collect(lane->prof);
 
   // ---- finalize on the host: best num_hypotheses by normalised score (stable) ----
   std::vector<int> n_fin(Bx), fin_len((size_t)Bx * FIN_CAP);
@@ -992,8 +998,8 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
 
   DecodeGroup& grp = dm->grp;
   std::unique_lock<std::mutex> lk(grp.mu);
-  // fw_model_set_decode_batch rebuilds the workspaces and the second lane under grp.resizing: nothing is read from
-  // them (capacities, dm->lane1) and nothing is queued until it is done
+  // fw_model_set_decode_batch rebuilds the workspaces and the lanes under grp.resizing: nothing is read from
+  // them (capacities, dm->lanes) and nothing is queued until it is done
   while (grp.resizing) grp.cv.wait(lk);
   {
     // this call alone must fit a lane (rows and self-attention cache), so that a call that cannot is refused here,
@@ -1012,7 +1018,7 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
   grp.queue.push_back(&req);
   grp.last_arrival = std::chrono::steady_clock::now();
   while (!req.done) {
-    const int n_lanes = n_lanes_of(dm);        // (read under grp.mu: stable while a request is queued, see above)
+    const int n_lanes = (int)dm->lanes.size();       // (read under grp.mu: stable while a request is queued, see above)
     if (req.taken || grp.gathering || grp.active_runs >= std::min(n_lanes, grp.lanes_enabled.load())) {
       grp.cv.wait(lk);
       continue;
@@ -1076,8 +1082,9 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
       }
     }
     int lane = 0;
-    while (lane + 1 < n_lanes && grp.lane_busy[lane]) ++lane;    // the first free lane (active_runs < lanes: there is one)
-    grp.lane_busy[lane] = true;
+    while (lane + 1 < n_lanes && dm->lanes[lane]->busy) ++lane;    // the first free lane (active_runs < lanes: one is)
+    DecodeLane* dl = dm->lanes[lane].get();    // own workspace, own stream; the weights and the pool are dm's
+    dl->busy = true;
     grp.active_runs += 1;
     grp.gathering = false;
     grp.cv.notify_all();                    // (the next leader may gather while this run decodes)
@@ -1092,9 +1099,8 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
     static const bool run_log = [] { const char* e = getenv("FWAMD_RUN_LOG"); return e && atoi(e) != 0; }();
     const auto t_run0 = std::chrono::steady_clock::now();
     {
-      Model* lm = lane_model(dm, lane);     // the lane's model: own workspace, own stream, same weights
-      std::lock_guard<std::mutex> dl(lm->dec_mu);
-      rc = generate_run(lm, batch);
+      std::lock_guard<std::mutex> run_lk(dl->mu);
+      rc = generate_run(dm, dl, batch);
     }
     if (run_log) {
       const auto t_run1 = std::chrono::steady_clock::now();
@@ -1106,7 +1112,7 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
     const std::string err = rc ? fw_last_error() : "";
     lk.lock();
     for (GenRequest* r : batch) { r->rc = rc; r->err = err; r->done = true; }
-    grp.lane_busy[lane] = false;
+    dl->busy = false;
     grp.active_runs -= 1;
     grp.cv.notify_all();
   }
@@ -1124,19 +1130,20 @@ int32_t fw_detect_language(fw_model* fm, const fw_tensor* enc_t, int32_t B, int3
   FW_CHECK_ARG(c.is_multilingual && c.n_langs > 0, "detect_language needs a multilingual model");
   FW_CHECK_ARG(enc->owner && decoder_of(enc->owner) == m && B == enc->B && B <= m->max_batch,
                "bad encoder output / batch");
-  std::lock_guard<std::mutex> lk(m->dec_mu);
+  DecodeLane* lane = m->lanes[0].get();
+  std::lock_guard<std::mutex> lk(lane->mu);
   FW_HIP(hipSetDevice(m->device));
   int rc;
-  if ((rc = gen_workspace_ensure(m))) return rc;
-  GenWorkspace* g = m->gen;
-  hipStream_t st = m->dec_stream;
-  CrossPool* pool = pool_of(m);
+  if ((rc = gen_workspace_ensure(m, lane))) return rc;
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  CrossPool* pool = m->xpool;
   PoolHold hold{pool, {}, st};
   std::vector<int> slots(B);
   {
     std::vector<char> hit;
     pool_acquire(pool, {enc->id}, {enc->B}, hold.blk, hit);
-    if ((rc = ensure_cross_kv(m, enc, hold.blk[0], hit[0] != 0))) return rc;
+    if ((rc = ensure_cross_kv(m, lane, enc, hold.blk[0], hit[0] != 0))) return rc;
     for (int b = 0; b < B; ++b) slots[b] = hold.blk[0] * pool->EB + b;
   }
   FW_HIP(hipMemcpyAsync(g->slot_map, slots.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1153,13 +1160,13 @@ int32_t fw_detect_language(fw_model* fm, const fw_tensor* enc_t, int32_t B, int3
   s.rows = B; s.kmul = 1; s.B = B; s.pos_fixed = 0; s.P = 1; s.tok = g->prompt_dev;
   s.need_logits = true; s.nospeech_rowmul = 0; s.beam_tail = false; s.done = g->zero_done;
   // rows of a prefill-style step use beam slot 0 of chunk b: slot stride is max_beam
-  if ((rc = run_step(m, gp, s))) return rc;
+  if ((rc = run_step(m, lane, gp, s))) return rc;
   std::vector<float> lg((size_t)B * c.n_langs);
   FW_HIP(hipMemcpy2DAsync(lg.data(), c.n_langs * sizeof(float), g->logits + c.tok_lang_begin,
                           (size_t)c.n_vocab * sizeof(float), c.n_langs * sizeof(float), B, hipMemcpyDeviceToHost, st));
   FW_HIP(hipStreamSynchronize(st));
   if ((rc = check_launch("detect_language"))) return rc;
-  prof_collect(m);
+  prof_collect(lane->prof);
   for (int b = 0; b < B; ++b) {
     const float* r = &lg[(size_t)b * c.n_langs];
     float mx = r[0];
@@ -1333,19 +1340,20 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   const int n_sel = (int)sel_heads.size();
   FW_CHECK_ARG(n_sel > 0, "no alignment heads");
 
-  std::lock_guard<std::mutex> lk(m->dec_mu);
+  DecodeLane* lane = m->lanes[0].get();
+  std::lock_guard<std::mutex> lk(lane->mu);
   FW_HIP(hipSetDevice(m->device));
   int rc;
-  if ((rc = gen_workspace_ensure(m))) return rc;
-  GenWorkspace* g = m->gen;
-  hipStream_t st = m->dec_stream;
-  CrossPool* pool = pool_of(m);
+  if ((rc = gen_workspace_ensure(m, lane))) return rc;
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  CrossPool* pool = m->xpool;
   PoolHold hold{pool, {}, st};
   std::vector<int> slots(B);
   {
     std::vector<char> hit;
     pool_acquire(pool, {enc->id}, {enc->B}, hold.blk, hit);
-    if ((rc = ensure_cross_kv(m, enc, hold.blk[0], hit[0] != 0))) return rc;
+    if ((rc = ensure_cross_kv(m, lane, enc, hold.blk[0], hit[0] != 0))) return rc;
     for (int b = 0; b < B; ++b) slots[b] = hold.blk[0] * pool->EB + b;
   }
   const int kv_slot0 = slots[0];
@@ -1436,7 +1444,7 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
     s.sel_heads_dev = heads_dev; s.sel_layer_off = layer_off.data(); s.probs = probs; s.n_sel_total = n_sel;
     s.kv_slot0 = kv_slot0;
     s.n_tok = max_tok; s.tok_idx = pos;
-    if ((rc = run_step(m, gp, s))) { cleanup(); return rc; }
+    if ((rc = run_step(m, lane, gp, s))) { cleanup(); return rc; }
     for (int j = 0; j < nb && any_target; ++j) {
       bool tj = false;
       for (int b = 0; b < B; ++b) tj |= target[(size_t)(pos + j) * B + b] >= 0;
@@ -1457,7 +1465,7 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
     set_error("align failed: %s", hipGetErrorString(he));
     return FW_ERUNTIME;
   }
-  prof_collect(m);
+  prof_collect(lane->prof);
   const int n0 = n_start + 1;
   for (int b = 0; b < B; ++b) {
     const int nt = ntok[b] - n0 - 1;

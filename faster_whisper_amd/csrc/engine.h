@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -116,6 +117,18 @@ struct ProfAcc {
   double ms = 0; int64_t launches = 0; double flops = 0; double bytes = 0;
 };
 
+// One profiling recorder, for the scopes of ONE stream: the model has one for its encoder stream, every decode lane one
+// for its own.  The mutex is there for the readers (fw_prof_get / fw_prof_reset, any thread).
+struct Prof {
+  std::mutex mu;
+  bool on = false;
+  ProfAcc acc[PF_COUNT];
+  struct PendingEv { hipEvent_t a, b; int fam; };
+  std::vector<PendingEv> pending;
+  std::vector<hipEvent_t> ev_pool;
+  ~Prof();
+};
+
 struct Model;
 struct Tensor {  // fw_tensor
   Model* owner = nullptr;
@@ -128,6 +141,20 @@ struct GenWorkspace;  // decoder-side buffers of one decode lane (decoder.hip)
 struct GenRequest;    // one fw_generate call waiting to be decoded (decoder.hip)
 struct CrossPool;     // cross-attention K / V^T of the encoder outputs in flight, shared by the lanes (decoder.hip)
 
+// Decode LANE of a decode group: a decode workspace, the stream its runs are launched on (and `spare`); n lanes: n runs
+// in flight, the HBM-bound cross-attention of one beside the linears of the other: two lanes +8 % (profiles/
+// r03_two_groups_probe.txt; 3 / 4 lanes: r06_ab_lanes.jsonl).  Config, weights, pool and sizes are the model's.
+constexpr int kMaxDecodeLanes = 4;
+struct DecodeLane {
+  GenWorkspace* gen = nullptr;    // created on first use, or by fw_model_set_decode_batch (decoder.hip)
+  hipStream_t stream = nullptr;   // created with the workspace (role "DEC") and kept until the lane goes
+  hipStream_t spare = nullptr;    // lanes 1 ..: IDLE second stream; four lanes are 4.5 % slower without
+  std::mutex mu;                  // held by whoever runs on the lane: a decode run, fw_detect_language, fw_align
+  Prof prof;                      // the decode scopes recorded on `stream`
+  bool busy = false;              // a run of the group has taken the lane (under DecodeGroup::mu)
+  ~DecodeLane();                  // waits for the stream, then frees the workspace and the streams (decoder.hip)
+};
+
 // Decode group of a device: the worker replicas that share one decode workspace.  Concurrent fw_generate calls
 // with identical options are merged into ONE decode run (their rows share every weight byte streamed per step);
 // the first caller that finds no run in progress leads it, the others wait for their results.
@@ -136,10 +163,9 @@ struct DecodeGroup {
   std::condition_variable cv;
   std::deque<GenRequest*> queue;
   bool gathering = false;         // a caller is collecting the requests of the next run (one at a time)
-  bool resizing = false;          // fw_model_set_decode_batch is rebuilding the workspaces / the second lane: callers wait
+  bool resizing = false;          // fw_model_set_decode_batch is rebuilding the workspaces / the lanes: callers wait
   int active_runs = 0;            // runs in flight (<= lanes of the group)
-  bool lane_busy[4] = {false, false, false, false};
-  std::atomic<int> lanes_enabled{4};   // fw_model_set_decode_lanes: runs allowed in flight (1 .. the lanes the group has)
+  std::atomic<int> lanes_enabled{kMaxDecodeLanes};   // fw_model_set_decode_lanes: runs allowed in flight
   std::atomic<int> encoding{0};   // member encodes in flight: requests that are about to arrive
   std::chrono::steady_clock::time_point last_arrival{};   // when the newest request was queued
   std::mutex enc_mu;              // one encoder pass at a time per device
@@ -206,23 +232,15 @@ struct Model {
   float* ws_xs = nullptr;                             //               its per-row scales [B*1500]
   int t_pad = 0;
 
-  // decode side.  A model either owns a decode workspace (gen, created on first use with room for decode_batch
-  // chunks, run on dec_stream under dec_mu) or has joined another model of the same device (decoder != null).
-  GenWorkspace* gen = nullptr;
+  // decode side.  A model either owns a decode group (lanes[0] from model creation, its workspace built on first use
+  // for decode_batch chunks; fw_model_set_decode_batch adds lanes) or has joined another model's (decoder != null).
+  // Only that rebuild changes the vector: fw_generate waits for it, fw_prof_* and fw_synchronize must not run beside.
+  std::vector<std::unique_ptr<DecodeLane>> lanes;
   Model* decoder = nullptr;
-  // Second decode LANE of a decode group (fw_model_set_decode_batch with room for >= 4 encoder batches): an internal,
-  // decoder-only model on the same weight blob with a workspace and a stream of its own, so that TWO decode runs of the
-  // group are in flight at once — the cross-attention stream of one (HBM-bound) beside the linears of the other:
-  // measured +8 % (profiles/r03_two_groups_probe.txt).  Owned by the primary; never visible through the C ABI.
-  // (FWAMD_DECODE_LANES = 3 / 4 builds further lanes of the same kind — measurement knob, profiles/r06_ab_lanes.jsonl)
-  Model* lane1 = nullptr;        // = xlanes[0]
-  Model* xlanes[3] = {nullptr, nullptr, nullptr};   // lanes 1 .. 3
-  bool is_lane = false;
-  // The cross-attention K / V^T cache is ONE pool per decode group (owned by the primary, borrowed by the second lane):
-  // blocks of max_batch chunk slots, one block per encoder output in flight, handed to whichever lane decodes the
-  // request — so both lanes can run full-size runs without each holding a cache of its own.
+  // The cross-attention K / V^T cache is ONE pool per decode group: blocks of max_batch chunk slots, one block per
+  // encoder output in flight, handed to whichever lane decodes the request — so every lane can run full-size runs
+  // without holding a cache of its own.
   CrossPool* xpool = nullptr;
-  Model* pool_owner = nullptr;   // a lane: the primary whose pool it reads
   int decode_batch = 0;          // chunk slots of the pool (= encoder chunks the group keeps in flight)
   int lane_batch = 0;            // chunks ONE decode run (one lane's workspace) holds; 0: decode_batch
   int decode_self_ctx = 0;   // self-attention cache positions per row at full row capacity (0 = the text context)
@@ -230,31 +248,23 @@ struct Model {
   bool free_deferred = false;   // fw_model_free was called while dependents > 0: freed with the last dependent
   void* self = nullptr;         // the fw_model this Model lives in
   Model* blob_owner = nullptr;  // the model whose blob this one borrows (fw_model_create_from_blob_dev on fw_model_blob)
-  hipStream_t dec_stream = nullptr;
-  std::mutex dec_mu;
   DecodeGroup grp;
 
   // pooled encoder-output buffers ([max_batch][T][d] each)
   std::mutex pool_mu;
   std::vector<half_t*> enc_pool;
 
-  // profiling.  The encoder thread of the model (under mu) and the leader of a decode run (under dec_mu, any worker
-  // thread) both record scopes on the same model, so the event lists have a mutex of their own.
-  std::mutex prof_mu;
-  bool prof_on = false;
-  ProfAcc prof[PF_COUNT];
-  struct PendingEv { hipEvent_t a, b; int fam; };
-  std::vector<PendingEv> pending;
-  std::vector<hipEvent_t> ev_pool;
+  Prof prof;   // the encoder's scopes (recorded on `stream` under mu); the decode scopes are the lanes'
 };
 
-// profiling scope: brackets a group of launches with HIP events on the model's stream
+// profiling scope: brackets a group of launches with HIP events on st, the stream p's owner launches on
 struct ProfScope {
-  Model* m; int fam; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-  ProfScope(Model* m_, int fam_, double flops, double bytes, hipStream_t st_ = nullptr);   // null: m->stream
+  Prof* p; int fam; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
+  ProfScope(Prof& p_, int fam_, double flops, double bytes, hipStream_t st_);
+  ProfScope(Model* m, int fam_, double flops, double bytes) : ProfScope(m->prof, fam_, flops, bytes, m->stream) {}
   ~ProfScope();
 };
-void prof_collect(Model* m);
+void prof_collect(Prof& p);   // waits for the scopes recorded so far and adds their times
 
 int dev_alloc(void** p, size_t bytes);
 // a non-blocking stream at the priority the environment variable `env` names ("high" / "low"; anything else, or unset:
@@ -290,8 +300,10 @@ int run_encoder(Model* m, int B, half_t* out);
 // decoder entry points (decoder.hip)
 void set_pos_blocks(int on);                  // fw_test_knob(4, ..): position blocks for the prompt forward and align
 uint64_t next_tensor_id();
-int gen_workspace_ensure(Model* dm);          // creates dm's decode workspace on first use (caller holds dm->dec_mu)
-void gen_workspace_free(Model* m);
+int gen_workspace_ensure(Model* dm, DecodeLane* lane);   // built on first use (caller holds lane->mu)
+int cross_pool_ensure(Model* dm, int pool_chunks);   // the two steps at explicit sizes (fw_model_set_decode_batch)
+int gen_workspace_build(const Model* dm, DecodeLane* lane, int lane_chunks, int self_ctx);
+void gen_workspace_free(DecodeLane* lane);
 // HBM of one lane's workspace for runs of up to lane_chunks chunks (self_ctx 0 = the text context) — without the
 // cross-attention pool, which is cross_pool_bytes(m, pool_chunks) once per group
 int64_t gen_workspace_bytes(const Model* m, int lane_chunks, int self_ctx);
@@ -303,12 +315,6 @@ void cross_pool_free(Model* m);
 void launch_align_post(hipStream_t st, const float* probs, float* stats, int n_sel, int n_tok_cap, int T, int B,
                        const int* n_tok, const int* nfr, int width, float* mat);
 inline Model* decoder_of(Model* m) { return m->decoder ? m->decoder : m; }
-inline int n_lanes_of(const Model* m) {
-  int n = 1;
-  for (const Model* l : m->xlanes) n += l ? 1 : 0;
-  return n;
-}
-inline Model* lane_model(Model* m, int lane) { return lane == 0 ? m : m->xlanes[lane - 1]; }
 inline int lane_chunks_of(const Model* m) {
   const int b = m->lane_batch > 0 ? m->lane_batch : m->decode_batch;
   return b > m->max_batch ? b : m->max_batch;

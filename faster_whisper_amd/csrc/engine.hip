@@ -44,55 +44,63 @@ static const char* kProfNames[PF_COUNT] = {
     "logmel", "enc_gemm", "enc_attn", "enc_layernorm", "cross_kv_gemm", "dec_gemm_qkv", "dec_gemm_dxd",
     "dec_gemm_ffn1", "dec_gemm_ffn2", "dec_self_attn", "dec_cross_attn", "dec_logits", "dec_sample", "dec_misc"};
 
-static hipEvent_t ev_get(Model* m) {
-  if (!m->ev_pool.empty()) {
-    hipEvent_t e = m->ev_pool.back();
-    m->ev_pool.pop_back();
+static hipEvent_t ev_get(Prof& p) {
+  if (!p.ev_pool.empty()) {
+    hipEvent_t e = p.ev_pool.back();
+    p.ev_pool.pop_back();
     return e;
   }
   hipEvent_t e;
   (void)hipEventCreate(&e);
   return e;
 }
-ProfScope::ProfScope(Model* m_, int fam_, double flops, double bytes, hipStream_t st_)
-    : m(m_), fam(fam_), st(st_ ? st_ : m_->stream) {
-  if (!m->prof_on) return;
+ProfScope::ProfScope(Prof& p_, int fam_, double flops, double bytes, hipStream_t st_) : p(&p_), fam(fam_), st(st_) {
+  if (!p->on) return;
   {
-    std::lock_guard<std::mutex> lk(m->prof_mu);
-    a = ev_get(m);
-    b = ev_get(m);
-    m->prof[fam].flops += flops;
-    m->prof[fam].bytes += bytes;
-    m->prof[fam].launches += 1;
+    std::lock_guard<std::mutex> lk(p->mu);
+    a = ev_get(*p);
+    b = ev_get(*p);
+    p->acc[fam].flops += flops;
+    p->acc[fam].bytes += bytes;
+    p->acc[fam].launches += 1;
   }
   (void)hipEventRecord(a, st);
 }
 ProfScope::~ProfScope() {
   if (!a) return;
   (void)hipEventRecord(b, st);
-  std::lock_guard<std::mutex> lk(m->prof_mu);
-  m->pending.push_back({a, b, fam});
+  std::lock_guard<std::mutex> lk(p->mu);
+  p->pending.push_back({a, b, fam});
 }
-void prof_collect(Model* m) {
-  // the events are waited for outside the lock (a scope of the other stream may be recorded meanwhile)
-  std::vector<Model::PendingEv> todo;
+void prof_collect(Prof& p) {
+  // the events are waited for outside the lock (a reader may ask for the totals meanwhile)
+  std::vector<Prof::PendingEv> todo;
   {
-    std::lock_guard<std::mutex> lk(m->prof_mu);
-    todo.swap(m->pending);
+    std::lock_guard<std::mutex> lk(p.mu);
+    todo.swap(p.pending);
   }
   std::vector<std::pair<int, float>> got;
-  for (auto& p : todo) {
-    (void)hipEventSynchronize(p.b);
+  for (auto& e : todo) {
+    (void)hipEventSynchronize(e.b);
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, p.a, p.b);
-    got.push_back({p.fam, ms});
+    (void)hipEventElapsedTime(&ms, e.a, e.b);
+    got.push_back({e.fam, ms});
   }
-  std::lock_guard<std::mutex> lk(m->prof_mu);
-  for (auto& g : got) m->prof[g.first].ms += g.second;
-  for (auto& p : todo) {
-    m->ev_pool.push_back(p.a);
-    m->ev_pool.push_back(p.b);
+  std::lock_guard<std::mutex> lk(p.mu);
+  for (auto& g : got) p.acc[g.first].ms += g.second;
+  for (auto& e : todo) {
+    p.ev_pool.push_back(e.a);
+    p.ev_pool.push_back(e.b);
   }
+}
+Prof::~Prof() {
+  for (auto& e : pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
+  for (auto e : ev_pool) (void)hipEventDestroy(e);
+}
+template <typename F>   // f on the model's recorder and on every decode lane's
+static void for_each_prof(Model* m, F&& f) {
+  f(m->prof);
+  for (auto& l : m->lanes) f(l->prof);
 }
 
 // ---------------------------------------------------------------- blob packing
@@ -659,7 +667,7 @@ static int alloc_workspaces(Model* m) {
 }
 
 static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned, int device, int max_batch,
-                           int max_beam, fw_model** out, bool decoder_lane = false) {
+                           int max_beam, fw_model** out) {
   FW_CHECK_ARG(max_batch >= 1 && max_batch <= 256, "max_batch must be in [1,256], got %d", max_batch);
   FW_CHECK_ARG(max_beam >= 1 && max_beam <= 16, "max_beam must be in [1,16], got %d", max_beam);
   FW_CHECK_ARG(max_batch * max_beam <= 2048, "max_batch * max_beam must be <= 2048 decoder rows, got %d", max_batch * max_beam);
@@ -678,6 +686,8 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
                    entries.size() * sizeof(BlobEntry), hipMemcpyDeviceToHost));
   fw_model* fm = new fw_model();
   Model* m = &fm->impl;
+  m->lanes.reserve(kMaxDecodeLanes);   // (lanes[0] stays put while a rebuild appends; other readers: see engine.h)
+  m->lanes.emplace_back(new DecodeLane());
   m->cfg = h.cfg;
   m->compute_type = h.compute_type;
   if (h.reserved != 6) {
@@ -700,13 +710,12 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
     m->tensors[e.name] = t;
   }
   auto fail = [&](int code) { fw_model_free(fm); return code; };
-  hipError_t he = create_stream(&m->stream, decoder_lane ? "DEC" : "ENC");
+  hipError_t he = create_stream(&m->stream, "ENC");
   if (he != hipSuccess) {
     set_error("hipStreamCreate failed: %s", hipGetErrorString(he));
     return fail(FW_ENODEV);
   }
   if ((rc = bind_weights(m))) return fail(rc);
-  m->is_lane = decoder_lane;
   {
     const char* lu = getenv("FWAMD_LN_UNFOLD");   // fp16 evaluation order of the decoder LayerNorms (engine.h)
     if (lu && lu[0] >= '0' && lu[0] <= '2' && !lu[1]) m->ln_unfold = lu[0] - '0';
@@ -716,10 +725,8 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
       return fail(FW_EINVAL);
     }
   }
-  if (!decoder_lane) {   // (a decode lane has no front end and no encoder: weights, a stream, a decode workspace)
-    if ((rc = setup_logmel_consts(m))) return fail(rc);
-    if ((rc = alloc_workspaces(m))) return fail(rc);
-  }
+  if ((rc = setup_logmel_consts(m))) return fail(rc);
+  if ((rc = alloc_workspaces(m))) return fail(rc);
   m->decode_batch = max_batch;   // the decode workspace itself is created on first use (decoder.hip)
   he = hipDeviceSynchronize();
   if (he != hipSuccess) {
@@ -730,10 +737,10 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
     // a model on a borrowed blob (fw_model_create_from_blob_dev on fw_model_blob's pointer) keeps the owner alive:
     // fw_model_free(owner) is deferred until its last dependent is gone
     std::lock_guard<std::mutex> lk(g_models_mu_ref());
-    if (!owned && !decoder_lane)
+    if (!owned)
       for (Model* o : g_live_models_ref())
         if (o->blob == m->blob && o->blob_owned) { m->blob_owner = o; o->dependents += 1; break; }
-    if (!decoder_lane) g_live_models_ref().push_back(m);   // (a lane lives and dies with its primary)
+    g_live_models_ref().push_back(m);
   }
   m->self = fm;
   *out = fm;
@@ -1137,16 +1144,9 @@ void fw_model_free(fw_model* fm) {
     release[1] = m->decoder;
   }
   (void)hipSetDevice(m->device);
-  for (Model*& l : m->xlanes) {
-    if (l) fw_model_free(static_cast<fw_model*>(l->self));
-    l = nullptr;
-  }
-  m->lane1 = nullptr;
   if (m->stream) (void)hipStreamSynchronize(m->stream);
-  if (m->dec_stream) (void)hipStreamSynchronize(m->dec_stream);
-  gen_workspace_free(m);
-  cross_pool_free(m);       // (a lane has none of its own: it reads the primary's)
-  if (m->dec_stream) (void)hipStreamDestroy(m->dec_stream);
+  m->lanes.clear();         // (each waits for its stream first)
+  cross_pool_free(m);
   for (half_t* p : m->enc_pool) (void)hipFree(p);
   m->enc_pool.clear();
   void* ptrs[] = {m->lm_consts, m->lm_filtT, m->ws_pcm, m->ws_offsets, m->ws_raw, m->ws_chunk_max, m->ws_nframes,
@@ -1155,8 +1155,6 @@ void fw_model_free(fw_model* fm) {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (m->blob && m->blob_owned) (void)hipFree(m->blob);
-  for (auto& p : m->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-  for (auto e : m->ev_pool) (void)hipEventDestroy(e);
   if (m->stream) (void)hipStreamDestroy(m->stream);
   delete fm;
   for (Model* t : release) {
@@ -1199,9 +1197,9 @@ int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
   FW_CHECK_ARG(!m->decoder, "this model has joined another model's decoder");
   FW_CHECK_ARG(decode_batch >= 1, "decode_batch must be positive");
   {
-    // The workspaces, the pool and the second lane's model are rebuilt below: not while the group has work, and no
-    // fw_generate call may read capacities / dm->lane1 or queue a request until the rebuild is done (grp.resizing:
-    // callers wait on grp.cv).  fw_detect_language / fw_align hold dec_mu, which the rebuild takes.
+    // The workspaces, the pool and the lanes are rebuilt below: not while the group has work, and no fw_generate
+    // call may read capacities / dm->lanes or queue a request until the rebuild is done (grp.resizing: callers wait
+    // on grp.cv).  fw_detect_language / fw_align hold the mutex of lanes[0], which the rebuild takes.
     std::lock_guard<std::mutex> gl(m->grp.mu);
     FW_CHECK_ARG(m->grp.active_runs == 0 && !m->grp.gathering && m->grp.queue.empty() && !m->grp.resizing,
                  "decode runs are queued or in flight: set the decode batch before the first generate call or after the last one returned");
@@ -1214,19 +1212,20 @@ int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
       g.cv.notify_all();
     }
   } done{m->grp};
-  std::lock_guard<std::mutex> lk(m->dec_mu);
+  DecodeLane* lane0 = m->lanes[0].get();   // (stays through the rebuild: its mutex is held)
+  std::lock_guard<std::mutex> lk(lane0->mu);
   FW_HIP(hipSetDevice(m->device));
   // Sizes, in 70 % of the free HBM:
   //   pool   = the cross-attention K / V^T of `decode_batch` chunks (whole encoder batches, at least one): what the
   //            workers of the group keep in flight, ONE copy whatever the number of lanes;
-  //   lanes  = two (two concurrent decode runs, engine.h: lane1) when the group holds at least four encoder batches,
+  //   lanes  = two (two concurrent decode runs: DecodeLane) when the group holds at least four encoder batches,
   //            each with a workspace for the largest run there can be: the pool's chunks, at most DEC_GROUP_RUN_ROWS rows
   //            (decoder.hip caps runs there; one lane: 2048 rows).  The self-attention cache of a lane is rows x
   //            positions and a RUN lays it out for its own max_length, so when the budget is short the positions per
   //            row are lowered first (down to 160: a run that asks for more simply holds fewer rows), then the pool.
   int want = std::max(decode_batch, m->max_batch) / m->max_batch * m->max_batch;
   int lanes_wanted = 2;
-  if (const char* e = getenv("FWAMD_DECODE_LANES")) lanes_wanted = std::min(4, std::max(1, atoi(e)));
+  if (const char* e = getenv("FWAMD_DECODE_LANES")) lanes_wanted = std::min(kMaxDecodeLanes, std::max(1, atoi(e)));
   const int n_lanes = want >= 4 * m->max_batch ? lanes_wanted : 1;
   const int max_rows = n_lanes >= 2 ? DEC_GROUP_RUN_ROWS : 2048;
   auto lane_of = [&](int pool_chunks) {
@@ -1236,9 +1235,8 @@ int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
   };
   size_t free_b = 0, total_b = 0;
   FW_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (m->gen) free_b += (size_t)gen_workspace_bytes(m, lane_chunks_of(m), m->decode_self_ctx);
-  for (const Model* l : m->xlanes)
-    if (l && l->gen) free_b += (size_t)gen_workspace_bytes(l, lane_chunks_of(l), l->decode_self_ctx);
+  for (const auto& l : m->lanes)
+    if (l->gen) free_b += (size_t)gen_workspace_bytes(m, lane_chunks_of(m), m->decode_self_ctx);
   if (m->xpool) free_b += (size_t)cross_pool_bytes(m, std::max(m->decode_batch, m->max_batch));
   const int64_t budget = (int64_t)(0.7 * (double)free_b);
   const int NT = m->cfg.n_text_ctx;
@@ -1254,35 +1252,35 @@ int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
     want -= m->max_batch;
   }
   const int lane_batch = lane_of(want);
-  const bool lanes_ok = n_lanes == n_lanes_of(m);
-  if (m->gen && m->xpool && lanes_ok && want == m->decode_batch && lane_batch == lane_chunks_of(m) &&
+  const bool lanes_ok = n_lanes == (int)m->lanes.size();
+  if (lane0->gen && m->xpool && lanes_ok && want == m->decode_batch && lane_batch == lane_chunks_of(m) &&
       self_ctx == m->decode_self_ctx)
     return FW_OK;
-  if (m->dec_stream) FW_HIP(hipStreamSynchronize(m->dec_stream));
-  gen_workspace_free(m);
-  for (Model*& l : m->xlanes) {
-    if (l) fw_model_free(static_cast<fw_model*>(l->self));
-    l = nullptr;
+  if (lane0->stream) FW_HIP(hipStreamSynchronize(lane0->stream));
+  // The old state goes first (its HBM is in the budget): the group is as fw_model_create made it, one lane without a
+  // workspace, no pool, one encoder batch.  All is then built at the new sizes and committed together, or reset again.
+  auto reset = [&] {
+    m->lanes.resize(1);
+    gen_workspace_free(lane0);
+    cross_pool_free(m);
+    m->decode_batch = m->max_batch; m->lane_batch = 0; m->decode_self_ctx = 0;
+  };
+  reset();
+  std::vector<std::unique_ptr<DecodeLane>> further;   // lanes 1 .. n_lanes - 1 (freed with the vector on failure)
+  int rc = cross_pool_ensure(m, want);
+  if (!rc) rc = gen_workspace_build(m, lane0, lane_batch, self_ctx);
+  for (int k = 1; !rc && k < n_lanes; ++k) {
+    further.emplace_back(new DecodeLane());
+    further.back()->prof.on = m->prof.on;
+    // Nothing launches on `spare`, but without it four lanes lose 4.5 % (bench --decode-lanes 4, FWAMD_DECODE_LANES=4,
+    // alternating: with 3 136 3 230 3 220 3 217x, without 3 010 3 083 3 079 3 068x; two lanes: the same)
+    const hipError_t he = create_stream(&further.back()->spare, "DEC");
+    if (he != hipSuccess) set_error("hipStreamCreate failed: %s", hipGetErrorString(he));
+    rc = he != hipSuccess ? FW_ENODEV : gen_workspace_build(m, further.back().get(), lane_batch, self_ctx);
   }
-  m->lane1 = nullptr;
-  cross_pool_free(m);
-  m->decode_batch = want;
-  m->lane_batch = lane_batch;
-  m->decode_self_ctx = self_ctx;
-  int rc = gen_workspace_ensure(m);     // (creates the pool too)
-  if (rc) return rc;
-  for (int k = 1; k < n_lanes; ++k) {
-    fw_model* l = nullptr;
-    if ((rc = model_from_blob(m->blob, m->blob_bytes, false, m->device, m->max_batch, m->max_beam, &l, true))) return rc;
-    l->impl.decode_batch = want;
-    l->impl.lane_batch = lane_batch;
-    l->impl.decode_self_ctx = self_ctx;
-    l->impl.pool_owner = m;
-    l->impl.prof_on = m->prof_on;
-    if ((rc = gen_workspace_ensure(&l->impl))) { fw_model_free(l); return rc; }
-    m->xlanes[k - 1] = &l->impl;
-  }
-  m->lane1 = m->xlanes[0];
+  if (rc) { reset(); return rc; }
+  m->decode_batch = want; m->lane_batch = lane_batch; m->decode_self_ctx = self_ctx;
+  for (auto& l : further) m->lanes.push_back(std::move(l));
   return FW_OK;
 }
 
@@ -1292,8 +1290,8 @@ int32_t fw_model_set_decode_lanes(fw_model* fm, int32_t lanes) {
   int have;
   {
     std::lock_guard<std::mutex> gl(dm->grp.mu);     // (the lanes are rebuilt under grp.resizing)
-    have = std::max(2, n_lanes_of(dm));             // (a group that has not built its second lane yet still takes 2 ...
-    if (const char* e = getenv("FWAMD_DECODE_LANES")) have = std::max(have, std::min(4, atoi(e)));   // ... or what it will build)
+    have = std::max(2, (int)dm->lanes.size());   // (a group that has not built its second lane yet still takes 2 ...
+    if (const char* e = getenv("FWAMD_DECODE_LANES")) have = std::max(have, std::min(kMaxDecodeLanes, atoi(e)));   // ... or what it will build)
   }
   FW_CHECK_ARG(lanes >= 1 && lanes <= have, "decode lanes: 1 .. %d", have);
   dm->grp.lanes_enabled.store(lanes);
@@ -1340,10 +1338,11 @@ int32_t fw_model_join_decoder(fw_model* fm, fw_model* decoder) {
   FW_CHECK_ARG(m->device == d->device && m->blob == d->blob && m->max_batch == d->max_batch && m->max_beam == d->max_beam,
                "models that share a decoder must share device, weight blob, max_batch and max_beam");
   FW_CHECK_ARG(!m->decoder, "this model has already joined a decoder");
-  std::lock_guard<std::mutex> lk(m->dec_mu);
+  DecodeLane* lane = m->lanes[0].get();
+  std::lock_guard<std::mutex> lk(lane->mu);
   FW_HIP(hipSetDevice(m->device));
-  if (m->dec_stream) FW_HIP(hipStreamSynchronize(m->dec_stream));
-  gen_workspace_free(m);
+  if (lane->stream) FW_HIP(hipStreamSynchronize(lane->stream));
+  gen_workspace_free(lane);
   cross_pool_free(m);
   {
     std::lock_guard<std::mutex> lk2(g_models_mu);   // the primary outlives its workers (fw_model_free defers)
@@ -1459,7 +1458,7 @@ int32_t fw_encode(fw_model* fm, const float* features, int32_t B, fw_tensor** ou
     set_error("encode failed: %s", hipGetErrorString(he));
     return FW_ERUNTIME;
   }
-  prof_collect(m);
+  prof_collect(m->prof);
   *out = t;
   return FW_OK;
 }
@@ -1479,7 +1478,7 @@ static int encode_pcm_common(Model* m, const float* pcm_dev, const int64_t* offs
     set_error("encode_pcm failed: %s", hipGetErrorString(he));
     return FW_ERUNTIME;
   }
-  prof_collect(m);
+  prof_collect(m->prof);
   *out = t;
   return FW_OK;
 }
@@ -1582,40 +1581,27 @@ void fw_tensor_free(fw_tensor* t) {
 // ---------------------------------------------------------------- measurement hooks
 void fw_prof_enable(fw_model* fm, int32_t on) {
   if (!fm) return;
-  fm->impl.prof_on = on != 0;
-  for (Model* l : fm->impl.xlanes)
-    if (l) l->prof_on = on != 0;
+  for_each_prof(&fm->impl, [&](Prof& p) { p.on = on != 0; });
 }
 void fw_prof_reset(fw_model* fm) {
   if (!fm) return;
-  prof_collect(&fm->impl);
-  {
-    std::lock_guard<std::mutex> lk(fm->impl.prof_mu);
-    for (auto& p : fm->impl.prof) p = ProfAcc();
-  }
-  for (Model* l : fm->impl.xlanes) {
-    if (!l) continue;
-    prof_collect(l);
-    std::lock_guard<std::mutex> lk(l->prof_mu);
-    for (auto& p : l->prof) p = ProfAcc();
-  }
+  for_each_prof(&fm->impl, [](Prof& p) {
+    prof_collect(p);
+    std::lock_guard<std::mutex> lk(p.mu);
+    for (auto& a : p.acc) a = ProfAcc();
+  });
 }
 int32_t fw_prof_count(void) { return PF_COUNT; }
 const char* fw_prof_name(int32_t i) { return (i >= 0 && i < PF_COUNT) ? kProfNames[i] : ""; }
 int32_t fw_prof_get(fw_model* fm, int32_t i, double* ms, int64_t* launches, double* flops, double* bytes) {
   FW_CHECK_ARG(fm && i >= 0 && i < PF_COUNT, "bad profile index");
-  prof_collect(&fm->impl);
   ProfAcc p;
-  {
-    std::lock_guard<std::mutex> lk(fm->impl.prof_mu);
-    p = fm->impl.prof[i];
-  }
-  for (Model* l : fm->impl.xlanes) {   // the further decode lanes of the group report through their primary
-    if (!l) continue;
-    prof_collect(l);
-    std::lock_guard<std::mutex> lk(l->prof_mu);
-    p.ms += l->prof[i].ms; p.launches += l->prof[i].launches; p.flops += l->prof[i].flops; p.bytes += l->prof[i].bytes;
-  }
+  for_each_prof(&fm->impl, [&](Prof& r) {   // the decode lanes of the group report through their model
+    prof_collect(r);
+    std::lock_guard<std::mutex> lk(r.mu);
+    const ProfAcc& a = r.acc[i];
+    p.ms += a.ms; p.launches += a.launches; p.flops += a.flops; p.bytes += a.bytes;
+  });
   if (ms) *ms = p.ms;
   if (launches) *launches = p.launches;
   if (flops) *flops = p.flops;
@@ -1626,9 +1612,8 @@ int32_t fw_synchronize(fw_model* fm) {
   FW_CHECK_ARG(fm, "null model");
   FW_HIP(hipSetDevice(fm->impl.device));
   FW_HIP(hipStreamSynchronize(fm->impl.stream));
-  if (fm->impl.dec_stream) FW_HIP(hipStreamSynchronize(fm->impl.dec_stream));
-  for (Model* l : fm->impl.xlanes)
-    if (l && l->dec_stream) FW_HIP(hipStreamSynchronize(l->dec_stream));
+  for (const auto& l : fm->impl.lanes)
+    if (l->stream) FW_HIP(hipStreamSynchronize(l->stream));
   return FW_OK;
 }
 int32_t fw_dev_alloc(fw_model* fm, int64_t bytes, void** out_dev) {

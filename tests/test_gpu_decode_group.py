@@ -363,3 +363,47 @@ def test_set_decode_batch_while_callers_arrive():
     assert not errs, errs
     print(f"resizes applied {n_done}, refused while busy {n_refused}, generate calls served {n_ok[0]}")
     assert n_ok[0] > 0 and n_done + n_refused == 40
+
+
+def test_profile_counts_the_launches_of_every_lane():
+    """Every decode lane records its profiling scopes itself; fw_prof_enable / fw_prof_get / fw_prof_reset on the model that
+    owns the group reach all of them, and a lane built while profiling is on (fw_model_set_decode_batch) inherits the switch.
+    A long call is in flight on the first lane when a short one with other options (no shared run) arrives, runs on the
+    second lane and returns first.  Profiling turns graph replay off, so every decode step is one dec_logits scope: their
+    count is the decode steps of both calls, and min_new_tokens = the budget makes the length of a returned sequence the
+    steps of its run."""
+    import time
+    cfg, model = _model("micro", 4)                       # 12 chunks >= 4 encoder batches: two lanes
+    lib, h = model._lib, model._replicas[0].handle
+    model.profile(True)
+    assert lib.fw_model_set_decode_batch(h, 6) == 0       # one lane ...
+    assert lib.fw_model_set_decode_batch(h, 12) == 0      # ... and two again: the second one is built with profiling on
+    assert model.decode_stats()["decode_batch"] == 12
+    prompt = list(cfg.sot_sequence) + [cfg.no_timestamps]
+    n_long = cfg.n_text_ctx - len(prompt)
+    long_kw = dict(beam_size=5, max_length=len(prompt) + n_long, min_new_tokens=n_long)
+    short_kw = dict(beam_size=2, max_length=len(prompt) + 9, min_new_tokens=9)
+    encs = [model.encode_pcm(b) for b in _batches(2, 3)]
+    out = [None] * 2
+    runs0 = model.decode_stats()["runs"]
+
+    def work():
+        out[0] = model.generate(encs[0], [prompt] * 3, **long_kw)
+
+    t = threading.Thread(target=work)
+    t.start()
+    t_end = time.time() + 30
+    while model.decode_stats()["runs"] == runs0 and time.time() < t_end:
+        time.sleep(0.0005)                                # the long run has taken the first lane
+    out[1] = model.generate(encs[1], [prompt] * 3, **short_kw)
+    overlapped = t.is_alive()                             # (the whole text context in eager steps against 9 steps)
+    t.join()
+    steps = [max(len(ids) for r in o for ids in r.sequences_ids) for o in out]
+    launches = model.profile_report()["dec_logits"]["launches"]
+    print(f"decode steps {steps}, dec_logits launches {launches}, second lane used: {overlapped}")
+    assert overlapped, "the short call did not run beside the long one: the second lane was not exercised"
+    assert steps[0] > steps[1] > 0
+    assert launches == sum(steps)
+    lib.fw_prof_reset(h)
+    assert model.profile_report()["dec_logits"]["launches"] == 0
+    model.profile(False)
