@@ -74,7 +74,7 @@ SYMBOLS = [
     "fw_logmel", "fw_logmel_full",
     "fw_encode", "fw_encode_pcm", "fw_encode_pcm_dev", "fw_tensor_shape", "fw_tensor_to_host",
     "fw_tensor_from_host", "fw_tensor_free",
-    "fw_generate", "fw_detect_language", "fw_align",
+    "fw_generate", "fw_generate_lp", "fw_detect_language", "fw_align",
     "fw_prof_enable", "fw_prof_reset", "fw_prof_count", "fw_prof_name", "fw_prof_get", "fw_synchronize",
     "fw_dev_alloc", "fw_dev_free", "fw_dev_upload",
     "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules",
@@ -82,6 +82,7 @@ SYMBOLS = [
     "fw_bench_gemm_epi", "fw_bench_dec_linear_epi",
     "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
     "fw_test_dec_beam_update", "fw_test_dec_embed", "fw_test_align_post",
+    "fw_test_logits_rules_lp", "fw_test_dec_beam_update_lp",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_vad_forward_audio_batch_dev",
     "fw_flac_info", "fw_flac_decode",
@@ -152,6 +153,8 @@ def load():
     lib.fw_tensor_free.argtypes = [vp]
     lib.fw_tensor_free.restype = None
     lib.fw_generate.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32p, i32p, f32p, f32p]
+    if hasattr(lib, "fw_generate_lp"):            # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_generate_lp.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32p, i32p, f32p, f32p, f32p, f32p]
     lib.fw_detect_language.argtypes = [vp, vp, i32, i32p, f32p]
     lib.fw_align.argtypes = [vp, vp, i32p, i32, i32p, i32p, i32p, i32, i32, i32, i32p, i32p, f32p]
     lib.fw_prof_enable.argtypes = [vp, i32]
@@ -195,6 +198,11 @@ def load():
                                                 i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.fw_test_dec_embed.argtypes = [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]
         lib.fw_test_align_post.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    if hasattr(lib, "fw_test_dec_beam_update_lp"):   # (absent from an older build loaded through FWAMD_LIB)
+        f32 = C.c_float
+        lib.fw_test_logits_rules_lp.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp]
+        lib.fw_test_dec_beam_update_lp.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp,
+                                                   vp, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]
     lib.fw_vad_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     lib.fw_vad_free.argtypes = [vp]

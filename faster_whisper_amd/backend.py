@@ -89,11 +89,16 @@ class StorageView:
 
 
 class WhisperGenerationResult:
-    def __init__(self, sequences_ids, scores, no_speech_prob):
+    def __init__(self, sequences_ids, scores, no_speech_prob, token_logprobs=None, end_logprobs=None):
         self.sequences_ids = sequences_ids
         self.sequences = [[str(t) for t in s] for s in sequences_ids]
         self.scores = scores
         self.no_speech_prob = no_speech_prob
+        # generate(return_token_logprobs=True): token_logprobs[h][i] = log-prob of sequences_ids[h][i] under the
+        # processed distribution (after the logits rules), end_logprobs[h] = that of the closing <eot> (0.0: cut at
+        # the budget).  Empty lists when not requested.
+        self.token_logprobs = token_logprobs if token_logprobs is not None else []
+        self.end_logprobs = end_logprobs if end_logprobs is not None else []
 
     def __repr__(self):
         return (f"WhisperGenerationResult(sequences_ids={self.sequences_ids}, scores={self.scores}, "
@@ -456,7 +461,7 @@ class Whisper:
                  max_initial_timestamp_index: int = 50, suppress_blank: bool = True,
                  suppress_tokens: Optional[Sequence[int]] = (-1,), sampling_topk: int = 1,
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
-                 seed: Optional[int] = None) -> List[WhisperGenerationResult]:
+                 seed: Optional[int] = None, return_token_logprobs: bool = False) -> List[WhisperGenerationResult]:
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
         enc = self._as_encoded(features if isinstance(features, StorageView) else StorageView.from_array(features))
@@ -473,6 +478,8 @@ class Whisper:
                       max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank,
                       suppress_tokens=suppress_tokens, sampling_topk=sampling_topk,
                       sampling_temperature=sampling_temperature, min_new_tokens=min_new_tokens, seed=seed)
+            if return_token_logprobs:
+                kw["return_token_logprobs"] = True
             out, b0 = [], 0
             for part in enc._parts:
                 out.extend(self.generate(part, prompts[b0:b0 + part._shape[0]], **kw))
@@ -501,14 +508,27 @@ class Whisper:
         scores = np.zeros((B, nh), dtype=np.float32)
         nsp = np.zeros((B,), dtype=np.float32)
         rep = enc._owner
-        _lib.check(self._lib.fw_generate(rep.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B,
-                                         C.byref(o), _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores),
-                                         _lib.as_f32p(nsp)))
+        if return_token_logprobs:
+            if not hasattr(self._lib, "fw_generate_lp"):   # an older build loaded through FWAMD_LIB
+                raise RuntimeError("this libfwamd.so has no fw_generate_lp: per-token log-probabilities need a current build")
+            tlp = np.zeros((B, nh, ml), dtype=np.float32)
+            elp = np.zeros((B, nh), dtype=np.float32)
+            _lib.check(self._lib.fw_generate_lp(rep.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B,
+                                                C.byref(o), _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores),
+                                                _lib.as_f32p(nsp), _lib.as_f32p(tlp), _lib.as_f32p(elp)))
+        else:
+            _lib.check(self._lib.fw_generate(rep.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B,
+                                             C.byref(o), _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores),
+                                             _lib.as_f32p(nsp)))
         out = []
         for b in range(B):
             seqs = [ids[b, h, :lens[b, h]].tolist() for h in range(nh)]
             sc = [float(scores[b, h]) for h in range(nh)] if return_scores else []
-            out.append(WhisperGenerationResult(seqs, sc, float(nsp[b]) if return_no_speech_prob else 0.0))
+            res = WhisperGenerationResult(seqs, sc, float(nsp[b]) if return_no_speech_prob else 0.0)
+            if return_token_logprobs:
+                res.token_logprobs = [tlp[b, h, :lens[b, h]].tolist() for h in range(nh)]
+                res.end_logprobs = [float(elp[b, h]) for h in range(nh)]
+            out.append(res)
         return out
 
     # ---- detect_language ----------------------------------------------------------------

@@ -77,10 +77,14 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 #define LP_SUP_WORDS 896
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok);
+                           int* cand_tok, float* cand_lp = nullptr);
+// cand_lp [R][32]: the log-prob of every candidate (cand_val = cum + cand_lp), lphist2 [2][R][NT] the log-prob history
+// beside hist2, fin_lp [.][FIN_CAP][NT + 1] the values of a finished hypothesis' tokens and, at [NT], of its <eot>.
+// Null (all three of the beam update, or none): the kernels skip these stores.
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
-                        int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum);
+                        int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum,
+                        const float* cand_lp = nullptr, float* lphist2 = nullptr, float* fin_lp = nullptr);
 void launch_step_advance(hipStream_t st, int* d_step);
 // row b reads logits row b * row_mul
 void launch_token_prob(hipStream_t st, const float* logits, int V, const int* target, float* out, int out_stride,

@@ -1479,7 +1479,8 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
                                                                         const int* __restrict__ d_step,
                                                                         const int* __restrict__ done,
                                                                         float* __restrict__ cand_val,
-                                                                        int* __restrict__ cand_tok) {
+                                                                        int* __restrict__ cand_tok,
+                                                                        float* __restrict__ cand_lp) {
   __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
   __shared__ float bkey_s[2][LP_WAVES];
   __shared__ int btok_s[2][LP_WAVES];
@@ -1680,6 +1681,10 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
         cand_val[(size_t)r * 32 + cidx] = NEG;
         cand_tok[(size_t)r * 32 + cidx] = 0;
         if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
+        if (cand_lp) {   // (a kernel argument: uniform)
+          cand_lp[(size_t)r * 32 + cidx] = NEG;
+          if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+        }
       }
       continue;
     }
@@ -1695,6 +1700,12 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
       cand_val[(size_t)r * 32 + cidx] = cum + raw;
       cand_tok[(size_t)r * 32 + cidx] = wt;
       if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
+      // the token's own log-prob, as it was added to cum: stored, not recovered later from two running sums
+      // (fl(cum + raw) - cum is not raw once |raw| > |cum|)
+      if (cand_lp) {
+        cand_lp[(size_t)r * 32 + cidx] = raw;
+        if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+      }
     }
   }
 }
@@ -1712,19 +1723,28 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
 //     only fin_*, n_fin, done and n_done change;
 //   * otherwise dead beams copy live beam 0 with cum = -inf, and history (+ token at `step`), slot table (+ parent byte
 //     at P - 1 + step), cum and cur_tok go to the OTHER parity half; the current half is left as it was.
+// Per-token log-probs (cand_lp / lphist2 / fin_lp, all three null or none; tests/token_logprob_refs.py): lphist2 [2][R][NT]
+// shadows hist2 value for value (entry q = the cand_lp of the candidate that put token q there), and a finished hypothesis
+// gets fin_lp [.][FIN_CAP][NT + 1]: its tokens' values, then at [NT] the value of the <eot> that closed it, 0 when it was
+// cut at the budget (its last candidate is then a token of its own).  The values are copied, never computed.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, const float* __restrict__ cand_val,
+// (amdgpu_waves_per_eu: with the three log-prob pointers the kernel's scalar registers pass 102 and the compiler would
+//  budget 7 waves per SIMD instead of 8; held at 8, 32 scalars live in lanes of two vector registers, nothing in scratch)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void dec_beam_update_kernel(fwd::GenDev gp, const float* __restrict__ cand_val,
                                                              const int* __restrict__ cand_tok, int* __restrict__ hist2,
                                                              float* __restrict__ cum2, uint8_t* __restrict__ kvidx2,
                                                              int* __restrict__ cur_tok, const int* __restrict__ d_step,
                                                              int* __restrict__ done, int* __restrict__ n_done,
                                                              int* __restrict__ n_fin, int* __restrict__ fin_tok,
                                                              int* __restrict__ fin_len, float* __restrict__ fin_score,
-                                                             float* __restrict__ fin_cum) {
-  __shared__ float ov[32];
+                                                             float* __restrict__ fin_cum,
+                                                             const float* __restrict__ cand_lp,
+                                                             float* __restrict__ lphist2, float* __restrict__ fin_lp) {
+  __shared__ float ov[32], olp[32];
   __shared__ int ok[32], ot[32];
   __shared__ int s_parent[16], s_tok[16];
-  __shared__ float s_cum[16];
+  __shared__ float s_cum[16], s_lp[16];
   __shared__ int s_done;
   const int c = blockIdx.x;
   if (done[c]) return;
@@ -1734,6 +1754,7 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
   const int cur = step & 1, nxt = cur ^ 1;
   const int pos = gp.P - 1 + step;
   const bool last_step = (step + 1) >= gp.budget;
+  const bool with_lp = cand_lp != nullptr;   // (a kernel argument: uniform)
   if (tid == 0) {
     // ---- merge: top-C of the (live rows x C) candidates ----
     const int nsrc = (step == 0) ? 1 : K;
@@ -1753,6 +1774,7 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
       }
       if (bk < 0) break;
       ov[nsel] = bvv; ok[nsel] = bk; ot[nsel] = btok;
+      if (with_lp) olp[nsel] = cand_lp[(size_t)(c * K + bk) * 32 + ptr[bk]];
       ptr[bk]++;
     }
     // ---- walk ----
@@ -1768,6 +1790,13 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
           int* dst = fin_tok + ((size_t)c * fwd::FIN_CAP + nf) * NT;
           int len = step;
           for (int q = 0; q < step; ++q) dst[q] = hsrc[q];
+          if (with_lp) {
+            const float* lsrc = lphist2 + ((size_t)cur * gp.R + c * K + kk) * NT;
+            float* ldst = fin_lp + ((size_t)c * fwd::FIN_CAP + nf) * (NT + 1);
+            for (int q = 0; q < step; ++q) ldst[q] = lsrc[q];
+            if (ot[jdx] != gp.eot) { ldst[step] = olp[jdx]; ldst[NT] = 0.f; }
+            else ldst[NT] = olp[jdx];
+          }
           if (ot[jdx] != gp.eot) { dst[len] = ot[jdx]; len++; }
           fin_len[c * fwd::FIN_CAP + nf] = len;
           fin_cum[c * fwd::FIN_CAP + nf] = ov[jdx];
@@ -1781,6 +1810,7 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
         if (jdx >= nsel) continue;
       }
       s_parent[nlive] = ok[jdx]; s_tok[nlive] = ot[jdx]; s_cum[nlive] = ov[jdx];
+      if (with_lp) s_lp[nlive] = olp[jdx];
       nlive++;
     }
     n_fin[c] = nf;
@@ -1790,6 +1820,8 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
       atomicAdd(n_done, 1);
     } else {
       for (int k = nlive; k < K; ++k) { s_parent[k] = s_parent[0]; s_tok[k] = s_tok[0]; s_cum[k] = -INFINITY; }
+      if (with_lp)
+        for (int k = nlive; k < K; ++k) s_lp[k] = s_lp[0];
     }
     s_done = fin ? 1 : 0;
   }
@@ -1804,6 +1836,12 @@ __global__ __launch_bounds__(64) void dec_beam_update_kernel(fwd::GenDev gp, con
     uint8_t* id = kvidx2 + ((size_t)nxt * gp.R + nr) * NT;
     for (int q = tid; q < step; q += 64) hd[q] = hs[q];
     for (int q = tid; q < pos; q += 64) id[q] = is[q];
+    if (with_lp) {
+      const float* ls = lphist2 + ((size_t)cur * gp.R + pr) * NT;
+      float* ld = lphist2 + ((size_t)nxt * gp.R + nr) * NT;
+      for (int q = tid; q < step; q += 64) ld[q] = ls[q];
+      if (tid == 0) ld[step] = s_lp[k];
+    }
     if (tid == 0) {
       hd[step] = s_tok[k];
       id[pos] = (uint8_t)s_parent[k];
@@ -2226,12 +2264,12 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok) {
+                           int* cand_tok, float* cand_lp) {
   // every Whisper vocabulary keeps its timestamp ids above 48 * 1024 (ts_begin 50 363 .. 50 365); the synthetic
   // test vocabularies do not: they take the instantiation with a per-lane class test everywhere
   const bool wide = gp.ts_begin >= 48 * LP_THREADS;
 #define LP_GO(SMP, TXI) \
-  dec_logits_process_kernel<SMP, TXI><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok)
+  dec_logits_process_kernel<SMP, TXI><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp)
   if (gp.sample) { if (wide) LP_GO(true, 48); else LP_GO(true, 0); }
   else { if (wide) LP_GO(false, 48); else LP_GO(false, 0); }
 #undef LP_GO
@@ -2239,9 +2277,12 @@ void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, cons
 
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
-                        int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum) {
+                        int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum, const float* cand_lp,
+                        float* lphist2, float* fin_lp) {
+  if (!cand_lp || !lphist2 || !fin_lp) { cand_lp = nullptr; lphist2 = nullptr; fin_lp = nullptr; }   // all three or none
   dec_beam_update_kernel<<<gp.B, 64, 0, st>>>(gp, cand_val, cand_tok, hist2, cum2, kvidx2, cur_tok, d_step, done,
-                                              n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum);
+                                              n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, cand_lp, lphist2,
+                                              fin_lp);
 }
 
 void launch_step_advance(hipStream_t st, int* d_step) { dec_step_advance_kernel<<<1, 1, 0, st>>>(d_step); }

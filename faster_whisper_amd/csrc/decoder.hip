@@ -83,6 +83,10 @@ struct GenWorkspace {
   uint8_t* kvidx2 = nullptr;             // [2][R][NT]
   float* cand_val = nullptr;             // [R][32]
   int* cand_tok = nullptr;
+  // per-token log-probs, recorded by every run beside their token twins (dec_kernels.h)
+  float* cand_lp = nullptr;              // [R][32]
+  float* lphist2 = nullptr;              // [2][R][NT]
+  float* fin_lp = nullptr;               // [R][FIN_CAP][NT + 1]
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -119,6 +123,7 @@ int64_t gen_workspace_bytes(const Model* m, int lane_chunks, int nts) {
   int64_t n = 2 * (L * R * NTs * d) * 2;                               // self K/V (fp16)
   n += R * (int64_t)c.n_vocab * 4 + R * 12 * d * 2 * 2;                // logits, activations
   n += R * FIN_CAP * NT * 4 + 3 * R * NT * 4;                          // finished hypotheses, histories
+  n += R * FIN_CAP * (NT + 1) * 4 + 2 * R * NT * 4 + R * 32 * 4;       // their per-token log-probs
   return n + (64 << 20);
 }
 
@@ -252,10 +257,13 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   A(g->kvidx2, 2 * R * NT);
   A(g->cand_val, R * 32);
   A(g->cand_tok, R * 32);
+  A(g->cand_lp, R * 32);
+  A(g->lphist2, 2 * R * NT);
   // per-chunk state is sized by ROWS: random sampling runs every hypothesis as its own beam-1 chunk
   A(g->done, R); A(g->n_done, 1); A(g->n_fin, R);
   A(g->fin_tok, R * FIN_CAP * NT); A(g->fin_len, R * FIN_CAP);
   A(g->fin_score, R * FIN_CAP); A(g->fin_cum, R * FIN_CAP);
+  A(g->fin_lp, R * FIN_CAP * (NT + 1));
   A(g->d_step, 1);
   A(g->no_speech, R);
   A(g->sup_bits, (size_t)LP_SUP_WORDS);
@@ -307,7 +315,8 @@ void gen_workspace_free(DecodeLane* lane) {
   void* ptrs[] = {g->slot_map, g->sk, g->sv, g->x, g->qkv, g->att, g->qc, g->ffn, g->logits, g->prompt_dev,
                   g->cur_tok, g->hist2, g->cum2, g->kvidx2, g->cand_val, g->cand_tok, g->done, g->n_done, g->n_fin,
                   g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->d_step, g->no_speech, g->sup_bits,
-                  g->zero_done, g->xq, g->xs, g->ekq, g->eks, g->x_frag, g->att_frag, g->ffn_frag, g->xn_frag, g->prompt_blk};
+                  g->zero_done, g->xq, g->xs, g->ekq, g->eks, g->x_frag, g->att_frag, g->ffn_frag, g->xn_frag, g->prompt_blk,
+                  g->cand_lp, g->lphist2, g->fin_lp};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete g;
@@ -579,9 +588,10 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   if (s.beam_tail) {
     ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
-                               g->cand_tok);
+                               g->cand_tok, g->cand_lp);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
-                            g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum);
+                            g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->cand_lp,
+                            g->lphist2, g->fin_lp);
     fwd::launch_step_advance(st, g->d_step);
   }
   return FW_OK;
@@ -613,6 +623,8 @@ struct GenRequest {
   int B, P;
   const fw_gen_opts* o;
   int32_t* out_ids; int32_t* out_lens; float* out_scores; float* out_no_speech;
+  float* out_token_logprobs = nullptr;   // [B, num_hypotheses, max_length] | null
+  float* out_end_logprobs = nullptr;     // [B, num_hypotheses] | null
   bool sampling;
   int with_ts = 1, sot_pos = -1;   // from the prompt: no <|notimestamps|> -> timestamp rules; position of <sot>
   int rc = FW_OK;
@@ -748,6 +760,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   // (the ping-pong halves of hist2 / kvidx2 / cum2 are gp.R rows apart: the kernels index them with the run's R)
   const size_t NT = g->NT, Rr = (size_t)gp.R;
   FW_HIP(hipMemsetAsync(g->hist2, 0, 2 * Rr * NT * sizeof(int), st));
+  FW_HIP(hipMemsetAsync(g->lphist2, 0, 2 * Rr * NT * sizeof(float), st));
   FW_HIP(hipMemsetAsync(g->kvidx2, 0, 2 * Rr * NT, st));
   FW_HIP(hipMemsetAsync(g->cum2, 0, 2 * Rr * sizeof(float), st));
   FW_HIP(hipMemsetAsync(g->done, 0, Rr * sizeof(int), st));
@@ -902,6 +915,14 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   FW_HIP(hipMemcpyAsync(fin_score.data(), g->fin_score, fin_score.size() * sizeof(float), hipMemcpyDeviceToHost, st));
   FW_HIP(hipMemcpyAsync(fin_tok.data(), g->fin_tok, fin_tok.size() * sizeof(int), hipMemcpyDeviceToHost, st));
   FW_HIP(hipMemcpyAsync(nsp.data(), g->no_speech, Bx * sizeof(float), hipMemcpyDeviceToHost, st));
+  // the per-token log-probs are recorded by every run; they come back only when a request of this one asked
+  bool want_lp = false;
+  for (const GenRequest* r : reqs) want_lp = want_lp || r->out_token_logprobs || r->out_end_logprobs;
+  std::vector<float> fin_lp;
+  if (want_lp) {
+    fin_lp.resize((size_t)Bx * FIN_CAP * (NT + 1));
+    FW_HIP(hipMemcpyAsync(fin_lp.data(), g->fin_lp, fin_lp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
   FW_HIP(hipStreamSynchronize(st));
   int cb = 0;   // first chunk of the request inside the run
   for (GenRequest* r : reqs) {
@@ -924,6 +945,9 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
         r->out_lens[b * nh + h] = len;
         if (r->o->return_scores) r->out_scores[b * nh + h] = fin_score[f];
         memcpy(r->out_ids + ((size_t)b * nh + h) * ml, &fin_tok[f * NT], (size_t)len * sizeof(int));
+        if (r->out_token_logprobs)
+          memcpy(r->out_token_logprobs + ((size_t)b * nh + h) * ml, &fin_lp[f * (NT + 1)], (size_t)len * sizeof(float));
+        if (r->out_end_logprobs) r->out_end_logprobs[b * nh + h] = fin_lp[f * (NT + 1) + NT];
       }
     }
     cb += r->B;
@@ -940,6 +964,13 @@ extern "C" {
 int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                     int32_t B, const fw_gen_opts* o, int32_t* out_ids, int32_t* out_lens, float* out_scores,
                     float* out_no_speech) {
+  return fw_generate_lp(fm, enc_t, prompts, prompt_offsets, B, o, out_ids, out_lens, out_scores, out_no_speech, nullptr,
+                        nullptr);
+}
+
+int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                       int32_t B, const fw_gen_opts* o, int32_t* out_ids, int32_t* out_lens, float* out_scores,
+                       float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   Model* m = &fm->impl;
@@ -977,10 +1008,13 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
   const int nh = o->num_hypotheses;
   for (int i = 0; i < B * nh; ++i) { out_lens[i] = 0; out_scores[i] = 0.f; }
   for (int b = 0; b < B; ++b) out_no_speech[b] = 0.f;
+  if (out_token_logprobs) std::fill(out_token_logprobs, out_token_logprobs + (size_t)B * nh * o->max_length, 0.f);
+  if (out_end_logprobs) std::fill(out_end_logprobs, out_end_logprobs + (size_t)B * nh, 0.f);
 
   GenRequest req;
   req.enc = enc; req.prompts = prompts; req.prompt_offsets = prompt_offsets; req.B = B; req.P = P; req.o = o;
   req.out_ids = out_ids; req.out_lens = out_lens; req.out_scores = out_scores; req.out_no_speech = out_no_speech;
+  req.out_token_logprobs = out_token_logprobs; req.out_end_logprobs = out_end_logprobs;
   req.sampling = sampling;
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the

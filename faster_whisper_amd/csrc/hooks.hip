@@ -850,9 +850,10 @@ int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows
 // (the same for every row), hist [R][n], cum [R]; out: cand_val / cand_tok [R][2 * beam_size] (sampling: [R][1]).
 // (This hook and the three after it launch on the null stream, without the model's lock, and end with a device-wide wait.)
 // ---------------------------------------------------------------------------------------------------
-int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
-                             const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
-                             int32_t* cand_tok) {
+// (cand_lp null: the kernel gets a null pointer and skips the log-prob stores, fw_test_logits_rules as it always was)
+static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                                 const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
+                                 int32_t* cand_tok, float* cand_lp) {
   FW_CHECK_ARG(fm && logits && cum && o && cand_val && cand_tok && R >= 1 && n >= 0, "bad arguments");
   Model* m = &fm->impl;
   const fw_config& c = m->cfg;
@@ -893,7 +894,8 @@ int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const
   std::vector<float> hv((size_t)R * 32);
   std::vector<int> ht((size_t)R * 32);
   HookBufs db;
-  float *d_lg, *d_cum, *d_cv;
+  std::vector<float> hl(cand_lp ? hv.size() : 0);
+  float *d_lg, *d_cum, *d_cv, *d_cl = nullptr;
   int *d_hist, *d_step, *d_done, *d_ct;
   unsigned long long* d_bits;
   int rc;
@@ -903,17 +905,33 @@ int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const
       (rc = db.alloc(&d_cv, hv.size())) || (rc = db.alloc(&d_ct, ht.size())) || (rc = db.zero(d_done, (size_t)R * sizeof(int), nullptr)) ||
       (rc = db.zero(d_cv, hv.size() * sizeof(float), nullptr)) || (rc = db.zero(d_ct, ht.size() * sizeof(int), nullptr)))
     return rc;
-  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct);
+  if (cand_lp && ((rc = db.alloc(&d_cl, hl.size())) || (rc = db.zero(d_cl, hl.size() * sizeof(float), nullptr)))) return rc;
+  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
   if ((rc = download(hv.data(), d_cv, hv.size())) || (rc = download(ht.data(), d_ct, ht.size()))) return rc;
+  if (cand_lp && (rc = download(hl.data(), d_cl, hl.size()))) return rc;
   const int C = sampling ? 1 : 2 * K;
   for (int r = 0; r < R; ++r)
     for (int j = 0; j < C; ++j) {
       cand_val[(size_t)r * C + j] = hv[(size_t)r * 32 + j];
       cand_tok[(size_t)r * C + j] = ht[(size_t)r * 32 + j];
+      if (cand_lp) cand_lp[(size_t)r * C + j] = hl[(size_t)r * 32 + j];
     }
   return FW_OK;
+}
+
+int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                             const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
+                             int32_t* cand_tok) {
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, nullptr);
+}
+
+int32_t fw_test_logits_rules_lp(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                                const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
+                                int32_t* cand_tok, float* cand_lp) {
+  FW_CHECK_ARG(cand_lp, "null argument");
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -922,12 +940,14 @@ int32_t fw_test_logits_rules(fw_model* fm, const float* logits, int32_t R, const
 // is checked before anything is allocated or launched: a mistaken test gets FW_EINVAL, never an out-of-bounds access.
 // ---------------------------------------------------------------------------------------------------
 // ONE launch of dec_beam_update_kernel (fwd::launch_beam_update) for B chunks of K beams at decode step `step`.
-int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+// (lp: the log-prob arrays of fw_test_dec_beam_update_lp; without them the kernel gets null pointers and skips those stores)
+struct BeamLpArgs { const float* cand_lp; const float* lphist; float* fin_lp; float* lphist2; };
+static int32_t beam_update_hook(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
                                 int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
                                 const int32_t* cand_tok, const int32_t* hist, const uint8_t* kvidx, const float* cum,
                                 int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
                                 int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
-                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok) {
+                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok, const BeamLpArgs* lp) {
   FW_CHECK_ARG(fm && cand_val && cand_tok && cum && done && n_done && n_fin && fin_tok && fin_len && fin_score &&
                    fin_cum && hist2 && kvidx2 && cum2 && cur_tok, "null argument");
   FW_CHECK_ARG(K >= 1 && K <= 16, "need 1 <= K <= 16 (K = %d)", K);
@@ -938,6 +958,7 @@ int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   FW_CHECK_ARG(eot >= 0 && eot < V && max_fin >= 1 && budget >= 1 && lp_pow == lp_pow, "bad eot / max_fin / budget / lp_pow");
   const int R = B * K, C = 2 * K, pos = P - 1 + step;
   FW_CHECK_ARG((step == 0 || hist) && (pos == 0 || kvidx), "null history / slot table");
+  FW_CHECK_ARG(!lp || (lp->cand_lp && lp->fin_lp && lp->lphist2 && (step == 0 || lp->lphist)), "null log-prob argument");
   for (int i = 0; i < R * C; ++i)
     FW_CHECK_ARG(cand_tok[i] >= 0 && cand_tok[i] < V, "cand_tok[%d] = %d outside [0, %d)", i, cand_tok[i], V);
   for (int64_t i = 0; i < (int64_t)R * pos; ++i)
@@ -955,6 +976,11 @@ int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   std::vector<uint8_t> k2(n_state, (uint8_t)sentinel_i);
   std::vector<float> c2(2 * (size_t)R, sentinel_f), cv((size_t)R * 32, -INFINITY);
   std::vector<int> ctk((size_t)R * 32, 0);
+  std::vector<float> cl(lp ? (size_t)R * 32 : 0, -INFINITY), l2(lp ? n_state : 0, sentinel_f);
+  for (int r = 0; r < R && lp; ++r) {
+    for (int q = 0; q < step; ++q) l2[((size_t)cur * R + r) * NT + q] = lp->lphist[(size_t)r * step + q];
+    for (int j = 0; j < C; ++j) cl[(size_t)r * 32 + j] = lp->cand_lp[(size_t)r * C + j];
+  }
   for (int r = 0; r < R; ++r) {
     for (int q = 0; q < step; ++q) h2[((size_t)cur * R + r) * NT + q] = hist[(size_t)r * step + q];
     for (int q = 0; q < pos; ++q) k2[((size_t)cur * R + r) * NT + q] = kvidx[(size_t)r * pos + q];
@@ -967,7 +993,7 @@ int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   Model* m = &fm->impl;
   FW_HIP(hipSetDevice(m->device));
   HookBufs db;
-  float *d_cv, *d_c2, *d_fs, *d_fc;
+  float *d_cv, *d_c2, *d_fs, *d_fc, *d_cl = nullptr, *d_l2 = nullptr, *d_flp = nullptr;
   int *d_ct, *d_h2, *d_cur, *d_step, *d_done, *d_ndone, *d_nfin, *d_ft, *d_fl;
   uint8_t* d_k2;
   const size_t n_f = (size_t)B * FIN_CAP;
@@ -980,8 +1006,11 @@ int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
       (rc = db.upload(&d_ft, fin_tok, n_f * NT)) || (rc = db.upload(&d_fl, fin_len, n_f)) ||
       (rc = db.upload(&d_fs, fin_score, n_f)) || (rc = db.upload(&d_fc, fin_cum, n_f)))
     return rc;
+  if (lp && ((rc = db.upload(&d_cl, cl.data(), cl.size())) || (rc = db.upload(&d_l2, l2.data(), n_state)) ||
+             (rc = db.upload(&d_flp, lp->fin_lp, n_f * (NT + 1)))))
+    return rc;
   fwd::launch_beam_update(nullptr, gp, d_cv, d_ct, d_h2, d_c2, d_k2, d_cur, d_step, d_done, d_ndone, d_nfin, d_ft, d_fl,
-                          d_fs, d_fc);
+                          d_fs, d_fc, d_cl, d_l2, d_flp);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
   if ((rc = download(hist2, d_h2, n_state)) || (rc = download(kvidx2, d_k2, n_state)) ||
@@ -991,7 +1020,33 @@ int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
       (rc = download(fin_len, d_fl, n_f)) || (rc = download(fin_score, d_fs, n_f)) ||
       (rc = download(fin_cum, d_fc, n_f)))
     return rc;
+  if (lp && ((rc = download(lp->lphist2, d_l2, n_state)) || (rc = download(lp->fin_lp, d_flp, n_f * (NT + 1))))) return rc;
   return FW_OK;
+}
+
+int32_t fw_test_dec_beam_update(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                const int32_t* cand_tok, const int32_t* hist, const uint8_t* kvidx, const float* cum,
+                                int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
+                                int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
+                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok) {
+  return beam_update_hook(fm, B, K, NT, V, P, step, budget, max_fin, lp_pow, eot, cand_val, cand_tok, hist, kvidx, cum,
+                          sentinel_i, sentinel_f, done, n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, hist2, kvidx2,
+                          cum2, cur_tok, nullptr);
+}
+
+int32_t fw_test_dec_beam_update_lp(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                   int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                   const int32_t* cand_tok, const float* cand_lp, const int32_t* hist,
+                                   const float* lphist, const uint8_t* kvidx, const float* cum, int32_t sentinel_i,
+                                   float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin, int32_t* fin_tok,
+                                   int32_t* fin_len, float* fin_score, float* fin_cum, float* fin_lp, int32_t* hist2,
+                                   float* lphist2, uint8_t* kvidx2, float* cum2, int32_t* cur_tok) {
+  FW_CHECK_ARG(cand_lp && fin_lp && lphist2, "null argument");
+  const BeamLpArgs lp{cand_lp, lphist, fin_lp, lphist2};
+  return beam_update_hook(fm, B, K, NT, V, P, step, budget, max_fin, lp_pow, eot, cand_val, cand_tok, hist, kvidx, cum,
+                          sentinel_i, sentinel_f, done, n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, hist2, kvidx2,
+                          cum2, cur_tok, &lp);
 }
 
 // ONE launch of dec_embed_kernel (fwd::launch_embed): x [rows][d] and the fragment-major copy, un-permuted on the host

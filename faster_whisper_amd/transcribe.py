@@ -72,6 +72,22 @@ class Segment:
 
 
 @dataclass
+class ScoredSegment(Segment):
+    """what transcribe(token_logprobs=True) yields: a Segment plus token_logprobs[i] = the log-prob of tokens[i] (timestamp
+    tokens included) under the distribution the decoder chose from, i.e. after the logits rules"""
+    token_logprobs: List[float]
+
+
+def _slice_token_logprobs(subs: List[dict], logprobs: List[float]) -> None:
+    """gives every sub-segment dict of one chunk the log-probs of its tokens: _split_segments_by_timestamps cuts
+    consecutive slices of the chunk's tokens from index 0 on (what follows the last cut belongs to no sub-segment)"""
+    pos = 0
+    for s in subs:
+        s["token_logprobs"] = list(logprobs[pos:pos + len(s["tokens"])])
+        pos += len(s["tokens"])
+
+
+@dataclass
 class TranscriptionOptions:
     beam_size: int
     best_of: int
@@ -363,11 +379,13 @@ class WhisperModel:
                    clip_timestamps: Union[str, List[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                   vad_speech_probs=None):
+                   vad_speech_probs=None, token_logprobs: bool = False):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
-        vad.get_speech_timestamps with precomputed window probabilities instead of running the Silero network."""
+        vad.get_speech_timestamps with precomputed window probabilities instead of running the Silero network.
+        token_logprobs=True (not in the reference): every segment is a ScoredSegment, whose token_logprobs are those of
+        the decode the fallback ladder kept; every other field is what the call without the keyword yields."""
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
@@ -427,7 +445,8 @@ class WhisperModel:
             append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
             hotwords=hotwords)
-        segments = self.generate_segments(features, tokenizer, options, log_progress, None)
+        segments = self.generate_segments(features, tokenizer, options, log_progress, None,
+                                          **(dict(token_logprobs=True) if token_logprobs else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
@@ -436,7 +455,8 @@ class WhisperModel:
         return segments, info
 
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
-                          log_progress: bool = False, encoder_output: Optional[StorageView] = None):
+                          log_progress: bool = False, encoder_output: Optional[StorageView] = None,
+                          token_logprobs: bool = False):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -491,7 +511,7 @@ class WhisperModel:
                 prompt = self.get_prompt(tokenizer, previous_tokens, without_timestamps=options.without_timestamps,
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
-                    encoder_output, prompt, tokenizer, options)
+                    encoder_output, prompt, tokenizer, options, **(dict(token_logprobs=True) if token_logprobs else {}))
 
                 if options.no_speech_threshold is not None:
                     skip = result.no_speech_prob > options.no_speech_threshold
@@ -505,6 +525,8 @@ class WhisperModel:
                 current, seek, single_timestamp_ending = self._split_segments_by_timestamps(
                     tokenizer=tokenizer, tokens=tokens, time_offset=time_offset, segment_size=segment_size,
                     segment_duration=segment_duration, seek=seek)
+                if token_logprobs:
+                    _slice_token_logprobs(current, result.token_logprobs[0])
 
                 if options.word_timestamps:
                     self.add_word_timestamps([current], tokenizer, encoder_output, segment_size,
@@ -553,10 +575,14 @@ class WhisperModel:
                         continue
                     all_tokens.extend(seg["tokens"])
                     idx += 1
-                    yield Segment(id=idx, seek=previous_seek, start=seg["start"], end=seg["end"], text=text,
+                    fields = dict(id=idx, seek=previous_seek, start=seg["start"], end=seg["end"], text=text,
                                   tokens=seg["tokens"], temperature=temperature, avg_logprob=avg_logprob,
                                   compression_ratio=compression_ratio, no_speech_prob=result.no_speech_prob,
                                   words=([Word(**w) for w in seg["words"]] if options.word_timestamps else None))
+                    if token_logprobs:
+                        yield ScoredSegment(token_logprobs=seg["token_logprobs"], **fields)
+                    else:
+                        yield Segment(**fields)
 
                 if not options.condition_on_previous_text or temperature > options.prompt_reset_on_temperature:
                     prompt_reset_since = len(all_tokens)
@@ -566,7 +592,7 @@ class WhisperModel:
             pbar.close()
 
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
-                               options: TranscriptionOptions):
+                               options: TranscriptionOptions, token_logprobs: bool = False):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
@@ -594,7 +620,8 @@ class WhisperModel:
                 repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
                 max_length=max_length, return_scores=True, return_no_speech_prob=True,
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
-                max_initial_timestamp_index=max_initial_timestamp_index, **mode)[0]
+                max_initial_timestamp_index=max_initial_timestamp_index, **mode,
+                **(dict(return_token_logprobs=True) if token_logprobs else {}))[0]
             tokens = result.sequences_ids[0]
             n = len(tokens)
             avg_logprob = result.scores[0] * (n ** options.length_penalty) / (n + 1)   # undo the length norm
@@ -781,9 +808,10 @@ class BatchedInferencePipeline:
 
     # ---- one batch: encode + generate ---------------------------------------------------
     def generate_segment_batched(self, features, tokenizer: Tokenizer, options: TranscriptionOptions,
-                                 audio_chunks: Optional[List[np.ndarray]] = None):
+                                 audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False):
         """features: [B, n_mels, 3000] float32, or None when `audio_chunks` is given (fused resident
-        PCM -> log-mel -> encoder path; the features never leave HBM)."""
+        PCM -> log-mel -> encoder path; the features never leave HBM).  token_logprobs: every output dict also carries
+        the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`)."""
         m = self.model
         batch_size = len(audio_chunks) if audio_chunks is not None else features.shape[0]
         prompt = m.get_prompt(tokenizer,
@@ -813,12 +841,15 @@ class BatchedInferencePipeline:
             length_penalty=options.length_penalty, max_length=max_length, suppress_blank=options.suppress_blank,
             suppress_tokens=options.suppress_tokens, return_scores=True, return_no_speech_prob=True,
             sampling_temperature=options.temperatures[0], repetition_penalty=options.repetition_penalty,
-            no_repeat_ngram_size=options.no_repeat_ngram_size)
+            no_repeat_ngram_size=options.no_repeat_ngram_size,
+            **(dict(return_token_logprobs=True) if token_logprobs else {}))
         output = []
         for r in results:
             n = len(r.sequences_ids[0])
             cum = r.scores[0] * (n ** options.length_penalty)
             output.append(dict(avg_logprob=cum / (n + 1), no_speech_prob=r.no_speech_prob, tokens=r.sequences_ids[0]))
+            if token_logprobs:
+                output[-1].update(token_logprobs=r.token_logprobs[0], end_logprob=r.end_logprobs[0])
         return encoder_output, output
 
     def forward(self, features, tokenizer, chunks_metadata, options, audio_chunks=None):
@@ -851,6 +882,8 @@ class BatchedInferencePipeline:
                      compression_ratio=get_compression_ratio(tokenizer.decode(s["tokens"])),
                      seek=int(meta["offset"] * m.frames_per_second))
                 for s in subs])
+            if "token_logprobs" in out:
+                _slice_token_logprobs(segmented[-1], out["token_logprobs"])
         return segmented, sizes
 
     # ---- the public entry point ---------------------------------------------------------
@@ -869,14 +902,19 @@ class BatchedInferencePipeline:
                    clip_timestamps: Optional[List[dict]] = None, hallucination_silence_threshold=None,
                    batch_size: int = 8, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                   shard: bool = False, fused_features: bool = True, vad_speech_probs=None):
+                   shard: bool = False, fused_features: bool = True, vad_speech_probs=None,
+                   token_logprobs: bool = False):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
+        token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
+        its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
         shard=True: inside a torch.distributed job every rank calls this with the same arguments; the
         chunk list is block-partitioned over the ranks and rank 0's generator yields ALL segments in
         order (other ranks yield nothing).  fused_features=False reproduces the reference data flow
         (features materialised on the host, then encode())."""
         m = self.model
         sr = m.feature_extractor.sampling_rate
+        if token_logprobs and shard:
+            raise ValueError("token_logprobs is not offered with shard=True: the gathered records carry no per-token values")
         if multilingual and not m.model.is_multilingual:
             m.logger.warning("The current model is English-only but the multilingual parameter is set to"
                              "True; setting to False instead.")
@@ -922,7 +960,8 @@ class BatchedInferencePipeline:
                                  duration_after_vad=duration_after_vad, transcription_options=options,
                                  vad_options=vad_parameters, all_language_probs=all_language_probs)
         gen = self._batched_segments_generator(audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                               log_progress, shard, fused_features)
+                                               log_progress, shard, fused_features,
+                                               **(dict(token_logprobs=True) if token_logprobs else {}))
         if not clips_given:
             gen = restore_speech_timestamps(gen, clips, sr)
         return gen, info
@@ -1019,7 +1058,7 @@ class BatchedInferencePipeline:
             without_timestamps=without_timestamps, max_initial_timestamp=0.0)
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                    log_progress, shard=False, fused_features=True):
+                                    log_progress, shard=False, fused_features=True, token_logprobs=False):
         from .sharding import gather_results, partition
         m = self.model
         rank, world, local_rank = 0, 1, 0
@@ -1042,7 +1081,7 @@ class BatchedInferencePipeline:
                 mid = lo + (hi - lo + 1) // 2
                 spans = [(lo, mid), (mid, hi)]
             return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
-                                            for i0, i1 in spans], shard, fused_features)
+                                            for i0, i1 in spans], shard, fused_features, token_logprobs)
 
         def emit(results):
             nonlocal seg_idx
@@ -1092,12 +1131,14 @@ class BatchedInferencePipeline:
     def _workers(self) -> int:
         return int(getattr(self.model.model, "inter_threads", 1) or 1)
 
-    def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True):
+    def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
+                      token_logprobs=False):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
         m = self.model
         feats = None if fused_features else m.model.log_mel(chunks)
         enc, outs = self.generate_segment_batched(feats, tokenizer, options,
-                                                  audio_chunks=chunks if fused_features else None)
+                                                  audio_chunks=chunks if fused_features else None,
+                                                  **(dict(token_logprobs=True) if token_logprobs else {}))
         local = aligned = None
         if not shard or options.word_timestamps:
             local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
@@ -1107,7 +1148,7 @@ class BatchedInferencePipeline:
                                         options.append_punctuations)
         return outs, local, aligned
 
-    def _batches_in_flight(self, jobs, shard=False, fused_features=True):
+    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False):
         """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
         The batches are independent (`condition_on_previous_text=False`): with worker replicas
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
@@ -1116,14 +1157,14 @@ class BatchedInferencePipeline:
         workers = self._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
-                yield self._decode_batch(*job, shard, fused_features)
+                yield self._decode_batch(*job, shard, fused_features, token_logprobs)
             return
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as pool:
             pending = deque()
             for job in jobs:
-                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features))
+                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs))
                 if len(pending) >= workers:
                     yield pending.popleft().result()
             while pending:
@@ -1135,11 +1176,16 @@ class BatchedInferencePipeline:
         idx = first_id
         for result in results:
             for seg in result:
-                yield Segment(seek=seg["seek"], id=idx, text=seg["text"], start=round(seg["start"], 3),
+                fields = dict(seek=seg["seek"], id=idx, text=seg["text"], start=round(seg["start"], 3),
                               end=round(seg["end"], 3), tokens=seg["tokens"], avg_logprob=seg["avg_logprob"],
                               words=(None if not options.word_timestamps else [Word(**w) for w in seg["words"]]),
                               no_speech_prob=seg["no_speech_prob"], compression_ratio=seg["compression_ratio"],
                               temperature=options.temperatures[0])
+                # (sub-segments carry token_logprobs exactly when the call asked for them: _split_outputs)
+                if "token_logprobs" in seg:
+                    yield ScoredSegment(token_logprobs=seg["token_logprobs"], **fields)
+                else:
+                    yield Segment(**fields)
                 idx += 1
 
     # ---- many recordings in one call ------------------------------------------------------------
@@ -1257,7 +1303,8 @@ class BatchedInferencePipeline:
         # ---- routing: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
         results = [[] for _ in range(n)]
         aligned = [[] for _ in range(n)]
-        for own, (_, local, al) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"])):
+        for own, (_, local, al) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
+                                                                       a["token_logprobs"])):
             for j, r in enumerate(own):
                 results[r].append(local[j])
                 if al is not None:

@@ -52,7 +52,7 @@ extern "C" {
  *    fw_model_run_capacity added, test / bench hooks moved to fwamd_test.h; the cross-attention cache of a decode group
  *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run);
  *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed),
- *    fw_vad_forward_audio_batch_dev likewise */
+ *    fw_vad_forward_audio_batch_dev likewise, and fw_generate_lp (fw_generate plus per-token log-probabilities) */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -251,6 +251,20 @@ void fw_tensor_free(fw_tensor* t);
 int32_t fw_generate(fw_model* m, const fw_tensor* enc, const int32_t* prompts,
                     const int32_t* prompt_offsets, int32_t B, const fw_gen_opts* opts,
                     int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech);
+/* fw_generate, plus per-token log-probabilities of every returned hypothesis:
+ *   out_token_logprobs float [B, num_hypotheses, max_length]  entry t = log-prob (after the logits rules, fp32 log-softmax)
+ *                                                             of out_ids[..., t]; entries >= out_lens are 0
+ *   out_end_logprobs   float [B, num_hypotheses]              log-prob of the <eot> that closed the hypothesis, 0 when it
+ *                                                             was cut at the budget
+ * Either pointer may be NULL.  Adding the values of a hypothesis in order in float32, then the end value, reproduces
+ * the cumulative log-prob that out_scores normalises — exactly.  These are the log-probs of the PROCESSED distribution,
+ * the one the search itself ranks by: after the repetition penalty, the no-repeat n-gram, suppress and timestamp rules
+ * (a token the rules left alone on a row gets log-prob 0).  When sampling they are not tempered.  fw_align's
+ * text_token_probs are the unconstrained counterpart: a second decoder pass without the rules.  fw_generate is
+ * fw_generate_lp(..., NULL, NULL); a call that asks for log-probs shares decode runs with calls that do not. */
+int32_t fw_generate_lp(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets, int32_t B,
+                       const fw_gen_opts* opts, int32_t* out_ids, int32_t* out_lens, float* out_scores,
+                       float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs);
 
 /* ---- detect_language -------------------------------------------------------
  * ctranslate2.models.Whisper.detect_language: one decoder step on [sot];

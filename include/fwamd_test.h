@@ -37,6 +37,11 @@ int32_t fw_test_dec_logits(fw_model* m, const float* x, int32_t R, float* out);
 int32_t fw_test_logits_rules(fw_model* m, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                              const float* cum, const fw_gen_opts* opts, int32_t with_timestamps, float* cand_val,
                              int32_t* cand_tok);
+/* fw_test_logits_rules plus cand_lp [R][2 * beam_size] ([R][1] when sampling): the log-prob the kernel recorded for each
+ * candidate (cand_val = cum + cand_lp; -inf where the row had nothing left).  tests/test_gpu_token_logprobs_kernels.py. */
+int32_t fw_test_logits_rules_lp(fw_model* m, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                                const float* cum, const fw_gen_opts* opts, int32_t with_timestamps, float* cand_val,
+                                int32_t* cand_tok, float* cand_lp);
 /* The three hooks of the decode-state kernels (tests/test_gpu_decode_state.py).  Geometry comes from the arguments, not
  * from the model.  Every quantity a kernel uses as an index or extent is checked BEFORE anything is allocated or
  * launched; a violation returns FW_EINVAL (a wrong test gets an error code, never a device fault).
@@ -59,6 +64,18 @@ int32_t fw_test_dec_beam_update(fw_model* m, int32_t B, int32_t K, int32_t NT, i
                                 int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
                                 int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
                                 uint8_t* kvidx2, float* cum2, int32_t* cur_tok);
+/* fw_test_dec_beam_update plus the per-token log-prob state (tests/test_gpu_token_logprobs_kernels.py):
+ *   in      cand_lp [R][2 K] beside cand_val / cand_tok, lphist [R][step] beside hist
+ *   in/out  fin_lp [B][48][NT + 1]: a finished hypothesis' token log-probs, at [NT] that of its <eot> (0: cut at the
+ *           budget); uploaded and downloaded whole
+ *   out     lphist2 [2][R][NT]: both parity halves whole; lphist went into half step & 1, the rest holds sentinel_f */
+int32_t fw_test_dec_beam_update_lp(fw_model* m, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                   int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                   const int32_t* cand_tok, const float* cand_lp, const int32_t* hist,
+                                   const float* lphist, const uint8_t* kvidx, const float* cum, int32_t sentinel_i,
+                                   float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin, int32_t* fin_tok,
+                                   int32_t* fin_len, float* fin_score, float* fin_cum, float* fin_lp, int32_t* hist2,
+                                   float* lphist2, uint8_t* kvidx2, float* cum2, int32_t* cur_tok);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
