@@ -22,19 +22,28 @@ struct GenDev {
   unsigned seed_lo, seed_hi;
   int kv_div;              // decode chunks per encoder chunk (sampling: num_hypotheses), 1 otherwise
   int ctx, cache_rows;     // self-attention cache geometry of this run: positions per slot, slots per layer
+  // RAGGED run (calls of different prompt lengths in one run): the step kernels take each chunk's prompt length from a
+  // device table instead of P, `reach` = min(max_length, n_text_ctx) is where every chunk's budget ends; P is then the
+  // shortest prompt and budget the longest budget.  0 / 0 in a uniform run: a cached step graph captured the table
+  // pointer (or null) by value, so the two kinds never share a graph.
+  int ragged, reach;
 };
 
+// ptab != null (decode steps of a ragged run; ignored with an explicit position): [chunks] prompt length per chunk, the
+// position of chunk c is min(ptab[c] - 1 + step, reach - 1) instead of P - 1 + step; kmul = rows per chunk
 // blk_n > 0: POSITION BLOCKS (prompt forward, align) — the rows of a chunk are blk_n consecutive positions pos_fixed ..
 // of its beam slot 0 (row = chunk * blk_n + j) instead of beams at one position; same per-row arithmetic, same bits
 void launch_embed(hipStream_t st, const int* tok, const half_t* emb, const half_t* pos_emb, half_t* x, half_t* xfrag,
                   int rows, int d,
-                  const int* d_step, int pos_fixed, int P, int blk_n = 0);
+                  const int* d_step, int pos_fixed, int P, int blk_n = 0,
+                  const int* ptab = nullptr, int kmul = 0, int reach = 0);
 // whether launch_self_attn can take position blocks for this cache geometry
 bool self_attn_block_ok(int n_ctx, int cache_ctx, int d, int R_total);
 // n_ctx: stride of the slot table (the text context); cache_ctx: positions per slot of the K/V cache of this run
 void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half_t* vc, int n_ctx, int cache_ctx, int H,
                       const uint8_t* kvidx2, int Kbeam, int kmul, half_t* out, int rows, const int* d_step,
-                      int pos_fixed, int P, int R_total, int frag, int blk_n = 0);
+                      int pos_fixed, int P, int R_total, int frag, int blk_n = 0, const int* ptab = nullptr,
+                      int reach = 0);
 // 0: the product's choice by launch size; 1: the first form (rounds 1-4); 2: latency form; 3: throughput form (same bits)
 void set_self_attn_form(int form);
 void set_cross_attn_regs(int cap);   // fw_test_knob(7, ..): register cap of dec_cross_attn_kernel (0 none, 1: 96, 2: 80)
@@ -84,7 +93,12 @@ void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, cons
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
                         int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum,
-                        const float* cand_lp = nullptr, float* lphist2 = nullptr, float* fin_lp = nullptr);
+                        const float* cand_lp = nullptr, float* lphist2 = nullptr, float* fin_lp = nullptr,
+                        const int* ptab = nullptr);
+// ragged runs: rows of the final hidden state at each chunk's <sot> position -> row `chunk` of xo (row-major) and xof
+// (fragment-major); nb > 0: a prompt pass over positions pos0 .. (row = chunk * nb + j), nb == 0: decode step 0
+void launch_gather_sot_rows(hipStream_t st, const half_t* x, const int* sot_tab, const int* ptab, int pos0, int nb,
+                            int rows_per_chunk, half_t* xo, half_t* xof, int d, int B);
 void launch_step_advance(hipStream_t st, int* d_step);
 // row b reads logits row b * row_mul
 void launch_token_prob(hipStream_t st, const float* logits, int V, const int* target, float* out, int out_stride,

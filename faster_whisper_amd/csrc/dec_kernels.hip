@@ -33,13 +33,26 @@ __device__ __forceinline__ size_t frag_off(int row, int k, int KS) {
   return ((size_t)((row >> 4) * KS + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + (row & 15)) * 8 + (k & 7);
 }
 
+// A decode step of a RAGGED run (calls of different prompt lengths, decoder.hip) takes the prompt length of the row's
+// chunk from `ptab`: the chunk's position is ptab[chunk] - 1 + step, held at reach - 1 once the chunk has used up its own
+// budget (the run goes on for the chunks with shorter prompts; a live chunk never gets there).
+static __device__ __forceinline__ int ragged_pos(const int* __restrict__ ptab, int chunk, int step, int reach) {
+  const int p = ptab[chunk] - 1 + step;
+  return p < reach ? p : reach - 1;
+}
+
 // blk_n > 0 (position blocks: prompt forward, align): row r = chunk * blk_n + j is position pos_fixed + j
+// ptab != null (ragged run, decode steps only): the rows of a chunk are `kmul` beams at the chunk's own position
 __global__ void dec_embed_kernel(const int* __restrict__ tok, const half_t* __restrict__ emb,
                                  const half_t* __restrict__ pos_emb, half_t* __restrict__ x,
                                  half_t* __restrict__ xfrag, int d, const int* __restrict__ d_step, int pos_fixed,
-                                 int P, int blk_n) {
+                                 int P, int blk_n, const int* __restrict__ ptab, int kmul, int reach) {
   const int r = blockIdx.x;
-  const int pos = blk_n > 0 ? pos_fixed + r % blk_n : (pos_fixed >= 0 ? pos_fixed : P - 1 + *d_step);
+  int pos;
+  if (blk_n > 0) pos = pos_fixed + r % blk_n;
+  else if (pos_fixed >= 0) pos = pos_fixed;
+  else if (ptab) pos = ragged_pos(ptab, r / kmul, *d_step, reach);
+  else pos = P - 1 + *d_step;
   const half2_t* e = reinterpret_cast<const half2_t*>(emb + (size_t)tok[r] * d);
   const half2_t* pe = reinterpret_cast<const half2_t*>(pos_emb + (size_t)pos * d);
   half2_t* xo = reinterpret_cast<half2_t*>(x + (size_t)r * d);
@@ -983,11 +996,15 @@ static __device__ __forceinline__ float sum8_dpp(float v) {
 }
 // (8 waves per SIMD: the kernel waits on memory 70 % of its wave cycles (profiles/r03_pmc_sq.json) with 70 registers = 7
 //  waves; at 55 registers it spills nothing and a CU holds six (head, chunk) workgroups of five beams instead of five)
+// RAG (ragged run, decode steps): the chunk's position comes from the prompt-length table (ragged_pos), one scalar load
+// at kernel entry.  An instantiation of its own: uniform runs launch the kernel they always did, ptab / reach unused.
+template <bool RAG = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void dec_self_attn_kernel(const half_t* __restrict__ qkv, int d, half_t* __restrict__ kc,
                                                              half_t* __restrict__ vc, int n_ctx, int cache_ctx,
                                                              int H, const uint8_t* __restrict__ kvidx2, int Kbeam, int kmul,
                                                              half_t* __restrict__ out, const int* __restrict__ d_step,
-                                                             int pos_fixed, int P, int R_total, int frag) {
+                                                             int pos_fixed, int P, int R_total, int frag,
+                                                             const int* __restrict__ ptab, int reach) {
   extern __shared__ float sa_smem[];            // per wave: sp[n_ctx] floats, ssrc[n_ctx] ints
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -996,7 +1013,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
   const int h = blockIdx.x, c = blockIdx.y;
   const int r = c * kmul + wave, kb = wave;
   const int step = *d_step;
-  const int pos = pos_fixed >= 0 ? pos_fixed : P - 1 + step;
+  const int pos = RAG ? ragged_pos(ptab, c, step, reach) : (pos_fixed >= 0 ? pos_fixed : P - 1 + step);
   const int slot = c * Kbeam + kb;
   const int cur = (pos_fixed >= 0) ? 0 : (step & 1);
   const uint8_t* kvidx = kvidx2 + ((size_t)cur * R_total + slot) * n_ctx;
@@ -1107,12 +1124,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 // of the chunk's beam slot 0 instead of kmul beams at one position.  Position p of the same block is a sibling row of
 // this launch: its K / V are read from the qkv buffer (the bytes the sibling writes to the cache), earlier positions
 // from the cache — the same values in the same order as position-by-position launches: the same bits.
-template <int U, bool PIPE, int MAXT, bool PB = false>
+// RAG: as in the first form (never together with PB: the prompt forward of a ragged run gives explicit positions).
+template <int U, bool PIPE, int MAXT, bool PB = false, bool RAG = false>
 __global__ __launch_bounds__(MAXT) void dec_self_attn2_kernel(const half_t* __restrict__ qkv, int d, half_t* __restrict__ kc,
                                                              half_t* __restrict__ vc, int n_ctx, int cache_ctx,
                                                              int H, const uint8_t* __restrict__ kvidx2, int Kbeam, int kmul,
                                                              half_t* __restrict__ out, const int* __restrict__ d_step,
-                                                             int pos_fixed, int P, int R_total, int frag) {
+                                                             int pos_fixed, int P, int R_total, int frag,
+                                                             const int* __restrict__ ptab, int reach) {
+  static_assert(!(PB && RAG), "position blocks take explicit positions");
   extern __shared__ float sa_smem[];            // per wave: sp[n_ctx] floats, ssrc[n_ctx] ints
   constexpr int NB = 4 * U;                     // rows per lane and batch; a batch covers 8 * NB positions
   const int lane = threadIdx.x & 63;
@@ -1122,7 +1142,8 @@ __global__ __launch_bounds__(MAXT) void dec_self_attn2_kernel(const half_t* __re
   const int h = blockIdx.x, c = blockIdx.y;
   const int r = c * kmul + wave, kb = PB ? 0 : wave;
   const int step = PB ? 0 : *d_step;
-  const int pos = PB ? pos_fixed + wave : (pos_fixed >= 0 ? pos_fixed : P - 1 + step);
+  const int pos = PB ? pos_fixed + wave
+                     : (RAG ? ragged_pos(ptab, c, step, reach) : (pos_fixed >= 0 ? pos_fixed : P - 1 + step));
   const int slot = c * Kbeam + kb;
   const int cur = (pos_fixed >= 0) ? 0 : (step & 1);
   const uint8_t* kvidx = kvidx2 + ((size_t)cur * R_total + slot) * n_ctx;
@@ -1730,8 +1751,12 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
 // ------------------------------------------------------------------------------------
 // (amdgpu_waves_per_eu: with the three log-prob pointers the kernel's scalar registers pass 102 and the compiler would
 //  budget 7 waves per SIMD instead of 8; held at 8, 32 scalars live in lanes of two vector registers, nothing in scratch)
+// RAG (ragged run, an instantiation of its own): the chunk's prompt length comes from ptab; its slot-table byte goes to
+// ptab[c] - 1 + step and its last step is the one that uses up ITS budget, gp.reach - ptab[c].  (A chunk is done from that
+// step on and returns at the top: the position needs no clamp here.)
+template <bool RAG>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
-void dec_beam_update_kernel(fwd::GenDev gp, const float* __restrict__ cand_val,
+void dec_beam_update_kernel(fwd::GenDev gp, const int* __restrict__ ptab, const float* __restrict__ cand_val,
                                                              const int* __restrict__ cand_tok, int* __restrict__ hist2,
                                                              float* __restrict__ cum2, uint8_t* __restrict__ kvidx2,
                                                              int* __restrict__ cur_tok, const int* __restrict__ d_step,
@@ -1752,8 +1777,9 @@ void dec_beam_update_kernel(fwd::GenDev gp, const float* __restrict__ cand_val,
   const int K = gp.K, C = 2 * K, NT = gp.n_text_ctx;
   const int step = *d_step;
   const int cur = step & 1, nxt = cur ^ 1;
-  const int pos = gp.P - 1 + step;
-  const bool last_step = (step + 1) >= gp.budget;
+  const int Pc = RAG ? ptab[c] : gp.P;
+  const int pos = Pc - 1 + step;
+  const bool last_step = (step + 1) >= (RAG ? gp.reach - Pc : gp.budget);
   const bool with_lp = cand_lp != nullptr;   // (a kernel argument: uniform)
   if (tid == 0) {
     // ---- merge: top-C of the (live rows x C) candidates ----
@@ -1939,8 +1965,10 @@ namespace fwd {
 // (per linear: DEC_BIG_RULES below)
 
 void launch_embed(hipStream_t st, const int* tok, const half_t* emb, const half_t* pos_emb, half_t* x, half_t* xfrag,
-                  int rows, int d, const int* d_step, int pos_fixed, int P, int blk_n) {
-  dec_embed_kernel<<<rows, 128, 0, st>>>(tok, emb, pos_emb, x, xfrag, d, d_step, pos_fixed, P, blk_n);
+                  int rows, int d, const int* d_step, int pos_fixed, int P, int blk_n, const int* ptab, int kmul,
+                  int reach) {
+  if (blk_n > 0 || pos_fixed >= 0 || kmul < 1) ptab = nullptr;
+  dec_embed_kernel<<<rows, 128, 0, st>>>(tok, emb, pos_emb, x, xfrag, d, d_step, pos_fixed, P, blk_n, ptab, kmul, reach);
 }
 
 template <bool LNF, int RT, int NT, int CH = 0>
@@ -2219,12 +2247,13 @@ bool self_attn_block_ok(int n_ctx, int cache_ctx, int d, int R_total) {
 
 void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half_t* vc, int n_ctx, int cache_ctx, int H,
                       const uint8_t* kvidx2, int Kbeam, int kmul, half_t* out, int rows, const int* d_step,
-                      int pos_fixed, int P, int R_total, int frag, int blk_n) {
+                      int pos_fixed, int P, int R_total, int frag, int blk_n, const int* ptab, int reach) {
   if (blk_n > 0) {   // a block of blk_n consecutive positions per chunk (self_attn_block_ok holds: the caller checked)
     dec_self_attn2_kernel<1, true, 1024, true><<<dim3(H, rows / blk_n), blk_n * 64, (size_t)blk_n * 2 * n_ctx * sizeof(float), st>>>(
-        qkv, d, kc, vc, n_ctx, cache_ctx, H, kvidx2, Kbeam, blk_n, out, d_step, pos_fixed, P, R_total, frag);
+        qkv, d, kc, vc, n_ctx, cache_ctx, H, kvidx2, Kbeam, blk_n, out, d_step, pos_fixed, P, R_total, frag, nullptr, 0);
     return;
   }
+  if (pos_fixed >= 0) ptab = nullptr;   // explicit position: the table is for decode steps
   // one workgroup per (head, chunk), one wave per row of the chunk (kmul <= 16); LDS: scores + source slots per wave
   const dim3 grid(H, rows / kmul);
   const size_t lds = (size_t)kmul * 2 * n_ctx * sizeof(float);
@@ -2233,8 +2262,13 @@ void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half
   if ((n_ctx & 3) != 0 || (size_t)R_total * cache_ctx * d * sizeof(half_t) >= ((size_t)1 << 32)) form = 1;
   if (form == 0) form = (kmul <= 8 && (int)(grid.x * grid.y) <= 768) ? 2 : 3;
   if (form == 2 && kmul > 8) form = 3;
-#define SA_ARGS qkv, d, kc, vc, n_ctx, cache_ctx, H, kvidx2, Kbeam, kmul, out, d_step, pos_fixed, P, R_total, frag
-  if (form == 1) dec_self_attn_kernel<<<grid, kmul * 64, lds, st>>>(SA_ARGS);
+#define SA_ARGS qkv, d, kc, vc, n_ctx, cache_ctx, H, kvidx2, Kbeam, kmul, out, d_step, pos_fixed, P, R_total, frag, ptab, reach
+  if (ptab) {   // ragged run: the same three forms, position per chunk
+    if (form == 1) dec_self_attn_kernel<true><<<grid, kmul * 64, lds, st>>>(SA_ARGS);
+    else if (form == 2) dec_self_attn2_kernel<4, false, 512, false, true><<<grid, kmul * 64, lds, st>>>(SA_ARGS);
+    else dec_self_attn2_kernel<1, true, 1024, false, true><<<grid, kmul * 64, lds, st>>>(SA_ARGS);
+  }
+  else if (form == 1) dec_self_attn_kernel<false><<<grid, kmul * 64, lds, st>>>(SA_ARGS);
   else if (form == 2) dec_self_attn2_kernel<4, false, 512><<<grid, kmul * 64, lds, st>>>(SA_ARGS);   // latency form
   else dec_self_attn2_kernel<1, true, 1024><<<grid, kmul * 64, lds, st>>>(SA_ARGS);                  // throughput form
 #undef SA_ARGS
@@ -2278,11 +2312,46 @@ void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, cons
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
                         int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum, const float* cand_lp,
-                        float* lphist2, float* fin_lp) {
+                        float* lphist2, float* fin_lp, const int* ptab) {
   if (!cand_lp || !lphist2 || !fin_lp) { cand_lp = nullptr; lphist2 = nullptr; fin_lp = nullptr; }   // all three or none
-  dec_beam_update_kernel<<<gp.B, 64, 0, st>>>(gp, cand_val, cand_tok, hist2, cum2, kvidx2, cur_tok, d_step, done,
-                                              n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, cand_lp, lphist2,
-                                              fin_lp);
+#define BU_ARGS gp, ptab, cand_val, cand_tok, hist2, cum2, kvidx2, cur_tok, d_step, done, n_done, n_fin, fin_tok, fin_len, \
+                fin_score, fin_cum, cand_lp, lphist2, fin_lp
+  if (ptab) dec_beam_update_kernel<true><<<gp.B, 64, 0, st>>>(BU_ARGS);
+  else dec_beam_update_kernel<false><<<gp.B, 64, 0, st>>>(BU_ARGS);
+#undef BU_ARGS
+}
+
+// Ragged runs, no-speech probability: the final hidden row of every chunk whose <sot> position falls into this pass goes
+// to row `chunk` of a B-row buffer, row-major (xo: what the final LayerNorm / the row quantiser read) and fragment-major
+// (xof: what the vocabulary projection reads when the LayerNorm is folded into it) — copies, no arithmetic.
+//   nb > 0:  a prompt pass over positions pos0 .. pos0 + nb - 1, row = chunk * nb + j; rows at or beyond the chunk's last
+//            prompt position (ptab[chunk] - 1) are padding and never taken;
+//   nb == 0: decode step 0, `rows_per_chunk` beam rows per chunk, all at the chunk's last prompt position.
+__global__ void dec_gather_sot_rows_kernel(const half_t* __restrict__ x, const int* __restrict__ sot_tab,
+                                           const int* __restrict__ ptab, int pos0, int nb, int rows_per_chunk,
+                                           half_t* __restrict__ xo, half_t* __restrict__ xof, int d) {
+  const int c = blockIdx.x;
+  const int sp = sot_tab[c], last = ptab[c] - 1;
+  int src;
+  if (nb > 0) {
+    if (sp < pos0 || sp >= pos0 + nb || sp >= last) return;
+    src = c * nb + (sp - pos0);
+  } else {
+    if (sp != last) return;
+    src = c * rows_per_chunk;
+  }
+  const half2_t* xi = reinterpret_cast<const half2_t*>(x + (size_t)src * d);
+  half2_t* o = reinterpret_cast<half2_t*>(xo + (size_t)c * d);
+  for (int i = threadIdx.x; i < d / 2; i += blockDim.x) {
+    const half2_t v = xi[i];
+    o[i] = v;
+    *reinterpret_cast<half2_t*>(xof + frag_off(c, 2 * i, d >> 5)) = v;
+  }
+}
+
+void launch_gather_sot_rows(hipStream_t st, const half_t* x, const int* sot_tab, const int* ptab, int pos0, int nb,
+                            int rows_per_chunk, half_t* xo, half_t* xof, int d, int B) {
+  dec_gather_sot_rows_kernel<<<B, 128, 0, st>>>(x, sot_tab, ptab, pos0, nb, rows_per_chunk, xo, xof, d);
 }
 
 void launch_step_advance(hipStream_t st, int* d_step) { dec_step_advance_kernel<<<1, 1, 0, st>>>(d_step); }

@@ -93,6 +93,10 @@ struct GenWorkspace {
   float* no_speech = nullptr;
   unsigned long long* sup_bits = nullptr;   // suppress list, one bit per token id
   int* zero_done = nullptr;              // [R] zeros (kernels that take a `done` pointer outside generate)
+  // ragged runs (calls of different prompt lengths in one run): prompt length and <sot> position per chunk, and the final
+  // hidden rows at the <sot> positions, gathered pass by pass for ONE vocabulary projection (row-major + fragment-major)
+  int *ptab = nullptr, *sot_tab = nullptr;   // [B]
+  half_t *nsp_x = nullptr, *nsp_xf = nullptr;   // [B rounded up to 16][d]
   half_t *x_frag = nullptr, *att_frag = nullptr, *ffn_frag = nullptr;   // fragment-major GEMM inputs (fp16)
   half_t* xn_frag = nullptr;             // fp16(LayerNorm(x)), fragment-major (explicit-LayerNorm order, Model::ln_unfold)
   int8_t* xq = nullptr;                  // int8_float16: quantised linear input, fragment-major [R16][4d]
@@ -238,7 +242,6 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   g->NTs = self_positions(m, g->B, self_ctx > 0 ? self_ctx : c.n_text_ctx);
   g->self_cap = (int64_t)g->R * g->NTs;
   const size_t B = g->B, R = g->R, d = c.d_model, L = c.n_dec_layers, NT = g->NT;
-  (void)B;
   FW_CHECK_ARG(R <= 2048, "decode_batch * max_beam must be <= 2048 (got %zu)", R);
   FW_HIP(hipSetDevice(m->device));
   if (!lane->stream) FW_HIP(create_stream(&lane->stream, "DEC"));
@@ -268,6 +271,13 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   A(g->no_speech, R);
   A(g->sup_bits, (size_t)LP_SUP_WORDS);
   A(g->zero_done, R);
+  const size_t B16 = (B + 15) / 16 * 16;
+  A(g->ptab, B); A(g->sot_tab, B);
+  A(g->nsp_x, B16 * d); A(g->nsp_xf, B16 * d);
+  FW_HIP(hipMemset(g->ptab, 0, B * sizeof(int)));
+  FW_HIP(hipMemset(g->sot_tab, 0, B * sizeof(int)));
+  FW_HIP(hipMemset(g->nsp_x, 0, B16 * d * sizeof(half_t)));
+  FW_HIP(hipMemset(g->nsp_xf, 0, B16 * d * sizeof(half_t)));
   const size_t R16 = (R + 15) / 16 * 16;   // whole 16-row tiles
   if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
     A(g->xq, R16 * 4 * d);
@@ -316,7 +326,7 @@ void gen_workspace_free(DecodeLane* lane) {
                   g->cur_tok, g->hist2, g->cum2, g->kvidx2, g->cand_val, g->cand_tok, g->done, g->n_done, g->n_fin,
                   g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->d_step, g->no_speech, g->sup_bits,
                   g->zero_done, g->xq, g->xs, g->ekq, g->eks, g->x_frag, g->att_frag, g->ffn_frag, g->xn_frag, g->prompt_blk,
-                  g->cand_lp, g->lphist2, g->fin_lp};
+                  g->cand_lp, g->lphist2, g->fin_lp, g->ptab, g->sot_tab, g->nsp_x, g->nsp_xf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete g;
@@ -423,6 +433,7 @@ struct StepCfg {
   int B;
   int pos_fixed;       // >= 0: explicit position (prefill / detect / align); -1: P-1+*d_step
   int P;
+  const int* ptab = nullptr;   // decode steps of a ragged run: [B] prompt length per chunk (device), instead of P
   const int* tok;      // [rows] device
   bool need_logits;
   int nospeech_rowmul; // > 0: run the no-speech kernel on rows b*rowmul after the logits GEMM
@@ -469,6 +480,29 @@ static int pos_block_size(const Model* m, const GenWorkspace* g, const GenDev& g
   return std::max(1, std::min(16, g->R / chunks));
 }
 
+// Final LayerNorm + vocabulary projection of `rows` hidden rows (x row-major, x_frag its fragment-major twin: the one the
+// model's LayerNorm order reads is used) -> g->logits.  Per-row arithmetic: a row gets the same logits wherever it sits.
+static int project_logits(Model* m, DecodeLane* lane, const half_t* x, const half_t* x_frag, int rows) {
+  GenWorkspace* g = lane->gen;
+  const fw_config& c = m->cfg;
+  const int d = c.d_model;
+  hipStream_t st = lane->stream;
+  ProfScope ps(lane->prof, PF_DEC_LOGITS, 2.0 * rows * (double)c.n_vocab * d, 2.0 * c.n_vocab * d, st);
+  if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
+    fwk::launch_quant_rows(st, x, d, m->dec_ln.g, m->dec_ln.b, g->xq, g->xs, rows, d, 1);
+    DG(fwd::launch_dec_logits(st, true, g->xq, g->xs, m->logits.wq, m->logits.wscale, nullptr, nullptr, g->logits,
+                              c.n_vocab, rows, c.n_vocab, d));
+  } else if (m->ln_unfold >= 1) {
+    fwk::launch_layernorm(st, x, m->dec_ln.g, m->dec_ln.b, g->xn_frag, rows, d, 1);
+    DG(fwd::launch_dec_logits(st, false, g->xn_frag, nullptr, m->logits_p.w, nullptr, nullptr, nullptr, g->logits,
+                              c.n_vocab, rows, c.n_vocab, d));
+  } else {
+    DG(fwd::launch_dec_logits(st, false, x_frag, nullptr, m->logits.w, nullptr, m->logits.s1, m->logits.cf, g->logits,
+                              c.n_vocab, rows, c.n_vocab, d));
+  }
+  return FW_OK;
+}
+
 // One decoder forward over `rows` rows.  Everything that varies from step to step lives in HBM (d_step, beam
 // tables), and everything a captured graph bakes in by value is part of GenDev (the graph key).
 static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg& s) {
@@ -483,7 +517,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   {
     ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
     fwd::launch_embed(st, s.tok, m->tok_emb, m->dec_pos, g->x, i8 ? nullptr : g->x_frag, rows, d, g->d_step,
-                      s.pos_fixed, s.P, s.blk_n);
+                      s.pos_fixed, s.P, s.blk_n, s.ptab, s.kmul, gp.reach);
   }
   // int8_float16 (K25): the row quantiser (fused with the LayerNorm where one feeds the linear) writes the int8
   // rows fragment-major, then the int8 skinny GEMM de-quantises in its epilogue
@@ -523,7 +557,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     {
       ProfScope ps(lane->prof, PF_DEC_SELF_ATTN, 0, 0, st);
       fwd::launch_self_attn(st, g->qkv, d, kc, vc, NT, gp.ctx, H, g->kvidx2, gp.K, s.kmul, frag ? g->att_frag : g->att, rows,
-                            g->d_step, s.pos_fixed, s.P, gp.R, frag, s.blk_n);
+                            g->d_step, s.pos_fixed, s.P, gp.R, frag, s.blk_n, s.ptab, gp.reach);
     }
     {
       ProfScope ps(lane->prof, PF_DEC_GEMM_DXD, 2.0 * rows * 2.0 * d * d, 2.0 * 2.0 * d * d, st);
@@ -566,19 +600,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     }
   }
   if (s.need_logits || s.beam_tail) {
-    ProfScope ps(lane->prof, PF_DEC_LOGITS, 2.0 * rows * (double)c.n_vocab * d, 2.0 * c.n_vocab * d, st);
-    if (i8) {
-      fwk::launch_quant_rows(st, g->x, d, m->dec_ln.g, m->dec_ln.b, g->xq, g->xs, rows, d, 1);
-      DG(fwd::launch_dec_logits(st, true, g->xq, g->xs, m->logits.wq, m->logits.wscale, nullptr, nullptr, g->logits,
-                                c.n_vocab, rows, c.n_vocab, d));
-    } else if (m->ln_unfold >= 1) {
-      fwk::launch_layernorm(st, g->x, m->dec_ln.g, m->dec_ln.b, g->xn_frag, rows, d, 1);
-      DG(fwd::launch_dec_logits(st, false, g->xn_frag, nullptr, m->logits_p.w, nullptr, nullptr, nullptr, g->logits,
-                                c.n_vocab, rows, c.n_vocab, d));
-    } else {
-      DG(fwd::launch_dec_logits(st, false, g->x_frag, nullptr, m->logits.w, nullptr, m->logits.s1, m->logits.cf,
-                                g->logits, c.n_vocab, rows, c.n_vocab, d));
-    }
+    if (int rc = project_logits(m, lane, g->x, g->x_frag, rows)) return rc;
   }
   if (s.nospeech_rowmul > 0) {
     ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
@@ -591,7 +613,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
                                g->cand_tok, g->cand_lp);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
                             g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->cand_lp,
-                            g->lphist2, g->fin_lp);
+                            g->lphist2, g->fin_lp, s.ptab);
     fwd::launch_step_advance(st, g->d_step);
   }
   return FW_OK;
@@ -633,12 +655,17 @@ struct GenRequest {
   bool done = false;
 };
 
-// calls that may share a decode run: same scalar options, same prompt length, same suppress list (beam / greedy
-// only: the hypotheses of a sampling call are rows of their own and run alone)
-static bool mergeable(const GenRequest& a, const GenRequest& b) {
+// calls that may share a decode run: same scalar options (max_length among them), same suppress list, same timestamp
+// mode (beam / greedy only: the hypotheses of a sampling call are rows of their own and run alone).  The PROMPT LENGTH and
+// the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
+// every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
+static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling || b.sampling) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
-  if (a.P != b.P || x.beam_size != y.beam_size || x.patience != y.patience || x.num_hypotheses != y.num_hypotheses ||
+  // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
+  // a run only with calls of its own prompt length and <sot> position, as before
+  if ((a.P != b.P || a.sot_pos != b.sot_pos) && std::max(a.P, b.P) >= std::min(x.max_length, n_text_ctx)) return false;
+  if (x.beam_size != y.beam_size || x.patience != y.patience || x.num_hypotheses != y.num_hypotheses ||
       x.length_penalty != y.length_penalty || x.repetition_penalty != y.repetition_penalty ||
       x.no_repeat_ngram_size != y.no_repeat_ngram_size || x.max_length != y.max_length ||
       x.max_initial_timestamp_index != y.max_initial_timestamp_index || x.suppress_blank != y.suppress_blank ||
@@ -646,9 +673,9 @@ static bool mergeable(const GenRequest& a, const GenRequest& b) {
     return false;
   if (x.n_suppress_tokens && memcmp(x.suppress_tokens, y.suppress_tokens, x.n_suppress_tokens * sizeof(int32_t)))
     return false;
-  // the timestamp rules are switched by <|notimestamps|> in the prompt, the <sot> position selects the no-speech
-  // row: both must agree; the prompts themselves may differ (language token per chunk, transcribe.py:212-220)
-  return a.with_ts == b.with_ts && a.sot_pos == b.sot_pos;
+  // the timestamp rules are switched by <|notimestamps|> in the prompt: that must agree; the prompts themselves may
+  // differ (language token per chunk, transcribe.py:212-220; previous text of any length in front of <sot>)
+  return a.with_ts == b.with_ts;
 }
 
 // chunks of a run led by `r` that fit the self-attention cache (before the workspace exists: its planned size)
@@ -697,8 +724,18 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   const fw_config& c = m->cfg;
   const GenRequest& r0 = *reqs[0];
   const fw_gen_opts* o = r0.o;
-  const int K = o->beam_size, P = r0.P;
+  const int K = o->beam_size;
   const bool sampling = r0.sampling;
+  // RAGGED run: its calls differ in prompt length or <sot> position (mergeable() lets them meet).  They share
+  // reach = min(max_length, n_text_ctx), hence the cache geometry; chunk c has its own prompt length P_c and its own budget
+  // reach - P_c.  P is the SHORTEST prompt (the run lasts reach - P steps), Pmax the longest (the prompt forward runs to
+  // Pmax - 1).  A uniform run (P == Pmax, one <sot> position) takes exactly the path it always took.
+  int P = r0.P, Pmax = r0.P;
+  bool ragged = false;
+  for (const GenRequest* r : reqs) {
+    P = std::min(P, r->P); Pmax = std::max(Pmax, r->P);
+    ragged = ragged || r->P != r0.P || r->sot_pos != r0.sot_pos;
+  }
   const int nh = o->num_hypotheses, ml = o->max_length;
   const int kv_div = sampling ? nh : 1;   // decode chunks per encoder chunk
   int B = 0;
@@ -708,6 +745,9 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
                kv_div * K);
   const int budget = max_new_tokens(std::min(o->max_length, c.n_text_ctx), P);
   const int ctx = run_ctx(c, o->max_length, P);
+  const int reach = std::min(o->max_length, c.n_text_ctx);
+  // (every position a ragged run touches lies below reach <= ctx: mergeable() keeps prompts that fill max_length out)
+  FW_CHECK_ARG(!ragged || (!sampling && Pmax < reach && Bx <= g->B), "ragged decode run: prompt of %d tokens with max_length %d", Pmax, ml);
   FW_CHECK_ARG((int64_t)Bx * K * ctx <= g->self_cap, "decode run of %d rows x %d positions exceeds the self-attention cache", Bx * K, ctx);
   FW_HIP(hipSetDevice(m->device));
   hipStream_t st = lane->stream;
@@ -733,8 +773,11 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   }
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
-  gp.B = Bx; gp.K = K; gp.R = Bx * K; gp.P = P; gp.budget = budget; gp.kv_div = kv_div;
+  // (ragged: the step kernels read neither P nor budget — zero in the key, so that ragged runs of one size share a graph
+  //  whatever their prompt lengths)
+  gp.B = Bx; gp.K = K; gp.R = Bx * K; gp.P = ragged ? 0 : P; gp.budget = ragged ? 0 : budget; gp.kv_div = kv_div;
   gp.ctx = ctx; gp.cache_rows = Bx * K;
+  gp.ragged = ragged ? 1 : 0; gp.reach = ragged ? reach : 0;   // (part of the step graph's key)
   gp.sample = sampling ? 1 : 0;
   gp.inv_temp = sampling ? 1.0f / o->sampling_temperature : 1.0f;
   gp.seed_lo = (unsigned)(o->seed & 0xffffffffu);
@@ -742,7 +785,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   gp.max_fin = std::max(1, (int)lroundf((float)K * o->patience));
   if (gp.max_fin > FIN_CAP - K) gp.max_fin = FIN_CAP - K;
   gp.V = c.n_vocab; gp.n_text_ctx = g->NT;
-  const int sot_pos = r0.sot_pos;
+  const int sot_pos = r0.sot_pos;   // (uniform runs; a ragged run reads each chunk's own, see the prompt forward)
   gp.with_ts = r0.with_ts;
   gp.suppress_blank = o->suppress_blank ? 1 : 0;
   gp.min_new = o->min_new_tokens;
@@ -774,17 +817,23 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
     if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
   }
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
-  // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam
-  std::vector<int> ptok((size_t)P * Bx), first((size_t)Bx * K);
+  // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
+  // chunk's last prompt token are padded with that token (see the prompt forward)
+  std::vector<int> ptok((size_t)Pmax * Bx), first((size_t)Bx * K), ptab_host((size_t)Bx), sot_host((size_t)Bx);
   {
     int bx = 0;
     for (const GenRequest* r : reqs)
       for (int b = 0; b < r->B; ++b)
         for (int j = 0; j < kv_div; ++j, ++bx) {
           const int32_t* pr = r->prompts + r->prompt_offsets[b];
-          for (int p = 0; p < P; ++p) ptok[(size_t)p * Bx + bx] = pr[p];
-          for (int k = 0; k < K; ++k) first[(size_t)bx * K + k] = pr[P - 1];
+          for (int p = 0; p < Pmax; ++p) ptok[(size_t)p * Bx + bx] = pr[std::min(p, r->P - 1)];
+          for (int k = 0; k < K; ++k) first[(size_t)bx * K + k] = pr[r->P - 1];
+          ptab_host[bx] = r->P; sot_host[bx] = r->sot_pos;
         }
+  }
+  if (ragged) {
+    FW_HIP(hipMemcpyAsync(g->ptab, ptab_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
+    FW_HIP(hipMemcpyAsync(g->sot_tab, sot_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
   }
   FW_HIP(hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP(hipMemcpyAsync(g->cur_tok, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -800,13 +849,21 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   // ---- prompt forward (all but the last token): Bx rows, beam slot 0 of every chunk ----
   //      in blocks of up to 16 positions per pass (one pass for the 3 positions of the usual 4-token prompt; a prompt that
   //      carries 223 tokens of previous text takes 14 passes instead of 223)
+  //      RAGGED run: the passes run to Pmax - 1 with ALL chunks in every pass.  Chunk c is really there only while
+  //      pos < P_c - 1; in later passes it rides along on padding (its own last prompt token).  That is harmless: a padded
+  //      row reads only its own chunk's cache slot and sibling rows, and what it writes — K / V of beam slot 0 at positions
+  //      >= P_c - 1, all below reach, inside the slot — is written again by the chunk's real decode steps before anything
+  //      reads it: step s writes position P_c - 1 + s on every beam slot and reads only positions below it.  Its valid rows
+  //      (positions < P_c - 1) see exactly what they see in a run of their own, so the chunk's bits do not change.
+  //      The no-speech probability is read at each chunk's own <sot> position: the final hidden row there is gathered into
+  //      a Bx-row buffer as its pass (or step 0) goes by, and ONE vocabulary projection follows step 0.
   {
     const int nbmax = pos_block_size(m, g, gp, Bx);
     std::vector<int> blk_tok;
-    if (nbmax > 1 && P - 1 > 1) {
-      blk_tok.reserve((size_t)(P - 1) * Bx);
-      for (int pos = 0; pos < P - 1;) {
-        const int nb = std::min(nbmax, P - 1 - pos);
+    if (nbmax > 1 && Pmax - 1 > 1) {
+      blk_tok.reserve((size_t)(Pmax - 1) * Bx);
+      for (int pos = 0; pos < Pmax - 1;) {
+        const int nb = std::min(nbmax, Pmax - 1 - pos);
         for (int b = 0; b < Bx; ++b)
           for (int j = 0; j < nb; ++j) blk_tok.push_back(ptok[(size_t)(pos + j) * Bx + b]);
         pos += nb;
@@ -814,11 +871,11 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
       FW_HIP(hipMemcpyAsync(g->prompt_blk, blk_tok.data(), blk_tok.size() * sizeof(int), hipMemcpyHostToDevice, st));
       FW_HIP(hipStreamSynchronize(st));
     }
-    for (int pos = 0; pos < P - 1;) {
-      const int nb = blk_tok.empty() ? 1 : std::min(nbmax, P - 1 - pos);
+    for (int pos = 0; pos < Pmax - 1;) {
+      const int nb = blk_tok.empty() ? 1 : std::min(nbmax, Pmax - 1 - pos);
       StepCfg s;
-      s.B = Bx; s.pos_fixed = pos; s.P = P;
-      s.need_logits = sot_pos >= pos && sot_pos < pos + nb && want_nsp;
+      s.B = Bx; s.pos_fixed = pos; s.P = Pmax;
+      s.need_logits = !ragged && sot_pos >= pos && sot_pos < pos + nb && want_nsp;
       s.beam_tail = false;
       s.done = g->done;
       if (nb > 1) {
@@ -830,6 +887,8 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
         s.nospeech_rowmul = s.need_logits ? 1 : 0;
       }
       if ((rc = run_step(m, lane, gp, s))) return rc;
+      if (ragged && want_nsp)
+        fwd::launch_gather_sot_rows(st, g->x, g->sot_tab, g->ptab, pos, nb, nb, g->nsp_x, g->nsp_xf, c.d_model, Bx);
       pos += nb;
     }
   }
@@ -840,13 +899,22 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
     // ---- step 0 (eager): last prompt token on all rows; beams are identical copies ----
     StepCfg s;
     s.rows = Bx * K; s.kmul = K; s.B = Bx; s.pos_fixed = -1; s.P = P; s.tok = g->cur_tok;
+    s.ptab = ragged ? g->ptab : nullptr;
     s.need_logits = true;
-    s.nospeech_rowmul = (sot_pos == P - 1 && want_nsp) ? K : 0;
+    s.nospeech_rowmul = (!ragged && sot_pos == P - 1 && want_nsp) ? K : 0;
     s.beam_tail = true;
     s.done = g->done;
     if ((rc = run_step(m, lane, gp, s))) return rc;
     steps_done = 1;
     s.nospeech_rowmul = 0;
+    if (ragged && want_nsp) {
+      // the chunks whose prompt ENDS with <sot> had their row in step 0 (g->x still holds its final hidden state); then one
+      // projection over the Bx gathered rows — g->logits is free between two steps
+      fwd::launch_gather_sot_rows(st, g->x, g->sot_tab, g->ptab, 0, 0, K, g->nsp_x, g->nsp_xf, c.d_model, Bx);
+      if ((rc = project_logits(m, lane, g->nsp_x, g->nsp_xf, Bx))) return rc;
+      ProfScope ps(lane->prof, PF_DEC_MISC, 0, 0, st);
+      fwd::launch_nospeech(st, g->logits, c.n_vocab, 1, c.tok_no_speech, g->no_speech, Bx);
+    }
 
     // ---- steps 1.. : one hipGraph replay per step; graphs are cached per GenDev (everything the captured
     //      kernels take by value, kv_div included) ----
@@ -928,7 +996,8 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   for (GenRequest* r : reqs) {
     for (int b = 0; b < r->B; ++b) {
       const int gb = cb + b;
-      if (r->o->return_no_speech_prob) r->out_no_speech[b] = nsp[(size_t)gb * kv_div];
+      // (ragged: a prompt without <sot> has no gathered row — 0, as in a run of its own)
+      if (r->o->return_no_speech_prob) r->out_no_speech[b] = (ragged && r->sot_pos < 0) ? 0.f : nsp[(size_t)gb * kv_div];
       // candidate hypotheses of encoder chunk gb: (decode chunk, finished index)
       std::vector<std::pair<int, int>> hyps;
       for (int j = 0; j < kv_div; ++j) {
@@ -1096,7 +1165,7 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
     std::vector<GenRequest*> batch;
     GenRequest* first = grp.queue.front();
     int chunks = 0;
-    // chunks the self-attention cache holds at this call's context (mergeable calls share max_length and P)
+    // chunks the self-attention cache holds at this call's context (mergeable calls share max_length, hence the context)
     // ... and the rows above which the 4 x 4-tile decoder linears no longer fit the chip in one round of workgroups
     // (d x d: 20 column groups x 25 row groups of 64 rows = 500 of 512 workgroup slots)
     int64_t run_cap = std::min<int64_t>(cap, std::max<int64_t>(first->B, self_chunk_capacity(dm, *first)));
@@ -1106,7 +1175,7 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
     const int max_calls = std::max(1, std::max(dm->decode_batch, dm->max_batch) / dm->max_batch);
     for (auto it = grp.queue.begin(); it != grp.queue.end();) {
       GenRequest* r = *it;
-      if (r == first || (mergeable(*first, *r) && chunks + r->B <= run_cap && (int)batch.size() < max_calls)) {
+      if (r == first || (mergeable(*first, *r, c.n_text_ctx) && chunks + r->B <= run_cap && (int)batch.size() < max_calls)) {
         batch.push_back(r);
         r->taken = true;
         chunks += r->B;
@@ -1140,8 +1209,10 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
       const auto t_run1 = std::chrono::steady_clock::now();
       const double s0 = std::chrono::duration<double>(t_run0.time_since_epoch()).count();
       const double s1 = std::chrono::duration<double>(t_run1.time_since_epoch()).count();
-      fprintf(stderr, "[fwamd run] lane %d calls %d chunks %d start %.4f end %.4f (%.1f ms)\n", lane, (int)batch.size(), chunks,
-              s0, s1, 1e3 * (s1 - s0));
+      int p_lo = batch[0]->P, p_hi = batch[0]->P;
+      for (const GenRequest* r : batch) { p_lo = std::min(p_lo, r->P); p_hi = std::max(p_hi, r->P); }
+      fprintf(stderr, "[fwamd run] lane %d calls %d chunks %d prompt %d..%d start %.4f end %.4f (%.1f ms)\n", lane,
+              (int)batch.size(), chunks, p_lo, p_hi, s0, s1, 1e3 * (s1 - s0));
     }
     const std::string err = rc ? fw_last_error() : "";
     lk.lock();

@@ -156,7 +156,8 @@ struct DecodeLane {
 };
 
 // Decode group of a device: the worker replicas that share one decode workspace.  Concurrent fw_generate calls
-// with identical options are merged into ONE decode run (their rows share every weight byte streamed per step);
+// whose options agree (decoder.hip: mergeable(); the prompt length need not) are merged into ONE decode run (their rows
+// share every weight byte streamed per step);
 // the first caller that finds no run in progress leads it, the others wait for their results.
 struct DecodeGroup {
   std::mutex mu;

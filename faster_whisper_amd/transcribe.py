@@ -454,6 +454,57 @@ class WhisperModel:
                                  vad_options=vad_parameters, all_language_probs=all_language_probs)
         return segments, info
 
+    # ---- many recordings through the sequential path ----
+    def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]], *, language=None, initial_prompt=None,
+                        **transcribe_kwargs) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+        """Sequential (seek-loop) transcription of several recordings in ONE call: the sequential counterpart of
+        BatchedInferencePipeline.transcribe_many.  result[i] = (list of segments, info) in input order.
+
+        The N transcribe() generators are run to completion on a pool of at most `num_workers` threads; each thread
+        works on one worker replica, as concurrent transcribe() calls do.  The windows the threads decode at the same
+        time share decode runs — also with condition_on_previous_text=True, where every window's prompt carries a
+        different amount of previous text: calls of different prompt lengths may share a run (include/fwamd.h).
+
+        language, initial_prompt: one value for all recordings (None, a string, for initial_prompt also a sequence of
+        token ids), or a sequence with one entry per recording.  Every other keyword is transcribe()'s.
+
+        With a temperature ladder that never leaves 0 (`temperature=0`, or thresholds that no decode fails) result[i] is
+        field for field what `transcribe(audios[i], ...)` alone returns: a decode run gives every caller what it gets
+        alone.  Sampled fallback attempts (temperature > 0) draw their seeds from the model's call counter in ARRIVAL
+        order, as concurrent transcribe() calls always did: which recording gets which seed then depends on timing.
+        An exception in one recording is raised here, after the recordings already started have finished."""
+        n = len(audios)
+        if n == 0:
+            return []
+        languages = self._per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
+        prompts = self._per_recording(
+            initial_prompt, n, "initial_prompt",
+            lambda v: v is None or isinstance(v, str)
+            or (len(v) != 0 and all(isinstance(t, (int, np.integer)) for t in v)))
+
+        def one(i):
+            segments, info = self.transcribe(audios[i], language=languages[i], initial_prompt=prompts[i],
+                                             **transcribe_kwargs)
+            return list(segments), info
+
+        workers = min(n, int(getattr(self.model, "inter_threads", 1) or 1))
+        if workers <= 1:
+            return [one(i) for i in range(n)]
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            futures = [pool.submit(one, i) for i in range(n)]
+            return [f.result() for f in futures]
+
+    @staticmethod
+    def _per_recording(value, n, name, is_single):
+        """one value for all recordings, or a sequence with one entry per recording -> a list of n"""
+        if is_single(value):
+            return [value] * n
+        value = list(value)
+        if len(value) != n:
+            raise ValueError(f"{name} has {len(value)} entries for {n} recordings")
+        return value
+
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
                           token_logprobs: bool = False):

@@ -174,9 +174,16 @@ int32_t fw_model_create_from_blob_dev(const fw_config* cfg, const void* blob_dev
  *       arrive during the rebuild wait for it;
  *   fw_model_join_decoder(worker, primary)  frees the worker's own decode workspace and routes its fw_generate /
  *       fw_detect_language / fw_align calls to the primary's.
- * fw_generate calls with identical options that arrive from different host threads while a decode run is in
- * progress are merged into the next run (up to decode_batch chunks); each caller gets exactly the result it would
- * get alone.  Encoders keep running per worker on their own streams and overlap with the running decode. */
+ * fw_generate calls that arrive from different host threads while a decode run is in progress are merged into the
+ * next run (up to decode_batch chunks); each caller gets exactly the result it would get alone.  What must agree for two
+ * calls to share a run: beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
+ * max_length, max_initial_timestamp_index, suppress_blank, min_new_tokens, the suppress list, and the timestamp mode
+ * (<|notimestamps|> in the prompt or not); sampling calls run alone.  The PROMPT LENGTH and the position of
+ * <|startoftranscript|> need NOT agree: every chunk of a run decodes at its own position of the text context with its
+ * own budget min(max_length, n_text_ctx) - prompt length (so prompts that carry different amounts of previous text
+ * share a run; only a call whose prompt already fills max_length keeps to calls of its own prompt length).  Inside ONE
+ * call all prompts must still have the same length (FW_EINVAL).  Encoders keep running per worker on their own streams
+ * and overlap with the running decode. */
 int32_t fw_model_set_decode_batch(fw_model* m, int32_t decode_batch);
 int32_t fw_model_decode_batch(const fw_model* m);
 /* chunks one decode run of the group can hold (<= fw_model_decode_batch) */

@@ -9,6 +9,16 @@ the VAD runs on the device with the peaked Silero weights of tests/test_gpu_c5.p
     (c) many        transcribe_many(recordings)
 plus the VAD front alone: N per-recording device calls (SileroVADModel.__call__) against one batched call (forward_many).
 Before any figure is printed, (c) is compared with (a) segment for segment (every field) and must be equal.
+A fourth way, for the SEQUENTIAL path (`--sequential N`, longer recordings of `--seq-seconds` LO HI, no VAD):
+    (d) seq_pool    `--workers` host threads, each calling WhisperModel.transcribe(condition_on_previous_text=True) on the
+                    next recording: every later window's prompt carries its own amount of previous text
+        seq_many    WhisperModel.transcribe_many(recordings, condition_on_previous_text=True), compared with seq_pool
+                    recording for recording before its figure counts
+    each with the decode group's counters over that way (decode runs, chunks, largest run): calls of different prompt lengths
+    share decode runs, so both should show fewer, larger runs than a build in which they cannot.  `--sequential-only`
+    skips (a) - (c) and the VAD front.  max_length stays 448 for every window (max_new_tokens would tie it to the prompt
+    length, and calls that differ in max_length never share a run); nothing is suppressed and every recording has an
+    initial prompt of its own length, so prompt lengths differ between recordings and from window to window.  (largest_run is the group's running maximum: the second way's figure is the maximum over both.)
 Prints one JSON line (and writes it to --out).  Needs a GPU; there is no fallback.
 
     python profiles/many_bench.py --out profiles/many_bench.json
@@ -39,6 +49,66 @@ def recordings(n, seed):
     return out
 
 
+def long_recordings(n, seed, lo, hi):
+    """n recordings of lo - hi s: bursts of 9 - 24 s with half a second of digital silence after each"""
+    from test_gpu_c5 import recording
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        total, spans = float(rng.uniform(lo, hi)), []
+        while total > 0:
+            sp = min(total, float(rng.uniform(9.0, 24.0)))
+            spans.append((sp, 0.5))
+            total -= sp + 0.5
+        out.append(recording(spans, seed=seed + 50 * i))
+    return out
+
+
+def sequential_modes(args, backend, wm, cfg):
+    """(d): thread pool of WhisperModel.transcribe against WhisperModel.transcribe_many, condition_on_previous_text=True"""
+    recs = long_recordings(args.sequential, args.seed + 7, *args.seq_seconds)
+    audio_s = sum(len(a) for a in recs) / 16000.0
+    # nothing suppressed: a window's text ends where the (synthetic) model says <|endoftext|>, so the previous text differs
+    # in length from window to window; and every recording starts from an initial prompt of its own length (0 - 120 tokens)
+    kw = dict(language="en", beam_size=args.beam, temperature=0.0, condition_on_previous_text=True,
+              without_timestamps=True, suppress_tokens=[])
+    rng = np.random.default_rng(args.seed + 11)
+    initial = [[int(t) for t in rng.integers(1000, 20000, size=int(n))] or None
+               for n in rng.integers(0, 121, size=len(recs))]
+
+    def seq_pool(k):
+        def one(i):
+            s, info = wm.transcribe(recs[i], initial_prompt=initial[i], **kw)
+            return list(s), info
+        with ThreadPoolExecutor(max_workers=args.workers) as ex:
+            return list(ex.map(one, range(k)))
+
+    def seq_many(k):
+        return wm.transcribe_many(recs[:k], initial_prompt=initial[:k], **kw)
+
+    ways = [seq_pool] + ([seq_many] if hasattr(wm, "transcribe_many") else [])
+    for fn in ways:                              # warm-up: code objects, workspaces, thread replicas
+        fn(min(len(recs), max(2, args.workers // 4)))
+    out, results = {"recordings": len(recs), "audio_s": round(audio_s, 1)}, {}
+    for fn in ways:
+        backend.synchronize()
+        st0 = backend.decode_stats()
+        t = time.perf_counter()
+        results[fn.__name__] = fn(len(recs))
+        dt = time.perf_counter() - t
+        st = backend.decode_stats()
+        print(f"[many_bench] {fn.__name__}: {dt:.3f} s", file=sys.stderr, flush=True)
+        out[fn.__name__] = {"wall_s": round(dt, 3), "rate": round(audio_s / dt, 1),
+                            "decode_stats": {"runs": st["runs"] - st0["runs"], "calls": st["requests"] - st0["requests"],
+                                             "chunks": st["chunks"] - st0["chunks"], "largest_run": st["max_run_chunks"]}}
+    if "seq_many" in results:
+        for r, ((gs, gi), (ws, wi)) in enumerate(zip(results["seq_many"], results["seq_pool"])):
+            assert [dataclasses.asdict(s) for s in gs] == [dataclasses.asdict(s) for s in ws], f"recording {r}: segments differ"
+            assert dataclasses.asdict(gi) == dataclasses.asdict(wi), f"recording {r}: info differs"
+        out["seq_many_equals_seq_pool"] = True
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("-n", "--recordings", type=int, default=256)
@@ -49,6 +119,9 @@ def main(argv=None):
     ap.add_argument("--new-tokens", type=int, default=100)
     ap.add_argument("--pool-reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=4000)
+    ap.add_argument("--sequential", type=int, default=0, help="(d): recordings for the sequential ways (0: skip them)")
+    ap.add_argument("--seq-seconds", type=float, nargs=2, default=(60.0, 120.0), metavar=("LO", "HI"))
+    ap.add_argument("--sequential-only", action="store_true", help="only (d): no loop / pool / many, no VAD front")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
 
@@ -68,6 +141,17 @@ def main(argv=None):
     load_s = time.perf_counter() - t0
     print(f"[many_bench] model loaded in {load_s:.1f} s", file=sys.stderr, flush=True)
     wm = bench.host_model(backend, cfg)
+    if args.sequential_only:
+        out = {"what": "long recordings, sequential path: thread pool of WhisperModel.transcribe / WhisperModel.transcribe_many",
+               "unit": "audio-seconds per wall-second", "model": args.model, "compute_type": "float16", "beam": args.beam,
+               "workers": args.workers, "model_load_s": round(load_s, 1),
+               "sequential": sequential_modes(args, backend, wm, cfg)}
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return out
     dev = fvad.SileroVADModel(weights=peaked_vad_weights(), device="cuda")
     fvad._VAD_MODEL = dev                       # what transcribe(vad_filter=True) runs per call
     recs = recordings(args.recordings, args.seed)
@@ -156,6 +240,8 @@ def main(argv=None):
                          "windows": int(sum(len(a) for a in padded) // 512), "equal": True},
         "decode_stats": backend.decode_stats(),
     }
+    if args.sequential > 0:
+        out["sequential"] = sequential_modes(args, backend, wm, cfg)
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:
