@@ -212,6 +212,32 @@ def call_seed(n: int) -> int:
     return z ^ (z >> 31)
 
 
+def _splitmix64(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
+
+
+def attempt_seed(base: int, seek: int, temperature_index: int) -> int:
+    """seed of ONE sampled fallback attempt of a transcribe(sampling_seed=base) call: the attempt at rung
+    `temperature_index` of the temperature ladder for the window that starts at frame `seek`.  Three chained splitmix64
+    steps (base, then seek, then the rung, each added to the state before the next mix): a pure function of its
+    arguments, so the attempt draws the same samples whatever ran before it or runs beside it, and two windows or two
+    rungs of one recording never share a seed by construction of the mix (64-bit collisions aside)."""
+    z = _splitmix64(int(base) & 0xFFFFFFFFFFFFFFFF)
+    z = _splitmix64(z ^ (int(seek) & 0xFFFFFFFFFFFFFFFF))
+    return _splitmix64(z ^ (int(temperature_index) & 0xFFFFFFFFFFFFFFFF))
+
+
+def recording_seed(base: int, i: int) -> int:
+    """sampling_seed of recording `i` of a transcribe_many(sampling_seed=base) call: splitmix64 of the mixed base with
+    the recording's index folded in (under a constant that keeps it apart from attempt_seed's chain).  result[i] of that
+    call is transcribe(audios[i], sampling_seed=recording_seed(base, i))."""
+    z = _splitmix64((int(base) & 0xFFFFFFFFFFFFFFFF) ^ 0xD1B54A32D192ED03)
+    return _splitmix64(z ^ (int(i) & 0xFFFFFFFFFFFFFFFF))
+
+
 class Whisper:
     """Drop-in for ctranslate2.models.Whisper on MI355X.
 
@@ -339,6 +365,15 @@ class Whisper:
         return {"runs": runs.value, "requests": reqs.value, "chunks": chunks.value, "max_run_chunks": mx.value,
                 "decode_batch": int(self._lib.fw_model_decode_batch(self._replicas[0].handle)),
                 "run_capacity": int(self._lib.fw_model_run_capacity(self._replicas[0].handle))}
+
+    def graph_captures(self) -> int:
+        """step graphs the decode group of device 0 has captured since the model was created (fwamd_test.h:
+        fw_test_graph_captures); -1 with an older build loaded through FWAMD_LIB, which does not count them"""
+        if not hasattr(self._lib, "fw_test_graph_captures"):
+            return -1
+        n = C.c_int64()
+        _lib.check(self._lib.fw_test_graph_captures(self._replicas[0].handle, C.byref(n)))
+        return int(n.value)
 
     def dec_big_min_rows(self) -> int:
         """rows from which a decode run's linears take the GEMM-shaped kernel (bench.py prices them accordingly)"""

@@ -18,6 +18,8 @@ struct GenDev {
   int eot, no_ts, ts_begin;
   int n_sup_begin, sup_begin[8];
   int sample;              // 1: draw the next token from softmax(logp / T) instead of arg-max / beam
+  // (sampling runs read temperature and seed per row from a SmpRow table: decode runs set these three to 1, 0, 0, so
+  //  that sampling runs of one size share a step graph whatever their calls' seeds and temperatures)
   float inv_temp;
   unsigned seed_lo, seed_hi;
   int kv_div;              // decode chunks per encoder chunk (sampling: num_hypotheses), 1 otherwise
@@ -28,6 +30,15 @@ struct GenDev {
   // pointer (or null) by value, so the two kinds never share a graph.
   int ragged, reach;
 };
+
+// Sampling runs: one entry per decode row.  The calls of a run keep their own temperature and seed, and a row draws its
+// noise as row `r - row0` of its call: what it is in a run of that call alone.
+struct SmpRow {
+  float inv_temp;
+  unsigned seed_lo, seed_hi;
+  int row0;                // first row of the entry's call inside the run
+};
+static_assert(sizeof(SmpRow) == 16, "one 16-byte load per row");
 
 // ptab != null (decode steps of a ragged run; ignored with an explicit position): [chunks] prompt length per chunk, the
 // position of chunk c is min(ptab[c] - 1 + step, reach - 1) instead of P - 1 + step; kmul = rows per chunk
@@ -83,10 +94,11 @@ int launch_dec_logits(hipStream_t st, bool i8, const void* xf, const float* x_sc
                       const float* w_scale, const float* s1, const float* cf, float* out, int ldo, int R, int N, int K);
 void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, int no_speech_id, float* out, int B);
 // sup_bits: the suppress list, one bit per token id, LP_SUP_WORDS 64-bit words (zero-padded past the vocabulary)
+// smp_tab [gp.R]: read when gp.sample (then it must not be null: the launcher launches nothing without it)
 #define LP_SUP_WORDS 896
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp = nullptr);
+                           int* cand_tok, float* cand_lp = nullptr, const SmpRow* smp_tab = nullptr);
 // cand_lp [R][32]: the log-prob of every candidate (cand_val = cum + cand_lp), lphist2 [2][R][NT] the log-prob history
 // beside hist2, fin_lp [.][FIN_CAP][NT + 1] the values of a finished hypothesis' tokens and, at [NT], of its <eot>.
 // Null (all three of the beam update, or none): the kernels skip these stores.

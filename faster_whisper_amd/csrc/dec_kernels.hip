@@ -1501,7 +1501,8 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
                                                                         const int* __restrict__ done,
                                                                         float* __restrict__ cand_val,
                                                                         int* __restrict__ cand_tok,
-                                                                        float* __restrict__ cand_lp) {
+                                                                        float* __restrict__ cand_lp,
+                                                                        const fwd::SmpRow* __restrict__ smp_tab) {
   __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
   __shared__ float bkey_s[2][LP_WAVES];
   __shared__ int btok_s[2][LP_WAVES];
@@ -1666,6 +1667,10 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
   // ---- log-probs; this thread's best key ----
   const float cum = cum2[(size_t)cur * gp.R + r];
   constexpr bool smp = SMP;   // a separate instantiation: 2 x 56 inlined logf stay out of the beam / greedy kernel
+  // sampling: temperature, seed and first row of this row's CALL (one uniform 16-byte load; the other instantiations
+  // never touch the table).  The noise of a row depends on (seed of its call, row inside its call, step, token) only.
+  fwd::SmpRow sr = {1.0f, 0u, 0u, 0};
+  if (smp) sr = smp_tab[r];
   const int C = smp ? 1 : 2 * gp.K;
   float bkey = NEG;
   int bq = -1;
@@ -1677,7 +1682,7 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
     x = x - lse_sub;
     val[i] = x;
     float key = x;
-    if (smp && x != NEG) key = x * gp.inv_temp + gumbel_noise(gp.seed_lo, gp.seed_hi, (unsigned)r, (unsigned)step, (unsigned)v);
+    if (smp && x != NEG) key = x * sr.inv_temp + gumbel_noise(sr.seed_lo, sr.seed_hi, (unsigned)(r - sr.row0), (unsigned)step, (unsigned)v);
     if (key > bkey) { bkey = key; bq = i; }   // ascending index: ties keep the lowest
   }
   // ---- top-C of cum + logp: C rounds (value desc, index asc).  Sampling mode (Gumbel-max): one round on
@@ -2298,12 +2303,13 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp) {
+                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab) {
+  if (gp.sample && !smp_tab) return;   // (a sampling launch without its table: nothing is launched, nothing is read)
   // every Whisper vocabulary keeps its timestamp ids above 48 * 1024 (ts_begin 50 363 .. 50 365); the synthetic
   // test vocabularies do not: they take the instantiation with a per-lane class test everywhere
   const bool wide = gp.ts_begin >= 48 * LP_THREADS;
 #define LP_GO(SMP, TXI) \
-  dec_logits_process_kernel<SMP, TXI><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp)
+  dec_logits_process_kernel<SMP, TXI><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab)
   if (gp.sample) { if (wide) LP_GO(true, 48); else LP_GO(true, 0); }
   else { if (wide) LP_GO(false, 48); else LP_GO(false, 0); }
 #undef LP_GO

@@ -95,8 +95,11 @@ struct GenWorkspace {
   int* zero_done = nullptr;              // [R] zeros (kernels that take a `done` pointer outside generate)
   // ragged runs (calls of different prompt lengths in one run): prompt length and <sot> position per chunk, and the final
   // hidden rows at the <sot> positions, gathered pass by pass for ONE vocabulary projection (row-major + fragment-major)
-  int *ptab = nullptr, *sot_tab = nullptr;   // [B]
-  half_t *nsp_x = nullptr, *nsp_xf = nullptr;   // [B rounded up to 16][d]
+  // (per DECODE chunk: a sampling run has num_hypotheses decode chunks per encoder chunk, up to R of them)
+  int *ptab = nullptr, *sot_tab = nullptr;   // [R]
+  half_t *nsp_x = nullptr, *nsp_xf = nullptr;   // [R rounded up to 16][d]
+  // sampling runs: temperature, seed and first row of its call for every decode row (dec_kernels.h)
+  fwd::SmpRow* smp_tab = nullptr;            // [R]
   half_t *x_frag = nullptr, *att_frag = nullptr, *ffn_frag = nullptr;   // fragment-major GEMM inputs (fp16)
   half_t* xn_frag = nullptr;             // fp16(LayerNorm(x)), fragment-major (explicit-LayerNorm order, Model::ln_unfold)
   int8_t* xq = nullptr;                  // int8_float16: quantised linear input, fragment-major [R16][4d]
@@ -241,7 +244,7 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   g->NT = c.n_text_ctx;
   g->NTs = self_positions(m, g->B, self_ctx > 0 ? self_ctx : c.n_text_ctx);
   g->self_cap = (int64_t)g->R * g->NTs;
-  const size_t B = g->B, R = g->R, d = c.d_model, L = c.n_dec_layers, NT = g->NT;
+  const size_t R = g->R, d = c.d_model, L = c.n_dec_layers, NT = g->NT;
   FW_CHECK_ARG(R <= 2048, "decode_batch * max_beam must be <= 2048 (got %zu)", R);
   FW_HIP(hipSetDevice(m->device));
   if (!lane->stream) FW_HIP(create_stream(&lane->stream, "DEC"));
@@ -271,14 +274,15 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   A(g->no_speech, R);
   A(g->sup_bits, (size_t)LP_SUP_WORDS);
   A(g->zero_done, R);
-  const size_t B16 = (B + 15) / 16 * 16;
-  A(g->ptab, B); A(g->sot_tab, B);
-  A(g->nsp_x, B16 * d); A(g->nsp_xf, B16 * d);
-  FW_HIP(hipMemset(g->ptab, 0, B * sizeof(int)));
-  FW_HIP(hipMemset(g->sot_tab, 0, B * sizeof(int)));
-  FW_HIP(hipMemset(g->nsp_x, 0, B16 * d * sizeof(half_t)));
-  FW_HIP(hipMemset(g->nsp_xf, 0, B16 * d * sizeof(half_t)));
   const size_t R16 = (R + 15) / 16 * 16;   // whole 16-row tiles
+  A(g->ptab, R); A(g->sot_tab, R);
+  A(g->nsp_x, R16 * d); A(g->nsp_xf, R16 * d);
+  A(g->smp_tab, R);
+  FW_HIP(hipMemset(g->ptab, 0, R * sizeof(int)));
+  FW_HIP(hipMemset(g->sot_tab, 0, R * sizeof(int)));
+  FW_HIP(hipMemset(g->nsp_x, 0, R16 * d * sizeof(half_t)));
+  FW_HIP(hipMemset(g->nsp_xf, 0, R16 * d * sizeof(half_t)));
+  FW_HIP(hipMemset(g->smp_tab, 0, R * sizeof(fwd::SmpRow)));
   if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
     A(g->xq, R16 * 4 * d);
     A(g->xs, R16);
@@ -326,7 +330,7 @@ void gen_workspace_free(DecodeLane* lane) {
                   g->cur_tok, g->hist2, g->cum2, g->kvidx2, g->cand_val, g->cand_tok, g->done, g->n_done, g->n_fin,
                   g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->d_step, g->no_speech, g->sup_bits,
                   g->zero_done, g->xq, g->xs, g->ekq, g->eks, g->x_frag, g->att_frag, g->ffn_frag, g->xn_frag, g->prompt_blk,
-                  g->cand_lp, g->lphist2, g->fin_lp, g->ptab, g->sot_tab, g->nsp_x, g->nsp_xf};
+                  g->cand_lp, g->lphist2, g->fin_lp, g->ptab, g->sot_tab, g->nsp_x, g->nsp_xf, g->smp_tab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete g;
@@ -610,7 +614,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   if (s.beam_tail) {
     ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
-                               g->cand_tok, g->cand_lp);
+                               g->cand_tok, g->cand_lp, g->smp_tab);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
                             g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->cand_lp,
                             g->lphist2, g->fin_lp, s.ptab);
@@ -656,11 +660,13 @@ struct GenRequest {
 };
 
 // calls that may share a decode run: same scalar options (max_length among them), same suppress list, same timestamp
-// mode (beam / greedy only: the hypotheses of a sampling call are rows of their own and run alone).  The PROMPT LENGTH and
+// mode.  SAMPLING calls share runs among themselves only (their hypotheses are beam-1 rows of their own, num_hypotheses
+// decode chunks per encoder chunk: a beam or greedy call has one); sampling_temperature and seed need NOT agree, every
+// row reads its call's from the run's SmpRow table.  The PROMPT LENGTH and
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
-  if (a.sampling || b.sampling) return false;
+  if (a.sampling != b.sampling) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -747,7 +753,8 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   const int ctx = run_ctx(c, o->max_length, P);
   const int reach = std::min(o->max_length, c.n_text_ctx);
   // (every position a ragged run touches lies below reach <= ctx: mergeable() keeps prompts that fill max_length out)
-  FW_CHECK_ARG(!ragged || (!sampling && Pmax < reach && Bx <= g->B), "ragged decode run: prompt of %d tokens with max_length %d", Pmax, ml);
+  // (ptab / sot_tab / nsp_x hold one entry per decode chunk, g->R of them: Bx <= g->R was checked above)
+  FW_CHECK_ARG(!ragged || Pmax < reach, "ragged decode run: prompt of %d tokens with max_length %d", Pmax, ml);
   FW_CHECK_ARG((int64_t)Bx * K * ctx <= g->self_cap, "decode run of %d rows x %d positions exceeds the self-attention cache", Bx * K, ctx);
   FW_HIP(hipSetDevice(m->device));
   hipStream_t st = lane->stream;
@@ -779,9 +786,9 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   gp.ctx = ctx; gp.cache_rows = Bx * K;
   gp.ragged = ragged ? 1 : 0; gp.reach = ragged ? reach : 0;   // (part of the step graph's key)
   gp.sample = sampling ? 1 : 0;
-  gp.inv_temp = sampling ? 1.0f / o->sampling_temperature : 1.0f;
-  gp.seed_lo = (unsigned)(o->seed & 0xffffffffu);
-  gp.seed_hi = (unsigned)(o->seed >> 32);
+  // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
+  // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
+  gp.inv_temp = 1.0f; gp.seed_lo = 0; gp.seed_hi = 0;
   gp.max_fin = std::max(1, (int)lroundf((float)K * o->patience));
   if (gp.max_fin > FIN_CAP - K) gp.max_fin = FIN_CAP - K;
   gp.V = c.n_vocab; gp.n_text_ctx = g->NT;
@@ -820,17 +827,25 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
   std::vector<int> ptok((size_t)Pmax * Bx), first((size_t)Bx * K), ptab_host((size_t)Bx), sot_host((size_t)Bx);
+  std::vector<fwd::SmpRow> smp_host(sampling ? (size_t)Bx : 0);   // (sampling: K == 1, decode chunk bx is row bx)
   {
     int bx = 0;
-    for (const GenRequest* r : reqs)
+    for (const GenRequest* r : reqs) {
+      const int row0 = bx;   // first row of this call: its rows draw their noise as rows 0 .. of a run of their own
       for (int b = 0; b < r->B; ++b)
         for (int j = 0; j < kv_div; ++j, ++bx) {
           const int32_t* pr = r->prompts + r->prompt_offsets[b];
           for (int p = 0; p < Pmax; ++p) ptok[(size_t)p * Bx + bx] = pr[std::min(p, r->P - 1)];
           for (int k = 0; k < K; ++k) first[(size_t)bx * K + k] = pr[r->P - 1];
           ptab_host[bx] = r->P; sot_host[bx] = r->sot_pos;
+          if (sampling)
+            smp_host[bx] = {1.0f / r->o->sampling_temperature, (unsigned)(r->o->seed & 0xffffffffu),
+                            (unsigned)(r->o->seed >> 32), row0};
         }
+    }
   }
+  if (sampling)
+    FW_HIP(hipMemcpyAsync(g->smp_tab, smp_host.data(), (size_t)Bx * sizeof(fwd::SmpRow), hipMemcpyHostToDevice, st));
   if (ragged) {
     FW_HIP(hipMemcpyAsync(g->ptab, ptab_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
     FW_HIP(hipMemcpyAsync(g->sot_tab, sot_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
@@ -940,6 +955,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
               for (GraphSlot& gs : g->graphs) if (gs.stamp < slot->stamp) slot = &gs;
               if (slot->exec) (void)hipGraphExecDestroy(slot->exec);
             }
+            m->grp.graph_captures.fetch_add(1);
             slot->exec = ne; slot->key = gp; slot->stamp = ++g->graph_clock; slot->forms = fwd::kernel_forms_epoch();
             exec = ne;
           }
@@ -1171,6 +1187,8 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
     int64_t run_cap = std::min<int64_t>(cap, std::max<int64_t>(first->B, self_chunk_capacity(dm, *first)));
     if (!first->sampling)
       run_cap = std::min<int64_t>(run_cap, std::max<int64_t>(dm->max_batch, DEC_RUN_MAX_ROWS / std::max(1, first->o->beam_size)));
+    else   // num_hypotheses rows per chunk, not bounded by max_beam: the run's rows must fit the lane's
+      run_cap = std::min<int64_t>(run_cap, std::max<int64_t>(first->B, (int64_t)cap * dm->max_beam / std::max(1, first->o->num_hypotheses)));
     // (one pool block per call: a run never takes more calls than the pool has blocks)
     const int max_calls = std::max(1, std::max(dm->decode_batch, dm->max_batch) / dm->max_batch);
     for (auto it = grp.queue.begin(); it != grp.queue.end();) {

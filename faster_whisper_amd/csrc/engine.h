@@ -176,6 +176,7 @@ struct DecodeGroup {
   // statistics (fw_model_decode_stats): decode runs, fw_generate calls served, chunks decoded, largest run
   std::atomic<int64_t> n_runs{0}, n_requests{0}, n_chunks{0};
   std::atomic<int> max_run_chunks{0};
+  std::atomic<int64_t> graph_captures{0};   // step graphs captured and instantiated by the group's lanes (fw_test_graph_captures)
 };
 
 struct Model {

@@ -851,9 +851,11 @@ int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows
 // (This hook and the three after it launch on the null stream, without the model's lock, and end with a device-wide wait.)
 // ---------------------------------------------------------------------------------------------------
 // (cand_lp null: the kernel gets a null pointer and skips the log-prob stores, fw_test_logits_rules as it always was)
+// smp: the sampling table of the launch, one entry per row (fw_test_logits_rules_smp_tab); null: every row is a row of ONE
+// call with the temperature and seed of `o` (row0 = 0), what a decode run of that call alone fills in
 static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                                  const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
-                                 int32_t* cand_tok, float* cand_lp) {
+                                 int32_t* cand_tok, float* cand_lp, const fwd::SmpRow* smp = nullptr) {
   FW_CHECK_ARG(fm && logits && cum && o && cand_val && cand_tok && R >= 1 && n >= 0, "bad arguments");
   Model* m = &fm->impl;
   const fw_config& c = m->cfg;
@@ -866,9 +868,7 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   memset(&gp, 0, sizeof(gp));
   gp.B = R / K; gp.K = K; gp.R = R; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx;
   gp.sample = sampling ? 1 : 0;
-  gp.inv_temp = sampling ? 1.0f / o->sampling_temperature : 1.0f;
-  gp.seed_lo = (unsigned)(o->seed & 0xffffffffu);
-  gp.seed_hi = (unsigned)(o->seed >> 32);
+  gp.inv_temp = 1.0f;   // (sampling: temperature and seed per row, from the table below — as in a decode run)
   gp.with_ts = with_timestamps ? 1 : 0;
   gp.suppress_blank = o->suppress_blank ? 1 : 0;
   gp.min_new = o->min_new_tokens;
@@ -906,7 +906,15 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
       (rc = db.zero(d_cv, hv.size() * sizeof(float), nullptr)) || (rc = db.zero(d_ct, ht.size() * sizeof(int), nullptr)))
     return rc;
   if (cand_lp && ((rc = db.alloc(&d_cl, hl.size())) || (rc = db.zero(d_cl, hl.size() * sizeof(float), nullptr)))) return rc;
-  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl);
+  fwd::SmpRow* d_smp = nullptr;
+  if (sampling) {
+    std::vector<fwd::SmpRow> tab((size_t)R);
+    for (int r = 0; r < R; ++r)
+      tab[r] = smp ? smp[r]
+                   : fwd::SmpRow{1.0f / o->sampling_temperature, (unsigned)(o->seed & 0xffffffffu), (unsigned)(o->seed >> 32), 0};
+    if ((rc = db.upload(&d_smp, tab.data(), tab.size()))) return rc;
+  }
+  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
   if ((rc = download(hv.data(), d_cv, hv.size())) || (rc = download(ht.data(), d_ct, ht.size()))) return rc;
@@ -932,6 +940,31 @@ int32_t fw_test_logits_rules_lp(fw_model* fm, const float* logits, int32_t R, co
                                 int32_t* cand_tok, float* cand_lp) {
   FW_CHECK_ARG(cand_lp, "null argument");
   return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp);
+}
+
+// The sampling instantiation over R rows that belong to DIFFERENT calls, as in a merged sampling run: row r draws with
+// 1 / inv_temp[r] as its temperature and seed[r], as row r - row0[r] of its call (0 <= row0[r] <= r: checked).  `o` gives the
+// rules and must select sampling (beam_size 1, sampling_topk 0); its own temperature and seed are not read.
+int32_t fw_test_logits_rules_smp_tab(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                                     const float* cum, const fw_gen_opts* o, int32_t with_timestamps,
+                                     const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
+                                     int32_t* cand_tok, float* cand_lp) {
+  FW_CHECK_ARG(o && inv_temp && seed && row0 && cand_lp && R >= 1, "null argument");
+  FW_CHECK_ARG(o->beam_size == 1 && o->sampling_topk == 0, "the options must select sampling (beam_size 1, sampling_topk 0)");
+  std::vector<fwd::SmpRow> tab((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    FW_CHECK_ARG(row0[r] >= 0 && row0[r] <= r && inv_temp[r] > 0.f, "row %d: row0 must lie in [0, row], inv_temp must be positive", r);
+    tab[r] = {inv_temp[r], (unsigned)(seed[r] & 0xffffffffu), (unsigned)(seed[r] >> 32), row0[r]};
+  }
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp, tab.data());
+}
+
+// step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together
+int32_t fw_test_graph_captures(const fw_model* fm, int64_t* out) {
+  FW_CHECK_ARG(fm && out, "null argument");
+  const Model* m = fm->impl.decoder ? fm->impl.decoder : &fm->impl;
+  *out = m->grp.graph_captures.load();
+  return FW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -32,7 +32,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .backend import StorageView, Whisper, language_token_strings
+from .backend import StorageView, Whisper, attempt_seed, language_token_strings, recording_seed
 from .config import WhisperConfig
 
 _LOG = logging.getLogger("faster_whisper")
@@ -379,13 +379,17 @@ class WhisperModel:
                    clip_timestamps: Union[str, List[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                   vad_speech_probs=None, token_logprobs: bool = False):
+                   vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
         vad.get_speech_timestamps with precomputed window probabilities instead of running the Silero network.
         token_logprobs=True (not in the reference): every segment is a ScoredSegment, whose token_logprobs are those of
-        the decode the fallback ladder kept; every other field is what the call without the keyword yields."""
+        the decode the fallback ladder kept; every other field is what the call without the keyword yields.
+        sampling_seed (not in the reference): makes the sampled attempts of the temperature fallback reproducible.  The
+        attempt at rung t of the ladder for the window at frame `seek` samples with backend.attempt_seed(sampling_seed,
+        seek, t): the same recording with the same seed gives the same transcript whatever else the model decodes before
+        or beside it.  None (the default): every sampling call takes the next seed of the model's call counter."""
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
@@ -446,7 +450,8 @@ class WhisperModel:
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
             hotwords=hotwords)
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
-                                          **(dict(token_logprobs=True) if token_logprobs else {}))
+                                          **(dict(token_logprobs=True) if token_logprobs else {}),
+                                          **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
@@ -456,7 +461,7 @@ class WhisperModel:
 
     # ---- many recordings through the sequential path ----
     def transcribe_many(self, audios: Sequence[Union[str, np.ndarray]], *, language=None, initial_prompt=None,
-                        **transcribe_kwargs) -> List[Tuple[List[Segment], TranscriptionInfo]]:
+                        sampling_seed=None, **transcribe_kwargs) -> List[Tuple[List[Segment], TranscriptionInfo]]:
         """Sequential (seek-loop) transcription of several recordings in ONE call: the sequential counterpart of
         BatchedInferencePipeline.transcribe_many.  result[i] = (list of segments, info) in input order.
 
@@ -468,10 +473,17 @@ class WhisperModel:
         language, initial_prompt: one value for all recordings (None, a string, for initial_prompt also a sequence of
         token ids), or a sequence with one entry per recording.  Every other keyword is transcribe()'s.
 
+        sampling_seed: None, one integer, or a sequence with one integer per recording.  An integer s gives recording i
+        the value backend.recording_seed(s, i).
+
         With a temperature ladder that never leaves 0 (`temperature=0`, or thresholds that no decode fails) result[i] is
         field for field what `transcribe(audios[i], ...)` alone returns: a decode run gives every caller what it gets
-        alone.  Sampled fallback attempts (temperature > 0) draw their seeds from the model's call counter in ARRIVAL
-        order, as concurrent transcribe() calls always did: which recording gets which seed then depends on timing.
+        alone.  With sampling_seed that also holds when the fallback samples (temperature > 0): result[i] is field for
+        field `transcribe(audios[i], sampling_seed=recording_seed(s, i), ...)`, whatever the thread timing — every
+        sampled attempt's seed is a function of (seed of its recording, window, rung) alone, and sampled attempts that
+        meet in a decode run (they do: sampling calls share runs among themselves) each draw what they draw alone.
+        Without sampling_seed the sampled attempts take their seeds from the model's call counter in arrival order, and
+        which recording gets which seed depends on timing.
         An exception in one recording is raised here, after the recordings already started have finished."""
         n = len(audios)
         if n == 0:
@@ -482,8 +494,16 @@ class WhisperModel:
             lambda v: v is None or isinstance(v, str)
             or (len(v) != 0 and all(isinstance(t, (int, np.integer)) for t in v)))
 
+        if sampling_seed is None:
+            seeds = [None] * n
+        elif isinstance(sampling_seed, (int, np.integer)):
+            seeds = [recording_seed(int(sampling_seed), i) for i in range(n)]
+        else:
+            seeds = self._per_recording(sampling_seed, n, "sampling_seed", lambda v: False)
+
         def one(i):
             segments, info = self.transcribe(audios[i], language=languages[i], initial_prompt=prompts[i],
+                                             **(dict(sampling_seed=seeds[i]) if seeds[i] is not None else {}),
                                              **transcribe_kwargs)
             return list(segments), info
 
@@ -507,7 +527,7 @@ class WhisperModel:
 
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
-                          token_logprobs: bool = False):
+                          token_logprobs: bool = False, sampling_seed: Optional[int] = None):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -562,7 +582,8 @@ class WhisperModel:
                 prompt = self.get_prompt(tokenizer, previous_tokens, without_timestamps=options.without_timestamps,
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
-                    encoder_output, prompt, tokenizer, options, **(dict(token_logprobs=True) if token_logprobs else {}))
+                    encoder_output, prompt, tokenizer, options, **(dict(token_logprobs=True) if token_logprobs else {}),
+                    **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
                     skip = result.no_speech_prob > options.no_speech_threshold
@@ -643,11 +664,14 @@ class WhisperModel:
             pbar.close()
 
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
-                               options: TranscriptionOptions, token_logprobs: bool = False):
+                               options: TranscriptionOptions, token_logprobs: bool = False,
+                               sampling_seed: Optional[int] = None, seek: int = 0):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
         attempt (preferring those under the compression threshold) is returned with the last temperature.
+        sampling_seed: the sampled attempt at rung t gets seed=attempt_seed(sampling_seed, seek, t), `seek` the window's
+        first frame; None: no seed is passed, the backend draws one from its call counter.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
         max_initial_timestamp_index = int(round(options.max_initial_timestamp / self.time_precision))
         max_length = len(prompt) + options.max_new_tokens if options.max_new_tokens is not None else self.max_length
@@ -660,10 +684,12 @@ class WhisperModel:
                 f"{self.max_length}.")
         attempts, compact = [], []
         chosen = None
-        for temperature in options.temperatures:
+        for rung, temperature in enumerate(options.temperatures):
             if temperature > 0:
                 mode = dict(beam_size=1, num_hypotheses=options.best_of, sampling_topk=0,
                             sampling_temperature=temperature)
+                if sampling_seed is not None:
+                    mode["seed"] = attempt_seed(sampling_seed, seek, rung)
             else:
                 mode = dict(beam_size=options.beam_size, patience=options.patience)
             result = self.model.generate(

@@ -178,7 +178,9 @@ int32_t fw_model_create_from_blob_dev(const fw_config* cfg, const void* blob_dev
  * next run (up to decode_batch chunks); each caller gets exactly the result it would get alone.  What must agree for two
  * calls to share a run: beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
  * max_length, max_initial_timestamp_index, suppress_blank, min_new_tokens, the suppress list, and the timestamp mode
- * (<|notimestamps|> in the prompt or not); sampling calls run alone.  The PROMPT LENGTH and the position of
+ * (<|notimestamps|> in the prompt or not).  Sampling calls (beam_size 1, sampling_topk 0) merge among themselves, never with
+ * beam or greedy calls; their sampling_temperature and seed need NOT agree (every row of a run draws with its own call's,
+ * as the row of that call that it is alone).  The PROMPT LENGTH and the position of
  * <|startoftranscript|> need NOT agree: every chunk of a run decodes at its own position of the text context with its
  * own budget min(max_length, n_text_ctx) - prompt length (so prompts that carry different amounts of previous text
  * share a run; only a call whose prompt already fills max_length keeps to calls of its own prompt length).  Inside ONE

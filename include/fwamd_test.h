@@ -42,6 +42,18 @@ int32_t fw_test_logits_rules(fw_model* m, const float* logits, int32_t R, const 
 int32_t fw_test_logits_rules_lp(fw_model* m, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                                 const float* cum, const fw_gen_opts* opts, int32_t with_timestamps, float* cand_val,
                                 int32_t* cand_tok, float* cand_lp);
+/* fw_test_logits_rules_lp for the rows of a MERGED sampling run: one launch of the sampling instantiation over R rows
+ * whose temperature, seed and call differ per row — inv_temp [R] (1 / temperature), seed [R], row0 [R] (first row of the
+ * row's call: the row draws its Gumbel noise as row r - row0[r] of that call; 0 <= row0[r] <= r: checked).  opts gives the
+ * rules and must select sampling (beam_size 1, sampling_topk 0); its sampling_temperature and seed are not read.
+ * Outputs [R][1]: the drawn token, cum + its log-prob, its log-prob.  tests/test_gpu_sampling_runs.py. */
+int32_t fw_test_logits_rules_smp_tab(fw_model* m, const float* logits, int32_t R, const int32_t* hist, int32_t n,
+                                     const float* cum, const fw_gen_opts* opts, int32_t with_timestamps,
+                                     const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
+                                     int32_t* cand_tok, float* cand_lp);
+/* out[0] = step graphs (one hipGraph per distinct decode-step geometry, decoder.hip) the model's decode group has
+ * captured and instantiated since the model was created, summed over its lanes */
+int32_t fw_test_graph_captures(const fw_model* m, int64_t* out);
 /* The three hooks of the decode-state kernels (tests/test_gpu_decode_state.py).  Geometry comes from the arguments, not
  * from the model.  Every quantity a kernel uses as an index or extent is checked BEFORE anything is allocated or
  * launched; a violation returns FW_EINVAL (a wrong test gets an error code, never a device fault).
