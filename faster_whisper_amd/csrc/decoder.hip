@@ -45,6 +45,7 @@ using fwd::GenDev;
 // detect_language, align after generate, the temperature ladder re-decoding a window) or the least recently used free
 // one.  A decode run takes all its blocks at once (no hold-and-wait between the lanes).
 struct CrossPool {
+  DevBufs bufs;                          // ck and cvt, freed with the pool
   half_t *ck = nullptr, *cvt = nullptr;
   int n_blocks = 0, EB = 0, kvp = 0;
   struct Block { uint64_t enc_id = 0; int n = 0; bool busy = false; uint64_t stamp = 0; };
@@ -62,8 +63,12 @@ struct GraphSlot {
   int forms = 0;    // fwd::kernel_forms_epoch() at capture: a measurement knob that changes which kernels a step
                     // launches (fw_test_knob) must not be answered with a graph captured before it was set
 };
+// step graphs a workspace keeps (merged runs come in every multiple of a batch up to the lane's capacity: 20 sizes with the
+// bench's workers; a cache of 12 re-captured and re-instantiated 261-node graphs all the time)
+constexpr size_t kStepGraphSlots = 40;
 
 struct GenWorkspace {
+  DevBufs bufs;                          // every device pointer below (gen_workspace_build), freed with the workspace
   int B = 0, K = 0, R = 0, NT = 0;       // capacity of a run: chunks, beams per chunk, rows = B * K
   int EB = 0;                            // chunks of one encoder output (the models' max_batch)
   int* slot_map = nullptr;               // [R] chunk of the run -> chunk slot of the cross-attention pool (device)
@@ -110,10 +115,26 @@ struct GenWorkspace {
   std::vector<GraphSlot> graphs;
   uint64_t graph_clock = 0;
   bool graphs_enabled = true;
+  ~GenWorkspace() {
+    for (GraphSlot& s : graphs)
+      if (s.exec) (void)hipGraphExecDestroy(s.exec);
+  }
 };
 
 static std::atomic<uint64_t> g_tensor_id{1};
 uint64_t next_tensor_id() { return g_tensor_id.fetch_add(1); }
+
+// A process-wide on / off knob, on by default: -1 = not read yet — the environment variable `env` is read once, on first
+// use (set to 0: off) — otherwise what its setter (fw_test_knob) stored.
+static bool env_knob_on(std::atomic<int>& v, const char* env) {
+  int x = v.load(std::memory_order_relaxed);
+  if (x < 0) {
+    const char* e = getenv(env);
+    x = (e && atoi(e) == 0) ? 0 : 1;
+    v.store(x);
+  }
+  return x != 0;
+}
 
 // positions per cache row at full row capacity: the whole text context when one encoder batch is all the workspace
 // holds, otherwise what set_decode_batch chose (>= the share that lets ONE full-context encoder batch run)
@@ -140,41 +161,33 @@ int64_t cross_pool_bytes(const Model* m, int pool_chunks) {
   return 2 * ((int64_t)c.n_dec_layers * pool_chunks * c.d_model * kvp) * 2;   // K and V^T, fp16
 }
 
+// blocks of a pool of `pool_chunks` chunk slots — and, one block per call, the calls a decode run may take
+static int pool_block_count(int pool_chunks, int max_batch) {
+  return std::max(1, std::max(pool_chunks, max_batch) / max_batch);
+}
+
 int cross_pool_ensure(Model* m, int pool_chunks) {
   if (m->xpool) return FW_OK;
   const fw_config& c = m->cfg;
-  CrossPool* p = new CrossPool();
+  std::unique_ptr<CrossPool> p(new CrossPool());   // (goes again, with its buffers, unless it is installed below)
   p->EB = m->max_batch;
-  p->n_blocks = std::max(1, std::max(pool_chunks, m->max_batch) / m->max_batch);
+  p->n_blocks = pool_block_count(pool_chunks, m->max_batch);
   p->kvp = ((c.n_audio_ctx + 31) / 32) * 32;
   p->blocks.assign(p->n_blocks, CrossPool::Block());
   const size_t n = (size_t)c.n_dec_layers * p->n_slots() * c.d_model * p->kvp;
   int rc;
-  if ((rc = dev_alloc_t(&p->ck, n)) || (rc = dev_alloc_t(&p->cvt, n))) {
-    if (p->ck) (void)hipFree(p->ck);
-    delete p;
-    return rc;
-  }
+  if ((rc = p->bufs.alloc(&p->ck, n)) || (rc = p->bufs.alloc(&p->cvt, n))) return rc;
   // the padded keys (>= T) are never written: K garbage is masked, V^T must be 0 (0 * NaN)
-  hipError_t he = hipMemset(p->ck, 0, n * sizeof(half_t));
-  if (he == hipSuccess) he = hipMemset(p->cvt, 0, n * sizeof(half_t));
-  if (he == hipSuccess) he = hipDeviceSynchronize();
-  if (he != hipSuccess) {
-    (void)hipFree(p->ck); (void)hipFree(p->cvt);
-    delete p;
-    set_error("cross-attention pool setup failed: %s", hipGetErrorString(he));
-    return FW_ENODEV;
-  }
-  m->xpool = p;
+  const HipFail fail{FW_ENODEV, "cross-attention pool setup"};
+  FW_HIP_AS(fail, hipMemset(p->ck, 0, n * sizeof(half_t)));
+  FW_HIP_AS(fail, hipMemset(p->cvt, 0, n * sizeof(half_t)));
+  FW_HIP_AS(fail, hipDeviceSynchronize());
+  m->xpool = p.release();
   return FW_OK;
 }
 
 void cross_pool_free(Model* m) {
-  CrossPool* p = m->xpool;
-  if (!p) return;
-  if (p->ck) (void)hipFree(p->ck);
-  if (p->cvt) (void)hipFree(p->cvt);
-  delete p;
+  delete m->xpool;   // (its DevBufs frees K and V^T)
   m->xpool = nullptr;
 }
 
@@ -233,10 +246,12 @@ struct PoolHold {   // releases its blocks when the decode run / detect_language
   }
 };
 
-static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks, int self_ctx) {
+// A workspace is installed whole or not at all: after a failed build (argument check, out of HBM) `ws` goes again with
+// what it has allocated, and the next call starts from scratch instead of launching kernels on a half-allocated one.
+int gen_workspace_build(const Model* m, DecodeLane* lane, int lane_chunks, int self_ctx) {
   const fw_config& c = m->cfg;
-  GenWorkspace* g = new GenWorkspace();
-  lane->gen = g;   // gen_workspace_build frees it again when anything below fails
+  std::unique_ptr<GenWorkspace> ws(new GenWorkspace());
+  GenWorkspace* g = ws.get();
   g->B = lane_chunks;
   g->EB = m->max_batch;
   g->K = m->max_beam;
@@ -249,8 +264,9 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   FW_HIP(hipSetDevice(m->device));
   if (!lane->stream) FW_HIP(create_stream(&lane->stream, "DEC"));
   int rc;
-#define A(p, n) do { if ((rc = dev_alloc_t(&(p), (n)))) return rc; } while (0)
-  A(g->slot_map, R);
+#define A(p, n) do { if ((rc = g->bufs.alloc(&(p), (n)))) return rc; } while (0)
+#define Z(p, n) do { if ((rc = g->bufs.zalloc(&(p), (n)))) return rc; } while (0)   // must start zeroed
+  Z(g->slot_map, R);
   A(g->sk, L * (size_t)g->self_cap * d);
   A(g->sv, L * (size_t)g->self_cap * d);
   A(g->x, R * d); A(g->qkv, R * 3 * d); A(g->att, R * d); A(g->qc, R * d);
@@ -270,49 +286,29 @@ static int gen_workspace_alloc(const Model* m, DecodeLane* lane, int lane_chunks
   A(g->fin_tok, R * FIN_CAP * NT); A(g->fin_len, R * FIN_CAP);
   A(g->fin_score, R * FIN_CAP); A(g->fin_cum, R * FIN_CAP);
   A(g->fin_lp, R * FIN_CAP * (NT + 1));
-  A(g->d_step, 1);
+  Z(g->d_step, 1);
   A(g->no_speech, R);
   A(g->sup_bits, (size_t)LP_SUP_WORDS);
-  A(g->zero_done, R);
+  Z(g->zero_done, R);
   const size_t R16 = (R + 15) / 16 * 16;   // whole 16-row tiles
-  A(g->ptab, R); A(g->sot_tab, R);
-  A(g->nsp_x, R16 * d); A(g->nsp_xf, R16 * d);
-  A(g->smp_tab, R);
-  FW_HIP(hipMemset(g->ptab, 0, R * sizeof(int)));
-  FW_HIP(hipMemset(g->sot_tab, 0, R * sizeof(int)));
-  FW_HIP(hipMemset(g->nsp_x, 0, R16 * d * sizeof(half_t)));
-  FW_HIP(hipMemset(g->nsp_xf, 0, R16 * d * sizeof(half_t)));
-  FW_HIP(hipMemset(g->smp_tab, 0, R * sizeof(fwd::SmpRow)));
+  Z(g->ptab, R); Z(g->sot_tab, R);
+  Z(g->nsp_x, R16 * d); Z(g->nsp_xf, R16 * d);
+  Z(g->smp_tab, R);
   if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
-    A(g->xq, R16 * 4 * d);
-    A(g->xs, R16);
-    FW_HIP(hipMemset(g->xq, 0, R16 * 4 * d));
-    FW_HIP(hipMemset(g->xs, 0, R16 * sizeof(float)));
+    Z(g->xq, R16 * 4 * d);
+    Z(g->xs, R16);
     A(g->ekq, (size_t)g->EB * c.n_audio_ctx * d);
     A(g->eks, (size_t)g->EB * c.n_audio_ctx);
   } else {
-    A(g->x_frag, R16 * d); A(g->att_frag, R16 * d); A(g->ffn_frag, R16 * 4 * d); A(g->xn_frag, R16 * d);
-    FW_HIP(hipMemset(g->xn_frag, 0, R16 * d * sizeof(half_t)));
-    FW_HIP(hipMemset(g->x_frag, 0, R16 * d * sizeof(half_t)));
-    FW_HIP(hipMemset(g->att_frag, 0, R16 * d * sizeof(half_t)));
-    FW_HIP(hipMemset(g->ffn_frag, 0, R16 * 4 * d * sizeof(half_t)));
+    Z(g->x_frag, R16 * d); Z(g->att_frag, R16 * d); Z(g->ffn_frag, R16 * 4 * d); Z(g->xn_frag, R16 * d);
   }
 #undef A
-  FW_HIP(hipMemset(g->slot_map, 0, R * sizeof(int)));
-  FW_HIP(hipMemset(g->zero_done, 0, R * sizeof(int)));
-  FW_HIP(hipMemset(g->d_step, 0, sizeof(int)));
+#undef Z
   FW_HIP(hipDeviceSynchronize());
   const char* ng = getenv("FWAMD_NO_GRAPH");   // rocprofv3 7.2 crashes on replayed graphs: profile eagerly
   g->graphs_enabled = !(ng && ng[0] == '1');
+  lane->gen = ws.release();
   return FW_OK;
-}
-
-// A workspace is installed whole or not at all: after a failed build (argument check, out of HBM) the next call
-// starts from scratch instead of launching kernels on a half-allocated one.
-int gen_workspace_build(const Model* m, DecodeLane* lane, int lane_chunks, int self_ctx) {
-  const int rc = gen_workspace_alloc(m, lane, lane_chunks, self_ctx);
-  if (rc) gen_workspace_free(lane);
-  return rc;
 }
 
 int gen_workspace_ensure(Model* m, DecodeLane* lane) {
@@ -322,18 +318,7 @@ int gen_workspace_ensure(Model* m, DecodeLane* lane) {
 }
 
 void gen_workspace_free(DecodeLane* lane) {
-  GenWorkspace* g = lane->gen;
-  if (!g) return;
-  for (GraphSlot& s : g->graphs)
-    if (s.exec) (void)hipGraphExecDestroy(s.exec);
-  void* ptrs[] = {g->slot_map, g->sk, g->sv, g->x, g->qkv, g->att, g->qc, g->ffn, g->logits, g->prompt_dev,
-                  g->cur_tok, g->hist2, g->cum2, g->kvidx2, g->cand_val, g->cand_tok, g->done, g->n_done, g->n_fin,
-                  g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->d_step, g->no_speech, g->sup_bits,
-                  g->zero_done, g->xq, g->xs, g->ekq, g->eks, g->x_frag, g->att_frag, g->ffn_frag, g->xn_frag, g->prompt_blk,
-                  g->cand_lp, g->lphist2, g->fin_lp, g->ptab, g->sot_tab, g->nsp_x, g->nsp_xf, g->smp_tab};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  delete g;
+  delete lane->gen;   // (destroys its step graphs; its DevBufs frees the device buffers)
   lane->gen = nullptr;
 }
 
@@ -351,15 +336,6 @@ DecodeLane::~DecodeLane() {
 // 1.875 rounds of 256 workgroups (the last round 7/8 full) with a prologue / epilogue ramp per launch; as one launch the K
 // (or V^T) projection of a 16-chunk batch is 15 360 tiles = 60 full rounds.  Same tiles, same arithmetic: the same bits.
 static std::atomic<int> g_cross_kv_layered{-1};
-static bool cross_kv_layered() {
-  int v = g_cross_kv_layered.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("FWAMD_CROSS_KV_LAYERED");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-    g_cross_kv_layered.store(v);
-  }
-  return v != 0;
-}
 void set_cross_kv_layered(int on) { g_cross_kv_layered.store(on ? 1 : 0); }
 // element strides between consecutive decoder layers' cross.kv weights / biases when they are uniform (they are for a blob
 // packed by pack_blob: every layer holds the same items at the same sizes), else 0
@@ -392,7 +368,7 @@ static int ensure_cross_kv(Model* m, DecodeLane* lane, const Tensor* enc, int bl
   const int kvp = pool->kvp;
   const int64_t kvs = (int64_t)d * kvp;   // one chunk's K (or V^T): H heads x kvp keys x 64
   int64_t ws = 0, bs = 0;
-  if (!i8 && cross_kv_layered() && cross_kv_strides(m, &ws, &bs)) {
+  if (!i8 && env_knob_on(g_cross_kv_layered, "FWAMD_CROSS_KV_LAYERED") && cross_kv_strides(m, &ws, &bs)) {
     const int64_t cls = (int64_t)pool->n_slots() * kvs;          // a layer's region of the pool
     half_t* kd = pool->ck + (size_t)b0 * kvs;
     half_t* vd = pool->cvt + (size_t)b0 * kvs;
@@ -400,12 +376,7 @@ static int ensure_cross_kv(Model* m, DecodeLane* lane, const Tensor* enc, int bl
       return rc;
     if ((rc = run_linear_layers(m, m->dec[0].cv, c.n_dec_layers, ws, bs, enc->data, d, xs, vd, kvp, kvs, cls, T, B, true, kvp, st)))
       return rc;
-    std::lock_guard<std::mutex> lk(pool->mu);
-    pool->blocks[blk].enc_id = enc->id;
-    pool->blocks[blk].n = B;
-    return FW_OK;
-  }
-  for (int l = 0; l < c.n_dec_layers; ++l) {
+  } else for (int l = 0; l < c.n_dec_layers; ++l) {
     const DecLayerW& L = m->dec[l];
     half_t* kd = pool->ck + ((size_t)l * pool->n_slots() + b0) * kvs;
     half_t* vd = pool->cvt + ((size_t)l * pool->n_slots() + b0) * kvs;
@@ -424,11 +395,9 @@ static int ensure_cross_kv(Model* m, DecodeLane* lane, const Tensor* enc, int bl
     if ((rc = run_linear(m, L.ck, enc->data, d, xs, kd, d, kvs, nullptr, 0, 0, T, B, 0, false, kvp, st))) return rc;
     if ((rc = run_linear(m, L.cv, enc->data, d, xs, vd, kvp, kvs, nullptr, 0, 0, T, B, 0, true, kvp, st))) return rc;
   }
-  {
-    std::lock_guard<std::mutex> lk(pool->mu);
-    pool->blocks[blk].enc_id = enc->id;
-    pool->blocks[blk].n = B;
-  }
+  std::lock_guard<std::mutex> lk(pool->mu);
+  pool->blocks[blk].enc_id = enc->id;
+  pool->blocks[blk].n = B;
   return FW_OK;
 }
 
@@ -466,20 +435,11 @@ struct StepCfg {
 // position blocks for the prompt forward and align (knob 4 / FWAMD_POS_BLOCKS, default ON; 0: one position per pass,
 // rounds 1-4): the same bits either way (tests/test_gpu_model.py::test_position_blocks_same_bits)
 static std::atomic<int> g_pos_blocks{-1};
-static bool pos_blocks_on() {
-  int v = g_pos_blocks.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("FWAMD_POS_BLOCKS");
-    v = (e && atoi(e) == 0) ? 0 : 1;
-    g_pos_blocks.store(v);
-  }
-  return v != 0;
-}
 void set_pos_blocks(int on) { g_pos_blocks.store(on ? 1 : 0); }
 // positions per block for a pass over `chunks` chunks: the workspace holds g->R rows, the cross-attention kernel takes
 // <= 16 queries per chunk
 static int pos_block_size(const Model* m, const GenWorkspace* g, const GenDev& gp, int chunks) {
-  if (!pos_blocks_on() || chunks < 1) return 1;
+  if (!env_knob_on(g_pos_blocks, "FWAMD_POS_BLOCKS") || chunks < 1) return 1;
   if (!fwd::self_attn_block_ok(g->NT, gp.ctx, m->cfg.d_model, gp.R)) return 1;
   return std::max(1, std::min(16, g->R / chunks));
 }
@@ -641,6 +601,88 @@ static int check_launch(const char* what) {
   return FW_OK;
 }
 
+// The step graph of a run: one hipGraph per distinct GenDev (everything the captured kernels take by value, kv_div
+// included) and kernel-forms epoch, kept by the lane's workspace.
+static hipGraphExec_t step_graph_find(GenWorkspace* g, const GenDev& gp) {
+  hipGraphExec_t exec = nullptr;
+  for (GraphSlot& gs : g->graphs)
+    if (gs.exec && gs.forms == fwd::kernel_forms_epoch() && memcmp(&gs.key, &gp, sizeof(gp)) == 0) {
+      exec = gs.exec; gs.stamp = ++g->graph_clock;
+    }
+  return exec;
+}
+// Captures step `s` on the lane's stream, instantiates it and keeps it, in a new slot or in place of the least recently
+// used one.  Null when capture or instantiation fails: the caller then launches its steps eagerly.
+static hipGraphExec_t step_graph_capture(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg& s) {
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  hipGraphExec_t exec = nullptr;
+  hipGraph_t graph = nullptr;
+  if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    const int rc2 = run_step(m, lane, gp, s);
+    const hipError_t e2 = hipStreamEndCapture(st, &graph);
+    hipGraphExec_t ne = nullptr;
+    if (rc2 == FW_OK && e2 == hipSuccess && graph && hipGraphInstantiate(&ne, graph, nullptr, nullptr, 0) == hipSuccess) {
+      GraphSlot* slot = nullptr;
+      if (g->graphs.size() < kStepGraphSlots) { g->graphs.emplace_back(); slot = &g->graphs.back(); }
+      else {   // evict the least recently used
+        slot = &g->graphs[0];
+        for (GraphSlot& gs : g->graphs) if (gs.stamp < slot->stamp) slot = &gs;
+        if (slot->exec) (void)hipGraphExecDestroy(slot->exec);
+      }
+      m->grp.graph_captures.fetch_add(1);
+      slot->exec = ne; slot->key = gp; slot->stamp = ++g->graph_clock; slot->forms = fwd::kernel_forms_epoch();
+      exec = ne;
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+  }
+  (void)hipGetLastError();
+  return exec;
+}
+
+// POSITION-BLOCK FORWARD: positions 0 .. n_pos - 1 of `chunks` chunks (beam slot 0 of each), all known up front — the
+// prompt forward of a decode run, the teacher-forced text of align — go through the decoder in blocks of up to 16
+// positions per pass (StepCfg::blk_n; pos_block_size) instead of one position per pass.  ptok holds the tokens as
+// [pos][chunk] and the caller has uploaded it to g->prompt_dev; the blocked order [block][chunk][position of the block] is
+// made and uploaded here (g->prompt_blk).  fill(s, pos, nb) completes the pass's StepCfg (need_logits, the no-speech row,
+// done, align's extras); after(pos, nb) launches what follows the pass.
+// A block of ONE position has the layout of an unblocked pass (rows = chunks, kmul = 1, blk_n = 0) and its tokens sit at
+// pos * chunks in either order, so a last block of one position needs no case of its own, and a forward of a single
+// position (a two-token prompt) reads g->prompt_dev as it lies: nothing to reorder, no upload to wait for.
+template <typename Fill, typename After>
+static int pos_block_forward(Model* m, DecodeLane* lane, const GenDev& gp, const std::vector<int>& ptok, int n_pos, int chunks,
+                             int P, const HipFail& upload_fail, Fill&& fill, After&& after) {
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  const int nbmax = pos_block_size(m, g, gp, chunks);
+  const bool blocked = nbmax > 1 && n_pos > 1;
+  if (blocked) {
+    std::vector<int> blk_tok;
+    blk_tok.reserve((size_t)n_pos * chunks);
+    for (int pos = 0; pos < n_pos;) {
+      const int nb = std::min(nbmax, n_pos - pos);
+      for (int b = 0; b < chunks; ++b)
+        for (int j = 0; j < nb; ++j) blk_tok.push_back(ptok[(size_t)(pos + j) * chunks + b]);
+      pos += nb;
+    }
+    FW_HIP_AS(upload_fail, hipMemcpyAsync(g->prompt_blk, blk_tok.data(), blk_tok.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    FW_HIP_AS(upload_fail, hipStreamSynchronize(st));   // blk_tok is a local
+  }
+  for (int pos = 0; pos < n_pos;) {
+    const int nb = blocked ? std::min(nbmax, n_pos - pos) : 1;
+    StepCfg s;
+    s.B = chunks; s.pos_fixed = pos; s.P = P;
+    s.rows = chunks * nb; s.kmul = nb; s.blk_n = nb > 1 ? nb : 0;
+    s.tok = (blocked ? g->prompt_blk : g->prompt_dev) + (size_t)pos * chunks;
+    s.beam_tail = false;
+    fill(s, pos, nb);
+    if (int rc = run_step(m, lane, gp, s)) return rc;
+    after(pos, nb);
+    pos += nb;
+  }
+  return FW_OK;
+}
+
 // ---- one fw_generate call ------------------------------------------------------------------------------------
 struct GenRequest {
   const Tensor* enc;
@@ -684,7 +726,6 @@ static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) 
   return a.with_ts == b.with_ts;
 }
 
-// chunks of a run led by `r` that fit the self-attention cache (before the workspace exists: its planned size)
 // share (percent) of a run's capacity an IDLE decode group (no run in progress) waits for; FWAMD_IDLE_FILL_PCT overrides
 static int idle_fill_pct() {
   static const int v = [] {
@@ -694,7 +735,7 @@ static int idle_fill_pct() {
   }();
   return v;
 }
-// an idle two-lane group splits the known work evenly over its runs (see the gather loop); FWAMD_IDLE_BALANCE=0 turns it
+// an idle two-lane group splits the known work evenly over its runs (leader_stops_gathering); FWAMD_IDLE_BALANCE=0 turns it
 // off (the A/B of profiles/r05_ab_idle_balance.jsonl: burst 2 904 -> 2 976x, steady state 3 105 -> 3 105x)
 static bool idle_balance() {
   static const bool v = [] { const char* e = getenv("FWAMD_IDLE_BALANCE"); return !e || atoi(e) != 0; }();
@@ -711,74 +752,89 @@ int64_t idle_lead_chunks(int64_t queued, int n_queued, int encoding, int64_t wan
   const int64_t n_runs = std::max<int64_t>(std::max(2, lanes), (outstanding + std::max<int64_t>(1, want) - 1) / std::max<int64_t>(1, want));
   return std::max<int64_t>(max_batch, (outstanding + n_runs - 1) / n_runs);
 }
-static int64_t planned_self_cap(const Model* dm) {   // rows x positions of a lane's self-attention cache
+
+// What a lane holds of runs led by a call of `B` chunks — THE statement of run capacity: the entry check of fw_generate,
+// the leader's wait (leader_wait), the gather loop (take_mergeable) and generate_run's workspace checks all read it.  The lane: `lane_chunks` chunks x
+// `max_beam` rows and a self-attention cache of `self_cap` row-positions (its planned size before the workspace exists,
+// the workspace's own in generate_run); the call: beam_size / num_hypotheses and ctx = run_ctx() of its max_length
+// (mergeable calls share max_length, hence the context).
+RunCapacity::RunCapacity(int lane_chunks, int max_batch, int max_beam, int64_t self_cap_, int B, bool sampling, int beam_size,
+                         int num_hypotheses, int ctx_) {
+  // rows of one encoder chunk in the run: beam_size, or num_hypotheses beam-1 rows when sampling (kv_div)
+  rows_per_chunk = sampling ? std::max(1, num_hypotheses) : beam_size;
+  rows = (int64_t)B * rows_per_chunk;
+  row_cap = (int64_t)lane_chunks * max_beam;
+  self_cap = self_cap_;
+  ctx = ctx_;
+  rows_fit = rows <= row_cap;
+  cache_fits = rows * ctx <= self_cap;
+  // the rows above which the 4 x 4-tile decoder linears no longer fit the chip in one round of workgroups
+  // (d x d: 20 column groups x 25 row groups of 64 rows = 500 of 512 workgroup slots)
+  const int64_t one_round = std::max<int64_t>(max_batch, DEC_RUN_MAX_ROWS / std::max(1, beam_size));
+  // (the leader of a run of SAMPLING calls does not wait for further ones: fallback attempts are stragglers)
+  want =sampling ? 0 : std::min<int64_t>(lane_chunks, one_round);
+  // chunks the self-attention cache holds at this context, never less than the leading call itself ...
+  run_cap = std::min<int64_t>(lane_chunks, std::max<int64_t>(B, self_cap / std::max<int64_t>(1, rows_per_chunk * ctx)));
+  if (!sampling)
+    run_cap = std::min(run_cap, one_round);
+  else   // ... num_hypotheses rows per chunk, not bounded by max_beam: the run's rows must fit the lane's
+    run_cap = std::min(run_cap, std::max<int64_t>(B, (int64_t)lane_chunks * max_beam / std::max(1, num_hypotheses)));
+}
+// ... of a lane of `dm` as planned (the workspace may not exist yet), for runs led by `r`
+static RunCapacity planned_capacity(const Model* dm, const GenRequest& r) {
   const int B = lane_chunks_of(dm);
   const int nts = self_positions(dm, B, dm->decode_self_ctx > 0 ? dm->decode_self_ctx : dm->cfg.n_text_ctx);
-  return (int64_t)B * dm->max_beam * nts;
-}
-static int64_t self_chunk_capacity(Model* dm, const GenRequest& r) {
-  // rows of one encoder chunk in the run: beam_size, or num_hypotheses beam-1 rows when sampling (kv_div)
-  const int64_t rows_per_chunk = r.sampling ? std::max(1, r.o->num_hypotheses) : r.o->beam_size;
-  return planned_self_cap(dm) / (rows_per_chunk * run_ctx(dm->cfg, r.o->max_length, r.P));
+  // (rows x positions of a lane's self-attention cache)
+  return RunCapacity(B, dm->max_batch, dm->max_beam, (int64_t)B * dm->max_beam * nts, r.B, r.sampling, r.o->beam_size,
+                     r.o->num_hypotheses, run_ctx(dm->cfg, r.o->max_length, r.P));
 }
 
-// Decode run over the concatenated chunks of `reqs` (all mergeable with reqs[0]).  Caller holds lane->mu.
-static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest*>& reqs) {
-  int rc = gen_workspace_ensure(m, lane);
-  if (rc) return rc;
-  GenWorkspace* g = lane->gen;
+// ---- a decode run over the concatenated chunks of `reqs` (all mergeable with reqs[0]), phase by phase; generate_run
+//      below strings the phases together.  Every phase runs under lane->mu on the lane's stream. ----
+struct RunPlan {
+  const fw_gen_opts* o;       // the leading call's options (mergeable calls agree on all that the run reads from them)
+  bool sampling, ragged, want_nsp;
+  int K, nh, ml;              // beam_size, num_hypotheses, max_length
+  int P, Pmax;                // shortest and longest prompt of the run
+  int B, Bx, kv_div;          // encoder chunks, decode chunks = B * kv_div, decode chunks per encoder chunk
+  int budget, ctx, reach, sot_pos;
+  GenDev gp;                  // what the step kernels take by value: the step graph's key
+};
+
+// Phase 1: the run's geometry, checked against the workspace, and its GenDev.
+static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<GenRequest*>& reqs, RunPlan& pl) {
   const fw_config& c = m->cfg;
   const GenRequest& r0 = *reqs[0];
-  const fw_gen_opts* o = r0.o;
-  const int K = o->beam_size;
-  const bool sampling = r0.sampling;
+  const fw_gen_opts* o = pl.o = r0.o;
+  const int K = pl.K = o->beam_size;
+  const bool sampling = pl.sampling = r0.sampling;
   // RAGGED run: its calls differ in prompt length or <sot> position (mergeable() lets them meet).  They share
   // reach = min(max_length, n_text_ctx), hence the cache geometry; chunk c has its own prompt length P_c and its own budget
   // reach - P_c.  P is the SHORTEST prompt (the run lasts reach - P steps), Pmax the longest (the prompt forward runs to
   // Pmax - 1).  A uniform run (P == Pmax, one <sot> position) takes exactly the path it always took.
-  int P = r0.P, Pmax = r0.P;
-  bool ragged = false;
+  pl.P = pl.Pmax = r0.P; pl.B = 0; pl.ragged = pl.want_nsp = false;
   for (const GenRequest* r : reqs) {
-    P = std::min(P, r->P); Pmax = std::max(Pmax, r->P);
-    ragged = ragged || r->P != r0.P || r->sot_pos != r0.sot_pos;
+    pl.P = std::min(pl.P, r->P); pl.Pmax = std::max(pl.Pmax, r->P);
+    pl.ragged = pl.ragged || r->P != r0.P || r->sot_pos != r0.sot_pos;
+    pl.want_nsp = pl.want_nsp || r->o->return_no_speech_prob;
+    pl.B += r->B;
   }
-  const int nh = o->num_hypotheses, ml = o->max_length;
-  const int kv_div = sampling ? nh : 1;   // decode chunks per encoder chunk
-  int B = 0;
-  for (const GenRequest* r : reqs) B += r->B;
-  const int Bx = B * kv_div;
-  FW_CHECK_ARG(Bx * K <= g->R && Bx <= g->R && B <= g->B, "decode run of %d chunks x %d rows exceeds the workspace", B,
-               kv_div * K);
-  const int budget = max_new_tokens(std::min(o->max_length, c.n_text_ctx), P);
-  const int ctx = run_ctx(c, o->max_length, P);
-  const int reach = std::min(o->max_length, c.n_text_ctx);
+  pl.nh = o->num_hypotheses; pl.ml = o->max_length;
+  const int P = pl.P, Pmax = pl.Pmax, B = pl.B;
+  const bool ragged = pl.ragged;
+  const int kv_div = pl.kv_div = sampling ? pl.nh : 1;
+  const int Bx = pl.Bx = B * kv_div;
+  const int budget = pl.budget = max_new_tokens(std::min(o->max_length, c.n_text_ctx), P);
+  const int ctx = pl.ctx = run_ctx(c, o->max_length, P);
+  const int reach = pl.reach = std::min(o->max_length, c.n_text_ctx);
+  // the whole run against the REAL workspace: its rows (= Bx * K; the per-chunk tables ptab / sot_tab / nsp_x hold one
+  // entry per decode chunk, g->R of them, and Bx <= Bx * K), its chunks and its cache
+  const RunCapacity cap(g->B, g->EB, g->K, g->self_cap, B, sampling, K, pl.nh, ctx);
+  FW_CHECK_ARG(cap.rows_fit && B <= g->B, "decode run of %d chunks x %d rows exceeds the workspace", B, kv_div * K);
   // (every position a ragged run touches lies below reach <= ctx: mergeable() keeps prompts that fill max_length out)
-  // (ptab / sot_tab / nsp_x hold one entry per decode chunk, g->R of them: Bx <= g->R was checked above)
-  FW_CHECK_ARG(!ragged || Pmax < reach, "ragged decode run: prompt of %d tokens with max_length %d", Pmax, ml);
-  FW_CHECK_ARG((int64_t)Bx * K * ctx <= g->self_cap, "decode run of %d rows x %d positions exceeds the self-attention cache", Bx * K, ctx);
-  FW_HIP(hipSetDevice(m->device));
-  hipStream_t st = lane->stream;
-  // ---- the run's blocks of the cross-attention pool (all at once), the projection of those that are not there yet,
-  //      and the run's chunk -> pool slot table ----
-  CrossPool* pool = m->xpool;
-  PoolHold hold{pool, {}, st};
-  std::vector<int> slot_host((size_t)Bx);
-  {
-    std::vector<uint64_t> ids;
-    std::vector<int> ns;
-    std::vector<char> hit;
-    for (const GenRequest* r : reqs) { ids.push_back(r->enc->id); ns.push_back(r->enc->B); }
-    FW_CHECK_ARG((int)reqs.size() <= pool->n_blocks, "decode run of %zu calls exceeds the %d blocks of the cross-attention pool",
-                 reqs.size(), pool->n_blocks);
-    pool_acquire(pool, ids, ns, hold.blk, hit);
-    int bx = 0;
-    for (size_t i = 0; i < reqs.size(); ++i) {
-      if ((rc = ensure_cross_kv(m, lane, reqs[i]->enc, hold.blk[i], hit[i] != 0))) return rc;
-      for (int b = 0; b < reqs[i]->B; ++b)
-        for (int j = 0; j < kv_div; ++j) slot_host[bx++] = hold.blk[i] * pool->EB + b;
-    }
-  }
-  GenDev gp;
+  FW_CHECK_ARG(!ragged || Pmax < reach, "ragged decode run: prompt of %d tokens with max_length %d", Pmax, pl.ml);
+  FW_CHECK_ARG(cap.cache_fits, "decode run of %d rows x %d positions exceeds the self-attention cache", Bx * K, ctx);
+  GenDev& gp = pl.gp;
   memset(&gp, 0, sizeof(gp));
   // (ragged: the step kernels read neither P nor budget — zero in the key, so that ragged runs of one size share a graph
   //  whatever their prompt lengths)
@@ -792,7 +848,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   gp.max_fin = std::max(1, (int)lroundf((float)K * o->patience));
   if (gp.max_fin > FIN_CAP - K) gp.max_fin = FIN_CAP - K;
   gp.V = c.n_vocab; gp.n_text_ctx = g->NT;
-  const int sot_pos = r0.sot_pos;   // (uniform runs; a ragged run reads each chunk's own, see the prompt forward)
+  pl.sot_pos = r0.sot_pos;   // (uniform runs; a ragged run reads each chunk's own, see the prompt forward)
   gp.with_ts = r0.with_ts;
   gp.suppress_blank = o->suppress_blank ? 1 : 0;
   gp.min_new = o->min_new_tokens;
@@ -803,12 +859,40 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
   gp.n_sup_begin = c.n_suppress_begin;
   for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
-  bool want_nsp = false;
-  for (const GenRequest* r : reqs) want_nsp = want_nsp || r->o->return_no_speech_prob;
+  return FW_OK;
+}
 
-  // ---- state init (only the rows of this run) ----
+// Phase 2: the run's blocks of the cross-attention pool (all at once; `hold` keeps them to the end of the run), the
+// projection of those that are not there yet, and the run's table encoder chunk -> pool slot (slots: [B], host).
+static int run_acquire_blocks(Model* m, DecodeLane* lane, const std::vector<GenRequest*>& reqs, PoolHold& hold,
+                              std::vector<int>& slots) {
+  CrossPool* pool = m->xpool;
+  std::vector<uint64_t> ids;
+  std::vector<int> ns;
+  std::vector<char> hit;
+  for (const GenRequest* r : reqs) { ids.push_back(r->enc->id); ns.push_back(r->enc->B); }
+  FW_CHECK_ARG((int)reqs.size() <= pool->n_blocks, "decode run of %zu calls exceeds the %d blocks of the cross-attention pool",
+               reqs.size(), pool->n_blocks);
+  pool_acquire(pool, ids, ns, hold.blk, hit);
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    if (int rc = ensure_cross_kv(m, lane, reqs[i]->enc, hold.blk[i], hit[i] != 0)) return rc;
+    for (int b = 0; b < reqs[i]->B; ++b) slots.push_back(hold.blk[i] * pool->EB + b);
+  }
+  return FW_OK;
+}
+
+// Phase 3: state init (only the rows of this run) and the host tables: suppress mask, prompts, first-step tokens, the
+// ragged / sampling tables, the slot table.  ptok: the prompt tokens as [pos][decode chunk], for the prompt forward.
+static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenRequest*>& reqs, const RunPlan& pl,
+                          const std::vector<int>& slots, std::vector<int>& ptok) {
+  GenWorkspace* g = lane->gen;
+  const fw_config& c = m->cfg;
+  hipStream_t st = lane->stream;
+  const fw_gen_opts* o = pl.o;
+  const bool sampling = pl.sampling, ragged = pl.ragged;
+  const int K = pl.K, Pmax = pl.Pmax, B = pl.B, Bx = pl.Bx, kv_div = pl.kv_div;
   // (the ping-pong halves of hist2 / kvidx2 / cum2 are gp.R rows apart: the kernels index them with the run's R)
-  const size_t NT = g->NT, Rr = (size_t)gp.R;
+  const size_t NT = g->NT, Rr = (size_t)pl.gp.R;
   FW_HIP(hipMemsetAsync(g->hist2, 0, 2 * Rr * NT * sizeof(int), st));
   FW_HIP(hipMemsetAsync(g->lphist2, 0, 2 * Rr * NT * sizeof(float), st));
   FW_HIP(hipMemsetAsync(g->kvidx2, 0, 2 * Rr * NT, st));
@@ -826,7 +910,8 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
-  std::vector<int> ptok((size_t)Pmax * Bx), first((size_t)Bx * K), ptab_host((size_t)Bx), sot_host((size_t)Bx);
+  ptok.assign((size_t)Pmax * Bx, 0);
+  std::vector<int> first((size_t)Bx * K), ptab_host((size_t)Bx), sot_host((size_t)Bx);
   std::vector<fwd::SmpRow> smp_host(sampling ? (size_t)Bx : 0);   // (sampling: K == 1, decode chunk bx is row bx)
   {
     int bx = 0;
@@ -853,62 +938,50 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   FW_HIP(hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP(hipMemcpyAsync(g->cur_tok, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
   // (the cross-attention kernel divides the decode chunk by kv_div before it looks the slot up: one entry per ENCODER chunk)
-  {
-    std::vector<int> enc_slots((size_t)B);
-    for (int b = 0; b < B; ++b) enc_slots[b] = slot_host[(size_t)b * kv_div];
-    slot_host.swap(enc_slots);
-  }
-  FW_HIP(hipMemcpyAsync(g->slot_map, slot_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP(hipMemcpyAsync(g->slot_map, slots.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP(hipStreamSynchronize(st));   // the host buffers above are locals
+  return FW_OK;
+}
 
-  // ---- prompt forward (all but the last token): Bx rows, beam slot 0 of every chunk ----
-  //      in blocks of up to 16 positions per pass (one pass for the 3 positions of the usual 4-token prompt; a prompt that
-  //      carries 223 tokens of previous text takes 14 passes instead of 223)
-  //      RAGGED run: the passes run to Pmax - 1 with ALL chunks in every pass.  Chunk c is really there only while
-  //      pos < P_c - 1; in later passes it rides along on padding (its own last prompt token).  That is harmless: a padded
-  //      row reads only its own chunk's cache slot and sibling rows, and what it writes — K / V of beam slot 0 at positions
-  //      >= P_c - 1, all below reach, inside the slot — is written again by the chunk's real decode steps before anything
-  //      reads it: step s writes position P_c - 1 + s on every beam slot and reads only positions below it.  Its valid rows
-  //      (positions < P_c - 1) see exactly what they see in a run of their own, so the chunk's bits do not change.
-  //      The no-speech probability is read at each chunk's own <sot> position: the final hidden row there is gathered into
-  //      a Bx-row buffer as its pass (or step 0) goes by, and ONE vocabulary projection follows step 0.
-  {
-    const int nbmax = pos_block_size(m, g, gp, Bx);
-    std::vector<int> blk_tok;
-    if (nbmax > 1 && Pmax - 1 > 1) {
-      blk_tok.reserve((size_t)(Pmax - 1) * Bx);
-      for (int pos = 0; pos < Pmax - 1;) {
-        const int nb = std::min(nbmax, Pmax - 1 - pos);
-        for (int b = 0; b < Bx; ++b)
-          for (int j = 0; j < nb; ++j) blk_tok.push_back(ptok[(size_t)(pos + j) * Bx + b]);
-        pos += nb;
-      }
-      FW_HIP(hipMemcpyAsync(g->prompt_blk, blk_tok.data(), blk_tok.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      FW_HIP(hipStreamSynchronize(st));
-    }
-    for (int pos = 0; pos < Pmax - 1;) {
-      const int nb = blk_tok.empty() ? 1 : std::min(nbmax, Pmax - 1 - pos);
-      StepCfg s;
-      s.B = Bx; s.pos_fixed = pos; s.P = Pmax;
-      s.need_logits = !ragged && sot_pos >= pos && sot_pos < pos + nb && want_nsp;
-      s.beam_tail = false;
-      s.done = g->done;
-      if (nb > 1) {
-        s.rows = Bx * nb; s.kmul = nb; s.blk_n = nb; s.tok = g->prompt_blk + (size_t)pos * Bx;
+// Phase 4: prompt forward (all but the last token): Bx rows, beam slot 0 of every chunk, in position blocks
+//      (pos_block_forward: one pass for the 3 positions of the usual 4-token prompt; a prompt that carries 223 tokens of
+//      previous text takes 14 passes instead of 223)
+//      RAGGED run: the passes run to Pmax - 1 with ALL chunks in every pass.  Chunk c is really there only while
+//      pos < P_c - 1; in later passes it rides along on padding (its own last prompt token).  That is harmless: a padded
+//      row reads only its own chunk's cache slot and sibling rows, and what it writes — K / V of beam slot 0 at positions
+//      >= P_c - 1, all below reach, inside the slot — is written again by the chunk's real decode steps before anything
+//      reads it: step s writes position P_c - 1 + s on every beam slot and reads only positions below it.  Its valid rows
+//      (positions < P_c - 1) see exactly what they see in a run of their own, so the chunk's bits do not change.
+//      The no-speech probability is read at each chunk's own <sot> position: the final hidden row there is gathered into
+//      a Bx-row buffer as its pass (or step 0) goes by, and ONE vocabulary projection follows step 0.
+static int run_prompt_forward(Model* m, DecodeLane* lane, const RunPlan& pl, const std::vector<int>& ptok) {
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  int rc = pos_block_forward(
+      m, lane, pl.gp, ptok, pl.Pmax - 1, pl.Bx, pl.Pmax, HipFail{FW_ENODEV, "prompt forward: token upload"},
+      [&](StepCfg& s, int pos, int nb) {
+        s.need_logits = !pl.ragged && pl.sot_pos >= pos && pl.sot_pos < pos + nb && pl.want_nsp;
         s.nospeech_rowmul = s.need_logits ? nb : 0;
-        s.nospeech_off = s.need_logits ? sot_pos - pos : 0;
-      } else {
-        s.rows = Bx; s.kmul = 1; s.tok = blk_tok.empty() ? g->prompt_dev + (size_t)pos * Bx : g->prompt_blk + (size_t)pos * Bx;
-        s.nospeech_rowmul = s.need_logits ? 1 : 0;
-      }
-      if ((rc = run_step(m, lane, gp, s))) return rc;
-      if (ragged && want_nsp)
-        fwd::launch_gather_sot_rows(st, g->x, g->sot_tab, g->ptab, pos, nb, nb, g->nsp_x, g->nsp_xf, c.d_model, Bx);
-      pos += nb;
-    }
-  }
-  if ((rc = check_launch("prompt forward"))) return rc;
+        s.nospeech_off = s.need_logits ? pl.sot_pos - pos : 0;
+        s.done = g->done;
+      },
+      [&](int pos, int nb) {
+        if (pl.ragged && pl.want_nsp)
+          fwd::launch_gather_sot_rows(st, g->x, g->sot_tab, g->ptab, pos, nb, nb, g->nsp_x, g->nsp_xf, m->cfg.d_model, pl.Bx);
+      });
+  if (rc) return rc;
+  return check_launch("prompt forward");
+}
 
+// Phase 5: step 0, eagerly, then one step-graph replay per step until every chunk is done or the budget is spent.
+static int run_decode_steps(Model* m, DecodeLane* lane, const RunPlan& pl) {
+  GenWorkspace* g = lane->gen;
+  const fw_config& c = m->cfg;
+  hipStream_t st = lane->stream;
+  const GenDev& gp = pl.gp;
+  const bool ragged = pl.ragged, want_nsp = pl.want_nsp;
+  const int K = pl.K, P = pl.P, Bx = pl.Bx, budget = pl.budget, sot_pos = pl.sot_pos;
+  int rc;
   int steps_done = 0;
   if (budget > 0) {
     // ---- step 0 (eager): last prompt token on all rows; beams are identical copies ----
@@ -935,34 +1008,8 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
     //      kernels take by value, kv_div included) ----
     hipGraphExec_t exec = nullptr;
     if (g->graphs_enabled && !lane->prof.on) {
-      for (GraphSlot& gs : g->graphs)
-        if (gs.exec && gs.forms == fwd::kernel_forms_epoch() && memcmp(&gs.key, &gp, sizeof(gp)) == 0) {
-          exec = gs.exec; gs.stamp = ++g->graph_clock;
-        }
-      if (!exec) {
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int rc2 = run_step(m, lane, gp, s);
-          const hipError_t e2 = hipStreamEndCapture(st, &graph);
-          hipGraphExec_t ne = nullptr;
-          if (rc2 == FW_OK && e2 == hipSuccess && graph && hipGraphInstantiate(&ne, graph, nullptr, nullptr, 0) == hipSuccess) {
-            GraphSlot* slot = nullptr;
-            // (merged runs come in every multiple of a batch up to the lane's capacity: 20 sizes with the bench's workers;
-            //  a cache of 12 re-captured and re-instantiated 261-node graphs all the time)
-            if (g->graphs.size() < 40) { g->graphs.emplace_back(); slot = &g->graphs.back(); }
-            else {   // evict the least recently used
-              slot = &g->graphs[0];
-              for (GraphSlot& gs : g->graphs) if (gs.stamp < slot->stamp) slot = &gs;
-              if (slot->exec) (void)hipGraphExecDestroy(slot->exec);
-            }
-            m->grp.graph_captures.fetch_add(1);
-            slot->exec = ne; slot->key = gp; slot->stamp = ++g->graph_clock; slot->forms = fwd::kernel_forms_epoch();
-            exec = ne;
-          }
-          if (graph) (void)hipGraphDestroy(graph);
-        }
-        (void)hipGetLastError();
-      }
+      exec = step_graph_find(g, gp);
+      if (!exec) exec = step_graph_capture(m, lane, gp, s);
     }
     int n_done_host = 0;
     while (steps_done < budget) {
@@ -987,8 +1034,17 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   FW_HIP(hipStreamSynchronize(st));
   if ((rc = check_launch("decode loop"))) return rc;
   prof_collect(lane->prof);
+  return FW_OK;
+}
 
-  // ---- finalize on the host: best num_hypotheses by normalised score (stable) ----
+// Phase 6: finalize on the host: the best num_hypotheses of every encoder chunk by normalised score (stable), into the
+// output buffers of the chunk's call.
+static int run_finalize(DecodeLane* lane, const std::vector<GenRequest*>& reqs, const RunPlan& pl) {
+  GenWorkspace* g = lane->gen;
+  hipStream_t st = lane->stream;
+  const bool ragged = pl.ragged;
+  const int Bx = pl.Bx, kv_div = pl.kv_div, nh = pl.nh, ml = pl.ml;
+  const size_t NT = g->NT;
   std::vector<int> n_fin(Bx), fin_len((size_t)Bx * FIN_CAP);
   std::vector<float> fin_score((size_t)Bx * FIN_CAP), nsp(Bx);
   std::vector<int> fin_tok((size_t)Bx * FIN_CAP * NT);
@@ -1037,6 +1093,176 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
     }
     cb += r->B;
   }
+  return FW_OK;
+}
+
+// Decode run over the concatenated chunks of `reqs` (all mergeable with reqs[0]).  Caller holds lane->mu.
+static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest*>& reqs) {
+  int rc = gen_workspace_ensure(m, lane);
+  if (rc) return rc;
+  RunPlan pl;
+  if ((rc = run_plan(m, lane->gen, reqs, pl))) return rc;
+  FW_HIP(hipSetDevice(m->device));
+  PoolHold hold{m->xpool, {}, lane->stream};
+  std::vector<int> slots, ptok;
+  if ((rc = run_acquire_blocks(m, lane, reqs, hold, slots))) return rc;
+  if ((rc = run_init_state(m, lane, reqs, pl, slots, ptok))) return rc;
+  if ((rc = run_prompt_forward(m, lane, pl, ptok))) return rc;
+  if ((rc = run_decode_steps(m, lane, pl))) return rc;
+  return run_finalize(lane, reqs, pl);
+}
+
+// ---- the run scheduler of a decode group.  A caller of fw_generate queues its request and, when no one else is gathering
+//      and a lane is free, LEADS the next run: leader_wait, take_mergeable, run_on_free_lane. ----
+
+// Should the leader of the next run stop waiting for further requests?  Policy only: every value was read under grp.mu.
+// `queued` chunks in `n_queued` requests; `encoding` member encodes in flight (requests about to arrive); `lanes` that may
+// run (fw_model_set_decode_lanes); `want` chunks a run led by the oldest request takes (RunCapacity); fill_pct: the share
+// of `want` at which the leader stops (fw_model_set_merge_wait); wait_over: the newest request arrived longer ago than
+// the merge wait.
+static bool leader_stops_gathering(int64_t queued, int n_queued, int encoding, int active_runs, int lanes, int64_t want,
+                                   int max_batch, int fill_pct, bool wait_over) {
+  // no run in progress at all: every further request waited for is decode time the chip spends idle on the HBM
+  // side (the encoders are MFMA-bound), so an idle group leads with a smaller share of a run's capacity
+  // (idle_fill_pct(): the driver's 20-step burst was ONE run of 288 chunks after 18 serial encoder passes plus two
+  // runs of 16 chunks; with 50 % it is two runs of 160 chunks, the second gathered under the first)
+  const int pct = active_runs == 0 ? std::min(fill_pct, idle_fill_pct()) : fill_pct;
+  if (queued * 100 >= want * pct || encoding <= 0) return true;
+  // ... and with two lanes it splits the work it KNOWS of evenly over the runs that work needs: what is queued plus
+  // one request per worker that is inside an encode call (running or waiting for the encoder; counted at the size of
+  // the queued requests).  20 batches in flight -> two runs of 10, not one of 18 and leftovers.
+  if (idle_balance() && active_runs == 0 && lanes >= 2 &&
+      queued >= idle_lead_chunks(queued, n_queued, encoding, want, max_batch, lanes))
+    return true;
+  return wait_over;
+}
+
+// The leader's wait: for the requests of workers that are still encoding (each arrives within one encoder pass) unless
+// most of a run's capacity is already claimed.  The wait trades this caller's latency for rows per run; it is bounded by
+// the merge-wait knob (fw_model_set_merge_wait: default 2.5 measured encoder passes after the last arrival, at most
+// 250 ms — a pass next to a decode run takes up to twice the pass the average was taken from, and a leader that
+// gives up between two arrivals starts a run of one or two batches: the driver's 20-step burst 2 976 -> 3 030x with
+// 150 or 250 ms, the steady state unchanged, profiles/r05_ab_idle_balance.jsonl; 0 = never) and skipped when no
+// member encode is in flight.
+// Locking: called with grp.mu held through `lk` and grp.gathering set by the caller (one caller gathers at a time); the
+// mutex is released only inside the timed waits, so requests keep arriving, and is held again on return.
+static void leader_wait(Model* dm, std::unique_lock<std::mutex>& lk) {
+  DecodeGroup& grp = dm->grp;
+  int wait_ms = grp.merge_wait_ms.load();
+  if (wait_ms < 0) wait_ms = std::min(250, std::max(5, (grp.enc_pass_us.load() * 5 / 2 + 999) / 1000));
+  if (lane_chunks_of(dm) <= dm->max_batch || wait_ms <= 0) return;
+  for (;;) {
+    const int64_t want = planned_capacity(dm, *grp.queue.front()).want;
+    if (want <= 0) return;   // (the oldest request is a sampling call)
+    int64_t queued = 0;
+    for (const GenRequest* r : grp.queue) queued += r->B;
+    const bool wait_over = std::chrono::steady_clock::now() - grp.last_arrival > std::chrono::milliseconds(wait_ms);
+    if (leader_stops_gathering(queued, (int)grp.queue.size(), grp.encoding.load(), grp.active_runs,
+                               std::min((int)dm->lanes.size(), grp.lanes_enabled.load()), want, dm->max_batch,
+                               grp.merge_fill_pct.load(), wait_over))
+      return;
+    grp.cv.wait_for(lk, std::chrono::microseconds(200));
+  }
+}
+
+// Takes the oldest request and every queued request that can share a run with it off the queue (marked `taken`), up to
+// the run's capacity and one pool block per call; returns the run's chunks.  Locking: grp.mu held throughout.
+static int take_mergeable(Model* dm, std::vector<GenRequest*>& batch) {
+  DecodeGroup& grp = dm->grp;
+  GenRequest* first = grp.queue.front();
+  const int64_t run_cap = planned_capacity(dm, *first).run_cap;
+  const int max_calls = pool_block_count(dm->decode_batch, dm->max_batch);
+  int chunks = 0;
+  for (auto it = grp.queue.begin(); it != grp.queue.end();) {
+    GenRequest* r = *it;
+    if (r == first || (mergeable(*first, *r, dm->cfg.n_text_ctx) && chunks + r->B <= run_cap && (int)batch.size() < max_calls)) {
+      batch.push_back(r);
+      r->taken = true;
+      chunks += r->B;
+      it = grp.queue.erase(it);
+    } else {
+      ++it;
+    }
+  }
+  return chunks;
+}
+
+// Runs `batch` (`chunks` chunks) on the first free lane and hands every request its result.  Locking: called with grp.mu
+// held through `lk` and a lane free (active_runs < lanes); takes the lane and ends the caller's gathering under the mutex,
+// RELEASES it for the run itself (which holds the lane's own mutex; the next leader may gather while this run decodes)
+// and holds it again on return, the requests done and the lane free.
+static void run_on_free_lane(Model* dm, std::unique_lock<std::mutex>& lk, const std::vector<GenRequest*>& batch, int chunks) {
+  DecodeGroup& grp = dm->grp;
+  const int n_lanes = (int)dm->lanes.size();
+  int lane = 0;
+  while (lane + 1 < n_lanes && dm->lanes[lane]->busy) ++lane;    // the first free lane (active_runs < lanes: one is)
+  DecodeLane* dl = dm->lanes[lane].get();    // own workspace, own stream; the weights and the pool are dm's
+  dl->busy = true;
+  grp.active_runs += 1;
+  grp.gathering = false;
+  grp.cv.notify_all();
+  lk.unlock();
+  grp.n_runs.fetch_add(1);
+  grp.n_requests.fetch_add((int64_t)batch.size());
+  grp.n_chunks.fetch_add(chunks);
+  if (chunks > grp.max_run_chunks.load()) grp.max_run_chunks.store(chunks);
+  int rc;
+  // FWAMD_RUN_LOG=1: one stderr line per decode run (start / end on the host clock, lane, calls, chunks) — the timeline of a
+  // burst (profiles/r06_run_log_burst.txt)
+  static const bool run_log = [] { const char* e = getenv("FWAMD_RUN_LOG"); return e && atoi(e) != 0; }();
+  const auto t_run0 = std::chrono::steady_clock::now();
+  {
+    std::lock_guard<std::mutex> run_lk(dl->mu);
+    rc = generate_run(dm, dl, batch);
+  }
+  if (run_log) {
+    const auto t_run1 = std::chrono::steady_clock::now();
+    const double s0 = std::chrono::duration<double>(t_run0.time_since_epoch()).count();
+    const double s1 = std::chrono::duration<double>(t_run1.time_since_epoch()).count();
+    int p_lo = batch[0]->P, p_hi = batch[0]->P;
+    for (const GenRequest* r : batch) { p_lo = std::min(p_lo, r->P); p_hi = std::max(p_hi, r->P); }
+    fprintf(stderr, "[fwamd run] lane %d calls %d chunks %d prompt %d..%d start %.4f end %.4f (%.1f ms)\n", lane,
+            (int)batch.size(), chunks, p_lo, p_hi, s0, s1, 1e3 * (s1 - s0));
+  }
+  const std::string err = rc ? fw_last_error() : "";
+  lk.lock();
+  for (GenRequest* r : batch) { r->rc = rc; r->err = err; r->done = true; }
+  dl->busy = false;
+  grp.active_runs -= 1;
+  grp.cv.notify_all();
+}
+
+// ---- a single teacher-forced call on lane 0 (fw_detect_language, fw_align): one encoder output, every position known ----
+struct SingleCall {
+  std::vector<int> slots;    // [B] pool slots of its chunks (contiguous); outlives `hold`, whose end waits for the upload
+  PoolHold hold{nullptr, {}, nullptr};   // the call's pool block, to the end of the call
+  GenDev gp;
+};
+// Takes the pool block of `enc` (projecting its cross-K/V if it is not there), uploads the slot table, clears the beam
+// tables that a teacher-forced pass reads (kvidx2: every row reads its own cache slot; d_step) and fills the GenDev of
+// P positions with `ctx` cache positions per row; builds the lane's workspace on first use.  Caller holds lane->mu and
+// waits for the stream before `sc` goes.
+static int single_call_begin(Model* m, DecodeLane* lane, const Tensor* enc, int P, int ctx, const HipFail& fail, SingleCall& sc) {
+  FW_HIP(hipSetDevice(m->device));
+  if (int rc = gen_workspace_ensure(m, lane)) return rc;
+  GenWorkspace* g = lane->gen;
+  const int B = enc->B;
+  hipStream_t st = lane->stream;
+  CrossPool* pool = m->xpool;
+  sc.hold.p = pool; sc.hold.st = st;
+  std::vector<char> hit;
+  pool_acquire(pool, {enc->id}, {enc->B}, sc.hold.blk, hit);
+  if (int rc = ensure_cross_kv(m, lane, enc, sc.hold.blk[0], hit[0] != 0)) return rc;
+  sc.slots.resize(B);
+  for (int b = 0; b < B; ++b) sc.slots[b] = sc.hold.blk[0] * pool->EB + b;
+  FW_HIP_AS(fail, hipMemcpyAsync(g->slot_map, sc.slots.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(fail, hipMemsetAsync(g->kvidx2, 0, 2 * (size_t)g->R * g->NT, st));
+  FW_HIP_AS(fail, hipMemsetAsync(g->d_step, 0, sizeof(int), st));
+  GenDev& gp = sc.gp;
+  memset(&gp, 0, sizeof(gp));
+  // rows of a prefill-style step use beam slot 0 of chunk b: slot stride is max_beam
+  gp.B = B; gp.K = m->max_beam; gp.R = g->R; gp.P = P; gp.V = m->cfg.n_vocab; gp.n_text_ctx = g->NT; gp.kv_div = 1;
+  gp.ctx = ctx; gp.cache_rows = B * m->max_beam;   // <= EB * K * NT <= self_cap
   return FW_OK;
 }
 
@@ -1120,19 +1346,15 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   // fw_model_set_decode_batch rebuilds the workspaces and the lanes under grp.resizing: nothing is read from
   // them (capacities, dm->lanes) and nothing is queued until it is done
   while (grp.resizing) grp.cv.wait(lk);
-  {
-    // this call alone must fit a lane (rows and self-attention cache), so that a call that cannot is refused here,
-    // before it is merged with others whose run it would fail
-    const int64_t rows = sampling ? (int64_t)B * o->num_hypotheses : (int64_t)B * K;
-    const int64_t row_cap = (int64_t)lane_chunks_of(dm) * dm->max_beam;
-    const int ctx = run_ctx(c, o->max_length, P);
-    if (rows > row_cap || rows * ctx > planned_self_cap(dm)) {
-      lk.unlock();
-      set_error("this call needs %lld decoder rows x %d positions; a decode run of this model holds %lld rows and %lld "
-                "row-positions (batch x num_hypotheses / beam_size too large for max_length %d)",
-                (long long)rows, ctx, (long long)row_cap, (long long)planned_self_cap(dm), o->max_length);
-      return FW_EINVAL;
-    }
+  // this call alone must fit a lane (rows and self-attention cache), so that a call that cannot is refused here,
+  // before it is merged with others whose run it would fail
+  const RunCapacity cap = planned_capacity(dm, req);
+  if (!cap.rows_fit || !cap.cache_fits) {
+    lk.unlock();
+    set_error("this call needs %lld decoder rows x %d positions; a decode run of this model holds %lld rows and %lld "
+              "row-positions (batch x num_hypotheses / beam_size too large for max_length %d)",
+              (long long)cap.rows, cap.ctx, (long long)cap.row_cap, (long long)cap.self_cap, o->max_length);
+    return FW_EINVAL;
   }
   grp.queue.push_back(&req);
   grp.last_arrival = std::chrono::steady_clock::now();
@@ -1142,102 +1364,13 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
       grp.cv.wait(lk);
       continue;
     }
-    // lead the next run: wait for the requests of workers that are still encoding (each arrives within one
-    // encoder pass) unless most of a run's capacity is already claimed, then take every queued request that can share
-    // a run with the oldest one.  The wait trades this caller's latency for rows per run; it is bounded by the
-    // merge-wait knob (fw_model_set_merge_wait: default 2.5 measured encoder passes after the last arrival, at most
-    // 250 ms — a pass next to a decode run takes up to twice the pass the average was taken from, and a leader that
-    // gives up between two arrivals starts a run of one or two batches: the driver's 20-step burst 2 976 -> 3 030x with
-    // 150 or 250 ms, the steady state unchanged, profiles/r05_ab_idle_balance.jsonl; 0 = never) and skipped when no
-    // member encode is in flight.  One caller gathers at a time; with two lanes
-    // the next one starts gathering as soon as this one has taken its requests and gone off to run them.
+    // lead the next run: the OLDEST request and what merges with it (if this caller's own is not among them, it goes round
+    // again).  With two lanes the next leader starts gathering as soon as this one has gone off to run its requests.
     grp.gathering = true;
-    const int cap = lane_chunks_of(dm);
-    int wait_ms = grp.merge_wait_ms.load();
-    if (wait_ms < 0) wait_ms = std::min(250, std::max(5, (grp.enc_pass_us.load() * 5 / 2 + 999) / 1000));
-    const int fill_pct = grp.merge_fill_pct.load();
-    if (cap > dm->max_batch && wait_ms > 0 && !grp.queue.front()->sampling) {
-      for (;;) {
-        int queued = 0;
-        for (const GenRequest* r : grp.queue) queued += r->B;
-        const int64_t want = std::min<int64_t>(cap, std::max<int64_t>(dm->max_batch, DEC_RUN_MAX_ROWS / std::max(1, grp.queue.front()->o->beam_size)));
-        // no run in progress at all: every further request waited for is decode time the chip spends idle on the HBM
-        // side (the encoders are MFMA-bound), so an idle group leads with a smaller share of a run's capacity
-        // (idle_fill_pct(): the driver's 20-step burst was ONE run of 288 chunks after 18 serial encoder passes plus two
-        // runs of 16 chunks; with 50 % it is two runs of 160 chunks, the second gathered under the first)
-        const int pct = grp.active_runs == 0 ? std::min(fill_pct, idle_fill_pct()) : fill_pct;
-        if ((int64_t)queued * 100 >= want * pct || grp.encoding.load() <= 0) break;
-        // ... and with two lanes it splits the work it KNOWS of evenly over the runs that work needs: what is queued plus
-        // one request per worker that is inside an encode call (running or waiting for the encoder; counted at the size of
-        // the queued requests).  20 batches in flight -> two runs of 10, not one of 18 and leftovers.
-        if (idle_balance() && grp.active_runs == 0 && n_lanes >= 2 && grp.lanes_enabled.load() >= 2 &&
-            queued >= idle_lead_chunks(queued, (int)grp.queue.size(), grp.encoding.load(), want, dm->max_batch,
-                                       std::min(n_lanes, grp.lanes_enabled.load())))
-          break;
-        if (std::chrono::steady_clock::now() - grp.last_arrival > std::chrono::milliseconds(wait_ms)) break;
-        grp.cv.wait_for(lk, std::chrono::microseconds(200));
-      }
-    }
+    leader_wait(dm, lk);
     std::vector<GenRequest*> batch;
-    GenRequest* first = grp.queue.front();
-    int chunks = 0;
-    // chunks the self-attention cache holds at this call's context (mergeable calls share max_length, hence the context)
-    // ... and the rows above which the 4 x 4-tile decoder linears no longer fit the chip in one round of workgroups
-    // (d x d: 20 column groups x 25 row groups of 64 rows = 500 of 512 workgroup slots)
-    int64_t run_cap = std::min<int64_t>(cap, std::max<int64_t>(first->B, self_chunk_capacity(dm, *first)));
-    if (!first->sampling)
-      run_cap = std::min<int64_t>(run_cap, std::max<int64_t>(dm->max_batch, DEC_RUN_MAX_ROWS / std::max(1, first->o->beam_size)));
-    else   // num_hypotheses rows per chunk, not bounded by max_beam: the run's rows must fit the lane's
-      run_cap = std::min<int64_t>(run_cap, std::max<int64_t>(first->B, (int64_t)cap * dm->max_beam / std::max(1, first->o->num_hypotheses)));
-    // (one pool block per call: a run never takes more calls than the pool has blocks)
-    const int max_calls = std::max(1, std::max(dm->decode_batch, dm->max_batch) / dm->max_batch);
-    for (auto it = grp.queue.begin(); it != grp.queue.end();) {
-      GenRequest* r = *it;
-      if (r == first || (mergeable(*first, *r, c.n_text_ctx) && chunks + r->B <= run_cap && (int)batch.size() < max_calls)) {
-        batch.push_back(r);
-        r->taken = true;
-        chunks += r->B;
-        it = grp.queue.erase(it);
-      } else {
-        ++it;
-      }
-    }
-    int lane = 0;
-    while (lane + 1 < n_lanes && dm->lanes[lane]->busy) ++lane;    // the first free lane (active_runs < lanes: one is)
-    DecodeLane* dl = dm->lanes[lane].get();    // own workspace, own stream; the weights and the pool are dm's
-    dl->busy = true;
-    grp.active_runs += 1;
-    grp.gathering = false;
-    grp.cv.notify_all();                    // (the next leader may gather while this run decodes)
-    lk.unlock();
-    grp.n_runs.fetch_add(1);
-    grp.n_requests.fetch_add((int64_t)batch.size());
-    grp.n_chunks.fetch_add(chunks);
-    if (chunks > grp.max_run_chunks.load()) grp.max_run_chunks.store(chunks);
-    int rc;
-    // FWAMD_RUN_LOG=1: one stderr line per decode run (start / end on the host clock, lane, calls, chunks) — the timeline of a
-    // burst (profiles/r06_run_log_burst.txt)
-    static const bool run_log = [] { const char* e = getenv("FWAMD_RUN_LOG"); return e && atoi(e) != 0; }();
-    const auto t_run0 = std::chrono::steady_clock::now();
-    {
-      std::lock_guard<std::mutex> run_lk(dl->mu);
-      rc = generate_run(dm, dl, batch);
-    }
-    if (run_log) {
-      const auto t_run1 = std::chrono::steady_clock::now();
-      const double s0 = std::chrono::duration<double>(t_run0.time_since_epoch()).count();
-      const double s1 = std::chrono::duration<double>(t_run1.time_since_epoch()).count();
-      int p_lo = batch[0]->P, p_hi = batch[0]->P;
-      for (const GenRequest* r : batch) { p_lo = std::min(p_lo, r->P); p_hi = std::max(p_hi, r->P); }
-      fprintf(stderr, "[fwamd run] lane %d calls %d chunks %d prompt %d..%d start %.4f end %.4f (%.1f ms)\n", lane,
-              (int)batch.size(), chunks, p_lo, p_hi, s0, s1, 1e3 * (s1 - s0));
-    }
-    const std::string err = rc ? fw_last_error() : "";
-    lk.lock();
-    for (GenRequest* r : batch) { r->rc = rc; r->err = err; r->done = true; }
-    dl->busy = false;
-    grp.active_runs -= 1;
-    grp.cv.notify_all();
+    const int chunks = take_mergeable(dm, batch);
+    run_on_free_lane(dm, lk, batch, chunks);
   }
   lk.unlock();
   if (req.rc) set_error("%s", req.err.c_str());
@@ -1255,35 +1388,18 @@ int32_t fw_detect_language(fw_model* fm, const fw_tensor* enc_t, int32_t B, int3
                "bad encoder output / batch");
   DecodeLane* lane = m->lanes[0].get();
   std::lock_guard<std::mutex> lk(lane->mu);
-  FW_HIP(hipSetDevice(m->device));
   int rc;
-  if ((rc = gen_workspace_ensure(m, lane))) return rc;
+  SingleCall sc;
+  if ((rc = single_call_begin(m, lane, enc, 1, 8, HipFail{FW_ENODEV, "detect_language setup"}, sc))) return rc;
   GenWorkspace* g = lane->gen;
   hipStream_t st = lane->stream;
-  CrossPool* pool = m->xpool;
-  PoolHold hold{pool, {}, st};
-  std::vector<int> slots(B);
-  {
-    std::vector<char> hit;
-    pool_acquire(pool, {enc->id}, {enc->B}, hold.blk, hit);
-    if ((rc = ensure_cross_kv(m, lane, enc, hold.blk[0], hit[0] != 0))) return rc;
-    for (int b = 0; b < B; ++b) slots[b] = hold.blk[0] * pool->EB + b;
-  }
-  FW_HIP(hipMemcpyAsync(g->slot_map, slots.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-  GenDev gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.B = B; gp.K = m->max_beam; gp.R = g->R; gp.P = 1; gp.V = c.n_vocab; gp.n_text_ctx = g->NT; gp.kv_div = 1;
-  gp.ctx = 8; gp.cache_rows = B * m->max_beam;
   std::vector<int> tok(B, c.tok_sot);
-  FW_HIP(hipMemsetAsync(g->kvidx2, 0, 2 * (size_t)g->R * g->NT, st));
-  FW_HIP(hipMemsetAsync(g->d_step, 0, sizeof(int), st));
   FW_HIP(hipMemcpyAsync(g->prompt_dev, tok.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP(hipStreamSynchronize(st));
   StepCfg s;
   s.rows = B; s.kmul = 1; s.B = B; s.pos_fixed = 0; s.P = 1; s.tok = g->prompt_dev;
   s.need_logits = true; s.nospeech_rowmul = 0; s.beam_tail = false; s.done = g->zero_done;
-  // rows of a prefill-style step use beam slot 0 of chunk b: slot stride is max_beam
-  if ((rc = run_step(m, lane, gp, s))) return rc;
+  if ((rc = run_step(m, lane, sc.gp, s))) return rc;
   std::vector<float> lg((size_t)B * c.n_langs);
   FW_HIP(hipMemcpy2DAsync(lg.data(), c.n_langs * sizeof(float), g->logits + c.tok_lang_begin,
                           (size_t)c.n_vocab * sizeof(float), c.n_langs * sizeof(float), B, hipMemcpyDeviceToHost, st));
@@ -1465,38 +1581,23 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
 
   DecodeLane* lane = m->lanes[0].get();
   std::lock_guard<std::mutex> lk(lane->mu);
-  FW_HIP(hipSetDevice(m->device));
   int rc;
-  if ((rc = gen_workspace_ensure(m, lane))) return rc;
+  const HipFail setup_fail{FW_ERUNTIME, "align setup"}, run_fail{FW_ERUNTIME, "align"};
+  // teacher forcing: every position is known up front (<= EB * K * NT row-positions of the cache: <= self_cap)
+  SingleCall sc;
+  if ((rc = single_call_begin(m, lane, enc, max_tok, std::min(c.n_text_ctx, (max_tok + 7) / 8 * 8), setup_fail, sc))) return rc;
   GenWorkspace* g = lane->gen;
   hipStream_t st = lane->stream;
-  CrossPool* pool = m->xpool;
-  PoolHold hold{pool, {}, st};
-  std::vector<int> slots(B);
-  {
-    std::vector<char> hit;
-    pool_acquire(pool, {enc->id}, {enc->B}, hold.blk, hit);
-    if ((rc = ensure_cross_kv(m, lane, enc, hold.blk[0], hit[0] != 0))) return rc;
-    for (int b = 0; b < B; ++b) slots[b] = hold.blk[0] * pool->EB + b;
-  }
-  const int kv_slot0 = slots[0];
+  const int kv_slot0 = sc.slots[0];
 
+  DevBufs tmp;   // (after `sc`: freed before the pool block is released)
   float *probs = nullptr, *stats = nullptr, *mat = nullptr, *tprob = nullptr;
   int *heads_dev = nullptr, *ntok_dev = nullptr, *nfr_dev = nullptr, *target_dev = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)probs, (void*)stats, (void*)mat, (void*)tprob, (void*)heads_dev, (void*)ntok_dev,
-                    (void*)nfr_dev, (void*)target_dev})
-      if (p) (void)hipFree(p);
-  };
-#define AL(p, n) do { if ((rc = dev_alloc_t(&(p), (n)))) { cleanup(); return rc; } } while (0)
-  AL(probs, (size_t)B * n_sel * max_tok * T);
-  AL(stats, (size_t)B * n_sel * T * 2);
-  AL(mat, (size_t)B * max_tok * T);
-  AL(tprob, (size_t)B * max_tok);
-  AL(heads_dev, (size_t)n_sel);
-  AL(ntok_dev, (size_t)B); AL(nfr_dev, (size_t)B);
-  AL(target_dev, (size_t)max_tok * B);
-#undef AL
+  if ((rc = tmp.alloc(&probs, (size_t)B * n_sel * max_tok * T)) || (rc = tmp.alloc(&stats, (size_t)B * n_sel * T * 2)) ||
+      (rc = tmp.alloc(&mat, (size_t)B * max_tok * T)) || (rc = tmp.alloc(&tprob, (size_t)B * max_tok)) ||
+      (rc = tmp.alloc(&heads_dev, (size_t)n_sel)) || (rc = tmp.alloc(&ntok_dev, (size_t)B)) ||
+      (rc = tmp.alloc(&nfr_dev, (size_t)B)) || (rc = tmp.alloc(&target_dev, (size_t)max_tok * B)))
+    return rc;
   std::vector<int> ntok(B), nfr(B), ptok((size_t)max_tok * B), target((size_t)max_tok * B, -1);
   for (int b = 0; b < B; ++b) {
     ntok[b] = (int)seq[b].size();
@@ -1509,85 +1610,43 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
       if (p >= n0 - 1 && p < n0 - 1 + nt) target[(size_t)p * B + b] = seq[b][p + 1];
     }
   }
-  hipError_t he = hipMemcpyAsync(heads_dev, sel_heads.data(), n_sel * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipMemcpyAsync(ntok_dev, ntok.data(), B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipMemcpyAsync(nfr_dev, nfr.data(), B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess)
-    he = hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess)
-    he = hipMemcpyAsync(target_dev, target.data(), target.size() * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipMemcpyAsync(g->slot_map, slots.data(), B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipMemsetAsync(g->kvidx2, 0, 2 * (size_t)g->R * g->NT, st);
-  if (he == hipSuccess) he = hipMemsetAsync(g->d_step, 0, sizeof(int), st);
-  if (he == hipSuccess) he = hipMemsetAsync(tprob, 0, (size_t)B * max_tok * sizeof(float), st);
-  if (he == hipSuccess) he = hipStreamSynchronize(st);
-  if (he != hipSuccess) {
-    cleanup();
-    set_error("align setup failed: %s", hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  GenDev gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.B = B; gp.K = m->max_beam; gp.R = g->R; gp.P = max_tok; gp.V = c.n_vocab; gp.n_text_ctx = g->NT; gp.kv_div = 1;
-  gp.ctx = std::min(g->NT, (max_tok + 7) / 8 * 8); gp.cache_rows = B * m->max_beam;   // <= EB * K * NT <= self_cap
-  // teacher forcing: every position is known up front, so the text goes through the decoder in blocks of up to 16
-  // positions per pass (a 100-token segment: 7 passes instead of 100)
-  const int nbmax = pos_block_size(m, g, gp, B);
-  if (nbmax > 1) {
-    std::vector<int> blk_tok;
-    blk_tok.reserve((size_t)max_tok * B);
-    for (int pos = 0; pos < max_tok;) {
-      const int nb = std::min(nbmax, max_tok - pos);
-      for (int b = 0; b < B; ++b)
-        for (int j = 0; j < nb; ++j) blk_tok.push_back(ptok[(size_t)(pos + j) * B + b]);
-      pos += nb;
-    }
-    he = hipMemcpyAsync(g->prompt_blk, blk_tok.data(), blk_tok.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) {
-      cleanup();
-      set_error("align setup failed: %s", hipGetErrorString(he));
-      return FW_ERUNTIME;
-    }
-  }
-  for (int pos = 0; pos < max_tok;) {
-    const int nb = std::min(nbmax, max_tok - pos);
-    StepCfg s;
-    s.B = B; s.pos_fixed = pos; s.P = max_tok;
-    if (nbmax > 1) {   // (a last block of one position has the same layout either way)
-      s.rows = B * nb; s.kmul = nb; s.blk_n = nb > 1 ? nb : 0; s.tok = g->prompt_blk + (size_t)pos * B;
-    } else {
-      s.rows = B; s.kmul = 1; s.tok = g->prompt_dev + (size_t)pos * B;
-    }
-    bool any_target = false;
-    for (int j = 0; j < nb; ++j)
-      for (int b = 0; b < B; ++b) any_target |= target[(size_t)(pos + j) * B + b] >= 0;
-    s.need_logits = any_target;
-    s.nospeech_rowmul = 0; s.beam_tail = false; s.done = g->zero_done;
-    s.sel_heads_dev = heads_dev; s.sel_layer_off = layer_off.data(); s.probs = probs; s.n_sel_total = n_sel;
-    s.kv_slot0 = kv_slot0;
-    s.n_tok = max_tok; s.tok_idx = pos;
-    if ((rc = run_step(m, lane, gp, s))) { cleanup(); return rc; }
-    for (int j = 0; j < nb && any_target; ++j) {
-      bool tj = false;
-      for (int b = 0; b < B; ++b) tj |= target[(size_t)(pos + j) * B + b] >= 0;
-      if (tj)
-        fwd::launch_token_prob(st, g->logits + (size_t)j * c.n_vocab, c.n_vocab, target_dev + (size_t)(pos + j) * B, tprob,
-                               max_tok, pos + j, B, nb);
-    }
-    pos += nb;
-  }
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(heads_dev, sel_heads.data(), n_sel * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(ntok_dev, ntok.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(nfr_dev, nfr.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(target_dev, target.data(), target.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemsetAsync(tprob, 0, (size_t)B * max_tok * sizeof(float), st));
+  FW_HIP_AS(setup_fail, hipStreamSynchronize(st));
+  // the text goes through the decoder in position blocks (a 100-token segment: 7 passes instead of 100); the selected
+  // heads' cross-attention probabilities of every position, and the probability of the next text token where there is one
+  auto targets_at = [&](int p) {
+    for (int b = 0; b < B; ++b)
+      if (target[(size_t)p * B + b] >= 0) return true;
+    return false;
+  };
+  rc = pos_block_forward(
+      m, lane, sc.gp, ptok, max_tok, B, max_tok, setup_fail,
+      [&](StepCfg& s, int pos, int nb) {
+        s.need_logits = false;
+        for (int j = 0; j < nb; ++j) s.need_logits = s.need_logits || targets_at(pos + j);
+        s.nospeech_rowmul = 0; s.done = g->zero_done;
+        s.sel_heads_dev = heads_dev; s.sel_layer_off = layer_off.data(); s.probs = probs; s.n_sel_total = n_sel;
+        s.kv_slot0 = kv_slot0;
+        s.n_tok = max_tok; s.tok_idx = pos;
+      },
+      [&](int pos, int nb) {
+        for (int j = 0; j < nb; ++j)
+          if (targets_at(pos + j))
+            fwd::launch_token_prob(st, g->logits + (size_t)j * c.n_vocab, c.n_vocab, target_dev + (size_t)(pos + j) * B, tprob,
+                                   max_tok, pos + j, B, nb);
+      });
+  if (rc) return rc;
   launch_align_post(st, probs, stats, n_sel, max_tok, T, B, ntok_dev, nfr_dev, median_filter_width, mat);
   std::vector<float> hmat((size_t)B * max_tok * T), htprob((size_t)B * max_tok);
-  he = hipMemcpyAsync(hmat.data(), mat, hmat.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess) he = hipMemcpyAsync(htprob.data(), tprob, htprob.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess) he = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = hipGetLastError();
-  cleanup();
-  if (he != hipSuccess) {
-    set_error("align failed: %s", hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
+  FW_HIP_AS(run_fail, hipMemcpyAsync(hmat.data(), mat, hmat.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  FW_HIP_AS(run_fail, hipMemcpyAsync(htprob.data(), tprob, htprob.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  FW_HIP_AS(run_fail, hipStreamSynchronize(st));
+  FW_HIP_AS(run_fail, hipGetLastError());
   prof_collect(lane->prof);
   const int n0 = n_start + 1;
   for (int b = 0; b < B; ++b) {

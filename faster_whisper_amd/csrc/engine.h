@@ -29,6 +29,17 @@ void set_error(const char* fmt, ...);
       return FW_ENODEV;                                                                \
     }                                                                                  \
   } while (0)
+// FW_HIP inside a helper that several entry points share: a failed call is reported with the caller's own message and
+// return code (fw_align: "align setup failed: ..." / FW_ERUNTIME; elsewhere FW_ENODEV, like FW_HIP)
+struct HipFail { int code; const char* what; };
+#define FW_HIP_AS(f, call)                                                          \
+  do {                                                                              \
+    hipError_t e_ = (call);                                                         \
+    if (e_ != hipSuccess) {                                                         \
+      fw::set_error("%s failed: %s", (f).what, hipGetErrorString(e_));             \
+      return (f).code;                                                              \
+    }                                                                               \
+  } while (0)
 #define FW_CHECK_ARG(cond, ...)        \
   do {                                 \
     if (!(cond)) {                     \
@@ -276,8 +287,42 @@ int dev_alloc(void** p, size_t bytes);
 hipError_t create_stream(hipStream_t* st, const char* role);   // role "ENC" / "DEC": engine.hip
 // decode groups (decoder.hip): chunks an idle two-lane group waits for before it leads a run
 int64_t idle_lead_chunks(int64_t queued, int n_queued, int encoding, int64_t want, int max_batch, int lanes = 2);
+// ... and what a lane holds of runs led by one call (decoder.hip; host arithmetic only: fw_test_run_capacity)
+struct RunCapacity {
+  int64_t rows_per_chunk;        // decoder rows per encoder chunk: beam_size, or num_hypotheses when sampling
+  int64_t rows, row_cap, self_cap;   // the leading call's rows; the lane's rows and self-attention row-positions
+  int ctx;                       // cache positions per row of the run
+  bool rows_fit, cache_fits;     // the leading call alone fits the lane (fw_generate refuses one that does not)
+  int64_t want;                  // chunks the leader waits for; 0: it does not wait (sampling)
+  int64_t run_cap;               // chunks the run is filled to (take_mergeable)
+  RunCapacity(int lane_chunks, int max_batch, int max_beam, int64_t self_cap, int B, bool sampling, int beam_size,
+              int num_hypotheses, int ctx);
+};
 template <typename T>
 inline int dev_alloc_t(T** p, size_t n) { return dev_alloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
+// Device buffers of one owner (a GenWorkspace, one fw_align call, one test-hook call): a buffer is recorded where it is
+// allocated, and all of them are freed with the owner, however the owner goes.
+struct DevBufs {
+  std::vector<void*> ptrs;
+  DevBufs() = default;
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <typename T>
+  int alloc(T** p, size_t n) {
+    if (int rc = dev_alloc_t(p, n)) return rc;
+    ptrs.push_back(*p);
+    return FW_OK;
+  }
+  template <typename T>
+  int zalloc(T** p, size_t n) {   // ... and zeroed (on the null stream: the owner synchronises before its first use)
+    if (int rc = alloc(p, n)) return rc;
+    FW_HIP(hipMemset(*p, 0, n * sizeof(T)));
+    return FW_OK;
+  }
+};
 
 // linear layer on "many rows": C = act(A W^T + b) + res   (encoder / prefill / align)
 // st == null: the model's encoder stream

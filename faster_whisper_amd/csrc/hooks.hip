@@ -22,18 +22,7 @@ using fwd::GenDev;
 
 namespace {
 
-struct HookBufs {   // device buffers of one hook call, freed on every return path
-  std::vector<void*> p;
-  HookBufs() = default;
-  HookBufs(const HookBufs&) = delete;
-  HookBufs& operator=(const HookBufs&) = delete;
-  ~HookBufs() { for (void* q : p) (void)hipFree(q); }
-  template <typename T>
-  int alloc(T** dst, size_t n) {
-    int rc = dev_alloc_t(dst, n);
-    if (!rc) p.push_back(*dst);
-    return rc;
-  }
+struct HookBufs : DevBufs {   // device buffers of one hook call, freed on every return path
   template <typename T>
   int upload(T** dst, const T* src, size_t n) {
     int rc = alloc(dst, n);
@@ -325,6 +314,17 @@ int32_t fw_test_knob(int32_t id, int32_t value) {
 // host-only: the run size an idle two-lane decode group leads with (decoder.hip: idle_lead_chunks); needs no device
 int64_t fw_test_idle_lead_chunks(int64_t queued, int32_t n_queued, int32_t encoding, int64_t want, int32_t max_batch) {
   return idle_lead_chunks(queued, n_queued, encoding, want, max_batch);
+}
+
+// host-only: what a lane holds of runs led by one call (decoder.hip: RunCapacity); needs no device
+int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max_beam, int64_t self_cap, int32_t B,
+                             int32_t sampling, int32_t beam_size, int32_t num_hypotheses, int32_t ctx,
+                             int64_t* rows_per_chunk, int64_t* want, int64_t* run_cap) {
+  const RunCapacity cap(lane_chunks, max_batch, max_beam, self_cap, B, sampling != 0, beam_size, num_hypotheses, ctx);
+  *rows_per_chunk = cap.rows_per_chunk;
+  *want = cap.want;
+  *run_cap = cap.run_cap;
+  return cap.rows_fit && cap.cache_fits ? 1 : 0;
 }
 
 int32_t fw_test_dec_logits(fw_model* fm, const float* x, int32_t R, float* out) {

@@ -225,6 +225,14 @@ int32_t fw_test_knob(int32_t id, int32_t value);
  * call) over the runs that work needs (>= 2; `want` = chunks one run takes), at least one batch.  The rule the leader of a
  * run applies when no run is in progress (fw_model_set_merge_wait, include/fwamd.h). */
 int64_t fw_test_idle_lead_chunks(int64_t queued, int32_t n_queued, int32_t encoding, int64_t want, int32_t max_batch);
+/* host-only (no device needed): what a decode lane of `lane_chunks` chunks x `max_beam` rows, with a self-attention cache of
+ * `self_cap` row-positions, holds of runs led by a call of `B` chunks (beam_size, or num_hypotheses sampled rows per chunk
+ * when `sampling`; ctx = cache positions per row at the call's max_length).  Returns 1 when the call alone fits the lane
+ * (fw_generate refuses it otherwise), 0 when not; *rows_per_chunk = decoder rows per encoder chunk; *want = chunks the
+ * leader of the run waits for (0: it does not wait: sampling); *run_cap = chunks the run is filled to. */
+int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max_beam, int64_t self_cap, int32_t B,
+                             int32_t sampling, int32_t beam_size, int32_t num_hypotheses, int32_t ctx,
+                             int64_t* rows_per_chunk, int64_t* want, int64_t* run_cap);
 
 #ifdef __cplusplus
 }

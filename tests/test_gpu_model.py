@@ -468,7 +468,10 @@ def test_position_blocks_same_bits(setup):
     are read from the qkv buffer instead of the cache) instead of one position per pass.  Every row keeps its arithmetic,
     so nothing may move by a bit: a 4-token prompt (one block of 3), a prompt with 37 tokens of previous text (blocks of
     16 + 16 + 4 with the <sot> row — the no-speech probability — inside the third), beam and greedy; align over texts
-    of 5 .. 40 tokens (the engine pads to the longest: several blocks, ragged ends)."""
+    of 5 .. 40 tokens (the engine pads to the longest: several blocks, ragged ends).  And the two edges of the block
+    loop: a two-token prompt (ONE prompt-forward position: nothing to block), and a prompt and an align text whose
+    position count is two whole blocks + 1, so that the last block holds exactly one position — the block size taken
+    from what the workspace really gives 3 chunks, min(16, workspace rows / 3)."""
     from faster_whisper_amd import _lib
     from faster_whisper_amd.backend import StorageView
     cfg, model, oracle, feats = setup
@@ -478,19 +481,28 @@ def test_position_blocks_same_bits(setup):
     prev = [cfg.sot_prev] + rng.integers(10, 300, size=36).tolist()
     text = [rng.integers(10, 300, size=n).tolist() for n in (33, 5, 40)]
     num_frames = [3000, 1250, 2000]
+    nb = max(1, min(16, model.decode_stats()["run_capacity"] * 5 // 3))       # (5: the fixture's max_beam)
+    base = _prompt(cfg, True)
+    # the prompt forward covers all but the last token: 2 nb + 1 positions = a prompt of 2 nb + 2 tokens
+    edge_prompt = [cfg.sot_prev] + rng.integers(10, 300, size=max(0, 2 * nb + 2 - 1 - len(base))).tolist() + base
+    # align's sequence is start + <|notimestamps|> + text + <|endoftext|>: 2 nb + 1 positions in the longest
+    edge_text = [rng.integers(10, 300, size=max(1, n)).tolist()
+                 for n in (2 * nb + 1 - len(cfg.sot_sequence) - 2, 5, 3)]
     res = {}
     try:
         for on in (0, 1):
             _lib.check(lib.fw_test_knob(4, on))
             out = []
-            for prompt, beam in ((_prompt(cfg, True), 5), (prev + _prompt(cfg, False), 5), (prev + _prompt(cfg, True), 1)):
+            for prompt, beam in ((_prompt(cfg, True), 5), (prev + _prompt(cfg, False), 5), (prev + _prompt(cfg, True), 1),
+                                 ([cfg.sot, cfg.no_timestamps], 5), (edge_prompt, 5)):
                 kw = dict(beam_size=beam, max_length=len(prompt) + 12, suppress_blank=True, suppress_tokens=_suppress(cfg),
                           max_initial_timestamp_index=50)
                 got = model.generate(enc, [prompt] * 3, return_scores=True, return_no_speech_prob=True, **kw)
                 out.append([(g.sequences_ids, [np.float32(s).tobytes() for s in g.scores],
                              np.float32(g.no_speech_prob).tobytes()) for g in got])
-            al = model.align(enc, cfg.sot_sequence, text, num_frames, median_filter_width=7)
-            out.append([(a.alignments, np.asarray(a.text_token_probs, np.float32).tobytes()) for a in al])
+            for txt in (text, edge_text):
+                al = model.align(enc, cfg.sot_sequence, txt, num_frames, median_filter_width=7)
+                out.append([(a.alignments, np.asarray(a.text_token_probs, np.float32).tobytes()) for a in al])
             res[on] = out
     finally:
         _lib.check(lib.fw_test_knob(4, 1))

@@ -149,6 +149,57 @@ def test_idle_decode_group_splits_known_work_evenly():
     assert f(0, 0, 0, 0, 1) == 1 and f(16, 0, -3, cap, 16) == 16
 
 
+def test_run_capacity_is_stated_once():
+    """What a decode lane holds of runs led by one call (csrc/decoder.hip: RunCapacity, through the host-only hook
+    fw_test_run_capacity — no device involved): rows per encoder chunk, whether the call alone fits the lane (the entry
+    refusal of fw_generate), the chunks the leader waits for and the chunks the run is filled to.  The reference is the
+    arithmetic the entry check, the leader's wait and the gather loop each spelt out on their own before they shared it,
+    restated here; 1 600 = the rows above which the decoder linears start a second round of workgroups."""
+    import ctypes as C
+    from faster_whisper_amd import _lib
+    lib = _lib.load()
+
+    def got(cap, max_batch, max_beam, self_cap, B, sampling, beam, nh, ctx):
+        rpc, want, run_cap = C.c_int64(), C.c_int64(), C.c_int64()
+        fits = lib.fw_test_run_capacity(cap, max_batch, max_beam, self_cap, B, int(sampling), beam, nh, ctx,
+                                        C.byref(rpc), C.byref(want), C.byref(run_cap))
+        return fits, rpc.value, want.value, run_cap.value
+
+    def ref(cap, max_batch, max_beam, self_cap, B, sampling, beam, nh, ctx):
+        rpc = max(1, nh) if sampling else beam
+        rows = B * nh if sampling else B * beam
+        fits = int(not (rows > cap * max_beam or rows * ctx > self_cap))
+        run_cap = min(cap, max(B, self_cap // (rpc * ctx)))
+        if not sampling:
+            want = min(cap, max(max_batch, 1600 // max(1, beam)))
+            run_cap = min(run_cap, max(max_batch, 1600 // max(1, beam)))
+        else:
+            want = 0                                   # the leader of a run of sampling calls does not wait
+            run_cap = min(run_cap, max(B, cap * max_beam // max(1, nh)))
+        return fits, rpc, want, run_cap
+
+    # anchors worked by hand: (lane chunks, max_batch, max_beam, self capacity, B, sampling, beam, hypotheses, context)
+    assert got(400, 16, 5, 400 * 5 * 448, 16, False, 5, 1, 448) == (1, 5, 320, 320)      # 1 600 rows bind
+    assert got(320, 16, 5, 320 * 5 * 448, 16, False, 5, 1, 448)[3] == 320
+    assert got(64, 16, 5, 64 * 5 * 448, 16, True, 1, 8, 448) == (1, 8, 0, 40)            # 8 rows per chunk; the lane's rows bind
+    n = 0
+    for cap, max_batch, max_beam in ((4, 4, 5), (16, 16, 5), (64, 16, 5), (320, 16, 5), (400, 16, 5), (409, 16, 5), (24, 8, 1)):
+        for nts in (8, 104, 448):                      # positions per cache row at full row capacity
+            self_cap = cap * max_beam * nts
+            for B in (1, 3, max_batch):
+                for ctx in (8, 104, 448):
+                    for beam in {1, 2, max_beam}:
+                        for nh in {1, beam}:
+                            args = (cap, max_batch, max_beam, self_cap, B, False, beam, nh, ctx)
+                            assert got(*args) == ref(*args), args
+                            n += 1
+                    for nh in (1, 5, 8, 40):
+                        args = (cap, max_batch, max_beam, self_cap, B, True, 1, nh, ctx)
+                        assert got(*args) == ref(*args), args
+                        n += 1
+    assert n > 1000
+
+
 def test_speech_timestamps_skip_ahead_equals_every_window():
     """round 6: get_speech_timestamps jumps over the windows that cannot change its state (an 8 h recording is 900 000
     windows); the plain walk over every window — the reference's loop, vad.py:85-160 — must give the same spans for any
