@@ -1288,7 +1288,7 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   Model* dm = decoder_of(m);
   const Tensor* enc = &enc_t->impl;
   const fw_config& c = m->cfg;
-  FW_CHECK_ARG(enc->owner && decoder_of(enc->owner) == dm, "encoder output belongs to a different model");
+  FW_CHECK_ARG(decoder_of(*enc) == dm, "encoder output belongs to a different model");
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= dm->max_batch, "batch %d exceeds max_batch %d", B, dm->max_batch);
   const int K = o->beam_size;
@@ -1384,7 +1384,7 @@ int32_t fw_detect_language(fw_model* fm, const fw_tensor* enc_t, int32_t B, int3
   const Tensor* enc = &enc_t->impl;
   const fw_config& c = m->cfg;
   FW_CHECK_ARG(c.is_multilingual && c.n_langs > 0, "detect_language needs a multilingual model");
-  FW_CHECK_ARG(enc->owner && decoder_of(enc->owner) == m && B == enc->B && B <= m->max_batch,
+  FW_CHECK_ARG(decoder_of(*enc) == m && B == enc->B && B <= m->max_batch,
                "bad encoder output / batch");
   DecodeLane* lane = m->lanes[0].get();
   std::lock_guard<std::mutex> lk(lane->mu);
@@ -1535,7 +1535,7 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   Model* m = decoder_of(&fm->impl);
   const Tensor* enc = &enc_t->impl;
   const fw_config& c = m->cfg;
-  FW_CHECK_ARG(enc->owner && decoder_of(enc->owner) == m && B == enc->B && B <= m->max_batch,
+  FW_CHECK_ARG(decoder_of(*enc) == m && B == enc->B && B <= m->max_batch,
                "bad encoder output / batch");
   FW_CHECK_ARG(n_start >= 1, "start_sequence must not be empty");
   FW_CHECK_ARG(median_filter_width >= 1 && median_filter_width <= 15 && (median_filter_width & 1),

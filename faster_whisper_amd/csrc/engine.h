@@ -9,7 +9,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -74,8 +73,18 @@ inline float quant_row_i8(const float* row, int K, int8_t* q, At&& at) {
   return amax > 0.f ? amax / 127.0f : 1.0f;
 }
 
+// Fragment-major position of element (row, k) of a [rows][K] operand of the decoder linears (dec_kernels.hip): 16-row
+// tiles x k-steps of KE elements (fp16: 32, int8: 64); the 16 bytes lane l = 16*((k / (KE/4)) % 4) + row % 16 feeds to the
+// MFMA for k-step ks of tile nt sit at ((nt * K/KE + ks) * 64 + l) * 16 B.  The one statement of it: the weight packer
+// permutes through it, the test hooks permute and un-permute through it.
+inline size_t frag_pos(int64_t row, int64_t k, int64_t K, int KE) {
+  const int OCT = KE / 4;
+  return (size_t)((((row >> 4) * (K / KE) + k / KE) * 64 + ((k / OCT) & 3) * 16 + (row & 15)) * OCT + (k % OCT));
+}
+
 // ---- weight blob (what travels over RCCL at load time) --------------------------------
 #define FW_BLOB_MAGIC "FWAMDBL1"
+constexpr int kBlobGeneration = 6;   // BlobHeader::reserved (engine.hip: check_blob_header)
 struct BlobHeader {
   char magic[8];
   int32_t version;
@@ -94,19 +103,12 @@ struct BlobEntry {
   int64_t nbytes;
 };
 
-struct DevTensor {
-  void* ptr = nullptr;
-  int dtype = 1;
-  int ndim = 0;
-  int64_t dims[4] = {0, 0, 0, 0};
-};
-
 struct LinearW {           // y = x W^T + b ; W [N][K] fp16 (or int8 + per-row scale)
   const half_t* w = nullptr;
   const half_t* b = nullptr;
   const int8_t* wq = nullptr;    // int8 weights [N][K]           (int8_float16 only)
   const float* wscale = nullptr; // dequant scale per output row  (int8_float16 only)
-  // LayerNorm-folded form (decoder): w = W.g, y = rstd*(w x - mu*s1) + cf   (engine.hip add_folded)
+  // LayerNorm-folded form (decoder): w = W.g, y = rstd*(w x - mu*s1) + cf   (engine.hip Packer::folded)
   const float* s1 = nullptr;
   const float* cf = nullptr;
   int N = 0, K = 0;
@@ -140,9 +142,70 @@ struct Prof {
   ~Prof();
 };
 
+int dev_alloc(void** p, size_t bytes);
+template <typename T>
+inline int dev_alloc_t(T** p, size_t n) { return dev_alloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
+// Device buffers of one owner (a Model, a GenWorkspace, one fw_align call, one test-hook call): a buffer is recorded
+// where it is allocated, and all of them are freed with the owner, however the owner goes.
+struct DevBufs {
+  std::vector<void*> ptrs;
+  DevBufs() = default;
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <typename T>
+  int alloc(T** p, size_t n) {
+    if (int rc = dev_alloc_t(p, n)) return rc;
+    ptrs.push_back(*p);
+    return FW_OK;
+  }
+  template <typename T>
+  int zalloc(T** p, size_t n) {   // ... and zeroed (on the null stream: the owner synchronises before its first use)
+    if (int rc = alloc(p, n)) return rc;
+    FW_HIP(hipMemset(*p, 0, n * sizeof(T)));
+    return FW_OK;
+  }
+};
+// A device buffer that grows by replacement (the old contents go), freed with its owner.
+template <typename T>
+struct GrowBuf {
+  T* p = nullptr;
+  int64_t cap = 0;   // elements
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() { if (p) (void)hipFree(p); }
+  int ensure(int64_t n) {
+    if (n <= cap) return FW_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (int rc = dev_alloc_t(&p, (size_t)n)) return rc;
+    cap = n;
+    return FW_OK;
+  }
+};
+
 struct Model;
+// Encoder-output buffers of one model, every one [max_batch][T][d] halves (hipMalloc / hipFree synchronise the whole
+// device and would serialise the replicas that share a GPU).  The model and each of its tensors hold the pool: a tensor
+// gives its buffer back to the pool it was taken from, whenever it is freed — after fw_model_free (which closes the
+// pool) the buffer is released instead.  A buffer can therefore never reach a pool of another size.
+struct EncPool {
+  std::mutex mu;
+  std::vector<half_t*> free;
+  const size_t elems;               // of every buffer
+  bool closed = false;
+  std::atomic<Model*> model;        // null once closed (decoder.hip asks which decode group a tensor belongs to)
+  EncPool(Model* m, size_t elems_) : elems(elems_), model(m) {}
+  int take(half_t** p);             // engine.hip
+  void give(half_t* p);
+  void close();
+};
 struct Tensor {  // fw_tensor
-  Model* owner = nullptr;
+  std::shared_ptr<EncPool> pool;
   half_t* data = nullptr;  // [B][T][D] fp16, device
   int B = 0, T = 0, D = 0;
   uint64_t id = 0;         // unique per encoder output (cross-K/V cache key)
@@ -190,19 +253,9 @@ struct DecodeGroup {
   std::atomic<int64_t> graph_captures{0};   // step graphs captured and instantiated by the group's lanes (fw_test_graph_captures)
 };
 
-struct Model {
-  fw_config cfg{};
-  int compute_type = 0;
-  int device = 0;
-  int max_batch = 0, max_beam = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
-
-  // weights
-  void* blob = nullptr;     // device blob (owned unless external)
-  bool blob_owned = true;
-  int64_t blob_bytes = 0;
-  std::map<std::string, DevTensor> tensors;
+// Where the kernels find the weights inside a blob: filled by the one walk over the weight list (engine.hip:
+// walk_weights), which the packer and the binder both make.
+struct Weights {
   int c_pad = 0;  // mel channels padded to a multiple of 64 for the conv1 GEMM
   LinearW conv1, conv2;
   const half_t* enc_pos = nullptr;
@@ -214,6 +267,24 @@ struct Model {
   LinearW logits;  // final LN folded into the tied-embedding projection (fp16) / int8 tied embedding
   LinearW logits_p;   // fp16: the tied embedding itself, fragment-major (explicit final LayerNorm, ln_unfold >= 1)
   LNW dec_ln;
+};
+// host only: the header is one this library packs for a blob of blob_bytes bytes; then every tensor the walk expects for
+// the header's config and compute type is in `entries` with the dtype, dims, size, alignment and bounds the walk implies
+// (FW_EINVAL with the tensor's name otherwise), and W points into `blob`.  *has_plain: the explicit-LayerNorm forms travel.
+int check_blob_header(const BlobHeader& h, int64_t blob_bytes);
+int bind_weights(const BlobHeader& h, const BlobEntry* entries, void* blob, Weights& W, bool* has_plain);
+
+struct Model : Weights {
+  fw_config cfg{};
+  int compute_type = 0;
+  int device = 0;
+  int max_batch = 0, max_beam = 0;
+  hipStream_t stream = nullptr;
+  std::mutex mu;
+
+  void* blob = nullptr;     // device blob (owned unless external)
+  bool blob_owned = true;
+  int64_t blob_bytes = 0;
   // fp16 evaluation order of the decoder LayerNorms.  0: folded into the consuming linear (one
   // launch fewer per LayerNorm; W o g is rounded to fp16 once more and the normalised row is never rounded); 1: the final
   // LayerNorm is its own kernel — fp16(LN(x)) times the tied embedding, the rounding points of the reference's fp16
@@ -227,10 +298,11 @@ struct Model {
   float* lm_filtT = nullptr;   // [224][mel_pad]
   int lm_mel_pad = 0;
 
-  // encoder workspaces (sized for max_batch)
-  float* ws_pcm = nullptr; int64_t ws_pcm_cap = 0;
+  // encoder workspaces (sized for max_batch), the log-mel constants among them, all owned by `bufs`
+  DevBufs bufs;
+  GrowBuf<float> ws_pcm;
   int64_t* ws_offsets = nullptr;
-  float* ws_raw = nullptr; int64_t ws_raw_cap = 0;   // raw log-mel
+  GrowBuf<float> ws_raw;                              // raw log-mel [B][n_mels][stride]
   int* ws_chunk_max = nullptr;
   int* ws_nframes = nullptr;
   float* ws_feat32 = nullptr;                         // [B][n_mels][3000]
@@ -263,9 +335,7 @@ struct Model {
   Model* blob_owner = nullptr;  // the model whose blob this one borrows (fw_model_create_from_blob_dev on fw_model_blob)
   DecodeGroup grp;
 
-  // pooled encoder-output buffers ([max_batch][T][d] each)
-  std::mutex pool_mu;
-  std::vector<half_t*> enc_pool;
+  std::shared_ptr<EncPool> enc_pool;   // pooled encoder-output buffers, shared with the tensors
 
   Prof prof;   // the encoder's scopes (recorded on `stream` under mu); the decode scopes are the lanes'
 };
@@ -279,7 +349,6 @@ struct ProfScope {
 };
 void prof_collect(Prof& p);   // waits for the scopes recorded so far and adds their times
 
-int dev_alloc(void** p, size_t bytes);
 // a non-blocking stream at the priority the environment variable `env` names ("high" / "low"; anything else, or unset:
 // the default priority).  ROCm gives every priority level its own hardware queues, so a decode stream created "high"
 // neither shares a hardware queue with the encoder streams of the workers nor waits behind their workgroups when a CU
@@ -297,31 +366,6 @@ struct RunCapacity {
   int64_t run_cap;               // chunks the run is filled to (take_mergeable)
   RunCapacity(int lane_chunks, int max_batch, int max_beam, int64_t self_cap, int B, bool sampling, int beam_size,
               int num_hypotheses, int ctx);
-};
-template <typename T>
-inline int dev_alloc_t(T** p, size_t n) { return dev_alloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
-// Device buffers of one owner (a GenWorkspace, one fw_align call, one test-hook call): a buffer is recorded where it is
-// allocated, and all of them are freed with the owner, however the owner goes.
-struct DevBufs {
-  std::vector<void*> ptrs;
-  DevBufs() = default;
-  DevBufs(const DevBufs&) = delete;
-  DevBufs& operator=(const DevBufs&) = delete;
-  ~DevBufs() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  int alloc(T** p, size_t n) {
-    if (int rc = dev_alloc_t(p, n)) return rc;
-    ptrs.push_back(*p);
-    return FW_OK;
-  }
-  template <typename T>
-  int zalloc(T** p, size_t n) {   // ... and zeroed (on the null stream: the owner synchronises before its first use)
-    if (int rc = alloc(p, n)) return rc;
-    FW_HIP(hipMemset(*p, 0, n * sizeof(T)));
-    return FW_OK;
-  }
 };
 
 // linear layer on "many rows": C = act(A W^T + b) + res   (encoder / prefill / align)
@@ -362,6 +406,12 @@ void cross_pool_free(Model* m);
 void launch_align_post(hipStream_t st, const float* probs, float* stats, int n_sel, int n_tok_cap, int T, int B,
                        const int* n_tok, const int* nfr, int width, float* mat);
 inline Model* decoder_of(Model* m) { return m->decoder ? m->decoder : m; }
+inline const Model* decoder_of(const Model* m) { return m->decoder ? m->decoder : m; }
+// the decode group an encoder output belongs to; null once the model that made it is gone
+inline Model* decoder_of(const Tensor& t) {
+  Model* m = t.pool ? t.pool->model.load() : nullptr;
+  return m ? decoder_of(m) : nullptr;
+}
 inline int lane_chunks_of(const Model* m) {
   const int b = m->lane_batch > 0 ? m->lane_batch : m->decode_batch;
   return b > m->max_batch ? b : m->max_batch;

@@ -14,6 +14,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
+#include <type_traits>
 
 #include "dec_kernels.h"
 #include "kernels.h"
@@ -106,12 +108,18 @@ static void for_each_prof(Model* m, F&& f) {
 // ---------------------------------------------------------------- blob packing
 struct PackItem {
   std::string name;
-  int ndim;
-  int64_t dims[4];
+  int dtype, ndim;             // dtype as in BlobEntry
+  int64_t dims[4] = {1, 1, 1, 1};
   std::vector<uint16_t> data;  // fp16 payload (dtype 1)
   std::vector<float> fdata;    // fp32 payload (dtype 0)
   std::vector<int8_t> qdata;   // int8 payload (dtype 2)
-  int dtype = 1;
+  PackItem(std::string name_, int dtype_, std::initializer_list<int64_t> dims_)   // a zero payload of dims_
+      : name(std::move(name_)), dtype(dtype_), ndim((int)dims_.size()) {
+    size_t n = 1;
+    std::copy(dims_.begin(), dims_.end(), dims);
+    for (int64_t x : dims_) n *= (size_t)x;
+    if (dtype == 1) data.resize(n); else if (dtype == 2) qdata.resize(n); else fdata.resize(n);
+  }
   const void* bytes() const {
     return dtype == 1 ? (const void*)data.data() : dtype == 2 ? (const void*)qdata.data() : (const void*)fdata.data();
   }
@@ -191,70 +199,217 @@ static int check_config(const fw_config* c) {
   return FW_OK;
 }
 
-// Build the device blob image on the host: all tensors in their final kernel layouts.
-static int pack_blob(const fw_config* cfg, const fw_weight* w, int nw, int compute_type,
-                     std::vector<uint8_t>& blob) {
-  const int d = cfg->d_model, nm = cfg->n_mels;
-  const int c_pad = ((nm + 63) / 64) * 64;
+// ---------------------------------------------------------------- the weight list
+// FWAMD_LN_UNFOLD (a diagnostic, default off: DESIGN.md section 5; Model::ln_unfold): 0, 1 or 2.  Set at PACK time (or
+// FWAMD_PACK_PLAIN=1: the probe packs once and creates models in all three orders) the fp16 blob also carries the plain
+// weights + LayerNorms of qkv / cross.q / ffn1 / the vocabulary projection (+1 GB at large-v3) for the explicit-LayerNorm
+// evaluation order; without it only the folded forms travel.
+static int env_ln_unfold() {
+  const char* e = getenv("FWAMD_LN_UNFOLD");
+  return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : 0;
+}
+static bool env_pack_plain() {
+  const char* e = getenv("FWAMD_PACK_PLAIN");
+  return env_ln_unfold() > 0 || (e && e[0] == '1');
+}
+
+// How a 2-D weight is stored: row-major [N][K]; fragment-major (engine.h: frag_pos) like the six per-layer decoder
+// linears, N % 32 == 0; fragment-major with N padded to a whole 16-row tile by zero rows (the vocabulary projection); or,
+// for the token embedding of an int8 model, row-major fp16 holding the de-quantised int8 rows.
+enum WForm { W_ROWS, W_FRAG, W_FRAG_PAD, W_TIED_I8 };
+static int64_t stored_rows(int64_t N, WForm f) { return f == W_FRAG || f == W_FRAG_PAD ? (N + 15) / 16 * 16 : N; }
+// rows [r0, r0 + n) of a row-major linear, as a linear of their own
+static LinearW rows_of(const LinearW& L, int r0, int n) {
+  LinearW o = L;
+  o.N = n;
+  if (o.w) o.w += (size_t)r0 * L.K;
+  if (o.wq) o.wq += (size_t)r0 * L.K;
+  if (o.wscale) o.wscale += r0;
+  if (o.b) o.b += r0;
+  return o;
+}
+
+// THE weight list of a model: every tensor of a blob in blob order — name, shape, form for the compute type, layout, and
+// the place in W that points at it.  The packer (Packer: builds the tensors from the caller's weights) and the binder
+// (Binder: checks a blob's entries against the list and points W into the blob) are its two visitors:
+//   v.plain(name, dims, &dst, form, src)        fp16 `name`: the caller's weight `src` (default: `name`) in `form`
+//   v.conv(base, cout, cin, cin_pad, L)         <base>.wg [cout][3 * cin_pad]: the caller's <base>.w [cout][cin][3] in
+//                                               GEMM form [out][tap * cin_pad + cin]; and the bias <base>.b
+//   v.folded(out, wname, bname, ln, N, K, form, L)   <out>.wf / .s1 / .cf: LayerNorm `ln` folded into W (Packer::folded)
+//   v.quant(out, wname, N, K, form, L)          <out>.wq / .ws: W quantised per output row (Packer::quant)
+// A visitor that returns non-zero ends the walk.
+template <typename V>
+static int walk_weights(const fw_config& c, bool i8, bool with_plain, Weights& W, V& v) {
+  const int d = c.d_model, NV = c.n_vocab;
+  int rc;
+#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
+  auto shaped = [](int N, int K) { LinearW L; L.N = N; L.K = K; return L; };
+  auto conv = [&](const std::string& base, int cout, int cin, int cin_pad, LinearW& L) {
+    L = shaped(cout, 3 * cin_pad);
+    return v.conv(base, cout, cin, cin_pad, L);
+  };
+  auto ln = [&](const std::string& base, LNW& L) -> int {
+    if (int r = v.plain(base + ".g", {d}, &L.g)) return r;
+    return v.plain(base + ".b", {d}, &L.b);
+  };
+  // a linear layer: fp16 weight <base>.w, or int8 <base>.wq + scale <base>.ws in int8_float16 mode; fp16 bias <base>.b
+  auto linear = [&](const std::string& base, int N, int K, WForm form, LinearW& L) -> int {
+    L = shaped(N, K);
+    int r = i8 ? v.quant(base, base + ".w", N, K, form, L) : v.plain(base + ".w", {N, K}, &L.w, form);
+    return r ? r : v.plain(base + ".b", {N}, &L.b);
+  };
+  // a decoder linear fed by a LayerNorm (decoder rows are few, so the LN kernel would be pure launch overhead): fp16:
+  // folded into L — and with_plain the plain linear Lp and the LayerNorm beside it; int8: the plain linear L and the
+  // LayerNorm, which the row quantiser applies
+  auto ln_linear = [&](const std::string& base, const std::string& lnb, int N, int K, LinearW& L, LinearW& Lp,
+                       LNW& lnw) -> int {
+    if (!i8) {
+      L = shaped(N, K);
+      int r = v.folded(base, base + ".w", base + ".b", lnb, N, K, W_FRAG, L);
+      if (r || !with_plain) return r;
+    }
+    int r = linear(base, N, K, W_FRAG, i8 ? L : Lp);
+    return r ? r : ln(lnb, lnw);
+  };
+  W.c_pad = ((c.n_mels + 63) / 64) * 64;
+  TRY(conv("enc.conv1", d, c.n_mels, W.c_pad, W.conv1));
+  TRY(conv("enc.conv2", d, d, d, W.conv2));
+  TRY(v.plain("enc.pos", {c.n_audio_ctx, d}, &W.enc_pos));
+  W.enc.assign(c.n_enc_layers, EncLayerW());
+  W.dec.assign(c.n_dec_layers, DecLayerW());
+  char nb[96];
+  for (int i = 0; i < c.n_enc_layers; ++i) {
+    EncLayerW& L = W.enc[i];
+    auto nm = [&](const char* s) { snprintf(nb, sizeof(nb), "enc.%d.%s", i, s); return std::string(nb); };
+    LinearW qkv;   // fused: Q | K rows [0, 2d) and V rows [2d, 3d) bind separately
+    TRY(ln(nm("ln1"), L.ln1));
+    TRY(linear(nm("attn.qkv"), 3 * d, d, W_ROWS, qkv));
+    L.qk = rows_of(qkv, 0, 2 * d);
+    L.v = rows_of(qkv, 2 * d, d);
+    TRY(linear(nm("attn.out"), d, d, W_ROWS, L.out));
+    TRY(ln(nm("ln2"), L.ln2));
+    TRY(linear(nm("ffn1"), 4 * d, d, W_ROWS, L.ffn1));
+    TRY(linear(nm("ffn2"), d, 4 * d, W_ROWS, L.ffn2));
+  }
+  TRY(ln("enc.ln_post", W.enc_ln_post));
+  // [CT2-ext] int8: the token embedding shares the int8 projection weight: a lookup returns the de-quantised row
+  TRY(v.plain("dec.tok_emb", {NV, d}, &W.tok_emb, i8 ? W_TIED_I8 : W_ROWS));
+  TRY(v.plain("dec.pos", {c.n_text_ctx, d}, &W.dec_pos));
+  for (int i = 0; i < c.n_dec_layers; ++i) {
+    DecLayerW& L = W.dec[i];
+    auto nm = [&](const char* s) { snprintf(nb, sizeof(nb), "dec.%d.%s", i, s); return std::string(nb); };
+    LinearW ckv;   // fused, and a "many rows" GEMM operand (row-major): K rows [0, d), V rows [d, 2d)
+    TRY(ln_linear(nm("self.qkv"), nm("ln1"), 3 * d, d, L.qkv, L.qkv_p, L.ln1));
+    TRY(linear(nm("self.out"), d, d, W_FRAG, L.out));
+    TRY(ln_linear(nm("cross.q"), nm("ln2"), d, d, L.cq, L.cq_p, L.ln2));
+    TRY(linear(nm("cross.kv"), 2 * d, d, W_ROWS, ckv));
+    L.ck = rows_of(ckv, 0, d);
+    L.cv = rows_of(ckv, d, d);
+    TRY(linear(nm("cross.out"), d, d, W_FRAG, L.cout));
+    TRY(ln_linear(nm("ffn1"), nm("ln3"), 4 * d, d, L.ffn1, L.ffn1_p, L.ln3));
+    TRY(linear(nm("ffn2"), d, 4 * d, W_FRAG, L.ffn2));
+  }
+  // the vocabulary projection: the tied embedding, quantised (int8) or with the final LayerNorm folded in (fp16)
+  W.logits = shaped(NV, d);
+  if (i8) {
+    TRY(v.quant("dec.logits", "dec.tok_emb", NV, d, W_FRAG_PAD, W.logits));
+    TRY(ln("dec.ln", W.dec_ln));
+  } else {
+    TRY(v.folded("dec.logits", "dec.tok_emb", "", "dec.ln", NV, d, W_FRAG_PAD, W.logits));
+    if (with_plain) {
+      // the explicit order: final LayerNorm as a kernel, then the tied embedding itself (fragment-major copy)
+      W.logits_p = shaped(NV, d);
+      TRY(v.plain("dec.logits.wp", {NV, d}, &W.logits_p.w, W_FRAG_PAD, "dec.tok_emb"));
+      TRY(ln("dec.ln", W.dec_ln));
+    }
+  }
+#undef TRY
+  return FW_OK;
+}
+
+// ---------------------------------------------------------------- blob packing
+// The tensor as stored fragment-major; pad_rows: N is padded to a whole tile with zero rows (dims[0] = the stored extent).
+static int to_frag_major(PackItem& it, bool pad_rows) {
+  const int64_t N = it.dims[0], K = it.dims[1], KE = it.dtype == 2 ? 64 : 32;
+  if ((!pad_rows && N % 32) || K % KE) {
+    set_error("fragment-major packing needs N %% 32 == 0 and K %% %lld == 0 (%s is %lld x %lld)", (long long)KE,
+              it.name.c_str(), (long long)N, (long long)K);
+    return FW_EINVAL;
+  }
+  const int64_t NP = stored_rows(N, W_FRAG);
+  it.dims[0] = NP;
+  auto permute = [&](auto& v) {
+    std::remove_reference_t<decltype(v)> src;
+    src.swap(v);
+    v.assign((size_t)NP * K, 0);
+    for (int64_t n = 0; n < N; ++n)
+      for (int64_t k = 0; k < K; ++k) v[frag_pos(n, k, K, (int)KE)] = src[n * K + k];
+  };
+  if (it.dtype == 2) permute(it.qdata); else permute(it.data);
+  return FW_OK;
+}
+
+// The packing visitor of the weight list: builds every tensor, in its final kernel layout, from the caller's weights.
+struct Packer {
+  const fw_weight* w;
+  int nw;
   std::vector<PackItem> items;
-  auto add_plain = [&](const std::string& name, std::initializer_list<int64_t> dims) -> int {
-    const fw_weight* t = find_w(w, nw, name);
-    int rc = expect_shape(t, name, dims);
-    if (rc) return rc;
-    PackItem it;
-    it.name = name;
-    it.ndim = (int)dims.size();
-    int i = 0;
-    for (int64_t x : dims) it.dims[i++] = x;
-    for (; i < 4; ++i) it.dims[i] = 1;
-    to_f16(t, it.data);
+  int source(const std::string& name, std::initializer_list<int64_t> dims, const fw_weight** t) const {
+    *t = find_w(w, nw, name);
+    return expect_shape(*t, name, dims);
+  }
+  int push(PackItem&& it, WForm form) {
+    if (form == W_FRAG || form == W_FRAG_PAD)
+      if (int rc = to_frag_major(it, form == W_FRAG_PAD)) return rc;
     items.push_back(std::move(it));
     return FW_OK;
-  };
-  // conv weights [out][in][3] -> GEMM form [out][tap*cin_pad + cin]
-  auto add_conv = [&](const std::string& name, int cout, int cin, int cin_pad) -> int {
-    const fw_weight* t = find_w(w, nw, name + ".w");
-    int rc = expect_shape(t, name + ".w", {cout, cin, 3});
-    if (rc) return rc;
-    PackItem it;
-    it.name = name + ".wg";
-    it.ndim = 2;
-    it.dims[0] = cout; it.dims[1] = 3 * cin_pad; it.dims[2] = it.dims[3] = 1;
-    it.data.assign((size_t)cout * 3 * cin_pad, 0);
+  }
+  int plain(const std::string& name, std::initializer_list<int64_t> dims, const half_t**, WForm form = W_ROWS,
+            const char* src = nullptr) {
+    const fw_weight* t;
+    if (int rc = source(src ? src : name, dims, &t)) return rc;
+    PackItem it(name, 1, dims);
+    to_f16(t, it.data);
+    if (form == W_TIED_I8) {
+      const int64_t N = it.dims[0], K = it.dims[1];
+      for (int64_t n = 0; n < N; ++n) {
+        float amax = 0.f;
+        for (int64_t k = 0; k < K; ++k) amax = std::max(amax, fabsf(f16_bits_to_f32(it.data[n * K + k])));
+        const float sc = amax > 0.f ? 127.0f / amax : 0.f, ds = amax > 0.f ? amax / 127.0f : 1.0f;
+        for (int64_t k = 0; k < K; ++k)
+          it.data[n * K + k] = f32_to_f16_bits((float)lrintf(f16_bits_to_f32(it.data[n * K + k]) * sc) * ds);
+      }
+    }
+    return push(std::move(it), form);
+  }
+  int conv(const std::string& base, int cout, int cin, int cin_pad, LinearW&) {
+    const fw_weight* t;
+    if (int rc = source(base + ".w", {cout, cin, 3}, &t)) return rc;
+    PackItem it(base + ".wg", 1, {cout, 3 * cin_pad});
     for (int o = 0; o < cout; ++o)
       for (int c = 0; c < cin; ++c)
         for (int k = 0; k < 3; ++k)
           it.data[(size_t)o * 3 * cin_pad + (size_t)k * cin_pad + c] =
               f32_to_f16_bits(w_at(t, ((int64_t)o * cin + c) * 3 + k));
     items.push_back(std::move(it));
-    return add_plain(name + ".b", {cout});
-  };
-  // LayerNorm folded into the consuming linear (decoder rows are few, so the LN kernel would be
-  // pure launch overhead):   y = W (g*(x-mu)*rstd + b) + bias
-  //                            = rstd * ( (W.g) x - mu * s1 ) + cf,   s1 = rowsum(W.g), cf = W b + bias
+    return plain(base + ".b", {cout}, nullptr);
+  }
+  // LayerNorm folded into the consuming linear:   y = W (g*(x-mu)*rstd + b) + bias
+  //                                                 = rstd * ( (W.g) x - mu * s1 ) + cf,   s1 = rowsum(W.g), cf = W b + bias
   // emits  <out>.wf [N][K] fp16 (W.g),  <out>.s1 [N] f32,  <out>.cf [N] f32
-  auto add_folded = [&](const std::string& out, const std::string& wname, const std::string& bname,
-                        const std::string& gname, const std::string& lbname, int N, int K) -> int {
-    const fw_weight* W = find_w(w, nw, wname);
-    const fw_weight* G = find_w(w, nw, gname);
-    const fw_weight* LB = find_w(w, nw, lbname);
-    const fw_weight* Bi = bname.empty() ? nullptr : find_w(w, nw, bname);
-    int rc = expect_shape(W, wname, {N, K});
-    if (rc) return rc;
-    if ((rc = expect_shape(G, gname, {K}))) return rc;
-    if ((rc = expect_shape(LB, lbname, {K}))) return rc;
-    if (!bname.empty() && (rc = expect_shape(Bi, bname, {N}))) return rc;
+  int folded(const std::string& out, const std::string& wname, const std::string& bname, const std::string& ln, int N,
+             int K, WForm form, LinearW&) {
+    const fw_weight *W, *G, *LB, *Bi = nullptr;
+    int rc;
+    if ((rc = source(wname, {N, K}, &W)) || (rc = source(ln + ".g", {K}, &G)) || (rc = source(ln + ".b", {K}, &LB)) ||
+        (!bname.empty() && (rc = source(bname, {N}, &Bi))))
+      return rc;
     std::vector<float> g(K), lb(K);
     for (int k = 0; k < K; ++k) {
       g[k] = f16_bits_to_f32(f32_to_f16_bits(w_at(G, k)));
       lb[k] = f16_bits_to_f32(f32_to_f16_bits(w_at(LB, k)));
     }
-    PackItem wf, s1, cf;
-    wf.name = out + ".wf"; wf.ndim = 2; wf.dims[0] = N; wf.dims[1] = K; wf.dims[2] = wf.dims[3] = 1;
-    wf.data.resize((size_t)N * K);
-    s1.name = out + ".s1"; s1.ndim = 1; s1.dims[0] = N; s1.dims[1] = s1.dims[2] = s1.dims[3] = 1; s1.dtype = 0;
-    cf.name = out + ".cf"; cf.ndim = 1; cf.dims[0] = N; cf.dims[1] = cf.dims[2] = cf.dims[3] = 1; cf.dtype = 0;
-    s1.fdata.resize(N); cf.fdata.resize(N);
+    PackItem wf(out + ".wf", 1, {N, K}), s1(out + ".s1", 0, {N}), cf(out + ".cf", 0, {N});
     for (int n = 0; n < N; ++n) {
       double a1 = 0.0, ac = 0.0;
       for (int k = 0; k < K; ++k) {
@@ -268,154 +423,36 @@ static int pack_blob(const fw_config* cfg, const fw_weight* w, int nw, int compu
       s1.fdata[n] = (float)a1;
       cf.fdata[n] = (float)ac;
     }
-    items.push_back(std::move(wf)); items.push_back(std::move(s1)); items.push_back(std::move(cf));
+    if ((rc = push(std::move(wf), form))) return rc;
+    items.push_back(std::move(s1));
+    items.push_back(std::move(cf));
     return FW_OK;
-  };
+  }
   // int8_float16 (K25, [CT2-ext] CTranslate2 convention): per output row n, scale = 127 / absmax(W[n,:]),
   // Wq = rint(W * scale) (round-half-even); the engine stores the DE-quantisation factor absmax / 127.
   // emits <out>.wq [N][K] int8 and <out>.ws [N] f32
-  auto add_quant = [&](const std::string& out, const std::string& wname, int N, int K) -> int {
-    const fw_weight* W = find_w(w, nw, wname);
-    int rc = expect_shape(W, wname, {N, K});
-    if (rc) return rc;
-    PackItem wq, ws;
-    wq.name = out + ".wq"; wq.ndim = 2; wq.dims[0] = N; wq.dims[1] = K; wq.dims[2] = wq.dims[3] = 1; wq.dtype = 2;
-    ws.name = out + ".ws"; ws.ndim = 1; ws.dims[0] = N; ws.dims[1] = ws.dims[2] = ws.dims[3] = 1; ws.dtype = 0;
-    wq.qdata.resize((size_t)N * K);
-    ws.fdata.resize(N);
+  int quant(const std::string& out, const std::string& wname, int N, int K, WForm form, LinearW&) {
+    const fw_weight* W;
+    if (int rc = source(wname, {N, K}, &W)) return rc;
+    PackItem wq(out + ".wq", 2, {N, K}), ws(out + ".ws", 0, {N});
     std::vector<float> row(K);
     for (int n = 0; n < N; ++n) {
       for (int k = 0; k < K; ++k) row[k] = f16_bits_to_f32(f32_to_f16_bits(w_at(W, (int64_t)n * K + k)));
       ws.fdata[n] = quant_row_i8(row.data(), K, wq.qdata.data(), [&](int k) { return (size_t)n * K + k; });
     }
-    items.push_back(std::move(wq)); items.push_back(std::move(ws));
+    if (int rc = push(std::move(wq), form)) return rc;
+    items.push_back(std::move(ws));
     return FW_OK;
-  };
-  const bool i8 = compute_type == FW_COMPUTE_INT8_FLOAT16;
-  // a linear layer: fp16 weight (+bias), or int8 weight + scale (+ fp16 bias) in int8_float16 mode
-  auto add_linear = [&](const std::string& base, int N, int K) -> int {
-    int rc = i8 ? add_quant(base, base + ".w", N, K) : add_plain(base + ".w", {N, K});
-    if (rc) return rc;
-    return add_plain(base + ".b", {N});
-  };
-  // a decoder linear fed by a LayerNorm: folded in fp16 mode; explicit LN (quantised output) in int8 mode
-  // FWAMD_LN_UNFOLD (a diagnostic, default off: DESIGN.md section 5) set at PACK time: the fp16 blob then also carries
-  // the plain weights + LayerNorms of qkv / cross.q / ffn1 / the vocabulary projection (+1 GB at large-v3) for the
-  // explicit-LayerNorm evaluation order; without it only the folded forms travel
-  const char* lu_env = getenv("FWAMD_LN_UNFOLD");
-  const char* pp_env = getenv("FWAMD_PACK_PLAIN");   // (the probe packs once and creates models in all three orders)
-  const bool with_plain = (lu_env && (lu_env[0] == '1' || lu_env[0] == '2') && !lu_env[1]) || (pp_env && pp_env[0] == '1');
-  auto add_ln_linear = [&](const std::string& base, const std::string& ln, int N, int K) -> int {
-    if (!i8) {
-      int rc = add_folded(base, base + ".w", base + ".b", ln + ".g", ln + ".b", N, K);
-      if (rc || !with_plain) return rc;
-    }
-    int rc = add_linear(base, N, K);
-    if (rc) return rc;
-    if ((rc = add_plain(ln + ".g", {K}))) return rc;
-    return add_plain(ln + ".b", {K});
-  };
-  int rc;
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
-  TRY(add_conv("enc.conv1", d, nm, c_pad));
-  TRY(add_conv("enc.conv2", d, d, d));
-  TRY(add_plain("enc.pos", {cfg->n_audio_ctx, d}));
-  char nb[96];
-  for (int i = 0; i < cfg->n_enc_layers; ++i) {
-    auto nmf = [&](const char* s) { snprintf(nb, sizeof(nb), "enc.%d.%s", i, s); return std::string(nb); };
-    TRY(add_plain(nmf("ln1.g"), {d})); TRY(add_plain(nmf("ln1.b"), {d}));
-    TRY(add_linear(nmf("attn.qkv"), 3 * d, d));
-    TRY(add_linear(nmf("attn.out"), d, d));
-    TRY(add_plain(nmf("ln2.g"), {d})); TRY(add_plain(nmf("ln2.b"), {d}));
-    TRY(add_linear(nmf("ffn1"), 4 * d, d));
-    TRY(add_linear(nmf("ffn2"), d, 4 * d));
   }
-  TRY(add_plain("enc.ln_post.g", {d})); TRY(add_plain("enc.ln_post.b", {d}));
-  TRY(add_plain("dec.tok_emb", {cfg->n_vocab, d}));
-  if (i8) {
-    // [CT2-ext] the token embedding shares the int8 projection weight: a lookup returns the de-quantised row
-    PackItem& te = items.back();
-    const int64_t K = d;
-    for (int64_t n = 0; n < cfg->n_vocab; ++n) {
-      float amax = 0.f;
-      for (int64_t k = 0; k < K; ++k) amax = std::max(amax, fabsf(f16_bits_to_f32(te.data[n * K + k])));
-      const float sc = amax > 0.f ? 127.0f / amax : 0.f, ds = amax > 0.f ? amax / 127.0f : 1.0f;
-      for (int64_t k = 0; k < K; ++k)
-        te.data[n * K + k] = f32_to_f16_bits((float)lrintf(f16_bits_to_f32(te.data[n * K + k]) * sc) * ds);
-    }
-  }
-  TRY(add_plain("dec.pos", {cfg->n_text_ctx, d}));
-  for (int i = 0; i < cfg->n_dec_layers; ++i) {
-    auto nmf = [&](const char* s) { snprintf(nb, sizeof(nb), "dec.%d.%s", i, s); return std::string(nb); };
-    // the three LayerNorms of a decoder block are folded into the linear that consumes them
-    TRY(add_ln_linear(nmf("self.qkv"), nmf("ln1"), 3 * d, d));
-    TRY(add_linear(nmf("self.out"), d, d));
-    TRY(add_ln_linear(nmf("cross.q"), nmf("ln2"), d, d));
-    TRY(add_linear(nmf("cross.kv"), 2 * d, d));
-    TRY(add_linear(nmf("cross.out"), d, d));
-    TRY(add_ln_linear(nmf("ffn1"), nmf("ln3"), 4 * d, d));
-    TRY(add_linear(nmf("ffn2"), d, 4 * d));
-  }
-  if (i8) {
-    TRY(add_quant("dec.logits", "dec.tok_emb", cfg->n_vocab, d));
-    TRY(add_plain("dec.ln.g", {d})); TRY(add_plain("dec.ln.b", {d}));
-  } else {
-    TRY(add_folded("dec.logits", "dec.tok_emb", "", "dec.ln.g", "dec.ln.b", cfg->n_vocab, d));
-    if (with_plain) {
-      // the explicit order: final LayerNorm as a kernel, then the tied embedding itself (fragment-major copy)
-      TRY(add_plain("dec.tok_emb", {cfg->n_vocab, d}));
-      items.back().name = "dec.logits.wp";
-      TRY(add_plain("dec.ln.g", {d})); TRY(add_plain("dec.ln.b", {d}));
-    }
-  }
-#undef TRY
+};
 
-  // Fragment-major decoder linears (dec_kernels.hip): the 16 bytes lane l feeds to the MFMA for k-step ks of
-  // column tile nt sit at ((nt*KS + ks)*64 + l)*16 B, i.e. element W[n][k] moves to
-  //   fp16: ((n/16 * K/32 + k/32) * 64 + 16*((k/8)%4)  + n%16) * 8  + k%8     (32 elements per k-step)
-  //   int8: ((n/16 * K/64 + k/64) * 64 + 16*((k/16)%4) + n%16) * 16 + k%16    (64 elements per k-step)
-  // The six per-layer linears and the vocabulary projection are stored this way (the projection's N is padded
-  // to a whole tile with zero rows); the big "many rows" GEMM (cross.kv) keeps [N][K].
-  for (PackItem& it : items) {
-    const std::string& nm = it.name;
-    if (nm.compare(0, 4, "dec.") != 0 || it.ndim != 2 || it.dtype != (i8 ? 2 : 1)) continue;
-    auto ends = [&](const char* suf) {
-      const size_t n = strlen(suf);
-      return nm.size() >= n && nm.compare(nm.size() - n, n, suf) == 0;
-    };
-    const bool hit = i8 ? (ends("self.qkv.wq") || ends("self.out.wq") || ends("cross.q.wq") || ends("cross.out.wq") ||
-                           ends("ffn1.wq") || ends("ffn2.wq") || nm == "dec.logits.wq")
-                        : (ends("self.qkv.wf") || ends("self.out.w") || ends("cross.q.wf") || ends("cross.out.w") ||
-                           ends("ffn1.wf") || ends("ffn2.w") || nm == "dec.logits.wf" || ends("self.qkv.w") ||
-                           ends("cross.q.w") || ends("ffn1.w") || nm == "dec.logits.wp");
-    if (!hit) continue;
-    const int64_t N = it.dims[0], K = it.dims[1], KE = i8 ? 64 : 32, OCT = KE / 4;
-    const bool logits = nm.compare(0, 10, "dec.logits") == 0;
-    if ((!logits && N % 32) || K % KE) {
-      set_error("fragment-major packing needs N %% 32 == 0 and K %% %lld == 0 (%s is %lld x %lld)", (long long)KE,
-                nm.c_str(), (long long)N, (long long)K);
-      return FW_EINVAL;
-    }
-    const int64_t NP = (N + 15) / 16 * 16, KS = K / KE;
-    it.dims[0] = NP;   // the stored extent (padding rows are zero)
-    auto at = [&](int64_t n, int64_t k) {
-      return (((n >> 4) * KS + k / KE) * 64 + ((k / OCT) & 3) * 16 + (n & 15)) * OCT + (k % OCT);
-    };
-    if (i8) {
-      std::vector<int8_t> src;
-      src.swap(it.qdata);
-      it.qdata.assign((size_t)NP * K, 0);
-      for (int64_t n = 0; n < N; ++n)
-        for (int64_t k = 0; k < K; ++k) it.qdata[at(n, k)] = src[n * K + k];
-    } else {
-      std::vector<uint16_t> src;
-      src.swap(it.data);
-      it.data.assign((size_t)NP * K, 0);
-      for (int64_t n = 0; n < N; ++n)
-        for (int64_t k = 0; k < K; ++k) it.data[at(n, k)] = src[n * K + k];
-    }
-  }
-
+// Build the device blob image on the host: all tensors in their final kernel layouts.
+static int pack_blob(const fw_config* cfg, const fw_weight* w, int nw, int compute_type,
+                     std::vector<uint8_t>& blob) {
+  Packer pk{w, nw, {}};
+  Weights unbound;
+  if (int rc = walk_weights(*cfg, compute_type == FW_COMPUTE_INT8_FLOAT16, env_pack_plain(), unbound, pk)) return rc;
+  const std::vector<PackItem>& items = pk.items;
   const int64_t hdr = (int64_t)sizeof(BlobHeader) + (int64_t)items.size() * sizeof(BlobEntry);
   int64_t off = (hdr + 255) / 256 * 256;
   std::vector<BlobEntry> entries(items.size());
@@ -438,15 +475,92 @@ static int pack_blob(const fw_config* cfg, const fw_weight* w, int nw, int compu
   h.n_tensors = (int32_t)items.size();
   h.total_bytes = off;
   h.compute_type = compute_type;
-  h.reserved = 6;   // layout generation: 4 = decoder linears and the vocabulary projection fragment-major; 5 = fp16
-                    // blobs carry the plain (LayerNorm-explicit) forms of qkv / cross.q / ffn1 / logits next to the folded
-                    // ones; 6 = only when packed with FWAMD_LN_UNFOLD set
+  h.reserved = kBlobGeneration;
   h.cfg = *cfg;
   memcpy(blob.data(), &h, sizeof(h));
   memcpy(blob.data() + sizeof(h), entries.data(), entries.size() * sizeof(BlobEntry));
   for (size_t i = 0; i < items.size(); ++i)
     memcpy(blob.data() + entries[i].offset, items[i].bytes(), (size_t)entries[i].nbytes);
   return FW_OK;
+}
+
+// ---------------------------------------------------------------- blob checking and binding
+// layout generation (BlobHeader::reserved): 4 = decoder linears and the vocabulary projection fragment-major; 5 = fp16
+// blobs carry the plain (LayerNorm-explicit) forms of qkv / cross.q / ffn1 / logits next to the folded ones; 6 = only
+// when packed with FWAMD_LN_UNFOLD set
+int check_blob_header(const BlobHeader& h, int64_t blob_bytes) {
+  FW_CHECK_ARG(memcmp(h.magic, FW_BLOB_MAGIC, 8) == 0 && h.version == 1, "bad weight blob magic/version");
+  FW_CHECK_ARG(h.total_bytes <= blob_bytes, "weight blob truncated (%lld > %lld)", (long long)h.total_bytes,
+               (long long)blob_bytes);
+  FW_CHECK_ARG(h.n_tensors >= 0 && (int64_t)sizeof(h) + h.n_tensors * (int64_t)sizeof(BlobEntry) <= h.total_bytes,
+               "weight blob: %d tensor entries do not fit its %lld bytes", h.n_tensors, (long long)h.total_bytes);
+  if (int rc = check_config(&h.cfg)) return rc;
+  FW_CHECK_ARG(h.compute_type == FW_COMPUTE_FLOAT16 || h.compute_type == FW_COMPUTE_INT8_FLOAT16,
+               "unsupported compute type %d", h.compute_type);
+  FW_CHECK_ARG(h.reserved == kBlobGeneration,
+               "weight blob was packed by an older libfwamd (layout generation %d, expected %d): repack it", h.reserved,
+               kBlobGeneration);
+  return FW_OK;
+}
+
+// The binding visitor of the weight list: every tensor is looked up in the blob's entries and compared with what the
+// list says of it BEFORE a pointer into the blob is formed.
+struct Binder {
+  const BlobHeader& h;
+  char* blob;
+  std::map<std::string, const BlobEntry*> by_name;
+  template <typename T>
+  int get(const std::string& name, int dtype, std::initializer_list<int64_t> dims, const T** out) const {
+    auto it = by_name.find(name);
+    FW_CHECK_ARG(it != by_name.end(), "weight blob lacks tensor '%s'", name.c_str());
+    const BlobEntry& e = *it->second;
+    const char* nm = name.c_str();
+    FW_CHECK_ARG(e.dtype == dtype, "weight blob tensor '%s': dtype %d, expected %d", nm, e.dtype, dtype);
+    FW_CHECK_ARG(e.ndim == (int)dims.size(), "weight blob tensor '%s': %d dims, expected %zu", nm, e.ndim, dims.size());
+    int64_t bytes = dtype == 1 ? 2 : dtype == 2 ? 1 : 4;
+    int i = 0;
+    for (int64_t x : dims) {
+      FW_CHECK_ARG(e.dims[i] == x, "weight blob tensor '%s': dim %d is %lld, expected %lld", nm, i, (long long)e.dims[i],
+                   (long long)x);
+      bytes *= x;
+      ++i;
+    }
+    FW_CHECK_ARG(e.nbytes == bytes, "weight blob tensor '%s': %lld bytes, its shape has %lld", nm, (long long)e.nbytes,
+                 (long long)bytes);
+    FW_CHECK_ARG(e.offset >= 0 && e.offset % 256 == 0 && e.offset <= h.total_bytes - bytes,
+                 "weight blob tensor '%s': offset %lld (%lld bytes) misaligned or outside the blob's %lld bytes", nm,
+                 (long long)e.offset, (long long)bytes, (long long)h.total_bytes);
+    *out = reinterpret_cast<const T*>(blob + e.offset);
+    return FW_OK;
+  }
+  int plain(const std::string& name, std::initializer_list<int64_t> dims, const half_t** dst, WForm form = W_ROWS,
+            const char* = nullptr) const {
+    if (dims.size() != 2) return get(name, 1, dims, dst);
+    return get(name, 1, {stored_rows(dims.begin()[0], form), dims.begin()[1]}, dst);
+  }
+  int conv(const std::string& base, int cout, int, int cin_pad, LinearW& L) const {
+    if (int rc = get(base + ".wg", 1, {cout, 3 * cin_pad}, &L.w)) return rc;
+    return get(base + ".b", 1, {cout}, &L.b);
+  }
+  int folded(const std::string& out, const std::string&, const std::string&, const std::string&, int N, int K,
+             WForm form, LinearW& L) const {
+    int rc;
+    if ((rc = get(out + ".wf", 1, {stored_rows(N, form), K}, &L.w)) || (rc = get(out + ".s1", 0, {N}, &L.s1))) return rc;
+    return get(out + ".cf", 0, {N}, &L.cf);
+  }
+  int quant(const std::string& out, const std::string&, int N, int K, WForm form, LinearW& L) const {
+    if (int rc = get(out + ".wq", 2, {stored_rows(N, form), K}, &L.wq)) return rc;
+    return get(out + ".ws", 0, {N}, &L.wscale);
+  }
+};
+
+int bind_weights(const BlobHeader& h, const BlobEntry* entries, void* blob, Weights& W, bool* has_plain) {
+  Binder b{h, reinterpret_cast<char*>(blob), {}};
+  for (int i = 0; i < h.n_tensors; ++i)
+    b.by_name[std::string(entries[i].name, strnlen(entries[i].name, sizeof(entries[i].name)))] = &entries[i];
+  const bool i8 = h.compute_type == FW_COMPUTE_INT8_FLOAT16;
+  *has_plain = !i8 && b.by_name.count("dec.logits.wp") != 0;   // packed with FWAMD_LN_UNFOLD: the explicit-LayerNorm forms travel too
+  return walk_weights(h.cfg, i8, *has_plain, W, b);
 }
 
 // ---------------------------------------------------------------- mel constants
@@ -496,173 +610,33 @@ static int setup_logmel_consts(Model* m) {
   for (int i = 0; i < m->cfg.n_mels; ++i)
     for (int k = 0; k < 201; ++k) filtT[(size_t)k * m->lm_mel_pad + i] = filt[(size_t)i * 201 + k];
   int rc;
-  if ((rc = dev_alloc_t(&m->lm_consts, 800))) return rc;
-  if ((rc = dev_alloc_t(&m->lm_filtT, filtT.size()))) return rc;
+  if ((rc = m->bufs.alloc(&m->lm_consts, 800)) || (rc = m->bufs.alloc(&m->lm_filtT, filtT.size()))) return rc;
   FW_HIP(hipMemcpy(m->lm_consts, consts.data(), 800 * sizeof(float), hipMemcpyHostToDevice));
   FW_HIP(hipMemcpy(m->lm_filtT, filtT.data(), filtT.size() * sizeof(float), hipMemcpyHostToDevice));
   return FW_OK;
 }
 
 // ---------------------------------------------------------------- model construction
-std::mutex& g_models_mu_ref();
-std::vector<Model*>& g_live_models_ref();
-static const half_t* tptr(Model* m, const std::string& name) {
-  auto it = m->tensors.find(name);
-  return it == m->tensors.end() ? nullptr : reinterpret_cast<const half_t*>(it->second.ptr);
-}
-
-static int bind_weights(Model* m) {
-  const fw_config& c = m->cfg;
-  const int d = c.d_model;
-  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
-  m->c_pad = ((c.n_mels + 63) / 64) * 64;
-  auto need = [&](const std::string& n, const half_t** out) -> int {
-    *out = tptr(m, n);
-    if (!*out) {
-      set_error("weight blob lacks tensor '%s'", n.c_str());
-      return FW_EINVAL;
-    }
-    return FW_OK;
-  };
-  auto need_f = [&](const std::string& n, const float** out) -> int {
-    const half_t* p = nullptr;
-    int r = need(n, &p);
-    *out = reinterpret_cast<const float*>(p);
-    return r;
-  };
-  // a linear: fp16 (<base>.w) or int8 (<base>.wq + <base>.ws); bias <base>.b.  rows [r0, r0+N) of the stored matrix
-  auto linear = [&](const std::string& base, LinearW* L, int N, int K, int r0) -> int {
-    int r;
-    *L = LinearW();
-    L->N = N; L->K = K;
-    if (i8) {
-      const half_t* q = nullptr;
-      if ((r = need(base + ".wq", &q))) return r;
-      L->wq = reinterpret_cast<const int8_t*>(q) + (size_t)r0 * K;
-      if ((r = need_f(base + ".ws", &L->wscale))) return r;
-      L->wscale += r0;
-    } else {
-      if ((r = need(base + ".w", &L->w))) return r;
-      L->w += (size_t)r0 * K;
-    }
-    if ((r = need(base + ".b", &L->b))) return r;
-    L->b += r0;
-    return FW_OK;
-  };
-  auto folded = [&](const std::string& base, LinearW* L, int N, int K) -> int {
-    int r;
-    *L = LinearW();
-    if ((r = need(base + ".wf", &L->w))) return r;
-    if ((r = need_f(base + ".s1", &L->s1))) return r;
-    if ((r = need_f(base + ".cf", &L->cf))) return r;
-    L->N = N; L->K = K;
-    return FW_OK;
-  };
-  auto ln = [&](const std::string& base, LNW* L) -> int {
-    int r;
-    if ((r = need(base + ".g", &L->g))) return r;
-    return need(base + ".b", &L->b);
-  };
-  int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
-  TRY(need("enc.conv1.wg", &m->conv1.w)); TRY(need("enc.conv1.b", &m->conv1.b));
-  m->conv1.N = d; m->conv1.K = 3 * m->c_pad;
-  TRY(need("enc.conv2.wg", &m->conv2.w)); TRY(need("enc.conv2.b", &m->conv2.b));
-  m->conv2.N = d; m->conv2.K = 3 * d;
-  TRY(need("enc.pos", &m->enc_pos));
-  m->enc.resize(c.n_enc_layers);
-  char nb[96];
-  for (int i = 0; i < c.n_enc_layers; ++i) {
-    EncLayerW& L = m->enc[i];
-    auto nm = [&](const char* s) { snprintf(nb, sizeof(nb), "enc.%d.%s", i, s); return std::string(nb); };
-    TRY(ln(nm("ln1"), &L.ln1));
-    TRY(linear(nm("attn.qkv"), &L.qk, 2 * d, d, 0));
-    TRY(linear(nm("attn.qkv"), &L.v, d, d, 2 * d));
-    TRY(linear(nm("attn.out"), &L.out, d, d, 0));
-    TRY(ln(nm("ln2"), &L.ln2));
-    TRY(linear(nm("ffn1"), &L.ffn1, 4 * d, d, 0));
-    TRY(linear(nm("ffn2"), &L.ffn2, d, 4 * d, 0));
-  }
-  TRY(ln("enc.ln_post", &m->enc_ln_post));
-  TRY(need("dec.tok_emb", &m->tok_emb)); TRY(need("dec.pos", &m->dec_pos));
-  m->dec.resize(c.n_dec_layers);
-  m->has_plain = !i8 && tptr(m, "dec.logits.wp") != nullptr;
-  for (int i = 0; i < c.n_dec_layers; ++i) {
-    DecLayerW& L = m->dec[i];
-    auto nm = [&](const char* s) { snprintf(nb, sizeof(nb), "dec.%d.%s", i, s); return std::string(nb); };
-    if (i8) {
-      TRY(ln(nm("ln1"), &L.ln1)); TRY(ln(nm("ln2"), &L.ln2)); TRY(ln(nm("ln3"), &L.ln3));
-      TRY(linear(nm("self.qkv"), &L.qkv, 3 * d, d, 0));
-      TRY(linear(nm("cross.q"), &L.cq, d, d, 0));
-      TRY(linear(nm("ffn1"), &L.ffn1, 4 * d, d, 0));
-    } else {
-      TRY(folded(nm("self.qkv"), &L.qkv, 3 * d, d));
-      TRY(folded(nm("cross.q"), &L.cq, d, d));
-      TRY(folded(nm("ffn1"), &L.ffn1, 4 * d, d));
-      if (m->has_plain) {   // packed with FWAMD_LN_UNFOLD: the explicit-LayerNorm forms travel too
-        TRY(ln(nm("ln1"), &L.ln1)); TRY(ln(nm("ln2"), &L.ln2)); TRY(ln(nm("ln3"), &L.ln3));
-        TRY(linear(nm("self.qkv"), &L.qkv_p, 3 * d, d, 0));
-        TRY(linear(nm("cross.q"), &L.cq_p, d, d, 0));
-        TRY(linear(nm("ffn1"), &L.ffn1_p, 4 * d, d, 0));
-      }
-    }
-    TRY(linear(nm("self.out"), &L.out, d, d, 0));
-    TRY(linear(nm("cross.kv"), &L.ck, d, d, 0));
-    TRY(linear(nm("cross.kv"), &L.cv, d, d, d));
-    TRY(linear(nm("cross.out"), &L.cout, d, d, 0));
-    TRY(linear(nm("ffn2"), &L.ffn2, d, 4 * d, 0));
-  }
-  if (i8) {
-    const half_t* q = nullptr;
-    m->logits = LinearW();
-    TRY(need("dec.logits.wq", &q));
-    m->logits.wq = reinterpret_cast<const int8_t*>(q);
-    TRY(need_f("dec.logits.ws", &m->logits.wscale));
-    m->logits.N = c.n_vocab; m->logits.K = d;
-    TRY(ln("dec.ln", &m->dec_ln));
-  } else {
-    TRY(folded("dec.logits", &m->logits, c.n_vocab, d));
-    m->logits_p = LinearW();
-    if (m->has_plain) {
-      TRY(need("dec.logits.wp", &m->logits_p.w));
-      m->logits_p.N = c.n_vocab; m->logits_p.K = d;
-      TRY(ln("dec.ln", &m->dec_ln));
-    }
-  }
-#undef TRY
-  return FW_OK;
-}
+// live models, for the two ties between them (Model::dependents): a borrowed blob and a joined decoder
+static std::mutex g_models_mu;
+static std::vector<Model*> g_live_models;
 
 static int alloc_workspaces(Model* m) {
   const fw_config& c = m->cfg;
   const size_t B = m->max_batch, d = c.d_model, T = c.n_audio_ctx;
   m->t_pad = ((c.n_audio_ctx + 63) / 64) * 64;  // 1536
+  DevBufs& db = m->bufs;
+  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
   int rc;
-#define A(p, n) do { if ((rc = dev_alloc_t(&(p), (n)))) return rc; } while (0)
-  A(m->ws_offsets, B + 1);
-  A(m->ws_chunk_max, B);
-  A(m->ws_nframes, B);
-  m->ws_raw_cap = (int64_t)B * c.n_mels * 3008;
-  A(m->ws_raw, (size_t)m->ws_raw_cap);
-  A(m->ws_feat32, B * c.n_mels * 3000);
-  A(m->ws_mel_cl, B * 3002 * m->c_pad);
-  A(m->ws_conv1, B * 3002 * d);
-  A(m->ws_x, B * T * d);
-  A(m->ws_x2, B * T * d);
-  A(m->ws_xn, B * T * d);
-  A(m->ws_qk, B * T * 2 * d);
-  A(m->ws_vt, B * d * m->t_pad);
-  A(m->ws_att, B * T * d);
-  A(m->ws_ffn, B * T * 4 * d);
-  if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
-    A(m->ws_xq, B * T * 4 * d);
-    A(m->ws_xs, B * T);
-  }
-#undef A
-  // conv padding rows / V^T time padding must be zero and are never written again
-  FW_HIP(hipMemset(m->ws_conv1, 0, B * 3002 * d * sizeof(half_t)));
-  FW_HIP(hipMemset(m->ws_vt, 0, B * d * m->t_pad * sizeof(half_t)));
-  FW_HIP(hipMemset(m->ws_mel_cl, 0, B * 3002 * m->c_pad * sizeof(half_t)));
+  // conv padding rows / V^T time padding must be zero and are never written again: ws_mel_cl, ws_conv1, ws_vt
+  if ((rc = db.alloc(&m->ws_offsets, B + 1)) || (rc = db.alloc(&m->ws_chunk_max, B)) || (rc = db.alloc(&m->ws_nframes, B)) ||
+      (rc = m->ws_raw.ensure((int64_t)B * c.n_mels * 3008)) || (rc = db.alloc(&m->ws_feat32, B * c.n_mels * 3000)) ||
+      (rc = db.zalloc(&m->ws_mel_cl, B * 3002 * m->c_pad)) || (rc = db.zalloc(&m->ws_conv1, B * 3002 * d)) ||
+      (rc = db.alloc(&m->ws_x, B * T * d)) || (rc = db.alloc(&m->ws_x2, B * T * d)) || (rc = db.alloc(&m->ws_xn, B * T * d)) ||
+      (rc = db.alloc(&m->ws_qk, B * T * 2 * d)) || (rc = db.zalloc(&m->ws_vt, B * d * m->t_pad)) ||
+      (rc = db.alloc(&m->ws_att, B * T * d)) || (rc = db.alloc(&m->ws_ffn, B * T * 4 * d)) ||
+      (i8 && ((rc = db.alloc(&m->ws_xq, B * T * 4 * d)) || (rc = db.alloc(&m->ws_xs, B * T)))))
+    return rc;
   return FW_OK;
 }
 
@@ -674,13 +648,8 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
   FW_CHECK_ARG(blob_bytes >= (int64_t)sizeof(BlobHeader), "weight blob too small");
   BlobHeader h;
   FW_HIP(hipMemcpy(&h, blob_dev, sizeof(h), hipMemcpyDeviceToHost));
-  FW_CHECK_ARG(memcmp(h.magic, FW_BLOB_MAGIC, 8) == 0 && h.version == 1, "bad weight blob magic/version");
-  FW_CHECK_ARG(h.total_bytes <= blob_bytes, "weight blob truncated (%lld > %lld)", (long long)h.total_bytes,
-               (long long)blob_bytes);
-  int rc = check_config(&h.cfg);
+  int rc = check_blob_header(h, blob_bytes);
   if (rc) return rc;
-  FW_CHECK_ARG(h.compute_type == FW_COMPUTE_FLOAT16 || h.compute_type == FW_COMPUTE_INT8_FLOAT16,
-               "unsupported compute type %d", h.compute_type);
   std::vector<BlobEntry> entries(h.n_tensors);
   FW_HIP(hipMemcpy(entries.data(), reinterpret_cast<const char*>(blob_dev) + sizeof(h),
                    entries.size() * sizeof(BlobEntry), hipMemcpyDeviceToHost));
@@ -690,40 +659,25 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
   m->lanes.emplace_back(new DecodeLane());
   m->cfg = h.cfg;
   m->compute_type = h.compute_type;
-  if (h.reserved != 6) {
-    delete fm;
-    set_error("weight blob was packed by an older libfwamd (layout generation %d, expected 6): repack it", h.reserved);
-    return FW_EINVAL;
-  }
   m->device = device;
   m->max_batch = max_batch;
   m->max_beam = max_beam;
   m->blob = const_cast<void*>(blob_dev);
   m->blob_owned = owned;
   m->blob_bytes = blob_bytes;
-  for (auto& e : entries) {
-    DevTensor t;
-    t.ptr = reinterpret_cast<char*>(m->blob) + e.offset;
-    t.dtype = e.dtype;
-    t.ndim = e.ndim;
-    for (int k = 0; k < 4; ++k) t.dims[k] = e.dims[k];
-    m->tensors[e.name] = t;
-  }
+  m->enc_pool = std::make_shared<EncPool>(m, (size_t)max_batch * h.cfg.n_audio_ctx * h.cfg.d_model);
   auto fail = [&](int code) { fw_model_free(fm); return code; };
   hipError_t he = create_stream(&m->stream, "ENC");
   if (he != hipSuccess) {
     set_error("hipStreamCreate failed: %s", hipGetErrorString(he));
     return fail(FW_ENODEV);
   }
-  if ((rc = bind_weights(m))) return fail(rc);
-  {
-    const char* lu = getenv("FWAMD_LN_UNFOLD");   // fp16 evaluation order of the decoder LayerNorms (engine.h)
-    if (lu && lu[0] >= '0' && lu[0] <= '2' && !lu[1]) m->ln_unfold = lu[0] - '0';
-    if (m->ln_unfold && m->compute_type != FW_COMPUTE_INT8_FLOAT16 && !m->has_plain) {
-      set_error("FWAMD_LN_UNFOLD=%d needs a weight blob packed with FWAMD_LN_UNFOLD set (this one carries the folded forms only)",
-                m->ln_unfold);
-      return fail(FW_EINVAL);
-    }
+  if ((rc = bind_weights(h, entries.data(), m->blob, *m, &m->has_plain))) return fail(rc);
+  m->ln_unfold = env_ln_unfold();   // fp16 evaluation order of the decoder LayerNorms (engine.h)
+  if (m->ln_unfold && m->compute_type != FW_COMPUTE_INT8_FLOAT16 && !m->has_plain) {
+    set_error("FWAMD_LN_UNFOLD=%d needs a weight blob packed with FWAMD_LN_UNFOLD set (this one carries the folded forms only)",
+              m->ln_unfold);
+    return fail(FW_EINVAL);
   }
   if ((rc = setup_logmel_consts(m))) return fail(rc);
   if ((rc = alloc_workspaces(m))) return fail(rc);
@@ -736,11 +690,11 @@ static int model_from_blob(const void* blob_dev, int64_t blob_bytes, bool owned,
   {
     // a model on a borrowed blob (fw_model_create_from_blob_dev on fw_model_blob's pointer) keeps the owner alive:
     // fw_model_free(owner) is deferred until its last dependent is gone
-    std::lock_guard<std::mutex> lk(g_models_mu_ref());
+    std::lock_guard<std::mutex> lk(g_models_mu);
     if (!owned)
-      for (Model* o : g_live_models_ref())
+      for (Model* o : g_live_models)
         if (o->blob == m->blob && o->blob_owned) { m->blob_owner = o; o->dependents += 1; break; }
-    g_live_models_ref().push_back(m);
+    g_live_models.push_back(m);
   }
   m->self = fm;
   *out = fm;
@@ -953,46 +907,66 @@ int run_encoder(Model* m, int B, half_t* out) {
   return FW_OK;
 }
 
+int EncPool::take(half_t** p) {
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (!free.empty()) {
+      *p = free.back();
+      free.pop_back();
+      return FW_OK;
+    }
+  }
+  return dev_alloc_t(p, elems);
+}
+void EncPool::give(half_t* p) {
+  std::unique_lock<std::mutex> lk(mu);
+  if (!closed) { free.push_back(p); return; }
+  lk.unlock();
+  (void)hipFree(p);
+}
+void EncPool::close() {   // fw_model_free: the tensors still out release their buffers themselves
+  std::vector<half_t*> rest;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    closed = true;
+    model.store(nullptr);
+    rest.swap(free);
+  }
+  for (half_t* p : rest) (void)hipFree(p);
+}
+
 static int new_tensor(Model* m, int B, fw_tensor** out) {
   fw_tensor* t = new fw_tensor();
-  t->impl.owner = m;
+  t->impl.pool = m->enc_pool;
   t->impl.B = B;
   t->impl.T = m->cfg.n_audio_ctx;
   t->impl.D = m->cfg.d_model;
   t->impl.id = next_tensor_id();
-  // encoder outputs come from a per-model pool (every buffer holds max_batch rows): hipMalloc/hipFree
-  // synchronise the whole device and would serialise the replicas that share a GPU
-  {
-    std::lock_guard<std::mutex> lk(m->pool_mu);
-    if (!m->enc_pool.empty()) {
-      t->impl.data = m->enc_pool.back();
-      m->enc_pool.pop_back();
-    }
-  }
-  if (!t->impl.data) {
-    int rc = dev_alloc_t(&t->impl.data, (size_t)m->max_batch * t->impl.T * t->impl.D);
-    if (rc) {
-      delete t;
-      return rc;
-    }
+  if (int rc = m->enc_pool->take(&t->impl.data)) {
+    delete t;
+    return rc;
   }
   *out = t;
   return FW_OK;
 }
 
-static std::mutex g_models_mu;
-static std::vector<Model*> g_live_models;
-std::mutex& g_models_mu_ref() { return g_models_mu; }
-std::vector<Model*>& g_live_models_ref() { return g_live_models; }
-
-static int ensure_pcm(Model* m, int64_t n) {
-  if (n <= m->ws_pcm_cap) return FW_OK;
-  if (m->ws_pcm) (void)hipFree(m->ws_pcm);
-  m->ws_pcm = nullptr;
-  m->ws_pcm_cap = 0;
-  int rc = dev_alloc_t(&m->ws_pcm, (size_t)n);
+// the shared tail of the encode entry points: the encoder on the mel image in ws_mel_cl, into a new tensor
+static int encode_to_tensor(Model* m, int B, const char* what, fw_tensor** out) {
+  fw_tensor* t = nullptr;
+  int rc = new_tensor(m, B, &t);
   if (rc) return rc;
-  m->ws_pcm_cap = n;
+  if ((rc = run_encoder(m, B, t->impl.data))) {
+    fw_tensor_free(t);
+    return rc;
+  }
+  hipError_t he = hipStreamSynchronize(m->stream);
+  if (he != hipSuccess) {
+    fw_tensor_free(t);
+    set_error("%s failed: %s", what, hipGetErrorString(he));
+    return FW_ERUNTIME;
+  }
+  prof_collect(m->prof);
+  *out = t;
   return FW_OK;
 }
 
@@ -1009,19 +983,6 @@ static int check_offsets(const int64_t* offsets, int B, int64_t* total, int* max
   return FW_OK;
 }
 
-// raw buffer able to hold [B][n_mels][stride]
-static int ensure_raw(Model* m, int B, int stride) {
-  const int64_t need = (int64_t)B * m->cfg.n_mels * stride;
-  if (need <= m->ws_raw_cap) return FW_OK;
-  (void)hipFree(m->ws_raw);
-  m->ws_raw = nullptr;
-  m->ws_raw_cap = 0;
-  int rc = dev_alloc_t(&m->ws_raw, (size_t)need);
-  if (rc) return rc;
-  m->ws_raw_cap = need;
-  return FW_OK;
-}
-
 // log-mel for B ragged chunks whose PCM already sits at pcm_dev; writes ws_feat32 and/or ws_mel_cl
 static int logmel_batch(Model* m, const float* pcm_dev, const int64_t* offsets_host, int B, bool want_f32,
                         bool want_cl) {
@@ -1030,12 +991,12 @@ static int logmel_batch(Model* m, const float* pcm_dev, const int64_t* offsets_h
   int rc = check_offsets(offsets_host, B, &total, &max_frames);
   if (rc) return rc;
   const int stride = std::max(3008, (max_frames + 7) / 8 * 8);
-  if ((rc = ensure_raw(m, B, stride))) return rc;
+  if ((rc = m->ws_raw.ensure((int64_t)B * m->cfg.n_mels * stride))) return rc;
   FW_HIP(hipMemcpyAsync(m->ws_offsets, offsets_host, (B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, m->stream));
   {
     ProfScope ps(m, PF_LOGMEL, 0, (double)total * 4 + (double)B * m->cfg.n_mels * 3000 * (want_f32 ? 4 : 2));
     fwk::launch_logmel(m->stream, pcm_dev, m->ws_offsets, B, max_frames, m->lm_consts, m->lm_filtT, m->lm_mel_pad,
-                       m->cfg.n_mels, m->ws_raw, (int64_t)m->cfg.n_mels * stride, stride, m->ws_chunk_max, 1, 3000,
+                       m->cfg.n_mels, m->ws_raw.p, (int64_t)m->cfg.n_mels * stride, stride, m->ws_chunk_max, 1, 3000,
                        want_f32 ? m->ws_feat32 : nullptr, want_cl ? m->ws_mel_cl : nullptr, m->c_pad, m->ws_nframes);
   }
   hipError_t he = hipGetLastError();
@@ -1147,16 +1108,10 @@ void fw_model_free(fw_model* fm) {
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   m->lanes.clear();         // (each waits for its stream first)
   cross_pool_free(m);
-  for (half_t* p : m->enc_pool) (void)hipFree(p);
-  m->enc_pool.clear();
-  void* ptrs[] = {m->lm_consts, m->lm_filtT, m->ws_pcm, m->ws_offsets, m->ws_raw, m->ws_chunk_max, m->ws_nframes,
-                  m->ws_feat32, m->ws_mel_cl, m->ws_conv1, m->ws_x, m->ws_x2, m->ws_xn, m->ws_qk, m->ws_vt,
-                  m->ws_att, m->ws_ffn, m->ws_xq, m->ws_xs};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  m->enc_pool->close();
   if (m->blob && m->blob_owned) (void)hipFree(m->blob);
   if (m->stream) (void)hipStreamDestroy(m->stream);
-  delete fm;
+  delete fm;   // (the workspaces go with it: Model::bufs, ws_pcm, ws_raw)
   for (Model* t : release) {
     if (!t) continue;
     bool free_now = false;
@@ -1190,6 +1145,11 @@ int32_t fw_model_info(const fw_model* fm, fw_config* cfg_out, int32_t* compute_t
 
 // rows of the largest decode run of a group (decoder.hip: DEC_RUN_MAX_ROWS)
 #define DEC_GROUP_RUN_ROWS 1600
+// lanes a decode group builds once it holds four encoder batches: two, or FWAMD_DECODE_LANES (1 .. kMaxDecodeLanes)
+static int env_decode_lanes() {
+  const char* e = getenv("FWAMD_DECODE_LANES");
+  return e ? std::min(kMaxDecodeLanes, std::max(1, atoi(e))) : 2;
+}
 
 int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
   FW_CHECK_ARG(fm, "null model");
@@ -1224,9 +1184,7 @@ int32_t fw_model_set_decode_batch(fw_model* fm, int32_t decode_batch) {
   //            positions and a RUN lays it out for its own max_length, so when the budget is short the positions per
   //            row are lowered first (down to 160: a run that asks for more simply holds fewer rows), then the pool.
   int want = std::max(decode_batch, m->max_batch) / m->max_batch * m->max_batch;
-  int lanes_wanted = 2;
-  if (const char* e = getenv("FWAMD_DECODE_LANES")) lanes_wanted = std::min(kMaxDecodeLanes, std::max(1, atoi(e)));
-  const int n_lanes = want >= 4 * m->max_batch ? lanes_wanted : 1;
+  const int n_lanes = want >= 4 * m->max_batch ? env_decode_lanes() : 1;
   const int max_rows = n_lanes >= 2 ? DEC_GROUP_RUN_ROWS : 2048;
   auto lane_of = [&](int pool_chunks) {
     int lc = pool_chunks;
@@ -1290,8 +1248,8 @@ int32_t fw_model_set_decode_lanes(fw_model* fm, int32_t lanes) {
   int have;
   {
     std::lock_guard<std::mutex> gl(dm->grp.mu);     // (the lanes are rebuilt under grp.resizing)
-    have = std::max(2, (int)dm->lanes.size());   // (a group that has not built its second lane yet still takes 2 ...
-    if (const char* e = getenv("FWAMD_DECODE_LANES")) have = std::max(have, std::min(kMaxDecodeLanes, atoi(e)));   // ... or what it will build)
+    // (a group that has not built its further lanes yet still takes 2, or what it will build)
+    have = std::max({2, env_decode_lanes(), (int)dm->lanes.size()});
   }
   FW_CHECK_ARG(lanes >= 1 && lanes <= have, "decode lanes: 1 .. %d", have);
   dm->grp.lanes_enabled.store(lanes);
@@ -1310,19 +1268,19 @@ int32_t fw_model_set_merge_wait(fw_model* fm, int32_t wait_ms, int32_t fill_perc
 
 int32_t fw_model_decode_batch(const fw_model* fm) {
   if (!fm) return 0;
-  const Model* m = fm->impl.decoder ? fm->impl.decoder : &fm->impl;
+  const Model* m = decoder_of(&fm->impl);
   return std::max(m->decode_batch, m->max_batch);
 }
 
 int32_t fw_model_run_capacity(const fw_model* fm) {
   if (!fm) return 0;
-  return lane_chunks_of(fm->impl.decoder ? fm->impl.decoder : &fm->impl);
+  return lane_chunks_of(decoder_of(&fm->impl));
 }
 
 int32_t fw_model_decode_stats(const fw_model* fm, int64_t* runs, int64_t* requests, int64_t* chunks,
                               int32_t* max_run_chunks) {
   FW_CHECK_ARG(fm, "null model");
-  const Model* m = fm->impl.decoder ? fm->impl.decoder : &fm->impl;
+  const Model* m = decoder_of(&fm->impl);
   if (runs) *runs = m->grp.n_runs.load();
   if (requests) *requests = m->grp.n_requests.load();
   if (chunks) *chunks = m->grp.n_chunks.load();
@@ -1363,9 +1321,9 @@ int32_t fw_logmel(fw_model* fm, const float* pcm, const int64_t* offsets, int32_
   int rc = check_offsets(offsets, B, &total, &mf);
   if (rc) return rc;
   FW_CHECK_ARG(total == 0 || pcm, "null pcm");
-  if ((rc = ensure_pcm(m, std::max<int64_t>(total, 1)))) return rc;
-  if (total) FW_HIP(hipMemcpyAsync(m->ws_pcm, pcm, total * sizeof(float), hipMemcpyHostToDevice, m->stream));
-  if ((rc = logmel_batch(m, m->ws_pcm, offsets, B, true, false))) return rc;
+  if ((rc = m->ws_pcm.ensure(std::max<int64_t>(total, 1)))) return rc;
+  if (total) FW_HIP(hipMemcpyAsync(m->ws_pcm.p, pcm, total * sizeof(float), hipMemcpyHostToDevice, m->stream));
+  if ((rc = logmel_batch(m, m->ws_pcm.p, offsets, B, true, false))) return rc;
   FW_HIP(hipMemcpyAsync(out, m->ws_feat32, (size_t)B * m->cfg.n_mels * 3000 * sizeof(float), hipMemcpyDeviceToHost,
                         m->stream));
   if (n_frames_out)
@@ -1384,10 +1342,10 @@ int32_t fw_logmel_full(fw_model* fm, const float* pcm, int64_t n_samples, float*
   std::lock_guard<std::mutex> lk(m->mu);
   FW_HIP(hipSetDevice(m->device));
   int rc;
-  if ((rc = ensure_pcm(m, std::max<int64_t>(n_samples, 1)))) return rc;
-  if (n_samples) FW_HIP(hipMemcpyAsync(m->ws_pcm, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice, m->stream));
+  if ((rc = m->ws_pcm.ensure(std::max<int64_t>(n_samples, 1)))) return rc;
+  if (n_samples) FW_HIP(hipMemcpyAsync(m->ws_pcm.p, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice, m->stream));
   const int stride = (int)((nf + 7) / 8 * 8);
-  if ((rc = ensure_raw(m, 1, std::max(stride, 3008)))) return rc;
+  if ((rc = m->ws_raw.ensure((int64_t)m->cfg.n_mels * std::max(stride, 3008)))) return rc;
   const int rstride = std::max(stride, 3008);
   int64_t offs[2] = {0, n_samples};
   FW_HIP(hipMemcpyAsync(m->ws_offsets, offs, 2 * sizeof(int64_t), hipMemcpyHostToDevice, m->stream));
@@ -1395,8 +1353,8 @@ int32_t fw_logmel_full(fw_model* fm, const float* pcm, int64_t n_samples, float*
   if ((rc = dev_alloc_t(&dout, (size_t)m->cfg.n_mels * nf))) return rc;
   {
     ProfScope ps(m, PF_LOGMEL, 0, (double)n_samples * 4 + (double)m->cfg.n_mels * nf * 4);
-    fwk::launch_logmel(m->stream, m->ws_pcm, m->ws_offsets, 1, (int)nf, m->lm_consts, m->lm_filtT, m->lm_mel_pad,
-                       m->cfg.n_mels, m->ws_raw, (int64_t)m->cfg.n_mels * rstride, rstride, m->ws_chunk_max, 0,
+    fwk::launch_logmel(m->stream, m->ws_pcm.p, m->ws_offsets, 1, (int)nf, m->lm_consts, m->lm_filtT, m->lm_mel_pad,
+                       m->cfg.n_mels, m->ws_raw.p, (int64_t)m->cfg.n_mels * rstride, rstride, m->ws_chunk_max, 0,
                        (int)nf, dout, nullptr, m->c_pad, nullptr);
   }
   hipError_t he = hipMemcpyAsync(out, dout, (size_t)m->cfg.n_mels * nf * sizeof(float), hipMemcpyDeviceToHost,
@@ -1445,42 +1403,12 @@ int32_t fw_encode(fw_model* fm, const float* features, int32_t B, fw_tensor** ou
   FW_HIP(hipMemcpyAsync(m->ws_feat32, features, (size_t)B * m->cfg.n_mels * 3000 * sizeof(float),
                         hipMemcpyHostToDevice, m->stream));
   fwk::launch_features_to_cl(m->stream, m->ws_feat32, B, m->cfg.n_mels, 3000, m->ws_mel_cl, m->c_pad);
-  fw_tensor* t = nullptr;
-  int rc = new_tensor(m, B, &t);
-  if (rc) return rc;
-  if ((rc = run_encoder(m, B, t->impl.data))) {
-    fw_tensor_free(t);
-    return rc;
-  }
-  hipError_t he = hipStreamSynchronize(m->stream);
-  if (he != hipSuccess) {
-    fw_tensor_free(t);
-    set_error("encode failed: %s", hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  prof_collect(m->prof);
-  *out = t;
-  return FW_OK;
+  return encode_to_tensor(m, B, "encode", out);
 }
 
 static int encode_pcm_common(Model* m, const float* pcm_dev, const int64_t* offsets, int B, fw_tensor** out) {
-  int rc;
-  if ((rc = logmel_batch(m, pcm_dev, offsets, B, false, true))) return rc;
-  fw_tensor* t = nullptr;
-  if ((rc = new_tensor(m, B, &t))) return rc;
-  if ((rc = run_encoder(m, B, t->impl.data))) {
-    fw_tensor_free(t);
-    return rc;
-  }
-  hipError_t he = hipStreamSynchronize(m->stream);
-  if (he != hipSuccess) {
-    fw_tensor_free(t);
-    set_error("encode_pcm failed: %s", hipGetErrorString(he));
-    return FW_ERUNTIME;
-  }
-  prof_collect(m->prof);
-  *out = t;
-  return FW_OK;
+  if (int rc = logmel_batch(m, pcm_dev, offsets, B, false, true)) return rc;
+  return encode_to_tensor(m, B, "encode_pcm", out);
 }
 
 int32_t fw_encode_pcm(fw_model* fm, const float* pcm, const int64_t* offsets, int32_t B, fw_tensor** out) {
@@ -1494,9 +1422,9 @@ int32_t fw_encode_pcm(fw_model* fm, const float* pcm, const int64_t* offsets, in
   int rc = check_offsets(offsets, B, &total, &mf);
   if (rc) return rc;
   FW_CHECK_ARG(total == 0 || pcm, "null pcm");
-  if ((rc = ensure_pcm(m, std::max<int64_t>(total, 1)))) return rc;
-  if (total) FW_HIP(hipMemcpyAsync(m->ws_pcm, pcm, total * sizeof(float), hipMemcpyHostToDevice, m->stream));
-  return encode_pcm_common(m, m->ws_pcm, offsets, B, out);
+  if ((rc = m->ws_pcm.ensure(std::max<int64_t>(total, 1)))) return rc;
+  if (total) FW_HIP(hipMemcpyAsync(m->ws_pcm.p, pcm, total * sizeof(float), hipMemcpyHostToDevice, m->stream));
+  return encode_pcm_common(m, m->ws_pcm.p, offsets, B, out);
 }
 
 int32_t fw_encode_pcm_dev(fw_model* fm, const float* pcm_dev, const int64_t* offsets, int32_t B, fw_tensor** out) {
@@ -1523,13 +1451,12 @@ int32_t fw_tensor_to_host(fw_model* fm, const fw_tensor* t, float* out) {
   std::lock_guard<std::mutex> lk(m->mu);
   FW_HIP(hipSetDevice(m->device));
   const size_t n = (size_t)t->impl.B * t->impl.T * t->impl.D;
+  DevBufs db;
   float* tmp = nullptr;
-  int rc = dev_alloc_t(&tmp, n);
-  if (rc) return rc;
+  if (int rc = db.alloc(&tmp, n)) return rc;
   fwk::launch_f16_to_f32(m->stream, t->impl.data, tmp, (int64_t)n);
   hipError_t he = hipMemcpyAsync(out, tmp, n * sizeof(float), hipMemcpyDeviceToHost, m->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(m->stream);
-  (void)hipFree(tmp);
   if (he != hipSuccess) {
     set_error("tensor_to_host failed: %s", hipGetErrorString(he));
     return FW_ERUNTIME;
@@ -1547,12 +1474,12 @@ int32_t fw_tensor_from_host(fw_model* fm, const float* data, int32_t B, fw_tenso
   int rc = new_tensor(m, B, &t);
   if (rc) return rc;
   const size_t n = (size_t)B * t->impl.T * t->impl.D;
+  DevBufs db;
   float* tmp = nullptr;
-  if ((rc = dev_alloc_t(&tmp, n))) { fw_tensor_free(t); return rc; }
+  if ((rc = db.alloc(&tmp, n))) { fw_tensor_free(t); return rc; }
   hipError_t he = hipMemcpyAsync(tmp, data, n * sizeof(float), hipMemcpyHostToDevice, m->stream);
   fwk::launch_f32_to_f16(m->stream, tmp, t->impl.data, (int64_t)n);
   if (he == hipSuccess) he = hipStreamSynchronize(m->stream);
-  (void)hipFree(tmp);
   if (he != hipSuccess) {
     fw_tensor_free(t);
     set_error("tensor_from_host failed: %s", hipGetErrorString(he));
@@ -1564,17 +1491,7 @@ int32_t fw_tensor_from_host(fw_model* fm, const float* data, int32_t B, fw_tenso
 
 void fw_tensor_free(fw_tensor* t) {
   if (!t) return;
-  if (t->impl.data) {
-    std::lock_guard<std::mutex> lk(g_models_mu);
-    Model* m = t->impl.owner;
-    const bool alive = std::find(g_live_models.begin(), g_live_models.end(), m) != g_live_models.end();
-    if (alive) {
-      std::lock_guard<std::mutex> lk2(m->pool_mu);
-      m->enc_pool.push_back(t->impl.data);
-    } else {
-      (void)hipFree(t->impl.data);
-    }
-  }
+  if (t->impl.data) t->impl.pool->give(t->impl.data);   // back to ITS pool, or released when the model is gone
   delete t;
 }
 

@@ -56,13 +56,7 @@ int download_f16(hipStream_t st, float* dst, const half_t* src, size_t n) {
   return FW_OK;
 }
 
-// fragment-major position of element (row, k) of a [rows][K] operand: 16-row tiles x k-steps of KE elements, the
-// 16 bytes of lane l = 16*((k / (KE/4)) % 4) + row % 16 contiguous (dec_kernels.hip)
-inline size_t frag_pos(int64_t row, int64_t k, int64_t K, int KE) {
-  const int OCT = KE / 4;
-  return (size_t)((((row >> 4) * (K / KE) + k / KE) * 64 + ((k / OCT) & 3) * 16 + (row & 15)) * OCT + (k % OCT));
-}
-// a fragment-major fp16 buffer of ceil(rows / 16) whole tiles, un-permuted into dst [rows][d]
+// a fragment-major (engine.h: frag_pos) fp16 buffer of ceil(rows / 16) whole tiles, un-permuted into dst [rows][d]
 int download_f16_frag(hipStream_t st, float* dst, const half_t* src, int rows, int d) {
   std::vector<float> f((size_t)((rows + 15) / 16 * 16) * d);
   int rc = download_f16(st, f.data(), src, f.size());
@@ -251,7 +245,7 @@ int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const f
     memcpy(out_from_frag, out, (size_t)R * N * sizeof(float));
     return FW_OK;
   }
-  // fp16: fold the LayerNorm exactly like the weight packer (add_folded)
+  // fp16: fold the LayerNorm exactly like the weight packer (engine.hip: Packer::folded)
   std::vector<uint16_t> wf((size_t)N * K), xf((size_t)R16 * K, 0);
   std::vector<float> s1(N, 0.f), cf(N, 0.f);
   for (int n = 0; n < N; ++n) {
@@ -325,6 +319,19 @@ int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max
   *want = cap.want;
   *run_cap = cap.run_cap;
   return cap.rows_fit && cap.cache_fits ? 1 : 0;
+}
+
+// host-only: what model creation checks of a blob before it binds it (engine.hip), on a host copy; needs no device
+int32_t fw_test_blob_check(const void* blob_host, int64_t bytes) {
+  FW_CHECK_ARG(blob_host && bytes >= (int64_t)sizeof(BlobHeader), "weight blob too small");
+  BlobHeader h;
+  memcpy(&h, blob_host, sizeof(h));
+  if (int rc = check_blob_header(h, bytes)) return rc;
+  std::vector<BlobEntry> entries(h.n_tensors);
+  memcpy(entries.data(), reinterpret_cast<const char*>(blob_host) + sizeof(h), entries.size() * sizeof(BlobEntry));
+  Weights unused;
+  bool has_plain;
+  return bind_weights(h, entries.data(), const_cast<void*>(blob_host), unused, &has_plain);
 }
 
 int32_t fw_test_dec_logits(fw_model* fm, const float* x, int32_t R, float* out) {

@@ -233,6 +233,12 @@ int64_t fw_test_idle_lead_chunks(int64_t queued, int32_t n_queued, int32_t encod
 int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max_beam, int64_t self_cap, int32_t B,
                              int32_t sampling, int32_t beam_size, int32_t num_hypotheses, int32_t ctx,
                              int64_t* rows_per_chunk, int64_t* want, int64_t* run_cap);
+/* host-only (no device needed): the checks model creation makes of a weight blob before it binds it, on a HOST copy of
+ * `bytes` bytes — header (magic, version, size, config, compute type, layout generation), then for every tensor the
+ * weight list expects for that config and compute type: present, dtype, ndim / dims (the stored extent of fragment-major
+ * tensors), nbytes = dims x element size, offset % 256 == 0, offset + nbytes <= total_bytes.  FW_OK, or FW_EINVAL with
+ * the tensor's name in fw_last_error. */
+int32_t fw_test_blob_check(const void* blob_host, int64_t bytes);
 
 #ifdef __cplusplus
 }

@@ -165,7 +165,7 @@ class OracleWhisper:
         return self._r(torch.nn.functional.layer_norm(x, (self.d,), self.w[p + ".g"], self.w[p + ".b"], 1e-5))
 
     def _fold(self, wkey: str, bkey: Optional[str], lnp: str):
-        """(W' = fp16(W * g), cf = W b + bias) of linear `wkey` behind LayerNorm `lnp` (engine.hip packer: add_folded)"""
+        """(W' = fp16(W * g), cf = W b + bias) of linear `wkey` behind LayerNorm `lnp` (engine.hip: Packer::folded)"""
         k = (wkey, lnp)
         if k not in self._folded:
             W, g, b = self.w[wkey], self.w[lnp + ".g"], self.w[lnp + ".b"]

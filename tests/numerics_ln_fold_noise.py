@@ -6,7 +6,7 @@ Orders compared on the same encoder output, same token ids (teacher forcing):
     o32   float32 throughout                                   (what the reference's CPU path computes)
     o16   fp16 storage, explicit decoder LayerNorms            (what the reference's fp16 path computes)
     fold  fp16 storage, decoder LayerNorms folded into the consuming linears, W' = fp16(W * g)
-          (what the engine computes: engine.hip add_folded, dec_kernels.hip dec_gemm_frag_kernel<LNF>)
+          (what the engine computes: engine.hip Packer::folded, dec_kernels.hip dec_gemm_frag_kernel<LNF>)
 The output is the justification of the tolerances in tests/test_gpu_full_size.py: the engine is compared tightly
 with `fold`, and with `o16` only at the level at which `fold` and `o16` (and `o16` and `o32`) differ here.
 Not a test (pytest does not collect it): it measures, it asserts nothing."""

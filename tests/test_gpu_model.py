@@ -509,3 +509,26 @@ def test_position_blocks_same_bits(setup):
     for i, (a, b) in enumerate(zip(res[0], res[1])):
         assert a == b, f"position blocks changed result set {i}"
     print(f"[{cfg.name}] position blocks on / off: identical ids, scores, no-speech, alignments and token probabilities")
+
+
+def test_encoder_outputs_freed_after_their_model():
+    """An encoder output gives its buffer back to the pool it was taken from, never to another model's: two outputs of a
+    max_batch = 1 model are freed after that model is closed and a max_batch = 4 model of the same weights exists.  The
+    larger model then encodes a batch of 4 twice — the second time into a buffer drawn from its pool — and both outputs
+    equal, bitwise, those of an untouched model of max_batch = 4."""
+    from faster_whisper_amd.backend import StorageView
+    cfg, w, a = make_model("micro", seed=11, max_batch=1, max_beam=1)
+    one = StorageView.from_array(a.log_mel([bench_audio(16000, seed=5)]))
+    kept = [a.encode(one), a.encode(one)]
+    a.unload_model()
+    _, _, b = make_model("micro", max_batch=4, max_beam=1, cfg=cfg, weights=w)
+    kept.clear()
+    batch = StorageView.from_array(b.log_mel([bench_audio(16000 * (i + 1), seed=20 + i) for i in range(4)]))
+    first = b.encode(batch)
+    got = [first.to_numpy()]
+    del first
+    got.append(b.encode(batch).to_numpy())
+    _, _, fresh = make_model("micro", max_batch=4, max_beam=1, cfg=cfg, weights=w)
+    ref = fresh.encode(batch).to_numpy()
+    assert np.isfinite(ref).all() and ref.shape == (4, cfg.n_audio_ctx, cfg.d_model)
+    assert np.array_equal(got[0], ref) and np.array_equal(got[1], ref)
