@@ -48,8 +48,10 @@ void launch_embed(hipStream_t st, const int* tok, const half_t* emb, const half_
                   int rows, int d,
                   const int* d_step, int pos_fixed, int P, int blk_n = 0,
                   const int* ptab = nullptr, int kmul = 0, int reach = 0);
-// whether launch_self_attn can take position blocks for this cache geometry
+// whether launch_self_attn's second form (forms 2 / 3, and with it position blocks) is usable for this cache geometry
 bool self_attn_block_ok(int n_ctx, int cache_ctx, int d, int R_total);
+// the form (1 / 2 / 3, below) launch_self_attn takes for `chunks` workgroups per head under knob value `knob`; pure
+int self_attn_form(int n_ctx, int cache_ctx, int d, int R_total, int kmul, int H, int chunks, int knob);
 // n_ctx: stride of the slot table (the text context); cache_ctx: positions per slot of the K/V cache of this run
 void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half_t* vc, int n_ctx, int cache_ctx, int H,
                       const uint8_t* kvidx2, int Kbeam, int kmul, half_t* out, int rows, const int* d_step,
@@ -64,25 +66,37 @@ void bump_kernel_forms_epoch();
 // slot_map: [B / kv_div] encoder chunk of the run -> chunk slot behind ck / cvt (the cross-attention pool)
 void launch_cross_attn(hipStream_t st, const half_t* qx, int d, const half_t* ck, const half_t* cvt, int T, int kvp,
                        int kmul, half_t* out, int B, int H, const int* done, int kv_div, int frag, const int* slot_map);
-// rows from which launch_dec_gemm_frag hands a decode run's linears to the GEMM-shaped kernel
+// rows from which a decode run's linears take the GEMM-shaped kernel (read from dec_linear_plan's table)
 int dec_big_min_rows();
 int dec_big_min_rows_of(int role, int compute_type);   // role 0 qkv, 1 d x d, 2 ffn1, 3 ffn2, < 0: the lowest; 0 fp16 / 1 int8
-// frag = 1: `out` is a fragment-major [rows/16][d/32][64][8] buffer (input of launch_dec_gemm_frag)
-int launch_dec_gemm_frag(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                         const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                         int N, int K, int act);
-// the skinny kernel whatever the row count (launch_dec_gemm_frag hands merged runs to the GEMM-shaped kernel)
-int launch_dec_gemm_skinny(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                           const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                           int N, int K, int act);
-// ... with an explicit tile grouping (1: one 16 x 16 tile per workgroup, 2: 2 x 2 tiles)
-int launch_dec_gemm_skinny_tiles(hipStream_t st, int tiles, const half_t* xf, const half_t* Wf, const half_t* bias,
-                                 const float* s1, const float* cf, const half_t* res, int ldr, half_t* out, int ldo,
-                                 half_t* out_frag, int R, int N, int K, int act);
-// the GEMM-shaped kernel of merged runs whatever the row count, workgroup shape cfg (dec_kernels.hip); same bits
-int launch_dec_gemm_big(hipStream_t st, int cfg, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                        const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                        int N, int K, int act);
+// Which kernel form a decoder linear takes: the numbers fw_test_dec_linear / fw_bench_dec_linear_epi pass through.
+enum DecLinForm {
+  DEC_LIN_PRODUCT = 0,       // the product's choice by shape and row count
+  DEC_LIN_SKINNY = 5,        // the register-streaming (skinny) kernel whatever the row count
+  DEC_LIN_SKINNY_1X1 = 6,    // ... with one 16 x 16 tile per workgroup
+  DEC_LIN_SKINNY_2X2 = 7,    // ... with 2 x 2 tiles per workgroup
+  DEC_LIN_BIG = 10,          // + cfg (0..2): the GEMM-shaped kernel of merged runs, workgroup shape cfg (dec_kernels.hip)
+};
+enum DecLinFamily { DEC_LIN_REFUSED = 0, DEC_LIN_FAMILY_SKINNY = 1, DEC_LIN_FAMILY_BIG = 2 };
+struct DecLinPlan {
+  int family;                       // DecLinFamily; the int8 kernel (compute_type 1) counts as skinny
+  int cfg;                          // big: 0..2, else -1
+  int row_tiles, col_tiles, chunk;  // skinny: 16 x 16 tiles per workgroup, k-steps of loads in flight per wave
+  int waves;                        // 4 | 8: the waves K is split over = the K slice count of the big kernel
+};
+// THE place that decides the form of a decoder linear of R rows, [N][K] weights, output / residual row strides ldo / ldr
+// (ldr = 0: no residual).  Arithmetic only: no HIP call, no lock, no allocation.  Every form returns the same bits.
+DecLinPlan dec_linear_plan(int R, int N, int K, int ldo, int ldr, int compute_type, int form);
+// xf / Wf fragment-major [rows/16][K/32][64][8] (what frag = 1 of the row kernels and launch_self_attn write); out
+// (row-major) and out_frag (fragment-major, for the next linear) are both optional; res is row-major; s1 / cf: the
+// LayerNorm-folded form (then bias is folded into cf)
+struct DecLin {
+  const half_t *xf, *Wf, *bias; const float *s1, *cf;
+  const half_t* res; int ldr; half_t* out; int ldo; half_t* out_frag;
+  int R, N, K, act;
+};
+// launches what dec_linear_plan says; -1 when the plan refuses (a forced form that does not fit, a shape no form takes)
+int launch_dec_linear(hipStream_t st, const DecLin& a, int form = DEC_LIN_PRODUCT);
 int launch_dec_gemm_frag_variant(hipStream_t st, int variant, bool lnf, const half_t* xf, const half_t* Wf,
                                  const half_t* bias, const float* s1, const float* cf, half_t* out, int R, int N,
                                  int K);

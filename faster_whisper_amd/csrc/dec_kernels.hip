@@ -1965,10 +1965,6 @@ __global__ __launch_bounds__(256) void dec_cross_probs_kernel(const half_t* __re
 
 namespace fwd {
 
-// row count from which the decoder linears of a decode run take the LDS-staged GEMM-shaped kernel
-// (profiles/r03_dec_linear_bench.txt)
-// (per linear: DEC_BIG_RULES below)
-
 void launch_embed(hipStream_t st, const int* tok, const half_t* emb, const half_t* pos_emb, half_t* x, half_t* xfrag,
                   int rows, int d, const int* d_step, int pos_fixed, int P, int blk_n, const int* ptab, int kmul,
                   int reach) {
@@ -1976,20 +1972,12 @@ void launch_embed(hipStream_t st, const int* tok, const half_t* emb, const half_
   dec_embed_kernel<<<rows, 128, 0, st>>>(tok, emb, pos_emb, x, xfrag, d, d_step, pos_fixed, P, blk_n, ptab, kmul, reach);
 }
 
-template <bool LNF, int RT, int NT, int CH = 0>
-static void frag_go(hipStream_t st, int waves, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                    const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R, int N,
-                    int K, int act) {
-  const dim3 grid((N / 16 + NT - 1) / NT, ((R + 15) / 16 + RT - 1) / RT);
-  if (waves == 8)
-    dec_gemm_frag_kernel<8, LNF, RT, NT, CH><<<grid, 512, 0, st>>>(xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R,
-                                                                   N, K, act);
-  else
-    dec_gemm_frag_kernel<4, LNF, RT, NT, CH><<<grid, 256, 0, st>>>(xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R,
-                                                                   N, K, act);
-}
+// ---------------------------------------------------------------- the decoder linears: the plan
+// Which linear of a decoder layer a shape is: 0 qkv (N = 3 K), 1 d x d (out / cross-q / cross-out), 2 ffn1, 3 ffn2.
+static int dec_linear_role(int N, int K) { return N == 3 * K ? 0 : (N >= 2560 ? 2 : (K >= 2560 ? 3 : 1)); }
 
-// GEMM-shaped kernel of merged runs (dec_gemm_big_kernel), workgroup shape `cfg`; -1 when the shape does not fit.
+// Workgroup shapes of the GEMM-shaped kernel of merged runs (dec_gemm_big_kernel), indexed by `cfg`: WM x WN waves, FB
+// column tiles per wave, KC k-steps per stage, a ring of NST stages.
 //   cfg 0: 4 x 2 waves, 256 rows x 128 columns, 2 k-steps per stage, 3 stages (144 KB)  — the wide linears (qkv, ffn1)
 //   cfg 1: 2 x 2 waves, 128 rows x 64 columns (2 column tiles per wave), 1 k-step per stage, 5 stages (60 KB, two
 //          workgroups per CU) — the linears with 1280 columns (out / cross-q / cross-out, ffn2), which a wider tile
@@ -2003,9 +1991,98 @@ static void frag_go(hipStream_t st, int waves, const half_t* xf, const half_t* W
 //    with two k-steps per stage (_call16_cfg7.txt))
 // (measured next to 256 x 64, 128 x 256, 8 waves on 128 x 128, deeper rings, two k-steps per barrier, LDS reads
 //  software-pipelined under the MFMAs, L2 touch-ahead: profiles/r03_dec_linear_bench.txt — none better)
+struct BigShape { int WM, WN, FB, KC, NST; };
+static constexpr BigShape BIG_SHAPES[3] = {{4, 2, 4, 2, 3}, {2, 2, 2, 1, 5}, {2, 2, 4, 1, 4}};
+
+// Row counts from which each linear of a decode run takes the GEMM-shaped kernel, and the workgroup shape it takes there
+// — ONE table: dec_linear_plan and dec_big_min_rows_of (the benchmark prices a linear against the MFMA roof only from ITS
+// row count on) read it.  (Why the kernel: per layer at 1 520 rows 216 -> 157 us, the register-streaming kernel with 4 x 4
+// tiles reaches 174: profiles/r03_dec_linear_bench.txt.)  The crossover is per linear because the fixed ~12-35 us of an LDS-staged launch (its K loop's
+// latency) is reached at a different row count by each shape.  Measured crossovers:
+// profiles/r05_dec_linear_bench_call1.txt (round 5), profiles/r06_dec_linear_bench_*.txt (round 6: staggered 256 x 128).
+struct DecBigRule { int rows; int cfg; };
+static const DecBigRule DEC_BIG_RULES[4][2] = {
+    // (round 6, after the LayerNorm-statistics split, profiles/r06_dec_linear_bench_call11_crossovers.txt, us per launch
+    //  register-streaming vs LDS-staged: qkv 576 / 640 / 768 rows 20.9 / 23.0 / 26.6 vs 22.1 / 21.9 / 22.4 (128 x 128); ffn1 448 /
+    //  512 / 768 rows 21.8 / 24.3 / 33.3 vs 22.0 / 22.2 / 23.6 (128 x 128; 256 x 128 is the same from ~900 rows); ffn2 768 / 832
+    //  rows 32.3 / 37.0 vs 34.2 / 34.0 (128 x 64); d x d 1 024 / 1 120 rows 12.3 / 13.2 vs 12.8 / 12.9 (128 x 64))
+    /* qkv  */ {{640, 2}, {1280, 0}},
+    /* dxd  */ {{1088, 1}, {1 << 30, 1}},
+    /* ffn1 */ {{512, 2}, {1280, 0}},
+    /* ffn2 */ {{832, 1}, {1 << 30, 1}},   // (NOT the two-k-steps form: 4 % faster isolated, 18 % slower in the pipeline, r06_ab_ffn2_cfg.jsonl)
+};
+// int8_float16: the 4 x 4-tile grouping from this row count for every linear (measured crossover of the int8 forms): a
+// quarter of the operand traffic per output (the fp16 form of this grouping measured 216 -> 174 us per layer at 1 520
+// rows); integer accumulation: the result does not depend on the grouping
+#define DEC_BIG_MIN_ROWS_I8 1024
+
+// role 0..3 as above, < 0: the lowest row count of any linear; compute_type 0 float16, 1 int8_float16
+int dec_big_min_rows_of(int role, int compute_type) {
+  if (compute_type == 1) return DEC_BIG_MIN_ROWS_I8;
+  if (role >= 0 && role < 4) return DEC_BIG_RULES[role][0].rows;
+  int lo = DEC_BIG_RULES[0][0].rows;
+  for (int k = 1; k < 4; ++k) lo = DEC_BIG_RULES[k][0].rows < lo ? DEC_BIG_RULES[k][0].rows : lo;
+  return lo;
+}
+int dec_big_min_rows() { return dec_big_min_rows_of(-1, 0); }
+
+// the GEMM-shaped kernel splits K into `slices` slices (the skinny kernel's waves: the same reduction order, the same
+// bits), each a whole number of stages, and fills its ring once; its row segments are 16 bytes
+static bool big_fits(int cfg, int slices, int K, int ldo, int ldr) {
+  if (cfg < 0 || cfg > 2) return false;
+  const BigShape& b = BIG_SHAPES[cfg];
+  const int KS = K / 32;
+  if (KS % slices != 0 || (KS / slices) % b.KC != 0 || KS / b.KC < b.NST) return false;
+  return ldo % 8 == 0 && ldr % 8 == 0;
+}
+
+DecLinPlan dec_linear_plan(int R, int N, int K, int ldo, int ldr, int compute_type, int form) {
+  const DecLinPlan refused{DEC_LIN_REFUSED, -1, 0, 0, 0, 0};
+  const int waves = K >= 2560 ? 8 : 4;   // keeps a wave's share at <= 20 k-steps = 2 chunks of loads
+  if (compute_type == 1) {               // (k-steps of 64; the product's choice is the only form)
+    if (K % 64 != 0 || N % 32 != 0 || R < 1 || form != DEC_LIN_PRODUCT) return refused;
+    if (R >= DEC_BIG_MIN_ROWS_I8 && N % 64 == 0) return {DEC_LIN_FAMILY_SKINNY, -1, 4, 4, waves == 8 ? 3 : 5, waves};
+    return {DEC_LIN_FAMILY_SKINNY, -1, 2, 2, 5, waves};
+  }
+  if (K % 32 != 0 || N % 32 != 0 || R < 1) return refused;
+  // Skinny kernel, tile grouping by row count (the arithmetic of an output does not depend on it: same bits).  One
+  // 16 x 16 tile per workgroup when there are few rows — twice to four times the workgroups streaming the weights, a
+  // wave's whole K share in flight at once: single utterance (5 rows) 41.8 -> 31.4 us per layer, and at a solo batch (80
+  // rows) for the linears with 1280 columns (5.6 -> 4.4, 12.1 -> 10.0 us); 2 x 2 tiles otherwise (measured best of
+  // {1,2} x {1,2}: profiles/r01_sweep_dec_gemm_frag_tiles.jsonl), also for merged runs below the table's row counts
+  // (4 x 2, 2 x 4, 4 x 4 tiles measured no better there: profiles/r03_dec_linear_bench.txt, README.md)
+  const DecLinPlan one{DEC_LIN_FAMILY_SKINNY, -1, 1, 1, 10, waves}, two{DEC_LIN_FAMILY_SKINNY, -1, 2, 2, 5, waves};
+  const DecLinPlan by_rows = (R <= 16 || (R <= 96 && N <= 1280)) ? one : two;
+  auto big = [&](int cfg) {
+    return big_fits(cfg, waves, K, ldo, ldr) ? DecLinPlan{DEC_LIN_FAMILY_BIG, cfg, 0, 0, 0, waves} : refused;
+  };
+  switch (form) {
+    case DEC_LIN_PRODUCT: {   // the table's shape from its row count on; a shape that does not fit stays skinny
+      const DecBigRule* r = DEC_BIG_RULES[dec_linear_role(N, K)];
+      const DecLinPlan p = big(R >= r[1].rows ? r[1].cfg : (R >= r[0].rows ? r[0].cfg : -1));
+      return p.family == DEC_LIN_FAMILY_BIG ? p : by_rows;
+    }
+    case DEC_LIN_SKINNY: return by_rows;
+    case DEC_LIN_SKINNY_1X1: return one;
+    case DEC_LIN_SKINNY_2X2: return two;
+    case DEC_LIN_BIG: case DEC_LIN_BIG + 1: case DEC_LIN_BIG + 2: return big(form - DEC_LIN_BIG);
+    default: return refused;
+  }
+}
+
+// ---------------------------------------------------------------- the decoder linears: a plan becomes a launch
+#define DL_ARGS a.xf, a.Wf, a.bias, a.s1, a.cf, a.res, a.ldr, a.out, a.ldo, a.out_frag, a.R, a.N, a.K, a.act
+// The skinny kernel: K split over the waves of a workgroup, RT x NT tiles of 16 x 16 per workgroup, row groups on grid.y
+// so any number of rows works (a merged decode run carries up to 128 chunks x 5 beams).
+template <bool LNF, int RT, int NT, int CH = 0>
+static void frag_go(hipStream_t st, int waves, const DecLin& a) {
+  const dim3 grid((a.N / 16 + NT - 1) / NT, ((a.R + 15) / 16 + RT - 1) / RT);
+  if (waves == 8) dec_gemm_frag_kernel<8, LNF, RT, NT, CH><<<grid, 512, 0, st>>>(DL_ARGS);
+  else dec_gemm_frag_kernel<4, LNF, RT, NT, CH><<<grid, 256, 0, st>>>(DL_ARGS);
+}
+
 template <bool LNF, int S, int WM, int WN, int FB, int KC, int NST>
-static int big_go(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1, const float* cf,
-                   const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R, int N, int K, int act) {
+static int big_go(hipStream_t st, const DecLin& a) {
   constexpr int lds = (4 * WM + FB * WN) * KC * 1024 * NST;
   // the dynamic-LDS limit is a per-device attribute of the function; decode lanes launch from several host threads:
   // one bit per device, set after the attribute call returned (two threads may both make the call: it is idempotent)
@@ -2018,34 +2095,42 @@ static int big_go(hipStream_t st, const half_t* xf, const half_t* Wf, const half
       return -1;
     attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
   }
-  const int nMt = ((R + 15) / 16 + 4 * WM - 1) / (4 * WM), nNt = (N / 16 + FB * WN - 1) / (FB * WN);
-  dec_gemm_big_kernel<LNF, S, WM, WN, FB, KC, NST><<<nMt * nNt, WM * WN * 64, lds, st>>>(xf, Wf, bias, s1, cf, res, ldr, out,
-                                                                                           ldo, out_frag, R, N, K, act, nNt);
+  const int nMt = ((a.R + 15) / 16 + 4 * WM - 1) / (4 * WM), nNt = (a.N / 16 + FB * WN - 1) / (FB * WN);
+  dec_gemm_big_kernel<LNF, S, WM, WN, FB, KC, NST><<<nMt * nNt, WM * WN * 64, lds, st>>>(DL_ARGS, nNt);
   return hipPeekAtLastError() == hipSuccess ? 0 : -1;
 }
-template <int WM, int WN, int FB, int KC, int NST>
-static int big_cfg(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1, const float* cf,
-                   const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R, int N, int K, int act) {
-  if (K % 32 != 0 || N % 32 != 0 || R < 1) return -1;
-  const int S = K >= 2560 ? 8 : 4;   // the slice count of launch_dec_gemm_skinny's instantiation for this K
-  const int KS = K / 32;
-  if (KS % S != 0 || (KS / S) % KC != 0 || KS / KC < NST) return -1;
-  if ((ldo % 8) || (res && (ldr % 8))) return -1;   // 16-byte row segments
-#define DGB(LNF_, S_) big_go<LNF_, S_, WM, WN, FB, KC, NST>(st, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act)
-  if (s1) return S == 8 ? DGB(true, 8) : DGB(true, 4);
-  return S == 8 ? DGB(false, 8) : DGB(false, 4);
+template <int CFG>
+static int big_cfg(hipStream_t st, int slices, const DecLin& a) {
+  constexpr BigShape b = BIG_SHAPES[CFG];
+#define DGB(LNF_, S_) big_go<LNF_, S_, b.WM, b.WN, b.FB, b.KC, b.NST>(st, a)
+  if (a.s1) return slices == 8 ? DGB(true, 8) : DGB(true, 4);
+  return slices == 8 ? DGB(false, 8) : DGB(false, 4);
 #undef DGB
 }
-int launch_dec_gemm_big(hipStream_t st, int cfg, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                        const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                        int N, int K, int act) {
-  switch (cfg) {
-    case 0: return big_cfg<4, 2, 4, 2, 3>(st, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    case 1: return big_cfg<2, 2, 2, 1, 5>(st, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    case 2: return big_cfg<2, 2, 4, 1, 4>(st, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    default: return -1;
+
+int launch_dec_linear(hipStream_t st, const DecLin& a, int form) {
+  const DecLinPlan p = dec_linear_plan(a.R, a.N, a.K, a.ldo, a.res ? a.ldr : 0, 0, form);
+  if (p.family == DEC_LIN_FAMILY_BIG) {
+    int rc = -1;
+    switch (p.cfg) {
+      case 0: rc = big_cfg<0>(st, p.waves, a); break;
+      case 1: rc = big_cfg<1>(st, p.waves, a); break;
+      case 2: rc = big_cfg<2>(st, p.waves, a); break;
+    }
+    // a run-time failure (the attribute call, the launch): the product goes on with the skinny kernel, a forced form fails
+    return rc == 0 || form != DEC_LIN_PRODUCT ? rc : launch_dec_linear(st, a, DEC_LIN_SKINNY);
   }
+  if (p.family != DEC_LIN_FAMILY_SKINNY) return -1;
+  if (p.row_tiles == 1) {
+    if (a.s1) frag_go<true, 1, 1, 10>(st, p.waves, a);
+    else frag_go<false, 1, 1, 10>(st, p.waves, a);
+  } else {
+    if (a.s1) frag_go<true, 2, 2>(st, p.waves, a);
+    else frag_go<false, 2, 2>(st, p.waves, a);
+  }
+  return 0;
 }
+#undef DL_ARGS
 
 // tile-shape experiments of profiles/dec_linear_bench.py (fw_bench_dec_linear): variant -> instantiation
 template <int WAVES, int RT, int NT, int CH>
@@ -2064,8 +2149,8 @@ int launch_dec_gemm_frag_variant(hipStream_t st, int variant, bool lnf, const ha
                                  int K) {
   if (K % 32 != 0 || N % 64 != 0 || R < 1) return -1;
   switch (variant) {
-    case 0: frag_variant<4, 2, 2, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;   // product, K < 2560
-    case 1: frag_variant<8, 2, 2, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;   // product, K >= 2560
+    case 0: frag_variant<4, 2, 2, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;   // the product's 2 x 2 grouping, 4 waves
+    case 1: frag_variant<8, 2, 2, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;   // ... 8 waves
     case 2: frag_variant<8, 4, 2, 3>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;
     case 3: frag_variant<8, 4, 2, 4>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;
     case 4: frag_variant<8, 4, 4, 2>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;
@@ -2081,109 +2166,9 @@ int launch_dec_gemm_frag_variant(hipStream_t st, int variant, bool lnf, const ha
     case 21: frag_variant<4, 4, 4, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;
     case 22: frag_variant<8, 4, 4, 5>(st, lnf, xf, Wf, bias, s1, cf, out, R, N, K); break;
     case 10: case 11: case 12:
-      return launch_dec_gemm_big(st, variant - 10, xf, Wf, lnf ? nullptr : bias, lnf ? s1 : nullptr, lnf ? cf : nullptr,
-                                 nullptr, 0, out, N, nullptr, R, N, K, 0);
+      return launch_dec_linear(st, DecLin{xf, Wf, lnf ? nullptr : bias, lnf ? s1 : nullptr, lnf ? cf : nullptr, nullptr, 0,
+                                          out, N, nullptr, R, N, K, 0}, variant);
     default: return -1;
-  }
-  return 0;
-}
-
-// Which linear of a decoder layer a shape is: 0 qkv (N = 3 K), 1 d x d (out / cross-q / cross-out), 2 ffn1, 3 ffn2.
-static int dec_linear_role(int N, int K) { return N == 3 * K ? 0 : (N >= 2560 ? 2 : (K >= 2560 ? 3 : 1)); }
-// Row counts from which each linear of a decode run takes the LDS-staged GEMM-shaped kernel, and the workgroup shape it
-// takes there (launch_dec_gemm_big's cfg) — ONE table: the launcher below, fw_dec_big_min_rows_of (the benchmark prices a
-// linear against the MFMA roof only from ITS row count on) and the tests read it.  Measured crossovers:
-// profiles/r05_dec_linear_bench_call1.txt (round 5), profiles/r06_dec_linear_bench_*.txt (round 6: staggered 256 x 128).
-struct DecBigRule { int rows; int cfg; };
-static const DecBigRule DEC_BIG_RULES[4][2] = {
-    // (round 6, after the LayerNorm-statistics split, profiles/r06_dec_linear_bench_call11_crossovers.txt, us per launch
-    //  register-streaming vs LDS-staged: qkv 576 / 640 / 768 rows 20.9 / 23.0 / 26.6 vs 22.1 / 21.9 / 22.4 (128 x 128); ffn1 448 /
-    //  512 / 768 rows 21.8 / 24.3 / 33.3 vs 22.0 / 22.2 / 23.6 (128 x 128; 256 x 128 is the same from ~900 rows); ffn2 768 / 832
-    //  rows 32.3 / 37.0 vs 34.2 / 34.0 (128 x 64); d x d 1 024 / 1 120 rows 12.3 / 13.2 vs 12.8 / 12.9 (128 x 64))
-    /* qkv  */ {{640, 2}, {1280, 0}},
-    /* dxd  */ {{1088, 1}, {1 << 30, 1}},
-    /* ffn1 */ {{512, 2}, {1280, 0}},
-    /* ffn2 */ {{832, 1}, {1 << 30, 1}},   // (NOT the two-k-steps form: 4 % faster isolated, 18 % slower in the pipeline, r06_ab_ffn2_cfg.jsonl)
-};
-static int dec_big_cfg_for(int R, int N, int K) {
-  const DecBigRule* r = DEC_BIG_RULES[dec_linear_role(N, K)];
-  if (R >= r[1].rows) return r[1].cfg;
-  if (R >= r[0].rows) return r[0].cfg;
-  return -1;
-}
-// role 0..3 as above; compute_type 0 float16, 1 int8_float16 (launch_dec_gemm_frag_i8: the 4 x 4-tile form from
-// DEC_BIG_MIN_ROWS_I8 rows for every linear); role < 0: the lowest row count of any linear
-#define DEC_BIG_MIN_ROWS_I8 1024
-int dec_big_min_rows_of(int role, int compute_type) {
-  if (compute_type == 1) return DEC_BIG_MIN_ROWS_I8;
-  if (role >= 0 && role < 4) return DEC_BIG_RULES[role][0].rows;
-  int lo = DEC_BIG_RULES[0][0].rows;
-  for (int k = 1; k < 4; ++k) lo = DEC_BIG_RULES[k][0].rows < lo ? DEC_BIG_RULES[k][0].rows : lo;
-  return lo;
-}
-
-static bool skinny_one_tile(int R, int N) { return R <= 16 || (R <= 96 && N <= 1280); }
-
-// The per-layer decoder linears: K split over the waves of a workgroup, 2 x 2 tiles of 16 x 16 per workgroup
-// (measured best of {1,2} x {1,2}: profiles/r01_sweep_dec_gemm_frag_tiles.jsonl), row groups on grid.y so any
-// number of rows works (a merged decode run carries up to 128 chunks x 5 beams).  out (row-major) and out_frag
-// (fragment-major, for the next GEMM) are both optional; res is row-major.
-int launch_dec_gemm_frag(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                         const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                         int N, int K, int act) {
-  // Merged runs of >= DEC_BIG_MIN_ROWS rows: the LDS-staged GEMM-shaped kernel, 256 x 128 tiles for the wide linears and
-  // 128 x 64 for those with 1280 columns (measured per layer at 1 520 rows: 216 -> 157 us; the register-streaming kernel
-  // with 4 x 4 tiles reaches 174: profiles/r03_dec_linear_bench.txt).  Same K slices, same reduction order, same pinned
-  // epilogue as the register-streaming kernel: the same bits.
-  // Round 5: the crossover is per linear (profiles/r05_dec_linear_bench_call1.txt, us per launch, register-streaming vs
-  // LDS-staged at 800 / 960 / 1 120 rows): qkv 27.3 / 31.8 / 36.1 vs 25.0 / 25.8 / 35.3 (128 x 128 tiles; 256 x 128 from
-  // 1 280 rows), ffn1 34.4 / 40.0 / 45.0 vs 34.9 / 35.3 / 37.3 (256 x 128), ffn2 33.0 / 39.1 / 45.1 vs 35.8 / 35.9 / 36.6
-  // (128 x 64), d x d 10.1 / 11.9 / 13.2 vs 12.8 / 13.0 / 13.1 (128 x 64): the fixed ~12-35 us of an LDS-staged launch
-  // (its K loop's latency) is reached at a different row count by each shape.  Same bits from every form.
-  const int cfg = dec_big_cfg_for(R, N, K);
-  if (cfg >= 0 &&
-      launch_dec_gemm_big(st, cfg, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act) == 0)
-    return 0;
-  return launch_dec_gemm_skinny(st, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-}
-
-int dec_big_min_rows() { return dec_big_min_rows_of(-1, 0); }
-
-int launch_dec_gemm_skinny(hipStream_t st, const half_t* xf, const half_t* Wf, const half_t* bias, const float* s1,
-                           const float* cf, const half_t* res, int ldr, half_t* out, int ldo, half_t* out_frag, int R,
-                           int N, int K, int act) {
-  if (K % 32 != 0 || N % 32 != 0 || R < 1) return -1;
-  const int waves = K >= 2560 ? 8 : 4;   // keeps a wave's share at <= 20 k-steps = 2 chunks of loads
-  // Tile grouping by row count (the arithmetic of an output does not depend on it: same bits).  One 16 x 16 tile per
-  // workgroup when there are few rows — twice to four times the workgroups streaming the weights, a wave's whole K share
-  // in flight at once: single utterance (5 rows) 41.8 -> 31.4 us per layer, and at a solo batch (80 rows) for the
-  // linears with 1280 columns (5.6 -> 4.4, 12.1 -> 10.0 us); 2 x 2 tiles otherwise, also for merged runs below
-  // DEC_BIG_MIN_ROWS (4 x 2, 2 x 4, 4 x 4 tiles measured no better there: profiles/r03_dec_linear_bench.txt, README.md)
-  const bool one_tile = skinny_one_tile(R, N);
-  if (one_tile) {
-    if (s1) frag_go<true, 1, 1, 10>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    else frag_go<false, 1, 1, 10>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    return 0;
-  }
-  if (s1) frag_go<true, 2, 2>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-  else frag_go<false, 2, 2>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-  return 0;
-}
-
-// the register-streaming kernel with an explicit tile grouping (tests: every grouping returns the same bits)
-int launch_dec_gemm_skinny_tiles(hipStream_t st, int tiles, const half_t* xf, const half_t* Wf, const half_t* bias,
-                                 const float* s1, const float* cf, const half_t* res, int ldr, half_t* out, int ldo,
-                                 half_t* out_frag, int R, int N, int K, int act) {
-  if (K % 32 != 0 || N % 32 != 0 || R < 1) return -1;
-  const int waves = K >= 2560 ? 8 : 4;
-  if (tiles == 1) {
-    if (s1) frag_go<true, 1, 1, 10>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    else frag_go<false, 1, 1, 10>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-  } else if (tiles == 2) {
-    if (s1) frag_go<true, 2, 2>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-    else frag_go<false, 2, 2>(st, waves, xf, Wf, bias, s1, cf, res, ldr, out, ldo, out_frag, R, N, K, act);
-  } else {
-    return -1;
   }
   return 0;
 }
@@ -2192,22 +2177,18 @@ int launch_dec_gemm_skinny_tiles(hipStream_t st, int tiles, const half_t* xf, co
 int launch_dec_gemm_frag_i8(hipStream_t st, const int8_t* xq, const float* x_scale, const int8_t* Wq,
                             const float* w_scale, const half_t* bias, const half_t* res, int ldr, half_t* out, int ldo,
                             int R, int N, int K, int act) {
-  if (K % 64 != 0 || N % 32 != 0 || R < 1 || !x_scale || !w_scale) return -1;
-  if (R >= DEC_BIG_MIN_ROWS_I8 && N % 64 == 0) {   // (measured crossover of the int8 forms)
-    // merged runs: 4 x 4 tiles per workgroup, a quarter of the operand traffic per output (the fp16 form of this grouping
-    // measured 216 -> 174 us per layer at 1 520 rows); integer accumulation: the result does not depend on the grouping
-    const dim3 g4(N / 64, ((R + 15) / 16 + 3) / 4);
-    if (K >= 2560)
-      dec_gemm_frag_i8_kernel<8, 4, 4, 3><<<g4, 512, 0, st>>>(xq, x_scale, Wq, w_scale, bias, res, ldr, out, ldo, R, N, K, act);
-    else
-      dec_gemm_frag_i8_kernel<4, 4, 4, 5><<<g4, 256, 0, st>>>(xq, x_scale, Wq, w_scale, bias, res, ldr, out, ldo, R, N, K, act);
-    return 0;
+  const DecLinPlan p = dec_linear_plan(R, N, K, ldo, res ? ldr : 0, 1, DEC_LIN_PRODUCT);
+  if (p.family != DEC_LIN_FAMILY_SKINNY || !x_scale || !w_scale) return -1;
+  const dim3 grid(N / 16 / p.col_tiles, ((R + 15) / 16 + p.row_tiles - 1) / p.row_tiles);
+#define I8_ARGS xq, x_scale, Wq, w_scale, bias, res, ldr, out, ldo, R, N, K, act
+  if (p.row_tiles == 4) {
+    if (p.waves == 8) dec_gemm_frag_i8_kernel<8, 4, 4, 3><<<grid, 512, 0, st>>>(I8_ARGS);
+    else dec_gemm_frag_i8_kernel<4, 4, 4, 5><<<grid, 256, 0, st>>>(I8_ARGS);
+  } else {
+    if (p.waves == 8) dec_gemm_frag_i8_kernel<8, 2, 2><<<grid, 512, 0, st>>>(I8_ARGS);
+    else dec_gemm_frag_i8_kernel<4, 2, 2><<<grid, 256, 0, st>>>(I8_ARGS);
   }
-  const dim3 grid(N / 32, ((R + 15) / 16 + 1) / 2);
-  if (K >= 2560)
-    dec_gemm_frag_i8_kernel<8, 2, 2><<<grid, 512, 0, st>>>(xq, x_scale, Wq, w_scale, bias, res, ldr, out, ldo, R, N, K, act);
-  else
-    dec_gemm_frag_i8_kernel<4, 2, 2><<<grid, 256, 0, st>>>(xq, x_scale, Wq, w_scale, bias, res, ldr, out, ldo, R, N, K, act);
+#undef I8_ARGS
   return 0;
 }
 
@@ -2246,8 +2227,17 @@ int launch_dec_logits(hipStream_t st, bool i8, const void* xf, const float* x_sc
   return 0;
 }
 
+// the second form needs n_ctx % 4 == 0 (4-byte slot-table loads) and a layer's cache below 4 GB (32-bit offsets)
 bool self_attn_block_ok(int n_ctx, int cache_ctx, int d, int R_total) {
   return (n_ctx & 3) == 0 && (size_t)R_total * cache_ctx * d * sizeof(half_t) < ((size_t)1 << 32);
+}
+
+// knob 0: by size (product); 1: first form; 2 / 3: forced.  One workgroup per (head, chunk), one wave per row of the chunk:
+// the latency form (2) holds at most 8 waves
+int self_attn_form(int n_ctx, int cache_ctx, int d, int R_total, int kmul, int H, int chunks, int knob) {
+  if (knob == 1 || !self_attn_block_ok(n_ctx, cache_ctx, d, R_total)) return 1;
+  if (knob == 0) return kmul <= 8 && H * chunks <= 768 ? 2 : 3;
+  return knob == 2 && kmul <= 8 ? 2 : 3;
 }
 
 void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half_t* vc, int n_ctx, int cache_ctx, int H,
@@ -2262,11 +2252,8 @@ void launch_self_attn(hipStream_t st, const half_t* qkv, int d, half_t* kc, half
   // one workgroup per (head, chunk), one wave per row of the chunk (kmul <= 16); LDS: scores + source slots per wave
   const dim3 grid(H, rows / kmul);
   const size_t lds = (size_t)kmul * 2 * n_ctx * sizeof(float);
-  int form = g_self_attn_form.load(std::memory_order_relaxed);   // 0: by size (product); 1: first form; 2 / 3: forced
-  // the second form needs n_ctx % 4 == 0 (4-byte slot-table loads) and a layer's cache below 4 GB (32-bit offsets)
-  if ((n_ctx & 3) != 0 || (size_t)R_total * cache_ctx * d * sizeof(half_t) >= ((size_t)1 << 32)) form = 1;
-  if (form == 0) form = (kmul <= 8 && (int)(grid.x * grid.y) <= 768) ? 2 : 3;
-  if (form == 2 && kmul > 8) form = 3;
+  const int form = self_attn_form(n_ctx, cache_ctx, d, R_total, kmul, H, rows / kmul,
+                                  g_self_attn_form.load(std::memory_order_relaxed));
 #define SA_ARGS qkv, d, kc, vc, n_ctx, cache_ctx, H, kvidx2, Kbeam, kmul, out, d_step, pos_fixed, P, R_total, frag, ptab, reach
   if (ptab) {   // ragged run: the same three forms, position per chunk
     if (form == 1) dec_self_attn_kernel<true><<<grid, kmul * 64, lds, st>>>(SA_ARGS);

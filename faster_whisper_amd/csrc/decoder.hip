@@ -493,8 +493,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   // adds), the FFN hidden only fragment-major; LayerNorms are folded into qkv / cross-q / ffn1
   auto lin_f = [&](const half_t* xin_frag, const LinearW& L, const half_t* res, half_t* outp, half_t* outp_frag,
                    int act) -> int {
-    return fwd::launch_dec_gemm_frag(st, xin_frag, L.w, L.b, L.s1, L.cf, res, L.N, outp, L.N, outp_frag, rows, L.N,
-                                     L.K, act);
+    return fwd::launch_dec_linear(st, fwd::DecLin{xin_frag, L.w, L.b, L.s1, L.cf, res, L.N, outp, L.N, outp_frag, rows,
+                                                  L.N, L.K, act});
   };
   const int frag = i8 ? 0 : 1;
   // fp16, explicit-LayerNorm order (Model::ln_unfold == 2): the LayerNorm is its own kernel, its fp16 output (fragment-
@@ -502,8 +502,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   const bool unf = !i8 && m->ln_unfold >= 2;
   auto lin_u = [&](const LNW& ln, const LinearW& L, half_t* outp, half_t* outp_frag, int act) -> int {
     fwk::launch_layernorm(st, g->x, ln.g, ln.b, g->xn_frag, rows, d, 1);
-    return fwd::launch_dec_gemm_frag(st, g->xn_frag, L.w, L.b, nullptr, nullptr, nullptr, L.N, outp, L.N, outp_frag, rows,
-                                     L.N, L.K, act);
+    return fwd::launch_dec_linear(st, fwd::DecLin{g->xn_frag, L.w, L.b, nullptr, nullptr, nullptr, L.N, outp, L.N,
+                                                  outp_frag, rows, L.N, L.K, act});
   };
   for (int l = 0; l < c.n_dec_layers; ++l) {
     const DecLayerW& L = m->dec[l];

@@ -744,19 +744,27 @@ hipError_t create_stream(hipStream_t* st, const char* role) {
 }
 
 // ---------------------------------------------------------------- layers
-int run_linear(Model* m, const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, half_t* C, int64_t ldc,
-               int64_t c_bs, const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans,
-               int head_rows, hipStream_t st) {
+// what every launch of the encoder GEMM states: operands, output, shape; everything else zero.  W: the weight form the
+// launch reads (L.w, or L.wq's codes)
+static fwk::GemmParams gemm_params(const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, const half_t* W, half_t* C,
+                                   int64_t ldc, int64_t c_bs, int M, int head_rows) {
   fwk::GemmParams p;
   memset(&p, 0, sizeof(p));
   p.A = A; p.lda = lda; p.a_bstride = a_bs;
-  p.W = L.w; p.ldw = L.K;
+  p.W = W; p.ldw = L.K;
   p.bias = L.b;
-  p.res = res; p.ldr = ldr; p.r_bstride = r_bs;
   p.C = C; p.ldc = ldc; p.c_bstride = c_bs;
   p.M = M; p.N = L.N; p.K = L.K;
-  p.act = act;
   p.head_rows = head_rows;
+  return p;
+}
+
+int run_linear(Model* m, const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, half_t* C, int64_t ldc,
+               int64_t c_bs, const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans,
+               int head_rows, hipStream_t st) {
+  fwk::GemmParams p = gemm_params(L, A, lda, a_bs, L.w, C, ldc, c_bs, M, head_rows);
+  p.res = res; p.ldr = ldr; p.r_bstride = r_bs;
+  p.act = act;
   if (fwk::launch_gemm(st ? st : m->stream, p, batch, trans) != 0) {
     set_error("gemm: unsupported shape M=%d N=%d K=%d lda=%lld", M, L.N, L.K, (long long)lda);
     return FW_ERUNTIME;
@@ -767,14 +775,7 @@ int run_linear(Model* m, const LinearW& L, const half_t* A, int64_t lda, int64_t
 int run_linear_layers(Model* m, const LinearW& L0, int n_layers, int64_t w_lstride, int64_t b_lstride, const half_t* A,
                       int64_t lda, int64_t a_bs, half_t* C, int64_t ldc, int64_t c_bs, int64_t c_lstride, int M, int batch,
                       bool trans, int head_rows, hipStream_t st) {
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.a_bstride = a_bs;
-  p.W = L0.w; p.ldw = L0.K;
-  p.bias = L0.b;
-  p.C = C; p.ldc = ldc; p.c_bstride = c_bs;
-  p.M = M; p.N = L0.N; p.K = L0.K;
-  p.head_rows = head_rows;
+  fwk::GemmParams p = gemm_params(L0, A, lda, a_bs, L0.w, C, ldc, c_bs, M, head_rows);
   p.n_layers = n_layers; p.w_lstride = w_lstride; p.bias_lstride = b_lstride; p.c_lstride = c_lstride;
   if (fwk::launch_gemm(st ? st : m->stream, p, batch, trans) != 0) {
     set_error("layered gemm: unsupported shape M=%d N=%d K=%d layers=%d", M, L0.N, L0.K, n_layers);
@@ -792,16 +793,10 @@ int run_linear_i8(Model* m, const LinearW& L, const half_t* A, const LNW* ln, ha
   if (!st) st = m->stream;
   if (!xq) { xq = m->ws_xq; xs = m->ws_xs; }
   if (A) fwk::launch_quant_rows(st, A, L.K, ln ? ln->g : nullptr, ln ? ln->b : nullptr, xq, xs, batch * M, L.K);
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = reinterpret_cast<const half_t*>(xq); p.lda = L.K; p.a_bstride = (int64_t)M * L.K;
-  p.W = reinterpret_cast<const half_t*>(L.wq); p.ldw = L.K;
-  p.bias = L.b;
+  fwk::GemmParams p = gemm_params(L, reinterpret_cast<const half_t*>(xq), L.K, (int64_t)M * L.K,
+                                  reinterpret_cast<const half_t*>(L.wq), C, ldc, c_bs, M, head_rows);
   p.res = res; p.ldr = ldr; p.r_bstride = r_bs;
-  p.C = C; p.ldc = ldc; p.c_bstride = c_bs;
-  p.M = M; p.N = L.N; p.K = L.K;
   p.act = act;
-  p.head_rows = head_rows;
   p.a_scale = xs; p.as_bstride = M; p.w_scale = L.wscale;
   if (fwk::launch_gemm(st, p, batch, trans) != 0) {
     set_error("int8 gemm: unsupported shape M=%d N=%d K=%d", M, L.N, L.K);

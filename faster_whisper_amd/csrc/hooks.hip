@@ -210,14 +210,15 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
 
 int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const float* bias, const float* ln_g,
                            const float* ln_b, const float* res, int32_t R, int32_t N, int32_t K, int32_t act,
-                           int32_t use_int8, float* out, float* out_from_frag) {
+                           int32_t form, float* out, float* out_from_frag) {
   FW_CHECK_ARG(fm && x && W && out && out_from_frag, "null argument");
   FW_CHECK_ARG(R >= 1 && N % 32 == 0 && K % 64 == 0, "need R >= 1, N %% 32 == 0, K %% 64 == 0");
   FW_CHECK_ARG((ln_g == nullptr) == (ln_b == nullptr), "ln_g and ln_b go together");
   Model* m = &fm->impl;
   std::lock_guard<std::mutex> lk(m->mu);
   FW_HIP(hipSetDevice(m->device));
-  if (use_int8 == 1 && (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || ln_g)) {
+  const bool i8 = form == 1;   // (1 is no DecLinForm: the int8 kernel on an int8_float16 model)
+  if (i8 && (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || ln_g)) {
     set_error("int8 decoder-linear test needs an int8_float16 model and no LayerNorm");
     return FW_EINVAL;
   }
@@ -228,7 +229,7 @@ int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const f
   half_t *d_res = nullptr, *d_bias = nullptr, *d_out;
   int rc;
   if ((res && (rc = db.upload_f16(&d_res, res, (size_t)R * N))) || (rc = db.alloc(&d_out, (size_t)R * N))) return rc;
-  if (use_int8 == 1) {
+  if (i8) {
     int8_t *d_wq, *d_xq;
     float *d_ws, *d_xs;
     half_t* d_x;
@@ -274,16 +275,11 @@ int32_t fw_test_dec_linear(fw_model* fm, const float* x, const float* W, const f
   } else if (bias) {
     if ((rc = db.upload_f16(&d_bias, bias, N))) return rc;
   }
-  const half_t *xfp = (const half_t*)d_xf, *wfp = (const half_t*)d_wf;
-  // use_int8 >= 10: the GEMM-shaped kernel of merged runs (dec_gemm_big_kernel), workgroup shape use_int8 - 10,
-  // whatever the row count; 5: the skinny kernel whatever the row count (the reference of the bit-identity test).
-  const int lr =
-      use_int8 >= 10 ? fwd::launch_dec_gemm_big(st, use_int8 - 10, xfp, wfp, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-      : use_int8 == 5 ? fwd::launch_dec_gemm_skinny(st, xfp, wfp, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-      : (use_int8 == 6 || use_int8 == 7) ? fwd::launch_dec_gemm_skinny_tiles(st, use_int8 - 5, xfp, wfp, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act)
-                      : fwd::launch_dec_gemm_frag(st, xfp, wfp, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act);
-  if (lr != 0) {
-    set_error("decoder linear: unsupported shape R=%d N=%d K=%d", R, N, K);
+  // form: fwd::DecLinForm (0: the product's choice; 5: the skinny kernel whatever the row count, the reference of the
+  // bit-identity test; 6 / 7: its tile groupings; 10 + cfg: the GEMM-shaped kernel of merged runs)
+  const fwd::DecLin lin{(const half_t*)d_xf, (const half_t*)d_wf, d_bias, d_s1, d_cf, d_res, N, d_out, N, d_of, R, N, K, act};
+  if (fwd::launch_dec_linear(st, lin, form) != 0) {
+    set_error("decoder linear: unsupported shape R=%d N=%d K=%d (form %d)", R, N, K, form);
     return FW_ERUNTIME;
   }
   if ((rc = download_f16(st, out, d_out, (size_t)R * N))) return rc;
@@ -319,6 +315,21 @@ int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max
   *want = cap.want;
   *run_cap = cap.run_cap;
   return cap.rows_fit && cap.cache_fits ? 1 : 0;
+}
+
+// host-only: the form a decoder linear takes (dec_kernels.hip: dec_linear_plan); needs no device
+int32_t fw_test_dec_linear_plan(int32_t R, int32_t N, int32_t K, int32_t ldo, int32_t ldr, int32_t compute_type,
+                                int32_t form, int32_t out[6]) {
+  const fwd::DecLinPlan p = fwd::dec_linear_plan(R, N, K, ldo, ldr, compute_type, form);
+  const int32_t f[6] = {p.family, p.cfg, p.row_tiles, p.col_tiles, p.chunk, p.waves};
+  memcpy(out, f, sizeof(f));
+  return FW_OK;
+}
+
+// host-only: the form a decode step's self-attention takes (dec_kernels.hip: self_attn_form); needs no device
+int32_t fw_test_self_attn_form(int32_t n_ctx, int32_t cache_ctx, int32_t d, int32_t R_total, int32_t kmul, int32_t H,
+                               int32_t chunks, int32_t knob) {
+  return fwd::self_attn_form(n_ctx, cache_ctx, d, R_total, kmul, H, chunks, knob);
 }
 
 // host-only: what model creation checks of a blob before it binds it (engine.hip), on a host copy; needs no device
@@ -540,9 +551,7 @@ int32_t fw_bench_dec_linear_epi(fw_model* fm, int32_t R, int32_t N, int32_t K, i
     const half_t* r = res ? o : nullptr;
     const half_t* b = lnf ? nullptr : dB;
     const float *s1 = lnf ? dS : nullptr, *cf = lnf ? dC : nullptr;
-    if (variant >= 10) return fwd::launch_dec_gemm_big(st, variant - 10, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
-    if (variant == 5) return fwd::launch_dec_gemm_skinny(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
-    return fwd::launch_dec_gemm_frag(st, dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act);
+    return fwd::launch_dec_linear(st, fwd::DecLin{dX, w, b, s1, cf, r, N, op, N, of, R, N, K, act}, variant);
   }, &ms);
   if (rc == LAUNCH_REFUSED) { set_error("fw_bench_dec_linear_epi: unsupported shape / variant"); return FW_EINVAL; }
   if (rc) return rc;

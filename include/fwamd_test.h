@@ -19,13 +19,14 @@ int32_t fw_test_gemm(fw_model* m, const float* A, const float* W, const float* b
 /* one decoder linear exactly as a decode step runs it (fragment-major operands, LayerNorm folded when ln_g/ln_b are
  * given, GELU when act = 1, residual added last): x [R][K], W [N][K], bias [N] | NULL, res [R][N] | NULL ->
  * out [R][N] (row-major result) and out_from_frag [R][N] (the fragment-major copy the next linear reads, un-permuted
- * on the host).  use_int8 = 0: what a decode step launches for this row count; 1: the int8_float16 form (needs an
- * int8_float16 model; ln must be NULL); 5: the register-streaming (skinny) kernel whatever the row count, 6 / 7: that kernel with one tile / 2 x 2 tiles per
- * workgroup; 10 + cfg: the GEMM-shaped kernel of
- * merged runs (dec_gemm_big_kernel) with workgroup shape cfg, whatever the row count.  0, 5, 6, 7, 10.. return the same bits. */
+ * on the host).  form = 0: what a decode step launches for this row count; 1: the int8_float16 form (needs an
+ * int8_float16 model; ln must be NULL); 5: the register-streaming (skinny) kernel whatever the row count, 6 / 7: that
+ * kernel with one tile / 2 x 2 tiles per workgroup; 10 + cfg: the GEMM-shaped kernel of merged runs
+ * (dec_gemm_big_kernel) with workgroup shape cfg, whatever the row count; any other form is refused.  0, 5, 6, 7, 10..
+ * return the same bits. */
 int32_t fw_test_dec_linear(fw_model* m, const float* x, const float* W, const float* bias, const float* ln_g,
                            const float* ln_b, const float* res, int32_t R, int32_t N, int32_t K, int32_t act,
-                           int32_t use_int8, float* out, float* out_from_frag);
+                           int32_t form, float* out, float* out_from_frag);
 /* the vocabulary projection of a decode step: x [R][d] raw residual rows -> float32 logits [R][n_vocab] (final
  * LayerNorm folded in fp16 mode, applied by the row quantiser in int8_float16 mode), with the model's own weights */
 int32_t fw_test_dec_logits(fw_model* m, const float* x, int32_t R, float* out);
@@ -203,7 +204,7 @@ int32_t fw_bench_attention(fw_model* m, int32_t B, int32_t H, int32_t T, int32_t
 int32_t fw_bench_resample(int32_t device_index, const float* x, int64_t n, int32_t rate_in, int32_t rate_out,
                           int32_t taps_per_phase, double beta, int32_t quantize_s16, int32_t iters, float* ms_out);
 
-/* rows from which a decode run's per-layer linears take the GEMM-shaped kernel (dec_kernels.hip: DEC_BIG_MIN_ROWS);
+/* rows from which a decode run's per-layer linears take the GEMM-shaped kernel (dec_kernels.hip: dec_linear_plan's table);
  * bench.py prices the decoder linears against the MFMA roof from this row count on, against HBM below */
 int32_t fw_dec_big_min_rows(void);
 /* the same per linear: role 0 qkv, 1 d x d (out / cross-q / cross-out), 2 ffn1, 3 ffn2 (< 0: the lowest of the four);
@@ -233,6 +234,19 @@ int64_t fw_test_idle_lead_chunks(int64_t queued, int32_t n_queued, int32_t encod
 int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max_beam, int64_t self_cap, int32_t B,
                              int32_t sampling, int32_t beam_size, int32_t num_hypotheses, int32_t ctx,
                              int64_t* rows_per_chunk, int64_t* want, int64_t* run_cap);
+/* host-only (no device needed): the kernel form a decoder linear of R rows and [N][K] weights takes (dec_kernels.hip:
+ * dec_linear_plan, the one place that decides it); ldo / ldr: row strides of the output and the residual in elements
+ * (ldr = 0: no residual); compute_type 0 float16, 1 int8_float16; form as in fw_test_dec_linear (0, 5, 6, 7, 10 + cfg).
+ * out[0] family (0 refused, 1 the skinny kernel — the int8 kernel counts as skinny —, 2 the GEMM-shaped kernel),
+ * out[1] cfg of the GEMM-shaped kernel (-1 otherwise), out[2] / out[3] / out[4] skinny: 16 x 16 row tiles / column tiles
+ * per workgroup and k-steps of loads in flight per wave (0 otherwise), out[5] waves K is split over (4 | 8) */
+int32_t fw_test_dec_linear_plan(int32_t R, int32_t N, int32_t K, int32_t ldo, int32_t ldr, int32_t compute_type,
+                                int32_t form, int32_t out[6]);
+/* host-only (no device needed): the form (1 first, 2 latency, 3 throughput) the decode self-attention takes for `chunks`
+ * chunks of kmul rows and H heads under knob 2's value `knob`; n_ctx / cache_ctx / d / R_total: the cache geometry as in
+ * fw_test_dec_self_attn (R_total = cache slots per layer) */
+int32_t fw_test_self_attn_form(int32_t n_ctx, int32_t cache_ctx, int32_t d, int32_t R_total, int32_t kmul, int32_t H,
+                               int32_t chunks, int32_t knob);
 /* host-only (no device needed): the checks model creation makes of a weight blob before it binds it, on a HOST copy of
  * `bytes` bytes — header (magic, version, size, config, compute type, layout generation), then for every tensor the
  * weight list expects for that config and compute type: present, dtype, ndim / dims (the stored extent of fragment-major

@@ -37,8 +37,9 @@ static void run(int cfg, int R, int N, int K, bool lnf) {
   hipMemset(B, 0, N * 2); hipMemset(S1, 0, N * 4); hipMemset(CF, 0, N * 4);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   auto go = [&](int i) {
-    return fwd::launch_dec_gemm_big(nullptr, cfg, X, W + (size_t)(i % 8) * nw, lnf ? nullptr : B, lnf ? S1 : nullptr,
-                                    lnf ? CF : nullptr, nullptr, 0, O, N, nullptr, R, N, K, 0);
+    return fwd::launch_dec_linear(nullptr, fwd::DecLin{X, W + (size_t)(i % 8) * nw, lnf ? nullptr : B, lnf ? S1 : nullptr,
+                                                       lnf ? CF : nullptr, nullptr, 0, O, N, nullptr, R, N, K, 0},
+                                  fwd::DEC_LIN_BIG + cfg);
   };
   if (go(0) != 0) { printf("cfg %d: shape refused\n", cfg); return; }
   hipDeviceSynchronize();

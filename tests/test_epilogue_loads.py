@@ -119,7 +119,7 @@ def test_encoder_gemm_epilogue_loads_are_grouped(trans, layered):
     assert n == 0, name
 
 
-# dec_gemm_big_kernel<LNF, S, WM, WN, FB, KC, NST>: the workgroup shapes of DEC_BIG_RULES (dec_kernels.hip: launch_dec_gemm_big)
+# dec_gemm_big_kernel<LNF, S, WM, WN, FB, KC, NST>: its workgroup shapes (dec_kernels.hip: BIG_SHAPES)
 @pytest.mark.parametrize("lnf", [0, 1])
 @pytest.mark.parametrize("cfg", [0, 1, 2])
 def test_dec_linear_big_epilogue_loads_are_grouped(cfg, lnf):

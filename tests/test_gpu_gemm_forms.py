@@ -422,7 +422,7 @@ def test_one_rounding_encoder_gemm(model, K):
 
 
 # workgroup shapes of dec_gemm_big_kernel (variant 10 + cfg) whose k-steps per stage do not fit K = 128 = 4 k-steps
-# (dec_kernels.hip: big_cfg): the launcher refuses them; at K = 256 all three run
+# (dec_kernels.hip: dec_linear_plan): the launcher refuses them; at K = 256 all three run
 BIG_REFUSED = {128: (10, 11), 256: ()}
 
 

@@ -200,6 +200,95 @@ def test_run_capacity_is_stated_once():
     assert n > 1000
 
 
+def test_decoder_linear_plan_states_the_products_choice():
+    """Which kernel form a decoder linear takes (csrc/dec_kernels.hip: dec_linear_plan, through the host-only hook
+    fw_test_dec_linear_plan — no device involved).  The GPU tests force a form and compare bits; this one states which form
+    the PRODUCT chooses, as literal expectations: the measured crossover rows of the table, the fit conditions of the
+    GEMM-shaped kernel (a rule whose shape does not fit K stays skinny), the tile grouping and the wave count."""
+    import ctypes as C
+    from faster_whisper_amd import _lib
+    lib = _lib.load()
+    REFUSED = (0, -1, 0, 0, 0, 0)
+
+    def plan(R, N, K, form=0, ldo=None, ldr=0, int8=0):
+        out = (C.c_int32 * 6)()
+        assert lib.fw_test_dec_linear_plan(R, N, K, N if ldo is None else ldo, ldr, int8, form, out) == 0
+        return tuple(out)
+
+    def one(waves=4):
+        return (1, -1, 1, 1, 10, waves)       # skinny, one 16 x 16 tile per workgroup, 10 k-steps in flight
+
+    def two(waves=4):
+        return (1, -1, 2, 2, 5, waves)        # skinny, 2 x 2 tiles
+
+    def big(cfg, slices=4):
+        return (2, cfg, 0, 0, 0, slices)
+
+    want = {
+        (3840, 1280): {639: two(), 640: big(2), 1279: big(2), 1280: big(0)},                          # large-v3 qkv
+        (1280, 1280): {5: one(), 16: one(), 17: one(), 96: one(), 97: two(), 1087: two(), 1088: big(1)},   # d x d
+        (5120, 1280): {16: one(), 17: two(), 511: two(), 512: big(2), 1280: big(0)},                  # ffn1
+        (1280, 5120): {80: one(8), 831: two(8), 832: big(1, 8)},                                      # ffn2
+        (1152, 384): {640: big(2), 1280: two()},      # tiny qkv: the rule's cfg 0 does not fit K = 384 -> skinny, not cfg 2
+        (384, 1536): {832: two(), 1088: big(1)},      # tiny ffn2 has the role d x d
+        (2048, 512): {512: two(), 1088: big(1)},      # base ffn1 has the role d x d
+    }
+    for (N, K), rows in want.items():
+        for R, w in rows.items():
+            assert plan(R, N, K) == w, (R, N, K)
+    # the shapes tests/test_gpu_gemm_forms.py: BIG_REFUSED states: K = 128 takes workgroup shape 2 only, K = 256 all three
+    for R in (80, 333):
+        assert [plan(R, 256, 128, form=10 + c) for c in range(3)] == [REFUSED, REFUSED, big(2)]
+        assert [plan(R, 256, 256, form=10 + c) for c in range(3)] == [big(0), big(1), big(2)]
+    assert plan(1088, 1280, 1280, ldo=1284) == two()             # row segments of the output not 16 bytes
+    assert plan(1088, 1280, 1280, ldr=1284) == two()             # ... of the residual
+    assert plan(1088, 1280, 1280, ldr=1280) == big(1)
+    assert plan(1088, 1280, 1280, form=11, ldo=1284) == REFUSED  # a forced form that does not fit is refused
+    for form in (0, 5, 6, 7, 10, 11, 12):
+        assert plan(80, 1280, 1296, form=form) == REFUSED        # K % 32 != 0
+        assert plan(0, 1280, 1280, form=form) == REFUSED
+    assert plan(80, 1280, 1280, form=13) == REFUSED and plan(80, 1280, 1280, form=2) == REFUSED   # no such form
+    # forced skinny forms: 5 groups by row count whatever the table says, 6 / 7 are one tile / 2 x 2 at any row count
+    assert plan(1088, 1280, 1280, form=5) == two() and plan(80, 1280, 1280, form=5) == one()
+    for R in (1, 80, 1088, 2000):
+        assert plan(R, 1280, 1280, form=6) == one() and plan(R, 1280, 1280, form=7) == two()
+        assert plan(R, 1280, 5120, form=6) == one(8) and plan(R, 1280, 5120, form=7) == two(8)
+    # int8_float16: 4 x 4 tiles from 1 024 rows when N % 64 == 0, 2 x 2 tiles otherwise; k-steps of 64
+    assert plan(1023, 1280, 1280, int8=1) == two() and plan(1024, 1280, 1280, int8=1) == (1, -1, 4, 4, 5, 4)
+    assert plan(1024, 1280, 5120, int8=1) == (1, -1, 4, 4, 3, 8)
+    assert plan(1024, 1312, 1280, int8=1) == two()
+    assert plan(80, 1280, 1312, int8=1) == REFUSED and plan(0, 1280, 1280, int8=1) == REFUSED
+    # what bench.py prices by: the exported row count of a role = the lowest row count at which the plan of that role's
+    # large-v3 shape leaves the 2 x 2 grouping (fp16: for the GEMM-shaped kernel; int8: for 4 x 4 tiles)
+    shapes = ((3840, 1280), (1280, 1280), (5120, 1280), (1280, 5120))
+    for role, (N, K) in enumerate(shapes):
+        first_big = next(R for R in range(1, 4096) if plan(R, N, K)[0] == 2)
+        assert lib.fw_dec_big_min_rows_of(role, 0) == first_big == (640, 1088, 512, 832)[role]
+        first_44 = next(R for R in range(1, 4096) if plan(R, N, K, int8=1)[2] == 4)
+        assert lib.fw_dec_big_min_rows_of(role, 1) == first_44 == 1024
+    assert lib.fw_dec_big_min_rows() == lib.fw_dec_big_min_rows_of(-1, 0) == 512
+
+
+def test_self_attention_form_is_stated_once():
+    """The form the decode self-attention takes (csrc/dec_kernels.hip: self_attn_form, through the host-only hook
+    fw_test_self_attn_form): 1 where the second form is unusable (slot-table stride not a multiple of 4, a layer's cache
+    of 4 GB or more), else by launch size — 2 (latency) up to 8 rows per chunk and 768 workgroups, 3 (throughput) beyond."""
+    from faster_whisper_amd import _lib
+    f = _lib.load().fw_test_self_attn_form
+
+    def form(n_ctx=448, cache_ctx=448, d=1280, R_total=1600, kmul=5, H=20, chunks=16, knob=0):
+        return f(n_ctx, cache_ctx, d, R_total, kmul, H, chunks, knob)
+
+    assert form(n_ctx=446, cache_ctx=446) == 1 and form(n_ctx=446, cache_ctx=446, knob=3) == 1
+    # 4096 slots x 512 positions x 1024 x 2 bytes = 2^32 exactly
+    assert form(cache_ctx=512, n_ctx=512, d=1024, R_total=4096) == 1
+    assert form(cache_ctx=512, n_ctx=512, d=1024, R_total=4095) == 2
+    assert form(chunks=38) == 2 and form(chunks=39) == 3            # 20 heads x 38 = 760 <= 768 < 780
+    assert form(kmul=8) == 2 and form(kmul=9) == 3
+    assert form(kmul=9, knob=2) == 3 and form(kmul=8, knob=2, chunks=400) == 2
+    assert form(knob=1) == 1 and form(knob=3) == 3
+
+
 def test_speech_timestamps_skip_ahead_equals_every_window():
     """round 6: get_speech_timestamps jumps over the windows that cannot change its state (an 8 h recording is 900 000
     windows); the plain walk over every window — the reference's loop, vad.py:85-160 — must give the same spans for any
