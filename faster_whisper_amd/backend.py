@@ -397,8 +397,10 @@ class Whisper:
             self._tls.replica = r
         return r
 
-    def _as_encoded(self, features: StorageView) -> StorageView:
+    def _as_encoded(self, features) -> StorageView:
         """generate/detect_language/align accept an encoder output or raw features (like CTranslate2)."""
+        if not isinstance(features, StorageView):
+            features = StorageView.from_array(features)
         if features._handle is not None or features._parts:
             return features
         a = np.asarray(features._array)
@@ -410,6 +412,17 @@ class Whisper:
             _lib.check(self._lib.fw_tensor_from_host(rep.handle, _lib.ptr(a), a.shape[0], C.byref(h)))
             return StorageView(handle=h, owner=rep, shape=a.shape)
         return self.encode(features)
+
+    @staticmethod
+    def _over_parts(enc: StorageView, call, *per_chunk) -> list:
+        """call(part, *per_chunk arguments of the part's chunks) for every device tensor of an encoder output, in order;
+        the per-chunk results concatenated (an output of at most max_batch chunks is its own single part)"""
+        out, b0 = [], 0
+        for part in enc._parts or [enc]:
+            b1 = b0 + part._shape[0]
+            out.extend(call(part, *(arg[b0:b1] for arg in per_chunk)))
+            b0 = b1
+        return out
 
     # ---- encode -------------------------------------------------------------------------
     def encode(self, features: StorageView, to_cpu: bool = False) -> StorageView:
@@ -499,28 +512,11 @@ class Whisper:
                  seed: Optional[int] = None, return_token_logprobs: bool = False) -> List[WhisperGenerationResult]:
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
-        enc = self._as_encoded(features if isinstance(features, StorageView) else StorageView.from_array(features))
-        B = enc._shape[0]
-        if len(prompts) != B:
-            raise ValueError(f"got {len(prompts)} prompts for a batch of {B}")
+        enc = self._as_encoded(features)
+        if len(prompts) != enc._shape[0]:
+            raise ValueError(f"got {len(prompts)} prompts for a batch of {enc._shape[0]}")
         if any(len(p) == 0 for p in prompts):
             raise ValueError("prompts must not be empty")
-        if enc._parts:
-            kw = dict(beam_size=beam_size, patience=patience, num_hypotheses=num_hypotheses,
-                      length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-                      no_repeat_ngram_size=no_repeat_ngram_size, max_length=max_length, return_scores=return_scores,
-                      return_no_speech_prob=return_no_speech_prob,
-                      max_initial_timestamp_index=max_initial_timestamp_index, suppress_blank=suppress_blank,
-                      suppress_tokens=suppress_tokens, sampling_topk=sampling_topk,
-                      sampling_temperature=sampling_temperature, min_new_tokens=min_new_tokens, seed=seed)
-            if return_token_logprobs:
-                kw["return_token_logprobs"] = True
-            out, b0 = [], 0
-            for part in enc._parts:
-                out.extend(self.generate(part, prompts[b0:b0 + part._shape[0]], **kw))
-                b0 += part._shape[0]
-            return out
-        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in prompts], np.int32, np.int32)
         o = _lib.FwGenOpts()
         o.beam_size, o.patience, o.num_hypotheses = int(beam_size), float(patience), int(num_hypotheses)
         o.length_penalty, o.repetition_penalty = float(length_penalty), float(repetition_penalty)
@@ -531,91 +527,87 @@ class Whisper:
         o.suppress_tokens = _lib.as_i32p(sup) if sup.size else None
         o.n_suppress_tokens = int(sup.size)
         o.sampling_topk, o.sampling_temperature = int(sampling_topk), float(sampling_temperature)
-        if seed is None:
-            # CTranslate2 draws from a global generator that advances from call to call; here every sampling call
-            # gets a seed of its own from a per-model counter (explicit seeds reproduce a call exactly)
-            seed = call_seed(next(self._seed_counter))
-        o.seed, o.min_new_tokens = int(seed), int(min_new_tokens)
+        o.min_new_tokens = int(min_new_tokens)
         nh = max(1, int(num_hypotheses))
         ml = max(1, int(max_length))
-        ids = np.zeros((B, nh, ml), dtype=np.int32)
-        lens = np.zeros((B, nh), dtype=np.int32)
-        scores = np.zeros((B, nh), dtype=np.float32)
-        nsp = np.zeros((B,), dtype=np.float32)
-        rep = enc._owner
-        if return_token_logprobs:
-            if not hasattr(self._lib, "fw_generate_lp"):   # an older build loaded through FWAMD_LIB
-                raise RuntimeError("this libfwamd.so has no fw_generate_lp: per-token log-probabilities need a current build")
-            tlp = np.zeros((B, nh, ml), dtype=np.float32)
-            elp = np.zeros((B, nh), dtype=np.float32)
-            _lib.check(self._lib.fw_generate_lp(rep.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B,
-                                                C.byref(o), _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores),
-                                                _lib.as_f32p(nsp), _lib.as_f32p(tlp), _lib.as_f32p(elp)))
-        else:
-            _lib.check(self._lib.fw_generate(rep.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B,
-                                             C.byref(o), _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores),
-                                             _lib.as_f32p(nsp)))
-        out = []
-        for b in range(B):
-            seqs = [ids[b, h, :lens[b, h]].tolist() for h in range(nh)]
-            sc = [float(scores[b, h]) for h in range(nh)] if return_scores else []
-            res = WhisperGenerationResult(seqs, sc, float(nsp[b]) if return_no_speech_prob else 0.0)
+
+        def one_call(enc, prompts):
+            """one engine call: an encoder output of at most max_batch chunks"""
+            B = enc._shape[0]
+            flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in prompts], np.int32, np.int32)
+            # CTranslate2 draws from a global generator that advances from call to call; here every engine call gets a
+            # seed of its own from a per-model counter (explicit seeds reproduce a call exactly)
+            o.seed = int(call_seed(next(self._seed_counter)) if seed is None else seed)
+            ids = np.zeros((B, nh, ml), dtype=np.int32)
+            lens = np.zeros((B, nh), dtype=np.int32)
+            scores = np.zeros((B, nh), dtype=np.float32)
+            nsp = np.zeros((B,), dtype=np.float32)
+            args = (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o),
+                    _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp))
             if return_token_logprobs:
-                res.token_logprobs = [tlp[b, h, :lens[b, h]].tolist() for h in range(nh)]
-                res.end_logprobs = [float(elp[b, h]) for h in range(nh)]
-            out.append(res)
-        return out
+                if not hasattr(self._lib, "fw_generate_lp"):   # an older build loaded through FWAMD_LIB
+                    raise RuntimeError("this libfwamd.so has no fw_generate_lp: per-token log-probabilities need a "
+                                       "current build")
+                tlp = np.zeros((B, nh, ml), dtype=np.float32)
+                elp = np.zeros((B, nh), dtype=np.float32)
+                _lib.check(self._lib.fw_generate_lp(*args, _lib.as_f32p(tlp), _lib.as_f32p(elp)))
+            else:
+                _lib.check(self._lib.fw_generate(*args))
+            out = []
+            for b in range(B):
+                seqs = [ids[b, h, :lens[b, h]].tolist() for h in range(nh)]
+                sc = [float(scores[b, h]) for h in range(nh)] if return_scores else []
+                res = WhisperGenerationResult(seqs, sc, float(nsp[b]) if return_no_speech_prob else 0.0)
+                if return_token_logprobs:
+                    res.token_logprobs = [tlp[b, h, :lens[b, h]].tolist() for h in range(nh)]
+                    res.end_logprobs = [float(elp[b, h]) for h in range(nh)]
+                out.append(res)
+            return out
+        return self._over_parts(enc, one_call, prompts)
 
     # ---- detect_language ----------------------------------------------------------------
     def detect_language(self, features: StorageView) -> List[List[Tuple[str, float]]]:
         if not self.is_multilingual:
             raise RuntimeError("detect_language can only be called on multilingual models")
-        enc = self._as_encoded(features if isinstance(features, StorageView) else StorageView.from_array(features))
-        if enc._parts:
-            return [row for part in enc._parts for row in self.detect_language(part)]
-        B, nl = enc._shape[0], self._cfg.n_langs
-        ids = np.zeros((B, nl), dtype=np.int32)
-        probs = np.zeros((B, nl), dtype=np.float32)
-        _lib.check(self._lib.fw_detect_language(enc._owner.handle, enc._handle, B, _lib.as_i32p(ids),
-                                                _lib.as_f32p(probs)))
         names = language_token_strings(self._cfg)
-        return [[(names[int(t) - self._cfg.lang_begin], float(p)) for t, p in zip(ids[b], probs[b])]
-                for b in range(B)]
+
+        def one_call(enc):
+            B, nl = enc._shape[0], self._cfg.n_langs
+            ids = np.zeros((B, nl), dtype=np.int32)
+            probs = np.zeros((B, nl), dtype=np.float32)
+            _lib.check(self._lib.fw_detect_language(enc._owner.handle, enc._handle, B, _lib.as_i32p(ids),
+                                                    _lib.as_f32p(probs)))
+            return [[(names[int(t) - self._cfg.lang_begin], float(p)) for t, p in zip(ids[b], probs[b])]
+                    for b in range(B)]
+        return self._over_parts(self._as_encoded(features), one_call)
 
     # ---- align --------------------------------------------------------------------------
     def align(self, features: StorageView, start_sequence: Sequence[int], text_tokens: List[List[int]],
               num_frames: Union[int, Sequence[int]], *, median_filter_width: int = 7
               ) -> List[WhisperAlignmentResult]:
-        enc = self._as_encoded(features if isinstance(features, StorageView) else StorageView.from_array(features))
-        B = enc._shape[0]
-        if len(text_tokens) != B:
-            raise ValueError(f"got {len(text_tokens)} token lists for a batch of {B}")
-        nf = np.asarray([num_frames] * B if isinstance(num_frames, int) else list(num_frames), dtype=np.int32)
-        if nf.shape[0] != B:
+        enc = self._as_encoded(features)
+        if len(text_tokens) != enc._shape[0]:
+            raise ValueError(f"got {len(text_tokens)} token lists for a batch of {enc._shape[0]}")
+        num_frames = np.asarray([num_frames] * enc._shape[0] if isinstance(num_frames, int) else list(num_frames),
+                                dtype=np.int32)
+        if num_frames.shape[0] != enc._shape[0]:
             raise ValueError("num_frames must be an int or have one entry per batch item")
-        if enc._parts:
-            out, b0 = [], 0
-            for part in enc._parts:
-                n = part._shape[0]
-                out.extend(self.align(part, start_sequence, text_tokens[b0:b0 + n], nf[b0:b0 + n].tolist(),
-                                      median_filter_width=median_filter_width))
-                b0 += n
-            return out
         start = np.asarray(list(start_sequence), dtype=np.int32)
-        flat, offs = _ragged([np.asarray(t, dtype=np.int32) for t in text_tokens], np.int32, np.int32)
-        max_pairs = int(max((len(t) for t in text_tokens), default=0)) + self._cfg.n_audio_ctx + 2
-        pairs = np.zeros((B, max_pairs, 2), dtype=np.int32)
-        npairs = np.zeros((B,), dtype=np.int32)
-        probs = np.zeros((max(1, flat.shape[0]),), dtype=np.float32)
-        _lib.check(self._lib.fw_align(enc._owner.handle, enc._handle, _lib.as_i32p(start), start.shape[0],
-                                      _lib.as_i32p(flat), _lib.as_i32p(offs), _lib.as_i32p(nf), B,
-                                      int(median_filter_width), max_pairs, _lib.as_i32p(pairs),
-                                      _lib.as_i32p(npairs), _lib.as_f32p(probs)))
-        out = []
-        for b in range(B):
-            al = [(int(a), int(t)) for a, t in pairs[b, :npairs[b]]]
-            out.append(WhisperAlignmentResult(al, probs[offs[b]:offs[b + 1]].tolist()))
-        return out
+
+        def one_call(enc, text_tokens, nf):
+            B = enc._shape[0]
+            flat, offs = _ragged([np.asarray(t, dtype=np.int32) for t in text_tokens], np.int32, np.int32)
+            max_pairs = int(max((len(t) for t in text_tokens), default=0)) + self._cfg.n_audio_ctx + 2
+            pairs = np.zeros((B, max_pairs, 2), dtype=np.int32)
+            npairs = np.zeros((B,), dtype=np.int32)
+            probs = np.zeros((max(1, flat.shape[0]),), dtype=np.float32)
+            _lib.check(self._lib.fw_align(enc._owner.handle, enc._handle, _lib.as_i32p(start), start.shape[0],
+                                          _lib.as_i32p(flat), _lib.as_i32p(offs), _lib.as_i32p(nf), B,
+                                          int(median_filter_width), max_pairs, _lib.as_i32p(pairs),
+                                          _lib.as_i32p(npairs), _lib.as_f32p(probs)))
+            return [WhisperAlignmentResult([(int(a), int(t)) for a, t in pairs[b, :npairs[b]]],
+                                           probs[offs[b]:offs[b + 1]].tolist()) for b in range(B)]
+        return self._over_parts(enc, one_call, text_tokens, num_frames)
 
     # ---- measurement --------------------------------------------------------------------
     def _primary_of(self, replica: int) -> int:

@@ -26,7 +26,7 @@ import json
 import logging
 import os
 import zlib
-from dataclasses import dataclass
+from dataclasses import dataclass, field, fields
 from math import ceil
 from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
@@ -126,6 +126,40 @@ class TranscriptionInfo:
     all_language_probs: Optional[List[Tuple[str, float]]]
     transcription_options: TranscriptionOptions
     vad_options: object
+
+
+def _transcription_options(args, tokenizer: "Tokenizer", **derived) -> TranscriptionOptions:
+    """The TranscriptionOptions of a transcribe() call.  args: the call's arguments by name.  Every field takes the
+    argument of its own name unless `derived` gives its value (`temperatures`, and whatever the driver fixes or has
+    resolved); a non-empty suppress_tokens is expanded by get_suppressed_tokens."""
+    values = {**args, **derived}
+    if values["suppress_tokens"]:
+        values["suppress_tokens"] = get_suppressed_tokens(tokenizer, values["suppress_tokens"])
+    return TranscriptionOptions(**{f.name: values[f.name] for f in fields(TranscriptionOptions)})
+
+
+def _per_recording(value, n, name, is_single):
+    """one value for all recordings, or a sequence with one entry per recording -> a list of n"""
+    if is_single(value):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"{name} has {len(value)} entries for {n} recordings")
+    return value
+
+
+def _avg_logprob(result, length_penalty: float) -> float:
+    """average log-prob per token (the closing <eot> counted) of a generate() result's first hypothesis: its score with
+    the length normalisation undone (transcribe.py:241-246, :1462-1467)"""
+    n = len(result.sequences_ids[0])
+    return result.scores[0] * (n ** length_penalty) / (n + 1)
+
+
+def _make_segment(values: dict, token_logprobs: Optional[List[float]] = None) -> Segment:
+    """a Segment, or with token_logprobs (what a token_logprobs=True call attaches to its sub-segments) a ScoredSegment"""
+    if token_logprobs is None:
+        return Segment(**values)
+    return ScoredSegment(token_logprobs=token_logprobs, **values)
 
 
 def pad_or_trim(array: np.ndarray, length: int = 3000, *, axis: int = -1) -> np.ndarray:
@@ -363,6 +397,47 @@ class WhisperModel:
             self.logger.warning("Could not load preprocessor config: %s", e)
         return config
 
+    # ---- what every transcribe entry point decides the same way ----
+    def _load_audio(self, audio) -> np.ndarray:
+        """a path or file object -> its samples at the model's rate, float32 (WAVE and FLAC natively, other containers
+        through PyAV); an array is returned as it is"""
+        if isinstance(audio, np.ndarray):
+            return audio
+        from .audio import decode_audio
+        return decode_audio(audio, sampling_rate=self.feature_extractor.sampling_rate,
+                            device_index=_resample_device_index(self.model))
+
+    def _effective_multilingual(self, multilingual: bool) -> bool:
+        if multilingual and not self.model.is_multilingual:
+            self.logger.warning("The current model is English-only but the multilingual parameter is set to"
+                                "True; setting to False instead.")
+            return False
+        return multilingual
+
+    def _effective_language(self, language: str) -> str:
+        """the language a call that names `language` decodes in"""
+        if not self.model.is_multilingual and language != "en":
+            self.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
+                                "using 'en' instead." % language)
+            return "en"
+        return language
+
+    def _max_length_for(self, prompt: List[int], max_new_tokens: Optional[int]) -> int:
+        """generate()'s max_length for `prompt`"""
+        max_length = len(prompt) + max_new_tokens if max_new_tokens is not None else self.max_length
+        if max_length > self.max_length:
+            raise ValueError(
+                f"The length of the prompt is {len(prompt)}, and the `max_new_tokens` {max_length - len(prompt)}. "
+                f"Thus, the combined length of the prompt and `max_new_tokens` is: {max_length}. This exceeds the "
+                f"`max_length` of the Whisper model: {self.max_length}. You should either reduce the length of your "
+                f"prompt, or reduce the value of `max_new_tokens`, so that their combined length is less that "
+                f"{self.max_length}.")
+        return max_length
+
+    def _workers(self) -> int:
+        """worker replicas of the backend = batches (or recordings) the host drivers may keep in flight"""
+        return int(getattr(self.model, "inter_threads", 1) or 1)
+
     # ---- sequential path (SURVEY.md section 8f-2; reference transcribe.py:747-1022, :1103-1389) ----
     def transcribe(self, audio: np.ndarray, language: Optional[str] = None, task: str = "transcribe",
                    log_progress: bool = False, beam_size: int = 5, best_of: int = 5, patience: float = 1,
@@ -390,16 +465,12 @@ class WhisperModel:
         attempt at rung t of the ladder for the window at frame `seek` samples with backend.attempt_seed(sampling_seed,
         seek, t): the same recording with the same seed gives the same transcript whatever else the model decodes before
         or beside it.  None (the default): every sampling call takes the next seed of the model's call counter."""
+        args = dict(locals())               # the call's arguments by name
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
-        if multilingual and not self.model.is_multilingual:
-            self.logger.warning("The current model is English-only but the multilingual parameter is set to"
-                                "True; setting to False instead.")
-            multilingual = False
-        if not isinstance(audio, np.ndarray):
-            from .audio import decode_audio   # path / file object: WAVE and FLAC natively, other containers through PyAV
-            audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(self.model))
+        multilingual = self._effective_multilingual(multilingual)
+        audio = self._load_audio(audio)
         duration = audio.shape[0] / sr
         duration_after_vad = duration
         speech_chunks = None
@@ -427,28 +498,11 @@ class WhisperModel:
                     features=features[..., seek:], language_detection_segments=language_detection_segments,
                     language_detection_threshold=language_detection_threshold)
         else:
-            if not self.model.is_multilingual and language != "en":
-                self.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
-                                    "using 'en' instead." % language)
-                language = "en"
-            language_probability = 1
+            language, language_probability = self._effective_language(language), 1
         tokenizer = self.make_tokenizer(task=task, language=language)
-        options = TranscriptionOptions(
-            beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            compression_ratio_threshold=compression_ratio_threshold,
-            condition_on_previous_text=condition_on_previous_text,
-            prompt_reset_on_temperature=prompt_reset_on_temperature,
-            temperatures=(temperature if isinstance(temperature, (list, tuple)) else [temperature]),
-            initial_prompt=initial_prompt, prefix=prefix, suppress_blank=suppress_blank,
-            suppress_tokens=(get_suppressed_tokens(tokenizer, suppress_tokens) if suppress_tokens
-                             else suppress_tokens),
-            without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-            word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
-            clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
-            hotwords=hotwords)
+        options = _transcription_options(
+            args, tokenizer, multilingual=multilingual,
+            temperatures=(temperature if isinstance(temperature, (list, tuple)) else [temperature]))
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
                                           **(dict(token_logprobs=True) if token_logprobs else {}),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
@@ -488,8 +542,8 @@ class WhisperModel:
         n = len(audios)
         if n == 0:
             return []
-        languages = self._per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
-        prompts = self._per_recording(
+        languages = _per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
+        prompts = _per_recording(
             initial_prompt, n, "initial_prompt",
             lambda v: v is None or isinstance(v, str)
             or (len(v) != 0 and all(isinstance(t, (int, np.integer)) for t in v)))
@@ -499,7 +553,7 @@ class WhisperModel:
         elif isinstance(sampling_seed, (int, np.integer)):
             seeds = [recording_seed(int(sampling_seed), i) for i in range(n)]
         else:
-            seeds = self._per_recording(sampling_seed, n, "sampling_seed", lambda v: False)
+            seeds = _per_recording(sampling_seed, n, "sampling_seed", lambda v: False)
 
         def one(i):
             segments, info = self.transcribe(audios[i], language=languages[i], initial_prompt=prompts[i],
@@ -507,23 +561,13 @@ class WhisperModel:
                                              **transcribe_kwargs)
             return list(segments), info
 
-        workers = min(n, int(getattr(self.model, "inter_threads", 1) or 1))
+        workers = min(n, self._workers())
         if workers <= 1:
             return [one(i) for i in range(n)]
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as pool:
             futures = [pool.submit(one, i) for i in range(n)]
             return [f.result() for f in futures]
-
-    @staticmethod
-    def _per_recording(value, n, name, is_single):
-        """one value for all recordings, or a sequence with one entry per recording -> a list of n"""
-        if is_single(value):
-            return [value] * n
-        value = list(value)
-        if len(value) != n:
-            raise ValueError(f"{name} has {len(value)} entries for {n} recordings")
-        return value
 
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
@@ -532,7 +576,7 @@ class WhisperModel:
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
         where the next window starts."""
-        from .words import get_end, is_segment_anomaly, next_words_segment
+        from .words import seek_after_words
         fe = self.feature_extractor
         tpf, fps = fe.time_per_frame, self.frames_per_second
         content_frames = features.shape[-1] - 1
@@ -604,42 +648,14 @@ class WhisperModel:
                     self.add_word_timestamps([current], tokenizer, encoder_output, segment_size,
                                              options.prepend_punctuations, options.append_punctuations,
                                              last_speech_timestamp=last_speech_timestamp)
-                    if not single_timestamp_ending:
-                        last_word_end = get_end(current)
-                        if last_word_end is not None and last_word_end > time_offset:
-                            seek = round(last_word_end * fps)
-                    threshold = options.hallucination_silence_threshold
-                    if threshold is not None:
-                        # leading silence before a probable hallucination: re-decode from where speech starts
-                        first = next_words_segment(current)
-                        if first is not None and is_segment_anomaly(first):
-                            gap = first["start"] - time_offset
-                            if gap > threshold:
-                                seek = previous_seek + round(gap * fps)
-                                continue
-                        # a probable hallucination surrounded by silence (or more of them): cut there
-                        hal_last_end = last_speech_timestamp
-                        for si, seg in enumerate(current):
-                            if not seg["words"]:
-                                continue
-                            if is_segment_anomaly(seg):
-                                nxt = next_words_segment(current[si + 1:])
-                                hal_next_start = nxt["words"][0]["start"] if nxt is not None \
-                                    else time_offset + segment_duration
-                                silence_before = (seg["start"] - hal_last_end > threshold or seg["start"] < threshold
-                                                  or seg["start"] - time_offset < 2.0)
-                                silence_after = (hal_next_start - seg["end"] > threshold or is_segment_anomaly(nxt)
-                                                 or window_end_time - seg["end"] < 2.0)
-                                if silence_before and silence_after:
-                                    seek = round(max(time_offset + 1, seg["start"]) * fps)
-                                    if content_duration - seg["end"] < threshold:
-                                        seek = content_frames
-                                    current[si:] = []
-                                    break
-                            hal_last_end = seg["end"]
-                    last_word_end = get_end(current)
-                    if last_word_end is not None:
-                        last_speech_timestamp = last_word_end
+                    seek, last_speech_timestamp, again = seek_after_words(
+                        current, seek=seek, previous_seek=previous_seek, time_offset=time_offset,
+                        segment_duration=segment_duration, window_end_time=window_end_time,
+                        content_frames=content_frames, content_duration=content_duration, frames_per_second=fps,
+                        single_timestamp_ending=single_timestamp_ending,
+                        threshold=options.hallucination_silence_threshold, last_speech_timestamp=last_speech_timestamp)
+                    if again:
+                        continue
 
                 for seg in current:
                     text = tokenizer.decode(seg["tokens"])
@@ -647,14 +663,11 @@ class WhisperModel:
                         continue
                     all_tokens.extend(seg["tokens"])
                     idx += 1
-                    fields = dict(id=idx, seek=previous_seek, start=seg["start"], end=seg["end"], text=text,
+                    values = dict(id=idx, seek=previous_seek, start=seg["start"], end=seg["end"], text=text,
                                   tokens=seg["tokens"], temperature=temperature, avg_logprob=avg_logprob,
                                   compression_ratio=compression_ratio, no_speech_prob=result.no_speech_prob,
                                   words=([Word(**w) for w in seg["words"]] if options.word_timestamps else None))
-                    if token_logprobs:
-                        yield ScoredSegment(token_logprobs=seg["token_logprobs"], **fields)
-                    else:
-                        yield Segment(**fields)
+                    yield _make_segment(values, seg.get("token_logprobs"))
 
                 if not options.condition_on_previous_text or temperature > options.prompt_reset_on_temperature:
                     prompt_reset_since = len(all_tokens)
@@ -674,14 +687,7 @@ class WhisperModel:
         first frame; None: no seed is passed, the backend draws one from its call counter.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
         max_initial_timestamp_index = int(round(options.max_initial_timestamp / self.time_precision))
-        max_length = len(prompt) + options.max_new_tokens if options.max_new_tokens is not None else self.max_length
-        if max_length > self.max_length:
-            raise ValueError(
-                f"The length of the prompt is {len(prompt)}, and the `max_new_tokens` {max_length - len(prompt)}. "
-                f"Thus, the combined length of the prompt and `max_new_tokens` is: {max_length}. This exceeds the "
-                f"`max_length` of the Whisper model: {self.max_length}. You should either reduce the length of your "
-                f"prompt, or reduce the value of `max_new_tokens`, so that their combined length is less that "
-                f"{self.max_length}.")
+        max_length = self._max_length_for(prompt, options.max_new_tokens)
         attempts, compact = [], []
         chosen = None
         for rung, temperature in enumerate(options.temperatures):
@@ -699,10 +705,8 @@ class WhisperModel:
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
                 max_initial_timestamp_index=max_initial_timestamp_index, **mode,
                 **(dict(return_token_logprobs=True) if token_logprobs else {}))[0]
-            tokens = result.sequences_ids[0]
-            n = len(tokens)
-            avg_logprob = result.scores[0] * (n ** options.length_penalty) / (n + 1)   # undo the length norm
-            compression_ratio = get_compression_ratio(tokenizer.decode(tokens).strip())
+            avg_logprob = _avg_logprob(result, options.length_penalty)
+            compression_ratio = get_compression_ratio(tokenizer.decode(result.sequences_ids[0]).strip())
             attempt = (result, avg_logprob, temperature, compression_ratio)
             attempts.append(attempt)
             retry = False
@@ -878,6 +882,28 @@ class WhisperModel:
         return language, prob, all_probs
 
 
+@dataclass
+class _Recording:
+    """one recording on its way through the batched pipeline: cut into chunks by _split_recording, language (where it
+    is detected) by the entry point's detection pass, the rest by _plan_decode"""
+    audio: np.ndarray
+    clip_timestamps: Optional[List[dict]]       # the caller's split, if any
+    clips: List[dict]                           # the spans the chunks are cut from, in samples
+    audio_chunks: List[np.ndarray]
+    chunks_metadata: List[dict]
+    duration_after_vad: float
+    vad_options: object
+    language: Optional[str] = None
+    language_probability: float = 1
+    all_language_probs: Optional[List[Tuple[str, float]]] = None
+    tokenizer: Optional[Tokenizer] = None
+    options: Optional[TranscriptionOptions] = None
+    info: Optional[TranscriptionInfo] = None
+    # transcribe_many: per chunk, in chunk order, its sub-segments and its word alignment
+    decoded: List[List[dict]] = field(default_factory=list)
+    aligned: List[dict] = field(default_factory=list)
+
+
 class BatchedInferencePipeline:
     def __init__(self, model: WhisperModel):
         self.model = model
@@ -896,14 +922,7 @@ class BatchedInferencePipeline:
                                                if isinstance(options.initial_prompt, str)
                                                else list(options.initial_prompt or [])),
                               without_timestamps=options.without_timestamps, hotwords=options.hotwords)
-        max_length = len(prompt) + options.max_new_tokens if options.max_new_tokens is not None else m.max_length
-        if max_length > m.max_length:
-            raise ValueError(
-                f"The length of the prompt is {len(prompt)}, and the `max_new_tokens` {max_length - len(prompt)}. "
-                f"Thus, the combined length of the prompt and `max_new_tokens` is: {max_length}. This exceeds the "
-                f"`max_length` of the Whisper model: {m.max_length}. You should either reduce the length of your "
-                f"prompt, or reduce the value of `max_new_tokens`, so that their combined length is less that "
-                f"{m.max_length}.")
+        max_length = m._max_length_for(prompt, options.max_new_tokens)
         encoder_output = m.model.encode_pcm(audio_chunks) if audio_chunks is not None else m.encode(features)
         prompts = [prompt.copy() for _ in range(batch_size)]
         if options.multilingual:
@@ -922,22 +941,17 @@ class BatchedInferencePipeline:
             **(dict(return_token_logprobs=True) if token_logprobs else {}))
         output = []
         for r in results:
-            n = len(r.sequences_ids[0])
-            cum = r.scores[0] * (n ** options.length_penalty)
-            output.append(dict(avg_logprob=cum / (n + 1), no_speech_prob=r.no_speech_prob, tokens=r.sequences_ids[0]))
+            output.append(dict(avg_logprob=_avg_logprob(r, options.length_penalty), no_speech_prob=r.no_speech_prob,
+                               tokens=r.sequences_ids[0]))
             if token_logprobs:
                 output[-1].update(token_logprobs=r.token_logprobs[0], end_logprob=r.end_logprobs[0])
         return encoder_output, output
 
     def forward(self, features, tokenizer, chunks_metadata, options, audio_chunks=None):
         encoder_output, outputs = self.generate_segment_batched(features, tokenizer, options, audio_chunks)
-        return self._segment_outputs(outputs, tokenizer, chunks_metadata, options, encoder_output)
-
-    def _segment_outputs(self, outputs, tokenizer, chunks_metadata, options, encoder_output=None):
-        m = self.model
         segmented, sizes = self._split_outputs(outputs, tokenizer, chunks_metadata)
         if options.word_timestamps:
-            self.last_speech_timestamp = m.add_word_timestamps(
+            self.last_speech_timestamp = self.model.add_word_timestamps(
                 segmented, tokenizer, encoder_output, sizes, options.prepend_punctuations,
                 options.append_punctuations, self.last_speech_timestamp)
         return segmented
@@ -988,62 +1002,31 @@ class BatchedInferencePipeline:
         chunk list is block-partitioned over the ranks and rank 0's generator yields ALL segments in
         order (other ranks yield nothing).  fused_features=False reproduces the reference data flow
         (features materialised on the host, then encode())."""
+        args = dict(locals())               # the call's arguments by name
+        from .vad import get_speech_timestamps
         m = self.model
-        sr = m.feature_extractor.sampling_rate
         if token_logprobs and shard:
             raise ValueError("token_logprobs is not offered with shard=True: the gathered records carry no per-token values")
-        if multilingual and not m.model.is_multilingual:
-            m.logger.warning("The current model is English-only but the multilingual parameter is set to"
-                             "True; setting to False instead.")
-            multilingual = False
-        if not isinstance(audio, np.ndarray):
-            from .audio import decode_audio   # path / file object: WAVE and FLAC natively, other containers through PyAV
-            audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(m.model))
-        audio = np.asarray(audio, dtype=np.float32)
-        duration = audio.shape[0] / sr
+        multilingual = m._effective_multilingual(multilingual)
+        audio = np.asarray(m._load_audio(audio), dtype=np.float32)
         chunk_length = chunk_length or m.feature_extractor.chunk_length
-        from .vad import get_speech_timestamps
-        from .words import restore_speech_timestamps
-        clips_given = bool(clip_timestamps)
         speech_spans = None
-        if not clips_given and vad_filter:
+        if not clip_timestamps and vad_filter:
             vad_parameters = self._vad_options(vad_parameters, chunk_length)
             speech_spans = get_speech_timestamps(audio, vad_parameters, speech_probs=vad_speech_probs)
-        clips, audio_chunks, chunks_metadata, duration_after_vad = self._split_recording(audio, clip_timestamps,
-                                                                                         speech_spans, chunk_length)
-
-        all_language_probs = None
-        if language is None:
-            if not m.model.is_multilingual:
-                language, language_probability = "en", 1
-            else:
-                feats = self._language_features(audio_chunks, language_detection_segments)
-                language, language_probability, all_language_probs = m.detect_language(
-                    features=feats, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold)
-        else:
-            language, language_probability = self._given_language(language), 1
-        tokenizer = m.make_tokenizer(task=task, language=language)
-        options = self._batched_options(
-            tokenizer, clip_timestamps if clips_given else clips, beam_size=beam_size, best_of=best_of,
-            patience=patience, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-            no_repeat_ngram_size=no_repeat_ngram_size, log_prob_threshold=log_prob_threshold,
-            no_speech_threshold=no_speech_threshold, compression_ratio_threshold=compression_ratio_threshold,
-            temperature=temperature, initial_prompt=initial_prompt, prefix=prefix, suppress_blank=suppress_blank,
-            suppress_tokens=suppress_tokens, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, hotwords=hotwords,
-            word_timestamps=word_timestamps, multilingual=multilingual, without_timestamps=without_timestamps)
-        info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
-                                 duration_after_vad=duration_after_vad, transcription_options=options,
-                                 vad_options=vad_parameters, all_language_probs=all_language_probs)
-        gen = self._batched_segments_generator(audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                               log_progress, shard, fused_features,
+        rec = self._split_recording(audio, clip_timestamps, speech_spans, chunk_length, vad_parameters)
+        if language is None and m.model.is_multilingual:
+            rec.language, rec.language_probability, rec.all_language_probs = m.detect_language(
+                features=self._language_features(rec.audio_chunks, language_detection_segments),
+                language_detection_segments=language_detection_segments,
+                language_detection_threshold=language_detection_threshold)
+        self._plan_decode(rec, args, language, multilingual, {})
+        gen = self._batched_segments_generator(rec.audio_chunks, rec.tokenizer, rec.chunks_metadata, batch_size,
+                                               rec.options, log_progress, shard, fused_features,
                                                **(dict(token_logprobs=True) if token_logprobs else {}))
-        if not clips_given:
-            gen = restore_speech_timestamps(gen, clips, sr)
-        return gen, info
+        return self._on_recording_time(rec, gen), rec.info
 
-    # ---- the pieces of transcribe's front that transcribe_many runs per recording -----------------
+    # ---- the steps of transcribe that transcribe_many runs per recording -----------------
     @staticmethod
     def _vad_options(vad_parameters, chunk_length):
         """the VAD options of the batched path: spans of at most one chunk"""
@@ -1055,9 +1038,9 @@ class BatchedInferencePipeline:
                               max_speech_duration_s=chunk_length)
         return vad_parameters
 
-    def _split_recording(self, audio, clip_timestamps, speech_spans, chunk_length):
-        """-> (clips, audio_chunks, chunks_metadata, duration_after_vad) of one recording.  clip_timestamps: the caller's
-        split (wins); speech_spans: the VAD's spans of the recording (None: the VAD did not run)"""
+    def _split_recording(self, audio, clip_timestamps, speech_spans, chunk_length, vad_options) -> "_Recording":
+        """the record of one recording, cut into chunks.  clip_timestamps: the caller's split (wins); speech_spans: the
+        VAD's spans of the recording (None: the VAD did not run); vad_options: what info.vad_options reports"""
         from .vad import collect_chunks
         m = self.model
         sr = m.feature_extractor.sampling_rate
@@ -1088,7 +1071,9 @@ class BatchedInferencePipeline:
         assert duration - duration_after_vad >= 0, "non-negative timestamp expected"
         if not duration_after_vad:
             audio_chunks, chunks_metadata = [], []
-        return clips, audio_chunks, chunks_metadata, duration_after_vad
+        return _Recording(audio=audio, clip_timestamps=clip_timestamps, clips=clips, audio_chunks=audio_chunks,
+                          chunks_metadata=chunks_metadata, duration_after_vad=duration_after_vad,
+                          vad_options=vad_options)
 
     def _language_features(self, audio_chunks, language_detection_segments):
         """the features language detection looks at: the reference concatenates the (unpadded) features of ALL chunks;
@@ -1104,35 +1089,43 @@ class BatchedInferencePipeline:
         # + one dummy frame so that empty audio still has a feature
         return np.concatenate(parts + [np.full((m.model.n_mels, 1), -1.5, dtype="float32")], axis=1)
 
-    def _given_language(self, language):
-        m = self.model
-        if not m.model.is_multilingual and language != "en":
-            m.logger.warning("The current model is English-only but the language parameter is set to '%s'; "
-                             "using 'en' instead." % language)
-            language = "en"
-        return language
-
     @staticmethod
-    def _batched_options(tokenizer, clip_timestamps, *, beam_size, best_of, patience, length_penalty, repetition_penalty,
-                         no_repeat_ngram_size, log_prob_threshold, no_speech_threshold, compression_ratio_threshold,
-                         temperature, initial_prompt, prefix, suppress_blank, suppress_tokens, prepend_punctuations,
-                         append_punctuations, max_new_tokens, hotwords, word_timestamps, multilingual,
-                         without_timestamps):
-        return TranscriptionOptions(
-            beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            compression_ratio_threshold=compression_ratio_threshold,
+    def _batched_options(args, tokenizer, clip_timestamps, multilingual) -> TranscriptionOptions:
+        """args: transcribe()'s arguments by name.  The batched path decodes once, at the first temperature, every chunk
+        on its own, and knows no hallucination skipping."""
+        temperature, suppress_tokens = args["temperature"], args["suppress_tokens"]
+        return _transcription_options(
+            args, tokenizer, clip_timestamps=clip_timestamps, multilingual=multilingual,
             temperatures=(list(temperature[:1]) if isinstance(temperature, (list, tuple)) else [temperature]),
-            initial_prompt=initial_prompt, prefix=prefix, suppress_blank=suppress_blank,
-            suppress_tokens=(get_suppressed_tokens(tokenizer, list(suppress_tokens)) if suppress_tokens
-                             else suppress_tokens),
-            prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
-            max_new_tokens=max_new_tokens, hotwords=hotwords, word_timestamps=word_timestamps,
-            hallucination_silence_threshold=None, condition_on_previous_text=False,
-            clip_timestamps=clip_timestamps, prompt_reset_on_temperature=0.5,
-            multilingual=multilingual,
-            without_timestamps=without_timestamps, max_initial_timestamp=0.0)
+            suppress_tokens=(list(suppress_tokens) if suppress_tokens else suppress_tokens),
+            hallucination_silence_threshold=None, condition_on_previous_text=False, prompt_reset_on_temperature=0.5,
+            max_initial_timestamp=0.0)
+
+    def _plan_decode(self, rec: "_Recording", args, language, multilingual, tokenizers) -> None:
+        """what is left to decide before a recording's chunks can be decoded: its language (the argument, "en" for an
+        English-only model, else what the detection pass has put into the record), tokenizer (one per language, kept in
+        `tokenizers`), options and info.  args: transcribe()'s arguments by name."""
+        m = self.model
+        if language is not None:
+            rec.language = m._effective_language(language)
+        elif not m.model.is_multilingual:
+            rec.language = "en"
+        if rec.language not in tokenizers:
+            tokenizers[rec.language] = m.make_tokenizer(task=args["task"], language=rec.language)
+        rec.tokenizer = tokenizers[rec.language]
+        rec.options = self._batched_options(args, rec.tokenizer, rec.clip_timestamps or rec.clips, multilingual)
+        rec.info = TranscriptionInfo(
+            language=rec.language, language_probability=rec.language_probability,
+            duration=rec.audio.shape[0] / m.feature_extractor.sampling_rate, duration_after_vad=rec.duration_after_vad,
+            transcription_options=rec.options, vad_options=rec.vad_options, all_language_probs=rec.all_language_probs)
+
+    def _on_recording_time(self, rec: "_Recording", segments):
+        """segments with their times on the recording's axis: chunks cut from speech spans carry times on the axis with
+        the silence removed (the caller's clips are on the recording's axis already)"""
+        if rec.clip_timestamps:
+            return segments
+        from .words import restore_speech_timestamps
+        return restore_speech_timestamps(segments, rec.clips, self.model.feature_extractor.sampling_rate)
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
                                     log_progress, shard=False, fused_features=True, token_logprobs=False):
@@ -1145,7 +1138,7 @@ class BatchedInferencePipeline:
             local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         n = len(audio_chunks)
         seg_idx = 0
-        workers = self._workers()
+        workers = m._workers()
 
         def batches(lo, hi):
             """(outs, local, aligned) per batch of the chunk range [lo, hi), in order, `workers` batches in flight"""
@@ -1204,10 +1197,6 @@ class BatchedInferencePipeline:
         yield from emit(results)
         self.last_speech_timestamp = 0.0
 
-
-    def _workers(self) -> int:
-        return int(getattr(self.model.model, "inter_threads", 1) or 1)
-
     def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
                       token_logprobs=False):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
@@ -1231,7 +1220,7 @@ class BatchedInferencePipeline:
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
         encoders run side by side and their generate() calls share decode runs (backend decode groups).  Only
         the word-timestamp pause heuristics chain through last_speech_timestamp; those run in order, in the caller."""
-        workers = self._workers()
+        workers = self.model._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
                 yield self._decode_batch(*job, shard, fused_features, token_logprobs)
@@ -1253,16 +1242,13 @@ class BatchedInferencePipeline:
         idx = first_id
         for result in results:
             for seg in result:
-                fields = dict(seek=seg["seek"], id=idx, text=seg["text"], start=round(seg["start"], 3),
+                values = dict(seek=seg["seek"], id=idx, text=seg["text"], start=round(seg["start"], 3),
                               end=round(seg["end"], 3), tokens=seg["tokens"], avg_logprob=seg["avg_logprob"],
                               words=(None if not options.word_timestamps else [Word(**w) for w in seg["words"]]),
                               no_speech_prob=seg["no_speech_prob"], compression_ratio=seg["compression_ratio"],
                               temperature=options.temperatures[0])
                 # (sub-segments carry token_logprobs exactly when the call asked for them: _split_outputs)
-                if "token_logprobs" in seg:
-                    yield ScoredSegment(token_logprobs=seg["token_logprobs"], **fields)
-                else:
-                    yield Segment(**fields)
+                yield _make_segment(values, seg.get("token_logprobs"))
                 idx += 1
 
     # ---- many recordings in one call ------------------------------------------------------------
@@ -1282,129 +1268,85 @@ class BatchedInferencePipeline:
         when every recording is done; shard=True is not offered here (ValueError)."""
         import inspect
         from .vad import get_speech_timestamps_many
-        from .words import restore_speech_timestamps
         if shard:
             raise ValueError("transcribe_many does not shard: call it per rank on that rank's recordings")
         a = inspect.signature(self.transcribe).bind(None, **kwargs)     # transcribe's keywords and defaults
         a.apply_defaults()
         a = a.arguments
         m = self.model
-        sr = m.feature_extractor.sampling_rate
         n = len(audios)
         if n == 0:
             return []
-        multilingual = a["multilingual"]
-        if multilingual and not m.model.is_multilingual:
-            m.logger.warning("The current model is English-only but the multilingual parameter is set to"
-                             "True; setting to False instead.")
-            multilingual = False
-        languages = self._per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
-        clip_lists = self._per_recording(clip_timestamps, n, "clip_timestamps",
-                                         lambda v: v is None or all(isinstance(c, dict) for c in v))
-        probs = self._per_recording(vad_speech_probs, n, "vad_speech_probs",
-                                    lambda v: v is None or isinstance(v, np.ndarray)
-                                    or all(np.ndim(p) == 0 and p is not None for p in v))
-        recs = []
-        for audio in audios:
-            if not isinstance(audio, np.ndarray):
-                from .audio import decode_audio
-                audio = decode_audio(audio, sampling_rate=sr, device_index=_resample_device_index(m.model))
-            recs.append(np.asarray(audio, dtype=np.float32))
+        multilingual = m._effective_multilingual(a["multilingual"])
+        languages = _per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
+        clip_lists = _per_recording(clip_timestamps, n, "clip_timestamps",
+                                    lambda v: v is None or all(isinstance(c, dict) for c in v))
+        probs = _per_recording(vad_speech_probs, n, "vad_speech_probs",
+                               lambda v: v is None or isinstance(v, np.ndarray)
+                               or all(np.ndim(p) == 0 and p is not None for p in v))
+        audios = [np.asarray(m._load_audio(audio), dtype=np.float32) for audio in audios]
         chunk_length = a["chunk_length"] or m.feature_extractor.chunk_length
 
         # ---- VAD: one pass over every recording that needs it ----
-        vad_options = [a["vad_parameters"]] * n
-        spans = [None] * n
+        spans, vad_options = [None] * n, [a["vad_parameters"]] * n
         need_vad = [r for r in range(n) if not clip_lists[r] and a["vad_filter"]]
         if need_vad:
             opts = self._vad_options(a["vad_parameters"], chunk_length)
-            found = get_speech_timestamps_many([recs[r] for r in need_vad], opts, vad_model=vad_model,
+            found = get_speech_timestamps_many([audios[r] for r in need_vad], opts, vad_model=vad_model,
                                                speech_probs=[probs[r] for r in need_vad])
-            for r, sp in zip(need_vad, found):
-                vad_options[r], spans[r] = opts, sp
-        split = [self._split_recording(recs[r], clip_lists[r], spans[r], chunk_length) for r in range(n)]
+            for r, found_spans in zip(need_vad, found):
+                spans[r], vad_options[r] = found_spans, opts
 
-        # ---- language: the first detection segment of all undecided recordings in batches ----
-        detected = {}
+        # ---- plan: every recording cut into chunks ----
+        recs = [self._split_recording(audio, clips, speech_spans, chunk_length, options)
+                for audio, clips, speech_spans, options in zip(audios, clip_lists, spans, vad_options)]
+
+        # ---- detect: the first detection segment of all undecided recordings in batches; then language, tokenizer
+        #      (one per language), options and info of every recording ----
         if m.model.is_multilingual:
-            undecided = [r for r in range(n) if languages[r] is None]
             frames = m.feature_extractor.nb_max_frames
-            feats = {r: self._language_features(split[r][1], a["language_detection_segments"])
-                     [..., :a["language_detection_segments"] * frames] for r in undecided}
+            undecided = [(rec, self._language_features(rec.audio_chunks, a["language_detection_segments"])
+                          [..., :a["language_detection_segments"] * frames])
+                         for rec, given in zip(recs, languages) if given is None]
             for i in range(0, len(undecided), a["batch_size"]):
                 part = undecided[i:i + a["batch_size"]]
-                enc = m.encode(np.stack([pad_or_trim(feats[r][..., :frames]) for r in part]))
-                for r, first in zip(part, m.model.detect_language(enc)):
+                enc = m.encode(np.stack([pad_or_trim(feats[..., :frames]) for _, feats in part]))
+                for (rec, feats), first in zip(part, m.model.detect_language(enc)):
                     # (a recording whose first segment stays under the threshold goes on alone with its further segments)
-                    detected[r] = m._detect_language_segments(feats[r], a["language_detection_threshold"], first=first)
+                    rec.language, rec.language_probability, rec.all_language_probs = m._detect_language_segments(
+                        feats, a["language_detection_threshold"], first=first)
+        tokenizers = {}
+        for rec, given in zip(recs, languages):
+            self._plan_decode(rec, a, given, multilingual, tokenizers)
 
-        # ---- per recording: tokenizer (one per language), options, info ----
-        tokenizers, infos, all_options = {}, [], []
-        for r in range(n):
-            all_language_probs = None
-            if languages[r] is not None:
-                lang, lang_prob = self._given_language(languages[r]), 1
-            elif not m.model.is_multilingual:
-                lang, lang_prob = "en", 1
-            else:
-                lang, lang_prob, all_language_probs = detected[r]
-            languages[r] = lang
-            if lang not in tokenizers:
-                tokenizers[lang] = m.make_tokenizer(task=a["task"], language=lang)
-            clips = split[r][0]
-            options = self._batched_options(
-                tokenizers[lang], clip_lists[r] if clip_lists[r] else clips, multilingual=multilingual,
-                **{k: a[k] for k in ("beam_size", "best_of", "patience", "length_penalty", "repetition_penalty",
-                                     "no_repeat_ngram_size", "log_prob_threshold", "no_speech_threshold",
-                                     "compression_ratio_threshold", "temperature", "initial_prompt", "prefix",
-                                     "suppress_blank", "suppress_tokens", "prepend_punctuations", "append_punctuations",
-                                     "max_new_tokens", "hotwords", "word_timestamps", "without_timestamps")})
-            all_options.append(options)
-            infos.append(TranscriptionInfo(language=lang, language_probability=lang_prob,
-                                           duration=recs[r].shape[0] / sr, duration_after_vad=split[r][3],
-                                           transcription_options=options, vad_options=vad_options[r],
-                                           all_language_probs=all_language_probs))
-
-        # ---- pooling: the chunks of all recordings in recording order, per language; a batch every batch_size chunks ----
+        # ---- pool: the chunks of all recordings in recording order, per language; a batch every batch_size chunks ----
         jobs, owners = [], []                                  # owners[j]: the recording of every chunk of job j
-        for lang, tokenizer in tokenizers.items():
-            pool = [(r, k) for r in range(n) if languages[r] == lang for k in range(len(split[r][1]))]
+        for tokenizer in tokenizers.values():
+            same_language = [rec for rec in recs if rec.tokenizer is tokenizer]
+            pool = [(rec, chunk, meta) for rec in same_language
+                    for chunk, meta in zip(rec.audio_chunks, rec.chunks_metadata)]
             # (what a batch's decode reads of the options is the same for every recording of a language: they differ in
             #  clip_timestamps alone)
-            options = next(all_options[r] for r in range(n) if languages[r] == lang)
+            options = same_language[0].options
             for i in range(0, len(pool), a["batch_size"]):
                 part = pool[i:i + a["batch_size"]]
-                jobs.append(([split[r][1][k] for r, k in part], [split[r][2][k] for r, k in part], tokenizer, options))
-                owners.append([r for r, _ in part])
+                jobs.append(([chunk for _, chunk, _ in part], [meta for _, _, meta in part], tokenizer, options))
+                owners.append([rec for rec, _, _ in part])
 
-        # ---- routing: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
-        results = [[] for _ in range(n)]
-        aligned = [[] for _ in range(n)]
-        for own, (_, local, al) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
-                                                                       a["token_logprobs"])):
-            for j, r in enumerate(own):
-                results[r].append(local[j])
-                if al is not None:
-                    aligned[r].append(al[j])
+        # ---- route: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
+        for owner, (_, local, aligned) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
+                                                                              a["token_logprobs"])):
+            for j, rec in enumerate(owner):
+                rec.decoded.append(local[j])
+                if aligned is not None:
+                    rec.aligned.append(aligned[j])
         out = []
-        for r in range(n):
+        for rec in recs:
             if a["word_timestamps"]:
-                m.apply_word_alignments(results[r], aligned[r], 0.0)   # the pause heuristics chain within a recording
-            segments = self._segments(results[r], all_options[r], 1)
-            if not clip_lists[r]:
-                segments = restore_speech_timestamps(segments, split[r][0], sr)
-            out.append((list(segments), infos[r]))
+                m.apply_word_alignments(rec.decoded, rec.aligned, 0.0)   # the pause heuristics chain within a recording
+            segments = self._on_recording_time(rec, self._segments(rec.decoded, rec.options, 1))
+            out.append((list(segments), rec.info))
         return out
-
-    @staticmethod
-    def _per_recording(value, n, name, is_single):
-        """one value for all recordings, or a sequence with one entry per recording -> a list of n"""
-        if is_single(value):
-            return [value] * n
-        value = list(value)
-        if len(value) != n:
-            raise ValueError(f"{name} has {len(value)} entries for {n} recordings")
-        return value
 
 
 class _OutRec:

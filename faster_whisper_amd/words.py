@@ -7,6 +7,7 @@ restoration after VAD chunking (row a13).  Host-side float/integer logic, same b
     assign_words              transcribe.py:1620-1696 (words -> sub-segments, pause heuristics, segment bounds)
     word_anomaly_score / is_segment_anomaly / next_words_segment
                               transcribe.py:1226-1250 (hallucination heuristics of the sequential path)
+    seek_after_words          transcribe.py:1288-1343 (the seek loop's step after a window's words are timed)
     get_end                   utils.py:148-152
     restore_speech_timestamps transcribe.py:1843-1870
 """
@@ -154,6 +155,50 @@ def get_end(segments: List[dict]) -> Optional[float]:
         if seg["words"]:
             return seg["words"][-1]["end"]
     return segments[-1]["end"] if segments else None
+
+
+def seek_after_words(current: List[dict], *, seek: int, previous_seek: int, time_offset: float, segment_duration: float,
+                     window_end_time: float, content_frames: int, content_duration: float, frames_per_second: int,
+                     single_timestamp_ending: bool, threshold: Optional[float],
+                     last_speech_timestamp: float) -> Tuple[int, float, bool]:
+    """The seek loop's step after a window's words are timed (transcribe.py:1288-1343).  current: the window's
+    sub-segments with `words`; seek: where the timestamp tokens put the next window; previous_seek / time_offset: this
+    window's first frame / second; threshold: hallucination_silence_threshold.  `seek` moves to the last word's end
+    (unless the window closed on a single timestamp); with a threshold, a probable hallucination after leading silence
+    has the window decoded again from where speech starts, and one surrounded by silence is cut out of `current` (in
+    place, with everything after it).  -> (seek, last_speech_timestamp, decode the window again)"""
+    if not single_timestamp_ending:
+        last_word_end = get_end(current)
+        if last_word_end is not None and last_word_end > time_offset:
+            seek = round(last_word_end * frames_per_second)
+    if threshold is not None:
+        first = next_words_segment(current)
+        if first is not None and is_segment_anomaly(first):
+            gap = first["start"] - time_offset
+            if gap > threshold:
+                return previous_seek + round(gap * frames_per_second), last_speech_timestamp, True
+        hal_last_end = last_speech_timestamp
+        for si, seg in enumerate(current):
+            if not seg["words"]:
+                continue
+            if is_segment_anomaly(seg):
+                nxt = next_words_segment(current[si + 1:])
+                hal_next_start = nxt["words"][0]["start"] if nxt is not None else time_offset + segment_duration
+                silence_before = (seg["start"] - hal_last_end > threshold or seg["start"] < threshold
+                                  or seg["start"] - time_offset < 2.0)
+                silence_after = (hal_next_start - seg["end"] > threshold or is_segment_anomaly(nxt)
+                                 or window_end_time - seg["end"] < 2.0)
+                if silence_before and silence_after:
+                    seek = round(max(time_offset + 1, seg["start"]) * frames_per_second)
+                    if content_duration - seg["end"] < threshold:
+                        seek = content_frames
+                    current[si:] = []
+                    break
+            hal_last_end = seg["end"]
+    last_word_end = get_end(current)
+    if last_word_end is not None:
+        last_speech_timestamp = last_word_end
+    return seek, last_speech_timestamp, False
 
 
 def restore_speech_timestamps(segments: Iterable, speech_chunks: List[dict], sampling_rate: int) -> Iterable:

@@ -158,6 +158,57 @@ def test_batches_larger_than_the_engine_workspace(wm):
         model.generate(enc, [prompt] * 5, beam_size=6)          # beam_size is bounded by max_beam_size
 
 
+def test_a_split_batch_is_the_engine_calls_on_its_parts(wm):
+    """five chunks on a workspace of two are three engine calls, on chunks 0-1, 2-3 and 4, in that order.  (a) a sampling
+    call without a seed draws one seed per engine call from the model's counter, in part order; (b) per-token log-probs
+    and (c) alignments are those of the per-part calls.  (Per part, not per chunk: sampling noise is keyed by the row
+    within a call.)"""
+    import itertools
+    from faster_whisper_amd import Whisper
+    from faster_whisper_amd.backend import call_seed
+    cfg, w, _ = wm
+    model = Whisper("synthetic:micro", device="cuda", files={"config": cfg, "weights": w}, max_batch_size=2,
+                    max_beam_size=5)
+    chunks = [bench_audio(480000 if i % 2 else 300000, seed=20 + i) for i in range(5)]
+    prompt = [cfg.sot, cfg.lang_begin, cfg.transcribe, cfg.no_timestamps]
+    enc = model.encode_pcm(chunks)
+    parts = enc._parts
+    assert [p.shape[0] for p in parts] == [2, 2, 1]
+    # (a)
+    k = 1000
+    kw = dict(beam_size=1, sampling_topk=0, sampling_temperature=0.7, num_hypotheses=2, max_length=len(prompt) + 8,
+              return_scores=True)
+    model._seed_counter = itertools.count(k)
+    got = model.generate(enc, [prompt] * 5, **kw)
+    want = [r for j, p in enumerate(parts) for r in model.generate(p, [prompt] * p.shape[0], seed=call_seed(k + j), **kw)]
+    assert len(got) == len(want) == 5
+    for g, x in zip(got, want):
+        assert len(g.sequences_ids) == 2 and g.sequences_ids == x.sequences_ids and g.scores == x.scores
+    assert len({tuple(map(tuple, g.sequences_ids)) for g in got}) > 1       # the comparison is not one of equal rows
+    # (b)
+    kw = dict(beam_size=5, max_length=len(prompt) + 8, return_scores=True, return_token_logprobs=True)
+    got = model.generate(enc, [prompt] * 5, **kw)
+    want = [r for p in parts for r in model.generate(p, [prompt] * p.shape[0], **kw)]
+    assert len(got) == len(want) == 5
+    for g, x in zip(got, want):
+        assert len(g.token_logprobs[0]) == len(g.sequences_ids[0]) > 0 and len(g.end_logprobs) == 1
+        assert g.sequences_ids == x.sequences_ids and g.scores == x.scores
+        assert g.token_logprobs == x.token_logprobs and g.end_logprobs == x.end_logprobs
+    # (c) (token lists and frame counts differ from chunk to chunk: a wrong slice shows)
+    tokens = [[11, 12, 13], [14, 15], [16, 17, 18, 19], [11], [12, 13]]
+    frames = [1800, 3000, 1700, 3000, 1600]
+    got = model.align(enc, cfg.sot_sequence, tokens, frames)
+    want, b0 = [], 0
+    for p in parts:
+        b1 = b0 + p.shape[0]
+        want.extend(model.align(p, cfg.sot_sequence, tokens[b0:b1], frames[b0:b1]))
+        b0 = b1
+    assert len(got) == len(want) == 5
+    for g, x, t in zip(got, want, tokens):
+        assert len(g.text_token_probs) == len(t) and len(g.alignments) > 0
+        assert g.alignments == x.alignments and g.text_token_probs == x.text_token_probs
+
+
 def test_empty_audio(wm):
     """the reference's tests/test_transcribe.py:91-97: an empty recording yields no segments on either driver and
     language detection still answers — here on the engine (zero-sample log-mel, one all-padding window)"""
