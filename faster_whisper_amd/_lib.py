@@ -70,6 +70,7 @@ SYMBOLS = [
     "fw_model_set_decode_batch", "fw_model_decode_batch", "fw_model_join_decoder", "fw_model_decode_stats",
     "fw_model_set_merge_wait", "fw_model_set_decode_lanes", "fw_model_run_capacity", "fw_dec_big_min_rows", "fw_dec_big_min_rows_of", "fw_test_knob",
     "fw_test_idle_lead_chunks", "fw_test_run_capacity", "fw_test_dec_linear_plan", "fw_test_self_attn_form",
+    "fw_test_gemm_plan",
     "fw_pack_blob_size", "fw_pack_blob_copy", "fw_pack_blob_free",
     "fw_logmel", "fw_logmel_full",
     "fw_encode", "fw_encode_pcm", "fw_encode_pcm_dev", "fw_tensor_shape", "fw_tensor_to_host",
@@ -142,6 +143,8 @@ def load():
         lib.fw_test_dec_linear_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32p]
         lib.fw_test_self_attn_form.argtypes = [i32] * 8
         lib.fw_test_self_attn_form.restype = i32
+    if hasattr(lib, "fw_test_gemm_plan"):         # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_test_gemm_plan.argtypes = [i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32p]
     lib.fw_model_join_decoder.argtypes = [vp, vp]
     lib.fw_model_set_merge_wait.argtypes = [vp, i32, i32]
     lib.fw_model_set_decode_lanes.argtypes = [vp, i32]

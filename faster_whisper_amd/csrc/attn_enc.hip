@@ -225,12 +225,11 @@ __global__ __launch_bounds__(256) void attn_enc_kernel(const half_t* __restrict_
 }
 
 namespace fwk {
-void launch_attn_enc(hipStream_t st, const half_t* q, const half_t* k, int64_t ld, int64_t qk_bstride,
-                     const half_t* vt, int64_t ldvt, int64_t vt_bstride, half_t* out, int64_t ldo,
-                     int64_t o_bstride, int B, int H, int T, int order) {
-  const int n_qt = (T + AE_Q - 1) / AE_Q, n_pairs = B * H;
+void launch_attn_enc(hipStream_t st, const AttnEnc& a) {
+  const int n_qt = (a.T + AE_Q - 1) / AE_Q, n_pairs = a.B * a.H;
   const int grid = ((n_pairs + 7) / 8) * 8 * n_qt;
   // (132 registers: 3 waves per SIMD.  Forcing 4 with __launch_bounds__(256, 4) spills and measured 6 % slower.)
-  attn_enc_kernel<<<grid, 256, 0, st>>>(q, k, ld, qk_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, T, H, n_pairs, n_qt, order);
+  attn_enc_kernel<<<grid, 256, 0, st>>>(a.q, a.k, a.ld, a.qk_bstride, a.vt, a.ldvt, a.vt_bstride, a.out, a.ldo, a.o_bstride, a.T,
+                                        a.H, n_pairs, n_qt, a.order);
 }
 }  // namespace fwk

@@ -109,8 +109,7 @@ struct GenWorkspace {
   half_t* xn_frag = nullptr;             // fp16(LayerNorm(x)), fragment-major (explicit-LayerNorm order, Model::ln_unfold)
   int8_t* xq = nullptr;                  // int8_float16: quantised linear input, fragment-major [R16][4d]
   float* xs = nullptr;                   //               per-row de-quantisation scale [R]
-  int8_t* ekq = nullptr;                 // int8_float16: one encoder output quantised for the cross-K/V projection
-  float* eks = nullptr;
+  QuantRows ekq;                         // int8_float16: one encoder output quantised for the cross-K/V projection
   // hipGraphs of the decode step, one per distinct GenDev (merged runs differ in their chunk count)
   std::vector<GraphSlot> graphs;
   uint64_t graph_clock = 0;
@@ -297,8 +296,10 @@ int gen_workspace_build(const Model* m, DecodeLane* lane, int lane_chunks, int s
   if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
     Z(g->xq, R16 * 4 * d);
     Z(g->xs, R16);
-    A(g->ekq, (size_t)g->EB * c.n_audio_ctx * d);
-    A(g->eks, (size_t)g->EB * c.n_audio_ctx);
+    g->ekq.cap_rows = (int64_t)g->EB * c.n_audio_ctx;
+    g->ekq.cap_elems = g->ekq.cap_rows * d;
+    A(g->ekq.q, (size_t)g->ekq.cap_elems);
+    A(g->ekq.scale, (size_t)g->ekq.cap_rows);
   } else {
     Z(g->x_frag, R16 * d); Z(g->att_frag, R16 * d); Z(g->ffn_frag, R16 * 4 * d); Z(g->xn_frag, R16 * d);
   }
@@ -367,33 +368,26 @@ static int ensure_cross_kv(Model* m, DecodeLane* lane, const Tensor* enc, int bl
   const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
   const int kvp = pool->kvp;
   const int64_t kvs = (int64_t)d * kvp;   // one chunk's K (or V^T): H heads x kvp keys x 64
+  const int64_t cls = (int64_t)pool->n_slots() * kvs;          // a layer's region of the pool
+  // both land in the MFMA-fragment-major layout of the decode kernel (head_rows = kvp selects it in the
+  // GEMM epilogue): K through the plain epilogue, V^T through the transposed one
+  LinCall k{.in = {enc->data, d, xs}, .C = pool->ck + (size_t)b0 * kvs, .ldc = d, .c_bs = kvs, .M = T, .batch = B,
+            .head_rows = kvp, .st = st};
+  LinCall v{.in = k.in, .C = pool->cvt + (size_t)b0 * kvs, .ldc = kvp, .c_bs = kvs, .M = T, .batch = B, .trans = true,
+            .head_rows = kvp, .st = st};
+  if (i8) {
+    // the encoder output is quantised once and shared by all 2L projections
+    if ((rc = quantise_rows(m, enc->data, nullptr, (int64_t)B * T, d, st, g->ekq))) return rc;
+    k.in = v.in = {.xq = &g->ekq};
+  }
   int64_t ws = 0, bs = 0;
   if (!i8 && env_knob_on(g_cross_kv_layered, "FWAMD_CROSS_KV_LAYERED") && cross_kv_strides(m, &ws, &bs)) {
-    const int64_t cls = (int64_t)pool->n_slots() * kvs;          // a layer's region of the pool
-    half_t* kd = pool->ck + (size_t)b0 * kvs;
-    half_t* vd = pool->cvt + (size_t)b0 * kvs;
-    if ((rc = run_linear_layers(m, m->dec[0].ck, c.n_dec_layers, ws, bs, enc->data, d, xs, kd, d, kvs, cls, T, B, false, kvp, st)))
-      return rc;
-    if ((rc = run_linear_layers(m, m->dec[0].cv, c.n_dec_layers, ws, bs, enc->data, d, xs, vd, kvp, kvs, cls, T, B, true, kvp, st)))
-      return rc;
+    k.n_layers = v.n_layers = c.n_dec_layers;
+    k.w_ls = v.w_ls = ws; k.b_ls = v.b_ls = bs; k.c_ls = v.c_ls = cls;
+    if ((rc = run_linear(m, m->dec[0].ck, k)) || (rc = run_linear(m, m->dec[0].cv, v))) return rc;
   } else for (int l = 0; l < c.n_dec_layers; ++l) {
-    const DecLayerW& L = m->dec[l];
-    half_t* kd = pool->ck + ((size_t)l * pool->n_slots() + b0) * kvs;
-    half_t* vd = pool->cvt + ((size_t)l * pool->n_slots() + b0) * kvs;
-    // both land in the MFMA-fragment-major layout of the decode kernel (head_rows = kvp selects it in the
-    // GEMM epilogue): K through the plain epilogue, V^T through the transposed one
-    if (i8) {
-      // the encoder output is quantised once (layer 0) and shared by all 2L projections
-      if ((rc = run_linear_i8(m, L.ck, l == 0 ? enc->data : nullptr, nullptr, kd, d, kvs, nullptr, 0, 0, T, B, 0,
-                              false, kvp, st, g->ekq, g->eks)))
-        return rc;
-      if ((rc = run_linear_i8(m, L.cv, nullptr, nullptr, vd, kvp, kvs, nullptr, 0, 0, T, B, 0, true, kvp, st, g->ekq,
-                              g->eks)))
-        return rc;
-      continue;
-    }
-    if ((rc = run_linear(m, L.ck, enc->data, d, xs, kd, d, kvs, nullptr, 0, 0, T, B, 0, false, kvp, st))) return rc;
-    if ((rc = run_linear(m, L.cv, enc->data, d, xs, vd, kvp, kvs, nullptr, 0, 0, T, B, 0, true, kvp, st))) return rc;
+    if (l) { k.C += cls; v.C += cls; }
+    if ((rc = run_linear(m, m->dec[l].ck, k)) || (rc = run_linear(m, m->dec[l].cv, v))) return rc;
   }
   std::lock_guard<std::mutex> lk(pool->mu);
   pool->blocks[blk].enc_id = enc->id;

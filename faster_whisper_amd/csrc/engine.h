@@ -16,6 +16,7 @@
 
 #include "../../include/fwamd.h"
 #include "common.h"
+#include "kernels.h"
 
 namespace fw {
 
@@ -188,6 +189,16 @@ struct GrowBuf {
   }
 };
 
+// int8_float16: the quantised input rows of the encoder GEMM — codes [rows][ld] and per-row de-quantisation scales [rows].
+// The capacity is set where the two buffers are allocated; quantise_rows (below) fills them and records what they hold.
+struct QuantRows {
+  int8_t* q = nullptr;
+  float* scale = nullptr;
+  int64_t cap_rows = 0, cap_elems = 0;
+  int64_t rows = 0, ld = 0;   // held now
+  bool fits(int64_t r, int64_t K) const { return r >= 0 && K >= 0 && r <= cap_rows && r * K <= cap_elems; }
+};
+
 struct Model;
 // Encoder-output buffers of one model, every one [max_batch][T][d] halves (hipMalloc / hipFree synchronise the whole
 // device and would serialise the replicas that share a GPU).  The model and each of its tensors hold the pool: a tensor
@@ -313,8 +324,7 @@ struct Model : Weights {
   half_t* ws_vt = nullptr;                            // [B][d][t_pad]
   half_t* ws_att = nullptr;                           // [B][1500][d]
   half_t* ws_ffn = nullptr;                           // [B][1500][4d]
-  int8_t* ws_xq = nullptr;                            // int8_float16: quantised GEMM input [B*1500][4d]
-  float* ws_xs = nullptr;                             //               its per-row scales [B*1500]
+  QuantRows ws_xq;                                    // int8_float16: quantised GEMM input, up to [B*1500][4d]
   int t_pad = 0;
 
   // decode side.  A model either owns a decode group (lanes[0] from model creation, its workspace built on first use
@@ -368,24 +378,34 @@ struct RunCapacity {
               int num_hypotheses, int ctx);
 };
 
-// linear layer on "many rows": C = act(A W^T + b) + res   (encoder / prefill / align)
-// st == null: the model's encoder stream
-int run_linear(Model* m, const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, half_t* C, int64_t ldc,
-               int64_t c_bs, const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans,
-               int head_rows = 0, hipStream_t st = nullptr);
-
-// xq / xs == null: the encoder's quantisation workspace (m->ws_xq / m->ws_xs)
-int run_linear_i8(Model* m, const LinearW& L, const half_t* A, const LNW* ln, half_t* C, int64_t ldc, int64_t c_bs,
-                  const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans, int head_rows,
-                  hipStream_t st = nullptr, int8_t* xq = nullptr, float* xs = nullptr);
-
-// encoder forward on the channel-last mel image already in m->ws_mel_cl; result into out [B][1500][d]
-// ONE launch for the same linear of `n_layers` consecutive layers on one input (fp16): layer l uses L0.w + l * w_lstride,
-// L0.b + l * b_lstride and writes C + l * c_lstride (element strides); gemm.hip "LAYERED launch"
-int run_linear_layers(Model* m, const LinearW& L0, int n_layers, int64_t w_lstride, int64_t b_lstride, const half_t* A,
-                      int64_t lda, int64_t a_bs, half_t* C, int64_t ldc, int64_t c_bs, int64_t c_lstride, int M, int batch,
-                      bool trans, int head_rows, hipStream_t st);
+// One launch of the encoder GEMM, a linear layer on "many rows": C = act(A W^T + b) + res (encoder, cross-K/V
+// projections).  Strides in elements; what a call site does not name is absent.
+struct LinIn {
+  const half_t* A = nullptr; int64_t lda = 0, a_bs = 0;     // fp16 input: row m of chunk z at A + z * a_bs + m * lda
+  const QuantRows* xq = nullptr;                            // ... or (int8_float16) the [batch * M] rows quantise_rows left
+};
+struct LinCall {
+  LinIn in;
+  half_t* C = nullptr; int64_t ldc = 0, c_bs = 0;           // trans: C^T, ldc its row stride
+  const half_t* res = nullptr; int64_t ldr = 0, r_bs = 0;   // added after act (r_bs = 0: one block shared by the chunks)
+  int M = 0, batch = 1;
+  int act = 0;                                              // 1: exact GELU
+  bool trans = false;
+  int head_rows = 0;                                        // > 0: fragment-major cross-attention K / V^T (kernels.h)
+  // n_layers > 1 (fp16): ONE launch for the same linear of consecutive layers on one input — layer l uses L.w + l * w_ls,
+  // L.b + l * b_ls and writes C + l * c_ls; gemm.hip "LAYERED launch"
+  int n_layers = 1; int64_t w_ls = 0, b_ls = 0, c_ls = 0;
+  hipStream_t st = nullptr;                                 // null: the model's encoder stream
+};
+// the one place that fills the GEMM's parameters; ldw: row stride of the weights (the product's are dense: L.K)
+fwk::GemmParams gemm_params(const LinearW& L, const LinCall& c, int64_t ldw);
+int run_linear(Model* m, const LinearW& L, const LinCall& c);
+// int8_float16 input of a linear (K25): per-row dynamic quantisation of A [rows][K] (dense), through the LayerNorm that
+// feeds it when ln is given, into qr — which any number of run_linear calls then read (the fused Q|K and V projections
+// share their input, the cross-K/V projections of all layers theirs).  FW_EINVAL when qr cannot hold the rows.
+int quantise_rows(Model* m, const half_t* A, const LNW* ln, int64_t rows, int K, hipStream_t st, QuantRows& qr);
 void set_cross_kv_layered(int on);                 // decoder.hip: knob 6
+// encoder forward on the channel-last mel image already in m->ws_mel_cl; result into out [B][1500][d]
 int run_encoder(Model* m, int B, half_t* out);
 
 // decoder entry points (decoder.hip)

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <map>
+#include <optional>
 #include <type_traits>
 
 #include "dec_kernels.h"
@@ -635,8 +636,9 @@ static int alloc_workspaces(Model* m) {
       (rc = db.alloc(&m->ws_x, B * T * d)) || (rc = db.alloc(&m->ws_x2, B * T * d)) || (rc = db.alloc(&m->ws_xn, B * T * d)) ||
       (rc = db.alloc(&m->ws_qk, B * T * 2 * d)) || (rc = db.zalloc(&m->ws_vt, B * d * m->t_pad)) ||
       (rc = db.alloc(&m->ws_att, B * T * d)) || (rc = db.alloc(&m->ws_ffn, B * T * 4 * d)) ||
-      (i8 && ((rc = db.alloc(&m->ws_xq, B * T * 4 * d)) || (rc = db.alloc(&m->ws_xs, B * T)))))
+      (i8 && ((rc = db.alloc(&m->ws_xq.q, B * T * 4 * d)) || (rc = db.alloc(&m->ws_xq.scale, B * T)))))
     return rc;
+  if (i8) { m->ws_xq.cap_rows = B * T; m->ws_xq.cap_elems = B * T * 4 * d; }
   return FW_OK;
 }
 
@@ -744,151 +746,117 @@ hipError_t create_stream(hipStream_t* st, const char* role) {
 }
 
 // ---------------------------------------------------------------- layers
-// what every launch of the encoder GEMM states: operands, output, shape; everything else zero.  W: the weight form the
-// launch reads (L.w, or L.wq's codes)
-static fwk::GemmParams gemm_params(const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, const half_t* W, half_t* C,
-                                   int64_t ldc, int64_t c_bs, int M, int head_rows) {
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.a_bstride = a_bs;
-  p.W = W; p.ldw = L.K;
+fwk::GemmParams gemm_params(const LinearW& L, const LinCall& c, int64_t ldw) {
+  fwk::GemmParams p{};
+  if (const QuantRows* xq = c.in.xq) {   // int8 x int8 -> int32 MFMA, de-quantising epilogue: codes where the halves were
+    p.A = reinterpret_cast<const half_t*>(xq->q); p.lda = xq->ld; p.a_bstride = c.M * xq->ld;
+    p.W = reinterpret_cast<const half_t*>(L.wq);
+    p.a_scale = xq->scale; p.as_bstride = c.M; p.w_scale = L.wscale;
+  } else {
+    p.A = c.in.A; p.lda = c.in.lda; p.a_bstride = c.in.a_bs;
+    p.W = L.w;
+  }
+  p.ldw = ldw;
   p.bias = L.b;
-  p.C = C; p.ldc = ldc; p.c_bstride = c_bs;
-  p.M = M; p.N = L.N; p.K = L.K;
-  p.head_rows = head_rows;
+  p.res = c.res; p.ldr = c.ldr; p.r_bstride = c.r_bs;
+  p.C = c.C; p.ldc = c.ldc; p.c_bstride = c.c_bs;
+  p.M = c.M; p.N = L.N; p.K = L.K;
+  p.act = c.act;
+  p.head_rows = c.head_rows;
+  p.n_layers = c.n_layers; p.w_lstride = c.w_ls; p.bias_lstride = c.b_ls; p.c_lstride = c.c_ls;
   return p;
 }
 
-int run_linear(Model* m, const LinearW& L, const half_t* A, int64_t lda, int64_t a_bs, half_t* C, int64_t ldc,
-               int64_t c_bs, const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans,
-               int head_rows, hipStream_t st) {
-  fwk::GemmParams p = gemm_params(L, A, lda, a_bs, L.w, C, ldc, c_bs, M, head_rows);
-  p.res = res; p.ldr = ldr; p.r_bstride = r_bs;
-  p.act = act;
-  if (fwk::launch_gemm(st ? st : m->stream, p, batch, trans) != 0) {
-    set_error("gemm: unsupported shape M=%d N=%d K=%d lda=%lld", M, L.N, L.K, (long long)lda);
+int run_linear(Model* m, const LinearW& L, const LinCall& c) {
+  if (const QuantRows* xq = c.in.xq)
+    FW_CHECK_ARG(xq->scale && xq->rows == (int64_t)c.batch * c.M && xq->ld == L.K,
+                 "int8 gemm: the quantised input holds %lld rows of %lld, the call reads %lld rows of %d", (long long)xq->rows,
+                 (long long)xq->ld, (long long)c.batch * c.M, L.K);
+  if (fwk::launch_gemm(c.st ? c.st : m->stream, gemm_params(L, c, L.K), c.batch, c.trans) != 0) {
+    set_error("%sgemm: unsupported shape M=%d N=%d K=%d lda=%lld layers=%d", c.in.xq ? "int8 " : "", c.M, L.N, L.K,
+              (long long)c.in.lda, c.n_layers);
     return FW_ERUNTIME;
   }
   return FW_OK;
 }
 
-int run_linear_layers(Model* m, const LinearW& L0, int n_layers, int64_t w_lstride, int64_t b_lstride, const half_t* A,
-                      int64_t lda, int64_t a_bs, half_t* C, int64_t ldc, int64_t c_bs, int64_t c_lstride, int M, int batch,
-                      bool trans, int head_rows, hipStream_t st) {
-  fwk::GemmParams p = gemm_params(L0, A, lda, a_bs, L0.w, C, ldc, c_bs, M, head_rows);
-  p.n_layers = n_layers; p.w_lstride = w_lstride; p.bias_lstride = b_lstride; p.c_lstride = c_lstride;
-  if (fwk::launch_gemm(st ? st : m->stream, p, batch, trans) != 0) {
-    set_error("layered gemm: unsupported shape M=%d N=%d K=%d layers=%d", M, L0.N, L0.K, n_layers);
-    return FW_ERUNTIME;
-  }
-  return FW_OK;
-}
-
-// int8_float16 linear on "many rows" (K25): per-row dynamic quantisation of A (optionally through the
-// LayerNorm that feeds it), int8 x int8 -> int32 MFMA GEMM, de-quantising epilogue.  A == nullptr reuses the
-// rows quantised by the previous call (fused Q|K and V projections share their input).
-int run_linear_i8(Model* m, const LinearW& L, const half_t* A, const LNW* ln, half_t* C, int64_t ldc, int64_t c_bs,
-                  const half_t* res, int64_t ldr, int64_t r_bs, int M, int batch, int act, bool trans,
-                  int head_rows, hipStream_t st, int8_t* xq, float* xs) {
-  if (!st) st = m->stream;
-  if (!xq) { xq = m->ws_xq; xs = m->ws_xs; }
-  if (A) fwk::launch_quant_rows(st, A, L.K, ln ? ln->g : nullptr, ln ? ln->b : nullptr, xq, xs, batch * M, L.K);
-  fwk::GemmParams p = gemm_params(L, reinterpret_cast<const half_t*>(xq), L.K, (int64_t)M * L.K,
-                                  reinterpret_cast<const half_t*>(L.wq), C, ldc, c_bs, M, head_rows);
-  p.res = res; p.ldr = ldr; p.r_bstride = r_bs;
-  p.act = act;
-  p.a_scale = xs; p.as_bstride = M; p.w_scale = L.wscale;
-  if (fwk::launch_gemm(st, p, batch, trans) != 0) {
-    set_error("int8 gemm: unsupported shape M=%d N=%d K=%d", M, L.N, L.K);
-    return FW_ERUNTIME;
-  }
+int quantise_rows(Model* m, const half_t* A, const LNW* ln, int64_t rows, int K, hipStream_t st, QuantRows& qr) {
+  FW_CHECK_ARG(qr.fits(rows, K), "quantise_rows: %lld rows x %d = %lld elements, the buffer holds %lld rows, %lld elements",
+               (long long)rows, K, (long long)(rows * K), (long long)qr.cap_rows, (long long)qr.cap_elems);
+  fwk::launch_quant_rows(st ? st : m->stream, A, K, ln ? ln->g : nullptr, ln ? ln->b : nullptr, qr.q, qr.scale, (int)rows, K);
+  qr.rows = rows; qr.ld = K;
   return FW_OK;
 }
 
 int run_encoder(Model* m, int B, half_t* out) {
   const fw_config& c = m->cfg;
   const int d = c.d_model, T = c.n_audio_ctx, H = c.n_heads;
-  const int64_t xs = (int64_t)T * d;
+  const int64_t xs = (int64_t)T * d, vts = (int64_t)d * m->t_pad;
+  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
+  auto gemm_flops = [&](double rows, double k) { return 2.0 * B * rows * d * k; };
   int rc;
   {
     // conv1: k=3, s=1 over the channel-last mel image; GELU; output rows 1..3000 of the padded conv1 image
-    ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * 3000.0 * d * (3.0 * c.n_mels), 0);
-    if ((rc = run_linear(m, m->conv1, m->ws_mel_cl, m->c_pad, (int64_t)3002 * m->c_pad, m->ws_conv1 + d, d,
-                         (int64_t)3002 * d, nullptr, 0, 0, 3000, B, 1, false)))
+    ProfScope ps(m, PF_ENC_GEMM, gemm_flops(3000.0, 3.0 * c.n_mels), 0);
+    if ((rc = run_linear(m, m->conv1, {.in = {m->ws_mel_cl, m->c_pad, (int64_t)3002 * m->c_pad}, .C = m->ws_conv1 + d,
+                                       .ldc = d, .c_bs = (int64_t)3002 * d, .M = 3000, .batch = B, .act = 1})))
       return rc;
   }
   {
     // conv2: k=3, s=2: row t reads padded rows 2t..2t+2 (lda = 2d, K = 3d); GELU; + positional embedding
-    ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * (3.0 * d), 0);
-    if ((rc = run_linear(m, m->conv2, m->ws_conv1, 2 * d, (int64_t)3002 * d, m->ws_x, d, xs, m->enc_pos, d, 0, T, B,
-                         1, false)))
+    ProfScope ps(m, PF_ENC_GEMM, gemm_flops(T, 3.0 * d), 0);
+    if ((rc = run_linear(m, m->conv2, {.in = {m->ws_conv1, 2 * d, (int64_t)3002 * d}, .C = m->ws_x, .ldc = d, .c_bs = xs,
+                                       .res = m->enc_pos, .ldr = d, .r_bs = 0, .M = T, .batch = B, .act = 1})))
       return rc;
   }
   half_t* x = m->ws_x;
   half_t* x2 = m->ws_x2;
-  const bool i8 = m->compute_type == FW_COMPUTE_INT8_FLOAT16;
+  // The two compute types meet in the input of a layer's linears, a [B * T][K] dense, through LayerNorm ln when given:
+  // fp16 launches the LayerNorm into ws_xn (normed, before the GEMMs' scope opens) and reads halves; int8_float16
+  // quantises every linear's input per row, the LayerNorm fused into the quantiser (input, inside the GEMMs' scope)
+  auto normed = [&](const half_t* a, const LNW& ln) -> const half_t* {
+    if (i8) return a;
+    ProfScope ps(m, PF_ENC_LN, 0, 4.0 * B * T * d);
+    fwk::launch_layernorm(m->stream, a, ln.g, ln.b, m->ws_xn, B * T, d);
+    return m->ws_xn;
+  };
+  auto input = [&](const half_t* a, int K, const LNW* ln, LinIn& in) -> int {
+    if (!i8) { in = {a, K, (int64_t)T * K}; return FW_OK; }
+    in = {.xq = &m->ws_xq};
+    return quantise_rows(m, a, ln, (int64_t)B * T, K, m->stream, m->ws_xq);
+  };
   for (int l = 0; l < c.n_enc_layers; ++l) {
     const EncLayerW& L = m->enc[l];
-    if (i8) {
-      // int8_float16: LayerNorm fused into the quantiser; every linear input is quantised per row
-      {
-        ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * (3.0 * d), 0);
-        if ((rc = run_linear_i8(m, L.qk, x, &L.ln1, m->ws_qk, 2 * d, (int64_t)T * 2 * d, nullptr, 0, 0, T, B, 0, false,
-                                0)))
-          return rc;
-        if ((rc = run_linear_i8(m, L.v, nullptr, nullptr, m->ws_vt, m->t_pad, (int64_t)d * m->t_pad, nullptr, 0, 0, T,
-                                B, 0, true, 0)))
-          return rc;
-      }
-      {
-        ProfScope ps(m, PF_ENC_ATTN, 4.0 * B * (double)T * T * d, 0);
-        fwk::launch_attn_enc(m->stream, m->ws_qk, m->ws_qk + d, 2 * d, (int64_t)T * 2 * d, m->ws_vt, m->t_pad,
-                             (int64_t)d * m->t_pad, m->ws_att, d, xs, B, H, T);
-      }
-      {
-        ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * (9.0 * d), 0);
-        if ((rc = run_linear_i8(m, L.out, m->ws_att, nullptr, x2, d, xs, x, d, xs, T, B, 0, false, 0))) return rc;
-        if ((rc = run_linear_i8(m, L.ffn1, x2, &L.ln2, m->ws_ffn, 4 * d, (int64_t)T * 4 * d, nullptr, 0, 0, T, B, 1,
-                                false, 0)))
-          return rc;
-        if ((rc = run_linear_i8(m, L.ffn2, m->ws_ffn, nullptr, x, d, xs, x2, d, xs, T, B, 0, false, 0))) return rc;
-      }
-      continue;
-    }
+    LinIn in;
+    const half_t* h = normed(x, L.ln1);
     {
-      ProfScope ps(m, PF_ENC_LN, 0, 4.0 * B * T * d);
-      fwk::launch_layernorm(m->stream, x, L.ln1.g, L.ln1.b, m->ws_xn, B * T, d);
-    }
-    {
-      ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * (3.0 * d), 0);
-      if ((rc = run_linear(m, L.qk, m->ws_xn, d, xs, m->ws_qk, 2 * d, (int64_t)T * 2 * d, nullptr, 0, 0, T, B, 0,
-                           false)))
-        return rc;
-      if ((rc = run_linear(m, L.v, m->ws_xn, d, xs, m->ws_vt, m->t_pad, (int64_t)d * m->t_pad, nullptr, 0, 0, T, B, 0,
-                           true)))
+      ProfScope ps(m, PF_ENC_GEMM, gemm_flops(T, 3.0 * d), 0);
+      if ((rc = input(h, d, &L.ln1, in)) ||   // (int8_float16: quantised once, projected twice)
+          (rc = run_linear(m, L.qk, {.in = in, .C = m->ws_qk, .ldc = 2 * d, .c_bs = 2 * xs, .M = T, .batch = B})) ||
+          (rc = run_linear(m, L.v, {.in = in, .C = m->ws_vt, .ldc = m->t_pad, .c_bs = vts, .M = T, .batch = B, .trans = true})))
         return rc;
     }
     {
       ProfScope ps(m, PF_ENC_ATTN, 4.0 * B * (double)T * T * d, 0);
-      fwk::launch_attn_enc(m->stream, m->ws_qk, m->ws_qk + d, 2 * d, (int64_t)T * 2 * d, m->ws_vt, m->t_pad,
-                           (int64_t)d * m->t_pad, m->ws_att, d, xs, B, H, T);
+      fwk::launch_attn_enc(m->stream, {.q = m->ws_qk, .k = m->ws_qk + d, .ld = 2 * d, .qk_bstride = 2 * xs, .vt = m->ws_vt,
+                                       .ldvt = m->t_pad, .vt_bstride = vts, .out = m->ws_att, .ldo = d, .o_bstride = xs,
+                                       .B = B, .H = H, .T = T});
     }
-    {
-      ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * d, 0);
-      if ((rc = run_linear(m, L.out, m->ws_att, d, xs, x2, d, xs, x, d, xs, T, B, 0, false))) return rc;
-    }
-    {
-      ProfScope ps(m, PF_ENC_LN, 0, 4.0 * B * T * d);
-      fwk::launch_layernorm(m->stream, x2, L.ln2.g, L.ln2.b, m->ws_xn, B * T, d);
-    }
-    {
-      ProfScope ps(m, PF_ENC_GEMM, 2.0 * B * (double)T * d * (8.0 * d), 0);
-      if ((rc = run_linear(m, L.ffn1, m->ws_xn, d, xs, m->ws_ffn, 4 * d, (int64_t)T * 4 * d, nullptr, 0, 0, T, B, 1,
-                           false)))
-        return rc;
-      if ((rc = run_linear(m, L.ffn2, m->ws_ffn, 4 * d, (int64_t)T * 4 * d, x, d, xs, x2, d, xs, T, B, 0, false)))
-        return rc;
-    }
+    // the profile's grouping: int8_float16 has ONE scope over the out-projection and the FFN (9 d); fp16 closes the
+    // out-projection's (d) for the LayerNorm's own scope and opens the FFN's (8 d) after it
+    std::optional<ProfScope> ps;
+    ps.emplace(m, PF_ENC_GEMM, gemm_flops(T, i8 ? 9.0 * d : d), 0);
+    if ((rc = input(m->ws_att, d, nullptr, in)) ||
+        (rc = run_linear(m, L.out, {.in = in, .C = x2, .ldc = d, .c_bs = xs, .res = x, .ldr = d, .r_bs = xs, .M = T, .batch = B})))
+      return rc;
+    if (!i8) ps.reset();
+    h = normed(x2, L.ln2);
+    if (!i8) ps.emplace(m, PF_ENC_GEMM, gemm_flops(T, 8.0 * d), 0);
+    if ((rc = input(h, d, &L.ln2, in)) ||
+        (rc = run_linear(m, L.ffn1, {.in = in, .C = m->ws_ffn, .ldc = 4 * d, .c_bs = 4 * xs, .M = T, .batch = B, .act = 1})) ||
+        (rc = input(m->ws_ffn, 4 * d, nullptr, in)) ||
+        (rc = run_linear(m, L.ffn2, {.in = in, .C = x, .ldc = d, .c_bs = xs, .res = x2, .ldr = d, .r_bs = xs, .M = T, .batch = B})))
+      return rc;
   }
   {
     ProfScope ps(m, PF_ENC_LN, 0, 4.0 * B * T * d);

@@ -559,24 +559,25 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(fwk::GemmParams p) {
 
 namespace fwk {
 
-// tile order of launch_gemm: 1 = blocked (the product), 0 = n fastest across the whole width (rounds 1-3); a process-wide
+// tile order (gemm_plan): 1 = blocked (the product), 0 = n fastest across the whole width (rounds 1-3); a process-wide
 // knob for the A/B of profiles/gemm_bench.py (fw_test_knob)
 std::atomic<int> g_gemm_order{1};
 // plain V^T epilogue: 1 = staged through LDS (the product), 0 = direct stores (rounds 1-4); knob 5 of fw_test_knob
 std::atomic<int> g_gemm_vt_stage{1};
 
-int launch_gemm(hipStream_t st, const GemmParams& pin, int batch, bool trans) {
-  GemmParams p = pin;
-  const bool i8 = p.a_scale != nullptr;
+GemmPlan gemm_plan(const GemmParams& pin, int batch, bool trans) {
+  GemmPlan pl{pin, -1, 0};
+  GemmParams& p = pl.p;
+  const bool i8 = p.a_scale != nullptr, layered = p.n_layers > 1;
   const int es = i8 ? 1 : 2;
-  if (p.K <= 0 || (p.K * es) % 128 != 0) return -1;
-  if (((p.lda * es) % 16) || ((p.ldw * es) % 16) || ((p.a_bstride * es) % 16)) return -1;
-  if (!trans && ((p.N % 4) || (p.ldc % 4) || (p.c_bstride % 4))) return -1;
-  if (i8 && !p.w_scale) return -1;
+  if (p.K <= 0 || (p.K * es) % 128 != 0) return pl;
+  if (((p.lda * es) % 16) || ((p.ldw * es) % 16) || ((p.a_bstride * es) % 16)) return pl;
+  if (!trans && ((p.N % 4) || (p.ldc % 4) || (p.c_bstride % 4))) return pl;
+  if (i8 && !p.w_scale) return pl;
+  if (layered && (i8 || p.res)) return pl;      // (the int8 path keeps one launch per layer; no layered residual)
   p.nMt = (p.M + GB_M - 1) / GB_M;
   p.nNt_layer = (p.N + GB_N - 1) / GB_N;
-  if (p.n_layers > 1 && (i8 || p.res)) return -1;      // (the int8 path keeps one launch per layer; no layered residual)
-  p.nNt = p.nNt_layer * (p.n_layers > 1 ? p.n_layers : 1);
+  p.nNt = p.nNt_layer * (layered ? p.n_layers : 1);
   p.n_mp = p.nMt * batch;
   p.blk_m = p.blk_n = 0;
   // (16-byte row segments of Ct need ldc and the batch stride to be multiples of 8 halves)
@@ -596,42 +597,27 @@ int launch_gemm(hipStream_t st, const GemmParams& pin, int batch, bool trans) {
     p.blk_n = bn;
     p.blk_m = 32 / bn > 1 ? 32 / bn : 1;
   }
+  pl.kernel = layered ? 4 + trans : 2 * i8 + trans;
+  pl.grid = p.nMt * p.nNt * batch;
+  return pl;
+}
+
+int launch_gemm(hipStream_t st, const GemmParams& pin, int batch, bool trans) {
+  const GemmPlan pl = gemm_plan(pin, batch, trans);
+  if (pl.kernel < 0) return -1;
+  static void (*const kernels[6])(GemmParams) = {   // GemmPlan::kernel
+      gemm_f16_kernel<false, false>, gemm_f16_kernel<true, false>,       gemm_f16_kernel<false, true>,
+      gemm_f16_kernel<true, true>,   gemm_f16_kernel<false, false, true>, gemm_f16_kernel<true, false, true>};
   const int lds = GB_LDS_BYTES;  // 128 KiB: one workgroup per CU
   static std::atomic<unsigned long long> attr_done{0};   // one bit per device (the limit is a per-device attribute)
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<false, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<true, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<false, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<true, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    for (auto* k : kernels)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
   }
-  const int grid = p.nMt * p.nNt * batch;
-  if (p.n_layers > 1) {
-    static std::atomic<unsigned long long> attr_l{0};
-    if (!((attr_l.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<true, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr_l.fetch_or(1ull << (dev & 63), std::memory_order_release);
-    }
-    if (trans) gemm_f16_kernel<true, false, true><<<grid, 512, lds, st>>>(p);
-    else gemm_f16_kernel<false, false, true><<<grid, 512, lds, st>>>(p);
-    return 0;
-  }
-  if (i8) {
-    if (trans) gemm_f16_kernel<true, true><<<grid, 512, lds, st>>>(p);
-    else gemm_f16_kernel<false, true><<<grid, 512, lds, st>>>(p);
-  } else {
-    if (trans) gemm_f16_kernel<true, false><<<grid, 512, lds, st>>>(p);
-    else gemm_f16_kernel<false, false><<<grid, 512, lds, st>>>(p);
-  }
+  hipLaunchKernelGGL(kernels[pl.kernel], dim3(pl.grid), dim3(512), lds, st, pl.p);
   return 0;
 }
 

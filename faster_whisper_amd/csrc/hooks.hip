@@ -158,11 +158,7 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
   std::lock_guard<std::mutex> lk(m->mu);
   FW_HIP(hipSetDevice(m->device));
   const bool frag_kv = !use_int8 && (act_gelu == 8 || act_gelu == 9);
-  if (use_int8 && (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || (int64_t)M * K > (int64_t)m->max_batch * 1500 * 4 * m->cfg.d_model ||
-                   M > m->max_batch * 1500)) {
-    set_error("int8 gemm test needs an int8_float16 model and M*K within its quantisation workspace");
-    return FW_EINVAL;
-  }
+  FW_CHECK_ARG(!use_int8 || m->compute_type == FW_COMPUTE_INT8_FLOAT16, "int8 gemm test needs an int8_float16 model");
   if (frag_kv && (N % 64 || residual)) { set_error("fragment-major gemm test: N %% 64 == 0, no residual"); return FW_EINVAL; }
   HookBufs db;
   half_t *dA, *dW, *dB = nullptr, *dR = nullptr, *dC;
@@ -172,16 +168,17 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
       (rc = db.alloc(&dC, (size_t)M * N)))
     return rc;
   LinearW L{dW, dB, nullptr, nullptr, nullptr, nullptr, N, K};
+  LinIn in{dA, K, 0};
   if (use_int8) {
     int8_t* dWq;
     float* dWs;
-    if ((rc = upload_quant_w(db, W, N, K, [&](int n, int k) { return (size_t)n * K + k; }, &dWq, &dWs))) return rc;
+    if ((rc = upload_quant_w(db, W, N, K, [&](int n, int k) { return (size_t)n * K + k; }, &dWq, &dWs)) ||
+        (rc = quantise_rows(m, dA, nullptr, M, K, nullptr, m->ws_xq)))
+      return rc;
     L.wq = dWq; L.wscale = dWs;
-    if (act_gelu >= 2)
-      rc = run_linear_i8(m, L, dA, nullptr, dC, M, 0, nullptr, 0, 0, M, 1, act_gelu - 2, true, 0);
-    else
-      rc = run_linear_i8(m, L, dA, nullptr, dC, N, 0, dR, N, 0, M, 1, act_gelu, false, 0);
-  } else if (frag_kv) {
+    in = {.xq = &m->ws_xq};
+  }
+  if (frag_kv) {
     // the cross-attention K (8) / V^T (9) projection epilogues: output MFMA-fragment-major per 64-column head
     // (gemm.hip), un-permuted here into out [M][N]; the padded keys of the last 32-key group must stay zero
     const bool vt = act_gelu == 9;
@@ -189,9 +186,9 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
     std::vector<float> hf((size_t)H * kvp * 64);
     half_t* dF;
     if ((rc = db.alloc(&dF, hf.size())) || (rc = db.zero(dF, hf.size() * sizeof(half_t), m->stream))) return rc;
-    rc = vt ? run_linear(m, L, dA, K, 0, dF, kvp, 0, nullptr, 0, 0, M, 1, 0, true, kvp)
-            : run_linear(m, L, dA, K, 0, dF, N, 0, nullptr, 0, 0, M, 1, 0, false, kvp);
-    if (rc || (rc = download_f16(m->stream, hf.data(), dF, hf.size()))) return rc;
+    if ((rc = run_linear(m, L, {.in = in, .C = dF, .ldc = vt ? kvp : N, .M = M, .trans = vt, .head_rows = kvp})) ||
+        (rc = download_f16(m->stream, hf.data(), dF, hf.size())))
+      return rc;
     for (int mm = 0; mm < kvp; ++mm)
       for (int n = 0; n < N; ++n) {
         const size_t off = cross_kv_frag_pos(vt, kvp, mm, n);
@@ -199,12 +196,10 @@ int32_t fw_test_gemm(fw_model* fm, const float* A, const float* W, const float* 
         else if (hf[off] != 0.f) { set_error("fragment-major epilogue wrote the padded key %d", mm); return FW_ERUNTIME; }
       }
     return FW_OK;
-  } else if (act_gelu >= 2) {
-    // transposed-output mode: out is [N][M]
-    rc = run_linear(m, L, dA, K, 0, dC, M, 0, nullptr, 0, 0, M, 1, act_gelu - 2, true);
-  } else {
-    rc = run_linear(m, L, dA, K, 0, dC, N, 0, dR, N, 0, M, 1, act_gelu, false);
   }
+  const bool trans = act_gelu >= 2;   // transposed-output mode: out is [N][M], act = act_gelu - 2, no residual
+  rc = run_linear(m, L, {.in = in, .C = dC, .ldc = trans ? M : N, .res = trans ? nullptr : dR, .ldr = trans ? 0 : N, .M = M,
+                         .act = trans ? act_gelu - 2 : act_gelu, .trans = trans});
   return rc ? rc : download_f16(m->stream, out, dC, (size_t)M * N);
 }
 
@@ -326,6 +321,25 @@ int32_t fw_test_dec_linear_plan(int32_t R, int32_t N, int32_t K, int32_t ldo, in
   return FW_OK;
 }
 
+// host-only: what a launch of the encoder GEMM does (gemm.hip: gemm_plan); needs no device
+int32_t fw_test_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t batch, int64_t lda, int64_t ldw, int64_t a_bstride,
+                          int64_t ldc, int64_t c_bstride, int32_t trans, int32_t int8, int32_t head_rows, int32_t n_layers,
+                          int32_t has_res, int32_t out[9]) {
+  static const float some_scale = 1.f;   // (the plan asks only whether the pointers are set)
+  static const half_t some_res = 0;
+  fwk::GemmParams p{};
+  p.lda = lda; p.a_bstride = a_bstride; p.ldw = ldw; p.ldc = ldc; p.c_bstride = c_bstride;
+  p.M = M; p.N = N; p.K = K;
+  p.head_rows = head_rows; p.n_layers = n_layers;
+  p.a_scale = int8 ? &some_scale : nullptr;
+  p.w_scale = int8 == 1 ? &some_scale : nullptr;
+  p.res = has_res ? &some_res : nullptr;
+  const fwk::GemmPlan pl = fwk::gemm_plan(p, batch, trans != 0);
+  const int32_t f[9] = {pl.kernel, pl.p.nMt, pl.p.nNt, pl.p.nNt_layer, pl.p.n_mp, pl.p.blk_n, pl.p.blk_m, pl.p.vt_stage, pl.grid};
+  memcpy(out, f, sizeof(f));   // (a refused shape: kernel -1, the rest as passed in: 0)
+  return FW_OK;
+}
+
 // host-only: the form a decode step's self-attention takes (dec_kernels.hip: self_attn_form); needs no device
 int32_t fw_test_self_attn_form(int32_t n_ctx, int32_t cache_ctx, int32_t d, int32_t R_total, int32_t kmul, int32_t H,
                                int32_t chunks, int32_t knob) {
@@ -441,13 +455,14 @@ int32_t fw_bench_gemm(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t bat
   if (i8 && ((rc = db.alloc(&dsa, (size_t)batch * M)) || (rc = db.alloc(&dsw, (size_t)N)) ||
              (rc = db.zero(dsa, (size_t)batch * M * 4, m->stream)) || (rc = db.zero(dsw, (size_t)N * 4, m->stream))))
     return rc;
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = dA; p.lda = lda; p.a_bstride = (int64_t)M * lda;
-  p.W = dW; p.ldw = ldw;
-  p.C = dC; p.ldc = trans ? ldct : N; p.c_bstride = trans ? (int64_t)N * ldct : (int64_t)M * N;
-  p.M = M; p.N = N; p.K = K;
-  p.a_scale = dsa; p.as_bstride = M; p.w_scale = dsw;
+  // (int8: the same bytes as codes, behind a record that describes them — rows of ld = lda codes — without owning them)
+  QuantRows xq;
+  xq.q = reinterpret_cast<int8_t*>(dA); xq.scale = dsa; xq.ld = lda;
+  const LinearW L{dW, nullptr, reinterpret_cast<const int8_t*>(dW), dsw, nullptr, nullptr, N, K};
+  LinCall call{.C = dC, .ldc = trans ? ldct : N, .c_bs = trans ? (int64_t)N * ldct : (int64_t)M * N, .M = M};
+  if (i8) call.in = {.xq = &xq};
+  else call.in = {dA, lda, (int64_t)M * lda};
+  const fwk::GemmParams p = gemm_params(L, call, ldw);
   float ms = 0.f;
   rc = time_launches(m->stream, 1, iters, [&](int) { return fwk::launch_gemm(m->stream, p, batch, trans != 0); }, &ms);
   if (rc == LAUNCH_REFUSED) { set_error("gemm bench failed: unsupported shape"); return FW_ERUNTIME; }
@@ -487,23 +502,17 @@ int32_t fw_bench_gemm_epi(fw_model* fm, int32_t M, int32_t N, int32_t K, int32_t
       (res && (rc = fill_lcg(dR, nr1, stage, 4242u, 1e-3f))) || (rc = db.zero(dC, nc * 2, m->stream)))
     return rc;
   for (int c = 1; res && c < copies; ++c) FW_HIP(hipMemcpy(dR + (size_t)c * nr1, dR, nr1 * 2, hipMemcpyDeviceToDevice));
-  fwk::GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = dA; p.lda = lda; p.a_bstride = (int64_t)M * lda;
-  p.W = dW; p.ldw = K;
-  p.bias = bias ? dB : nullptr;
-  p.C = dC; p.ldc = layered ? (trans ? kvp : N) : (trans ? ldct : N); p.c_bstride = c_bs;
-  p.M = M; p.N = N; p.K = K;
-  p.act = act;
+  const LinearW L{dW, bias ? dB : nullptr, nullptr, nullptr, nullptr, nullptr, N, K};
+  LinCall call{.in = {dA, lda, (int64_t)M * lda}, .C = dC, .ldc = trans ? ldct : N, .c_bs = c_bs, .ldr = N,
+               .r_bs = res == 1 ? (int64_t)M * N : 0, .M = M, .act = act};
   if (layered) {
-    p.head_rows = (int)kvp;
-    p.n_layers = n_layers; p.w_lstride = (int64_t)N * K; p.bias_lstride = N; p.c_lstride = c_ls;
+    call.head_rows = (int)kvp;
+    call.n_layers = n_layers; call.w_ls = (int64_t)N * K; call.b_ls = N; call.c_ls = c_ls;
   }
-  p.ldr = N; p.r_bstride = res == 1 ? (int64_t)M * N : 0;
   float ms = 0.f;
   rc = time_launches(m->stream, 1, iters, [&](int i) {
-    p.res = res ? dR + (size_t)(i % copies) * nr1 : nullptr;
-    return fwk::launch_gemm(m->stream, p, batch, trans != 0);
+    call.res = res ? dR + (size_t)(i % copies) * nr1 : nullptr;
+    return fwk::launch_gemm(m->stream, gemm_params(L, call, K), batch, trans != 0);
   }, &ms);
   if (rc == LAUNCH_REFUSED) { set_error("gemm epilogue bench failed: unsupported shape"); return FW_ERUNTIME; }
   if (rc) return rc;
@@ -640,14 +649,8 @@ int32_t fw_test_gemm_ex(fw_model* fm, const float* A, int64_t a_elems, int64_t l
 
   Model* m = &fm->impl;
   std::lock_guard<std::mutex> lk(m->mu);
-  if (use_int8) {
-    const int64_t T = m->cfg.n_audio_ctx;
-    if (m->compute_type != FW_COMPUTE_INT8_FLOAT16 || (int64_t)batch * M * K > (int64_t)m->max_batch * T * 4 * m->cfg.d_model ||
-        (int64_t)batch * M > (int64_t)m->max_batch * T || (ln_g && K > 1536)) {
-      set_error("int8 gemm test needs an int8_float16 model, batch*M*K within its quantisation workspace, K <= 1536 with LayerNorm");
-      return FW_EINVAL;
-    }
-  }
+  FW_CHECK_ARG(!use_int8 || (m->compute_type == FW_COMPUTE_INT8_FLOAT16 && !(ln_g && K > 1536)),
+               "int8 gemm test needs an int8_float16 model, K <= 1536 with LayerNorm");
   FW_HIP(hipSetDevice(m->device));
   HookBufs db;
   half_t *dA, *dW, *dB = nullptr, *dR = nullptr, *dC, *dG = nullptr, *dLb = nullptr;
@@ -658,21 +661,20 @@ int32_t fw_test_gemm_ex(fw_model* fm, const float* A, int64_t a_elems, int64_t l
       (ln_g && ((rc = db.upload_f16(&dG, ln_g, K)) || (rc = db.upload_f16(&dLb, ln_b, K)))))
     return rc;
   LinearW L{dW, dB, nullptr, nullptr, nullptr, nullptr, N, K};
+  LinCall call{.in = {dA, lda, a_bstride}, .C = dC + c_off, .ldc = ldc, .c_bs = c_bstride, .res = dR, .ldr = ldr,
+               .r_bs = r_bstride, .M = M, .batch = batch, .act = act, .trans = trans != 0, .head_rows = head_rows,
+               .n_layers = n_layers, .w_ls = (int64_t)N * K, .b_ls = bias ? N : 0, .c_ls = c_lstride};
   if (use_int8) {
     int8_t* dWq;
     float* dWs;
-    if ((rc = upload_quant_w(db, W, N, K, [&](int n, int k) { return (size_t)n * K + k; }, &dWq, &dWs))) return rc;
+    const LNW ln{dG, dLb};
+    if ((rc = upload_quant_w(db, W, N, K, [&](int n, int k) { return (size_t)n * K + k; }, &dWq, &dWs)) ||
+        (rc = quantise_rows(m, dA, ln_g ? &ln : nullptr, (int64_t)batch * M, K, nullptr, m->ws_xq)))
+      return rc;
     L.wq = dWq; L.wscale = dWs;
-    LNW ln{dG, dLb};
-    rc = run_linear_i8(m, L, dA, ln_g ? &ln : nullptr, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act,
-                       trans != 0, head_rows);
-  } else if (n_layers > 1) {
-    rc = run_linear_layers(m, L, n_layers, (int64_t)N * K, bias ? N : 0, dA, lda, a_bstride, dC + c_off, ldc, c_bstride,
-                           c_lstride, M, batch, trans != 0, head_rows, nullptr);
-  } else {
-    rc = run_linear(m, L, dA, lda, a_bstride, dC + c_off, ldc, c_bstride, dR, ldr, r_bstride, M, batch, act, trans != 0,
-                    head_rows, nullptr);
+    call.in = {.xq = &m->ws_xq};
   }
+  rc = run_linear(m, L, call);
   return rc ? rc : download_f16(m->stream, C, dC, (size_t)c_elems);
 }
 
@@ -695,8 +697,9 @@ int32_t fw_test_attention(fw_model* fm, const float* q, const float* k, const fl
   if ((rc = db.upload_f16(&dq, q, n)) || (rc = db.upload_f16(&dk, k, n)) || (rc = db.upload_f16(&dvt, vt.data(), vt.size())) ||
       (rc = db.alloc(&dout, n)))
     return rc;
-  fwk::launch_attn_enc(m->stream, dq, dk, d, (int64_t)T * d, dvt, tp, (int64_t)d * tp, dout, d, (int64_t)T * d, B, H,
-                       T);
+  fwk::launch_attn_enc(m->stream, {.q = dq, .k = dk, .ld = d, .qk_bstride = (int64_t)T * d, .vt = dvt, .ldvt = tp,
+                                   .vt_bstride = (int64_t)d * tp, .out = dout, .ldo = d, .o_bstride = (int64_t)T * d,
+                                   .B = B, .H = H, .T = T});
   return download_f16(m->stream, out, dout, n);
 }
 
@@ -718,11 +721,10 @@ int32_t fw_bench_attention(fw_model* fm, int32_t B, int32_t H, int32_t T, int32_
       (rc = fill_lcg(dqk, nqk, stage, 777u, 2e-3f)) || (rc = fill_lcg(dvt, nvt, stage, 777u, 2e-3f)))
     return rc;
   float ms = 0.f;
-  rc = time_launches(m->stream, 1, iters, [&](int) {
-    fwk::launch_attn_enc(m->stream, dqk, dqk + d, 2 * d, (int64_t)T * 2 * d, dvt, tp, (int64_t)d * tp, dout, d, (int64_t)T * d, B,
-                         H, T, variant);
-    return 0;
-  }, &ms);
+  const fwk::AttnEnc att{.q = dqk, .k = dqk + d, .ld = 2 * d, .qk_bstride = (int64_t)T * 2 * d, .vt = dvt, .ldvt = tp,
+                         .vt_bstride = (int64_t)d * tp, .out = dout, .ldo = d, .o_bstride = (int64_t)T * d,
+                         .B = B, .H = H, .T = T, .order = variant};
+  rc = time_launches(m->stream, 1, iters, [&](int) { fwk::launch_attn_enc(m->stream, att); return 0; }, &ms);
   if (rc) return rc;
   *ms_out = ms / (float)iters;
   return FW_OK;

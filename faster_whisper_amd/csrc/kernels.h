@@ -27,7 +27,7 @@ struct GemmParams {
                                                       // layout per 64-column head, head_rows = keys per head padded to 32
   // int8 path (a_scale != null): A and W point to int8 data; dequant scales per A row / per W row
   const float* a_scale; int64_t as_bstride; const float* w_scale;
-  int nMt, nNt;                                       // filled by launch_gemm
+  int nMt, nNt;                                       // filled by gemm_plan
   int n_mp, blk_m, blk_n;                             // ... m panels of the whole batch, tile-order block (gemm.hip)
   int vt_stage;                                       // ... TRANS, plain Ct: epilogue staged through LDS (gemm.hip), 0 = direct stores
   // LAYERED launch (n_layers > 1; fp16 only): the same A is multiplied with the W of n_layers layers in ONE launch — the
@@ -35,9 +35,17 @@ struct GemmParams {
   // layer l reads W + l * w_lstride, bias + l * bias_lstride and writes C + l * c_lstride (element strides).  Used for the
   // cross-attention K / V^T projections of all decoder layers (decoder.hip: 2 launches instead of 2 x 32)
   int n_layers; int64_t w_lstride, bias_lstride, c_lstride;
-  int nNt_layer;                                      // filled by launch_gemm: n tiles of one layer
+  int nNt_layer;                                      // filled by gemm_plan: n tiles of one layer
 };
-int launch_gemm(hipStream_t st, const GemmParams& p, int batch, bool trans);
+// What a launch does for (p, batch, trans) — host arithmetic only, and the ONE place that knows which shapes are
+// refused, the tile counts, the tile-order block (knob 1), the vt_stage condition (knob 5) and which instantiation runs
+struct GemmPlan {
+  GemmParams p;   // the caller's, with the "filled by gemm_plan" fields set
+  int kernel;     // trans + 2 * int8, layered: 4 + trans (launch_gemm's table); -1: the shape is refused
+  int grid;
+};
+GemmPlan gemm_plan(const GemmParams& p, int batch, bool trans);
+int launch_gemm(hipStream_t st, const GemmParams& p, int batch, bool trans);   // non-zero: refused, nothing launched
 extern std::atomic<int> g_gemm_order;                 // tile order knob (gemm.hip), for A/B measurements only
 extern std::atomic<int> g_gemm_vt_stage;              // 1 (product): the plain V^T epilogue goes through LDS; 0: direct stores (A/B)
 
@@ -57,8 +65,13 @@ void launch_f16_to_f32(hipStream_t st, const half_t* x, float* y, int64_t n);
 // ---- encoder attention (attn_enc.hip) ---------------------------------------------
 // q,k: [B][T][ld] fp16 (head h at column h*64), vt: [B][H*64][ldvt] (V transposed, time contiguous)
 // out: [B][T][ldo]. softmax(q k^T / 8) v, non-causal, T keys.
-void launch_attn_enc(hipStream_t st, const half_t* q, const half_t* k, int64_t ld, int64_t qk_bstride,
-                     const half_t* vt, int64_t ldvt, int64_t vt_bstride, half_t* out, int64_t ldo,
-                     int64_t o_bstride, int B, int H, int T, int order = 0);
+struct AttnEnc {
+  const half_t *q, *k; int64_t ld, qk_bstride;
+  const half_t* vt; int64_t ldvt, vt_bstride;
+  half_t* out; int64_t ldo, o_bstride;
+  int B, H, T;
+  int order = 0;   // workgroup mapping (attn_enc.hip): 0 = XCD-aware, the product's; 1 = round 3's (A/B)
+};
+void launch_attn_enc(hipStream_t st, const AttnEnc& a);
 
 }  // namespace fwk

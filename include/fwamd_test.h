@@ -139,12 +139,12 @@ int32_t fw_test_layernorm_frag(fw_model* m, const float* x, const float* g, cons
  * d % 64 == 0; d <= 1536 with LayerNorm, <= 5120 without (the kernel's limits). */
 int32_t fw_test_quant_rows(fw_model* m, const float* x, int32_t rows, int32_t d, int64_t ldx, const float* ln_g,
                            const float* ln_b, int32_t frag, int8_t* xq, float* scale);
-/* one launch of the encoder GEMM in any form the product launches, through the product's entry points (engine.hip:
- * run_linear; run_linear_layers when n_layers > 1; run_linear_i8 when use_int8).  The caller describes the device buffers
- * as they lie in memory (all counts in elements):
+/* one launch of the encoder GEMM in any form the product launches, through the product's entry point (engine.hip:
+ * run_linear; use_int8: quantise_rows into the model's quantisation workspace first — FW_EINVAL when batch * M rows of K
+ * do not fit it).  The caller describes the device buffers as they lie in memory (all counts in elements):
  *   A    a_elems values; chunk z, row r starts at z * a_bstride + r * lda (rows may overlap: conv2 has lda < K).
- *        use_int8: contiguous [batch * M][K] (lda = K, a_bstride = M * K: what run_linear_i8 takes), quantised by the
- *        launch's own row quantiser, through LayerNorm(ln_g, ln_b [K]) when those are given
+ *        use_int8: contiguous [batch * M][K] (lda = K, a_bstride = M * K: what quantise_rows takes), quantised by the
+ *        product's row quantiser, through LayerNorm(ln_g, ln_b [K]) when those are given
  *   W    [n_layers][N][K], bias [n_layers][N] | NULL (use_int8: W quantised per row on the host like fw_test_gemm)
  *   res  r_elems values | NULL; chunk z, row r at z * r_bstride + r * ldr (r_bstride = 0: one block shared by all
  *        chunks); row-major output only
@@ -242,6 +242,16 @@ int32_t fw_test_run_capacity(int32_t lane_chunks, int32_t max_batch, int32_t max
  * per workgroup and k-steps of loads in flight per wave (0 otherwise), out[5] waves K is split over (4 | 8) */
 int32_t fw_test_dec_linear_plan(int32_t R, int32_t N, int32_t K, int32_t ldo, int32_t ldr, int32_t compute_type,
                                 int32_t form, int32_t out[6]);
+/* host-only (no device needed): what the encoder GEMM's launcher does for a launch of C[batch][M][N] = A[batch][M][K]
+ * W[N][K]^T (gemm.hip: gemm_plan, the one place that decides it) under the current knobs 1 and 5.  Strides in elements;
+ * int8 0: fp16 operands, 1: int8 codes with both scales, 2: int8 codes without the weight scale; has_res: a residual.
+ * out[0] instantiation (-1: the shape is refused and nothing would be launched; else trans + 2 * int8, layered 4 + trans),
+ * out[1] m tiles of a chunk, out[2] n tiles of all layers, out[3] n tiles of one layer, out[4] m panels of the batch,
+ * out[5] / out[6] the tile-order block in n tiles / m panels (0 / 0: n fastest across the width), out[7] vt_stage,
+ * out[8] workgroups */
+int32_t fw_test_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t batch, int64_t lda, int64_t ldw, int64_t a_bstride,
+                          int64_t ldc, int64_t c_bstride, int32_t trans, int32_t int8, int32_t head_rows, int32_t n_layers,
+                          int32_t has_res, int32_t out[9]);
 /* host-only (no device needed): the form (1 first, 2 latency, 3 throughput) the decode self-attention takes for `chunks`
  * chunks of kmul rows and H heads under knob 2's value `knob`; n_ctx / cache_ctx / d / R_total: the cache geometry as in
  * fw_test_dec_self_attn (R_total = cache slots per layer) */

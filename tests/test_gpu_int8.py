@@ -88,6 +88,42 @@ def test_gemm_int8_transposed_epilogue(kmodel, M, N, K):
     assert np.abs(out - ref).max() / np.abs(ref).max() < 1e-3
 
 
+def test_gemm_int8_quantisation_workspace_bound(kmodel):
+    """the rows an int8 linear quantises must fit the model's quantisation workspace (csrc/engine.hip: quantise_rows; for
+    this model max_batch x 1500 = 3000 rows and 3000 x 4 d = 3000 x 512 codes): exactly 3000 rows run and match the
+    references, 3001 rows — or 3000 rows of 640 — are refused with FW_EINVAL before anything is launched"""
+    import gemm_refs as gr
+    from faster_whisper_amd import _lib
+    lib = _lib.load()
+    N, K, cap = 64, 128, 3000
+    rng = np.random.default_rng(41)
+    W = _h(rng.standard_normal((N, K)).astype(np.float32) * 0.3)
+    b = _h(rng.standard_normal(N).astype(np.float32))
+
+    def launch(A, batch, M, W=W, K=K):
+        C = gr.sentinel_buffer(batch * M * N + 64)
+        rc = lib.fw_test_gemm_ex(kmodel._replicas[0].handle, _lib.ptr(A), A.size, K, M * K, _lib.ptr(W), _lib.ptr(b), None,
+                                 0, 0, 0, _lib.ptr(C), C.size, 0, N, M * N, 0, M, N, K, batch, 1, 0, 0, 0, 1, None, None)
+        return rc, C
+
+    A = _h(rng.standard_normal((cap + 1, K)).astype(np.float32))
+    rc, C = launch(A, 1, cap + 1)                                  # one row beyond
+    assert rc == _lib.FW_EINVAL and b"3001 rows" in lib.fw_last_error() and (C == gr.SENTINEL).all()
+    W5 = np.zeros((N, 5 * K), np.float32)
+    rc, C = launch(np.zeros((cap, 5 * K), np.float32), 2, cap // 2, W=W5, K=5 * K)   # the rows fit, their codes do not
+    assert rc == _lib.FW_EINVAL and (C == gr.SENTINEL).all()
+    rc, C = launch(A[:cap], 2, cap // 2)                           # exactly at capacity, as two chunks
+    _lib.check(rc)
+    out = C[:cap * N].reshape(cap, N)
+    assert (C[cap * N:] == gr.SENTINEL).all()
+    aq, a_s = _quant_rows(A[:cap])
+    wq, w_s = _quant_rows(W)
+    ref = _h((aq @ wq.T).astype(np.float32) * a_s[:, None] * w_s[None, :] + b)
+    assert np.abs(out - ref).max() / max(1.0, np.abs(ref).max()) < 1e-3          # test_gemm_int8_exact's bounds
+    full = gr.gemm64(A[:cap], W, b)
+    assert np.abs(out - full).max() / np.abs(full).max() < 5e-2
+
+
 @pytest.mark.parametrize("R,N,K", [(80, 1280, 1280), (80, 5120, 1280), (80, 1280, 5120), (77, 3840, 1280),
                                    (5, 128, 128), (333, 256, 512), (640, 1280, 1280),
                                    # merged runs: 4 x 4 tiles per workgroup from 1 024 rows on (ragged last row group)

@@ -269,6 +269,116 @@ def test_decoder_linear_plan_states_the_products_choice():
     assert lib.fw_dec_big_min_rows() == lib.fw_dec_big_min_rows_of(-1, 0) == 512
 
 
+def test_encoder_gemm_plan_states_the_products_choice():
+    """What the encoder GEMM's launcher does for a launch (csrc/gemm.hip: gemm_plan, through the host-only hook
+    fw_test_gemm_plan — no device involved).  The GPU tests compare the blocked tile order and the staged V^T epilogue with
+    their knob-off forms bit for bit; this one states, as literal expectations, which tile-order block, epilogue and
+    instantiation the PRODUCT chooses for the encoder's own launches (large-v3: d = 1280, 32 decoder layers; tiny: d = 384,
+    4 decoder layers; T = 1500, conv1's M = 3000; one chunk and 16), and which shapes it refuses.  The tile is 256 x 256."""
+    import ctypes as C
+    from faster_whisper_amd import _lib
+    lib = _lib.load()
+    REFUSED = (-1, 0, 0, 0, 0, 0, 0, 0, 0)
+    F16, F16_T, I8, I8_T, LAYERED, LAYERED_T = range(6)      # the instantiations: trans + 2 * int8, layered 4 + trans
+
+    def plan(M, N, K, batch=1, lda=None, ldw=None, a_bs=None, ldc=None, c_bs=None, trans=0, int8=0, head_rows=0,
+             n_layers=1, res=0):
+        lda = K if lda is None else lda
+        ldc = ((M + 63) // 64 * 64 if trans else N) if ldc is None else ldc
+        out = (C.c_int32 * 9)()
+        assert lib.fw_test_gemm_plan(M, N, K, batch, lda, K if ldw is None else ldw, M * lda if a_bs is None else a_bs,
+                                     ldc, (N if trans else M) * ldc if c_bs is None else c_bs, trans, int8, head_rows,
+                                     n_layers, res, out) == 0
+        return tuple(out)
+
+    def want(kernel, nMt, nNt, batch, blk, vt_stage=0, n_layers=1):
+        """blk = (n tiles, m panels) of the tile-order block"""
+        return (kernel, nMt, nNt, nNt // n_layers, nMt * batch, blk[0], blk[1], vt_stage, nMt * nNt * batch)
+
+    T, kvp, t_pad = 1500, 1504, 1536
+    for batch in (1, 16):
+        for int8 in (0, 1):
+            lin, lin_t = (I8, I8_T) if int8 else (F16, F16_T)
+            # ---- large-v3: every width is a multiple of 5 n tiles -> blocks of 5 n tiles x 6 m panels
+            d = 1280
+            kw = dict(batch=batch, int8=int8)
+            assert plan(T, 2 * d, d, **kw) == want(lin, 6, 10, batch, (5, 6))                              # Q|K
+            # V^T: the staged epilogue is the fp16 one's
+            assert plan(T, d, d, trans=1, ldc=t_pad, **kw) == want(lin_t, 6, 5, batch, (5, 6), vt_stage=1 - int8)
+            assert plan(T, d, d, res=1, **kw) == want(lin, 6, 5, batch, (5, 6))                            # out
+            assert plan(T, 4 * d, d, **kw) == want(lin, 6, 20, batch, (5, 6))                              # ffn1
+            assert plan(T, d, 4 * d, res=1, **kw) == want(lin, 6, 5, batch, (5, 6))                        # ffn2
+            # ---- tiny: 3 x 10 for Q|K, 2 x 16 for the d-wide outputs, 6 x 5 for ffn1
+            d = 384
+            assert plan(T, 2 * d, d, **kw) == want(lin, 6, 3, batch, (3, 10))
+            assert plan(T, d, d, trans=1, ldc=t_pad, **kw) == want(lin_t, 6, 2, batch, (2, 16), vt_stage=1 - int8)
+            assert plan(T, d, d, res=1, **kw) == want(lin, 6, 2, batch, (2, 16))
+            assert plan(T, 4 * d, d, **kw) == want(lin, 6, 6, batch, (6, 5))
+            assert plan(T, d, 4 * d, res=1, **kw) == want(lin, 6, 2, batch, (2, 16))
+        # the convolutions are fp16 GEMMs in both compute types: conv1 over the padded mel image (128 channels, K = 3 x 128,
+        # rows one channel row apart), conv2 over the padded conv1 image (K = 3 d, rows 2 d apart)
+        for d, blk in ((1280, (5, 6)), (384, (2, 16))):
+            nNt = -(-d // 256)
+            assert plan(3000, d, 384, batch=batch, lda=128, a_bs=3002 * 128, c_bs=3002 * d) == want(F16, 12, nNt, batch, blk)
+            assert plan(T, d, 3 * d, batch=batch, lda=2 * d, a_bs=3002 * d, res=1) == want(F16, 6, nNt, batch, blk)
+            # cross-attention K / V^T, fragment-major (head_rows), one launch per layer (int8_float16, knob 6 off) ...
+            for int8 in (0, 1):
+                assert plan(T, d, d, batch=batch, c_bs=d * kvp, head_rows=kvp, int8=int8) == \
+                    want(I8 if int8 else F16, 6, nNt, batch, blk)
+                assert plan(T, d, d, batch=batch, trans=1, ldc=kvp, c_bs=d * kvp, head_rows=kvp, int8=int8) == \
+                    want(I8_T if int8 else F16_T, 6, nNt, batch, blk)
+        # ... and all decoder layers in one launch (fp16): 32 x 5 = 160 n tiles / 4 x 2 = 8 n tiles -> 8 x 4
+        for d, L in ((1280, 32), (384, 4)):
+            nNt = -(-d // 256) * L
+            kw = dict(batch=batch, c_bs=d * kvp, head_rows=kvp, n_layers=L)
+            assert plan(T, d, d, **kw) == want(LAYERED, 6, nNt, batch, (8, 4), n_layers=L)
+            assert plan(T, d, d, trans=1, ldc=kvp, **kw) == want(LAYERED_T, 6, nNt, batch, (8, 4), n_layers=L)
+    # one m panel or one n tile: nothing to block
+    assert plan(256, 1280, 1280) == want(F16, 1, 5, 1, (0, 0))
+    assert plan(257, 1280, 1280) == want(F16, 2, 5, 1, (5, 6))
+    assert plan(256, 1280, 1280, batch=2) == want(F16, 1, 5, 2, (5, 6))
+    assert plan(1500, 256, 1280, batch=16) == want(F16, 6, 1, 16, (0, 0))
+    # a width with no divisor but 1 up to 16 (17 n tiles): blocks of 1 x 32
+    assert plan(1500, 17 * 256, 128) == want(F16, 6, 17, 1, (1, 32))
+    # the staged V^T epilogue: trans, fp16, plain layout, ldc and the chunk stride multiples of 8 halves
+    assert plan(300, 128, 128, trans=1, ldc=304)[7] == 1 and plan(300, 128, 128, trans=1, ldc=304, batch=2)[7] == 1
+    assert plan(300, 128, 128, trans=1, ldc=300)[7] == 0 and plan(300, 128, 128, trans=1, ldc=304, c_bs=128 * 304 + 4)[7] == 0
+    assert plan(300, 128, 128, ldc=304)[7] == 0 and plan(300, 128, 128, trans=1, ldc=304, int8=1)[7] == 0
+    assert plan(300, 128, 128, trans=1, ldc=320, c_bs=128 * 320, head_rows=320)[7] == 0
+    # the knobs' off settings (the references of the GPU bit-identity tests): no staging, n fastest across the width
+    try:
+        _lib.check(lib.fw_test_knob(5, 0))
+        assert plan(T, 1280, 1280, trans=1, ldc=t_pad, batch=16) == want(F16_T, 6, 5, 16, (5, 6), vt_stage=0)
+        _lib.check(lib.fw_test_knob(5, 1))
+        _lib.check(lib.fw_test_knob(1, 0))
+        assert plan(T, 1280, 1280, trans=1, ldc=t_pad, batch=16) == want(F16_T, 6, 5, 16, (0, 0), vt_stage=1)
+        assert plan(T, 1280, 1280, batch=16, c_bs=1280 * kvp, head_rows=kvp, n_layers=32) == \
+            want(LAYERED, 6, 160, 16, (0, 0), n_layers=32)
+    finally:
+        _lib.check(lib.fw_test_knob(5, 1))
+        _lib.check(lib.fw_test_knob(1, 1))
+    assert plan(T, 1280, 1280, trans=1, ldc=t_pad, batch=16) == want(F16_T, 6, 5, 16, (5, 6), vt_stage=1)
+    # ---- refusals (nothing is launched): K rows of whole 128-byte lines
+    assert plan(300, 128, 64) == want(F16, 2, 1, 1, (0, 0)) and plan(300, 128, 96) == REFUSED and plan(300, 128, 0) == REFUSED
+    assert plan(300, 128, 128, int8=1) == want(I8, 2, 1, 1, (0, 0)) and plan(300, 128, 64, int8=1) == REFUSED
+    # 16-byte aligned rows of A and W and chunks of A (8 halves, 16 codes)
+    assert plan(300, 128, 128, lda=136) != REFUSED and plan(300, 128, 128, lda=132) == REFUSED
+    assert plan(300, 128, 128, ldw=136) != REFUSED and plan(300, 128, 128, ldw=132) == REFUSED
+    assert plan(300, 128, 128, a_bs=300 * 128 + 8) != REFUSED and plan(300, 128, 128, a_bs=300 * 128 + 4) == REFUSED
+    assert plan(300, 128, 128, lda=144, int8=1) != REFUSED and plan(300, 128, 128, lda=136, int8=1) == REFUSED
+    # row-major output: N, ldc and the chunk stride multiples of 4; the transposed one takes any
+    assert plan(300, 260, 128) != REFUSED and plan(300, 258, 128, ldc=260) == REFUSED
+    assert plan(300, 260, 128, ldc=262) == REFUSED and plan(300, 260, 128, c_bs=300 * 260 + 2) == REFUSED
+    assert plan(300, 258, 128, trans=1, ldc=301, c_bs=258 * 301 + 1) == want(F16_T, 2, 2, 1, (2, 16))
+    # int8 codes need the weight scale; the layered launch is fp16 without a residual
+    assert plan(300, 128, 128, int8=2) == REFUSED and plan(300, 128, 128, trans=1, int8=2) == REFUSED
+    assert plan(300, 128, 128, n_layers=2, int8=1) == REFUSED and plan(300, 128, 128, n_layers=2, res=1) == REFUSED
+    # ---- the six instantiations
+    assert [plan(300, 128, 128, trans=t, int8=i)[0] for i in (0, 1) for t in (0, 1)] == [F16, F16_T, I8, I8_T]
+    assert [plan(300, 128, 128, trans=t, n_layers=2)[0] for t in (0, 1)] == [LAYERED, LAYERED_T]
+    assert plan(300, 128, 128, n_layers=1, res=1)[0] == F16
+
+
 def test_self_attention_form_is_stated_once():
     """The form the decode self-attention takes (csrc/dec_kernels.hip: self_attn_form, through the host-only hook
     fw_test_self_attn_form): 1 where the second form is unusable (slot-table stride not a multiple of 4, a layer's cache
