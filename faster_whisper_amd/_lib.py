@@ -84,7 +84,7 @@ SYMBOLS = [
     "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
     "fw_test_dec_beam_update", "fw_test_dec_embed", "fw_test_align_post",
     "fw_test_logits_rules_lp", "fw_test_dec_beam_update_lp",
-    "fw_test_logits_rules_smp_tab", "fw_test_graph_captures", "fw_test_blob_check",
+    "fw_test_logits_rules_smp_tab", "fw_test_logits_rules_ex", "fw_test_graph_captures", "fw_test_blob_check",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_vad_forward_audio_batch_dev",
     "fw_flac_info", "fw_flac_decode",
@@ -217,7 +217,9 @@ def load():
     if hasattr(lib, "fw_test_graph_captures"):       # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_logits_rules_smp_tab.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp, vp, vp, vp]
         lib.fw_test_graph_captures.argtypes = [vp, i64p]
-    if hasattr(lib, "fw_test_blob_check"):           # (absent from an older build loaded through FWAMD_LIB)
+    if hasattr(lib, "fw_test_logits_rules_ex"):      # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_test_logits_rules_ex.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]
     lib.fw_vad_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]

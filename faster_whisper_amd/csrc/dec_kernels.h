@@ -31,6 +31,15 @@ struct GenDev {
   int ragged, reach;
 };
 
+// GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
+// kernel forbids ids from ts_begin + mits + 1 on at the first step, in int arithmetic: a limit at or past the number of
+// timestamp ids forbids nothing, and so does a negative one — both become -1, "no limit", which also gives equivalent
+// values one step-graph key.  decoder.hip and the rules hook (hooks.hip) both fill mits through this.
+static inline int initial_timestamp_limit(long long max_initial_timestamp_index, int n_vocab, int ts_begin) {
+  const long long n_ts = (long long)n_vocab - ts_begin;
+  return (max_initial_timestamp_index < 0 || max_initial_timestamp_index >= n_ts) ? -1 : (int)max_initial_timestamp_index;
+}
+
 // Sampling runs: one entry per decode row.  The calls of a run keep their own temperature and seed, and a row draws its
 // noise as row `r - row0` of its call: what it is in a run of that call alone.
 struct SmpRow {

@@ -1650,20 +1650,24 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
   float sum_t = 0.f, sum_s = 0.f;
 #pragma unroll
   for (int i = 0; i < LP_WAVES; ++i) { sum_t += red_st[i]; sum_s += red_ss[i]; }   // fixed order: every thread agrees
-  const float lse_t = (max_t == NEG) ? NEG : max_t + logf(sum_t);
-  const float lse_s = (max_s == NEG) ? NEG : max_s + logf(sum_s);
-  float lse;
-  if (lse_t == NEG) lse = lse_s;
-  else if (lse_s == NEG) lse = lse_t;
-  else {
-    const float hi = fmaxf(lse_t, lse_s), lo = fminf(lse_t, lse_s);
-    lse = hi + log1pf(expf(lo - hi));
-  }
+  const float log_t = logf(sum_t), log_s = logf(sum_s);   // (an empty class: max -inf, sum 0, its log is never used)
+  const float lse_s = (max_s == NEG) ? NEG : max_s + log_s;
   // rule (e): if logsumexp(timestamps) > max(text) (in log-prob space the common lse cancels): text is masked
   const bool mask_text = __builtin_amdgcn_readfirstlane((gp.with_ts && lse_s > max_t) ? 1 : 0) != 0;   // uniform
-  if (mask_text) lse = lse_s;
-  // (-inf - finite = -inf: the masked ids need no test; lse is -inf only when every id is masked)
-  const float lse_sub = (lse == NEG) ? 0.f : lse;
+  // The log-sum-exp of what is left is subtracted in two parts, logp = (x - M) - L with M the maximum and L the log of
+  // the sum of exp(x - M): x - M is exact or nearly so and L is small, so logp carries the round-off of ITS OWN size.
+  // (x - (M + L) rounds M + L at the spacing of |M| first: 8e-6 at |M| = 128, whatever the size of logp.)
+  // (-inf - finite = -inf: the masked ids need no test; every id masked: nothing is subtracted, M = L = 0)
+  float lse_m = 0.f, lse_l = 0.f;
+  if (mask_text || max_t == NEG) {
+    if (max_s != NEG) { lse_m = max_s; lse_l = log_s; }
+  } else if (max_s == NEG) {
+    lse_m = max_t; lse_l = log_t;
+  } else {   // both classes alive: the class sums on the larger maximum
+    const bool t_hi = max_t >= max_s;
+    lse_m = t_hi ? max_t : max_s;
+    lse_l = logf((t_hi ? sum_t : sum_s) + (t_hi ? sum_s : sum_t) * expf((t_hi ? max_s : max_t) - lse_m));
+  }
   // ---- log-probs; this thread's best key ----
   const float cum = cum2[(size_t)cur * gp.R + r];
   constexpr bool smp = SMP;   // a separate instantiation: 2 x 56 inlined logf stay out of the beam / greedy kernel
@@ -1679,7 +1683,7 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
     const int v = tid + i * LP_THREADS;
     float x = val[i];
     if (mask_text) x = (v < tb) ? NEG : x;
-    x = x - lse_sub;
+    x = (x - lse_m) - lse_l;
     val[i] = x;
     float key = x;
     if (smp && x != NEG) key = x * sr.inv_temp + gumbel_noise(sr.seed_lo, sr.seed_hi, (unsigned)(r - sr.row0), (unsigned)step, (unsigned)v);

@@ -846,7 +846,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.with_ts = r0.with_ts;
   gp.suppress_blank = o->suppress_blank ? 1 : 0;
   gp.min_new = o->min_new_tokens;
-  gp.mits = o->max_initial_timestamp_index;
+  gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
   gp.ngram = o->no_repeat_ngram_size;
   gp.rep_pen = o->repetition_penalty;
   gp.lp_pow = o->length_penalty;

@@ -866,14 +866,22 @@ int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows
 // logits and row state, outside any decode run: tests/test_gpu_logits_rules.py compares the candidates with the
 // oracle's rule restatement id for id.  rows = R (row r belongs to chunk r / beam_size), n = tokens generated so far
 // (the same for every row), hist [R][n], cum [R]; out: cand_val / cand_tok [R][2 * beam_size] (sampling: [R][1]).
-// (This hook and the three after it launch on the null stream, without the model's lock, and end with a device-wide wait.)
+// (This hook and the four after it launch on the null stream, without the model's lock, and end with a device-wide wait.)
 // ---------------------------------------------------------------------------------------------------
 // (cand_lp null: the kernel gets a null pointer and skips the log-prob stores, fw_test_logits_rules as it always was)
 // smp: the sampling table of the launch, one entry per row (fw_test_logits_rules_smp_tab); null: every row is a row of ONE
 // call with the temperature and seed of `o` (row0 = 0), what a decode run of that call alone fills in
+// ex (fw_test_logits_rules_ex): the state exposed.  done [R / K] | null (all live); the logits rows are downloaded whole
+// into logits_io after the launch; cand_val / cand_tok / cand_lp are [R][32], the kernel's own stride, IN / OUT: the device
+// buffers start as the caller's values and come back whole.  Without it the outputs start as zeros and the first C columns
+// of every row are returned.
+// Every history id is checked in [0, V) before anything is allocated or launched: the repetition penalty and the n-gram
+// rule use them as indices into the row (a wrong test gets FW_EINVAL, never a device fault).
+struct RulesEx { const int32_t* done; float* logits_io; };
 static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                                  const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
-                                 int32_t* cand_tok, float* cand_lp, const fwd::SmpRow* smp = nullptr) {
+                                 int32_t* cand_tok, float* cand_lp, const fwd::SmpRow* smp = nullptr,
+                                 const RulesEx* ex = nullptr) {
   FW_CHECK_ARG(fm && logits && cum && o && cand_val && cand_tok && R >= 1 && n >= 0, "bad arguments");
   Model* m = &fm->impl;
   const fw_config& c = m->cfg;
@@ -881,6 +889,11 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   const bool sampling = K == 1 && o->sampling_topk != 1;
   FW_CHECK_ARG(K >= 1 && K <= 16 && R % K == 0 && n < c.n_text_ctx && (n == 0 || hist), "bad geometry");
   FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64, "vocabulary too large for the rules kernel");
+  for (size_t i = 0; i < (size_t)R * n; ++i)
+    FW_CHECK_ARG(hist[i] >= 0 && hist[i] < c.n_vocab, "hist[%d][%d] = %d outside [0, %d)", (int)(i / n), (int)(i % n),
+                 hist[i], c.n_vocab);
+  if (ex && ex->done)
+    for (int b = 0; b < R / K; ++b) FW_CHECK_ARG(ex->done[b] == 0 || ex->done[b] == 1, "done[%d] = %d is not 0 / 1", b, ex->done[b]);
   FW_HIP(hipSetDevice(m->device));
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
@@ -890,7 +903,7 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   gp.with_ts = with_timestamps ? 1 : 0;
   gp.suppress_blank = o->suppress_blank ? 1 : 0;
   gp.min_new = o->min_new_tokens;
-  gp.mits = o->max_initial_timestamp_index;
+  gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
   gp.ngram = o->no_repeat_ngram_size;
   gp.rep_pen = o->repetition_penalty;
   gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
@@ -909,21 +922,27 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
     for (int i = 0; i < n; ++i) h2[((size_t)cur * R + r) * NT + i] = hist[(size_t)r * n + i];
     c2[(size_t)cur * R + r] = cum[r];
   }
-  std::vector<float> hv((size_t)R * 32);
-  std::vector<int> ht((size_t)R * 32);
+  std::vector<int> dn((size_t)R, 0);   // (the kernel reads done[r / K]; R entries as the hook always allocated)
+  if (ex && ex->done) std::copy(ex->done, ex->done + R / K, dn.begin());
+  const size_t NC = (size_t)R * 32;
+  std::vector<float> hv(NC, 0.f), hl(cand_lp ? NC : 0, 0.f);
+  std::vector<int> ht(NC, 0);
+  if (ex) {
+    std::copy(cand_val, cand_val + NC, hv.begin());
+    std::copy(cand_tok, cand_tok + NC, ht.begin());
+    if (cand_lp) std::copy(cand_lp, cand_lp + NC, hl.begin());
+  }
   HookBufs db;
-  std::vector<float> hl(cand_lp ? hv.size() : 0);
   float *d_lg, *d_cum, *d_cv, *d_cl = nullptr;
   int *d_hist, *d_step, *d_done, *d_ct;
   unsigned long long* d_bits;
   int rc;
   if ((rc = db.upload(&d_lg, logits, (size_t)R * c.n_vocab)) || (rc = db.upload(&d_cum, c2.data(), c2.size())) ||
       (rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n, 1)) ||
-      (rc = db.upload(&d_bits, mask.data(), mask.size())) || (rc = db.alloc(&d_done, (size_t)R)) ||
-      (rc = db.alloc(&d_cv, hv.size())) || (rc = db.alloc(&d_ct, ht.size())) || (rc = db.zero(d_done, (size_t)R * sizeof(int), nullptr)) ||
-      (rc = db.zero(d_cv, hv.size() * sizeof(float), nullptr)) || (rc = db.zero(d_ct, ht.size() * sizeof(int), nullptr)))
+      (rc = db.upload(&d_bits, mask.data(), mask.size())) || (rc = db.upload(&d_done, dn.data(), dn.size())) ||
+      (rc = db.upload(&d_cv, hv.data(), NC)) || (rc = db.upload(&d_ct, ht.data(), NC)))
     return rc;
-  if (cand_lp && ((rc = db.alloc(&d_cl, hl.size())) || (rc = db.zero(d_cl, hl.size() * sizeof(float), nullptr)))) return rc;
+  if (cand_lp && (rc = db.upload(&d_cl, hl.data(), NC))) return rc;
   fwd::SmpRow* d_smp = nullptr;
   if (sampling) {
     std::vector<fwd::SmpRow> tab((size_t)R);
@@ -935,9 +954,10 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
-  if ((rc = download(hv.data(), d_cv, hv.size())) || (rc = download(ht.data(), d_ct, ht.size()))) return rc;
-  if (cand_lp && (rc = download(hl.data(), d_cl, hl.size()))) return rc;
-  const int C = sampling ? 1 : 2 * K;
+  if ((rc = download(hv.data(), d_cv, NC)) || (rc = download(ht.data(), d_ct, NC))) return rc;
+  if (cand_lp && (rc = download(hl.data(), d_cl, NC))) return rc;
+  if (ex && ex->logits_io && (rc = download(ex->logits_io, d_lg, (size_t)R * c.n_vocab))) return rc;
+  const int C = ex ? 32 : sampling ? 1 : 2 * K;
   for (int r = 0; r < R; ++r)
     for (int j = 0; j < C; ++j) {
       cand_val[(size_t)r * C + j] = hv[(size_t)r * 32 + j];
@@ -960,6 +980,17 @@ int32_t fw_test_logits_rules_lp(fw_model* fm, const float* logits, int32_t R, co
   return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp);
 }
 
+// the sampling table of a launch from the per-row arrays of the C ABI (row0[r] in [0, r], inv_temp[r] > 0: checked)
+static int32_t smp_table(int32_t R, const float* inv_temp, const uint64_t* seed, const int32_t* row0,
+                         std::vector<fwd::SmpRow>& tab) {
+  tab.resize((size_t)R);
+  for (int r = 0; r < R; ++r) {
+    FW_CHECK_ARG(row0[r] >= 0 && row0[r] <= r && inv_temp[r] > 0.f, "row %d: row0 must lie in [0, row], inv_temp must be positive", r);
+    tab[r] = {inv_temp[r], (unsigned)(seed[r] & 0xffffffffu), (unsigned)(seed[r] >> 32), row0[r]};
+  }
+  return FW_OK;
+}
+
 // The sampling instantiation over R rows that belong to DIFFERENT calls, as in a merged sampling run: row r draws with
 // 1 / inv_temp[r] as its temperature and seed[r], as row r - row0[r] of its call (0 <= row0[r] <= r: checked).  `o` gives the
 // rules and must select sampling (beam_size 1, sampling_topk 0); its own temperature and seed are not read.
@@ -969,12 +1000,28 @@ int32_t fw_test_logits_rules_smp_tab(fw_model* fm, const float* logits, int32_t 
                                      int32_t* cand_tok, float* cand_lp) {
   FW_CHECK_ARG(o && inv_temp && seed && row0 && cand_lp && R >= 1, "null argument");
   FW_CHECK_ARG(o->beam_size == 1 && o->sampling_topk == 0, "the options must select sampling (beam_size 1, sampling_topk 0)");
-  std::vector<fwd::SmpRow> tab((size_t)R);
-  for (int r = 0; r < R; ++r) {
-    FW_CHECK_ARG(row0[r] >= 0 && row0[r] <= r && inv_temp[r] > 0.f, "row %d: row0 must lie in [0, row], inv_temp must be positive", r);
-    tab[r] = {inv_temp[r], (unsigned)(seed[r] & 0xffffffffu), (unsigned)(seed[r] >> 32), row0[r]};
-  }
+  std::vector<fwd::SmpRow> tab;
+  if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
   return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp, tab.data());
+}
+
+// fw_test_logits_rules_lp with the state exposed (include/fwamd_test.h): logits IN / OUT, done per chunk, candidate arrays
+// [R][32] IN / OUT, the sampling table of fw_test_logits_rules_smp_tab or none.
+int32_t fw_test_logits_rules_ex(fw_model* fm, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                const fw_gen_opts* o, int32_t with_timestamps, const int32_t* done, const float* inv_temp,
+                                const uint64_t* seed, const int32_t* row0, float* cand_val, int32_t* cand_tok,
+                                float* cand_lp) {
+  FW_CHECK_ARG(o && cand_lp && R >= 1, "null argument");
+  const bool tab_given = inv_temp || seed || row0;
+  FW_CHECK_ARG(!tab_given || (inv_temp && seed && row0), "the sampling table needs inv_temp, seed and row0 together");
+  std::vector<fwd::SmpRow> tab;
+  if (tab_given) {
+    FW_CHECK_ARG(o->beam_size == 1 && o->sampling_topk == 0, "the options must select sampling (beam_size 1, sampling_topk 0)");
+    if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
+  }
+  const RulesEx ex{done, logits};
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp,
+                           tab_given ? tab.data() : nullptr, &ex);
 }
 
 // step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together

@@ -52,6 +52,20 @@ int32_t fw_test_logits_rules_smp_tab(fw_model* m, const float* logits, int32_t R
                                      const float* cum, const fw_gen_opts* opts, int32_t with_timestamps,
                                      const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
                                      int32_t* cand_tok, float* cand_lp);
+/* fw_test_logits_rules_lp with the state of the launch exposed (tests/test_gpu_logits_rules.py):
+ *   in/out  logits [R][n_vocab]: uploaded, and downloaded WHOLE after the launch (the sparse rules edit the row in place)
+ *   in      done [R / beam_size] (0 / 1: the rows of a finished chunk are skipped) | NULL: every chunk is live
+ *   in      inv_temp / seed / row0 [R]: the sampling table of fw_test_logits_rules_smp_tab (opts must then select
+ *           sampling) | all three NULL: sampling rows draw with opts' own temperature and seed
+ *   in/out  cand_val / cand_tok / cand_lp [R][32], the kernel's own stride: the device buffers start as the caller's
+ *           values and are returned whole, so slots the launch did not write keep what the caller put there
+ * Checked before anything is allocated or launched (FW_EINVAL, outputs untouched): R % beam_size == 0, every hist id in
+ * [0, n_vocab) — the repetition penalty and the n-gram rule index the row with them; the three older hooks check this
+ * too —, every done entry 0 or 1. */
+int32_t fw_test_logits_rules_ex(fw_model* m, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
+                                const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
+                                int32_t* cand_tok, float* cand_lp);
 /* out[0] = step graphs (one hipGraph per distinct decode-step geometry, decoder.hip) the model's decode group has
  * captured and instantiated since the model was created, summed over its lanes */
 int32_t fw_test_graph_captures(const fw_model* m, int64_t* out);

@@ -129,6 +129,29 @@ def test_generate_beam(setup, beam, timestamps):
         assert abs(g.no_speech_prob - r.no_speech_prob) < 1e-3
 
 
+def test_generate_unbounded_initial_timestamp_index(setup):
+    """max_initial_timestamp_index has no upper limit (CTranslate2 takes a size_t; the oracle masks nothing for a value
+    past the last timestamp id): the largest int32 must give what -1, "no limit", gives, token for token — the rules
+    kernel adds it to ts_begin in int arithmetic, so the engine bounds it first (dec_kernels.h:
+    initial_timestamp_limit).  Beam 5, timestamps on: the first step is the one the value governs."""
+    from faster_whisper_amd.backend import StorageView
+    cfg, model, oracle, feats = setup
+    enc = model.encode(StorageView.from_array(feats))
+    prompt = _prompt(cfg, True)
+    kw = dict(beam_size=5, patience=1.0, length_penalty=1.0, max_length=len(prompt) + 12, suppress_tokens=_suppress(cfg),
+              return_scores=True)
+    free = model.generate(enc, [prompt] * 3, max_initial_timestamp_index=-1, **kw)
+    for mits in (2 ** 31 - 1, 100000, 1501):
+        got = model.generate(enc, [prompt] * 3, max_initial_timestamp_index=mits, **kw)
+        for g, f in zip(got, free):
+            assert len(f.sequences_ids[0]) >= 1 and f.sequences_ids[0][0] >= cfg.timestamp_begin
+            assert g.sequences_ids == f.sequences_ids, (mits, g.sequences_ids, f.sequences_ids)
+            assert abs(g.scores[0] - f.scores[0]) <= 1e-6 * max(1.0, abs(f.scores[0])), (mits, g.scores, f.scores)
+    # ... and the limit still binds where it is one: index 0 leaves the first timestamp id alone
+    for g in model.generate(enc, [prompt] * 3, max_initial_timestamp_index=0, **kw):
+        assert g.sequences_ids[0][0] == cfg.timestamp_begin
+
+
 def test_generate_eot_and_early_finish(setup):
     """make <eot> very likely after a few tokens via min_new_tokens=0 and a tiny budget: exercises
     finished-hypothesis bookkeeping and the max-length finalisation"""
