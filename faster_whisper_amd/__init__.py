@@ -1,15 +1,15 @@
 """faster_whisper_amd — MI355X-native (gfx950, HIP) Whisper transcription engine that keeps
 faster-whisper's `WhisperModel` / `BatchedInferencePipeline.transcribe()` surface and replaces
 the `ctranslate2.models.Whisper` backend (see DESIGN.md / INTEGRATION.md)."""
-from .backend import (StorageView, Whisper, WhisperAlignmentResult, WhisperGenerationResult, pack_blob,
-                      save_model_dir)
+from .backend import (StorageView, Whisper, WhisperAlignmentResult, WhisperGenerationResult, WhisperScoringResult,
+                      pack_blob, save_model_dir)
 from .config import WhisperConfig, get_config
 from .weights import synthetic_weights
 
 __version__ = "0.1.0"
 
 __all__ = [
-    "Whisper", "StorageView", "WhisperGenerationResult", "WhisperAlignmentResult", "WhisperConfig",
+    "Whisper", "StorageView", "WhisperGenerationResult", "WhisperAlignmentResult", "WhisperScoringResult", "WhisperConfig",
     "get_config", "synthetic_weights", "pack_blob", "save_model_dir",
 ]
 

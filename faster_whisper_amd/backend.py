@@ -111,6 +111,36 @@ class WhisperAlignmentResult:
         self.text_token_probs = text_token_probs
 
 
+class WhisperScoringResult:
+    """Whisper.score for one chunk.  Per candidate sequence h: token_logprobs[h][i] = log-prob of the given token i,
+    end_logprobs[h] = that of the <eot> that would close the sequence, best_ids[h] / best_logprobs[h] = the arg-max of
+    the same distribution at every position, the <eot> position last (len(sequence) + 1 entries)."""
+
+    def __init__(self, sequences_ids, token_logprobs, end_logprobs, best_ids, best_logprobs):
+        self.sequences_ids = sequences_ids
+        self.token_logprobs = token_logprobs
+        self.end_logprobs = end_logprobs
+        self.best_ids = best_ids
+        self.best_logprobs = best_logprobs
+
+    def cum_logprob(self, h: int = 0) -> float:
+        """the tokens' values, then the <eot>'s, added in order in float32: generate's cumulative log-prob"""
+        acc = np.float32(0.0)
+        for v in self.token_logprobs[h] + [self.end_logprobs[h]]:
+            acc = np.float32(acc + np.float32(v))
+        return float(acc)
+
+    def score(self, h: int = 0, length_penalty: float = 1) -> float:
+        """generate's normalised score of candidate h: cum_logprob / len ** length_penalty (float32, as the engine)"""
+        n = max(1, len(self.sequences_ids[h]))
+        denom = np.float32(n) ** np.float32(length_penalty) if length_penalty != 0 else np.float32(1.0)
+        return float(np.float32(self.cum_logprob(h)) / np.float32(denom))
+
+    def __repr__(self):
+        return (f"WhisperScoringResult(sequences_ids={self.sequences_ids}, token_logprobs={self.token_logprobs}, "
+                f"end_logprobs={self.end_logprobs})")
+
+
 class _Replica:
     """one fw_model on one GPU"""
 
@@ -275,6 +305,7 @@ class Whisper:
             cfg, weights = load_model_dir(model_path)
         self._cfg = cfg
         self._max_batch = int(max_batch_size)
+        self._max_beam = int(max_beam_size)
         idx = [device_index] if isinstance(device_index, int) else list(device_index)
         self._device_index = idx
         self._lib = _lib.load()
@@ -608,6 +639,76 @@ class Whisper:
             return [WhisperAlignmentResult([(int(a), int(t)) for a, t in pairs[b, :npairs[b]]],
                                            probs[offs[b]:offs[b + 1]].tolist()) for b in range(B)]
         return self._over_parts(enc, one_call, text_tokens, num_frames)
+
+    # ---- score --------------------------------------------------------------------------
+    _RULE_DEFAULTS = dict(repetition_penalty=1, no_repeat_ngram_size=0, suppress_blank=True, suppress_tokens=(-1,),
+                          max_initial_timestamp_index=50)
+
+    def score(self, features: StorageView, prompts: List[List[int]], targets, *, rules: bool = False,
+              **rule_kwargs) -> List[WhisperScoringResult]:
+        """Teacher-forced log-probs of given transcripts (fwamd.h: fw_score; not in CTranslate2's Whisper class).
+        targets[b]: one sequence of ids, or a list of up to max_beam_size sequences, scored against chunk b.
+        rules=False: the raw distribution.  rules=True: the distribution generate()'s search ranks by, with generate's
+        rule keywords and their defaults (repetition_penalty, no_repeat_ngram_size, suppress_blank, suppress_tokens,
+        max_initial_timestamp_index); the timestamp rules follow the prompt.  result.score(h, length_penalty=1) is then
+        what generate(return_scores=True) reports for the same ids."""
+        unknown = set(rule_kwargs) - set(self._RULE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
+        if rule_kwargs and not rules:
+            raise ValueError(f"{sorted(rule_kwargs)} need rules=True: without it the raw distribution is scored")
+        if not hasattr(self._lib, "fw_score"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_score: scoring needs a current build")
+        enc = self._as_encoded(features)
+        if len(prompts) != enc._shape[0] or len(targets) != enc._shape[0]:
+            raise ValueError(f"got {len(prompts)} prompts and {len(targets)} targets for a batch of {enc._shape[0]}")
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError("prompts must not be empty")
+
+        def candidates(t):   # one sequence of ids -> [sequence]
+            t = list(t)
+            return [list(s) for s in t] if t and isinstance(t[0], (list, tuple, np.ndarray)) else [t]
+        cands = [candidates(t) for t in targets]
+        H = max(len(c) for c in cands)
+        if H < 1 or H > self._max_beam:
+            raise ValueError(f"{H} candidate sequences for one chunk: score() takes 1 .. max_beam_size={self._max_beam}")
+        o = None
+        if rules:
+            kw = dict(self._RULE_DEFAULTS, **rule_kwargs)
+            o = _lib.FwGenOpts()
+            o.repetition_penalty, o.no_repeat_ngram_size = float(kw["repetition_penalty"]), int(kw["no_repeat_ngram_size"])
+            o.max_initial_timestamp_index, o.suppress_blank = int(kw["max_initial_timestamp_index"]), int(kw["suppress_blank"])
+            sup = np.asarray([t for t in (kw["suppress_tokens"] or []) if t >= 0], dtype=np.int32)
+            o.suppress_tokens = _lib.as_i32p(sup) if sup.size else None
+            o.n_suppress_tokens = int(sup.size)
+
+        def one_call(enc, prompts, cands):
+            B = enc._shape[0]
+            # every chunk gets H rows: a chunk with fewer candidates is filled up with empty sequences, dropped below
+            seqs = [c[h] if h < len(c) else [] for c in cands for h in range(H)]
+            pflat, poffs = _ragged([np.asarray(p, dtype=np.int32) for p in prompts], np.int32, np.int32)
+            tflat, toffs = _ragged([np.asarray(s, dtype=np.int32) for s in seqs], np.int32, np.int32)
+            n_out = int(toffs[-1]) + B * H
+            lp = np.zeros((n_out,), dtype=np.float32)
+            bid = np.zeros((n_out,), dtype=np.int32)
+            blp = np.zeros((n_out,), dtype=np.float32)
+            _lib.check(self._lib.fw_score(enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs),
+                                          _lib.as_i32p(tflat), _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None,
+                                          _lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp)))
+            out = []
+            for b in range(B):
+                res = WhisperScoringResult([], [], [], [], [])
+                for h in range(len(cands[b])):
+                    i = b * H + h
+                    n, e0 = len(seqs[i]), int(toffs[i]) + i
+                    res.sequences_ids.append([int(t) for t in seqs[i]])
+                    res.token_logprobs.append(lp[e0:e0 + n].tolist())
+                    res.end_logprobs.append(float(lp[e0 + n]))
+                    res.best_ids.append(bid[e0:e0 + n + 1].tolist())
+                    res.best_logprobs.append(blp[e0:e0 + n + 1].tolist())
+                out.append(res)
+            return out
+        return self._over_parts(enc, one_call, prompts, cands)
 
     # ---- measurement --------------------------------------------------------------------
     def _primary_of(self, replica: int) -> int:

@@ -140,5 +140,21 @@ void launch_token_prob(hipStream_t st, const float* logits, int V, const int* ta
                        int out_off, int rows, int row_mul = 1);
 void launch_cross_probs(hipStream_t st, const half_t* qx, int d, const half_t* ck, int T, int kvp, const int* heads,
                         int n_layer_heads, int n_sel, float* probs, int n_tok, int tok_idx, int B, int blk_n = 0);
+// Scoring (fw_score): what one logits row is scored against.  target < 0: the row has no target, nothing is written.
+struct ScoreRow {
+  int target;              // the id whose log-prob is wanted
+  int n;                   // tokens in front of it: the row's history is hist_pool[hist_off .. hist_off + n)
+  int hist_off;
+  int out;                 // index into out_lp / out_best_id / out_best_lp
+};
+static_assert(sizeof(ScoreRow) == 16, "one 16-byte load per row");
+// dec_score_kernel over `rows` logits rows in ONE launch: row r is position pos0 + r % nb of sequence r / nb and reads
+// tab[(r / nb) * tab_stride + pos0 + r % nb].  rules: the decoding rules of gp (with_ts, suppress_blank, mits, ngram,
+// rep_pen, the token ids) and sup_bits first, on a greedy row whose history is the ScoreRow's; otherwise the raw
+// distribution (sup_bits and hist_pool are not read).  The logits are not written.  Every id (targets, histories) must lie
+// in [0, gp.V) and every n below LP_THREADS: the caller checks.  out_best_id / out_best_lp: both or neither.
+void launch_score(hipStream_t st, const GenDev& gp, bool rules, const float* logits, const unsigned long long* sup_bits,
+                  const ScoreRow* tab, int tab_stride, int pos0, int nb, int rows, const int* hist_pool, float* out_lp,
+                  int* out_best_id, float* out_best_lp);
 
 }  // namespace fwd

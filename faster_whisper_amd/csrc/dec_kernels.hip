@@ -1741,6 +1741,219 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
 }
 
 // ------------------------------------------------------------------------------------
+// Scoring (fw_score): the log-prob of a GIVEN token per logits row, with the row's arg-max beside it, one workgroup per
+// row, every row of a position block in one launch.  Row r of the launch is position pos0 + r % nb of sequence r / nb and
+// reads its ScoreRow (target id, history, output index) from tab[(r / nb) * tab_stride + pos0 + r % nb]; a row without
+// a target (target < 0) writes nothing.
+// The row is held and reduced exactly as dec_logits_process_kernel does it — the same loads, the same class maxima and
+// class sums in the same order, the same two-part subtraction — so that a row scored here gets the bits that kernel
+// gives the same row of a greedy decode step.  What differs:
+//   * RULES: the decoding rules of a greedy row whose history is hist[0 .. n) (n = the row's own position among its
+//     targets: no d_step, no parity half, no min_new_tokens).  !RULES: the raw distribution, every id one class.
+//   * the logits are READ ONLY.  The two sparse rules (repetition penalty, no-repeat n-gram) mark their ids in two LDS
+//     bit maps laid out like the suppress mask (one 64-bit word per 64 consecutive ids a wave holds in val[i]): the
+//     n-gram bits join the suppress word, the penalty is applied to the register copy of the words that have a bit set.
+//   * one arg-max round instead of top-C, and the target's value picked out of its owner's registers.
+// ------------------------------------------------------------------------------------
+template <bool RULES>
+__global__ __launch_bounds__(LP_THREADS) void dec_score_kernel(fwd::GenDev gp, const float* __restrict__ logits,
+                                                               const unsigned long long* __restrict__ sup_bits,
+                                                               const fwd::ScoreRow* __restrict__ tab, int tab_stride,
+                                                               int pos0, int nb, const int* __restrict__ hist_pool,
+                                                               float* __restrict__ out_lp, int* __restrict__ out_best_id,
+                                                               float* __restrict__ out_best_lp) {
+  __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
+  __shared__ float bkey_s[LP_WAVES];
+  __shared__ int btok_s[LP_WAVES];
+  __shared__ int sh_last_ts;
+  __shared__ unsigned pen_bits[2 * LP_SUP_WORDS], ng_bits[2 * LP_SUP_WORDS];
+  const int r = blockIdx.x;
+  const int sq = r / nb;
+  const fwd::ScoreRow row = tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
+  if (row.target < 0) return;   // (uniform)
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = row.n;
+  const int* hist = hist_pool + row.hist_off;
+  const float* lg = logits + (size_t)r * gp.V;
+  const int V = gp.V, tb = gp.ts_begin;
+  const float NEG = -INFINITY;
+  const int NONE = 0x7fffffff;
+  // ---- sparse rules: the ids they touch, one bit each ----
+  const bool pen_on = RULES && gp.rep_pen != 1.0f && n > 0;
+  const bool ng_on = RULES && gp.ngram > 0 && n + 1 >= gp.ngram;
+  if (pen_on || ng_on) {
+    for (int i = tid; i < 2 * LP_SUP_WORDS; i += LP_THREADS) { pen_bits[i] = 0u; ng_bits[i] = 0u; }
+    __syncthreads();
+    if (pen_on)
+      for (int i = tid; i < n; i += LP_THREADS) {
+        const int t = hist[i];
+        atomicOr(&pen_bits[t >> 5], 1u << (t & 31));   // (a bit: an id is penalised once however often it occurs)
+      }
+    if (ng_on) {
+      const int k = gp.ngram;
+      for (int s = tid; s + k <= n; s += LP_THREADS) {
+        bool match = true;
+        for (int q = 0; q < k - 1; ++q)
+          if (hist[s + q] != hist[n - (k - 1) + q]) { match = false; break; }
+        if (match) {
+          const int t = hist[s + k - 1];
+          atomicOr(&ng_bits[t >> 5], 1u << (t & 31));
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // ---- the row: every load in flight at once (unconditional, clamped: see dec_logits_process_kernel) ----
+  float val[LP_NV];
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) {
+    const int v = tid + i * LP_THREADS;
+    const float x = lg[v < V ? v : V - 1];
+    val[i] = (v < V) ? x : NEG;
+  }
+  // ---- timestamp-rule scalars (uniform), as in dec_logits_process_kernel ----
+  int a_hi = 0;        // ids in [0, a_hi) are forbidden
+  int b_hi = tb;       // timestamps in [tb, b_hi) are forbidden
+  int c_lo = NONE;     // ids >= c_lo are forbidden
+  const bool with_ts = RULES && gp.with_ts;
+  if (with_ts) {
+    if (tid == 0) sh_last_ts = -1;
+    __syncthreads();
+    if (tid < n && hist[tid] >= tb) atomicMax(&sh_last_ts, tid);   // n <= n_text_ctx <= LP_THREADS
+    __syncthreads();
+    const int lp = sh_last_ts;
+    const bool last_ts = n >= 1 && lp == n - 1;
+    const bool penult_ts = n < 2 || hist[n - 2] >= tb;
+    if (lp >= 0) {
+      const int last_seen = hist[lp];
+      b_hi = (last_ts && !penult_ts) ? last_seen : last_seen + 1;
+    }
+    if (last_ts) {
+      if (penult_ts) b_hi = NONE;   // a closed pair: no timestamp at all
+      else a_hi = gp.eot;           // an open one: text is forbidden, the pair has to close
+    }
+    if (n == 0) {
+      a_hi = tb;                    // the first token is a timestamp
+      if (gp.mits >= 0) c_lo = tb + gp.mits + 1;
+    }
+  }
+  // ---- element-wise masks (one 64-bit lane mask per i, built by lane i), class maxima ----
+  auto below = [](int nbits) -> unsigned long long {
+    return nbits <= 0 ? 0ull : (nbits >= 64 ? ~0ull : ((1ull << nbits) - 1ull));
+  };
+  auto span = [&](int lo, int hi, int v0) -> unsigned long long { return below(hi - v0) & ~below(lo - v0); };
+  unsigned km_lo = 0u, km_hi = 0u, pm_lo = 0u, pm_hi = 0u;
+  if (RULES) {
+    const int li = lane < LP_NV ? lane : LP_NV - 1;
+    const int w = li * LP_WAVES + wv;
+    const int v0 = w * 64;
+    const int kill_b = with_ts ? gp.no_ts : -1;
+    unsigned long long km = sup_bits[w];
+    km |= below(a_hi - v0) | span(tb, b_hi, v0) | ~below(c_lo - v0) | span(kill_b, kill_b + 1, v0);
+    if (n == 0 && gp.suppress_blank) {   // first position only
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < gp.n_sup_begin) km |= span(gp.sup_begin[q], gp.sup_begin[q] + 1, v0);
+    }
+    if (ng_on) km |= ((unsigned long long)ng_bits[2 * w + 1] << 32) | (unsigned long long)ng_bits[2 * w];
+    km_lo = (unsigned)km; km_hi = (unsigned)(km >> 32);
+    if (pen_on) { pm_lo = pen_bits[2 * w]; pm_hi = pen_bits[2 * w + 1]; }
+  }
+  float mt = NEG, ms = NEG;
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) {
+    float x = val[i];
+    if (RULES) {
+      if (pen_on) {
+        const unsigned long long pm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)pm_hi, i) << 32) |
+                                      (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)pm_lo, i);
+        if (pm != 0ull) {   // (a scalar: nearly every word is empty)
+          const float pv = x < 0.f ? x * gp.rep_pen : x / gp.rep_pen;
+          x = __builtin_amdgcn_inverse_ballot_w64(pm) ? pv : x;
+        }
+      }
+      const unsigned long long km = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_hi, i) << 32) |
+                                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_lo, i);
+      x = __builtin_amdgcn_inverse_ballot_w64(km) ? NEG : x;
+      val[i] = x;
+    }
+    const bool text = !RULES || tid + i * LP_THREADS < tb;
+    mt = fmaxf(mt, text ? x : NEG);
+    ms = fmaxf(ms, text ? NEG : x);
+  }
+  mt = wave_max_v(mt);
+  ms = wave_max_v(ms);
+  if (lane == 0) { red_mt[wv] = mt; red_ms[wv] = ms; }
+  __syncthreads();
+  float max_t = red_mt[0], max_s = red_ms[0];
+#pragma unroll
+  for (int i = 1; i < LP_WAVES; ++i) { max_t = fmaxf(max_t, red_mt[i]); max_s = fmaxf(max_s, red_ms[i]); }
+  // ---- class sums of exp(x - class max) ----
+  const float off_t = (max_t == NEG) ? 0.f : max_t, off_s = (max_s == NEG) ? 0.f : max_s;
+  float st = 0.f, ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) {
+    const bool text = !RULES || tid + i * LP_THREADS < tb;
+    const float e = __expf(val[i] - (text ? off_t : off_s));
+    st += text ? e : 0.f;
+    ss += text ? 0.f : e;
+  }
+  st = wave_sum_v(st);
+  ss = wave_sum_v(ss);
+  if (lane == 0) { red_st[wv] = st; red_ss[wv] = ss; }
+  __syncthreads();
+  float sum_t = 0.f, sum_s = 0.f;
+#pragma unroll
+  for (int i = 0; i < LP_WAVES; ++i) { sum_t += red_st[i]; sum_s += red_ss[i]; }
+  const float log_t = logf(sum_t), log_s = logf(sum_s);
+  const float lse_s = (max_s == NEG) ? NEG : max_s + log_s;
+  const bool mask_text = __builtin_amdgcn_readfirstlane((with_ts && lse_s > max_t) ? 1 : 0) != 0;   // rule (e)
+  // logp = (x - M) - L, the two-part subtraction dec_logits_process_kernel explains
+  float lse_m = 0.f, lse_l = 0.f;
+  if (mask_text || max_t == NEG) {
+    if (max_s != NEG) { lse_m = max_s; lse_l = log_s; }
+  } else if (max_s == NEG) {
+    lse_m = max_t; lse_l = log_t;
+  } else {
+    const bool t_hi = max_t >= max_s;
+    lse_m = t_hi ? max_t : max_s;
+    lse_l = logf((t_hi ? sum_t : sum_s) + (t_hi ? sum_s : sum_t) * expf((t_hi ? max_s : max_t) - lse_m));
+  }
+  // ---- log-probs; this thread's best; the target's value ----
+  const int tq = ((row.target & (LP_THREADS - 1)) == tid) ? row.target / LP_THREADS : -1;
+  float bkey = NEG, tval = NEG;
+  int bq = -1;
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) {
+    const int v = tid + i * LP_THREADS;
+    float x = val[i];
+    if (mask_text) x = (v < tb) ? NEG : x;
+    x = (x - lse_m) - lse_l;
+    if (i == tq) tval = x;
+    if (x > bkey) { bkey = x; bq = i; }   // ascending index: ties keep the lowest
+  }
+  if (tq >= 0) out_lp[row.out] = tval;
+  if (!out_best_id) return;   // (kernel arguments: uniform; both or none)
+  float k = bkey;
+  int t = (bq < 0) ? NONE : tid + bq * LP_THREADS;
+  wave_argmax_v(k, t);
+  if (lane == 0) { bkey_s[wv] = k; btok_s[wv] = t; }
+  __syncthreads();
+  float wk = bkey_s[lane & (LP_WAVES - 1)];
+  int wt = btok_s[lane & (LP_WAVES - 1)];
+  argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR1>(wk), dpp_i<FW_DPP_XOR1>(wt));
+  argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR2>(wk), dpp_i<FW_DPP_XOR2>(wt));
+  argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR4>(wk), dpp_i<FW_DPP_ROR4>(wt));
+  argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR8>(wk), dpp_i<FW_DPP_ROR8>(wt));
+  if (tid == 0) {
+    out_best_id[row.out] = (wt == NONE) ? 0 : wt;   // (nothing left on the row: id 0 at -inf, as the rules kernel records it)
+    out_best_lp[row.out] = (wt == NONE) ? NEG : wk;
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // K19/K20: per-chunk beam update [CT2-ext: BeamSearch::search].  Merges the K rows' top-2K
 // candidates (stable: value desc, flat index asc), walks the first K slots (EOS / last step ->
 // finished hypothesis, replaced by the next non-EOS secondary candidate), then rewrites
@@ -2356,6 +2569,14 @@ void launch_step_advance(hipStream_t st, int* d_step) { dec_step_advance_kernel<
 void launch_token_prob(hipStream_t st, const float* logits, int V, const int* target, float* out, int out_stride,
                        int out_off, int rows, int row_mul) {
   dec_token_prob_kernel<<<rows, 1024, 0, st>>>(logits, V, target, out, out_stride, out_off, row_mul);
+}
+
+void launch_score(hipStream_t st, const GenDev& gp, bool rules, const float* logits, const unsigned long long* sup_bits,
+                  const ScoreRow* tab, int tab_stride, int pos0, int nb, int rows, const int* hist_pool, float* out_lp,
+                  int* out_best_id, float* out_best_lp) {
+  if (!out_best_id || !out_best_lp) { out_best_id = nullptr; out_best_lp = nullptr; }   // both or none
+  if (rules) dec_score_kernel<true><<<rows, LP_THREADS, 0, st>>>(gp, logits, sup_bits, tab, tab_stride, pos0, nb, hist_pool, out_lp, out_best_id, out_best_lp);
+  else dec_score_kernel<false><<<rows, LP_THREADS, 0, st>>>(gp, logits, sup_bits, tab, tab_stride, pos0, nb, hist_pool, out_lp, out_best_id, out_best_lp);
 }
 
 void launch_cross_probs(hipStream_t st, const half_t* qx, int d, const half_t* ck, int T, int kvp, const int* heads,

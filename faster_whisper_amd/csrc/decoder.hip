@@ -1663,3 +1663,144 @@ extern "C" int32_t fw_align(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   }
   return FW_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// score: teacher-forced log-probs of GIVEN transcripts.  B chunks x H candidate sequences; sequence i = b * H + h is a
+// decode chunk of its own (one cache slot, beam slot 0) that reads the cross-attention K / V^T of encoder chunk b, the way
+// the hypotheses of a sampling run share theirs (kv_div = H).  prompt + targets go through the decoder in position
+// blocks; a block that holds a target position gets its logits and ONE dec_score_kernel launch over all its rows.
+// The logits at position P - 1 + k predict target k; position P - 1 + n_i predicts the <eot> that closes sequence i.
+// ------------------------------------------------------------------------------------
+extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                            const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                            const fw_gen_opts* rules, float* out_token_logprobs, int32_t* out_best_ids,
+                            float* out_best_logprobs) {
+  FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
+  FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
+  Model* m = decoder_of(&fm->impl);
+  const Tensor* enc = &enc_t->impl;
+  const fw_config& c = m->cfg;
+  FW_CHECK_ARG(decoder_of(*enc) == m, "encoder output belongs to a different model");
+  FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
+  FW_CHECK_ARG(B >= 1 && B <= m->max_batch, "batch %d exceeds max_batch %d", B, m->max_batch);
+  FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
+  FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
+  const int Bx = B * H;
+  const int P = prompt_offsets[1] - prompt_offsets[0];
+  FW_CHECK_ARG(P >= 1, "prompts must not be empty");
+  int with_ts = 1;
+  for (int b = 0; b < B; ++b) {
+    FW_CHECK_ARG(prompt_offsets[b + 1] - prompt_offsets[b] == P,
+                 "all prompts of a score() call must have the same length (prompt %d has %d tokens, expected %d)", b,
+                 prompt_offsets[b + 1] - prompt_offsets[b], P);
+    int wt = 1;
+    for (int i = 0; i < P; ++i) {
+      const int t = prompts[prompt_offsets[b] + i];
+      FW_CHECK_ARG(t >= 0 && t < c.n_vocab, "prompt token %d out of range", t);
+      if (t == c.tok_no_timestamps) wt = 0;
+    }
+    if (b == 0) with_ts = wt;
+    FW_CHECK_ARG(!rules || wt == with_ts, "the prompts of a score() call with rules must agree on <|notimestamps|>");
+  }
+  FW_CHECK_ARG(target_offsets[0] >= 0, "bad target offsets");
+  int max_n = 0;
+  for (int i = 0; i < Bx; ++i) {
+    const int n = target_offsets[i + 1] - target_offsets[i];
+    FW_CHECK_ARG(n >= 0, "target offsets must not decrease (sequence %d)", i);
+    FW_CHECK_ARG(P + n + 1 <= c.n_text_ctx, "prompt of %d + %d targets + <eot> exceed the text context %d (sequence %d)", P, n,
+                 c.n_text_ctx, i);
+    for (int k = 0; k < n; ++k) {
+      const int t = targets[target_offsets[i] + k];
+      FW_CHECK_ARG(t >= 0 && t < c.n_vocab, "target token %d out of range (sequence %d)", t, i);
+    }
+    max_n = std::max(max_n, n);
+  }
+  const int off0 = target_offsets[0];
+  const size_t n_tgt = (size_t)(target_offsets[Bx] - off0), n_out = n_tgt + Bx;
+  const int n_pos = P + max_n;                                   // positions 0 .. P - 1 + max_n
+  const int ctx = std::min(c.n_text_ctx, (n_pos + 7) / 8 * 8);
+
+  DecodeLane* lane = m->lanes[0].get();
+  std::lock_guard<std::mutex> lk(lane->mu);
+  int rc;
+  const HipFail setup_fail{FW_ERUNTIME, "score setup"}, run_fail{FW_ERUNTIME, "score"};
+  FW_HIP_AS(setup_fail, hipSetDevice(m->device));
+  if ((rc = gen_workspace_ensure(m, lane))) return rc;
+  GenWorkspace* g = lane->gen;
+  FW_CHECK_ARG(Bx <= g->R && (int64_t)Bx * ctx <= g->self_cap,
+               "this call needs %d decoder rows x %d positions; a lane of this model holds %d rows and %lld row-positions", Bx,
+               ctx, g->R, (long long)g->self_cap);
+  SingleCall sc;
+  if ((rc = single_call_begin(m, lane, enc, n_pos, ctx, setup_fail, sc))) return rc;
+  hipStream_t st = lane->stream;
+  GenDev& gp = sc.gp;
+  // one decode chunk per sequence, one cache slot each; H of them per encoder chunk (g->slot_map holds the B pool slots)
+  gp.B = Bx; gp.K = 1; gp.kv_div = H; gp.cache_rows = Bx;
+  if (rules) {
+    gp.with_ts = with_ts;
+    gp.suppress_blank = rules->suppress_blank ? 1 : 0;
+    gp.mits = fwd::initial_timestamp_limit(rules->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
+    gp.ngram = rules->no_repeat_ngram_size;
+    gp.rep_pen = rules->repetition_penalty;
+    gp.n_sup_begin = c.n_suppress_begin;
+    for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
+  }
+  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
+
+  std::vector<int> ptok((size_t)n_pos * Bx);
+  std::vector<fwd::ScoreRow> tab((size_t)Bx * n_pos, fwd::ScoreRow{-1, 0, 0, 0});
+  for (int i = 0; i < Bx; ++i) {
+    const int32_t* pr = prompts + prompt_offsets[i / H];
+    const int32_t* tg = targets + target_offsets[i];
+    const int n = target_offsets[i + 1] - target_offsets[i];
+    const int hist_off = target_offsets[i] - off0;
+    for (int p = 0; p < n_pos; ++p) {
+      ptok[(size_t)p * Bx + i] = p < P ? pr[p] : (p - P < n ? tg[p - P] : c.tok_eot);   // (padding rides along on <eot>)
+      const int k = p - (P - 1);
+      if (k >= 0 && k <= n) tab[(size_t)i * n_pos + p] = {k < n ? tg[k] : c.tok_eot, k, hist_off, hist_off + i + k};
+    }
+  }
+  DevBufs tmp;   // (after `sc`: freed before the pool block is released)
+  fwd::ScoreRow* tab_dev = nullptr;
+  int *hist_dev = nullptr, *bid_dev = nullptr;
+  float *lp_dev = nullptr, *blp_dev = nullptr;
+  if ((rc = tmp.alloc(&tab_dev, tab.size())) || (rc = tmp.alloc(&hist_dev, std::max<size_t>(1, n_tgt))) ||
+      (rc = tmp.alloc(&lp_dev, n_out)))
+    return rc;
+  if (out_best_ids && ((rc = tmp.alloc(&bid_dev, n_out)) || (rc = tmp.alloc(&blp_dev, n_out)))) return rc;
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
+  if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));
+  FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
+  if (rules) {
+    for (int i = 0; i < rules->n_suppress_tokens; ++i) {
+      const int t = rules->suppress_tokens[i];
+      if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
+    }
+    FW_HIP_AS(setup_fail, hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
+  }
+  FW_HIP_AS(setup_fail, hipStreamSynchronize(st));
+  rc = pos_block_forward(
+      m, lane, gp, ptok, n_pos, Bx, n_pos, setup_fail,
+      [&](StepCfg& s, int pos, int nb) {
+        s.need_logits = pos + nb - 1 >= P - 1;   // every sequence has a target from position P - 1 on (its <eot> at least)
+        s.nospeech_rowmul = 0; s.done = g->zero_done;
+      },
+      [&](int pos, int nb) {
+        if (pos + nb - 1 < P - 1) return;
+        ProfScope ps(lane->prof, PF_DEC_MISC, 0, 4.0 * Bx * nb * (double)c.n_vocab, st);
+        fwd::launch_score(st, gp, rules != nullptr, g->logits, g->sup_bits, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev, lp_dev,
+                          bid_dev, blp_dev);
+      });
+  if (rc) return rc;
+  float* out_lp = out_token_logprobs + off0;
+  FW_HIP_AS(run_fail, hipMemcpyAsync(out_lp, lp_dev, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (out_best_ids) {
+    FW_HIP_AS(run_fail, hipMemcpyAsync(out_best_ids + off0, bid_dev, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
+    FW_HIP_AS(run_fail, hipMemcpyAsync(out_best_logprobs + off0, blp_dev, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  FW_HIP_AS(run_fail, hipStreamSynchronize(st));
+  FW_HIP_AS(run_fail, hipGetLastError());
+  prof_collect(lane->prof);
+  return FW_OK;
+}

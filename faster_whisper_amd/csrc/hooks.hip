@@ -1024,6 +1024,70 @@ int32_t fw_test_logits_rules_ex(fw_model* fm, float* logits, int32_t R, const in
                            tab_given ? tab.data() : nullptr, &ex);
 }
 
+// ONE launch of the scoring kernel on caller-provided rows (include/fwamd_test.h): row r is scored against targets[r] with
+// the history hist[hist_offsets[r] .. hist_offsets[r + 1]); opts null: the raw distribution.  Every id is checked before
+// anything is allocated or launched: the sparse rules and the target pick index the row with them.
+int32_t fw_test_score_rows(fw_model* fm, float* logits, int32_t rows, const int32_t* targets, const int32_t* hist,
+                           const int32_t* hist_offsets, const fw_gen_opts* o, int32_t with_timestamps, float* out_lp,
+                           int32_t* out_best_id, float* out_best_lp) {
+  FW_CHECK_ARG(fm && logits && targets && hist_offsets && out_lp && out_best_id && out_best_lp && rows >= 1, "bad arguments");
+  Model* m = &fm->impl;
+  const fw_config& c = m->cfg;
+  FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
+  FW_CHECK_ARG(hist_offsets[0] == 0, "hist_offsets must start at 0");
+  std::vector<fwd::ScoreRow> tab((size_t)rows);
+  for (int r = 0; r < rows; ++r) {
+    const int n = hist_offsets[r + 1] - hist_offsets[r];
+    FW_CHECK_ARG(n >= 0 && n < c.n_text_ctx && (n == 0 || hist), "row %d: a history of %d ids (text context %d)", r, n, c.n_text_ctx);
+    FW_CHECK_ARG(targets[r] < c.n_vocab, "targets[%d] = %d outside [0, %d)", r, targets[r], c.n_vocab);
+    for (int i = 0; i < n; ++i) {
+      const int t = hist[hist_offsets[r] + i];
+      FW_CHECK_ARG(t >= 0 && t < c.n_vocab, "hist of row %d, entry %d = %d outside [0, %d)", r, i, t, c.n_vocab);
+    }
+    tab[r] = {targets[r], n, hist_offsets[r], r};
+  }
+  FW_HIP(hipSetDevice(m->device));
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.B = rows; gp.K = 1; gp.R = rows; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1;
+  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
+  gp.rep_pen = 1.0f;
+  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
+  if (o) {
+    gp.with_ts = with_timestamps ? 1 : 0;
+    gp.suppress_blank = o->suppress_blank ? 1 : 0;
+    gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
+    gp.ngram = o->no_repeat_ngram_size;
+    gp.rep_pen = o->repetition_penalty;
+    gp.n_sup_begin = c.n_suppress_begin;
+    for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
+    for (int i = 0; i < o->n_suppress_tokens; ++i) {
+      const int t = o->suppress_tokens[i];
+      if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
+    }
+  }
+  const size_t n_hist = (size_t)hist_offsets[rows];
+  const int zero = 0;
+  HookBufs db;
+  float *d_lg, *d_lp, *d_blp;
+  int *d_hist, *d_bid;
+  fwd::ScoreRow* d_tab;
+  unsigned long long* d_bits;
+  int rc;
+  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * c.n_vocab)) || (rc = db.upload(&d_tab, tab.data(), tab.size())) ||
+      (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))) ||
+      (rc = db.upload(&d_bits, mask.data(), mask.size())) || (rc = db.upload(&d_lp, (const float*)out_lp, (size_t)rows)) ||
+      (rc = db.upload(&d_bid, (const int*)out_best_id, (size_t)rows)) || (rc = db.upload(&d_blp, (const float*)out_best_lp, (size_t)rows)))
+    return rc;
+  fwd::launch_score(nullptr, gp, o != nullptr, d_lg, d_bits, d_tab, 1, 0, 1, rows, d_hist, d_lp, d_bid, d_blp);
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipDeviceSynchronize());
+  if ((rc = download(out_lp, d_lp, (size_t)rows)) || (rc = download(out_best_id, d_bid, (size_t)rows)) ||
+      (rc = download(out_best_lp, d_blp, (size_t)rows)))
+    return rc;
+  return download(logits, d_lg, (size_t)rows * c.n_vocab);
+}
+
 // step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together
 int32_t fw_test_graph_captures(const fw_model* fm, int64_t* out) {
   FW_CHECK_ARG(fm && out, "null argument");

@@ -12,7 +12,7 @@ Only what the reference touches is provided: `models.Whis
 import sys
 import types
 
-from .backend import StorageView, Whisper, WhisperAlignmentResult, WhisperGenerationResult
+from .backend import StorageView, Whisper, WhisperAlignmentResult, WhisperGenerationResult, WhisperScoringResult
 
 __version__ = "4.5.0+fwamd"
 
@@ -20,6 +20,7 @@ models = types.ModuleType("ctranslate2.models")
 models.Whisper = Whisper
 models.WhisperGenerationResult = WhisperGenerationResult
 models.WhisperAlignmentResult = WhisperAlignmentResult
+models.WhisperScoringResult = WhisperScoringResult   # (Whisper.score: not in CTranslate2's Whisper class)
 
 
 def get_supported_compute_types(device: str, device_index: int = 0):

@@ -14,6 +14,7 @@
  *   .generate          transcribe.py:222-236, 1446-1459 -> fw_generate
  *   .detect_language   transcribe.py:215,1193,1823      -> fw_detect_language
  *   .align             transcribe.py:1709-1715          -> fw_align
+ *   .score             (not in the reference: CTranslate2's score_batch for Whisper) -> fw_score
  *
  * plus the log-mel front end the reference runs in numpy on the host
  * (faster_whisper/feature_extractor.py:198-230, called at
@@ -52,7 +53,8 @@ extern "C" {
  *    fw_model_run_capacity added, test / bench hooks moved to fwamd_test.h; the cross-attention cache of a decode group
  *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run);
  *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed),
- *    fw_vad_forward_audio_batch_dev likewise, and fw_generate_lp (fw_generate plus per-token log-probabilities) */
+ *    fw_vad_forward_audio_batch_dev likewise, fw_generate_lp (fw_generate plus per-token log-probabilities) and
+ *    fw_score (teacher-forced log-probs of given transcripts) */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -274,6 +276,31 @@ int32_t fw_generate(fw_model* m, const fw_tensor* enc, const int32_t* prompts,
 int32_t fw_generate_lp(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets, int32_t B,
                        const fw_gen_opts* opts, int32_t* out_ids, int32_t* out_lens, float* out_scores,
                        float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs);
+
+/* ---- score ---------------------------------------------------------------
+ * Teacher-forced log-probs of GIVEN transcripts (CTranslate2 has score_batch for its other model classes): how likely
+ * is this text under the model, for text that was not decoded here — a corrected transcript, another system's output,
+ * an n-best list.  prompts: B prompts of equal length, as fw_generate.  targets: B * H sequences back to back,
+ * target_offsets[B * H + 1], ragged, any of them may be empty; sequence i = b * H + h is candidate h of chunk b of `enc`
+ * (1 <= H <= max_beam: the candidates of a chunk share its cross-attention K/V the way beams do).
+ * Outputs, three arrays of target_offsets[B * H] + B * H entries: sequence i with n_i targets owns entries
+ * target_offsets[i] + i .. + n_i of each; the first n_i belong to its tokens, the last to the <eot> that would close it.
+ *   out_token_logprobs  log-prob of the given token (of <eot> in the last entry); -inf for a token the rules forbid
+ *   out_best_ids        the arg-max of the same distribution (ties: the lowest id) ...
+ *   out_best_logprobs   ... and its log-prob.  Both NULL, or both given.
+ * rules == NULL: the raw distribution (fp32 log-softmax of the logits).  Otherwise the distribution fw_generate's search
+ * ranks by, for a greedy row whose history is the sequence's own prefix: repetition_penalty, no_repeat_ngram_size,
+ * suppress_blank, suppress_tokens and max_initial_timestamp_index are read, the timestamp rules are on unless the prompts
+ * carry <|notimestamps|> (they must agree on it), and EVERY other field — beam_size, patience, num_hypotheses,
+ * length_penalty, max_length, min_new_tokens, the return_* switches, sampling_* and seed — is ignored.  Adding a
+ * sequence's entries in order in float32 then gives the cumulative log-prob fw_generate would normalise into its score.
+ * FW_EINVAL before anything is launched: a null argument, B != the encoder output's batch or > max_batch, H out of range,
+ * an id outside [0, n_vocab), prompt length + n_i + 1 > n_text_ctx, offsets that decrease, more rows than a decode lane
+ * holds.  Runs on the first decode lane like fw_align: prompt + targets go through the decoder in position blocks, one
+ * scoring-kernel launch per block. */
+int32_t fw_score(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                 const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
+                 float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
 
 /* ---- detect_language -------------------------------------------------------
  * ctranslate2.models.Whisper.detect_language: one decoder step on [sot];

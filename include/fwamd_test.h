@@ -66,6 +66,21 @@ int32_t fw_test_logits_rules_ex(fw_model* m, float* logits, int32_t R, const int
                                 const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
                                 const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
                                 int32_t* cand_tok, float* cand_lp);
+/* ONE launch of the scoring kernel (dec_score_kernel, what fw_score launches per position block) on caller-provided rows
+ * (tests/test_gpu_score_kernel.py):
+ *   in/out  logits [rows][n_vocab] float32: uploaded, and downloaded WHOLE after the launch (the kernel must not write it)
+ *   in      targets [rows]: the id scored on each row; < 0: the row has no target and nothing is written for it
+ *   in      hist, hist_offsets [rows + 1]: row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1]), fewer than
+ *           n_text_ctx ids (read only with rules; hist may be NULL when every history is empty)
+ *   in      opts | NULL: NULL scores the raw distribution; otherwise the decoding rules of a greedy row with that history
+ *           (repetition_penalty, no_repeat_ngram_size, suppress_blank, suppress_tokens, max_initial_timestamp_index;
+ *           with_timestamps switches the timestamp rules; every other field is ignored)
+ *   in/out  out_lp / out_best_id / out_best_lp [rows]: the device buffers start as the caller's values
+ * Checked before anything is allocated or launched (FW_EINVAL): targets below n_vocab, every hist id in [0, n_vocab),
+ * offsets that do not decrease, histories shorter than n_text_ctx. */
+int32_t fw_test_score_rows(fw_model* m, float* logits, int32_t rows, const int32_t* targets, const int32_t* hist,
+                           const int32_t* hist_offsets, const fw_gen_opts* opts, int32_t with_timestamps, float* out_lp,
+                           int32_t* out_best_id, float* out_best_lp);
 /* out[0] = step graphs (one hipGraph per distinct decode-step geometry, decoder.hip) the model's decode group has
  * captured and instantiated since the model was created, summed over its lanes */
 int32_t fw_test_graph_captures(const fw_model* m, int64_t* out);
