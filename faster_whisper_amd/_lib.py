@@ -22,6 +22,7 @@ COMPUTE_INT8_FLOAT16 = 1
 FW_DT_F32 = 0
 FW_DT_F16 = 1
 FW_MAX_ALIGN_HEADS = 64
+FW_MAX_ALTERNATIVES = 8
 
 
 class FwConfig(C.Structure):
@@ -75,7 +76,7 @@ SYMBOLS = [
     "fw_logmel", "fw_logmel_full",
     "fw_encode", "fw_encode_pcm", "fw_encode_pcm_dev", "fw_tensor_shape", "fw_tensor_to_host",
     "fw_tensor_from_host", "fw_tensor_free",
-    "fw_generate", "fw_generate_lp", "fw_detect_language", "fw_align", "fw_score",
+    "fw_generate", "fw_generate_lp", "fw_generate_alt", "fw_detect_language", "fw_align", "fw_score",
     "fw_prof_enable", "fw_prof_reset", "fw_prof_count", "fw_prof_name", "fw_prof_get", "fw_synchronize",
     "fw_dev_alloc", "fw_dev_free", "fw_dev_upload",
     "fw_test_gemm", "fw_test_layernorm", "fw_test_attention", "fw_test_dec_linear", "fw_test_dec_logits", "fw_test_logits_rules",
@@ -84,6 +85,7 @@ SYMBOLS = [
     "fw_test_gemm_ex", "fw_test_cross_kv_frag_index", "fw_test_quant_rows", "fw_test_layernorm_frag",
     "fw_test_dec_beam_update", "fw_test_dec_embed", "fw_test_align_post",
     "fw_test_logits_rules_lp", "fw_test_dec_beam_update_lp",
+    "fw_test_logits_rules_alt", "fw_test_dec_beam_update_alt", "fw_test_alt_gather",
     "fw_test_logits_rules_smp_tab", "fw_test_logits_rules_ex", "fw_test_score_rows", "fw_test_graph_captures", "fw_test_blob_check",
     "fw_vad_create", "fw_vad_forward", "fw_vad_free", "fw_vad_forward_dev", "fw_vad_forward_audio_dev",
     "fw_vad_forward_audio_batch_dev",
@@ -166,6 +168,16 @@ def load():
     lib.fw_generate.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32p, i32p, f32p, f32p]
     if hasattr(lib, "fw_generate_lp"):            # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_generate_lp.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32p, i32p, f32p, f32p, f32p, f32p]
+    if hasattr(lib, "fw_generate_alt"):           # (absent from an older build loaded through FWAMD_LIB)
+        f32 = C.c_float
+        lib.fw_generate_alt.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32, i32p, i32p, f32p, f32p, f32p,
+                                        f32p, i32p, f32p, i32p, f32p]
+        lib.fw_test_logits_rules_alt.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp, vp, vp,
+                                                 vp, vp, i32, vp, vp]
+        lib.fw_test_dec_beam_update_alt.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp,
+                                                    vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    vp, vp, vp]
+        lib.fw_test_alt_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.fw_detect_language.argtypes = [vp, vp, i32, i32p, f32p]
     lib.fw_align.argtypes = [vp, vp, i32p, i32, i32p, i32p, i32p, i32, i32, i32, i32p, i32p, f32p]
     lib.fw_prof_enable.argtypes = [vp, i32]

@@ -25,6 +25,8 @@ from . import _lib
 from .config import WhisperConfig, get_config
 from .weights import synthetic_weights, weight_shapes
 
+MAX_ALTERNATIVES = _lib.FW_MAX_ALTERNATIVES   # generate(return_alternatives=N): N at most
+
 _COMPUTE_TYPES = {
     "default": _lib.COMPUTE_FLOAT16, "auto": _lib.COMPUTE_FLOAT16, "float16": _lib.COMPUTE_FLOAT16,
     "int8_float16": _lib.COMPUTE_INT8_FLOAT16, "int8": _lib.COMPUTE_INT8_FLOAT16,
@@ -99,6 +101,12 @@ class WhisperGenerationResult:
         # the budget).  Empty lists when not requested.
         self.token_logprobs = token_logprobs if token_logprobs is not None else []
         self.end_logprobs = end_logprobs if end_logprobs is not None else []
+        # generate(return_alternatives=N): token_alternatives[h][i] = the N most likely (id, log-prob) pairs of the
+        # distribution sequences_ids[h][i] was chosen from (log-prob descending, id ascending; (0, -inf) where fewer than N
+        # ids were left), end_alternatives[h] = those of the step that produced the closing <eot>, None when the
+        # hypothesis was cut at the budget.  Empty lists when not requested.
+        self.token_alternatives = []
+        self.end_alternatives = []
 
     def __repr__(self):
         return (f"WhisperGenerationResult(sequences_ids={self.sequences_ids}, scores={self.scores}, "
@@ -540,9 +548,14 @@ class Whisper:
                  max_initial_timestamp_index: int = 50, suppress_blank: bool = True,
                  suppress_tokens: Optional[Sequence[int]] = (-1,), sampling_topk: int = 1,
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
-                 seed: Optional[int] = None, return_token_logprobs: bool = False) -> List[WhisperGenerationResult]:
+                 seed: Optional[int] = None, return_token_logprobs: bool = False,
+                 return_alternatives: int = 0) -> List[WhisperGenerationResult]:
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
+        n_alt = int(return_alternatives)
+        if not 0 <= n_alt <= MAX_ALTERNATIVES:
+            raise ValueError(f"return_alternatives must lie in [0, {MAX_ALTERNATIVES}] (got {return_alternatives})")
+        return_token_logprobs = bool(return_token_logprobs) or n_alt > 0
         enc = self._as_encoded(features)
         if len(prompts) != enc._shape[0]:
             raise ValueError(f"got {len(prompts)} prompts for a batch of {enc._shape[0]}")
@@ -576,12 +589,22 @@ class Whisper:
             args = (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o),
                     _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp))
             if return_token_logprobs:
-                if not hasattr(self._lib, "fw_generate_lp"):   # an older build loaded through FWAMD_LIB
-                    raise RuntimeError("this libfwamd.so has no fw_generate_lp: per-token log-probabilities need a "
-                                       "current build")
+                need = "fw_generate_alt" if n_alt else "fw_generate_lp"
+                if not hasattr(self._lib, need):   # an older build loaded through FWAMD_LIB
+                    raise RuntimeError(f"this libfwamd.so has no {need}: per-token log-probabilities"
+                                       f"{' and alternatives' if n_alt else ''} need a current build")
                 tlp = np.zeros((B, nh, ml), dtype=np.float32)
                 elp = np.zeros((B, nh), dtype=np.float32)
-                _lib.check(self._lib.fw_generate_lp(*args, _lib.as_f32p(tlp), _lib.as_f32p(elp)))
+                if n_alt:
+                    aid = np.zeros((B, nh, ml, n_alt), dtype=np.int32)
+                    alp = np.zeros((B, nh, ml, n_alt), dtype=np.float32)
+                    eid = np.zeros((B, nh, n_alt), dtype=np.int32)
+                    elps = np.zeros((B, nh, n_alt), dtype=np.float32)
+                    _lib.check(self._lib.fw_generate_alt(*args[:6], n_alt, *args[6:], _lib.as_f32p(tlp), _lib.as_f32p(elp),
+                                                         _lib.as_i32p(aid), _lib.as_f32p(alp), _lib.as_i32p(eid),
+                                                         _lib.as_f32p(elps)))
+                else:
+                    _lib.check(self._lib.fw_generate_lp(*args, _lib.as_f32p(tlp), _lib.as_f32p(elp)))
             else:
                 _lib.check(self._lib.fw_generate(*args))
             out = []
@@ -592,6 +615,14 @@ class Whisper:
                 if return_token_logprobs:
                     res.token_logprobs = [tlp[b, h, :lens[b, h]].tolist() for h in range(nh)]
                     res.end_logprobs = [float(elp[b, h]) for h in range(nh)]
+                if n_alt:
+                    res.token_alternatives = [          # (one tolist per hypothesis, not one per position)
+                        [list(zip(i, v)) for i, v in zip(aid[b, h, :lens[b, h]].tolist(), alp[b, h, :lens[b, h]].tolist())]
+                        for h in range(nh)]
+                    # (id -1: no closing step — the hypothesis was cut at the budget, or the slot holds no hypothesis)
+                    res.end_alternatives = [
+                        list(zip(eid[b, h].tolist(), elps[b, h].tolist())) if eid[b, h, 0] >= 0 else None
+                        for h in range(nh)]
                 out.append(res)
             return out
         return self._over_parts(enc, one_call, prompts)

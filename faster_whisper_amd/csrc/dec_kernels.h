@@ -29,6 +29,9 @@ struct GenDev {
   // shortest prompt and budget the longest budget.  0 / 0 in a uniform run: a cached step graph captured the table
   // pointer (or null) by value, so the two kinds never share a graph.
   int ragged, reach;
+  // ALTERNATIVES (fw_generate_alt): the rules kernel also records the row's n_alt most likely ids per step (the largest
+  // n_alt of the run's calls, <= FW_MAX_ALTERNATIVES).  0 in every run that records none: the key and the kernels of today.
+  int n_alt;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -121,7 +124,15 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 #define LP_SUP_WORDS 896
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp = nullptr, const SmpRow* smp_tab = nullptr);
+                           int* cand_tok, float* cand_lp = nullptr, const SmpRow* smp_tab = nullptr,
+                           int* alt_tok = nullptr, float* alt_lp = nullptr);
+// ALTERNATIVES (gp.n_alt > 0 and both alt pointers given, otherwise today's kernels): alt_tok / alt_lp [steps][gp.R][n_alt],
+// row r at step s writes the first n_alt rounds of its extraction (log-prob descending, id ascending; (0, -inf) once
+// nothing is left) to [s][r][.] — the registers cand_lp is written from; a sampling row runs n_alt plain rounds on the
+// unperturbed log-probs after its draw.  fin_path [chunks][FIN_CAP][NT + 1] (beam update): for a finished hypothesis
+// recorded at step s, byte q < s = the beam slot whose row produced token q (the source row's slot-table byte at
+// Pc - 1 + q), byte s = the source row's own beam index: alt_*[q][c * K + fin_path[q]] belong to its tokens and to the step
+// that closed it.  Nothing is copied per step.
 // cand_lp [R][32]: the log-prob of every candidate (cand_val = cum + cand_lp), lphist2 [2][R][NT] the log-prob history
 // beside hist2, fin_lp [.][FIN_CAP][NT + 1] the values of a finished hypothesis' tokens and, at [NT], of its <eot>.
 // Null (all three of the beam update, or none): the kernels skip these stores.
@@ -129,7 +140,16 @@ void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
                         int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum,
                         const float* cand_lp = nullptr, float* lphist2 = nullptr, float* fin_lp = nullptr,
-                        const int* ptab = nullptr);
+                        const int* ptab = nullptr, uint8_t* fin_path = nullptr);
+// One returned hypothesis for launch_alt_gather: decode chunk, finished slot, length, and the step whose row produced the
+// closing <eot> (-1: cut at the budget, no closing step).
+struct AltHyp { int chunk, fin, len, end; };
+static_assert(sizeof(AltHyp) == 16, "one 16-byte load per hypothesis");
+// out_tok / out_lp [n_hyp][T + 1][n_alt]: entry t < len = alt_*[t][chunk * K + fin_path[t]][.], entry T = those of step
+// `end`; entries in [len, T), and entry T of a hypothesis without closing step, are (-1, 0).  R: rows of the run that
+// filled alt_* (its step stride).  Every len <= T, end < steps of alt_*, path byte < K: the caller's to guarantee.
+void launch_alt_gather(hipStream_t st, const int* alt_tok, const float* alt_lp, const uint8_t* fin_path, const AltHyp* hyps,
+                       int n_hyp, int R, int K, int NT, int n_alt, int T, int* out_tok, float* out_lp);
 // ragged runs: rows of the final hidden state at each chunk's <sot> position -> row `chunk` of xo (row-major) and xof
 // (fragment-major); nb > 0: a prompt pass over positions pos0 .. (row = chunk * nb + j), nb == 0: decode step 0
 void launch_gather_sot_rows(hipStream_t st, const half_t* x, const int* sot_tab, const int* ptab, int pos0, int nb,

@@ -1492,7 +1492,12 @@ static __device__ __forceinline__ float gumbel_noise(unsigned seed_lo, unsigned 
 // arg-max + 16 partials through LDS, and only the winning thread rescans its 56 values.
 // TXI: the first TXI values of every thread are text ids whatever the thread (ts_begin >= TXI * 1024: 48 for every
 // Whisper vocabulary, 0 for the synthetic test vocabularies) — a compile-time class split, no per-lane test there.
-template <bool SMP, int TXI>
+// ALT (fw_generate_alt; instantiations of their own, the others are the code they always were): the row also writes the
+// first gp.n_alt rounds of its extraction to alt_tok / alt_lp [steps][R][n_alt] at [step][r][.], from the registers
+// cand_lp is written from.  Beam / greedy: max(2K, n_alt) rounds, rounds < 2K fill cand_*, rounds < n_alt fill alt_*.
+// Sampling: the draw is round 0 and does NOT retire its value (nothing after it read the retired value; the token, its
+// cand_val and cand_lp keep their bits), then every thread finds its best plain log-prob and n_alt plain rounds follow.
+template <bool SMP, int TXI, bool ALT = false>
 __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::GenDev gp, float* __restrict__ logits,
                                                                         const unsigned long long* __restrict__ sup_bits,
                                                                         const int* __restrict__ hist2,
@@ -1502,7 +1507,9 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
                                                                         float* __restrict__ cand_val,
                                                                         int* __restrict__ cand_tok,
                                                                         float* __restrict__ cand_lp,
-                                                                        const fwd::SmpRow* __restrict__ smp_tab) {
+                                                                        const fwd::SmpRow* __restrict__ smp_tab,
+                                                                        int* __restrict__ alt_tok,
+                                                                        float* __restrict__ alt_lp) {
   __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
   __shared__ float bkey_s[2][LP_WAVES];
   __shared__ int btok_s[2][LP_WAVES];
@@ -1691,7 +1698,22 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
   }
   // ---- top-C of cum + logp: C rounds (value desc, index asc).  Sampling mode (Gumbel-max): one round on
   //      logp/T + Gumbel noise; the recorded score stays cum + logp. ----
-  for (int cidx = 0; cidx < C; ++cidx) {
+  // ALT: round `rd` fills candidate slot rd (while rd < C) and alternative slot `ai` (while 0 <= ai < n_alt): ai = rd,
+  // but rd - 1 when sampling, whose round 0 is the draw.
+  const int n_alt = ALT ? gp.n_alt : 0;
+  const int NR = !ALT ? C : (smp ? 1 + n_alt : (C > n_alt ? C : n_alt));
+  const size_t alt0 = ALT ? ((size_t)step * gp.R + r) * n_alt : 0;
+  for (int cidx = 0; cidx < NR; ++cidx) {
+    const bool plain = !smp || (ALT && cidx > 0);   // a round on the log-probs themselves: the winner finds its next best
+    const bool w_cand = !ALT || cidx < C;           // (uniform)
+    const int ai = smp ? cidx - 1 : cidx;
+    const bool w_alt = ALT && ai >= 0 && ai < n_alt;
+    if (ALT && smp && cidx == 1) {   // after the draw: this thread's best plain log-prob (the draw retired nothing)
+      bkey = NEG; bq = -1;
+#pragma unroll
+      for (int i = 0; i < LP_NV; ++i)
+        if (val[i] > bkey) { bkey = val[i]; bq = i; }
+    }
     float k = bkey;
     int t = (bq < 0) ? NONE : tid + bq * LP_THREADS;
     wave_argmax_v(k, t);        // DPP / permlane exchanges (the ds_bpermute butterfly was ~1 500 cycles per round)
@@ -1708,13 +1730,16 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
     argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR8>(wk), dpp_i<FW_DPP_ROR8>(wt));
     if (wt == NONE) {   // nothing left on this row
       if (tid == 0) {
-        cand_val[(size_t)r * 32 + cidx] = NEG;
-        cand_tok[(size_t)r * 32 + cidx] = 0;
-        if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
-        if (cand_lp) {   // (a kernel argument: uniform)
-          cand_lp[(size_t)r * 32 + cidx] = NEG;
-          if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+        if (w_cand) {
+          cand_val[(size_t)r * 32 + cidx] = NEG;
+          cand_tok[(size_t)r * 32 + cidx] = 0;
+          if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
+          if (cand_lp) {   // (a kernel argument: uniform)
+            cand_lp[(size_t)r * 32 + cidx] = NEG;
+            if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+          }
         }
+        if (w_alt) { alt_tok[alt0 + ai] = 0; alt_lp[alt0 + ai] = NEG; }
       }
       continue;
     }
@@ -1724,18 +1749,21 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
       bkey = NEG; bq = -1;
 #pragma unroll
       for (int i = 0; i < LP_NV; ++i) {
-        if (i == wq) { raw = val[i]; val[i] = NEG; }
-        if (!smp && val[i] > bkey) { bkey = val[i]; bq = i; }
+        if (i == wq) { raw = val[i]; if (!(ALT && smp) || cidx > 0) val[i] = NEG; }
+        if (plain && val[i] > bkey) { bkey = val[i]; bq = i; }
       }
-      cand_val[(size_t)r * 32 + cidx] = cum + raw;
-      cand_tok[(size_t)r * 32 + cidx] = wt;
-      if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
-      // the token's own log-prob, as it was added to cum: stored, not recovered later from two running sums
-      // (fl(cum + raw) - cum is not raw once |raw| > |cum|)
-      if (cand_lp) {
-        cand_lp[(size_t)r * 32 + cidx] = raw;
-        if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+      if (w_cand) {
+        cand_val[(size_t)r * 32 + cidx] = cum + raw;
+        cand_tok[(size_t)r * 32 + cidx] = wt;
+        if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
+        // the token's own log-prob, as it was added to cum: stored, not recovered later from two running sums
+        // (fl(cum + raw) - cum is not raw once |raw| > |cum|)
+        if (cand_lp) {
+          cand_lp[(size_t)r * 32 + cidx] = raw;
+          if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
+        }
       }
+      if (w_alt) { alt_tok[alt0 + ai] = wt; alt_lp[alt0 + ai] = raw; }
     }
   }
 }
@@ -1976,7 +2004,10 @@ __global__ __launch_bounds__(LP_THREADS) void dec_score_kernel(fwd::GenDev gp, c
 // RAG (ragged run, an instantiation of its own): the chunk's prompt length comes from ptab; its slot-table byte goes to
 // ptab[c] - 1 + step and its last step is the one that uses up ITS budget, gp.reach - ptab[c].  (A chunk is done from that
 // step on and returns at the top: the position needs no clamp here.)
-template <bool RAG>
+// ALT (alternatives; instantiations of their own): a recorded hypothesis also gets its PATH, fin_path [.][FIN_CAP][NT + 1]
+// bytes: entry q < step = the source row's slot-table byte at Pc - 1 + q (the beam slot whose row produced token q), entry
+// step = the source row's own beam index.  Written where fin_tok is written, nowhere else; the row-state rewrite is as it was.
+template <bool RAG, bool ALT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void dec_beam_update_kernel(fwd::GenDev gp, const int* __restrict__ ptab, const float* __restrict__ cand_val,
                                                              const int* __restrict__ cand_tok, int* __restrict__ hist2,
@@ -1987,7 +2018,8 @@ void dec_beam_update_kernel(fwd::GenDev gp, const int* __restrict__ ptab, const 
                                                              int* __restrict__ fin_len, float* __restrict__ fin_score,
                                                              float* __restrict__ fin_cum,
                                                              const float* __restrict__ cand_lp,
-                                                             float* __restrict__ lphist2, float* __restrict__ fin_lp) {
+                                                             float* __restrict__ lphist2, float* __restrict__ fin_lp,
+                                                             uint8_t* __restrict__ fin_path) {
   __shared__ float ov[32], olp[32];
   __shared__ int ok[32], ot[32];
   __shared__ int s_parent[16], s_tok[16];
@@ -2044,6 +2076,12 @@ void dec_beam_update_kernel(fwd::GenDev gp, const int* __restrict__ ptab, const 
             for (int q = 0; q < step; ++q) ldst[q] = lsrc[q];
             if (ot[jdx] != gp.eot) { ldst[step] = olp[jdx]; ldst[NT] = 0.f; }
             else ldst[NT] = olp[jdx];
+          }
+          if (ALT) {
+            const uint8_t* isrc = kvidx2 + ((size_t)cur * gp.R + c * K + kk) * NT + (Pc - 1);
+            uint8_t* pdst = fin_path + ((size_t)c * fwd::FIN_CAP + nf) * (NT + 1);
+            for (int q = 0; q < step; ++q) pdst[q] = isrc[q];
+            pdst[step] = (uint8_t)kk;
           }
           if (ot[jdx] != gp.eot) { dst[len] = ot[jdx]; len++; }
           fin_len[c * fwd::FIN_CAP + nf] = len;
@@ -2507,28 +2545,67 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab) {
+                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab, int* alt_tok, float* alt_lp) {
   if (gp.sample && !smp_tab) return;   // (a sampling launch without its table: nothing is launched, nothing is read)
   // every Whisper vocabulary keeps its timestamp ids above 48 * 1024 (ts_begin 50 363 .. 50 365); the synthetic
   // test vocabularies do not: they take the instantiation with a per-lane class test everywhere
   const bool wide = gp.ts_begin >= 48 * LP_THREADS;
-#define LP_GO(SMP, TXI) \
-  dec_logits_process_kernel<SMP, TXI><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab)
-  if (gp.sample) { if (wide) LP_GO(true, 48); else LP_GO(true, 0); }
-  else { if (wide) LP_GO(false, 48); else LP_GO(false, 0); }
+  const bool alt = gp.n_alt > 0 && alt_tok && alt_lp;
+  if (gp.n_alt > 0 && !alt) return;   // (a key that says alternatives without their buffers: nothing is launched)
+#define LP_GO(SMP, TXI, ALT) \
+  dec_logits_process_kernel<SMP, TXI, ALT><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab, alt_tok, alt_lp)
+  if (alt) {
+    if (gp.sample) { if (wide) LP_GO(true, 48, true); else LP_GO(true, 0, true); }
+    else { if (wide) LP_GO(false, 48, true); else LP_GO(false, 0, true); }
+  } else if (gp.sample) { if (wide) LP_GO(true, 48, false); else LP_GO(true, 0, false); }
+  else { if (wide) LP_GO(false, 48, false); else LP_GO(false, 0, false); }
 #undef LP_GO
 }
 
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
                         int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum, const float* cand_lp,
-                        float* lphist2, float* fin_lp, const int* ptab) {
+                        float* lphist2, float* fin_lp, const int* ptab, uint8_t* fin_path) {
   if (!cand_lp || !lphist2 || !fin_lp) { cand_lp = nullptr; lphist2 = nullptr; fin_lp = nullptr; }   // all three or none
 #define BU_ARGS gp, ptab, cand_val, cand_tok, hist2, cum2, kvidx2, cur_tok, d_step, done, n_done, n_fin, fin_tok, fin_len, \
-                fin_score, fin_cum, cand_lp, lphist2, fin_lp
-  if (ptab) dec_beam_update_kernel<true><<<gp.B, 64, 0, st>>>(BU_ARGS);
-  else dec_beam_update_kernel<false><<<gp.B, 64, 0, st>>>(BU_ARGS);
+                fin_score, fin_cum, cand_lp, lphist2, fin_lp, fin_path
+  if (fin_path) {
+    if (ptab) dec_beam_update_kernel<true, true><<<gp.B, 64, 0, st>>>(BU_ARGS);
+    else dec_beam_update_kernel<false, true><<<gp.B, 64, 0, st>>>(BU_ARGS);
+  } else if (ptab) dec_beam_update_kernel<true, false><<<gp.B, 64, 0, st>>>(BU_ARGS);
+  else dec_beam_update_kernel<false, false><<<gp.B, 64, 0, st>>>(BU_ARGS);
 #undef BU_ARGS
+}
+
+// Alternatives of the returned hypotheses, once per run after the last step: one workgroup per hypothesis walks its path
+// (fin_path) through the step-major alt_* buffers and writes [hyp][T + 1][n_alt]; copies, no arithmetic (dec_kernels.h).
+__global__ __launch_bounds__(256) void dec_alt_gather_kernel(const int* __restrict__ alt_tok, const float* __restrict__ alt_lp,
+                                                             const uint8_t* __restrict__ fin_path,
+                                                             const fwd::AltHyp* __restrict__ hyps, int R, int K, int NT,
+                                                             int n_alt, int T, int* __restrict__ out_tok,
+                                                             float* __restrict__ out_lp) {
+  const fwd::AltHyp h = hyps[blockIdx.x];
+  const uint8_t* path = fin_path + ((size_t)h.chunk * fwd::FIN_CAP + h.fin) * (NT + 1);
+  const size_t o0 = (size_t)blockIdx.x * (T + 1) * n_alt;
+  for (int i = threadIdx.x; i < (T + 1) * n_alt; i += blockDim.x) {
+    const int t = i / n_alt, j = i - t * n_alt;
+    const int q = t < T ? (t < h.len ? t : -1) : h.end;   // the step whose row is read
+    int tok = -1;
+    float lp = 0.f;
+    if (q >= 0) {
+      const size_t src = ((size_t)q * R + h.chunk * K + path[q]) * n_alt + j;
+      tok = alt_tok[src];
+      lp = alt_lp[src];
+    }
+    out_tok[o0 + i] = tok;
+    out_lp[o0 + i] = lp;
+  }
+}
+
+void launch_alt_gather(hipStream_t st, const int* alt_tok, const float* alt_lp, const uint8_t* fin_path, const AltHyp* hyps,
+                       int n_hyp, int R, int K, int NT, int n_alt, int T, int* out_tok, float* out_lp) {
+  if (n_hyp <= 0) return;
+  dec_alt_gather_kernel<<<n_hyp, 256, 0, st>>>(alt_tok, alt_lp, fin_path, hyps, R, K, NT, n_alt, T, out_tok, out_lp);
 }
 
 // Ragged runs, no-speech probability: the final hidden row of every chunk whose <sot> position falls into this pass goes

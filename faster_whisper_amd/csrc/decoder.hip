@@ -92,6 +92,14 @@ struct GenWorkspace {
   float* cand_lp = nullptr;              // [R][32]
   float* lphist2 = nullptr;              // [2][R][NT]
   float* fin_lp = nullptr;               // [R][FIN_CAP][NT + 1]
+  // alternatives (fw_generate_alt; dec_kernels.h): nothing until a run records some (run_alt_ensure), then sized by the largest
+  // run so far.  A step graph holds these pointers by value: growing them drops the graphs that record alternatives.
+  GrowBuf<int> alt_tok;                  // [steps][rows of the run][n_alt of the run]
+  GrowBuf<float> alt_lp;
+  GrowBuf<uint8_t> fin_path;             // [R][FIN_CAP][NT + 1]
+  GrowBuf<int> alt_out_tok;              // the gather's output: [returned hypotheses][budget + 1][n_alt]
+  GrowBuf<float> alt_out_lp;
+  GrowBuf<fwd::AltHyp> alt_hyps;
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -567,11 +575,13 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   }
   if (s.beam_tail) {
     ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
+    const bool alt = gp.n_alt > 0;   // (run_alt_ensure has sized the buffers for this run)
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
-                               g->cand_tok, g->cand_lp, g->smp_tab);
+                               g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
+                               alt ? g->alt_lp.p : nullptr);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
                             g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->cand_lp,
-                            g->lphist2, g->fin_lp, s.ptab);
+                            g->lphist2, g->fin_lp, s.ptab, alt ? g->fin_path.p : nullptr);
     fwd::launch_step_advance(st, g->d_step);
   }
   return FW_OK;
@@ -687,6 +697,14 @@ struct GenRequest {
   int32_t* out_ids; int32_t* out_lens; float* out_scores; float* out_no_speech;
   float* out_token_logprobs = nullptr;   // [B, num_hypotheses, max_length] | null
   float* out_end_logprobs = nullptr;     // [B, num_hypotheses] | null
+  // alternatives: all four, or none with n_alt == 0 (fw_generate_alt checks).  NOT part of what must agree between the calls
+  // of a run: the run records the largest n_alt of its calls, each call receives its own first n_alt entries — extraction
+  // is a total order, so the first n of the top m are the top n.
+  int n_alt = 0;
+  int32_t* out_alt_ids = nullptr;        // [B, num_hypotheses, max_length, n_alt]
+  float* out_alt_logprobs = nullptr;
+  int32_t* out_end_alt_ids = nullptr;    // [B, num_hypotheses, n_alt]
+  float* out_end_alt_logprobs = nullptr;
   bool sampling;
   int with_ts = 1, sot_pos = -1;   // from the prompt: no <|notimestamps|> -> timestamp rules; position of <sot>
   int rc = FW_OK;
@@ -807,11 +825,13 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   // reach - P_c.  P is the SHORTEST prompt (the run lasts reach - P steps), Pmax the longest (the prompt forward runs to
   // Pmax - 1).  A uniform run (P == Pmax, one <sot> position) takes exactly the path it always took.
   pl.P = pl.Pmax = r0.P; pl.B = 0; pl.ragged = pl.want_nsp = false;
+  int n_alt = 0;   // the largest of the run's calls: what the run records (0: nothing, the kernels and graph keys of always)
   for (const GenRequest* r : reqs) {
     pl.P = std::min(pl.P, r->P); pl.Pmax = std::max(pl.Pmax, r->P);
     pl.ragged = pl.ragged || r->P != r0.P || r->sot_pos != r0.sot_pos;
     pl.want_nsp = pl.want_nsp || r->o->return_no_speech_prob;
     pl.B += r->B;
+    n_alt = std::max(n_alt, r->n_alt);
   }
   pl.nh = o->num_hypotheses; pl.ml = o->max_length;
   const int P = pl.P, Pmax = pl.Pmax, B = pl.B;
@@ -836,6 +856,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.ctx = ctx; gp.cache_rows = Bx * K;
   gp.ragged = ragged ? 1 : 0; gp.reach = ragged ? reach : 0;   // (part of the step graph's key)
   gp.sample = sampling ? 1 : 0;
+  gp.n_alt = n_alt;
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
   gp.inv_temp = 1.0f; gp.seed_lo = 0; gp.seed_hi = 0;
@@ -853,6 +874,25 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
   gp.n_sup_begin = c.n_suppress_begin;
   for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
+  return FW_OK;
+}
+
+// Alternatives: the lane's buffers for a run that records n_alt > 0 per row and step, allocated by the first such run and
+// grown by replacement when a later one needs more (the lane is idle: its mutex is held and its stream was waited for).  A
+// cached step graph holds the old pointers: the graphs that record alternatives go with them.  Runs that record none
+// allocate nothing and touch nothing here.
+static int run_alt_ensure(DecodeLane* lane, const RunPlan& pl) {
+  GenWorkspace* g = lane->gen;
+  if (pl.gp.n_alt <= 0) return FW_OK;
+  const int64_t n_alt = (int64_t)pl.budget * pl.gp.R * pl.gp.n_alt;
+  const int64_t n_path = (int64_t)g->R * FIN_CAP * (g->NT + 1);
+  if (n_alt > g->alt_tok.cap || n_alt > g->alt_lp.cap || n_path > g->fin_path.cap) {
+    FW_HIP(hipStreamSynchronize(lane->stream));
+    for (GraphSlot& gs : g->graphs)
+      if (gs.exec && gs.key.n_alt > 0) { (void)hipGraphExecDestroy(gs.exec); gs.exec = nullptr; gs.stamp = 0; }
+    int rc;
+    if ((rc = g->alt_tok.ensure(n_alt)) || (rc = g->alt_lp.ensure(n_alt)) || (rc = g->fin_path.ensure(n_path))) return rc;
+  }
   return FW_OK;
 }
 
@@ -1058,6 +1098,11 @@ static int run_finalize(DecodeLane* lane, const std::vector<GenRequest*>& reqs, 
     FW_HIP(hipMemcpyAsync(fin_lp.data(), g->fin_lp, fin_lp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   FW_HIP(hipStreamSynchronize(st));
+  // alternatives: the returned hypotheses of the calls that asked, in the order they are met below; one gather launch
+  // after the selection, then every call copies its own first n_alt of the run's
+  std::vector<fwd::AltHyp> alt_hyps;
+  std::vector<std::pair<GenRequest*, size_t>> alt_dst;
+  const int n_alt_run = pl.gp.n_alt, alt_T = pl.budget;
   int cb = 0;   // first chunk of the request inside the run
   for (GenRequest* r : reqs) {
     for (int b = 0; b < r->B; ++b) {
@@ -1083,9 +1128,44 @@ static int run_finalize(DecodeLane* lane, const std::vector<GenRequest*>& reqs, 
         if (r->out_token_logprobs)
           memcpy(r->out_token_logprobs + ((size_t)b * nh + h) * ml, &fin_lp[f * (NT + 1)], (size_t)len * sizeof(float));
         if (r->out_end_logprobs) r->out_end_logprobs[b * nh + h] = fin_lp[f * (NT + 1) + NT];
+        if (r->n_alt > 0) {
+          // recorded on <eot> at step fin_len < the chunk's budget, or cut at the last step with fin_len == budget
+          const int budget_c = max_new_tokens(std::min(ml, (int)NT), r->P);
+          alt_hyps.push_back({hyps[h].first, hyps[h].second, len, fin_len[f] < budget_c ? fin_len[f] : -1});
+          alt_dst.push_back({r, (size_t)b * nh + h});
+        }
       }
     }
     cb += r->B;
+  }
+  if (alt_hyps.empty()) return FW_OK;
+  const int n_hyp = (int)alt_hyps.size();
+  const size_t per_hyp = (size_t)(alt_T + 1) * n_alt_run;
+  int rc;
+  if ((rc = g->alt_hyps.ensure(n_hyp)) || (rc = g->alt_out_tok.ensure((int64_t)(n_hyp * per_hyp))) ||
+      (rc = g->alt_out_lp.ensure((int64_t)(n_hyp * per_hyp))))
+    return rc;
+  std::vector<int> a_tok(n_hyp * per_hyp);
+  std::vector<float> a_lp(n_hyp * per_hyp);
+  FW_HIP(hipMemcpyAsync(g->alt_hyps.p, alt_hyps.data(), n_hyp * sizeof(fwd::AltHyp), hipMemcpyHostToDevice, st));
+  fwd::launch_alt_gather(st, g->alt_tok.p, g->alt_lp.p, g->fin_path.p, g->alt_hyps.p, n_hyp, pl.gp.R, pl.K, (int)NT,
+                         n_alt_run, alt_T, g->alt_out_tok.p, g->alt_out_lp.p);
+  FW_HIP(hipMemcpyAsync(a_tok.data(), g->alt_out_tok.p, a_tok.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  FW_HIP(hipMemcpyAsync(a_lp.data(), g->alt_out_lp.p, a_lp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  FW_HIP(hipStreamSynchronize(st));
+  if ((rc = check_launch("alternatives gather"))) return rc;
+  for (size_t ih = 0; ih < alt_hyps.size(); ++ih) {   // hypothesis ih belongs to slot alt_dst[ih] of its call
+    GenRequest* r = alt_dst[ih].first;
+    const size_t slot = alt_dst[ih].second;   // b * nh + h
+    const int n = r->n_alt, len = alt_hyps[ih].len;
+    const int* stok = &a_tok[ih * per_hyp];
+    const float* slp = &a_lp[ih * per_hyp];
+    for (int t = 0; t <= len; ++t) {   // t == len: the end slot, row alt_T of the gather's output
+      const size_t src = (size_t)(t < len ? t : alt_T) * n_alt_run;
+      int32_t* oi = t < len ? r->out_alt_ids + (slot * ml + t) * n : r->out_end_alt_ids + slot * n;
+      float* ol = t < len ? r->out_alt_logprobs + (slot * ml + t) * n : r->out_end_alt_logprobs + slot * n;
+      for (int j = 0; j < n; ++j) { oi[j] = stok[src + j]; ol[j] = slp[src + j]; }
+    }
   }
   return FW_OK;
 }
@@ -1099,6 +1179,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   FW_HIP(hipSetDevice(m->device));
   PoolHold hold{m->xpool, {}, lane->stream};
   std::vector<int> slots, ptok;
+  if ((rc = run_alt_ensure(lane, pl))) return rc;
   if ((rc = run_acquire_blocks(m, lane, reqs, hold, slots))) return rc;
   if ((rc = run_init_state(m, lane, reqs, pl, slots, ptok))) return rc;
   if ((rc = run_prompt_forward(m, lane, pl, ptok))) return rc;
@@ -1276,8 +1357,24 @@ int32_t fw_generate(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts
 int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                        int32_t B, const fw_gen_opts* o, int32_t* out_ids, int32_t* out_lens, float* out_scores,
                        float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs) {
+  return fw_generate_alt(fm, enc_t, prompts, prompt_offsets, B, o, 0, out_ids, out_lens, out_scores, out_no_speech,
+                         out_token_logprobs, out_end_logprobs, nullptr, nullptr, nullptr, nullptr);
+}
+
+int32_t fw_generate_alt(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                        int32_t B, const fw_gen_opts* o, int32_t n_alt, int32_t* out_ids, int32_t* out_lens,
+                        float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
+                        int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                        float* out_end_alt_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
+  FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
+  if (n_alt == 0)
+    FW_CHECK_ARG(!out_alt_ids && !out_alt_logprobs && !out_end_alt_ids && !out_end_alt_logprobs,
+                 "n_alt == 0 takes no alternative arrays");
+  else
+    FW_CHECK_ARG(out_alt_ids && out_alt_logprobs && out_end_alt_ids && out_end_alt_logprobs,
+                 "n_alt > 0 needs all four alternative arrays");
   Model* m = &fm->impl;
   Model* dm = decoder_of(m);
   const Tensor* enc = &enc_t->impl;
@@ -1315,11 +1412,20 @@ int32_t fw_generate_lp(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   for (int b = 0; b < B; ++b) out_no_speech[b] = 0.f;
   if (out_token_logprobs) std::fill(out_token_logprobs, out_token_logprobs + (size_t)B * nh * o->max_length, 0.f);
   if (out_end_logprobs) std::fill(out_end_logprobs, out_end_logprobs + (size_t)B * nh, 0.f);
+  if (n_alt > 0) {   // (id -1, log-prob 0): entries past a hypothesis' length, and the end slot of one cut at the budget
+    const size_t n_tok = (size_t)B * nh * o->max_length * n_alt, n_end = (size_t)B * nh * n_alt;
+    std::fill(out_alt_ids, out_alt_ids + n_tok, -1);
+    std::fill(out_alt_logprobs, out_alt_logprobs + n_tok, 0.f);
+    std::fill(out_end_alt_ids, out_end_alt_ids + n_end, -1);
+    std::fill(out_end_alt_logprobs, out_end_alt_logprobs + n_end, 0.f);
+  }
 
   GenRequest req;
   req.enc = enc; req.prompts = prompts; req.prompt_offsets = prompt_offsets; req.B = B; req.P = P; req.o = o;
   req.out_ids = out_ids; req.out_lens = out_lens; req.out_scores = out_scores; req.out_no_speech = out_no_speech;
   req.out_token_logprobs = out_token_logprobs; req.out_end_logprobs = out_end_logprobs;
+  req.n_alt = n_alt; req.out_alt_ids = out_alt_ids; req.out_alt_logprobs = out_alt_logprobs;
+  req.out_end_alt_ids = out_end_alt_ids; req.out_end_alt_logprobs = out_end_alt_logprobs;
   req.sampling = sampling;
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the

@@ -877,7 +877,9 @@ int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows
 // of every row are returned.
 // Every history id is checked in [0, V) before anything is allocated or launched: the repetition penalty and the n-gram
 // rule use them as indices into the row (a wrong test gets FW_EINVAL, never a device fault).
-struct RulesEx { const int32_t* done; float* logits_io; };
+// alt (fw_test_logits_rules_alt): n_alt in [1, FW_MAX_ALTERNATIVES] and alt_tok / alt_lp [R][n_alt] IN / OUT — the rows' slab
+// [n][.][.] of a step-major device buffer of n + 1 steps, which is what the kernel indexes with its step counter.
+struct RulesEx { const int32_t* done; float* logits_io; int32_t n_alt = 0; int32_t* alt_tok = nullptr; float* alt_lp = nullptr; };
 static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                                  const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
                                  int32_t* cand_tok, float* cand_lp, const fwd::SmpRow* smp = nullptr,
@@ -894,10 +896,13 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
                  hist[i], c.n_vocab);
   if (ex && ex->done)
     for (int b = 0; b < R / K; ++b) FW_CHECK_ARG(ex->done[b] == 0 || ex->done[b] == 1, "done[%d] = %d is not 0 / 1", b, ex->done[b]);
+  const int n_alt = ex ? ex->n_alt : 0;
+  FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
   FW_HIP(hipSetDevice(m->device));
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.B = R / K; gp.K = K; gp.R = R; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx;
+  gp.n_alt = n_alt;
   gp.sample = sampling ? 1 : 0;
   gp.inv_temp = 1.0f;   // (sampling: temperature and seed per row, from the table below — as in a decode run)
   gp.with_ts = with_timestamps ? 1 : 0;
@@ -951,10 +956,21 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
                    : fwd::SmpRow{1.0f / o->sampling_temperature, (unsigned)(o->seed & 0xffffffffu), (unsigned)(o->seed >> 32), 0};
     if ((rc = db.upload(&d_smp, tab.data(), tab.size()))) return rc;
   }
-  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp);
+  int* d_at = nullptr;
+  float* d_al = nullptr;
+  const size_t n_slab = (size_t)R * n_alt;   // the slab of step n; the steps before it are never touched
+  if (n_alt > 0) {
+    if ((rc = db.alloc(&d_at, (size_t)(n + 1) * n_slab)) || (rc = db.alloc(&d_al, (size_t)(n + 1) * n_slab))) return rc;
+    FW_HIP(hipMemcpy(d_at + (size_t)n * n_slab, ex->alt_tok, n_slab * sizeof(int), hipMemcpyHostToDevice));
+    FW_HIP(hipMemcpy(d_al + (size_t)n * n_slab, ex->alt_lp, n_slab * sizeof(float), hipMemcpyHostToDevice));
+  }
+  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp, d_at, d_al);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
   if ((rc = download(hv.data(), d_cv, NC)) || (rc = download(ht.data(), d_ct, NC))) return rc;
+  if (n_alt > 0 && ((rc = download(ex->alt_tok, d_at + (size_t)n * n_slab, n_slab)) ||
+                    (rc = download(ex->alt_lp, d_al + (size_t)n * n_slab, n_slab))))
+    return rc;
   if (cand_lp && (rc = download(hl.data(), d_cl, NC))) return rc;
   if (ex && ex->logits_io && (rc = download(ex->logits_io, d_lg, (size_t)R * c.n_vocab))) return rc;
   const int C = ex ? 32 : sampling ? 1 : 2 * K;
@@ -1020,6 +1036,25 @@ int32_t fw_test_logits_rules_ex(fw_model* fm, float* logits, int32_t R, const in
     if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
   }
   const RulesEx ex{done, logits};
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp,
+                           tab_given ? tab.data() : nullptr, &ex);
+}
+
+// fw_test_logits_rules_ex plus alternatives (include/fwamd_test.h): the ALT instantiations of the rules kernel.
+int32_t fw_test_logits_rules_alt(fw_model* fm, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                 const fw_gen_opts* o, int32_t with_timestamps, const int32_t* done, const float* inv_temp,
+                                 const uint64_t* seed, const int32_t* row0, float* cand_val, int32_t* cand_tok,
+                                 float* cand_lp, int32_t n_alt, int32_t* alt_tok, float* alt_lp) {
+  FW_CHECK_ARG(o && cand_lp && alt_tok && alt_lp && R >= 1, "null argument");
+  FW_CHECK_ARG(n_alt >= 1 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [1, %d]", n_alt, FW_MAX_ALTERNATIVES);
+  const bool tab_given = inv_temp || seed || row0;
+  FW_CHECK_ARG(!tab_given || (inv_temp && seed && row0), "the sampling table needs inv_temp, seed and row0 together");
+  std::vector<fwd::SmpRow> tab;
+  if (tab_given) {
+    FW_CHECK_ARG(o->beam_size == 1 && o->sampling_topk == 0, "the options must select sampling (beam_size 1, sampling_topk 0)");
+    if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
+  }
+  const RulesEx ex{done, logits, n_alt, alt_tok, alt_lp};
   return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp,
                            tab_given ? tab.data() : nullptr, &ex);
 }
@@ -1104,12 +1139,17 @@ int32_t fw_test_graph_captures(const fw_model* fm, int64_t* out) {
 // ONE launch of dec_beam_update_kernel (fwd::launch_beam_update) for B chunks of K beams at decode step `step`.
 // (lp: the log-prob arrays of fw_test_dec_beam_update_lp; without them the kernel gets null pointers and skips those stores)
 struct BeamLpArgs { const float* cand_lp; const float* lphist; float* fin_lp; float* lphist2; };
+// (alt: fw_test_dec_beam_update_alt.  ptab [B] | null: a RAGGED launch, chunk c with a prompt of ptab[c] tokens; P must be
+//  the shortest of them, the run reaches P + budget, kvidx is [R][max(ptab) - 1 + step] and chunk c's rows use the first
+//  ptab[c] - 1 + step bytes of theirs.  fin_path [B][FIN_CAP][NT + 1] IN / OUT | null: the kernel gets a null pointer.)
+struct BeamAltArgs { const int32_t* ptab; uint8_t* fin_path; };
 static int32_t beam_update_hook(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
                                 int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
                                 const int32_t* cand_tok, const int32_t* hist, const uint8_t* kvidx, const float* cum,
                                 int32_t sentinel_i, float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin,
                                 int32_t* fin_tok, int32_t* fin_len, float* fin_score, float* fin_cum, int32_t* hist2,
-                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok, const BeamLpArgs* lp) {
+                                uint8_t* kvidx2, float* cum2, int32_t* cur_tok, const BeamLpArgs* lp,
+                                const BeamAltArgs* alt = nullptr) {
   FW_CHECK_ARG(fm && cand_val && cand_tok && cum && done && n_done && n_fin && fin_tok && fin_len && fin_score &&
                    fin_cum && hist2 && kvidx2 && cum2 && cur_tok, "null argument");
   FW_CHECK_ARG(K >= 1 && K <= 16, "need 1 <= K <= 16 (K = %d)", K);
@@ -1118,19 +1158,30 @@ static int32_t beam_update_hook(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   FW_CHECK_ARG(P >= 1 && step >= 0 && step < NT && (int64_t)P - 1 + step < NT,
                "need P >= 1, 0 <= step < NT and P - 1 + step < NT (P = %d, step = %d, NT = %d)", P, step, NT);
   FW_CHECK_ARG(eot >= 0 && eot < V && max_fin >= 1 && budget >= 1 && lp_pow == lp_pow, "bad eot / max_fin / budget / lp_pow");
-  const int R = B * K, C = 2 * K, pos = P - 1 + step;
+  const int R = B * K, C = 2 * K;
+  const int32_t* ptab = alt ? alt->ptab : nullptr;
+  int Pmax = P;
+  for (int c = 0; c < B && ptab; ++c) {   // every chunk live at this step: its position below what the run reaches
+    FW_CHECK_ARG(ptab[c] >= P && (int64_t)ptab[c] - 1 + step < std::min<int64_t>(NT, (int64_t)P + budget),
+                 "ptab[%d] = %d: need P <= ptab[c] and ptab[c] - 1 + step < min(NT, P + budget)", c, ptab[c]);
+    Pmax = std::max(Pmax, ptab[c]);
+  }
+  const int pos = Pmax - 1 + step;   // bytes per kvidx row (ragged: of the longest prompt)
   FW_CHECK_ARG((step == 0 || hist) && (pos == 0 || kvidx), "null history / slot table");
   FW_CHECK_ARG(!lp || (lp->cand_lp && lp->fin_lp && lp->lphist2 && (step == 0 || lp->lphist)), "null log-prob argument");
   for (int i = 0; i < R * C; ++i)
     FW_CHECK_ARG(cand_tok[i] >= 0 && cand_tok[i] < V, "cand_tok[%d] = %d outside [0, %d)", i, cand_tok[i], V);
-  for (int64_t i = 0; i < (int64_t)R * pos; ++i)
+  for (int64_t i = 0; i < (int64_t)R * pos; ++i) {   // (ragged: the bytes a row uses)
+    if (ptab && i % pos >= ptab[i / pos / K] - 1 + step) continue;
     FW_CHECK_ARG(kvidx[i] < K, "kvidx[%lld] = %d is not a beam of %d", (long long)i, (int)kvidx[i], K);
+  }
   for (int c = 0; c < B; ++c)
     FW_CHECK_ARG(n_fin[c] >= 0 && n_fin[c] <= FIN_CAP, "n_fin[%d] = %d outside [0, %d]", c, n_fin[c], FIN_CAP);
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.B = B; gp.K = K; gp.R = R; gp.P = P; gp.budget = budget; gp.max_fin = max_fin; gp.V = V; gp.n_text_ctx = NT;
   gp.lp_pow = lp_pow; gp.eot = eot; gp.kv_div = 1;
+  if (ptab) { gp.ragged = 1; gp.reach = P + budget; }
   // both parity halves: the inputs go to half step & 1, everything else holds the caller's sentinel
   const int cur = step & 1;
   const size_t n_state = 2 * (size_t)R * NT;
@@ -1145,7 +1196,8 @@ static int32_t beam_update_hook(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   }
   for (int r = 0; r < R; ++r) {
     for (int q = 0; q < step; ++q) h2[((size_t)cur * R + r) * NT + q] = hist[(size_t)r * step + q];
-    for (int q = 0; q < pos; ++q) k2[((size_t)cur * R + r) * NT + q] = kvidx[(size_t)r * pos + q];
+    const int pos_r = ptab ? ptab[r / K] - 1 + step : pos;
+    for (int q = 0; q < pos_r; ++q) k2[((size_t)cur * R + r) * NT + q] = kvidx[(size_t)r * pos + q];
     c2[(size_t)cur * R + r] = cum[r];
     for (int j = 0; j < C; ++j) {   // the kernel's row stride of 32 candidates
       cv[(size_t)r * 32 + j] = cand_val[(size_t)r * C + j];
@@ -1171,10 +1223,15 @@ static int32_t beam_update_hook(fw_model* fm, int32_t B, int32_t K, int32_t NT, 
   if (lp && ((rc = db.upload(&d_cl, cl.data(), cl.size())) || (rc = db.upload(&d_l2, l2.data(), n_state)) ||
              (rc = db.upload(&d_flp, lp->fin_lp, n_f * (NT + 1)))))
     return rc;
+  int* d_ptab = nullptr;
+  uint8_t* d_path = nullptr;
+  if (ptab && (rc = db.upload(&d_ptab, ptab, (size_t)B))) return rc;
+  if (alt && alt->fin_path && (rc = db.upload(&d_path, (const uint8_t*)alt->fin_path, n_f * (NT + 1)))) return rc;
   fwd::launch_beam_update(nullptr, gp, d_cv, d_ct, d_h2, d_c2, d_k2, d_cur, d_step, d_done, d_ndone, d_nfin, d_ft, d_fl,
-                          d_fs, d_fc, d_cl, d_l2, d_flp);
+                          d_fs, d_fc, d_cl, d_l2, d_flp, d_ptab, d_path);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
+  if (d_path && (rc = download(alt->fin_path, d_path, n_f * (NT + 1)))) return rc;
   if ((rc = download(hist2, d_h2, n_state)) || (rc = download(kvidx2, d_k2, n_state)) ||
       (rc = download(cum2, d_c2, c2.size())) || (rc = download(cur_tok, d_cur, (size_t)R)) ||
       (rc = download(done, d_done, (size_t)B)) || (rc = download(n_done, d_ndone, 1)) ||
@@ -1209,6 +1266,68 @@ int32_t fw_test_dec_beam_update_lp(fw_model* fm, int32_t B, int32_t K, int32_t N
   return beam_update_hook(fm, B, K, NT, V, P, step, budget, max_fin, lp_pow, eot, cand_val, cand_tok, hist, kvidx, cum,
                           sentinel_i, sentinel_f, done, n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, hist2, kvidx2,
                           cum2, cur_tok, &lp);
+}
+
+int32_t fw_test_dec_beam_update_alt(fw_model* fm, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                    int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                    const int32_t* cand_tok, const float* cand_lp, const int32_t* hist,
+                                    const float* lphist, const uint8_t* kvidx, const float* cum, int32_t sentinel_i,
+                                    float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin, int32_t* fin_tok,
+                                    int32_t* fin_len, float* fin_score, float* fin_cum, float* fin_lp, int32_t* hist2,
+                                    float* lphist2, uint8_t* kvidx2, float* cum2, int32_t* cur_tok, const int32_t* ptab,
+                                    uint8_t* fin_path) {
+  FW_CHECK_ARG(cand_lp && fin_lp && lphist2, "null argument");
+  const BeamLpArgs lp{cand_lp, lphist, fin_lp, lphist2};
+  const BeamAltArgs alt{ptab, fin_path};
+  return beam_update_hook(fm, B, K, NT, V, P, step, budget, max_fin, lp_pow, eot, cand_val, cand_tok, hist, kvidx, cum,
+                          sentinel_i, sentinel_f, done, n_done, n_fin, fin_tok, fin_len, fin_score, fin_cum, hist2, kvidx2,
+                          cum2, cur_tok, &lp, &alt);
+}
+
+// ONE launch of the alternatives gather (fwd::launch_alt_gather) on caller-provided step-major alt_tok / alt_lp
+// [steps][R][n_alt], paths fin_path [R / K][FIN_CAP][NT + 1] and n_hyp hypotheses (chunk, finished slot, length, closing
+// step | -1); out_tok / out_lp [n_hyp][T + 1][n_alt] IN / OUT.  Everything the kernel turns into an index is checked first.
+int32_t fw_test_alt_gather(fw_model* fm, const int32_t* alt_tok, const float* alt_lp, int32_t steps, int32_t R, int32_t K,
+                           int32_t NT, int32_t n_alt, const uint8_t* fin_path, int32_t n_hyp, const int32_t* hyp_chunk,
+                           const int32_t* hyp_fin, const int32_t* hyp_len, const int32_t* hyp_end, int32_t T,
+                           int32_t* out_tok, float* out_lp) {
+  FW_CHECK_ARG(fm && alt_tok && alt_lp && fin_path && hyp_chunk && hyp_fin && hyp_len && hyp_end && out_tok && out_lp,
+               "null argument");
+  FW_CHECK_ARG(n_alt >= 1 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [1, %d]", n_alt, FW_MAX_ALTERNATIVES);
+  FW_CHECK_ARG(K >= 1 && K <= 16 && R >= K && R <= 4096 && R % K == 0, "need 1 <= K <= 16, R a multiple of K, R <= 4096");
+  FW_CHECK_ARG(NT >= 1 && NT <= 4096 && steps >= 1 && steps <= NT + 1 && T >= 0 && T <= NT && n_hyp >= 1 && n_hyp <= 65535,
+               "need 1 <= NT <= 4096, 1 <= steps <= NT + 1, 0 <= T <= NT, 1 <= n_hyp <= 65535");
+  const int B = R / K;
+  std::vector<fwd::AltHyp> hyps((size_t)n_hyp);
+  for (int i = 0; i < n_hyp; ++i) {
+    FW_CHECK_ARG(hyp_chunk[i] >= 0 && hyp_chunk[i] < B && hyp_fin[i] >= 0 && hyp_fin[i] < FIN_CAP,
+                 "hypothesis %d: chunk %d / finished slot %d out of range", i, hyp_chunk[i], hyp_fin[i]);
+    FW_CHECK_ARG(hyp_len[i] >= 0 && hyp_len[i] <= std::min(T, steps) && hyp_end[i] >= -1 && hyp_end[i] < steps,
+                 "hypothesis %d: length %d / closing step %d out of range", i, hyp_len[i], hyp_end[i]);
+    const uint8_t* path = fin_path + ((size_t)hyp_chunk[i] * FIN_CAP + hyp_fin[i]) * (NT + 1);
+    for (int q = 0; q < steps; ++q)
+      if (q < hyp_len[i] || q == hyp_end[i])
+        FW_CHECK_ARG(path[q] < K, "hypothesis %d: path byte %d = %d is not a beam of %d", i, q, (int)path[q], K);
+    hyps[i] = {hyp_chunk[i], hyp_fin[i], hyp_len[i], hyp_end[i]};
+  }
+  Model* m = &fm->impl;
+  FW_HIP(hipSetDevice(m->device));
+  HookBufs db;
+  const size_t n_a = (size_t)steps * R * n_alt, n_o = (size_t)n_hyp * (T + 1) * n_alt;
+  int *d_at, *d_ot;
+  float *d_al, *d_ol;
+  uint8_t* d_path;
+  fwd::AltHyp* d_h;
+  int rc;
+  if ((rc = db.upload(&d_at, (const int*)alt_tok, n_a)) || (rc = db.upload(&d_al, alt_lp, n_a)) ||
+      (rc = db.upload(&d_path, fin_path, (size_t)B * FIN_CAP * (NT + 1))) || (rc = db.upload(&d_h, hyps.data(), hyps.size())) ||
+      (rc = db.upload(&d_ot, (const int*)out_tok, n_o)) || (rc = db.upload(&d_ol, (const float*)out_lp, n_o)))
+    return rc;
+  fwd::launch_alt_gather(nullptr, d_at, d_al, d_path, d_h, n_hyp, R, K, NT, n_alt, T, d_ot, d_ol);
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipDeviceSynchronize());
+  if ((rc = download(out_tok, d_ot, n_o))) return rc;
+  return download(out_lp, d_ol, n_o);
 }
 
 // ONE launch of dec_embed_kernel (fwd::launch_embed): x [rows][d] and the fragment-major copy, un-permuted on the host

@@ -78,13 +78,38 @@ class ScoredSegment(Segment):
     token_logprobs: List[float]
 
 
-def _slice_token_logprobs(subs: List[dict], logprobs: List[float]) -> None:
+@dataclass
+class AlternativesSegment(ScoredSegment):
+    """what transcribe(token_alternatives=N) yields: a ScoredSegment plus token_alternatives[i] = the N most likely
+    (id, log-prob) pairs of the distribution tokens[i] was chosen from, log-prob descending then id ascending ((0, -inf)
+    where the rules left fewer than N ids)"""
+    token_alternatives: List[List[Tuple[int, float]]]
+
+
+def _slice_token_logprobs(subs: List[dict], logprobs: List[float], key: str = "token_logprobs") -> None:
     """gives every sub-segment dict of one chunk the log-probs of its tokens: _split_segments_by_timestamps cuts
-    consecutive slices of the chunk's tokens from index 0 on (what follows the last cut belongs to no sub-segment)"""
+    consecutive slices of the chunk's tokens from index 0 on (what follows the last cut belongs to no sub-segment).
+    key="token_alternatives": the same cut of the chunk's per-token alternatives."""
     pos = 0
     for s in subs:
-        s["token_logprobs"] = list(logprobs[pos:pos + len(s["tokens"])])
+        s[key] = list(logprobs[pos:pos + len(s["tokens"])])
         pos += len(s["tokens"])
+
+
+def _slice_token_values(subs: List[dict], logprobs: List[float], alternatives: Optional[list] = None) -> None:
+    """the per-token values a token_logprobs / token_alternatives call attaches to the sub-segments of one chunk"""
+    _slice_token_logprobs(subs, logprobs)
+    if alternatives is not None:
+        _slice_token_logprobs(subs, alternatives, "token_alternatives")
+
+
+def _value_keywords(token_logprobs: bool, token_alternatives: int, logprobs_key: str = "token_logprobs",
+                    alternatives_key: str = "token_alternatives") -> dict:
+    """the keywords a call passes down for its per-token values — only those it was asked for, so that a layer below that
+    does not know them (a scripted backend, CTranslate2 behind the shim) never sees them otherwise"""
+    if token_alternatives:
+        return {alternatives_key: int(token_alternatives)}
+    return {logprobs_key: True} if token_logprobs else {}
 
 
 @dataclass
@@ -155,11 +180,15 @@ def _avg_logprob(result, length_penalty: float) -> float:
     return result.scores[0] * (n ** length_penalty) / (n + 1)
 
 
-def _make_segment(values: dict, token_logprobs: Optional[List[float]] = None) -> Segment:
-    """a Segment, or with token_logprobs (what a token_logprobs=True call attaches to its sub-segments) a ScoredSegment"""
+def _make_segment(values: dict, token_logprobs: Optional[List[float]] = None,
+                  token_alternatives: Optional[list] = None) -> Segment:
+    """a Segment, or with token_logprobs (what a token_logprobs=True call attaches to its sub-segments) a ScoredSegment,
+    or with token_alternatives as well (a token_alternatives=N call) an AlternativesSegment"""
     if token_logprobs is None:
         return Segment(**values)
-    return ScoredSegment(token_logprobs=token_logprobs, **values)
+    if token_alternatives is None:
+        return ScoredSegment(token_logprobs=token_logprobs, **values)
+    return AlternativesSegment(token_logprobs=token_logprobs, token_alternatives=token_alternatives, **values)
 
 
 def pad_or_trim(array: np.ndarray, length: int = 3000, *, axis: int = -1) -> np.ndarray:
@@ -454,13 +483,17 @@ class WhisperModel:
                    clip_timestamps: Union[str, List[float]] = "0",
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                   vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None):
+                   vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
+                   token_alternatives: int = 0):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
         vad.get_speech_timestamps with precomputed window probabilities instead of running the Silero network.
         token_logprobs=True (not in the reference): every segment is a ScoredSegment, whose token_logprobs are those of
         the decode the fallback ladder kept; every other field is what the call without the keyword yields.
+        token_alternatives=N (not in the reference; 1 <= N <= backend.MAX_ALTERNATIVES): every segment is an
+        AlternativesSegment, a ScoredSegment whose token_alternatives[i] lists the N most likely (id, log-prob) pairs at
+        the position of tokens[i], again those of the decode the ladder kept.
         sampling_seed (not in the reference): makes the sampled attempts of the temperature fallback reproducible.  The
         attempt at rung t of the ladder for the window at frame `seek` samples with backend.attempt_seed(sampling_seed,
         seek, t): the same recording with the same seed gives the same transcript whatever else the model decodes before
@@ -504,7 +537,7 @@ class WhisperModel:
             args, tokenizer, multilingual=multilingual,
             temperatures=(temperature if isinstance(temperature, (list, tuple)) else [temperature]))
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
-                                          **(dict(token_logprobs=True) if token_logprobs else {}),
+                                          **_value_keywords(token_logprobs, token_alternatives),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
@@ -571,7 +604,8 @@ class WhisperModel:
 
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
-                          token_logprobs: bool = False, sampling_seed: Optional[int] = None):
+                          token_logprobs: bool = False, sampling_seed: Optional[int] = None,
+                          token_alternatives: int = 0):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -626,7 +660,7 @@ class WhisperModel:
                 prompt = self.get_prompt(tokenizer, previous_tokens, without_timestamps=options.without_timestamps,
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
-                    encoder_output, prompt, tokenizer, options, **(dict(token_logprobs=True) if token_logprobs else {}),
+                    encoder_output, prompt, tokenizer, options, **_value_keywords(token_logprobs, token_alternatives),
                     **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
@@ -641,8 +675,9 @@ class WhisperModel:
                 current, seek, single_timestamp_ending = self._split_segments_by_timestamps(
                     tokenizer=tokenizer, tokens=tokens, time_offset=time_offset, segment_size=segment_size,
                     segment_duration=segment_duration, seek=seek)
-                if token_logprobs:
-                    _slice_token_logprobs(current, result.token_logprobs[0])
+                if token_logprobs or token_alternatives:
+                    _slice_token_values(current, result.token_logprobs[0],
+                                        result.token_alternatives[0] if token_alternatives else None)
 
                 if options.word_timestamps:
                     self.add_word_timestamps([current], tokenizer, encoder_output, segment_size,
@@ -667,7 +702,7 @@ class WhisperModel:
                                   tokens=seg["tokens"], temperature=temperature, avg_logprob=avg_logprob,
                                   compression_ratio=compression_ratio, no_speech_prob=result.no_speech_prob,
                                   words=([Word(**w) for w in seg["words"]] if options.word_timestamps else None))
-                    yield _make_segment(values, seg.get("token_logprobs"))
+                    yield _make_segment(values, seg.get("token_logprobs"), seg.get("token_alternatives"))
 
                 if not options.condition_on_previous_text or temperature > options.prompt_reset_on_temperature:
                     prompt_reset_since = len(all_tokens)
@@ -678,7 +713,7 @@ class WhisperModel:
 
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
                                options: TranscriptionOptions, token_logprobs: bool = False,
-                               sampling_seed: Optional[int] = None, seek: int = 0):
+                               sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
@@ -704,7 +739,7 @@ class WhisperModel:
                 max_length=max_length, return_scores=True, return_no_speech_prob=True,
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
                 max_initial_timestamp_index=max_initial_timestamp_index, **mode,
-                **(dict(return_token_logprobs=True) if token_logprobs else {}))[0]
+                **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))[0]
             avg_logprob = _avg_logprob(result, options.length_penalty)
             compression_ratio = get_compression_ratio(tokenizer.decode(result.sequences_ids[0]).strip())
             attempt = (result, avg_logprob, temperature, compression_ratio)
@@ -911,10 +946,13 @@ class BatchedInferencePipeline:
 
     # ---- one batch: encode + generate ---------------------------------------------------
     def generate_segment_batched(self, features, tokenizer: Tokenizer, options: TranscriptionOptions,
-                                 audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False):
+                                 audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False,
+                                 token_alternatives: int = 0):
         """features: [B, n_mels, 3000] float32, or None when `audio_chunks` is given (fused resident
         PCM -> log-mel -> encoder path; the features never leave HBM).  token_logprobs: every output dict also carries
-        the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`)."""
+        the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`);
+        token_alternatives=N: those, and the N most likely (id, log-prob) pairs per token (`token_alternatives`) and at
+        the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget)."""
         m = self.model
         batch_size = len(audio_chunks) if audio_chunks is not None else features.shape[0]
         prompt = m.get_prompt(tokenizer,
@@ -938,13 +976,15 @@ class BatchedInferencePipeline:
             suppress_tokens=options.suppress_tokens, return_scores=True, return_no_speech_prob=True,
             sampling_temperature=options.temperatures[0], repetition_penalty=options.repetition_penalty,
             no_repeat_ngram_size=options.no_repeat_ngram_size,
-            **(dict(return_token_logprobs=True) if token_logprobs else {}))
+            **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))
         output = []
         for r in results:
             output.append(dict(avg_logprob=_avg_logprob(r, options.length_penalty), no_speech_prob=r.no_speech_prob,
                                tokens=r.sequences_ids[0]))
-            if token_logprobs:
+            if token_logprobs or token_alternatives:
                 output[-1].update(token_logprobs=r.token_logprobs[0], end_logprob=r.end_logprobs[0])
+            if token_alternatives:
+                output[-1].update(token_alternatives=r.token_alternatives[0], end_alternatives=r.end_alternatives[0])
         return encoder_output, output
 
     def forward(self, features, tokenizer, chunks_metadata, options, audio_chunks=None):
@@ -974,7 +1014,7 @@ class BatchedInferencePipeline:
                      seek=int(meta["offset"] * m.frames_per_second))
                 for s in subs])
             if "token_logprobs" in out:
-                _slice_token_logprobs(segmented[-1], out["token_logprobs"])
+                _slice_token_values(segmented[-1], out["token_logprobs"], out.get("token_alternatives"))
         return segmented, sizes
 
     # ---- the public entry point ---------------------------------------------------------
@@ -994,10 +1034,13 @@ class BatchedInferencePipeline:
                    batch_size: int = 8, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    shard: bool = False, fused_features: bool = True, vad_speech_probs=None,
-                   token_logprobs: bool = False):
+                   token_logprobs: bool = False, token_alternatives: int = 0):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
+        token_alternatives=N (not in the reference; 1 <= N <= backend.MAX_ALTERNATIVES): every segment is an
+        AlternativesSegment, a ScoredSegment that also lists the N most likely (id, log-prob) pairs at the position of each
+        of its tokens (not offered with shard=True either).
         shard=True: inside a torch.distributed job every rank calls this with the same arguments; the
         chunk list is block-partitioned over the ranks and rank 0's generator yields ALL segments in
         order (other ranks yield nothing).  fused_features=False reproduces the reference data flow
@@ -1005,8 +1048,9 @@ class BatchedInferencePipeline:
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model
-        if token_logprobs and shard:
-            raise ValueError("token_logprobs is not offered with shard=True: the gathered records carry no per-token values")
+        if (token_logprobs or token_alternatives) and shard:
+            raise ValueError("token_logprobs / token_alternatives are not offered with shard=True: the gathered records "
+                             "carry no per-token values")
         multilingual = m._effective_multilingual(multilingual)
         audio = np.asarray(m._load_audio(audio), dtype=np.float32)
         chunk_length = chunk_length or m.feature_extractor.chunk_length
@@ -1023,7 +1067,7 @@ class BatchedInferencePipeline:
         self._plan_decode(rec, args, language, multilingual, {})
         gen = self._batched_segments_generator(rec.audio_chunks, rec.tokenizer, rec.chunks_metadata, batch_size,
                                                rec.options, log_progress, shard, fused_features,
-                                               **(dict(token_logprobs=True) if token_logprobs else {}))
+                                               **_value_keywords(token_logprobs, token_alternatives))
         return self._on_recording_time(rec, gen), rec.info
 
     # ---- the steps of transcribe that transcribe_many runs per recording -----------------
@@ -1128,7 +1172,8 @@ class BatchedInferencePipeline:
         return restore_speech_timestamps(segments, rec.clips, self.model.feature_extractor.sampling_rate)
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                    log_progress, shard=False, fused_features=True, token_logprobs=False):
+                                    log_progress, shard=False, fused_features=True, token_logprobs=False,
+                                    token_alternatives=0):
         from .sharding import gather_results, partition
         m = self.model
         rank, world, local_rank = 0, 1, 0
@@ -1151,7 +1196,8 @@ class BatchedInferencePipeline:
                 mid = lo + (hi - lo + 1) // 2
                 spans = [(lo, mid), (mid, hi)]
             return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
-                                            for i0, i1 in spans], shard, fused_features, token_logprobs)
+                                            for i0, i1 in spans], shard, fused_features, token_logprobs,
+                                           token_alternatives)
 
         def emit(results):
             nonlocal seg_idx
@@ -1198,13 +1244,13 @@ class BatchedInferencePipeline:
         self.last_speech_timestamp = 0.0
 
     def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
-                      token_logprobs=False):
+                      token_logprobs=False, token_alternatives=0):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
         m = self.model
         feats = None if fused_features else m.model.log_mel(chunks)
         enc, outs = self.generate_segment_batched(feats, tokenizer, options,
                                                   audio_chunks=chunks if fused_features else None,
-                                                  **(dict(token_logprobs=True) if token_logprobs else {}))
+                                                  **_value_keywords(token_logprobs, token_alternatives))
         local = aligned = None
         if not shard or options.word_timestamps:
             local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
@@ -1214,7 +1260,7 @@ class BatchedInferencePipeline:
                                         options.append_punctuations)
         return outs, local, aligned
 
-    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False):
+    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False, token_alternatives=0):
         """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
         The batches are independent (`condition_on_previous_text=False`): with worker replicas
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
@@ -1223,14 +1269,15 @@ class BatchedInferencePipeline:
         workers = self.model._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
-                yield self._decode_batch(*job, shard, fused_features, token_logprobs)
+                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives)
             return
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as pool:
             pending = deque()
             for job in jobs:
-                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs))
+                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs,
+                                           token_alternatives))
                 if len(pending) >= workers:
                     yield pending.popleft().result()
             while pending:
@@ -1248,7 +1295,7 @@ class BatchedInferencePipeline:
                               no_speech_prob=seg["no_speech_prob"], compression_ratio=seg["compression_ratio"],
                               temperature=options.temperatures[0])
                 # (sub-segments carry token_logprobs exactly when the call asked for them: _split_outputs)
-                yield _make_segment(values, seg.get("token_logprobs"))
+                yield _make_segment(values, seg.get("token_logprobs"), seg.get("token_alternatives"))
                 idx += 1
 
     # ---- many recordings in one call ------------------------------------------------------------
@@ -1335,7 +1382,8 @@ class BatchedInferencePipeline:
 
         # ---- route: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
         for owner, (_, local, aligned) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
-                                                                              a["token_logprobs"])):
+                                                                              a["token_logprobs"],
+                                                                              a["token_alternatives"])):
             for j, rec in enumerate(owner):
                 rec.decoded.append(local[j])
                 if aligned is not None:

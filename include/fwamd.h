@@ -54,7 +54,8 @@ extern "C" {
  *    is one pool shared by its lanes (fw_model_decode_batch = chunks of the pool, fw_model_run_capacity = chunks of one run);
  *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed),
  *    fw_vad_forward_audio_batch_dev likewise, fw_generate_lp (fw_generate plus per-token log-probabilities) and
- *    fw_score (teacher-forced log-probs of given transcripts) */
+ *    fw_score (teacher-forced log-probs of given transcripts), fw_generate_alt (fw_generate_lp plus the n most
+ *    likely tokens at every position) */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -276,6 +277,33 @@ int32_t fw_generate(fw_model* m, const fw_tensor* enc, const int32_t* prompts,
 int32_t fw_generate_lp(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets, int32_t B,
                        const fw_gen_opts* opts, int32_t* out_ids, int32_t* out_lens, float* out_scores,
                        float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs);
+/* fw_generate_lp, plus the n_alt most likely tokens at every position of every returned hypothesis: what else the model
+ * considered there, and how close it was.
+ *   out_alt_ids / out_alt_logprobs          int32 / float [B, num_hypotheses, max_length, n_alt]
+ *   out_end_alt_ids / out_end_alt_logprobs  int32 / float [B, num_hypotheses, n_alt]
+ * Entry [b, h, t, :] holds the n_alt most likely ids, with their log-probs, of the distribution out_ids[b, h, t] was
+ * chosen from: the one on the hypothesis's own row at that step, and the one out_token_logprobs speaks of (after the
+ * repetition penalty, the n-gram, suppress and timestamp rules, fp32 log-softmax, not tempered when sampling).  The end
+ * arrays hold the same for the step that produced the closing <eot>.  Order: log-prob descending, id ascending.  A
+ * distribution with fewer than n_alt live ids fills the tail with (id 0, -inf).  Entries at t >= out_lens are (id -1,
+ * log-prob 0), and so are the end entries of a hypothesis that was cut at the budget (it has no closing step): the id -1
+ * is the mark, a genuine log-prob can be 0.
+ * Two identities hold exactly: (1) when out_ids[b, h, t] is among the alternatives of its position, its log-prob there is
+ * out_token_logprobs[b, h, t] bit for bit (when it is not, out_token_logprobs[b, h, t] <= the last alternative's), and
+ * likewise <eot> and out_end_logprobs; for a greedy call alternative 0 IS (out_ids, out_token_logprobs).  (2) fw_score
+ * with the call's rules on out_ids[b, h, :t] followed by an alternative id returns that alternative's log-prob bit for
+ * bit for a greedy hypothesis, and its out_best_ids at that position is alternative 0.
+ * 0 <= n_alt <= FW_MAX_ALTERNATIVES.  n_alt == 0 requires the four pointers to be NULL and is fw_generate_lp; n_alt > 0
+ * requires all four.  Anything else is FW_EINVAL before anything is queued.  A call with alternatives shares decode runs
+ * with calls without and with calls of another n_alt, and every caller gets what it would get alone, bit for bit.  The
+ * buffers behind this are allocated by the first decode run that needs them (FW_ENOMEM for the calls of that run). */
+#define FW_MAX_ALTERNATIVES 8
+int32_t fw_generate_alt(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                        int32_t B, const fw_gen_opts* opts, int32_t n_alt,
+                        int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                        float* out_token_logprobs, float* out_end_logprobs,
+                        int32_t* out_alt_ids, float* out_alt_logprobs,          /* [B, num_hypotheses, max_length, n_alt] */
+                        int32_t* out_end_alt_ids, float* out_end_alt_logprobs); /* [B, num_hypotheses, n_alt] */
 
 /* ---- score ---------------------------------------------------------------
  * Teacher-forced log-probs of GIVEN transcripts (CTranslate2 has score_batch for its other model classes): how likely

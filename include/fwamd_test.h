@@ -66,6 +66,16 @@ int32_t fw_test_logits_rules_ex(fw_model* m, float* logits, int32_t R, const int
                                 const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
                                 const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
                                 int32_t* cand_tok, float* cand_lp);
+/* fw_test_logits_rules_ex plus alternatives (tests/test_gpu_alternatives_kernels.py): the ALT instantiations of the rules
+ * kernel, which also write the first n_alt rounds of every live row's extraction.
+ *   in      n_alt in [1, FW_MAX_ALTERNATIVES] (checked: FW_EINVAL, outputs untouched)
+ *   in/out  alt_tok / alt_lp [R][n_alt]: the device slab of step n starts as the caller's values, so the rows of a chunk
+ *           marked done keep them; a live row gets its n_alt best (log-prob descending, id ascending), (0, -inf) once
+ *           nothing is left.  Sampling rows: the draw in cand_*, the plain top n_alt here. */
+int32_t fw_test_logits_rules_alt(fw_model* m, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                 const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
+                                 const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
+                                 int32_t* cand_tok, float* cand_lp, int32_t n_alt, int32_t* alt_tok, float* alt_lp);
 /* ONE launch of the scoring kernel (dec_score_kernel, what fw_score launches per position block) on caller-provided rows
  * (tests/test_gpu_score_kernel.py):
  *   in/out  logits [rows][n_vocab] float32: uploaded, and downloaded WHOLE after the launch (the kernel must not write it)
@@ -118,6 +128,34 @@ int32_t fw_test_dec_beam_update_lp(fw_model* m, int32_t B, int32_t K, int32_t NT
                                    float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin, int32_t* fin_tok,
                                    int32_t* fin_len, float* fin_score, float* fin_cum, float* fin_lp, int32_t* hist2,
                                    float* lphist2, uint8_t* kvidx2, float* cum2, int32_t* cur_tok);
+/* fw_test_dec_beam_update_lp plus the path of a finished hypothesis and ragged launches
+ * (tests/test_gpu_alternatives_kernels.py):
+ *   in      ptab [B] | NULL: chunk c has a prompt of ptab[c] tokens (the RAGGED instantiation).  P must then be the
+ *           shortest, the run reaches P + budget positions, kvidx is [R][max(ptab) - 1 + step] and the rows of chunk c use
+ *           the first ptab[c] - 1 + step bytes of theirs.  Checked: P <= ptab[c], ptab[c] - 1 + step < min(NT, P + budget)
+ *   in/out  fin_path [B][48][NT + 1] bytes | NULL (the kernel gets a null pointer: fw_test_dec_beam_update_lp bit for
+ *           bit): for a hypothesis recorded at this step, byte q < step = its source row's kvidx byte at ptab[c] - 1 + q,
+ *           byte step = the source row's beam index; uploaded and downloaded whole */
+int32_t fw_test_dec_beam_update_alt(fw_model* m, int32_t B, int32_t K, int32_t NT, int32_t V, int32_t P, int32_t step,
+                                    int32_t budget, int32_t max_fin, float lp_pow, int32_t eot, const float* cand_val,
+                                    const int32_t* cand_tok, const float* cand_lp, const int32_t* hist,
+                                    const float* lphist, const uint8_t* kvidx, const float* cum, int32_t sentinel_i,
+                                    float sentinel_f, int32_t* done, int32_t* n_done, int32_t* n_fin, int32_t* fin_tok,
+                                    int32_t* fin_len, float* fin_score, float* fin_cum, float* fin_lp, int32_t* hist2,
+                                    float* lphist2, uint8_t* kvidx2, float* cum2, int32_t* cur_tok, const int32_t* ptab,
+                                    uint8_t* fin_path);
+/* ONE launch of the alternatives gather (what a decode run launches once after its last step):
+ *   in      alt_tok / alt_lp [steps][R][n_alt] (step-major, as the rules kernel writes them), fin_path [R / K][48][NT + 1]
+ *   in      n_hyp hypotheses: decode chunk, finished slot, length, and the step whose row produced the closing <eot>
+ *           (-1: cut at the budget, no closing step)
+ *   in/out  out_tok / out_lp [n_hyp][T + 1][n_alt]: entry t < len = alt_*[t][chunk * K + path[t]], entry T = those of
+ *           the closing step; entries in [len, T), and entry T without a closing step, are (-1, 0)
+ * Checked: 1 <= n_alt <= FW_MAX_ALTERNATIVES, 1 <= K <= 16, R % K == 0, R <= 4096, 1 <= NT <= 4096, 1 <= steps <= NT + 1,
+ * 0 <= T <= NT, chunk < R / K, slot < 48, 0 <= len <= min(T, steps), -1 <= end < steps, every path byte read < K. */
+int32_t fw_test_alt_gather(fw_model* m, const int32_t* alt_tok, const float* alt_lp, int32_t steps, int32_t R, int32_t K,
+                           int32_t NT, int32_t n_alt, const uint8_t* fin_path, int32_t n_hyp, const int32_t* hyp_chunk,
+                           const int32_t* hyp_fin, const int32_t* hyp_len, const int32_t* hyp_end, int32_t T,
+                           int32_t* out_tok, float* out_lp);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
