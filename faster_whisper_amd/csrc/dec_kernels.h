@@ -1,10 +1,16 @@
-// Launch API of the decoder-step kernels (dec_kernels.hip).
+// Launch API of the decoder-step kernels (dec_kernels.hip; the kernels that hold one vocabulary row: dec_vocab.hip).
 #pragma once
+#include <vector>
+
+#include "../../include/fwamd.h"
 #include "common.h"
 
 namespace fwd {
 
 constexpr int FIN_CAP = 48;  // finished hypotheses kept per chunk (>= round(K*patience) + K)
+// 64-bit words of the suppress mask (one bit per token id, zero-padded past the vocabulary): 56 * 1024 ids, what a
+// workgroup of the rules kernel holds in registers
+#define LP_SUP_WORDS 896
 
 // Per-generate constants handed to the kernels by value.
 struct GenDev {
@@ -37,10 +43,35 @@ struct GenDev {
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
 // kernel forbids ids from ts_begin + mits + 1 on at the first step, in int arithmetic: a limit at or past the number of
 // timestamp ids forbids nothing, and so does a negative one — both become -1, "no limit", which also gives equivalent
-// values one step-graph key.  decoder.hip and the rules hook (hooks.hip) both fill mits through this.
+// values one step-graph key.  fill_rule_fields (below) fills mits through this.
 static inline int initial_timestamp_limit(long long max_initial_timestamp_index, int n_vocab, int ts_begin) {
   const long long n_ts = (long long)n_vocab - ts_begin;
   return (max_initial_timestamp_index < 0 || max_initial_timestamp_index >= n_ts) ? -1 : (int)max_initial_timestamp_index;
+}
+
+// THE place that fills the rule fields of GenDev (what the rules kernel and the scoring kernel read of the caller's
+// options and of the model's token ids).  o == null: no rule at all, the raw distribution (the scoring paths).
+static inline void fill_rule_fields(GenDev& gp, const fw_config& c, const fw_gen_opts* o, int with_ts) {
+  gp.with_ts = (o && with_ts) ? 1 : 0;
+  gp.suppress_blank = (o && o->suppress_blank) ? 1 : 0;
+  gp.min_new = o ? o->min_new_tokens : 0;
+  gp.mits = o ? initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin) : -1;
+  gp.ngram = o ? o->no_repeat_ngram_size : 0;
+  gp.rep_pen = o ? o->repetition_penalty : 1.0f;
+  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
+  gp.n_sup_begin = o ? c.n_suppress_begin : 0;
+  for (int i = 0; i < gp.n_sup_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
+}
+
+// The suppress list as the kernels read it: one bit per token id, LP_SUP_WORDS 64-bit words; ids outside the vocabulary
+// are dropped.
+static inline std::vector<unsigned long long> suppress_mask(const int32_t* tokens, int n_tokens, int n_vocab) {
+  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
+  for (int i = 0; i < n_tokens; ++i) {
+    const int t = tokens[i];
+    if (t >= 0 && t < n_vocab) mask[t >> 6] |= 1ull << (t & 63);
+  }
+  return mask;
 }
 
 // Sampling runs: one entry per decode row.  The calls of a run keep their own temperature and seed, and a row draws its
@@ -119,9 +150,8 @@ int launch_dec_gemm_frag_i8(hipStream_t st, const int8_t* xq, const float* x_sca
 int launch_dec_logits(hipStream_t st, bool i8, const void* xf, const float* x_scale, const void* Wf,
                       const float* w_scale, const float* s1, const float* cf, float* out, int ldo, int R, int N, int K);
 void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, int no_speech_id, float* out, int B);
-// sup_bits: the suppress list, one bit per token id, LP_SUP_WORDS 64-bit words (zero-padded past the vocabulary)
+// sup_bits: the suppress list, one bit per token id, LP_SUP_WORDS 64-bit words (suppress_mask above)
 // smp_tab [gp.R]: read when gp.sample (then it must not be null: the launcher launches nothing without it)
-#define LP_SUP_WORDS 896
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
                            int* cand_tok, float* cand_lp = nullptr, const SmpRow* smp_tab = nullptr,

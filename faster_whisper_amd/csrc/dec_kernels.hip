@@ -1,4 +1,5 @@
-// K12-K20, K22-K23 — decoder-step kernels for gfx950.
+// K12-K16, K19-K20, K23 — decoder-step kernels for gfx950.  (The kernels that hold one row of vocabulary logits — the
+// logits rules K17/K18, the scoring kernel, the no-speech K22 and token probabilities — are dec_vocab.hip.)
 //
 // One decode step works on R = B*K rows (B chunks x K beams).  Everything a step needs
 // (step counter, beam parents, token history, KV-slot indirection) lives in HBM, so the
@@ -1438,550 +1439,6 @@ __global__ __launch_bounds__(CA_WAVES * 64, MINW) void dec_cross_attn_kernel(con
 }
 
 // ------------------------------------------------------------------------------------
-// K22: no-speech probability = softmax(logits at the <sot> position)[no_speech]
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void dec_nospeech_kernel(const float* __restrict__ logits, int V, int row_mul,
-                                                            int no_speech_id, float* __restrict__ out) {
-  __shared__ float red[32];
-  const int b = blockIdx.x;
-  const float* lg = logits + (size_t)b * row_mul * V;
-  float mx = -3.0e38f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, lg[v]);
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  float m2 = -3.0e38f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m2 = fmaxf(m2, red[i]);
-  __syncthreads();
-  float s = 0.f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) s += __expf(lg[v] - m2);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tot += red[i];
-    out[b] = __expf(lg[no_speech_id] - m2) / tot;
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// K17/K18 (+ the row part of K19): logits rules, fp32 log-softmax and the row's top-C
-// candidates of cum + logp, one workgroup per row.
-// Rule order: repetition penalty, no-repeat-ngram, suppress-blank (first
-// step), suppress list, [min_new_tokens], timestamp rules (a)-(e), log-softmax.
-// ------------------------------------------------------------------------------------
-#define LP_THREADS 1024
-#define LP_WAVES (LP_THREADS / 64)
-#define LP_NV 56 /* values per thread kept in registers: V <= 56*1024 */
-// counter-based Gumbel noise: murmur3 finaliser of (seed, row, step, token) -> u strictly in (0,1) -> -log(-log u).
-// oracle/whisper.py::_gumbel restates the same integer hash.
-static __device__ __forceinline__ float gumbel_noise(unsigned seed_lo, unsigned seed_hi, unsigned row, unsigned step,
-                                                     unsigned v) {
-  unsigned h = seed_lo ^ (row * 0x9E3779B9u) ^ (step * 0x85EBCA6Bu) ^ (v * 0xC2B2AE35u) ^ (seed_hi * 0x27D4EB2Fu);
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  // 23 bits: (h >> 9) + 0.5 is exact in fp32 for every h, so u stays strictly inside (0, 1) (with 24 bits the
-  // top value rounds to 1.0 and the noise becomes +inf: that token would win whatever its probability)
-  const float u = ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
-  return -logf(-logf(u));
-}
-
-// The row lives in registers (56 values per thread): all of its loads are issued back to back before the first use,
-// the suppress list is one bit per token (one scalar 8-byte load per 64 tokens of a wave), every element-wise rule
-// is a range test on uniform scalars.  Top-C: each thread keeps its own best (key, slot); a round is one wave
-// arg-max + 16 partials through LDS, and only the winning thread rescans its 56 values.
-// TXI: the first TXI values of every thread are text ids whatever the thread (ts_begin >= TXI * 1024: 48 for every
-// Whisper vocabulary, 0 for the synthetic test vocabularies) — a compile-time class split, no per-lane test there.
-// ALT (fw_generate_alt; instantiations of their own, the others are the code they always were): the row also writes the
-// first gp.n_alt rounds of its extraction to alt_tok / alt_lp [steps][R][n_alt] at [step][r][.], from the registers
-// cand_lp is written from.  Beam / greedy: max(2K, n_alt) rounds, rounds < 2K fill cand_*, rounds < n_alt fill alt_*.
-// Sampling: the draw is round 0 and does NOT retire its value (nothing after it read the retired value; the token, its
-// cand_val and cand_lp keep their bits), then every thread finds its best plain log-prob and n_alt plain rounds follow.
-template <bool SMP, int TXI, bool ALT = false>
-__global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::GenDev gp, float* __restrict__ logits,
-                                                                        const unsigned long long* __restrict__ sup_bits,
-                                                                        const int* __restrict__ hist2,
-                                                                        const float* __restrict__ cum2,
-                                                                        const int* __restrict__ d_step,
-                                                                        const int* __restrict__ done,
-                                                                        float* __restrict__ cand_val,
-                                                                        int* __restrict__ cand_tok,
-                                                                        float* __restrict__ cand_lp,
-                                                                        const fwd::SmpRow* __restrict__ smp_tab,
-                                                                        int* __restrict__ alt_tok,
-                                                                        float* __restrict__ alt_lp) {
-  __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
-  __shared__ float bkey_s[2][LP_WAVES];
-  __shared__ int btok_s[2][LP_WAVES];
-  __shared__ int sh_last_ts;
-  const int r = blockIdx.x;
-  const int c = r / gp.K;
-  if (done[c]) return;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int step = *d_step;
-  const int cur = step & 1;
-  const int n = step;  // tokens generated so far on this row
-  const int* hist = hist2 + ((size_t)cur * gp.R + r) * gp.n_text_ctx;
-  float* lg = logits + (size_t)r * gp.V;
-  const int V = gp.V, tb = gp.ts_begin;
-  const float NEG = -INFINITY;
-  const int NONE = 0x7fffffff;
-
-  // ---- sparse rules that touch a few ids (in HBM, before the row is pulled into registers) ----
-  if (gp.rep_pen != 1.0f && n > 0) {
-    for (int i = tid; i < n; i += LP_THREADS) {
-      const int t = hist[i];
-      bool first = true;
-      for (int q = 0; q < i; ++q)
-        if (hist[q] == t) { first = false; break; }
-      if (first) {
-        const float v = lg[t];
-        lg[t] = v < 0.f ? v * gp.rep_pen : v / gp.rep_pen;
-      }
-    }
-    __syncthreads();
-  }
-  if (gp.ngram > 0 && n + 1 >= gp.ngram) {
-    const int k = gp.ngram;
-    for (int s = tid; s + k <= n; s += LP_THREADS) {
-      bool match = true;
-      for (int q = 0; q < k - 1; ++q)
-        if (hist[s + q] != hist[n - (k - 1) + q]) { match = false; break; }
-      if (match) lg[hist[s + k - 1]] = NEG;
-    }
-    __syncthreads();
-  }
-  // ---- the row: every load in flight at once ----
-  float val[LP_NV];
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const int v = tid + i * LP_THREADS;
-    // (unconditional, clamped address: a load under `if (v < V)` becomes a branch around the load and the wait-count
-    //  pass then drains vmcnt(0) after every second one — 28 dependent round trips, 71 us per row, instead of one)
-    const float x = lg[v < V ? v : V - 1];
-    val[i] = (v < V) ? x : NEG;
-  }
-  // ---- timestamp-rule scalars (uniform): the position of the last timestamp token by a block arg-max ----
-  int a_hi = 0;        // ids in [0, a_hi) are forbidden
-  int b_hi = tb;       // timestamps in [tb, b_hi) are forbidden
-  int c_lo = NONE;     // ids >= c_lo are forbidden
-  if (gp.with_ts) {
-    if (tid == 0) sh_last_ts = -1;
-    __syncthreads();
-    if (tid < n && hist[tid] >= tb) atomicMax(&sh_last_ts, tid);   // n <= n_text_ctx <= LP_THREADS
-    __syncthreads();
-    const int lp = sh_last_ts;
-    const bool last_ts = n >= 1 && lp == n - 1;
-    const bool penult_ts = n < 2 || hist[n - 2] >= tb;
-    if (lp >= 0) {
-      const int last_seen = hist[lp];
-      b_hi = (last_ts && !penult_ts) ? last_seen : last_seen + 1;
-    }
-    if (last_ts) {
-      if (penult_ts) b_hi = NONE;   // a closed pair: no timestamp at all
-      else a_hi = gp.eot;           // an open one: text is forbidden, the pair has to close
-    }
-    if (n == 0) {
-      a_hi = tb;                    // the first token is a timestamp
-      if (gp.mits >= 0) c_lo = tb + gp.mits + 1;
-    }
-  }
-  const int kill_a = (n < gp.min_new) ? gp.eot : -1;
-  const int kill_b = gp.with_ts ? gp.no_ts : -1;
-  // ---- element-wise masks, class maxima (text / timestamp ids) ----
-  // The 64 tokens a wave holds in val[i] are CONSECUTIVE ids (v0 = 64 * (16 i + wave) .. v0 + 63), so every rule — the
-  // suppress list, the id ranges of the timestamp rules, the single ids — is one 64-bit lane mask per i.  Lane l of
-  // the wave builds the mask of i = l (56 lanes, once); applying mask i is then two v_readlane + ONE v_cndmask (the
-  // mask as the select operand) per value instead of ~12 vector compares / selects per value.  The class split (text
-  // ids below ts_begin, timestamps from there) is uniform for every i but tb / 1024, where it is a per-lane test.
-  auto below = [](int nb) -> unsigned long long {   // lanes [0, nb) of a wave's 64 ids
-    return nb <= 0 ? 0ull : (nb >= 64 ? ~0ull : ((1ull << nb) - 1ull));
-  };
-  auto span = [&](int lo, int hi, int v0) -> unsigned long long {   // ids in [lo, hi) among v0 .. v0 + 63
-    return below(hi - v0) & ~below(lo - v0);
-  };
-  unsigned km_lo, km_hi;
-  {
-    const int li = lane < LP_NV ? lane : LP_NV - 1;
-    const int v0 = (li * LP_WAVES + wv) * 64;
-    unsigned long long km = sup_bits[li * LP_WAVES + wv];
-    km |= below(a_hi - v0) | span(tb, b_hi, v0) | ~below(c_lo - v0) | span(kill_a, kill_a + 1, v0) |
-          span(kill_b, kill_b + 1, v0);
-    if (n == 0 && gp.suppress_blank) {   // first step only
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (q < gp.n_sup_begin) km |= span(gp.sup_begin[q], gp.sup_begin[q] + 1, v0);
-    }
-    km_lo = (unsigned)km; km_hi = (unsigned)(km >> 32);
-  }
-  float mt = NEG, ms = NEG;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const unsigned long long km = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_hi, i) << 32) |
-                                  (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_lo, i);
-    const float x = __builtin_amdgcn_inverse_ballot_w64(km) ? NEG : val[i];
-    val[i] = x;
-    if (i < TXI) mt = fmaxf(mt, x);
-    else {
-      const bool text = tid + i * LP_THREADS < tb;
-      mt = fmaxf(mt, text ? x : NEG);
-      ms = fmaxf(ms, text ? NEG : x);
-    }
-  }
-  mt = wave_max_v(mt);
-  ms = wave_max_v(ms);
-  if (lane == 0) { red_mt[wv] = mt; red_ms[wv] = ms; }
-  __syncthreads();
-  float max_t = red_mt[0], max_s = red_ms[0];
-#pragma unroll
-  for (int i = 1; i < LP_WAVES; ++i) { max_t = fmaxf(max_t, red_mt[i]); max_s = fmaxf(max_s, red_ms[i]); }
-  // ---- class sums of exp(x - class max): exp(-inf) = 0 drops the masked ids ----
-  const float off_t = (max_t == NEG) ? 0.f : max_t, off_s = (max_s == NEG) ? 0.f : max_s;
-  float st = 0.f, ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    if (i < TXI) st += __expf(val[i] - off_t);
-    else {
-      const bool text = tid + i * LP_THREADS < tb;
-      const float e = __expf(val[i] - (text ? off_t : off_s));
-      st += text ? e : 0.f;     // (x + 0 == x: the bits of `if (text) st += e; else ss += e;`)
-      ss += text ? 0.f : e;
-    }
-  }
-  st = wave_sum_v(st);   // the butterfly of __shfl_xor 32 .. 1 on the VALU: same partners, same bits (common.h)
-  ss = wave_sum_v(ss);
-  if (lane == 0) { red_st[wv] = st; red_ss[wv] = ss; }
-  __syncthreads();
-  float sum_t = 0.f, sum_s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP_WAVES; ++i) { sum_t += red_st[i]; sum_s += red_ss[i]; }   // fixed order: every thread agrees
-  const float log_t = logf(sum_t), log_s = logf(sum_s);   // (an empty class: max -inf, sum 0, its log is never used)
-  const float lse_s = (max_s == NEG) ? NEG : max_s + log_s;
-  // rule (e): if logsumexp(timestamps) > max(text) (in log-prob space the common lse cancels): text is masked
-  const bool mask_text = __builtin_amdgcn_readfirstlane((gp.with_ts && lse_s > max_t) ? 1 : 0) != 0;   // uniform
-  // The log-sum-exp of what is left is subtracted in two parts, logp = (x - M) - L with M the maximum and L the log of
-  // the sum of exp(x - M): x - M is exact or nearly so and L is small, so logp carries the round-off of ITS OWN size.
-  // (x - (M + L) rounds M + L at the spacing of |M| first: 8e-6 at |M| = 128, whatever the size of logp.)
-  // (-inf - finite = -inf: the masked ids need no test; every id masked: nothing is subtracted, M = L = 0)
-  float lse_m = 0.f, lse_l = 0.f;
-  if (mask_text || max_t == NEG) {
-    if (max_s != NEG) { lse_m = max_s; lse_l = log_s; }
-  } else if (max_s == NEG) {
-    lse_m = max_t; lse_l = log_t;
-  } else {   // both classes alive: the class sums on the larger maximum
-    const bool t_hi = max_t >= max_s;
-    lse_m = t_hi ? max_t : max_s;
-    lse_l = logf((t_hi ? sum_t : sum_s) + (t_hi ? sum_s : sum_t) * expf((t_hi ? max_s : max_t) - lse_m));
-  }
-  // ---- log-probs; this thread's best key ----
-  const float cum = cum2[(size_t)cur * gp.R + r];
-  constexpr bool smp = SMP;   // a separate instantiation: 2 x 56 inlined logf stay out of the beam / greedy kernel
-  // sampling: temperature, seed and first row of this row's CALL (one uniform 16-byte load; the other instantiations
-  // never touch the table).  The noise of a row depends on (seed of its call, row inside its call, step, token) only.
-  fwd::SmpRow sr = {1.0f, 0u, 0u, 0};
-  if (smp) sr = smp_tab[r];
-  const int C = smp ? 1 : 2 * gp.K;
-  float bkey = NEG;
-  int bq = -1;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const int v = tid + i * LP_THREADS;
-    float x = val[i];
-    if (mask_text) x = (v < tb) ? NEG : x;
-    x = (x - lse_m) - lse_l;
-    val[i] = x;
-    float key = x;
-    if (smp && x != NEG) key = x * sr.inv_temp + gumbel_noise(sr.seed_lo, sr.seed_hi, (unsigned)(r - sr.row0), (unsigned)step, (unsigned)v);
-    if (key > bkey) { bkey = key; bq = i; }   // ascending index: ties keep the lowest
-  }
-  // ---- top-C of cum + logp: C rounds (value desc, index asc).  Sampling mode (Gumbel-max): one round on
-  //      logp/T + Gumbel noise; the recorded score stays cum + logp. ----
-  // ALT: round `rd` fills candidate slot rd (while rd < C) and alternative slot `ai` (while 0 <= ai < n_alt): ai = rd,
-  // but rd - 1 when sampling, whose round 0 is the draw.
-  const int n_alt = ALT ? gp.n_alt : 0;
-  const int NR = !ALT ? C : (smp ? 1 + n_alt : (C > n_alt ? C : n_alt));
-  const size_t alt0 = ALT ? ((size_t)step * gp.R + r) * n_alt : 0;
-  for (int cidx = 0; cidx < NR; ++cidx) {
-    const bool plain = !smp || (ALT && cidx > 0);   // a round on the log-probs themselves: the winner finds its next best
-    const bool w_cand = !ALT || cidx < C;           // (uniform)
-    const int ai = smp ? cidx - 1 : cidx;
-    const bool w_alt = ALT && ai >= 0 && ai < n_alt;
-    if (ALT && smp && cidx == 1) {   // after the draw: this thread's best plain log-prob (the draw retired nothing)
-      bkey = NEG; bq = -1;
-#pragma unroll
-      for (int i = 0; i < LP_NV; ++i)
-        if (val[i] > bkey) { bkey = val[i]; bq = i; }
-    }
-    float k = bkey;
-    int t = (bq < 0) ? NONE : tid + bq * LP_THREADS;
-    wave_argmax_v(k, t);        // DPP / permlane exchanges (the ds_bpermute butterfly was ~1 500 cycles per round)
-    const int par = cidx & 1;   // partials double-buffered: one barrier per round
-    if (lane == 0) { bkey_s[par][wv] = k; btok_s[par][wv] = t; }
-    __syncthreads();
-    // the 16 wave partials: lane l takes partial l % 16, four exchanges inside the 16-lane row leave the winner in
-    // every lane (the relation is a total order on (key, token): the result does not depend on the exchange pattern)
-    float wk = bkey_s[par][lane & (LP_WAVES - 1)];
-    int wt = btok_s[par][lane & (LP_WAVES - 1)];
-    argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR1>(wk), dpp_i<FW_DPP_XOR1>(wt));
-    argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR2>(wk), dpp_i<FW_DPP_XOR2>(wt));
-    argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR4>(wk), dpp_i<FW_DPP_ROR4>(wt));
-    argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR8>(wk), dpp_i<FW_DPP_ROR8>(wt));
-    if (wt == NONE) {   // nothing left on this row
-      if (tid == 0) {
-        if (w_cand) {
-          cand_val[(size_t)r * 32 + cidx] = NEG;
-          cand_tok[(size_t)r * 32 + cidx] = 0;
-          if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
-          if (cand_lp) {   // (a kernel argument: uniform)
-            cand_lp[(size_t)r * 32 + cidx] = NEG;
-            if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
-          }
-        }
-        if (w_alt) { alt_tok[alt0 + ai] = 0; alt_lp[alt0 + ai] = NEG; }
-      }
-      continue;
-    }
-    if ((wt & (LP_THREADS - 1)) == tid) {   // the winning thread: record, retire the value, find its next best
-      const int wq = wt / LP_THREADS;
-      float raw = NEG;
-      bkey = NEG; bq = -1;
-#pragma unroll
-      for (int i = 0; i < LP_NV; ++i) {
-        if (i == wq) { raw = val[i]; if (!(ALT && smp) || cidx > 0) val[i] = NEG; }
-        if (plain && val[i] > bkey) { bkey = val[i]; bq = i; }
-      }
-      if (w_cand) {
-        cand_val[(size_t)r * 32 + cidx] = cum + raw;
-        cand_tok[(size_t)r * 32 + cidx] = wt;
-        if (smp) { cand_val[(size_t)r * 32 + 1] = NEG; cand_tok[(size_t)r * 32 + 1] = 0; }
-        // the token's own log-prob, as it was added to cum: stored, not recovered later from two running sums
-        // (fl(cum + raw) - cum is not raw once |raw| > |cum|)
-        if (cand_lp) {
-          cand_lp[(size_t)r * 32 + cidx] = raw;
-          if (smp) cand_lp[(size_t)r * 32 + 1] = NEG;
-        }
-      }
-      if (w_alt) { alt_tok[alt0 + ai] = wt; alt_lp[alt0 + ai] = raw; }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// Scoring (fw_score): the log-prob of a GIVEN token per logits row, with the row's arg-max beside it, one workgroup per
-// row, every row of a position block in one launch.  Row r of the launch is position pos0 + r % nb of sequence r / nb and
-// reads its ScoreRow (target id, history, output index) from tab[(r / nb) * tab_stride + pos0 + r % nb]; a row without
-// a target (target < 0) writes nothing.
-// The row is held and reduced exactly as dec_logits_process_kernel does it — the same loads, the same class maxima and
-// class sums in the same order, the same two-part subtraction — so that a row scored here gets the bits that kernel
-// gives the same row of a greedy decode step.  What differs:
-//   * RULES: the decoding rules of a greedy row whose history is hist[0 .. n) (n = the row's own position among its
-//     targets: no d_step, no parity half, no min_new_tokens).  !RULES: the raw distribution, every id one class.
-//   * the logits are READ ONLY.  The two sparse rules (repetition penalty, no-repeat n-gram) mark their ids in two LDS
-//     bit maps laid out like the suppress mask (one 64-bit word per 64 consecutive ids a wave holds in val[i]): the
-//     n-gram bits join the suppress word, the penalty is applied to the register copy of the words that have a bit set.
-//   * one arg-max round instead of top-C, and the target's value picked out of its owner's registers.
-// ------------------------------------------------------------------------------------
-template <bool RULES>
-__global__ __launch_bounds__(LP_THREADS) void dec_score_kernel(fwd::GenDev gp, const float* __restrict__ logits,
-                                                               const unsigned long long* __restrict__ sup_bits,
-                                                               const fwd::ScoreRow* __restrict__ tab, int tab_stride,
-                                                               int pos0, int nb, const int* __restrict__ hist_pool,
-                                                               float* __restrict__ out_lp, int* __restrict__ out_best_id,
-                                                               float* __restrict__ out_best_lp) {
-  __shared__ float red_mt[LP_WAVES], red_ms[LP_WAVES], red_st[LP_WAVES], red_ss[LP_WAVES];
-  __shared__ float bkey_s[LP_WAVES];
-  __shared__ int btok_s[LP_WAVES];
-  __shared__ int sh_last_ts;
-  __shared__ unsigned pen_bits[2 * LP_SUP_WORDS], ng_bits[2 * LP_SUP_WORDS];
-  const int r = blockIdx.x;
-  const int sq = r / nb;
-  const fwd::ScoreRow row = tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
-  if (row.target < 0) return;   // (uniform)
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = row.n;
-  const int* hist = hist_pool + row.hist_off;
-  const float* lg = logits + (size_t)r * gp.V;
-  const int V = gp.V, tb = gp.ts_begin;
-  const float NEG = -INFINITY;
-  const int NONE = 0x7fffffff;
-  // ---- sparse rules: the ids they touch, one bit each ----
-  const bool pen_on = RULES && gp.rep_pen != 1.0f && n > 0;
-  const bool ng_on = RULES && gp.ngram > 0 && n + 1 >= gp.ngram;
-  if (pen_on || ng_on) {
-    for (int i = tid; i < 2 * LP_SUP_WORDS; i += LP_THREADS) { pen_bits[i] = 0u; ng_bits[i] = 0u; }
-    __syncthreads();
-    if (pen_on)
-      for (int i = tid; i < n; i += LP_THREADS) {
-        const int t = hist[i];
-        atomicOr(&pen_bits[t >> 5], 1u << (t & 31));   // (a bit: an id is penalised once however often it occurs)
-      }
-    if (ng_on) {
-      const int k = gp.ngram;
-      for (int s = tid; s + k <= n; s += LP_THREADS) {
-        bool match = true;
-        for (int q = 0; q < k - 1; ++q)
-          if (hist[s + q] != hist[n - (k - 1) + q]) { match = false; break; }
-        if (match) {
-          const int t = hist[s + k - 1];
-          atomicOr(&ng_bits[t >> 5], 1u << (t & 31));
-        }
-      }
-    }
-    __syncthreads();
-  }
-  // ---- the row: every load in flight at once (unconditional, clamped: see dec_logits_process_kernel) ----
-  float val[LP_NV];
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const int v = tid + i * LP_THREADS;
-    const float x = lg[v < V ? v : V - 1];
-    val[i] = (v < V) ? x : NEG;
-  }
-  // ---- timestamp-rule scalars (uniform), as in dec_logits_process_kernel ----
-  int a_hi = 0;        // ids in [0, a_hi) are forbidden
-  int b_hi = tb;       // timestamps in [tb, b_hi) are forbidden
-  int c_lo = NONE;     // ids >= c_lo are forbidden
-  const bool with_ts = RULES && gp.with_ts;
-  if (with_ts) {
-    if (tid == 0) sh_last_ts = -1;
-    __syncthreads();
-    if (tid < n && hist[tid] >= tb) atomicMax(&sh_last_ts, tid);   // n <= n_text_ctx <= LP_THREADS
-    __syncthreads();
-    const int lp = sh_last_ts;
-    const bool last_ts = n >= 1 && lp == n - 1;
-    const bool penult_ts = n < 2 || hist[n - 2] >= tb;
-    if (lp >= 0) {
-      const int last_seen = hist[lp];
-      b_hi = (last_ts && !penult_ts) ? last_seen : last_seen + 1;
-    }
-    if (last_ts) {
-      if (penult_ts) b_hi = NONE;   // a closed pair: no timestamp at all
-      else a_hi = gp.eot;           // an open one: text is forbidden, the pair has to close
-    }
-    if (n == 0) {
-      a_hi = tb;                    // the first token is a timestamp
-      if (gp.mits >= 0) c_lo = tb + gp.mits + 1;
-    }
-  }
-  // ---- element-wise masks (one 64-bit lane mask per i, built by lane i), class maxima ----
-  auto below = [](int nbits) -> unsigned long long {
-    return nbits <= 0 ? 0ull : (nbits >= 64 ? ~0ull : ((1ull << nbits) - 1ull));
-  };
-  auto span = [&](int lo, int hi, int v0) -> unsigned long long { return below(hi - v0) & ~below(lo - v0); };
-  unsigned km_lo = 0u, km_hi = 0u, pm_lo = 0u, pm_hi = 0u;
-  if (RULES) {
-    const int li = lane < LP_NV ? lane : LP_NV - 1;
-    const int w = li * LP_WAVES + wv;
-    const int v0 = w * 64;
-    const int kill_b = with_ts ? gp.no_ts : -1;
-    unsigned long long km = sup_bits[w];
-    km |= below(a_hi - v0) | span(tb, b_hi, v0) | ~below(c_lo - v0) | span(kill_b, kill_b + 1, v0);
-    if (n == 0 && gp.suppress_blank) {   // first position only
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (q < gp.n_sup_begin) km |= span(gp.sup_begin[q], gp.sup_begin[q] + 1, v0);
-    }
-    if (ng_on) km |= ((unsigned long long)ng_bits[2 * w + 1] << 32) | (unsigned long long)ng_bits[2 * w];
-    km_lo = (unsigned)km; km_hi = (unsigned)(km >> 32);
-    if (pen_on) { pm_lo = pen_bits[2 * w]; pm_hi = pen_bits[2 * w + 1]; }
-  }
-  float mt = NEG, ms = NEG;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    float x = val[i];
-    if (RULES) {
-      if (pen_on) {
-        const unsigned long long pm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)pm_hi, i) << 32) |
-                                      (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)pm_lo, i);
-        if (pm != 0ull) {   // (a scalar: nearly every word is empty)
-          const float pv = x < 0.f ? x * gp.rep_pen : x / gp.rep_pen;
-          x = __builtin_amdgcn_inverse_ballot_w64(pm) ? pv : x;
-        }
-      }
-      const unsigned long long km = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_hi, i) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)km_lo, i);
-      x = __builtin_amdgcn_inverse_ballot_w64(km) ? NEG : x;
-      val[i] = x;
-    }
-    const bool text = !RULES || tid + i * LP_THREADS < tb;
-    mt = fmaxf(mt, text ? x : NEG);
-    ms = fmaxf(ms, text ? NEG : x);
-  }
-  mt = wave_max_v(mt);
-  ms = wave_max_v(ms);
-  if (lane == 0) { red_mt[wv] = mt; red_ms[wv] = ms; }
-  __syncthreads();
-  float max_t = red_mt[0], max_s = red_ms[0];
-#pragma unroll
-  for (int i = 1; i < LP_WAVES; ++i) { max_t = fmaxf(max_t, red_mt[i]); max_s = fmaxf(max_s, red_ms[i]); }
-  // ---- class sums of exp(x - class max) ----
-  const float off_t = (max_t == NEG) ? 0.f : max_t, off_s = (max_s == NEG) ? 0.f : max_s;
-  float st = 0.f, ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const bool text = !RULES || tid + i * LP_THREADS < tb;
-    const float e = __expf(val[i] - (text ? off_t : off_s));
-    st += text ? e : 0.f;
-    ss += text ? 0.f : e;
-  }
-  st = wave_sum_v(st);
-  ss = wave_sum_v(ss);
-  if (lane == 0) { red_st[wv] = st; red_ss[wv] = ss; }
-  __syncthreads();
-  float sum_t = 0.f, sum_s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP_WAVES; ++i) { sum_t += red_st[i]; sum_s += red_ss[i]; }
-  const float log_t = logf(sum_t), log_s = logf(sum_s);
-  const float lse_s = (max_s == NEG) ? NEG : max_s + log_s;
-  const bool mask_text = __builtin_amdgcn_readfirstlane((with_ts && lse_s > max_t) ? 1 : 0) != 0;   // rule (e)
-  // logp = (x - M) - L, the two-part subtraction dec_logits_process_kernel explains
-  float lse_m = 0.f, lse_l = 0.f;
-  if (mask_text || max_t == NEG) {
-    if (max_s != NEG) { lse_m = max_s; lse_l = log_s; }
-  } else if (max_s == NEG) {
-    lse_m = max_t; lse_l = log_t;
-  } else {
-    const bool t_hi = max_t >= max_s;
-    lse_m = t_hi ? max_t : max_s;
-    lse_l = logf((t_hi ? sum_t : sum_s) + (t_hi ? sum_s : sum_t) * expf((t_hi ? max_s : max_t) - lse_m));
-  }
-  // ---- log-probs; this thread's best; the target's value ----
-  const int tq = ((row.target & (LP_THREADS - 1)) == tid) ? row.target / LP_THREADS : -1;
-  float bkey = NEG, tval = NEG;
-  int bq = -1;
-#pragma unroll
-  for (int i = 0; i < LP_NV; ++i) {
-    const int v = tid + i * LP_THREADS;
-    float x = val[i];
-    if (mask_text) x = (v < tb) ? NEG : x;
-    x = (x - lse_m) - lse_l;
-    if (i == tq) tval = x;
-    if (x > bkey) { bkey = x; bq = i; }   // ascending index: ties keep the lowest
-  }
-  if (tq >= 0) out_lp[row.out] = tval;
-  if (!out_best_id) return;   // (kernel arguments: uniform; both or none)
-  float k = bkey;
-  int t = (bq < 0) ? NONE : tid + bq * LP_THREADS;
-  wave_argmax_v(k, t);
-  if (lane == 0) { bkey_s[wv] = k; btok_s[wv] = t; }
-  __syncthreads();
-  float wk = bkey_s[lane & (LP_WAVES - 1)];
-  int wt = btok_s[lane & (LP_WAVES - 1)];
-  argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR1>(wk), dpp_i<FW_DPP_XOR1>(wt));
-  argmax_pair_step(wk, wt, dpp_f<FW_DPP_XOR2>(wk), dpp_i<FW_DPP_XOR2>(wt));
-  argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR4>(wk), dpp_i<FW_DPP_ROR4>(wt));
-  argmax_pair_step(wk, wt, dpp_f<FW_DPP_ROR8>(wk), dpp_i<FW_DPP_ROR8>(wt));
-  if (tid == 0) {
-    out_best_id[row.out] = (wt == NONE) ? 0 : wt;   // (nothing left on the row: id 0 at -inf, as the rules kernel records it)
-    out_best_lp[row.out] = (wt == NONE) ? NEG : wk;
-  }
-}
-
-// ------------------------------------------------------------------------------------
 // K19/K20: per-chunk beam update [CT2-ext: BeamSearch::search].  Merges the K rows' top-2K
 // candidates (stable: value desc, flat index asc), walks the first K slots (EOS / last step ->
 // finished hypothesis, replaced by the next non-EOS secondary candidate), then rewrites
@@ -2138,34 +1595,6 @@ void dec_beam_update_kernel(fwd::GenDev gp, const int* __restrict__ ptab, const 
 }
 
 __global__ void dec_step_advance_kernel(int* d_step) { *d_step += 1; }
-
-// per-token probability for align: p[r] = softmax(logits[r])[target[r]]
-__global__ __launch_bounds__(1024) void dec_token_prob_kernel(const float* __restrict__ logits, int V,
-                                                              const int* __restrict__ target, float* __restrict__ out,
-                                                              int out_stride, int out_off, int row_mul) {
-  __shared__ float red[32];
-  const int b = blockIdx.x;
-  const float* lg = logits + (size_t)b * row_mul * V;   // (position blocks: chunk b's row of this position)
-  float mx = -3.0e38f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, lg[v]);
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  float m2 = -3.0e38f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m2 = fmaxf(m2, red[i]);
-  __syncthreads();
-  float s = 0.f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) s += __expf(lg[v] - m2);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tot += red[i];
-    const int t = target[b];
-    out[(size_t)b * out_stride + out_off] = (t >= 0 && t < V) ? __expf(lg[t] - m2) / tot : 0.f;
-  }
-}
 
 // cross-attention probabilities of selected heads for align:
 // probs[b][hsel][tok][t] = softmax_t( q[b][head] . K[b][t][head] / 8 ),  one workgroup per (hsel, b)
@@ -2539,29 +1968,6 @@ void launch_cross_attn(hipStream_t st, const half_t* qx, int d, const half_t* ck
 }
 void set_cross_attn_regs(int cap) { g_cross_regs.store(cap); g_forms_epoch.fetch_add(1); }
 
-void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, int no_speech_id, float* out, int B) {
-  dec_nospeech_kernel<<<B, 1024, 0, st>>>(logits, V, row_mul, no_speech_id, out);
-}
-
-void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
-                           const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab, int* alt_tok, float* alt_lp) {
-  if (gp.sample && !smp_tab) return;   // (a sampling launch without its table: nothing is launched, nothing is read)
-  // every Whisper vocabulary keeps its timestamp ids above 48 * 1024 (ts_begin 50 363 .. 50 365); the synthetic
-  // test vocabularies do not: they take the instantiation with a per-lane class test everywhere
-  const bool wide = gp.ts_begin >= 48 * LP_THREADS;
-  const bool alt = gp.n_alt > 0 && alt_tok && alt_lp;
-  if (gp.n_alt > 0 && !alt) return;   // (a key that says alternatives without their buffers: nothing is launched)
-#define LP_GO(SMP, TXI, ALT) \
-  dec_logits_process_kernel<SMP, TXI, ALT><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab, alt_tok, alt_lp)
-  if (alt) {
-    if (gp.sample) { if (wide) LP_GO(true, 48, true); else LP_GO(true, 0, true); }
-    else { if (wide) LP_GO(false, 48, true); else LP_GO(false, 0, true); }
-  } else if (gp.sample) { if (wide) LP_GO(true, 48, false); else LP_GO(true, 0, false); }
-  else { if (wide) LP_GO(false, 48, false); else LP_GO(false, 0, false); }
-#undef LP_GO
-}
-
 void launch_beam_update(hipStream_t st, const GenDev& gp, const float* cand_val, const int* cand_tok, int* hist2,
                         float* cum2, uint8_t* kvidx2, int* cur_tok, const int* d_step, int* done, int* n_done,
                         int* n_fin, int* fin_tok, int* fin_len, float* fin_score, float* fin_cum, const float* cand_lp,
@@ -2642,19 +2048,6 @@ void launch_gather_sot_rows(hipStream_t st, const half_t* x, const int* sot_tab,
 }
 
 void launch_step_advance(hipStream_t st, int* d_step) { dec_step_advance_kernel<<<1, 1, 0, st>>>(d_step); }
-
-void launch_token_prob(hipStream_t st, const float* logits, int V, const int* target, float* out, int out_stride,
-                       int out_off, int rows, int row_mul) {
-  dec_token_prob_kernel<<<rows, 1024, 0, st>>>(logits, V, target, out, out_stride, out_off, row_mul);
-}
-
-void launch_score(hipStream_t st, const GenDev& gp, bool rules, const float* logits, const unsigned long long* sup_bits,
-                  const ScoreRow* tab, int tab_stride, int pos0, int nb, int rows, const int* hist_pool, float* out_lp,
-                  int* out_best_id, float* out_best_lp) {
-  if (!out_best_id || !out_best_lp) { out_best_id = nullptr; out_best_lp = nullptr; }   // both or none
-  if (rules) dec_score_kernel<true><<<rows, LP_THREADS, 0, st>>>(gp, logits, sup_bits, tab, tab_stride, pos0, nb, hist_pool, out_lp, out_best_id, out_best_lp);
-  else dec_score_kernel<false><<<rows, LP_THREADS, 0, st>>>(gp, logits, sup_bits, tab, tab_stride, pos0, nb, hist_pool, out_lp, out_best_id, out_best_lp);
-}
 
 void launch_cross_probs(hipStream_t st, const half_t* qx, int d, const half_t* ck, int T, int kvp, const int* heads,
                         int n_layer_heads, int n_sel, float* probs, int n_tok, int tok_idx, int B, int blk_n) {

@@ -864,16 +864,8 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   if (gp.max_fin > FIN_CAP - K) gp.max_fin = FIN_CAP - K;
   gp.V = c.n_vocab; gp.n_text_ctx = g->NT;
   pl.sot_pos = r0.sot_pos;   // (uniform runs; a ragged run reads each chunk's own, see the prompt forward)
-  gp.with_ts = r0.with_ts;
-  gp.suppress_blank = o->suppress_blank ? 1 : 0;
-  gp.min_new = o->min_new_tokens;
-  gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
-  gp.ngram = o->no_repeat_ngram_size;
-  gp.rep_pen = o->repetition_penalty;
+  fwd::fill_rule_fields(gp, c, o, r0.with_ts);
   gp.lp_pow = o->length_penalty;
-  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
-  gp.n_sup_begin = c.n_suppress_begin;
-  for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
   return FW_OK;
 }
 
@@ -936,11 +928,7 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   FW_HIP(hipMemsetAsync(g->n_fin, 0, Rr * sizeof(int), st));
   FW_HIP(hipMemsetAsync(g->d_step, 0, sizeof(int), st));
   FW_HIP(hipMemsetAsync(g->no_speech, 0, Rr * sizeof(float), st));
-  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
-  for (int i = 0; i < o->n_suppress_tokens; ++i) {
-    const int t = o->suppress_tokens[i];
-    if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
-  }
+  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
@@ -1842,16 +1830,8 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   GenDev& gp = sc.gp;
   // one decode chunk per sequence, one cache slot each; H of them per encoder chunk (g->slot_map holds the B pool slots)
   gp.B = Bx; gp.K = 1; gp.kv_div = H; gp.cache_rows = Bx;
-  if (rules) {
-    gp.with_ts = with_ts;
-    gp.suppress_blank = rules->suppress_blank ? 1 : 0;
-    gp.mits = fwd::initial_timestamp_limit(rules->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
-    gp.ngram = rules->no_repeat_ngram_size;
-    gp.rep_pen = rules->repetition_penalty;
-    gp.n_sup_begin = c.n_suppress_begin;
-    for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
-  }
-  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
+  fwd::fill_rule_fields(gp, c, rules, with_ts);
+  gp.min_new = 0;   // a given token is scored, none is generated: min_new_tokens is not a rule of scoring (include/fwamd.h)
 
   std::vector<int> ptok((size_t)n_pos * Bx);
   std::vector<fwd::ScoreRow> tab((size_t)Bx * n_pos, fwd::ScoreRow{-1, 0, 0, 0});
@@ -1877,12 +1857,9 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
+  std::vector<unsigned long long> mask;   // (lives until the synchronize below)
   if (rules) {
-    for (int i = 0; i < rules->n_suppress_tokens; ++i) {
-      const int t = rules->suppress_tokens[i];
-      if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
-    }
+    mask = fwd::suppress_mask(rules->suppress_tokens, rules->n_suppress_tokens, c.n_vocab);
     FW_HIP_AS(setup_fail, hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
   }
   FW_HIP_AS(setup_fail, hipStreamSynchronize(st));

@@ -905,20 +905,8 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   gp.n_alt = n_alt;
   gp.sample = sampling ? 1 : 0;
   gp.inv_temp = 1.0f;   // (sampling: temperature and seed per row, from the table below — as in a decode run)
-  gp.with_ts = with_timestamps ? 1 : 0;
-  gp.suppress_blank = o->suppress_blank ? 1 : 0;
-  gp.min_new = o->min_new_tokens;
-  gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
-  gp.ngram = o->no_repeat_ngram_size;
-  gp.rep_pen = o->repetition_penalty;
-  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
-  gp.n_sup_begin = c.n_suppress_begin;
-  for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
-  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
-  for (int i = 0; i < o->n_suppress_tokens; ++i) {
-    const int t = o->suppress_tokens[i];
-    if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
-  }
+  fwd::fill_rule_fields(gp, c, o, with_timestamps);
+  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
   const size_t NT = (size_t)c.n_text_ctx;
   std::vector<int> h2(2 * (size_t)R * NT, 0);
   std::vector<float> c2(2 * (size_t)R, 0.f);
@@ -1085,22 +1073,9 @@ int32_t fw_test_score_rows(fw_model* fm, float* logits, int32_t rows, const int3
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.B = rows; gp.K = 1; gp.R = rows; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1;
-  gp.eot = c.tok_eot; gp.no_ts = c.tok_no_timestamps; gp.ts_begin = c.tok_timestamp_begin;
-  gp.rep_pen = 1.0f;
-  std::vector<unsigned long long> mask(LP_SUP_WORDS, 0ull);
-  if (o) {
-    gp.with_ts = with_timestamps ? 1 : 0;
-    gp.suppress_blank = o->suppress_blank ? 1 : 0;
-    gp.mits = fwd::initial_timestamp_limit(o->max_initial_timestamp_index, c.n_vocab, c.tok_timestamp_begin);
-    gp.ngram = o->no_repeat_ngram_size;
-    gp.rep_pen = o->repetition_penalty;
-    gp.n_sup_begin = c.n_suppress_begin;
-    for (int i = 0; i < c.n_suppress_begin; ++i) gp.sup_begin[i] = c.suppress_begin[i];
-    for (int i = 0; i < o->n_suppress_tokens; ++i) {
-      const int t = o->suppress_tokens[i];
-      if (t >= 0 && t < c.n_vocab) mask[t >> 6] |= 1ull << (t & 63);
-    }
-  }
+  fwd::fill_rule_fields(gp, c, o, with_timestamps);
+  gp.min_new = 0;   // as fw_score: min_new_tokens is not a rule of scoring
+  const std::vector<unsigned long long> mask = fwd::suppress_mask(o ? o->suppress_tokens : nullptr, o ? o->n_suppress_tokens : 0, c.n_vocab);
   const size_t n_hist = (size_t)hist_offsets[rows];
   const int zero = 0;
   HookBufs db;

@@ -636,7 +636,7 @@ def _logsumexp(x: np.ndarray) -> np.float32:
 
 
 def _gumbel(seed: int, row: int, step: int, n: int) -> np.ndarray:
-    """counter-based Gumbel noise, same integer hash as dec_kernels.hip::gumbel_noise"""
+    """counter-based Gumbel noise, same integer hash as dec_vocab.hip::gumbel_noise"""
     M = np.uint64(0xFFFFFFFF)
     v = np.arange(n, dtype=np.uint64)
     h = (np.uint64(seed & 0xFFFFFFFF) ^ ((np.uint64(row) * np.uint64(0x9E3779B9)) & M)
@@ -647,7 +647,7 @@ def _gumbel(seed: int, row: int, step: int, n: int) -> np.ndarray:
     h ^= h >> np.uint64(13)
     h = (h * np.uint64(0xC2B2AE35)) & M
     h ^= h >> np.uint64(16)
-    # 23 bits keep u strictly inside (0, 1) in float32 (see gumbel_noise in dec_kernels.hip)
+    # 23 bits keep u strictly inside (0, 1) in float32 (see gumbel_noise in dec_vocab.hip)
     u = ((h >> np.uint64(9)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 8388608.0)
     return (-np.log(-np.log(u))).astype(np.float32)
 

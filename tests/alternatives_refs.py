@@ -1,5 +1,5 @@
-"""Plain numpy references of the alternatives bookkeeping (dec_kernels.hip: the ALT instantiations of the rules kernel and of
-the beam update, dec_alt_gather_kernel), on top of token_logprob_refs.beam_update_lp_ref, which stays the reference of
+"""Plain numpy references of the alternatives bookkeeping (the ALT instantiations of the rules kernel, dec_vocab.hip, and of the
+beam update, dec_kernels.hip, and dec_alt_gather_kernel), on top of token_logprob_refs.beam_update_lp_ref, which stays the reference of
 everything the existing contract covers.
 
   * top_n: the first n of a row's extraction — log-prob descending, id ascending, (0, -inf) once nothing is left;

@@ -6,7 +6,7 @@ import numpy as np
 
 SENT_F = -1234.0            # what every candidate slot holds before a launch (floats)
 SENT_I = -77                # ... and the id slots
-STRIDE = 32                 # candidate slots per row (dec_kernels.hip: 2 K at max_beam = 16)
+STRIDE = 32                 # candidate slots per row (dec_vocab.hip: 2 K at max_beam = 16)
 GAP = 2.4e-4                # smallest gap the distinct families must leave among a row's best 2K + 1 values
 
 

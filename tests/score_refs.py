@@ -1,7 +1,7 @@
 """References of the scoring tests (tests/test_score_refs.py on the CPU, tests/test_gpu_score_kernel.py and
 tests/test_gpu_score.py on the GPU).  No GPU here.
 
-  * the scoring kernel (dec_kernels.hip: dec_score_kernel) restated in float64, row by row: the raw log-softmax, or the
+  * the scoring kernel (dec_vocab.hip: dec_score_kernel) restated in float64, row by row: the raw log-softmax, or the
     decoding rules first — WHICH ids the rules forbid is asked of the oracle (oracle/whisper.py::_process_logits on the
     row's history; rule (e) included), the one float32 operation the rules contain (the repetition penalty, v * p or
     v / p once per distinct history id) is applied as the kernel's contract states it, and the log-softmax of what is

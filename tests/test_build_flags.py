@@ -4,7 +4,8 @@ moves per 64-key tile of a vector-bound kernel, 548 vs 405 vector instructions, 
 bump that drops or renames the option would silently cost 4-5 % of the encoder attention.  This test compiles the file the way
 build.sh does and checks what the flag buys: no AGPRs in `attn_enc_kernel` and a register count that still lets three waves per
 SIMD in; and that every kernel of the decoder file stays out of scratch memory (a wave-uniform branch around array elements
-once put the LayerNorm sums of dec_gemm_big_kernel there: profiles/NOTES.md, round 6)."""
+once put the LayerNorm sums of dec_gemm_big_kernel there: profiles/NOTES.md, round 6); and that the kernels which hold a
+vocabulary row in registers (dec_vocab.hip) still do."""
 import os
 import re
 import shutil
@@ -61,3 +62,17 @@ def test_decoder_kernels_use_no_scratch_memory():
     capped = ("dec_cross_attn_kernelILi8ELb1ELi5E", "dec_cross_attn_kernelILi8ELb1ELi6E")
     spilled = {n: v for n, v in res.items() if int(v.get("ScratchSize", 0)) != 0 and not any(c in n for c in capped)}
     assert not spilled, spilled
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")
+def test_vocabulary_row_kernels_keep_the_row_in_registers():
+    """dec_vocab.hip: the rules kernel and the scoring kernel hold 56 values of the row per thread, and a workgroup is 1 024
+    threads: past 128 registers it cannot be launched, and a value in scratch memory is a round trip per use.  Both call
+    the same device functions for the row, so one edit there moves all ten instantiations."""
+    res = _resources("dec_vocab.hip", [])
+    assert len(res) == 12 and not {n: v for n, v in res.items() if int(v.get("ScratchSize", 0)) != 0}, res
+    k = {n: v for n, v in res.items() if "dec_logits_process_kernel" in n or "dec_score_kernel" in n}
+    assert len(k) == 10, list(res)        # <SMP, TXI, ALT>: 2 x 2 x 2, and <RULES>: 2
+    for n, v in k.items():
+        assert int(v["ScratchSize"]) == 0, (n, v)
+        assert int(v["VGPRs"]) <= 128, (n, v)

@@ -1,4 +1,4 @@
-"""The logits-rules kernel (dec_kernels.hip: dec_logits_process_kernel — suppress lists, repetition penalty, no-repeat
+"""The logits-rules kernel (dec_vocab.hip: dec_logits_process_kernel — suppress lists, repetition penalty, no-repeat
 n-gram, the five timestamp rules, fp32 log-softmax, top-2K candidates of cum + logp; Gumbel arg-max when sampling)
 against the oracle's restatement of CTranslate2's logits processors (oracle/whisper.py::_process_logits, SURVEY.md
 A.3), ONE launch on seeded random logits through the C ABI test hook fw_test_logits_rules.

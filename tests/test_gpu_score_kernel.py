@@ -1,4 +1,4 @@
-"""The scoring kernel (dec_kernels.hip: dec_score_kernel — the log-prob of a GIVEN token per logits row, raw or after the
+"""The scoring kernel (dec_vocab.hip: dec_score_kernel — the log-prob of a GIVEN token per logits row, raw or after the
 decoding rules, with the row's arg-max) alone: ONE launch per case through the C ABI test hook fw_test_score_rows on
 seeded logits rows, against the float64 restatement of tests/score_refs.py (tests/test_score_refs.py shows on the CPU
 what those inputs hold, and that rule (e) is never a tie on them: no row is excluded here).
@@ -133,6 +133,55 @@ def test_measured_error_over_all_seeds(env):
     rules = max(_run_rules(env, s) for s in sr.SEEDS)
     print(f"[V={cfg.n_vocab}] MEASURED over seeds {sr.SEEDS}: raw {raw:.3e}, rules {rules:.3e}; ABS_TOL {ABS_TOL:.1e}")
     assert max(raw, rules) < ABS_TOL
+
+
+def _rules_kernel_first(model, logits, hists, rules, with_ts):
+    """the rules kernel on the same rows through fw_test_logits_rules_lp — greedy, beam 1, min_new_tokens 0, cum 0, one
+    launch per history length (that hook takes one n per launch) -> (cand_tok[0], cand_lp[0]) of every row"""
+    from faster_whisper_amd import _lib
+    o, keep = _opts(**rules)
+    o.beam_size, o.num_hypotheses, o.sampling_topk, o.min_new_tokens = 1, 1, 1, 0
+    o.patience, o.length_penalty = 1.0, 1.0
+    R = logits.shape[0]
+    tok = np.full(R, sr.SENT_I, np.int32)
+    lp = np.full(R, sr.SENT_F, np.float32)
+    for n in sorted({len(h) for h in hists}):
+        rows = [r for r in range(R) if len(hists[r]) == n]
+        lg = np.ascontiguousarray(logits[rows], np.float32)
+        h = np.ascontiguousarray([hists[r] for r in rows], np.int32).reshape(len(rows), n) if n else np.zeros((len(rows), 1), np.int32)
+        cum = np.zeros(len(rows), np.float32)
+        cv, ct = np.zeros((len(rows), 2), np.float32), np.full((len(rows), 2), sr.SENT_I, np.int32)
+        cl = np.full((len(rows), 2), sr.SENT_F, np.float32)
+        _lib.check(model._lib.fw_test_logits_rules_lp(model._replicas[0].handle, _lib.ptr(lg), len(rows), _lib.ptr(h), n,
+                                                      _lib.ptr(cum), C.byref(o), int(with_ts), _lib.ptr(cv), _lib.ptr(ct),
+                                                      _lib.ptr(cl)))
+        tok[rows], lp[rows] = ct[:, 0], cl[:, 0]
+    return tok, lp
+
+
+def test_same_bits_as_the_rules_kernel(env):
+    """The contract Whisper.score documents, at kernel level: a row scored against the rules kernel's first candidate
+    gets that candidate's id as its arg-max and the BITS of its log-prob, as the target's value and as the best value
+    (the two kernels hold and reduce the row through the same device functions, dec_vocab.hip).  Every rule-mode row of
+    score_refs.rule_cases, and two rows with nothing left (all -inf): id 0 at -inf on both sides.  No tolerance."""
+    cfg, model = env
+    cases = [(what, lg, hists, opt, with_ts) for what, lg, _, hists, opt, with_ts in sr.rule_cases(cfg, sr.SEEDS[0])]
+    dead = np.full((2, cfg.n_vocab), -np.inf, np.float32)
+    cases.append(("everything masked", dead, [[], [40, 41]], dict(suppress_tokens=lr.suppress_list(cfg)), True))
+    for what, lg, hists, opt, with_ts in cases:
+        hists = [list(h) for h in hists]
+        tok, lp = _rules_kernel_first(model, lg, hists, opt, with_ts)
+        got = _launch(model, lg, tok, hists, opt, with_ts)
+        print(f"[V={cfg.n_vocab}] {what}: rules kernel {tok.tolist()} {lp.tolist()}; score kernel {got['best_id'].tolist()} "
+              f"{got['best_lp'].tolist()} {got['lp'].tolist()}")
+        assert (tok >= 0).all() and not np.isnan(lp).any(), (what, tok, lp)
+        assert np.array_equal(got["best_id"], tok), (what, got["best_id"], tok)
+        assert np.array_equal(lr.bits(got["best_lp"]), lr.bits(lp)), (what, got["best_lp"], lp)
+        assert np.array_equal(lr.bits(got["lp"]), lr.bits(lp)), (what, got["lp"], lp)
+        if what == "everything masked":
+            assert (tok == 0).all() and (lp == -np.inf).all(), (tok, lp)
+        else:
+            assert np.isfinite(lp).all(), (what, lp)
 
 
 def test_hook_refuses_ids_out_of_range(env):
