@@ -91,6 +91,8 @@ SYMBOLS = [
     "fw_vad_forward_audio_batch_dev",
     "fw_flac_info", "fw_flac_decode",
     "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
+    "fw_boost_create", "fw_boost_free", "fw_generate_boost", "fw_score_boost",
+    "fw_test_boost_rows", "fw_test_boost_rows_host",
 ]
 
 _lib = None
@@ -234,6 +236,15 @@ def load():
     if hasattr(lib, "fw_score"):                    # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_score.argtypes = [vp, vp, i32p, i32p, i32p, i32p, i32, i32, C.POINTER(FwGenOpts), f32p, i32p, f32p]
         lib.fw_test_score_rows.argtypes = [vp, vp, i32, vp, vp, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp]
+    if hasattr(lib, "fw_boost_create"):             # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_boost_create.argtypes = [i32, i32p, i32p, i32, f32p, C.POINTER(vp)]
+        lib.fw_boost_free.argtypes = [vp]
+        lib.fw_boost_free.restype = None
+        lib.fw_generate_boost.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32, vp, i32p, i32p, f32p, f32p,
+                                          f32p, f32p, i32p, f32p, i32p, f32p]
+        lib.fw_score_boost.argtypes = [vp, vp, i32p, i32p, i32p, i32p, i32, i32, C.POINTER(FwGenOpts), vp, f32p, i32p, f32p]
+        lib.fw_test_boost_rows.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp]
+        lib.fw_test_boost_rows_host.argtypes = [vp, i32, vp, vp, vp]
     if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

@@ -149,6 +149,49 @@ class WhisperScoringResult:
                 f"end_logprobs={self.end_logprobs})")
 
 
+class BoostList:
+    """A validated, compiled list of phrases to boost (fwamd.h: fw_boost_create): phrases[j] is a sequence of token ids,
+    boosts[j] the float added to the logit of the phrase's next token wherever the generated history ends with the tokens
+    in front of it (the first token: at every step).  Where several phrases ask for one id the largest boost counts, not the
+    sum; the decoding rules run after the boost and still win.  Host-only: needs no device.  Whisper.boost_list builds one
+    for the model's vocabulary; pass it as generate(boost=...) / score(boost=...)."""
+
+    def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]], boosts: Sequence[float]):
+        phrases = [list(p) for p in phrases]
+        boosts = list(boosts)
+        if len(phrases) != len(boosts):
+            raise ValueError(f"got {len(phrases)} phrases and {len(boosts)} boosts")
+        lib = _lib.load()
+        if not hasattr(lib, "fw_boost_create"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_boost_create: phrase boosting needs a current build")
+        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
+        b = np.asarray(boosts, dtype=np.float32).reshape(-1)
+        self.n_vocab = int(n_vocab)
+        self.n_phrases = len(phrases)
+        self._handle = C.c_void_p()
+        _lib.check(lib.fw_boost_create(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
+                                       _lib.as_f32p(b) if b.size else None, C.byref(self._handle)))
+
+    def __len__(self):
+        return self.n_phrases
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            try:
+                _lib.load().fw_boost_free(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+
+
+def _boost_handle(boost):
+    if boost is None:
+        return None
+    if not isinstance(boost, BoostList):
+        raise TypeError("boost must be a BoostList (Whisper.boost_list) or None")
+    return boost._handle
+
+
 class _Replica:
     """one fw_model on one GPU"""
 
@@ -540,6 +583,13 @@ class Whisper:
         _lib.check(self._lib.fw_logmel_full(rep.handle, _lib.ptr(w), w.shape[0], _lib.ptr(out), nf))
         return out
 
+    # ---- phrase boosting ----------------------------------------------------------------
+    def boost_list(self, phrases: Sequence[Sequence[int]], boosts: Sequence[float]) -> BoostList:
+        """A BoostList for this model's vocabulary: phrases[j] a sequence of token ids, boosts[j] its strength in logit
+        units.  ValueError (fwamd.h: FW_BOOST_MAX_PHRASES / _LEN / _TOKENS): more than 1024 phrases, a phrase of no token or
+        more than 32, more than 4096 tokens in all, an id outside the vocabulary, a boost that is not finite."""
+        return BoostList(self._cfg.n_vocab, phrases, boosts)
+
     # ---- generate -----------------------------------------------------------------------
     def generate(self, features: StorageView, prompts: List[List[int]], *, asynchronous: bool = False,
                  beam_size: int = 5, patience: float = 1, num_hypotheses: int = 1, length_penalty: float = 1,
@@ -549,9 +599,14 @@ class Whisper:
                  suppress_tokens: Optional[Sequence[int]] = (-1,), sampling_topk: int = 1,
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
                  seed: Optional[int] = None, return_token_logprobs: bool = False,
-                 return_alternatives: int = 0) -> List[WhisperGenerationResult]:
+                 return_alternatives: int = 0, boost: Optional[BoostList] = None) -> List[WhisperGenerationResult]:
+        """boost (not in CTranslate2): a BoostList (boost_list()) whose phrases are made more likely at the logit, in front
+        of the decoding rules; None or an empty list: the call without it."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
+        boost_h = _boost_handle(boost)
+        if boost_h is not None and not hasattr(self._lib, "fw_generate_boost"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_generate_boost: phrase boosting needs a current build")
         n_alt = int(return_alternatives)
         if not 0 <= n_alt <= MAX_ALTERNATIVES:
             raise ValueError(f"return_alternatives must lie in [0, {MAX_ALTERNATIVES}] (got {return_alternatives})")
@@ -588,18 +643,26 @@ class Whisper:
             nsp = np.zeros((B,), dtype=np.float32)
             args = (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o),
                     _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp))
+            tlp = elp = aid = alp = eid = elps = None
             if return_token_logprobs:
+                tlp = np.zeros((B, nh, ml), dtype=np.float32)
+                elp = np.zeros((B, nh), dtype=np.float32)
+            if n_alt:
+                aid = np.zeros((B, nh, ml, n_alt), dtype=np.int32)
+                alp = np.zeros((B, nh, ml, n_alt), dtype=np.float32)
+                eid = np.zeros((B, nh, n_alt), dtype=np.int32)
+                elps = np.zeros((B, nh, n_alt), dtype=np.float32)
+            if boost_h is not None:
+                def f32(a): return _lib.as_f32p(a) if a is not None else None
+                def i32(a): return _lib.as_i32p(a) if a is not None else None
+                _lib.check(self._lib.fw_generate_boost(*args[:6], n_alt, boost_h, *args[6:], f32(tlp), f32(elp), i32(aid),
+                                                       f32(alp), i32(eid), f32(elps)))
+            elif return_token_logprobs:
                 need = "fw_generate_alt" if n_alt else "fw_generate_lp"
                 if not hasattr(self._lib, need):   # an older build loaded through FWAMD_LIB
                     raise RuntimeError(f"this libfwamd.so has no {need}: per-token log-probabilities"
                                        f"{' and alternatives' if n_alt else ''} need a current build")
-                tlp = np.zeros((B, nh, ml), dtype=np.float32)
-                elp = np.zeros((B, nh), dtype=np.float32)
                 if n_alt:
-                    aid = np.zeros((B, nh, ml, n_alt), dtype=np.int32)
-                    alp = np.zeros((B, nh, ml, n_alt), dtype=np.float32)
-                    eid = np.zeros((B, nh, n_alt), dtype=np.int32)
-                    elps = np.zeros((B, nh, n_alt), dtype=np.float32)
                     _lib.check(self._lib.fw_generate_alt(*args[:6], n_alt, *args[6:], _lib.as_f32p(tlp), _lib.as_f32p(elp),
                                                          _lib.as_i32p(aid), _lib.as_f32p(alp), _lib.as_i32p(eid),
                                                          _lib.as_f32p(elps)))
@@ -676,13 +739,15 @@ class Whisper:
                           max_initial_timestamp_index=50)
 
     def score(self, features: StorageView, prompts: List[List[int]], targets, *, rules: bool = False,
-              **rule_kwargs) -> List[WhisperScoringResult]:
+              boost: Optional[BoostList] = None, **rule_kwargs) -> List[WhisperScoringResult]:
         """Teacher-forced log-probs of given transcripts (fwamd.h: fw_score; not in CTranslate2's Whisper class).
         targets[b]: one sequence of ids, or a list of up to max_beam_size sequences, scored against chunk b.
         rules=False: the raw distribution.  rules=True: the distribution generate()'s search ranks by, with generate's
         rule keywords and their defaults (repetition_penalty, no_repeat_ngram_size, suppress_blank, suppress_tokens,
         max_initial_timestamp_index); the timestamp rules follow the prompt.  result.score(h, length_penalty=1) is then
-        what generate(return_scores=True) reports for the same ids."""
+        what generate(return_scores=True) reports for the same ids.
+        boost: the BoostList of a generate(boost=...) call, added in front of the rules with the sequence's own prefix as the
+        generated history; needs rules=True."""
         unknown = set(rule_kwargs) - set(self._RULE_DEFAULTS)
         if unknown:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
@@ -690,6 +755,11 @@ class Whisper:
             raise ValueError(f"{sorted(rule_kwargs)} need rules=True: without it the raw distribution is scored")
         if not hasattr(self._lib, "fw_score"):   # an older build loaded through FWAMD_LIB
             raise RuntimeError("this libfwamd.so has no fw_score: scoring needs a current build")
+        boost_h = _boost_handle(boost)
+        if boost_h is not None and not rules:
+            raise ValueError("boost needs rules=True: the boost is the first step of the decoding rules")
+        if boost_h is not None and not hasattr(self._lib, "fw_score_boost"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_score_boost: phrase boosting needs a current build")
         enc = self._as_encoded(features)
         if len(prompts) != enc._shape[0] or len(targets) != enc._shape[0]:
             raise ValueError(f"got {len(prompts)} prompts and {len(targets)} targets for a batch of {enc._shape[0]}")
@@ -723,9 +793,13 @@ class Whisper:
             lp = np.zeros((n_out,), dtype=np.float32)
             bid = np.zeros((n_out,), dtype=np.int32)
             blp = np.zeros((n_out,), dtype=np.float32)
-            _lib.check(self._lib.fw_score(enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs),
-                                          _lib.as_i32p(tflat), _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None,
-                                          _lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp)))
+            head = (enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs), _lib.as_i32p(tflat),
+                    _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None)
+            outs = (_lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp))
+            if boost_h is not None:
+                _lib.check(self._lib.fw_score_boost(*head, boost_h, *outs))
+            else:
+                _lib.check(self._lib.fw_score(*head, *outs))
             out = []
             for b in range(B):
                 res = WhisperScoringResult([], [], [], [], [])

@@ -38,6 +38,9 @@ struct GenDev {
   // ALTERNATIVES (fw_generate_alt): the rules kernel also records the row's n_alt most likely ids per step (the largest
   // n_alt of the run's calls, <= FW_MAX_ALTERNATIVES).  0 in every run that records none: the key and the kernels of today.
   int n_alt;
+  // BOOST (fw_generate_boost): 1 when the step launches dec_boost_kernel in front of the rules kernel.  0 in every run
+  // without a list: the key and the graphs of today.  The table's sizes travel in the table's header, not here.
+  int boost;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -207,4 +210,44 @@ void launch_score(hipStream_t st, const GenDev& gp, bool rules, const float* log
                   const ScoreRow* tab, int tab_stride, int pos0, int nb, int rows, const int* hist_pool, float* out_lp,
                   int* out_best_id, float* out_best_lp);
 
+// ---- phrase boosting (include/fwamd.h: fw_boost; kernel and table compiler: dec_boost.hip) ----
+// The compiled table, 32-bit words: a header {G groups, E entries, T phrase tokens, n_vocab}, then
+//   grp_id [G]      the target ids, ascending: one group per distinct id some phrase holds
+//   grp_off [G + 1] group g owns entries grp_off[g] .. grp_off[g + 1]
+//   ent [E][3]      one per pair (j, k): {start of phrase j in tok, k, the bits of boosts[j]}; target id = tok[start + k]
+//   tok [T]         the phrases back to back
+// E == T (every token of every phrase is the target of exactly one pair), G <= E <= FW_BOOST_MAX_TOKENS.
+constexpr int BOOST_HDR_WORDS = 4;
+constexpr int BOOST_TABLE_MAX_WORDS = BOOST_HDR_WORDS + 2 * FW_BOOST_MAX_TOKENS + 1 + 3 * FW_BOOST_MAX_TOKENS + FW_BOOST_MAX_TOKENS;
+struct BoostView {
+  int G, E, T;
+  const int *grp_id, *grp_off, *ent, *tok;
+};
+static __host__ __device__ inline BoostView boost_view(const int* tab) {
+  BoostView v;
+  v.G = tab[0]; v.E = tab[1]; v.T = tab[2];
+  v.grp_id = tab + BOOST_HDR_WORDS;
+  v.grp_off = v.grp_id + v.G;
+  v.ent = v.grp_off + v.G + 1;
+  v.tok = v.ent + 3 * v.E;
+  return v;
+}
+// dec_boost_kernel, decode-step form, in front of launch_logits_process: row r of gp.R rows reads its history from the
+// parity half of hist2 that *d_step selects (n = step), rows of chunks with done[r / gp.K] are skipped.  logits [gp.R][gp.V]
+// IN / OUT: logits[r][v] += boost(v) for the ids with a matching pair, every other value keeps its bits.
+void launch_boost_step(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const int* hist2,
+                       const int* d_step, const int* done);
+// ... score form, in front of launch_score, same row addressing: rows without a target (target < 0) are skipped, the
+// history is the ScoreRow's.  Every n <= n_text_ctx, every table built by fw_boost_create for gp.V: the caller's to guarantee.
+void launch_boost_score(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const ScoreRow* tab,
+                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// the same walk in plain C++ (fw_test_boost_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
+
 }  // namespace fwd
+
+// what fw_boost_create returns: the list's vocabulary size and its compiled table (above)
+struct fw_boost {
+  int32_t n_vocab;
+  std::vector<int32_t> table;
+};

@@ -100,6 +100,10 @@ struct GenWorkspace {
   GrowBuf<int> alt_out_tok;              // the gather's output: [returned hypotheses][budget + 1][n_alt]
   GrowBuf<float> alt_out_lp;
   GrowBuf<fwd::AltHyp> alt_hyps;
+  // phrase boosting (fw_generate_boost): the run's compiled table.  Nothing until the first boosted run, which allocates it
+  // at its maximum size (fwd::BOOST_TABLE_MAX_WORDS): the pointer never changes afterwards, so a cached step graph stays
+  // valid whatever list the next run brings — the sizes travel in the table's header — and no graph holds a caller's pointer.
+  GrowBuf<int> boost_tab;
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -576,6 +580,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   if (s.beam_tail) {
     ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
     const bool alt = gp.n_alt > 0;   // (run_alt_ensure has sized the buffers for this run)
+    // the boost comes first: the rules below see the boosted logits (run_init_state has filled the table for this run)
+    if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
                                alt ? g->alt_lp.p : nullptr);
@@ -705,6 +711,7 @@ struct GenRequest {
   float* out_alt_logprobs = nullptr;
   int32_t* out_end_alt_ids = nullptr;    // [B, num_hypotheses, n_alt]
   float* out_end_alt_logprobs = nullptr;
+  const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
   bool sampling;
   int with_ts = 1, sot_pos = -1;   // from the prompt: no <|notimestamps|> -> timestamp rules; position of <sot>
   int rc = FW_OK;
@@ -719,8 +726,11 @@ struct GenRequest {
 // row reads its call's from the run's SmpRow table.  The PROMPT LENGTH and
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
+// BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
+  if ((a.boost != nullptr) != (b.boost != nullptr)) return false;
+  if (a.boost && a.boost != b.boost && a.boost->table != b.boost->table) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -857,6 +867,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.ragged = ragged ? 1 : 0; gp.reach = ragged ? reach : 0;   // (part of the step graph's key)
   gp.sample = sampling ? 1 : 0;
   gp.n_alt = n_alt;
+  gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
   gp.inv_temp = 1.0f; gp.seed_lo = 0; gp.seed_hi = 0;
@@ -930,6 +941,12 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   FW_HIP(hipMemsetAsync(g->no_speech, 0, Rr * sizeof(float), st));
   const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
+  if (pl.gp.boost) {   // the run's boost table, into the lane's buffer (allocated once, at its maximum size)
+    const std::vector<int32_t>& tab = reqs[0]->boost->table;
+    FW_CHECK_ARG(tab.size() <= (size_t)fwd::BOOST_TABLE_MAX_WORDS, "boost table of %zu words", tab.size());
+    if (int rc = g->boost_tab.ensure(fwd::BOOST_TABLE_MAX_WORDS)) return rc;
+    FW_HIP(hipMemcpyAsync(g->boost_tab.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
+  }
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
   ptok.assign((size_t)Pmax * Bx, 0);
@@ -1354,6 +1371,16 @@ int32_t fw_generate_alt(fw_model* fm, const fw_tensor* enc_t, const int32_t* pro
                         float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
                         int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
                         float* out_end_alt_logprobs) {
+  return fw_generate_boost(fm, enc_t, prompts, prompt_offsets, B, o, n_alt, nullptr, out_ids, out_lens, out_scores,
+                           out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids, out_alt_logprobs,
+                           out_end_alt_ids, out_end_alt_logprobs);
+}
+
+int32_t fw_generate_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                          int32_t B, const fw_gen_opts* o, int32_t n_alt, const fw_boost* boost, int32_t* out_ids,
+                          int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
+                          float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs,
+                          int32_t* out_end_alt_ids, float* out_end_alt_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
@@ -1370,6 +1397,8 @@ int32_t fw_generate_alt(fw_model* fm, const fw_tensor* enc_t, const int32_t* pro
   FW_CHECK_ARG(decoder_of(*enc) == dm, "encoder output belongs to a different model");
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= dm->max_batch, "batch %d exceeds max_batch %d", B, dm->max_batch);
+  FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
+               boost ? boost->n_vocab : 0, c.n_vocab);
   const int K = o->beam_size;
   FW_CHECK_ARG(K >= 1 && K <= dm->max_beam, "beam_size %d not in [1, max_beam=%d]", K, dm->max_beam);
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
@@ -1415,6 +1444,7 @@ int32_t fw_generate_alt(fw_model* fm, const fw_tensor* enc_t, const int32_t* pro
   req.n_alt = n_alt; req.out_alt_ids = out_alt_ids; req.out_alt_logprobs = out_alt_logprobs;
   req.out_end_alt_ids = out_end_alt_ids; req.out_end_alt_logprobs = out_end_alt_logprobs;
   req.sampling = sampling;
+  req.boost = (boost && boost->table[0] > 0) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -1769,7 +1799,17 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
                             const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
                             const fw_gen_opts* rules, float* out_token_logprobs, int32_t* out_best_ids,
                             float* out_best_logprobs) {
+  return fw_score_boost(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, nullptr, out_token_logprobs,
+                        out_best_ids, out_best_logprobs);
+}
+
+// fw_score with a boost list: dec_boost_kernel on the block's logits (recomputed per block) in front of the scoring kernel
+extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                                  const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                                  const fw_gen_opts* rules, const fw_boost* boost, float* out_token_logprobs,
+                                  int32_t* out_best_ids, float* out_best_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
+  FW_CHECK_ARG(!boost || rules, "a boost list needs rules: the boost is the first step of the decoding rules");
   FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
   Model* m = decoder_of(&fm->impl);
   const Tensor* enc = &enc_t->impl;
@@ -1777,6 +1817,9 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
   FW_CHECK_ARG(decoder_of(*enc) == m, "encoder output belongs to a different model");
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= m->max_batch, "batch %d exceeds max_batch %d", B, m->max_batch);
+  FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
+               boost ? boost->n_vocab : 0, c.n_vocab);
+  if (boost && boost->table[0] == 0) boost = nullptr;   // (an empty list does nothing)
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
   FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
   const int Bx = B * H;
@@ -1854,6 +1897,11 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
       (rc = tmp.alloc(&lp_dev, n_out)))
     return rc;
   if (out_best_ids && ((rc = tmp.alloc(&bid_dev, n_out)) || (rc = tmp.alloc(&blp_dev, n_out)))) return rc;
+  int* boost_dev = nullptr;
+  if (boost) {
+    if ((rc = tmp.alloc(&boost_dev, boost->table.size()))) return rc;
+    FW_HIP_AS(setup_fail, hipMemcpyAsync(boost_dev, boost->table.data(), boost->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
   FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1872,6 +1920,7 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
       [&](int pos, int nb) {
         if (pos + nb - 1 < P - 1) return;
         ProfScope ps(lane->prof, PF_DEC_MISC, 0, 4.0 * Bx * nb * (double)c.n_vocab, st);
+        if (boost_dev) fwd::launch_boost_score(st, gp, g->logits, boost_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         fwd::launch_score(st, gp, rules != nullptr, g->logits, g->sup_bits, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev, lp_dev,
                           bid_dev, blp_dev);
       });

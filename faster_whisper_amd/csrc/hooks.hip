@@ -1098,6 +1098,89 @@ int32_t fw_test_score_rows(fw_model* fm, float* logits, int32_t rows, const int3
   return download(logits, d_lg, (size_t)rows * c.n_vocab);
 }
 
+// the histories of a boost hook: offsets from 0, non-decreasing, every n below `n_limit` (< 0: no limit), every id in [0, V)
+static int32_t boost_hist_check(int32_t rows, const int32_t* hist, const int32_t* hist_offsets, int n_limit, int V) {
+  FW_CHECK_ARG(hist_offsets[0] == 0, "hist_offsets must start at 0");
+  for (int r = 0; r < rows; ++r) {
+    const int64_t n = (int64_t)hist_offsets[r + 1] - hist_offsets[r];
+    FW_CHECK_ARG(n >= 0 && (n_limit < 0 || n < n_limit) && (n == 0 || hist), "row %d: a history of %lld ids", r, (long long)n);
+    for (int i = 0; i < n; ++i) {
+      const int t = hist[hist_offsets[r] + i];
+      FW_CHECK_ARG(t >= 0 && t < V, "hist of row %d, entry %d = %d outside [0, %d)", r, i, t, V);
+    }
+  }
+  return FW_OK;
+}
+
+// ONE launch of dec_boost_kernel in either row form (include/fwamd_test.h); everything is checked before anything is
+// allocated or launched.
+int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                           int32_t K, const int32_t* done, int32_t form, const fw_boost* boost) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  Model* m = &fm->impl;
+  const fw_config& c = m->cfg;
+  FW_CHECK_ARG(boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
+               boost->n_vocab, c.n_vocab);
+  FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, c.n_text_ctx, c.n_vocab)) return rc;
+  const int n0 = hist_offsets[1];
+  if (form == 0)
+    for (int r = 0; r < rows; ++r)
+      FW_CHECK_ARG(hist_offsets[r + 1] - hist_offsets[r] == n0, "form 0 takes one n for all rows (row %d)", r);
+  const int n_done = form == 0 ? rows / K : rows;
+  if (done)
+    for (int b = 0; b < n_done; ++b) FW_CHECK_ARG(done[b] == 0 || done[b] == 1, "done[%d] = %d is not 0 / 1", b, done[b]);
+  FW_HIP(hipSetDevice(m->device));
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.B = rows / K; gp.K = K; gp.R = rows; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.boost = 1;
+  HookBufs db;
+  float* d_lg;
+  int* d_tab;
+  int rc;
+  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * c.n_vocab)) ||
+      (rc = db.upload(&d_tab, (const int*)boost->table.data(), boost->table.size())))
+    return rc;
+  if (form == 0) {
+    const size_t NT = (size_t)c.n_text_ctx;
+    std::vector<int> h2(2 * (size_t)rows * NT, 0), dn((size_t)rows, 0);
+    for (int r = 0; r < rows; ++r)
+      for (int i = 0; i < n0; ++i) h2[((size_t)(n0 & 1) * rows + r) * NT + i] = hist[hist_offsets[r] + i];
+    if (done) std::copy(done, done + n_done, dn.begin());
+    int *d_hist, *d_step, *d_done;
+    if ((rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n0, 1)) ||
+        (rc = db.upload(&d_done, dn.data(), dn.size())))
+      return rc;
+    fwd::launch_boost_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
+  } else {
+    std::vector<fwd::ScoreRow> tab((size_t)rows);
+    for (int r = 0; r < rows; ++r)
+      tab[r] = {(done && done[r]) ? -1 : 0, hist_offsets[r + 1] - hist_offsets[r], hist_offsets[r], r};
+    const size_t n_hist = (size_t)hist_offsets[rows];
+    const int zero = 0;
+    fwd::ScoreRow* d_rows;
+    int* d_hist;
+    if ((rc = db.upload(&d_rows, tab.data(), tab.size())) ||
+        (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
+      return rc;
+    fwd::launch_boost_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
+  }
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipDeviceSynchronize());
+  return download(logits, d_lg, (size_t)rows * c.n_vocab);
+}
+
+// the same table walked on the host: no device, no model
+int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                const fw_boost* boost) {
+  FW_CHECK_ARG(logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, boost->n_vocab)) return rc;
+  const int zero = 0;
+  fwd::boost_rows_host(boost->table.data(), logits, rows, boost->n_vocab, hist ? hist : &zero, hist_offsets);
+  return FW_OK;
+}
+
 // step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together
 int32_t fw_test_graph_captures(const fw_model* fm, int64_t* out) {
   FW_CHECK_ARG(fm && out, "null argument");

@@ -112,6 +112,19 @@ def _value_keywords(token_logprobs: bool, token_alternatives: int, logprobs_key:
     return {logprobs_key: True} if token_logprobs else {}
 
 
+class _BuiltBoost:
+    """a boost list that is built already, in the place of transcribe()'s boost_phrases: how transcribe_many hands ONE list
+    to the transcribe() of every recording"""
+
+    def __init__(self, boost):
+        self.boost = boost
+
+
+def _boost_keyword(boost) -> dict:
+    """the keyword a call passes down for its boost list — only when it has one (as _value_keywords)"""
+    return {} if boost is None else {"boost": boost}
+
+
 @dataclass
 class TranscriptionOptions:
     beam_size: int
@@ -161,6 +174,16 @@ def _transcription_options(args, tokenizer: "Tokenizer", **derived) -> Transcrip
     if values["suppress_tokens"]:
         values["suppress_tokens"] = get_suppressed_tokens(tokenizer, values["suppress_tokens"])
     return TranscriptionOptions(**{f.name: values[f.name] for f in fields(TranscriptionOptions)})
+
+
+def _check_boost_arguments(boost_phrases, phrase_boost) -> None:
+    """boost_phrases: None, or a sequence of strings; with phrases phrase_boost must be given (ValueError)"""
+    if boost_phrases is None or isinstance(boost_phrases, _BuiltBoost):
+        return
+    if isinstance(boost_phrases, (str, bytes)) or not all(isinstance(p, str) for p in boost_phrases):
+        raise ValueError("boost_phrases must be a sequence of strings, one per phrase")
+    if len(boost_phrases) and phrase_boost is None:
+        raise ValueError("boost_phrases need phrase_boost: the strength of the boost in logit units has no default")
 
 
 def _per_recording(value, n, name, is_single):
@@ -484,7 +507,8 @@ class WhisperModel:
                    hallucination_silence_threshold: Optional[float] = None, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
-                   token_alternatives: int = 0):
+                   token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
+                   phrase_boost: Optional[float] = None):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -497,8 +521,12 @@ class WhisperModel:
         sampling_seed (not in the reference): makes the sampled attempts of the temperature fallback reproducible.  The
         attempt at rung t of the ladder for the window at frame `seek` samples with backend.attempt_seed(sampling_seed,
         seek, t): the same recording with the same seed gives the same transcript whatever else the model decodes before
-        or beside it.  None (the default): every sampling call takes the next seed of the model's call counter."""
+        or beside it.  None (the default): every sampling call takes the next seed of the model's call counter.
+        boost_phrases, phrase_boost (not in the reference): see boost_list_for — names and terms made more likely by
+        phrase_boost at the logit, in every window and every attempt of the fallback ladder, without spending prompt text
+        as `hotwords` does."""
         args = dict(locals())               # the call's arguments by name
+        _check_boost_arguments(boost_phrases, phrase_boost)
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
@@ -538,6 +566,7 @@ class WhisperModel:
             temperatures=(temperature if isinstance(temperature, (list, tuple)) else [temperature]))
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
                                           **_value_keywords(token_logprobs, token_alternatives),
+                                          **_boost_keyword(self.boost_list_for(boost_phrases, phrase_boost, tokenizer)),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
@@ -571,10 +600,18 @@ class WhisperModel:
         meet in a decode run (they do: sampling calls share runs among themselves) each draw what they draw alone.
         Without sampling_seed the sampled attempts take their seeds from the model's call counter in arrival order, and
         which recording gets which seed depends on timing.
+        boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcribe(), so the
+        windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
         An exception in one recording is raised here, after the recordings already started have finished."""
         n = len(audios)
+        _check_boost_arguments(transcribe_kwargs.get("boost_phrases"), transcribe_kwargs.get("phrase_boost"))
         if n == 0:
             return []
+        if transcribe_kwargs.get("boost_phrases") is not None:
+            # (the text encoding does not depend on task or language: any tokenizer of the model gives the same ids)
+            built = self.boost_list_for(transcribe_kwargs["boost_phrases"], transcribe_kwargs.get("phrase_boost"),
+                                        self.make_tokenizer())
+            transcribe_kwargs = dict(transcribe_kwargs, boost_phrases=None if built is None else _BuiltBoost(built))
         languages = _per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
         prompts = _per_recording(
             initial_prompt, n, "initial_prompt",
@@ -605,7 +642,7 @@ class WhisperModel:
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
                           token_logprobs: bool = False, sampling_seed: Optional[int] = None,
-                          token_alternatives: int = 0):
+                          token_alternatives: int = 0, boost=None):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -661,6 +698,7 @@ class WhisperModel:
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
                     encoder_output, prompt, tokenizer, options, **_value_keywords(token_logprobs, token_alternatives),
+                    **_boost_keyword(boost),
                     **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
@@ -713,13 +751,15 @@ class WhisperModel:
 
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
                                options: TranscriptionOptions, token_logprobs: bool = False,
-                               sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0):
+                               sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0,
+                               boost=None):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
         attempt (preferring those under the compression threshold) is returned with the last temperature.
         sampling_seed: the sampled attempt at rung t gets seed=attempt_seed(sampling_seed, seek, t), `seek` the window's
         first frame; None: no seed is passed, the backend draws one from its call counter.
+        boost: the call's boost list (boost_list_for), the same one for every attempt.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
         max_initial_timestamp_index = int(round(options.max_initial_timestamp / self.time_precision))
         max_length = self._max_length_for(prompt, options.max_new_tokens)
@@ -738,7 +778,7 @@ class WhisperModel:
                 repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
                 max_length=max_length, return_scores=True, return_no_speech_prob=True,
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
-                max_initial_timestamp_index=max_initial_timestamp_index, **mode,
+                max_initial_timestamp_index=max_initial_timestamp_index, **mode, **_boost_keyword(boost),
                 **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))[0]
             avg_logprob = _avg_logprob(result, options.length_penalty)
             compression_ratio = get_compression_ratio(tokenizer.decode(result.sequences_ids[0]).strip())
@@ -763,6 +803,24 @@ class WhisperModel:
             best = max(compact or attempts, key=lambda a: a[1])
             chosen = (best[0], best[1], temperature, best[3])   # last temperature drives the prompt reset
         return chosen
+
+    def boost_list_for(self, boost_phrases, phrase_boost, tokenizer: Tokenizer):
+        """The boost list of a transcribe() call (backend.Whisper.boost_list), or None without phrases.  Every phrase is
+        encoded as " " + phrase.strip(), the form `hotwords` uses: ONE variant per phrase — the word as it stands after a
+        space, in the caller's casing; a caller who wants the capitalised or the sentence-initial form boosted lists it as
+        a phrase of its own.  All phrases get the strength phrase_boost (logit units; where phrases share a prefix the
+        boost counts once: the list takes the maximum, not the sum).  phrase_boost has no default: no measurement on real
+        speech stands behind any value, so phrases without a strength are a ValueError.  The list is built once per call
+        and reused for every window, every attempt of the temperature ladder and every batch."""
+        _check_boost_arguments(boost_phrases, phrase_boost)
+        if boost_phrases is None:
+            return None
+        if isinstance(boost_phrases, _BuiltBoost):
+            return boost_phrases.boost
+        phrases = [tokenizer.encode(" " + p.strip()) for p in boost_phrases]
+        if not phrases:
+            return None
+        return self.model.boost_list(phrases, [float(phrase_boost)] * len(phrases))
 
     def make_tokenizer(self, task="transcribe", language="en") -> Tokenizer:
         return Tokenizer(self.hf_tokenizer, self.model.config, self.model.is_multilingual, task=task, language=language)
@@ -947,12 +1005,13 @@ class BatchedInferencePipeline:
     # ---- one batch: encode + generate ---------------------------------------------------
     def generate_segment_batched(self, features, tokenizer: Tokenizer, options: TranscriptionOptions,
                                  audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False,
-                                 token_alternatives: int = 0):
+                                 token_alternatives: int = 0, boost=None):
         """features: [B, n_mels, 3000] float32, or None when `audio_chunks` is given (fused resident
         PCM -> log-mel -> encoder path; the features never leave HBM).  token_logprobs: every output dict also carries
         the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`);
         token_alternatives=N: those, and the N most likely (id, log-prob) pairs per token (`token_alternatives`) and at
-        the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget)."""
+        the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget).  boost: the call's boost list
+        (WhisperModel.boost_list_for), passed to generate when there is one."""
         m = self.model
         batch_size = len(audio_chunks) if audio_chunks is not None else features.shape[0]
         prompt = m.get_prompt(tokenizer,
@@ -975,7 +1034,7 @@ class BatchedInferencePipeline:
             length_penalty=options.length_penalty, max_length=max_length, suppress_blank=options.suppress_blank,
             suppress_tokens=options.suppress_tokens, return_scores=True, return_no_speech_prob=True,
             sampling_temperature=options.temperatures[0], repetition_penalty=options.repetition_penalty,
-            no_repeat_ngram_size=options.no_repeat_ngram_size,
+            no_repeat_ngram_size=options.no_repeat_ngram_size, **_boost_keyword(boost),
             **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))
         output = []
         for r in results:
@@ -1034,7 +1093,8 @@ class BatchedInferencePipeline:
                    batch_size: int = 8, hotwords: Optional[str] = None,
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    shard: bool = False, fused_features: bool = True, vad_speech_probs=None,
-                   token_logprobs: bool = False, token_alternatives: int = 0):
+                   token_logprobs: bool = False, token_alternatives: int = 0,
+                   boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1044,10 +1104,12 @@ class BatchedInferencePipeline:
         shard=True: inside a torch.distributed job every rank calls this with the same arguments; the
         chunk list is block-partitioned over the ranks and rank 0's generator yields ALL segments in
         order (other ranks yield nothing).  fused_features=False reproduces the reference data flow
-        (features materialised on the host, then encode())."""
+        (features materialised on the host, then encode()).
+        boost_phrases, phrase_boost (not in the reference): see WhisperModel.boost_list_for — one list for every batch."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model
+        _check_boost_arguments(boost_phrases, phrase_boost)
         if (token_logprobs or token_alternatives) and shard:
             raise ValueError("token_logprobs / token_alternatives are not offered with shard=True: the gathered records "
                              "carry no per-token values")
@@ -1067,7 +1129,8 @@ class BatchedInferencePipeline:
         self._plan_decode(rec, args, language, multilingual, {})
         gen = self._batched_segments_generator(rec.audio_chunks, rec.tokenizer, rec.chunks_metadata, batch_size,
                                                rec.options, log_progress, shard, fused_features,
-                                               **_value_keywords(token_logprobs, token_alternatives))
+                                               **_value_keywords(token_logprobs, token_alternatives),
+                                               **_boost_keyword(m.boost_list_for(boost_phrases, phrase_boost, rec.tokenizer)))
         return self._on_recording_time(rec, gen), rec.info
 
     # ---- the steps of transcribe that transcribe_many runs per recording -----------------
@@ -1173,7 +1236,7 @@ class BatchedInferencePipeline:
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
                                     log_progress, shard=False, fused_features=True, token_logprobs=False,
-                                    token_alternatives=0):
+                                    token_alternatives=0, boost=None):
         from .sharding import gather_results, partition
         m = self.model
         rank, world, local_rank = 0, 1, 0
@@ -1197,7 +1260,7 @@ class BatchedInferencePipeline:
                 spans = [(lo, mid), (mid, hi)]
             return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
                                             for i0, i1 in spans], shard, fused_features, token_logprobs,
-                                           token_alternatives)
+                                           token_alternatives, boost)
 
         def emit(results):
             nonlocal seg_idx
@@ -1244,13 +1307,14 @@ class BatchedInferencePipeline:
         self.last_speech_timestamp = 0.0
 
     def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
-                      token_logprobs=False, token_alternatives=0):
+                      token_logprobs=False, token_alternatives=0, boost=None):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
         m = self.model
         feats = None if fused_features else m.model.log_mel(chunks)
         enc, outs = self.generate_segment_batched(feats, tokenizer, options,
                                                   audio_chunks=chunks if fused_features else None,
-                                                  **_value_keywords(token_logprobs, token_alternatives))
+                                                  **_value_keywords(token_logprobs, token_alternatives),
+                                                  **_boost_keyword(boost))
         local = aligned = None
         if not shard or options.word_timestamps:
             local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
@@ -1260,7 +1324,8 @@ class BatchedInferencePipeline:
                                         options.append_punctuations)
         return outs, local, aligned
 
-    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False, token_alternatives=0):
+    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False, token_alternatives=0,
+                           boost=None):
         """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
         The batches are independent (`condition_on_previous_text=False`): with worker replicas
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
@@ -1269,7 +1334,7 @@ class BatchedInferencePipeline:
         workers = self.model._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
-                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives)
+                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives, boost)
             return
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
@@ -1277,7 +1342,7 @@ class BatchedInferencePipeline:
             pending = deque()
             for job in jobs:
                 pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs,
-                                           token_alternatives))
+                                           token_alternatives, boost))
                 if len(pending) >= workers:
                     yield pending.popleft().result()
             while pending:
@@ -1322,6 +1387,7 @@ class BatchedInferencePipeline:
         a = a.arguments
         m = self.model
         n = len(audios)
+        _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
         if n == 0:
             return []
         multilingual = m._effective_multilingual(a["multilingual"])
@@ -1381,9 +1447,11 @@ class BatchedInferencePipeline:
                 owners.append([rec for rec, _, _ in part])
 
         # ---- route: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
+        # (ONE boost list for the batches of every recording and language: the text encoding is the vocabulary's)
+        boost = m.boost_list_for(a["boost_phrases"], a["phrase_boost"], next(iter(tokenizers.values())))
         for owner, (_, local, aligned) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
                                                                               a["token_logprobs"],
-                                                                              a["token_alternatives"])):
+                                                                              a["token_alternatives"], boost)):
             for j, rec in enumerate(owner):
                 rec.decoded.append(local[j])
                 if aligned is not None:

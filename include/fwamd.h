@@ -15,6 +15,7 @@
  *   .detect_language   transcribe.py:215,1193,1823      -> fw_detect_language
  *   .align             transcribe.py:1709-1715          -> fw_align
  *   .score             (not in the reference: CTranslate2's score_batch for Whisper) -> fw_score
+ *   boost=             (not in the reference: phrase boosting at the logit) -> fw_boost_create, fw_generate_boost, fw_score_boost
  *
  * plus the log-mel front end the reference runs in numpy on the host
  * (faster_whisper/feature_extractor.py:198-230, called at
@@ -55,7 +56,8 @@ extern "C" {
  *    fw_resample_filter and fw_resample_dev were added within version 2 (new symbols only: nothing existing changed),
  *    fw_vad_forward_audio_batch_dev likewise, fw_generate_lp (fw_generate plus per-token log-probabilities) and
  *    fw_score (teacher-forced log-probs of given transcripts), fw_generate_alt (fw_generate_lp plus the n most
- *    likely tokens at every position) */
+ *    likely tokens at every position), fw_boost_create / fw_boost_free / fw_generate_boost / fw_score_boost (phrases made
+ *    more likely by a stated amount, at the logit) */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -180,7 +182,8 @@ int32_t fw_model_create_from_blob_dev(const fw_config* cfg, const void* blob_dev
  * fw_generate calls that arrive from different host threads while a decode run is in progress are merged into the
  * next run (up to decode_batch chunks); each caller gets exactly the result it would get alone.  What must agree for two
  * calls to share a run: beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
- * max_length, max_initial_timestamp_index, suppress_blank, min_new_tokens, the suppress list, and the timestamp mode
+ * max_length, max_initial_timestamp_index, suppress_blank, min_new_tokens, the suppress list, the boost list
+ * (fw_generate_boost: none on both sides, or byte-equal compiled tables), and the timestamp mode
  * (<|notimestamps|> in the prompt or not).  Sampling calls (beam_size 1, sampling_topk 0) merge among themselves, never with
  * beam or greedy calls; their sampling_temperature and seed need NOT agree (every row of a run draws with its own call's,
  * as the row of that call that it is alone).  The PROMPT LENGTH and the position of
@@ -305,6 +308,43 @@ int32_t fw_generate_alt(fw_model* m, const fw_tensor* enc, const int32_t* prompt
                         int32_t* out_alt_ids, float* out_alt_logprobs,          /* [B, num_hypotheses, max_length, n_alt] */
                         int32_t* out_end_alt_ids, float* out_end_alt_logprobs); /* [B, num_hypotheses, n_alt] */
 
+/* ---- phrase boosting (contextual biasing; not in CTranslate2) ----------------
+ * A boost list is n_phrases phrases.  Phrase j is the token-id sequence p_j[0 .. L_j) = tokens[offsets[j] .. offsets[j + 1])
+ * with one float boosts[j].  Consider a row whose GENERATED history is h[0 .. n) (generated tokens only, timestamps
+ * included, never the prompt).  The pair (j, k), 0 <= k < L_j, MATCHES when k <= n and h[n - k .. n) == p_j[0 .. k); k = 0
+ * always matches, so a phrase's first token is boosted at every step.  The boost of an id v is the MAXIMUM boosts[j] over
+ * all matching pairs with p_j[k] == v — a max, never a sum: phrase [a, a, a] after history [a, a] boosts `a` once — and
+ * logit[v] += boost(v) is one fp32 add.  Ids with no matching pair keep their bits.
+ * The boost comes FIRST; the rules then run exactly as always (repetition penalty, no-repeat n-gram, suppress, timestamp
+ * rules, log-softmax).  So the rules still win (a forbidden id stays -inf), token log-probs, alternatives and scores are
+ * those of the boosted, processed distribution, and sampling draws from it.  There is no back-off (nothing is subtracted
+ * when a match breaks) and no matching across the prompt boundary.
+ * fw_boost_create is host code: it needs no device and no model.  It validates the list and compiles it into the table the
+ * kernel walks (entries (j, k) grouped by target id: one worker owns one id and does one add).  FW_EINVAL: n_vocab < 1, a
+ * null pointer with n_phrases > 0, more than FW_BOOST_MAX_PHRASES phrases, offsets[0] != 0, a phrase of no token or of more
+ * than FW_BOOST_MAX_LEN, more than FW_BOOST_MAX_TOKENS tokens in all, an id outside [0, n_vocab), a boost that is not
+ * finite.  An empty list (n_phrases == 0; the pointers may be NULL) is valid and does nothing. */
+#define FW_BOOST_MAX_PHRASES 1024
+#define FW_BOOST_MAX_LEN 32
+#define FW_BOOST_MAX_TOKENS 4096
+typedef struct fw_boost fw_boost;   /* opaque: a validated, compiled boost list (host memory); any number of calls may read it at once */
+int32_t fw_boost_create(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
+                        const float* boosts, fw_boost** out);
+void fw_boost_free(fw_boost* b);
+/* fw_generate_alt plus a boost list.  boost == NULL (or an empty list) is fw_generate_alt exactly; FW_EINVAL when the list
+ * was built for another n_vocab than the model's.  Identity (1) of fw_generate_alt holds unchanged on boosted calls, and
+ * (2) with fw_score_boost in fw_score's place.  Two calls share a decode run only when both have no list or their compiled
+ * tables are byte-equal (lists built separately from equal arguments are): a boosted call never shares a run with a plain
+ * one; everything else about merging is unchanged, and every caller gets its solo result bit for bit.  A boosted run costs
+ * one small kernel launch per step more; its table is copied into a buffer of the decode lane at the start of the run
+ * (the list may be freed once the call has returned). */
+int32_t fw_generate_boost(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                          int32_t B, const fw_gen_opts* opts, int32_t n_alt, const fw_boost* boost,
+                          int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                          float* out_token_logprobs, float* out_end_logprobs,
+                          int32_t* out_alt_ids, float* out_alt_logprobs,
+                          int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
+
 /* ---- score ---------------------------------------------------------------
  * Teacher-forced log-probs of GIVEN transcripts (CTranslate2 has score_batch for its other model classes): how likely
  * is this text under the model, for text that was not decoded here — a corrected transcript, another system's output,
@@ -329,6 +369,14 @@ int32_t fw_generate_alt(fw_model* m, const fw_tensor* enc, const int32_t* prompt
 int32_t fw_score(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
                  const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
                  float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
+/* fw_score plus a boost list (above): the boost is added to every scored row's logits first, with the row's history —
+ * the sequence's own prefix — as the generated history, then the rules run.  boost == NULL (or an empty list) is fw_score
+ * exactly; boost != NULL needs rules != NULL (FW_EINVAL), and a list built for the model's n_vocab (FW_EINVAL).  For a
+ * greedy hypothesis of fw_generate_boost, fw_score_boost with the call's rules and list returns its out_token_logprobs
+ * and out_end_logprobs bit for bit, and out_best_ids / out_best_logprobs are its alternative 0. */
+int32_t fw_score_boost(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                       const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
+                       const fw_boost* boost, float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
 
 /* ---- detect_language -------------------------------------------------------
  * ctranslate2.models.Whisper.detect_language: one decoder step on [sot];

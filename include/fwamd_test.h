@@ -156,6 +156,22 @@ int32_t fw_test_alt_gather(fw_model* m, const int32_t* alt_tok, const float* alt
                            int32_t NT, int32_t n_alt, const uint8_t* fin_path, int32_t n_hyp, const int32_t* hyp_chunk,
                            const int32_t* hyp_fin, const int32_t* hyp_len, const int32_t* hyp_end, int32_t T,
                            int32_t* out_tok, float* out_lp);
+/* ONE launch of dec_boost_kernel (phrase boosting, include/fwamd.h) in either row form on caller-provided rows: logits
+ * [rows][n_vocab] IN / OUT, returned whole; row r's generated history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+ * (hist_offsets[0] == 0; hist may be NULL when every history is empty).
+ *   form 0, the decode step: every row has the SAME n (uniform offsets: checked), the histories are laid out as the
+ *           parity half of hist2 that step n selects and the device step counter holds n; rows % K == 0, 1 <= K <= 16;
+ *           done [rows / K] (0 / 1: checked) | NULL: the rows of a done chunk are skipped;
+ *   form 1, scoring: one ScoreRow per row, ragged histories; K must be 1; done [rows] | NULL: a row with done[r] != 0 has
+ *           no target (target < 0) and is skipped.
+ * Checked before anything is allocated or launched: the pointers, rows >= 1, form, K, every n < n_text_ctx, every history
+ * id in [0, n_vocab), the done values, and that the list was built for the model's n_vocab. */
+int32_t fw_test_boost_rows(fw_model* m, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                           int32_t K, const int32_t* done, int32_t form, const fw_boost* boost);
+/* host-only (no device, no model needed): the same table walked in plain C++ over logits [rows][n_vocab of the list]
+ * IN / OUT with ragged histories as above — what fw_boost_create compiled, testable without a GPU */
+int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                const fw_boost* boost);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
