@@ -93,6 +93,7 @@ SYMBOLS = [
     "fw_resample_filter", "fw_resample_dev", "fw_bench_resample",
     "fw_boost_create", "fw_boost_free", "fw_generate_boost", "fw_score_boost",
     "fw_test_boost_rows", "fw_test_boost_rows_host",
+    "fw_generate_trunc", "fw_test_logits_rules_trunc",
 ]
 
 _lib = None
@@ -245,6 +246,11 @@ def load():
         lib.fw_score_boost.argtypes = [vp, vp, i32p, i32p, i32p, i32p, i32, i32, C.POINTER(FwGenOpts), vp, f32p, i32p, f32p]
         lib.fw_test_boost_rows.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp]
         lib.fw_test_boost_rows_host.argtypes = [vp, i32, vp, vp, vp]
+    if hasattr(lib, "fw_generate_trunc"):           # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_generate_trunc.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32, C.c_float, i32, vp, i32p, i32p,
+                                          f32p, f32p, f32p, f32p, i32p, f32p, i32p, f32p]
+        lib.fw_test_logits_rules_trunc.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp, i32, vp, vp]
     if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

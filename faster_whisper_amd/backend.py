@@ -599,14 +599,23 @@ class Whisper:
                  suppress_tokens: Optional[Sequence[int]] = (-1,), sampling_topk: int = 1,
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
                  seed: Optional[int] = None, return_token_logprobs: bool = False,
-                 return_alternatives: int = 0, boost: Optional[BoostList] = None) -> List[WhisperGenerationResult]:
+                 return_alternatives: int = 0, boost: Optional[BoostList] = None, top_k: int = 0,
+                 top_p: float = 1.0) -> List[WhisperGenerationResult]:
         """boost (not in CTranslate2): a BoostList (boost_list()) whose phrases are made more likely at the logit, in front
-        of the decoding rules; None or an empty list: the call without it."""
+        of the decoding rules; None or an empty list: the call without it.
+        top_k / top_p (not in CTranslate2's generate(); fwamd.h: fw_generate_trunc): limits on the draw of a SAMPLING call
+        (beam_size 1, sampling_topk 0) — the top_k most likely tokens, then the nucleus holding top_p of their tempered
+        mass.  0 / 1.0: no limit, and the call is the one it always was.  ValueError: top_k < 0, top_p outside (0, 1], a
+        limit on a call that does not sample.  Token log-probs and alternatives stay those of the whole distribution."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
         boost_h = _boost_handle(boost)
         if boost_h is not None and not hasattr(self._lib, "fw_generate_boost"):   # an older build loaded through FWAMD_LIB
             raise RuntimeError("this libfwamd.so has no fw_generate_boost: phrase boosting needs a current build")
+        top_k, top_p = int(top_k), float(top_p)
+        trunc = top_k != 0 or top_p != 1.0   # (NaN included: the engine refuses it)
+        if trunc and not hasattr(self._lib, "fw_generate_trunc"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_generate_trunc: top_k / top_p need a current build")
         n_alt = int(return_alternatives)
         if not 0 <= n_alt <= MAX_ALTERNATIVES:
             raise ValueError(f"return_alternatives must lie in [0, {MAX_ALTERNATIVES}] (got {return_alternatives})")
@@ -652,9 +661,12 @@ class Whisper:
                 alp = np.zeros((B, nh, ml, n_alt), dtype=np.float32)
                 eid = np.zeros((B, nh, n_alt), dtype=np.int32)
                 elps = np.zeros((B, nh, n_alt), dtype=np.float32)
-            if boost_h is not None:
-                def f32(a): return _lib.as_f32p(a) if a is not None else None
-                def i32(a): return _lib.as_i32p(a) if a is not None else None
+            def f32(a): return _lib.as_f32p(a) if a is not None else None
+            def i32(a): return _lib.as_i32p(a) if a is not None else None
+            if trunc:
+                _lib.check(self._lib.fw_generate_trunc(*args[:6], top_k, top_p, n_alt, boost_h, *args[6:], f32(tlp), f32(elp),
+                                                       i32(aid), f32(alp), i32(eid), f32(elps)))
+            elif boost_h is not None:
                 _lib.check(self._lib.fw_generate_boost(*args[:6], n_alt, boost_h, *args[6:], f32(tlp), f32(elp), i32(aid),
                                                        f32(alp), i32(eid), f32(elps)))
             elif return_token_logprobs:

@@ -41,6 +41,10 @@ struct GenDev {
   // BOOST (fw_generate_boost): 1 when the step launches dec_boost_kernel in front of the rules kernel.  0 in every run
   // without a list: the key and the graphs of today.  The table's sizes travel in the table's header, not here.
   int boost;
+  // TRUNC (fw_generate_trunc): 1 when some call of a sampling run limits its draw (top_k > 0 or top_p < 1): the step then
+  // launches the TRUNC instantiations of the rules kernel, which read a TruncRow per row.  0 in every other run: the key,
+  // the kernels and the graphs of today.
+  int trunc;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -85,6 +89,15 @@ struct SmpRow {
   int row0;                // first row of the entry's call inside the run
 };
 static_assert(sizeof(SmpRow) == 16, "one 16-byte load per row");
+
+// Truncated sampling (fw_generate_trunc): the limits of the row's CALL, one entry per decode row, beside the SmpRow table and
+// not inside it: SmpRow stays one 16-byte load for the kernels that never truncate, and only the TRUNC instantiations
+// read this one (one uniform 8-byte load).  (0, 1.0): the row draws from its whole distribution.
+struct TruncRow {
+  int top_k;               // >= 0; 0: no limit
+  float top_p;             // in (0, 1]; 1: no limit
+};
+static_assert(sizeof(TruncRow) == 8, "one 8-byte load per row");
 
 // ptab != null (decode steps of a ragged run; ignored with an explicit position): [chunks] prompt length per chunk, the
 // position of chunk c is min(ptab[c] - 1 + step, reach - 1) instead of P - 1 + step; kmul = rows per chunk
@@ -158,7 +171,14 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
                            int* cand_tok, float* cand_lp = nullptr, const SmpRow* smp_tab = nullptr,
-                           int* alt_tok = nullptr, float* alt_lp = nullptr);
+                           int* alt_tok = nullptr, float* alt_lp = nullptr, const TruncRow* trunc_tab = nullptr);
+// TRUNC (gp.trunc != 0: sampling launches only, and trunc_tab [gp.R] must be given — otherwise nothing is launched): the
+// TRUNC instantiations; a row whose entry is (0, 1.0) skips the stage and gets the bits of the plain sampling kernel.
+// (the TRUNC launches themselves: dec_trunc.hip; called by launch_logits_process only)
+void launch_logits_process_trunc(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
+                                 const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
+                                 int* cand_tok, float* cand_lp, const SmpRow* smp_tab, int* alt_tok, float* alt_lp,
+                                 const TruncRow* trunc_tab);
 // ALTERNATIVES (gp.n_alt > 0 and both alt pointers given, otherwise today's kernels): alt_tok / alt_lp [steps][gp.R][n_alt],
 // row r at step s writes the first n_alt rounds of its extraction (log-prob descending, id ascending; (0, -inf) once
 // nothing is left) to [s][r][.] — the registers cand_lp is written from; a sampling row runs n_alt plain rounds on the

@@ -3,6 +3,9 @@
 // the score of a given token (dec_score_kernel), and the two plain softmax probabilities (dec_nospeech_kernel,
 // dec_token_prob_kernel).  The rules and the score kernel promise each other's bits for the same row: everything the two
 // do alike is ONE device function below, called by both.
+// dec_trunc.hip includes this file with DEC_VOCAB_TRUNC_UNIT defined: it then holds the row helpers and the kernel templates
+// only, and that unit instantiates the TRUNC forms of the rules kernel (this one never does: its kernels stay the twelve
+// they were).
 #include "common.h"
 #include "dec_kernels.h"
 
@@ -30,6 +33,7 @@ static __device__ __forceinline__ float row_softmax_prob(const float* __restrict
   return __expf(lg[id] - m2) / tot;
 }
 
+#ifndef DEC_VOCAB_TRUNC_UNIT
 // K22: no-speech probability = softmax(logits at the <sot> position)[no_speech]
 __global__ __launch_bounds__(1024) void dec_nospeech_kernel(const float* __restrict__ logits, int V, int row_mul,
                                                             int no_speech_id, float* __restrict__ out) {
@@ -51,6 +55,7 @@ __global__ __launch_bounds__(1024) void dec_token_prob_kernel(const float* __res
   const float p = row_softmax_prob(logits + (size_t)b * row_mul * V, V, ok ? t : 0, red);
   if (threadIdx.x == 0) out[(size_t)b * out_stride + out_off] = ok ? p : 0.f;
 }
+#endif  // DEC_VOCAB_TRUNC_UNIT
 
 // ------------------------------------------------------------------------------------
 // K17/K18 (+ the row part of K19): logits rules, fp32 log-softmax and the row's top-C
@@ -271,6 +276,154 @@ static __device__ __forceinline__ void lp_block_argmax(float& k, int& t, float* 
   argmax_pair_step(k, t, dpp_f<FW_DPP_ROR8>(k), dpp_i<FW_DPP_ROR8>(t));
 }
 
+// ---- TRUNC: the cut of a truncated draw (fw_generate_trunc; include/fwamd.h states the contract) ----
+// The ids a row may draw are a PREFIX of the order (log-prob descending, id ascending), so the whole set is one pair:
+// S = {v : logp[v] > cut.lp, or logp[v] == cut.lp and v <= cut.id}.  Both limits are monotone measures of a threshold t on
+// the log-prob — the COUNT of ids at or above t for top-k, their tempered MASS for the nucleus — so one bisection serves
+// both: over the order-preserving integer image of the fp32 value (31 rounds whatever k), which ends on the boundary
+// VALUE exactly; the ids that share that value are then told apart by a second bisection over the id (16 rounds, taken
+// only when the cut falls inside a tie group).  A round is one pass over the 56 registers, the 16 wave partials through
+// LDS and ONE barrier (partials double-buffered).  Counts never leave the scalar unit (popcount of the compare mask);
+// masses are summed per thread in ascending i, over the wave by wave_sum_v, over the waves in ascending order: a fixed
+// order, no atomics, so a row gets the same cut wherever and however often it runs.  val[] is only read.
+struct LpCut { float lp; int id; };
+// the image: u(x) < u(y) <=> x < y over the floats without NaN; x is a log-prob here (<= 0, -inf for a masked id)
+static __device__ __forceinline__ unsigned lp_img(float x) {
+  const unsigned b = __builtin_bit_cast(unsigned, x + 0.0f);   // (-0 -> +0)
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+static __device__ __forceinline__ float lp_img_inv(unsigned u) {
+  return __builtin_bit_cast(float, (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+#define LP_IMG_NEG_INF 0x007FFFFFu   /* lp_img(-inf): every live value lies above */
+// a float every lane agrees on, held in a scalar register (a uniform float computed on the vector unit keeps a vector
+// register across the rounds)
+static __device__ __forceinline__ float lp_uniform(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+// workgroup totals of a per-wave scalar count / of per-thread masses; `rd` counts the rounds (their parity picks the buffer)
+static __device__ __forceinline__ int lp_block_sum_i(int c, int (&part)[2][LP_WAVES], int& rd, int lane, int wv) {
+  const int par = rd & 1;
+  ++rd;
+  if (lane == 0) part[par][wv] = c;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int i = 0; i < LP_WAVES; ++i) t += part[par][i];
+  return __builtin_amdgcn_readfirstlane(t);
+}
+static __device__ __forceinline__ float lp_block_sum_f(float s, int (&part)[2][LP_WAVES], int& rd, int lane, int wv) {
+  const int par = rd & 1;
+  ++rd;
+  s = wave_sum_v(s);
+  if (lane == 0) part[par][wv] = __builtin_bit_cast(int, s);
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < LP_WAVES; ++i) t += __builtin_bit_cast(float, part[par][i]);   // fixed order
+  return lp_uniform(t);
+}
+// this wave's ids with val >= t
+static __device__ __forceinline__ int lp_count_ge(const float (&val)[LP_NV], float t) {
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) c += __builtin_popcountll(__builtin_amdgcn_ballot_w64(val[i] >= t));
+  return c;
+}
+// this thread's tempered mass exp((logp - max logp) / T) of its ids with t_lo <= val < t_hi (lmax = -max logp); a group of
+// 64 ids with nothing in the window costs two compares (the window shrinks by half per round)
+static __device__ __forceinline__ float lp_mass_window(const float (&val)[LP_NV], float t_lo, float t_hi, float lmax,
+                                                       float inv_temp) {
+  // (lmax behind an empty asm: the 56 exponents (val[i] + lmax) * inv_temp do not depend on the round, and hoisted out of
+  //  the bisection they are 56 more live registers beside the row)
+  asm volatile("" : "+s"(lmax));
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < LP_NV; ++i) {
+    const bool in = val[i] >= t_lo && val[i] < t_hi;
+    if (__builtin_amdgcn_ballot_w64(in) != 0ull) s += in ? __expf((val[i] + lmax) * inv_temp) : 0.f;
+  }
+  return s;
+}
+// the n-th lowest id (n >= 1, at most the group's size) among the ids with val == t
+static __device__ __forceinline__ int lp_nth_id(const float (&val)[LP_NV], float t, int n, int V, int (&part)[2][LP_WAVES],
+                                                int& rd, int tid, int lane, int wv) {
+  int lo = -1, hi = V - 1;   // ids <= lo hold fewer than n of the group, ids <= hi at least n
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    // (t behind an empty asm: 56 compare masks `val[i] == t` hoisted out of the rounds are 112 scalar registers, which
+    //  spill into vector registers and push eight values of the row into scratch)
+    asm volatile("" : "+s"(t), "+v"(tid));   // (tid: likewise, the ids of these rounds are their own)
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < LP_NV; ++i)
+      // (the id test against a scalar: `tid + i * LP_THREADS <= mid` would keep 56 hoisted ids alive across the rounds)
+      c += __builtin_popcountll(__builtin_amdgcn_ballot_w64(val[i] == t && tid <= mid - i * LP_THREADS));
+    if (lp_block_sum_i(c, part, rd, lane, wv) >= n) hi = mid; else lo = mid;
+  }
+  return hi;
+}
+// val[]: the row's plain log-probs; lmax: lse.l (the row's best log-prob is (m - m) - l = -l exactly); every argument but
+// val and the thread's own indices is uniform, and so is every branch and trip count below.
+static __device__ __forceinline__ LpCut lp_trunc_cut(const float (&val)[LP_NV], int V, float lmax_v, float inv_temp, int top_k,
+                                                     float top_p, int tid, int lane, int wv) {
+  __shared__ int part[2][LP_WAVES];
+  const float lmax = lp_uniform(lmax_v);
+  int rd = 0;
+  LpCut cut = {-INFINITY, LP_NONE};   // everything that is live
+  const int n_live = lp_block_sum_i(lp_count_ge(val, lp_img_inv(LP_IMG_NEG_INF + 1u)), part, rd, lane, wv);
+  if (n_live == 0) return cut;
+  const unsigned img_top = lp_img(-lmax) + 1u;   // above every value of the row
+  // ---- top-k: the largest t with count(t) >= k, then the lowest ids of its tie group ----
+  int k_need = 0;   // ids S_k takes from the tie group at cut.lp (0: no top-k cut, cut.lp = -inf)
+  if (top_k >= 1 && top_k < n_live) {
+    unsigned lo = LP_IMG_NEG_INF, hi = img_top;   // count(lo) >= k > count(hi)
+    int c_lo = n_live, c_hi = 0;
+    while (hi - lo > 1u) {
+      const unsigned mid = lo + (hi - lo) / 2u;
+      const int c = lp_block_sum_i(lp_count_ge(val, lp_img_inv(mid)), part, rd, lane, wv);
+      if (c >= top_k) { lo = mid; c_lo = c; } else { hi = mid; c_hi = c; }
+    }
+    cut.lp = lp_img_inv(lo);
+    k_need = top_k - c_hi;
+    if (k_need < c_lo - c_hi) cut.id = lp_nth_id(val, cut.lp, k_need, V, part, rd, tid, lane, wv);
+  }
+  // ---- nucleus over S_k: the largest t with mass(t) >= p * Z, then as many ids of its tie group as stay below p * Z ----
+  if (top_p < 1.0f) {
+    const unsigned img_k = lp_img(cut.lp);
+    // Z: what lies above the top-k boundary value, plus the ids S_k takes at it (equal log-probs: equal weights)
+    const float w_k = k_need > 0 ? __expf((cut.lp + lmax) * inv_temp) : 0.f;
+    const float Z = lp_block_sum_f(lp_mass_window(val, lp_img_inv(img_k + 1u), INFINITY, lmax, inv_temp), part, rd, lane, wv) +
+                    (float)k_need * w_k;
+    const float target = lp_uniform(top_p * Z);
+    unsigned lo = img_k, hi = img_top;   // mass(lo) = Z >= target > mass(hi): lo itself is never evaluated
+    float m_hi = 0.f, t_hi = INFINITY;   // mass(hi), and hi as a value
+    while (hi - lo > 1u) {
+      const unsigned mid = lo + (hi - lo) / 2u;
+      const float t = lp_img_inv(mid);
+      const float m = lp_uniform(m_hi + lp_block_sum_f(lp_mass_window(val, t, t_hi, lmax, inv_temp), part, rd, lane, wv));
+      if (m >= target) lo = mid; else { hi = mid; m_hi = m; t_hi = t; }
+    }
+    // the boundary value's tie group inside S_k: g ids of weight w each, m_hi ahead of the first of them
+    const float t = lp_img_inv(lo);
+    int g = k_need;
+    if (lo != img_k) {
+      int c = 0;
+#pragma unroll
+      for (int i = 0; i < LP_NV; ++i) c += __builtin_popcountll(__builtin_amdgcn_ballot_w64(val[i] == t));
+      g = lp_block_sum_i(c, part, rd, lane, wv);
+    }
+    if (lo != img_k) { cut.lp = t; cut.id = LP_NONE; }
+    if (g > 0) {
+      const float w = __expf((t + lmax) * inv_temp);
+      const float need = ceilf((target - m_hi) / w);   // ids j = 0 .. with m_hi + j * w < target; the first is always in
+      const int n_in = !(need < (float)g) ? g : (need < 1.f ? 1 : (int)need);
+      if (n_in < g) cut.id = lp_nth_id(val, t, n_in, V, part, rd, tid, lane, wv);
+    }
+  }
+  return cut;
+}
+
 // Top-C: each thread keeps its own best (key, slot); a round is one block arg-max, and only the winning thread rescans
 // its 56 values.
 // TXI: the compile-time class split of lp_mask_reduce.
@@ -279,7 +432,12 @@ static __device__ __forceinline__ void lp_block_argmax(float& k, int& t, float* 
 // cand_lp is written from.  Beam / greedy: max(2K, n_alt) rounds, rounds < 2K fill cand_*, rounds < n_alt fill alt_*.
 // Sampling: the draw is round 0 and does NOT retire its value (nothing after it read the retired value; the token, its
 // cand_val and cand_lp keep their bits), then every thread finds its best plain log-prob and n_alt plain rounds follow.
-template <bool SMP, int TXI, bool ALT = false>
+// TRUNC (fw_generate_trunc; sampling only, instantiations of their own again): the row's (top_k, top_p) come from
+// trunc_tab[r]; the log-prob loop leaves the keys to a second loop, lp_trunc_cut runs between the two, and the key loop
+// gives an id outside the cut no key.  The noise of an id does not depend on the cut, val[] keeps the plain log-probs, and
+// what is recorded (cand_val, cand_lp, the alternatives) is read from val[] as always.  A row with (0, 1.0) skips the stage
+// (uniform) and every live id gets the key the plain sampling kernel gives it: the same draw, the same bits.
+template <bool SMP, int TXI, bool ALT = false, bool TRUNC = false>
 __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::GenDev gp, float* __restrict__ logits,
                                                                         const unsigned long long* __restrict__ sup_bits,
                                                                         const int* __restrict__ hist2,
@@ -291,7 +449,9 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
                                                                         float* __restrict__ cand_lp,
                                                                         const fwd::SmpRow* __restrict__ smp_tab,
                                                                         int* __restrict__ alt_tok,
-                                                                        float* __restrict__ alt_lp) {
+                                                                        float* __restrict__ alt_lp,
+                                                                        const fwd::TruncRow* __restrict__ trunc_tab) {
+  static_assert(SMP || !TRUNC, "only a sampled draw is truncated");
   __shared__ float red[4][LP_WAVES];
   __shared__ int sh_last_ts;
   __shared__ float bkey_s[2][LP_WAVES];
@@ -341,9 +501,12 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
   const unsigned long long kml = lp_rule_word(sup_bits, lp_lane_word(lane, wv), tsb, (n < gp.min_new) ? gp.eot : -1,
                                               gp.with_ts ? gp.no_ts : -1, n, gp);
   const LpClasses cls = lp_mask_reduce<TXI, true>(val, (unsigned)kml, (unsigned)(kml >> 32), tb, red, tid, lane, wv, LpNoPre());
-  const LpLse lse = lp_lse_split(cls, gp.with_ts != 0);
+  LpLse lse = lp_lse_split(cls, gp.with_ts != 0);
   // ---- log-probs; this thread's best key ----
-  const float cum = cum2[(size_t)cur * gp.R + r];
+  float cum = cum2[(size_t)cur * gp.R + r];
+  if (TRUNC) {   // (uniform values into scalar registers: the stage below needs the vector registers they would hold)
+    lse.m = lp_uniform(lse.m); lse.l = lp_uniform(lse.l); cum = lp_uniform(cum);
+  }
   constexpr bool smp = SMP;   // a separate instantiation: 2 x 56 inlined logf stay out of the beam / greedy kernel
   // sampling: temperature, seed and first row of this row's CALL (one uniform 16-byte load; the other instantiations
   // never touch the table).  The noise of a row depends on (seed of its call, row inside its call, step, token) only.
@@ -357,9 +520,27 @@ __global__ __launch_bounds__(LP_THREADS) void dec_logits_process_kernel(fwd::Gen
     const int v = tid + i * LP_THREADS;
     const float x = lp_logp(val[i], v, tb, lse);
     val[i] = x;
+    if (TRUNC) continue;   // (the keys follow the cut, below)
     float key = x;
     if (smp && x != NEG) key = x * sr.inv_temp + gumbel_noise(sr.seed_lo, sr.seed_hi, (unsigned)(r - sr.row0), (unsigned)step, (unsigned)v);
     if (key > bkey) { bkey = key; bq = i; }   // ascending index: ties keep the lowest
+  }
+  if (TRUNC) {
+    const fwd::TruncRow tr = trunc_tab[r];   // (uniform)
+    LpCut cut = {NEG, LP_NONE};
+    if (tr.top_k > 0 || tr.top_p < 1.0f) cut = lp_trunc_cut(val, gp.V, lse.l, sr.inv_temp, tr.top_k, tr.top_p, tid, lane, wv);
+    int tid_k = tid;
+    asm volatile("" : "+v"(tid_k));   // (the ids of this loop are its own: none is kept alive from the loops above)
+#pragma unroll
+    for (int i = 0; i < LP_NV; ++i) {
+      const int v = tid_k + i * LP_THREADS;
+      const float x = val[i];
+      const bool in = x != NEG && (x > cut.lp || (x == cut.lp && tid_k <= cut.id - i * LP_THREADS));
+      if (__builtin_amdgcn_ballot_w64(in) == 0ull) continue;   // (64 consecutive ids outside the cut: no noise is drawn for them)
+      float key = NEG;
+      if (in) key = x * sr.inv_temp + gumbel_noise(sr.seed_lo, sr.seed_hi, (unsigned)(r - sr.row0), (unsigned)step, (unsigned)v);
+      if (key > bkey) { bkey = key; bq = i; }
+    }
   }
   // ---- top-C of cum + logp: C rounds (value desc, index asc).  Sampling mode (Gumbel-max): one round on
   //      logp/T + Gumbel noise; the recorded score stays cum + logp. ----
@@ -531,6 +712,7 @@ __global__ __launch_bounds__(LP_THREADS) void dec_score_kernel(fwd::GenDev gp, c
   }
 }
 
+#ifndef DEC_VOCAB_TRUNC_UNIT
 namespace fwd {
 
 void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, int no_speech_id, float* out, int B) {
@@ -539,20 +721,25 @@ void launch_nospeech(hipStream_t st, const float* logits, int V, int row_mul, in
 
 void launch_logits_process(hipStream_t st, const GenDev& gp, float* logits, const unsigned long long* sup_bits,
                            const int* hist2, const float* cum2, const int* d_step, const int* done, float* cand_val,
-                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab, int* alt_tok, float* alt_lp) {
+                           int* cand_tok, float* cand_lp, const SmpRow* smp_tab, int* alt_tok, float* alt_lp,
+                           const TruncRow* trunc_tab) {
   if (gp.sample && !smp_tab) return;   // (a sampling launch without its table: nothing is launched, nothing is read)
   // every Whisper vocabulary keeps its timestamp ids above 48 * 1024 (ts_begin 50 363 .. 50 365); the synthetic
   // test vocabularies do not: they take the instantiation with a per-lane class test everywhere
   const bool wide = gp.ts_begin >= 48 * LP_THREADS;
   const bool alt = gp.n_alt > 0 && alt_tok && alt_lp;
   if (gp.n_alt > 0 && !alt) return;   // (a key that says alternatives without their buffers: nothing is launched)
-#define LP_GO(SMP, TXI, ALT) \
-  dec_logits_process_kernel<SMP, TXI, ALT><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab, alt_tok, alt_lp)
-  if (alt) {
-    if (gp.sample) { if (wide) LP_GO(true, 48, true); else LP_GO(true, 0, true); }
-    else { if (wide) LP_GO(false, 48, true); else LP_GO(false, 0, true); }
-  } else if (gp.sample) { if (wide) LP_GO(true, 48, false); else LP_GO(true, 0, false); }
-  else { if (wide) LP_GO(false, 48, false); else LP_GO(false, 0, false); }
+  if (gp.trunc && (!gp.sample || !trunc_tab)) return;   // (a key that says truncation on a launch that cannot: nothing is launched)
+#define LP_GO(SMP, TXI, ALT, TRUNC) \
+  dec_logits_process_kernel<SMP, TXI, ALT, TRUNC><<<gp.R, LP_THREADS, 0, st>>>(gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab, alt_tok, alt_lp, trunc_tab)
+  if (gp.trunc) {   // (the TRUNC instantiations live in dec_trunc.hip)
+    launch_logits_process_trunc(st, gp, logits, sup_bits, hist2, cum2, d_step, done, cand_val, cand_tok, cand_lp, smp_tab,
+                                alt ? alt_tok : nullptr, alt ? alt_lp : nullptr, trunc_tab);
+  } else if (alt) {
+    if (gp.sample) { if (wide) LP_GO(true, 48, true, false); else LP_GO(true, 0, true, false); }
+    else { if (wide) LP_GO(false, 48, true, false); else LP_GO(false, 0, true, false); }
+  } else if (gp.sample) { if (wide) LP_GO(true, 48, false, false); else LP_GO(true, 0, false, false); }
+  else { if (wide) LP_GO(false, 48, false, false); else LP_GO(false, 0, false, false); }
 #undef LP_GO
 }
 
@@ -570,3 +757,4 @@ void launch_score(hipStream_t st, const GenDev& gp, bool rules, const float* log
 }
 
 }  // namespace fwd
+#endif  // DEC_VOCAB_TRUNC_UNIT

@@ -117,6 +117,8 @@ struct GenWorkspace {
   half_t *nsp_x = nullptr, *nsp_xf = nullptr;   // [R rounded up to 16][d]
   // sampling runs: temperature, seed and first row of its call for every decode row (dec_kernels.h)
   fwd::SmpRow* smp_tab = nullptr;            // [R]
+  // ... and, for the runs that truncate their draw (fw_generate_trunc), the (top_k, top_p) of every decode row's call
+  fwd::TruncRow* trunc_tab = nullptr;        // [R]
   half_t *x_frag = nullptr, *att_frag = nullptr, *ffn_frag = nullptr;   // fragment-major GEMM inputs (fp16)
   half_t* xn_frag = nullptr;             // fp16(LayerNorm(x)), fragment-major (explicit-LayerNorm order, Model::ln_unfold)
   int8_t* xq = nullptr;                  // int8_float16: quantised linear input, fragment-major [R16][4d]
@@ -305,6 +307,7 @@ int gen_workspace_build(const Model* m, DecodeLane* lane, int lane_chunks, int s
   Z(g->ptab, R); Z(g->sot_tab, R);
   Z(g->nsp_x, R16 * d); Z(g->nsp_xf, R16 * d);
   Z(g->smp_tab, R);
+  Z(g->trunc_tab, R);
   if (m->compute_type == FW_COMPUTE_INT8_FLOAT16) {
     Z(g->xq, R16 * 4 * d);
     Z(g->xs, R16);
@@ -584,7 +587,7 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
-                               alt ? g->alt_lp.p : nullptr);
+                               alt ? g->alt_lp.p : nullptr, gp.trunc ? g->trunc_tab : nullptr);
     fwd::launch_beam_update(st, gp, g->cand_val, g->cand_tok, g->hist2, g->cum2, g->kvidx2, g->cur_tok, g->d_step,
                             g->done, g->n_done, g->n_fin, g->fin_tok, g->fin_len, g->fin_score, g->fin_cum, g->cand_lp,
                             g->lphist2, g->fin_lp, s.ptab, alt ? g->fin_path.p : nullptr);
@@ -712,6 +715,10 @@ struct GenRequest {
   int32_t* out_end_alt_ids = nullptr;    // [B, num_hypotheses, n_alt]
   float* out_end_alt_logprobs = nullptr;
   const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
+  // truncated sampling (fw_generate_trunc): the limits on this call's draws, (0, 1) = none.  Like temperature and seed they
+  // need NOT agree between the calls of a run: every row reads its call's from the run's TruncRow table.
+  int top_k = 0;
+  float top_p = 1.0f;
   bool sampling;
   int with_ts = 1, sot_pos = -1;   // from the prompt: no <|notimestamps|> -> timestamp rules; position of <sot>
   int rc = FW_OK;
@@ -723,7 +730,8 @@ struct GenRequest {
 // calls that may share a decode run: same scalar options (max_length among them), same suppress list, same timestamp
 // mode.  SAMPLING calls share runs among themselves only (their hypotheses are beam-1 rows of their own, num_hypotheses
 // decode chunks per encoder chunk: a beam or greedy call has one); sampling_temperature and seed need NOT agree, every
-// row reads its call's from the run's SmpRow table.  The PROMPT LENGTH and
+// row reads its call's from the run's SmpRow table, and the same holds for top_k and top_p (fw_generate_trunc; the TruncRow
+// table): a truncating call shares runs with sampling calls that truncate otherwise or not at all.  The PROMPT LENGTH and
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
 // BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
@@ -836,12 +844,14 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   // Pmax - 1).  A uniform run (P == Pmax, one <sot> position) takes exactly the path it always took.
   pl.P = pl.Pmax = r0.P; pl.B = 0; pl.ragged = pl.want_nsp = false;
   int n_alt = 0;   // the largest of the run's calls: what the run records (0: nothing, the kernels and graph keys of always)
+  bool trunc = false;   // some call of the run limits its draw (sampling calls only: fw_generate_trunc checks)
   for (const GenRequest* r : reqs) {
     pl.P = std::min(pl.P, r->P); pl.Pmax = std::max(pl.Pmax, r->P);
     pl.ragged = pl.ragged || r->P != r0.P || r->sot_pos != r0.sot_pos;
     pl.want_nsp = pl.want_nsp || r->o->return_no_speech_prob;
     pl.B += r->B;
     n_alt = std::max(n_alt, r->n_alt);
+    trunc = trunc || r->top_k > 0 || r->top_p < 1.0f;
   }
   pl.nh = o->num_hypotheses; pl.ml = o->max_length;
   const int P = pl.P, Pmax = pl.Pmax, B = pl.B;
@@ -868,6 +878,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.sample = sampling ? 1 : 0;
   gp.n_alt = n_alt;
   gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
+  gp.trunc = (sampling && trunc) ? 1 : 0;   // (a run without a truncating call: today's kernels and graphs)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
   gp.inv_temp = 1.0f; gp.seed_lo = 0; gp.seed_hi = 0;
@@ -952,6 +963,7 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   ptok.assign((size_t)Pmax * Bx, 0);
   std::vector<int> first((size_t)Bx * K), ptab_host((size_t)Bx), sot_host((size_t)Bx);
   std::vector<fwd::SmpRow> smp_host(sampling ? (size_t)Bx : 0);   // (sampling: K == 1, decode chunk bx is row bx)
+  std::vector<fwd::TruncRow> trunc_host(pl.gp.trunc ? (size_t)Bx : 0);
   {
     int bx = 0;
     for (const GenRequest* r : reqs) {
@@ -965,11 +977,14 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
           if (sampling)
             smp_host[bx] = {1.0f / r->o->sampling_temperature, (unsigned)(r->o->seed & 0xffffffffu),
                             (unsigned)(r->o->seed >> 32), row0};
+          if (pl.gp.trunc) trunc_host[bx] = {r->top_k, r->top_p};
         }
     }
   }
   if (sampling)
     FW_HIP(hipMemcpyAsync(g->smp_tab, smp_host.data(), (size_t)Bx * sizeof(fwd::SmpRow), hipMemcpyHostToDevice, st));
+  if (pl.gp.trunc)
+    FW_HIP(hipMemcpyAsync(g->trunc_tab, trunc_host.data(), (size_t)Bx * sizeof(fwd::TruncRow), hipMemcpyHostToDevice, st));
   if (ragged) {
     FW_HIP(hipMemcpyAsync(g->ptab, ptab_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
     FW_HIP(hipMemcpyAsync(g->sot_tab, sot_host.data(), (size_t)Bx * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1381,6 +1396,17 @@ int32_t fw_generate_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
                           int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
                           float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs,
                           int32_t* out_end_alt_ids, float* out_end_alt_logprobs) {
+  return fw_generate_trunc(fm, enc_t, prompts, prompt_offsets, B, o, 0, 1.0f, n_alt, boost, out_ids, out_lens, out_scores,
+                           out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids, out_alt_logprobs,
+                           out_end_alt_ids, out_end_alt_logprobs);
+}
+
+int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                          int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt,
+                          const fw_boost* boost, int32_t* out_ids, int32_t* out_lens, float* out_scores,
+                          float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
+                          int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                          float* out_end_alt_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
@@ -1404,6 +1430,10 @@ int32_t fw_generate_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
   // sampling_topk 0 (whole distribution), num_hypotheses = best_of independent samples per chunk
   const bool sampling = (K == 1 && o->sampling_topk != 1);
+  FW_CHECK_ARG(top_k >= 0, "top_k %d must not be negative", top_k);
+  FW_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "top_p %g not in (0, 1]", (double)top_p);   // (NaN fails both)
+  FW_CHECK_ARG((top_k == 0 && top_p == 1.f) || (sampling && o->sampling_topk == 0),
+               "top_k / top_p limit a sampled draw: the call must sample (beam_size 1, sampling_topk 0)");
   if (sampling) {
     FW_CHECK_ARG(o->sampling_topk == 0, "sampling_topk must be 1 (greedy) or 0 (sample the whole distribution)");
     FW_CHECK_ARG(o->sampling_temperature > 0.f, "sampling_temperature must be positive");
@@ -1444,6 +1474,7 @@ int32_t fw_generate_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
   req.n_alt = n_alt; req.out_alt_ids = out_alt_ids; req.out_alt_logprobs = out_alt_logprobs;
   req.out_end_alt_ids = out_end_alt_ids; req.out_end_alt_logprobs = out_end_alt_logprobs;
   req.sampling = sampling;
+  req.top_k = top_k; req.top_p = top_p;
   req.boost = (boost && boost->table[0] > 0) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the

@@ -879,7 +879,12 @@ int32_t fw_test_dec_softmax_pick(fw_model* fm, const float* logits, int32_t rows
 // rule use them as indices into the row (a wrong test gets FW_EINVAL, never a device fault).
 // alt (fw_test_logits_rules_alt): n_alt in [1, FW_MAX_ALTERNATIVES] and alt_tok / alt_lp [R][n_alt] IN / OUT — the rows' slab
 // [n][.][.] of a step-major device buffer of n + 1 steps, which is what the kernel indexes with its step counter.
-struct RulesEx { const int32_t* done; float* logits_io; int32_t n_alt = 0; int32_t* alt_tok = nullptr; float* alt_lp = nullptr; };
+// trunc (fw_test_logits_rules_trunc): top_k / top_p [R], the launch's TruncRow table; the launch is then ONE launch of the
+// TRUNC instantiation (gp.trunc = 1) whatever the rows' limits are.
+struct RulesEx {
+  const int32_t* done; float* logits_io; int32_t n_alt = 0; int32_t* alt_tok = nullptr; float* alt_lp = nullptr;
+  const int32_t* top_k = nullptr; const float* top_p = nullptr;
+};
 static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, const int32_t* hist, int32_t n,
                                  const float* cum, const fw_gen_opts* o, int32_t with_timestamps, float* cand_val,
                                  int32_t* cand_tok, float* cand_lp, const fwd::SmpRow* smp = nullptr,
@@ -904,6 +909,13 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
   gp.B = R / K; gp.K = K; gp.R = R; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx;
   gp.n_alt = n_alt;
   gp.sample = sampling ? 1 : 0;
+  const bool trunc = ex && ex->top_k && ex->top_p;
+  FW_CHECK_ARG(!trunc || sampling, "truncation needs options that select sampling");
+  if (trunc)
+    for (int r = 0; r < R; ++r)
+      FW_CHECK_ARG(ex->top_k[r] >= 0 && ex->top_p[r] > 0.f && ex->top_p[r] <= 1.f, "row %d: top_k %d / top_p %g out of range",
+                   r, ex->top_k[r], (double)ex->top_p[r]);
+  gp.trunc = trunc ? 1 : 0;
   gp.inv_temp = 1.0f;   // (sampling: temperature and seed per row, from the table below — as in a decode run)
   fwd::fill_rule_fields(gp, c, o, with_timestamps);
   const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
@@ -952,7 +964,14 @@ static int32_t logits_rules_hook(fw_model* fm, const float* logits, int32_t R, c
     FW_HIP(hipMemcpy(d_at + (size_t)n * n_slab, ex->alt_tok, n_slab * sizeof(int), hipMemcpyHostToDevice));
     FW_HIP(hipMemcpy(d_al + (size_t)n * n_slab, ex->alt_lp, n_slab * sizeof(float), hipMemcpyHostToDevice));
   }
-  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp, d_at, d_al);
+  fwd::TruncRow* d_trunc = nullptr;
+  if (trunc) {
+    std::vector<fwd::TruncRow> tab((size_t)R);
+    for (int r = 0; r < R; ++r) tab[r] = {ex->top_k[r], ex->top_p[r]};
+    if ((rc = db.upload(&d_trunc, tab.data(), tab.size()))) return rc;
+  }
+  fwd::launch_logits_process(nullptr, gp, d_lg, d_bits, d_hist, d_cum, d_step, d_done, d_cv, d_ct, d_cl, d_smp, d_at, d_al,
+                             d_trunc);
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
   if ((rc = download(hv.data(), d_cv, NC)) || (rc = download(ht.data(), d_ct, NC))) return rc;
@@ -1043,6 +1062,26 @@ int32_t fw_test_logits_rules_alt(fw_model* fm, float* logits, int32_t R, const i
     if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
   }
   const RulesEx ex{done, logits, n_alt, alt_tok, alt_lp};
+  return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp,
+                           tab_given ? tab.data() : nullptr, &ex);
+}
+
+// fw_test_logits_rules_alt plus per-row limits (include/fwamd_test.h): ONE launch of the TRUNC instantiation; n_alt may be 0.
+int32_t fw_test_logits_rules_trunc(fw_model* fm, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                   const fw_gen_opts* o, int32_t with_timestamps, const int32_t* done, const float* inv_temp,
+                                   const uint64_t* seed, const int32_t* row0, const int32_t* top_k, const float* top_p,
+                                   float* cand_val, int32_t* cand_tok, float* cand_lp, int32_t n_alt, int32_t* alt_tok,
+                                   float* alt_lp) {
+  FW_CHECK_ARG(o && cand_lp && top_k && top_p && R >= 1, "null argument");
+  FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
+  FW_CHECK_ARG(n_alt == 0 ? (!alt_tok && !alt_lp) : (alt_tok && alt_lp), "alt_tok / alt_lp: both with n_alt > 0, none with n_alt == 0");
+  FW_CHECK_ARG(o->beam_size == 1 && o->sampling_topk == 0, "the options must select sampling (beam_size 1, sampling_topk 0)");
+  const bool tab_given = inv_temp || seed || row0;
+  FW_CHECK_ARG(!tab_given || (inv_temp && seed && row0), "the sampling table needs inv_temp, seed and row0 together");
+  std::vector<fwd::SmpRow> tab;
+  if (tab_given)
+    if (int rc = smp_table(R, inv_temp, seed, row0, tab)) return rc;
+  const RulesEx ex{done, logits, n_alt, alt_tok, alt_lp, top_k, top_p};
   return logits_rules_hook(fm, logits, R, hist, n, cum, o, with_timestamps, cand_val, cand_tok, cand_lp,
                            tab_given ? tab.data() : nullptr, &ex);
 }

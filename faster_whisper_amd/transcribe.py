@@ -125,6 +125,27 @@ def _boost_keyword(boost) -> dict:
     return {} if boost is None else {"boost": boost}
 
 
+def _check_trunc_arguments(sampling_top_k, sampling_top_p) -> None:
+    """sampling_top_k: an integer >= 0; sampling_top_p: a number in (0, 1] (ValueError) — what fw_generate_trunc accepts,
+    checked before anything is decoded"""
+    if isinstance(sampling_top_k, bool) or not isinstance(sampling_top_k, (int, np.integer)) or sampling_top_k < 0:
+        raise ValueError(f"sampling_top_k must be an integer >= 0 (got {sampling_top_k!r})")
+    if isinstance(sampling_top_p, bool) or not isinstance(sampling_top_p, (int, float, np.integer, np.floating)) \
+            or not 0 < sampling_top_p <= 1:
+        raise ValueError(f"sampling_top_p must lie in (0, 1] (got {sampling_top_p!r})")
+
+
+def _trunc_keywords(sampling_top_k, sampling_top_p, top_k_key: str = "sampling_top_k",
+                    top_p_key: str = "sampling_top_p") -> dict:
+    """the keywords a call passes down for its sampling limits — only those that limit something (as _value_keywords)"""
+    out = {}
+    if sampling_top_k:
+        out[top_k_key] = int(sampling_top_k)
+    if sampling_top_p != 1:
+        out[top_p_key] = float(sampling_top_p)
+    return out
+
+
 @dataclass
 class TranscriptionOptions:
     beam_size: int
@@ -508,7 +529,7 @@ class WhisperModel:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
                    token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
-                   phrase_boost: Optional[float] = None):
+                   phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -524,9 +545,14 @@ class WhisperModel:
         or beside it.  None (the default): every sampling call takes the next seed of the model's call counter.
         boost_phrases, phrase_boost (not in the reference): see boost_list_for — names and terms made more likely by
         phrase_boost at the logit, in every window and every attempt of the fallback ladder, without spending prompt text
-        as `hotwords` does."""
+        as `hotwords` does.
+        sampling_top_k, sampling_top_p (not in the reference): limits on the sampled attempts of the fallback ladder (the
+        rungs with temperature > 0; the attempt at temperature 0 is a beam search and takes none): every draw comes from
+        the sampling_top_k most likely tokens, then from the nucleus that holds sampling_top_p of their tempered mass
+        (include/fwamd.h: fw_generate_trunc).  0 / 1.0 (the defaults): the whole distribution, as the reference samples."""
         args = dict(locals())               # the call's arguments by name
         _check_boost_arguments(boost_phrases, phrase_boost)
+        _check_trunc_arguments(sampling_top_k, sampling_top_p)
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
@@ -567,6 +593,7 @@ class WhisperModel:
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
                                           **_value_keywords(token_logprobs, token_alternatives),
                                           **_boost_keyword(self.boost_list_for(boost_phrases, phrase_boost, tokenizer)),
+                                          **_trunc_keywords(sampling_top_k, sampling_top_p),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
@@ -602,9 +629,12 @@ class WhisperModel:
         which recording gets which seed depends on timing.
         boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcribe(), so the
         windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
+        sampling_top_k / sampling_top_p (not in the reference): transcribe()'s, the same limits for every recording; sampled
+        attempts share decode runs whatever their limits.
         An exception in one recording is raised here, after the recordings already started have finished."""
         n = len(audios)
         _check_boost_arguments(transcribe_kwargs.get("boost_phrases"), transcribe_kwargs.get("phrase_boost"))
+        _check_trunc_arguments(transcribe_kwargs.get("sampling_top_k", 0), transcribe_kwargs.get("sampling_top_p", 1.0))
         if n == 0:
             return []
         if transcribe_kwargs.get("boost_phrases") is not None:
@@ -642,7 +672,8 @@ class WhisperModel:
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
                           token_logprobs: bool = False, sampling_seed: Optional[int] = None,
-                          token_alternatives: int = 0, boost=None):
+                          token_alternatives: int = 0, boost=None, sampling_top_k: int = 0,
+                          sampling_top_p: float = 1.0):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -698,7 +729,7 @@ class WhisperModel:
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
                     encoder_output, prompt, tokenizer, options, **_value_keywords(token_logprobs, token_alternatives),
-                    **_boost_keyword(boost),
+                    **_boost_keyword(boost), **_trunc_keywords(sampling_top_k, sampling_top_p),
                     **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
@@ -752,7 +783,7 @@ class WhisperModel:
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
                                options: TranscriptionOptions, token_logprobs: bool = False,
                                sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0,
-                               boost=None):
+                               boost=None, sampling_top_k: int = 0, sampling_top_p: float = 1.0):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
@@ -760,6 +791,8 @@ class WhisperModel:
         sampling_seed: the sampled attempt at rung t gets seed=attempt_seed(sampling_seed, seek, t), `seek` the window's
         first frame; None: no seed is passed, the backend draws one from its call counter.
         boost: the call's boost list (boost_list_for), the same one for every attempt.
+        sampling_top_k / sampling_top_p: limits on the draws of the sampled attempts (temperature > 0) only; at 0 / 1.0 no
+        keyword is passed to generate.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
         max_initial_timestamp_index = int(round(options.max_initial_timestamp / self.time_precision))
         max_length = self._max_length_for(prompt, options.max_new_tokens)
@@ -771,6 +804,7 @@ class WhisperModel:
                             sampling_temperature=temperature)
                 if sampling_seed is not None:
                     mode["seed"] = attempt_seed(sampling_seed, seek, rung)
+                mode.update(_trunc_keywords(sampling_top_k, sampling_top_p, "top_k", "top_p"))
             else:
                 mode = dict(beam_size=options.beam_size, patience=options.patience)
             result = self.model.generate(
@@ -1094,7 +1128,8 @@ class BatchedInferencePipeline:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    shard: bool = False, fused_features: bool = True, vad_speech_probs=None,
                    token_logprobs: bool = False, token_alternatives: int = 0,
-                   boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None):
+                   boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None,
+                   sampling_top_k: int = 0, sampling_top_p: float = 1.0):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1105,11 +1140,15 @@ class BatchedInferencePipeline:
         chunk list is block-partitioned over the ranks and rank 0's generator yields ALL segments in
         order (other ranks yield nothing).  fused_features=False reproduces the reference data flow
         (features materialised on the host, then encode()).
-        boost_phrases, phrase_boost (not in the reference): see WhisperModel.boost_list_for — one list for every batch."""
+        boost_phrases, phrase_boost (not in the reference): see WhisperModel.boost_list_for — one list for every batch.
+        sampling_top_k, sampling_top_p (not in the reference): WhisperModel.transcribe's limits on sampled attempts,
+        validated here as there (ValueError).  They apply to the temperature > 0 rungs of the fallback ladder only, and the
+        batched path decodes every chunk once, without sampling (as the reference's does): here they limit nothing."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model
         _check_boost_arguments(boost_phrases, phrase_boost)
+        _check_trunc_arguments(sampling_top_k, sampling_top_p)
         if (token_logprobs or token_alternatives) and shard:
             raise ValueError("token_logprobs / token_alternatives are not offered with shard=True: the gathered records "
                              "carry no per-token values")
@@ -1388,6 +1427,7 @@ class BatchedInferencePipeline:
         m = self.model
         n = len(audios)
         _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
+        _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
         if n == 0:
             return []
         multilingual = m._effective_multilingual(a["multilingual"])

@@ -186,7 +186,8 @@ int32_t fw_model_create_from_blob_dev(const fw_config* cfg, const void* blob_dev
  * (fw_generate_boost: none on both sides, or byte-equal compiled tables), and the timestamp mode
  * (<|notimestamps|> in the prompt or not).  Sampling calls (beam_size 1, sampling_topk 0) merge among themselves, never with
  * beam or greedy calls; their sampling_temperature and seed need NOT agree (every row of a run draws with its own call's,
- * as the row of that call that it is alone).  The PROMPT LENGTH and the position of
+ * as the row of that call that it is alone), and neither do the top_k / top_p of fw_generate_trunc (a truncating call
+ * shares runs with sampling calls that truncate otherwise or not at all).  The PROMPT LENGTH and the position of
  * <|startoftranscript|> need NOT agree: every chunk of a run decodes at its own position of the text context with its
  * own budget min(max_length, n_text_ctx) - prompt length (so prompts that carry different amounts of previous text
  * share a run; only a call whose prompt already fills max_length keeps to calls of its own prompt length).  Inside ONE
@@ -340,6 +341,38 @@ void fw_boost_free(fw_boost* b);
  * (the list may be freed once the call has returned). */
 int32_t fw_generate_boost(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
                           int32_t B, const fw_gen_opts* opts, int32_t n_alt, const fw_boost* boost,
+                          int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                          float* out_token_logprobs, float* out_end_logprobs,
+                          int32_t* out_alt_ids, float* out_alt_logprobs,
+                          int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
+
+/* ---- truncated sampling: top-k and nucleus (top-p) limits on the sampled draw -------------------------------
+ * fw_generate_boost plus two limits on what a SAMPLING call (beam_size 1, sampling_topk 0) may draw.  For one row at one
+ * step, after the boost, the rules and the fp32 log-softmax exactly as always, with logp[v] the processed log-prob:
+ *   1. L = {v : logp[v] > -inf}, in the order of the alternatives: logp descending, id ascending.
+ *   2. top-k: S_k = the first min(top_k, |L|) ids of L (ties at the cut go to the lower id); S_k = L when top_k == 0.
+ *   3. nucleus: w(v) = exp((logp[v] - max logp) / sampling_temperature) — temperature comes before the nucleus —, Z = the
+ *      sum of w over S_k, S = {v in S_k : the sum of w over the ids of S_k in front of v is < top_p * Z}; S = S_k when
+ *      top_p == 1.  The first id of the order is always in S.  The sums are fp32 in an order of the implementation's: an id
+ *      whose mass-ahead lies within rounding of top_p * Z may fall on either side.
+ *   4. the draw is the arg-max over S of logp[v] / T + gumbel(seed, row, step, v), lowest id on a tie.  The noise of an id
+ *      does not depend on S: whenever the untruncated draw lies in S, the truncated draw is that same id.
+ *   5. what is recorded does not change: out_token_logprobs is the plain processed logp of the drawn id (not tempered, not
+ *      renormalised over S), the alternatives are the plain top n_alt of L, and identities (1) and (2) of fw_generate_alt
+ *      hold as they are.
+ * top_k == 0 && top_p == 1 is fw_generate_boost exactly, bit for bit.  top_k == 1 draws the arg-max: ids and token
+ * log-probs of a one-hypothesis call equal the greedy call's.  FW_EINVAL before anything is queued: top_k < 0; top_p NaN,
+ * <= 0 or > 1; a limit (top_k > 0 or top_p < 1) on a call that does not sample.  opts->sampling_topk keeps its meaning
+ * (1 greedy, 0 sample; anything else FW_EINVAL).
+ * Merging: top_k and top_p need NOT agree — like temperature and seed they are per call and travel in a per-row table.  A
+ * truncating call shares decode runs with other sampling calls, truncating or not, and every caller gets its solo result
+ * bit for bit; a run with no truncating call launches the kernels and graphs it always did.
+ * [CT2-ext] CTranslate2's own sampler (sampling_topk > 1, sampling_topp) is not reached by the reference and is not on hand:
+ * whether it renormalises in exactly this order (temperature, top-k, then the nucleus over the top-k mass) is not pinned,
+ * next to the A.7 unknowns of SURVEY.md. */
+int32_t fw_generate_trunc(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                          int32_t B, const fw_gen_opts* opts, int32_t top_k, float top_p, int32_t n_alt,
+                          const fw_boost* boost,
                           int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
                           float* out_token_logprobs, float* out_end_logprobs,
                           int32_t* out_alt_ids, float* out_alt_logprobs,

@@ -76,6 +76,17 @@ int32_t fw_test_logits_rules_alt(fw_model* m, float* logits, int32_t R, const in
                                  const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
                                  const float* inv_temp, const uint64_t* seed, const int32_t* row0, float* cand_val,
                                  int32_t* cand_tok, float* cand_lp, int32_t n_alt, int32_t* alt_tok, float* alt_lp);
+/* fw_test_logits_rules_alt plus per-row truncation limits (tests/test_gpu_sampling_trunc_kernel.py): ONE launch of the
+ * TRUNC instantiation of the rules kernel, whatever the rows' limits are.
+ *   in      top_k / top_p [R]: the launch's second per-row table, beside inv_temp / seed / row0; top_k >= 0, top_p in
+ *           (0, 1] (checked: FW_EINVAL); a row with (0, 1.0) must get the bits of the plain sampling kernel
+ *   in      n_alt in [0, FW_MAX_ALTERNATIVES]; with n_alt == 0 alt_tok / alt_lp are NULL
+ * opts must select sampling (beam_size 1, sampling_topk 0).  Everything else as fw_test_logits_rules_alt. */
+int32_t fw_test_logits_rules_trunc(fw_model* m, float* logits, int32_t R, const int32_t* hist, int32_t n, const float* cum,
+                                   const fw_gen_opts* opts, int32_t with_timestamps, const int32_t* done,
+                                   const float* inv_temp, const uint64_t* seed, const int32_t* row0, const int32_t* top_k,
+                                   const float* top_p, float* cand_val, int32_t* cand_tok, float* cand_lp, int32_t n_alt,
+                                   int32_t* alt_tok, float* alt_lp);
 /* ONE launch of the scoring kernel (dec_score_kernel, what fw_score launches per position block) on caller-provided rows
  * (tests/test_gpu_score_kernel.py):
  *   in/out  logits [rows][n_vocab] float32: uploaded, and downloaded WHOLE after the launch (the kernel must not write it)
