@@ -94,6 +94,8 @@ SYMBOLS = [
     "fw_boost_create", "fw_boost_free", "fw_generate_boost", "fw_score_boost",
     "fw_test_boost_rows", "fw_test_boost_rows_host",
     "fw_generate_trunc", "fw_test_logits_rules_trunc",
+    "fw_constraint_create", "fw_constraint_free", "fw_generate_constrain", "fw_score_constrain",
+    "fw_test_constrain_rows", "fw_test_constrain_rows_host", "fw_test_constraint_table",
 ]
 
 _lib = None
@@ -251,6 +253,17 @@ def load():
                                           f32p, f32p, f32p, f32p, i32p, f32p, i32p, f32p]
         lib.fw_test_logits_rules_trunc.argtypes = [vp, vp, i32, vp, i32, vp, C.POINTER(FwGenOpts), i32, vp, vp, vp, vp, vp,
                                                    vp, vp, vp, vp, i32, vp, vp]
+    if hasattr(lib, "fw_constraint_create"):        # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_constraint_create.argtypes = [i32, i32p, i32p, i32, C.POINTER(vp)]
+        lib.fw_constraint_free.argtypes = [vp]
+        lib.fw_constraint_free.restype = None
+        lib.fw_generate_constrain.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32, C.c_float, i32, vp, vp,
+                                              i32p, i32p, f32p, f32p, f32p, f32p, i32p, f32p, i32p, f32p]
+        lib.fw_score_constrain.argtypes = [vp, vp, i32p, i32p, i32p, i32p, i32, i32, C.POINTER(FwGenOpts), vp, vp, f32p, i32p,
+                                           f32p]
+        lib.fw_test_constrain_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
+        lib.fw_test_constrain_rows_host.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        lib.fw_test_constraint_table.argtypes = [vp, vp, i32, i32p]
     if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

@@ -192,6 +192,47 @@ def _boost_handle(boost):
     return boost._handle
 
 
+class ConstraintList:
+    """A validated, compiled list of the phrases a decode may produce (fwamd.h: fw_constraint_create): phrases[j] is a
+    sequence of token ids.  At every step the ids that continue no listed phrase after the row's generated text are set to
+    -inf in front of the decoding rules, and <eot> is allowed only where a phrase is complete: a hypothesis with a finite
+    score that closes on <eot> is, its timestamps apart, one phrase of the list.  Duplicates and phrases that are prefixes
+    of others are valid; the list is a set (order and repeats do not matter).  Host-only: needs no device.
+    Whisper.constraint_list builds one for the model's vocabulary; pass it as generate(constraint=...) /
+    score(constraint=...).  An empty list constrains nothing."""
+
+    def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]]):
+        phrases = [list(p) for p in phrases]
+        lib = _lib.load()
+        if not hasattr(lib, "fw_constraint_create"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_constraint_create: constrained decoding needs a current build")
+        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
+        self.n_vocab = int(n_vocab)
+        self.n_phrases = len(phrases)
+        self._handle = C.c_void_p()
+        _lib.check(lib.fw_constraint_create(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
+                                            C.byref(self._handle)))
+
+    def __len__(self):
+        return self.n_phrases
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            try:
+                _lib.load().fw_constraint_free(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+
+
+def _constraint_handle(constraint):
+    if constraint is None:
+        return None
+    if not isinstance(constraint, ConstraintList):
+        raise TypeError("constraint must be a ConstraintList (Whisper.constraint_list) or None")
+    return constraint._handle
+
+
 class _Replica:
     """one fw_model on one GPU"""
 
@@ -590,6 +631,14 @@ class Whisper:
         more than 32, more than 4096 tokens in all, an id outside the vocabulary, a boost that is not finite."""
         return BoostList(self._cfg.n_vocab, phrases, boosts)
 
+    # ---- constrained decoding -----------------------------------------------------------
+    def constraint_list(self, phrases: Sequence[Sequence[int]]) -> ConstraintList:
+        """A ConstraintList for this model's vocabulary: phrases[j] a sequence of token ids.  ValueError (fwamd.h:
+        FW_CONSTRAIN_MAX_PHRASES / _LEN / _TOKENS): more than 1024 phrases, a phrase of no token or more than 32, more than
+        4096 tokens in all, an id outside the vocabulary.  What a generate / score call refuses of a list (an id from <eot>
+        on, a suppressed id, ...) is checked by that call, against its own rules."""
+        return ConstraintList(self._cfg.n_vocab, phrases)
+
     # ---- generate -----------------------------------------------------------------------
     def generate(self, features: StorageView, prompts: List[List[int]], *, asynchronous: bool = False,
                  beam_size: int = 5, patience: float = 1, num_hypotheses: int = 1, length_penalty: float = 1,
@@ -600,18 +649,27 @@ class Whisper:
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
                  seed: Optional[int] = None, return_token_logprobs: bool = False,
                  return_alternatives: int = 0, boost: Optional[BoostList] = None, top_k: int = 0,
-                 top_p: float = 1.0) -> List[WhisperGenerationResult]:
+                 top_p: float = 1.0, constraint: Optional[ConstraintList] = None) -> List[WhisperGenerationResult]:
         """boost (not in CTranslate2): a BoostList (boost_list()) whose phrases are made more likely at the logit, in front
         of the decoding rules; None or an empty list: the call without it.
         top_k / top_p (not in CTranslate2's generate(); fwamd.h: fw_generate_trunc): limits on the draw of a SAMPLING call
         (beam_size 1, sampling_topk 0) — the top_k most likely tokens, then the nucleus holding top_p of their tempered
         mass.  0 / 1.0: no limit, and the call is the one it always was.  ValueError: top_k < 0, top_p outside (0, 1], a
-        limit on a call that does not sample.  Token log-probs and alternatives stay those of the whole distribution."""
+        limit on a call that does not sample.  Token log-probs and alternatives stay those of the whole distribution.
+        constraint (not in CTranslate2; fwamd.h: fw_generate_constrain): a ConstraintList (constraint_list()); every
+        hypothesis is then, its timestamps apart, one phrase of the list (or a prefix of one when the budget cut it).  Runs
+        behind the boost and in front of the rules; log-probs, alternatives and scores are those of the constrained
+        distribution.  None or an empty list: the call without it.  ValueError: a list for another vocabulary, a phrase id
+        from <eot> on or in suppress_tokens, a first id that suppress_blank forbids, no_repeat_ngram_size > 0,
+        min_new_tokens > 0."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
         boost_h = _boost_handle(boost)
         if boost_h is not None and not hasattr(self._lib, "fw_generate_boost"):   # an older build loaded through FWAMD_LIB
             raise RuntimeError("this libfwamd.so has no fw_generate_boost: phrase boosting needs a current build")
+        constraint_h = _constraint_handle(constraint)
+        if constraint_h is not None and not hasattr(self._lib, "fw_generate_constrain"):   # an older build (FWAMD_LIB)
+            raise RuntimeError("this libfwamd.so has no fw_generate_constrain: constrained decoding needs a current build")
         top_k, top_p = int(top_k), float(top_p)
         trunc = top_k != 0 or top_p != 1.0   # (NaN included: the engine refuses it)
         if trunc and not hasattr(self._lib, "fw_generate_trunc"):   # an older build loaded through FWAMD_LIB
@@ -663,7 +721,10 @@ class Whisper:
                 elps = np.zeros((B, nh, n_alt), dtype=np.float32)
             def f32(a): return _lib.as_f32p(a) if a is not None else None
             def i32(a): return _lib.as_i32p(a) if a is not None else None
-            if trunc:
+            if constraint_h is not None:
+                _lib.check(self._lib.fw_generate_constrain(*args[:6], top_k, top_p, n_alt, boost_h, constraint_h, *args[6:],
+                                                           f32(tlp), f32(elp), i32(aid), f32(alp), i32(eid), f32(elps)))
+            elif trunc:
                 _lib.check(self._lib.fw_generate_trunc(*args[:6], top_k, top_p, n_alt, boost_h, *args[6:], f32(tlp), f32(elp),
                                                        i32(aid), f32(alp), i32(eid), f32(elps)))
             elif boost_h is not None:
@@ -751,7 +812,8 @@ class Whisper:
                           max_initial_timestamp_index=50)
 
     def score(self, features: StorageView, prompts: List[List[int]], targets, *, rules: bool = False,
-              boost: Optional[BoostList] = None, **rule_kwargs) -> List[WhisperScoringResult]:
+              boost: Optional[BoostList] = None, constraint: Optional[ConstraintList] = None,
+              **rule_kwargs) -> List[WhisperScoringResult]:
         """Teacher-forced log-probs of given transcripts (fwamd.h: fw_score; not in CTranslate2's Whisper class).
         targets[b]: one sequence of ids, or a list of up to max_beam_size sequences, scored against chunk b.
         rules=False: the raw distribution.  rules=True: the distribution generate()'s search ranks by, with generate's
@@ -759,7 +821,9 @@ class Whisper:
         max_initial_timestamp_index); the timestamp rules follow the prompt.  result.score(h, length_penalty=1) is then
         what generate(return_scores=True) reports for the same ids.
         boost: the BoostList of a generate(boost=...) call, added in front of the rules with the sequence's own prefix as the
-        generated history; needs rules=True."""
+        generated history; needs rules=True.
+        constraint: the ConstraintList of a generate(constraint=...) call, applied behind the boost and in front of the
+        rules; needs rules=True.  A target that leaves the list scores -inf from there on."""
         unknown = set(rule_kwargs) - set(self._RULE_DEFAULTS)
         if unknown:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
@@ -772,6 +836,11 @@ class Whisper:
             raise ValueError("boost needs rules=True: the boost is the first step of the decoding rules")
         if boost_h is not None and not hasattr(self._lib, "fw_score_boost"):   # an older build loaded through FWAMD_LIB
             raise RuntimeError("this libfwamd.so has no fw_score_boost: phrase boosting needs a current build")
+        constraint_h = _constraint_handle(constraint)
+        if constraint_h is not None and not rules:
+            raise ValueError("constraint needs rules=True: the constraint is a step of the decoding rules")
+        if constraint_h is not None and not hasattr(self._lib, "fw_score_constrain"):   # an older build (FWAMD_LIB)
+            raise RuntimeError("this libfwamd.so has no fw_score_constrain: constrained decoding needs a current build")
         enc = self._as_encoded(features)
         if len(prompts) != enc._shape[0] or len(targets) != enc._shape[0]:
             raise ValueError(f"got {len(prompts)} prompts and {len(targets)} targets for a batch of {enc._shape[0]}")
@@ -808,7 +877,9 @@ class Whisper:
             head = (enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs), _lib.as_i32p(tflat),
                     _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None)
             outs = (_lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp))
-            if boost_h is not None:
+            if constraint_h is not None:
+                _lib.check(self._lib.fw_score_constrain(*head, boost_h, constraint_h, *outs))
+            elif boost_h is not None:
                 _lib.check(self._lib.fw_score_boost(*head, boost_h, *outs))
             else:
                 _lib.check(self._lib.fw_score(*head, *outs))

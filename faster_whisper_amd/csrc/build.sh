@@ -6,7 +6,7 @@ OUT=../libfwamd.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable"
 mkdir -p build
 pids=()
-for f in logmel gemm rowops attn_enc engine decoder dec_kernels dec_vocab dec_trunc dec_boost vad resample hooks; do
+for f in logmel gemm rowops attn_enc engine decoder dec_kernels dec_vocab dec_trunc dec_boost dec_constrain vad resample hooks; do
   if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ kernels.h -nt build/$f.o ] || [ engine.h -nt build/$f.o ] || [ dec_kernels.h -nt build/$f.o ] || [ ../../include/fwamd.h -nt build/$f.o ] || [ ../../include/fwamd_test.h -nt build/$f.o ] || [ vad_model.h -nt build/$f.o ] || [ build.sh -nt build/$f.o ] || { [ $f = dec_trunc ] && [ dec_vocab.hip -nt build/$f.o ]; }; then
     # attn_enc: MFMA accumulators in VGPRs (-amdgpu-mfma-vgpr-form): the softmax reads every score and rescales the output
     # accumulators, which with AGPR accumulators costs 191 v_accvgpr moves per 64-key tile of a vector-bound kernel (548 ->

@@ -45,6 +45,10 @@ struct GenDev {
   // launches the TRUNC instantiations of the rules kernel, which read a TruncRow per row.  0 in every other run: the key,
   // the kernels and the graphs of today.
   int trunc;
+  // CONSTRAIN (fw_generate_constrain): 1 when the step launches dec_constrain_kernel between the boost and the rules
+  // kernel.  0 in every run without a list: the key, the kernels and the graphs of today.  The table's sizes travel in the
+  // table's header, not here.
+  int constrain;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -264,10 +268,53 @@ void launch_boost_score(hipStream_t st, const GenDev& gp, float* logits, const i
 // the same walk in plain C++ (fw_test_boost_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
 
+// ---- constrained decoding (include/fwamd.h: fw_constraint; kernel and table compiler: dec_constrain.hip) ----
+// The compiled table, 32-bit words: a header {P phrases, T phrase tokens, n_vocab, 0}, then
+//   off [P + 1]     phrase j is tok[off[j] .. off[j + 1]), off[0] = 0
+//   tok [T]         the phrases back to back
+// The phrases are a set: sorted by their ids (lexicographically), no duplicates.  P <= FW_CONSTRAIN_MAX_PHRASES,
+// T <= FW_CONSTRAIN_MAX_TOKENS, every phrase 1 .. FW_CONSTRAIN_MAX_LEN tokens.
+constexpr int CONSTRAIN_HDR_WORDS = 4;
+constexpr int CONSTRAIN_TABLE_MAX_WORDS = CONSTRAIN_HDR_WORDS + FW_CONSTRAIN_MAX_PHRASES + 1 + FW_CONSTRAIN_MAX_TOKENS;
+struct ConstrainView {
+  int P, T;
+  const int *off, *tok;
+};
+static __host__ __device__ inline ConstrainView constrain_view(const int* tab) {
+  ConstrainView v;
+  v.P = tab[0]; v.T = tab[1];
+  v.off = tab + CONSTRAIN_HDR_WORDS;
+  v.tok = v.off + v.P + 1;
+  return v;
+}
+// dec_constrain_kernel, decode-step form, behind launch_boost_step and in front of launch_logits_process: row r of gp.R
+// rows reads its history from the parity half of hist2 that *d_step selects (n = step), rows of chunks with
+// done[r / gp.K] are skipped.  logits [gp.R][gp.V] IN / OUT: every text id (< gp.ts_begin) that no phrase allows after the
+// row's history (include/fwamd.h) becomes -inf, gp.eot included unless the history is a whole phrase; the timestamp ids
+// become -inf unless gp.with_ts; every other value keeps its bits, nothing is read.  Reads gp.V, K, R, n_text_ctx, eot,
+// ts_begin, with_ts.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS: the callers check.
+void launch_constrain_step(hipStream_t st, const GenDev& gp, float* logits, const int* constrain_tab, const int* hist2,
+                           const int* d_step, const int* done);
+// ... score form, in front of launch_score, same row addressing: rows without a target (target < 0) are skipped, the
+// history is the ScoreRow's.  Every n <= n_text_ctx, a table built by fw_constraint_create: the caller's to guarantee.
+void launch_constrain_score(hipStream_t st, const GenDev& gp, float* logits, const int* constrain_tab, const ScoreRow* tab,
+                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// the same walk in plain C++ (fw_test_constrain_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void constrain_rows_host(const int* constrain_tab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts,
+                         const int* hist, const int* hist_offsets);
+
 }  // namespace fwd
 
 // what fw_boost_create returns: the list's vocabulary size and its compiled table (above)
 struct fw_boost {
   int32_t n_vocab;
   std::vector<int32_t> table;
+};
+
+// what fw_constraint_create returns: the list's vocabulary size, its compiled table (above) and, per compiled phrase, the
+// index the caller gave its first occurrence (for messages only: never compared)
+struct fw_constraint {
+  int32_t n_vocab;
+  std::vector<int32_t> table;
+  std::vector<int32_t> first;
 };

@@ -104,6 +104,9 @@ struct GenWorkspace {
   // at its maximum size (fwd::BOOST_TABLE_MAX_WORDS): the pointer never changes afterwards, so a cached step graph stays
   // valid whatever list the next run brings — the sizes travel in the table's header — and no graph holds a caller's pointer.
   GrowBuf<int> boost_tab;
+  // constrained decoding (fw_generate_constrain): the run's compiled table, held the same way (allocated once, by the first
+  // constrained run, at fwd::CONSTRAIN_TABLE_MAX_WORDS)
+  GrowBuf<int> constrain_tab;
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -585,6 +588,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     const bool alt = gp.n_alt > 0;   // (run_alt_ensure has sized the buffers for this run)
     // the boost comes first: the rules below see the boosted logits (run_init_state has filled the table for this run)
     if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
+    // then the constraint: what the list does not allow is -inf before the rules look
+    if (gp.constrain) fwd::launch_constrain_step(st, gp, g->logits, g->constrain_tab.p, g->hist2, g->d_step, g->done);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
                                alt ? g->alt_lp.p : nullptr, gp.trunc ? g->trunc_tab : nullptr);
@@ -715,6 +720,7 @@ struct GenRequest {
   int32_t* out_end_alt_ids = nullptr;    // [B, num_hypotheses, n_alt]
   float* out_end_alt_logprobs = nullptr;
   const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
+  const fw_constraint* constraint = nullptr;   // a non-empty constraint list | null (likewise)
   // truncated sampling (fw_generate_trunc): the limits on this call's draws, (0, 1) = none.  Like temperature and seed they
   // need NOT agree between the calls of a run: every row reads its call's from the run's TruncRow table.
   int top_k = 0;
@@ -735,10 +741,13 @@ struct GenRequest {
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
 // BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
+// CONSTRAINT LISTS (fw_generate_constrain) likewise.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
   if ((a.boost != nullptr) != (b.boost != nullptr)) return false;
   if (a.boost && a.boost != b.boost && a.boost->table != b.boost->table) return false;
+  if ((a.constraint != nullptr) != (b.constraint != nullptr)) return false;
+  if (a.constraint && a.constraint != b.constraint && a.constraint->table != b.constraint->table) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -878,6 +887,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.sample = sampling ? 1 : 0;
   gp.n_alt = n_alt;
   gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
+  gp.constrain = r0.constraint ? 1 : 0;   // (likewise)
   gp.trunc = (sampling && trunc) ? 1 : 0;   // (a run without a truncating call: today's kernels and graphs)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
@@ -957,6 +967,12 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
     FW_CHECK_ARG(tab.size() <= (size_t)fwd::BOOST_TABLE_MAX_WORDS, "boost table of %zu words", tab.size());
     if (int rc = g->boost_tab.ensure(fwd::BOOST_TABLE_MAX_WORDS)) return rc;
     FW_HIP(hipMemcpyAsync(g->boost_tab.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
+  }
+  if (pl.gp.constrain) {   // the run's constraint table, likewise
+    const std::vector<int32_t>& tab = reqs[0]->constraint->table;
+    FW_CHECK_ARG(tab.size() <= (size_t)fwd::CONSTRAIN_TABLE_MAX_WORDS, "constraint table of %zu words", tab.size());
+    if (int rc = g->constrain_tab.ensure(fwd::CONSTRAIN_TABLE_MAX_WORDS)) return rc;
+    FW_HIP(hipMemcpyAsync(g->constrain_tab.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   }
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
@@ -1407,6 +1423,49 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
                           float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
                           int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
                           float* out_end_alt_logprobs) {
+  return fw_generate_constrain(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, nullptr, out_ids,
+                               out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
+                               out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
+}
+
+// What fw_generate_constrain and fw_score_constrain refuse (include/fwamd.h): a list for another vocabulary, and rules
+// under which a listed phrase cannot be reached or a row is left without a live id.  `o`: the call's options / the scoring
+// rules; check_min_new: generate only (scoring does not read min_new_tokens).
+static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, const fw_gen_opts* o, bool check_min_new) {
+  FW_CHECK_ARG(ct->n_vocab == c.n_vocab, "the constraint list was built for a vocabulary of %d ids, the model has %d",
+               ct->n_vocab, c.n_vocab);
+  if (ct->table[0] == 0) return FW_OK;   // (an empty list: no constraint, nothing to refuse)
+  FW_CHECK_ARG(c.tok_eot >= 0 && c.tok_eot < c.tok_timestamp_begin && c.tok_timestamp_begin <= c.n_vocab &&
+                   c.n_vocab <= LP_SUP_WORDS * 64,
+               "this model's vocabulary layout (<eot> %d, first timestamp %d, %d ids) is not one the constraint kernel takes",
+               c.tok_eot, c.tok_timestamp_begin, c.n_vocab);
+  FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "a constraint list does not go with no_repeat_ngram_size %d: a listed phrase "
+               "that repeats an n-gram would be unreachable", o->no_repeat_ngram_size);
+  FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "a constraint list does not go with min_new_tokens %d: a row "
+               "whose phrase is complete would have no live id", o->min_new_tokens);
+  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
+  const fwd::ConstrainView cv = fwd::constrain_view(ct->table.data());
+  for (int j = 0; j < cv.P; ++j)
+    for (int i = cv.off[j]; i < cv.off[j + 1]; ++i) {
+      const int t = cv.tok[i];
+      FW_CHECK_ARG(t < c.tok_eot, "constraint phrase %d holds id %d: phrases are text, ids below <eot> = %d", ct->first[j], t,
+                   c.tok_eot);
+      FW_CHECK_ARG(!((mask[t >> 6] >> (t & 63)) & 1ull), "constraint phrase %d holds id %d, which the suppress list forbids",
+                   ct->first[j], t);
+      if (i == cv.off[j] && o->suppress_blank)
+        for (int k = 0; k < c.n_suppress_begin; ++k)
+          FW_CHECK_ARG(t != c.suppress_begin[k], "constraint phrase %d starts with id %d, which suppress_blank forbids at "
+                       "the first step", ct->first[j], t);
+    }
+  return FW_OK;
+}
+
+int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                              int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt,
+                              const fw_boost* boost, const fw_constraint* constraint, int32_t* out_ids, int32_t* out_lens,
+                              float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
+                              int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                              float* out_end_alt_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
@@ -1425,6 +1484,8 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
   FW_CHECK_ARG(B >= 1 && B <= dm->max_batch, "batch %d exceeds max_batch %d", B, dm->max_batch);
   FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
                boost ? boost->n_vocab : 0, c.n_vocab);
+  if (constraint)
+    if (int rc = constraint_check(constraint, c, o, true)) return rc;
   const int K = o->beam_size;
   FW_CHECK_ARG(K >= 1 && K <= dm->max_beam, "beam_size %d not in [1, max_beam=%d]", K, dm->max_beam);
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
@@ -1476,6 +1537,7 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
   req.sampling = sampling;
   req.top_k = top_k; req.top_p = top_p;
   req.boost = (boost && boost->table[0] > 0) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
+  req.constraint = (constraint && constraint->table[0] > 0) ? constraint : nullptr;   // (likewise)
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -1834,13 +1896,25 @@ extern "C" int32_t fw_score(fw_model* fm, const fw_tensor* enc_t, const int32_t*
                         out_best_ids, out_best_logprobs);
 }
 
-// fw_score with a boost list: dec_boost_kernel on the block's logits (recomputed per block) in front of the scoring kernel
+// fw_score with a boost list: fw_score_constrain without a constraint list
 extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                                   const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
                                   const fw_gen_opts* rules, const fw_boost* boost, float* out_token_logprobs,
                                   int32_t* out_best_ids, float* out_best_logprobs) {
+  return fw_score_constrain(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, nullptr,
+                            out_token_logprobs, out_best_ids, out_best_logprobs);
+}
+
+// fw_score with a boost list and / or a constraint list: dec_boost_kernel, then dec_constrain_kernel, on the block's logits
+// (recomputed per block) in front of the scoring kernel
+extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts,
+                                      const int32_t* prompt_offsets, const int32_t* targets, const int32_t* target_offsets,
+                                      int32_t B, int32_t H, const fw_gen_opts* rules, const fw_boost* boost,
+                                      const fw_constraint* constraint, float* out_token_logprobs, int32_t* out_best_ids,
+                                      float* out_best_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
   FW_CHECK_ARG(!boost || rules, "a boost list needs rules: the boost is the first step of the decoding rules");
+  FW_CHECK_ARG(!constraint || rules, "a constraint list needs rules: the constraint is a step of the decoding rules");
   FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
   Model* m = decoder_of(&fm->impl);
   const Tensor* enc = &enc_t->impl;
@@ -1851,6 +1925,10 @@ extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const in
   FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
                boost ? boost->n_vocab : 0, c.n_vocab);
   if (boost && boost->table[0] == 0) boost = nullptr;   // (an empty list does nothing)
+  if (constraint) {
+    if (int crc = constraint_check(constraint, c, rules, false)) return crc;
+    if (constraint->table[0] == 0) constraint = nullptr;   // (likewise)
+  }
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
   FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
   const int Bx = B * H;
@@ -1933,6 +2011,12 @@ extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const in
     if ((rc = tmp.alloc(&boost_dev, boost->table.size()))) return rc;
     FW_HIP_AS(setup_fail, hipMemcpyAsync(boost_dev, boost->table.data(), boost->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
+  int* constrain_dev = nullptr;
+  if (constraint) {
+    const std::vector<int32_t>& ctab = constraint->table;
+    if ((rc = tmp.alloc(&constrain_dev, ctab.size()))) return rc;
+    FW_HIP_AS(setup_fail, hipMemcpyAsync(constrain_dev, ctab.data(), ctab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
   FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -1952,6 +2036,8 @@ extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const in
         if (pos + nb - 1 < P - 1) return;
         ProfScope ps(lane->prof, PF_DEC_MISC, 0, 4.0 * Bx * nb * (double)c.n_vocab, st);
         if (boost_dev) fwd::launch_boost_score(st, gp, g->logits, boost_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
+        if (constrain_dev)
+          fwd::launch_constrain_score(st, gp, g->logits, constrain_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         fwd::launch_score(st, gp, rules != nullptr, g->logits, g->sup_bits, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev, lp_dev,
                           bid_dev, blp_dev);
       });

@@ -1220,6 +1220,98 @@ int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist
   return FW_OK;
 }
 
+// what both constraint hooks check of the caller's vocabulary geometry and list
+static int32_t constrain_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, int32_t with_timestamps,
+                                    const fw_constraint* ct) {
+  FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
+               "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
+  FW_CHECK_ARG(with_timestamps == 0 || with_timestamps == 1, "with_timestamps %d is not 0 / 1", with_timestamps);
+  FW_CHECK_ARG(ct->n_vocab == n_vocab, "the constraint list was built for a vocabulary of %d ids, not %d", ct->n_vocab, n_vocab);
+  return FW_OK;
+}
+
+// ONE launch of dec_constrain_kernel in either row form (include/fwamd_test.h); everything is checked before anything is
+// allocated or launched.  The model gives the device and the text context (the stride of the step form's histories) only.
+int32_t fw_test_constrain_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                               int32_t tok_ts_begin, int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                               int32_t K, const int32_t* done, int32_t form, const fw_constraint* constraint) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && constraint && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  Model* m = &fm->impl;
+  const fw_config& c = m->cfg;
+  if (int rc = constrain_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint)) return rc;
+  FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, c.n_text_ctx, n_vocab)) return rc;
+  const int n0 = hist_offsets[1];
+  if (form == 0)
+    for (int r = 0; r < rows; ++r)
+      FW_CHECK_ARG(hist_offsets[r + 1] - hist_offsets[r] == n0, "form 0 takes one n for all rows (row %d)", r);
+  const int n_done = form == 0 ? rows / K : rows;
+  if (done)
+    for (int b = 0; b < n_done; ++b) FW_CHECK_ARG(done[b] == 0 || done[b] == 1, "done[%d] = %d is not 0 / 1", b, done[b]);
+  FW_HIP(hipSetDevice(m->device));
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.B = rows / K; gp.K = K; gp.R = rows; gp.V = n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.constrain = 1;
+  gp.eot = tok_eot; gp.ts_begin = tok_ts_begin; gp.with_ts = with_timestamps;
+  HookBufs db;
+  float* d_lg;
+  int* d_tab;
+  int rc;
+  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * n_vocab)) ||
+      (rc = db.upload(&d_tab, (const int*)constraint->table.data(), constraint->table.size())))
+    return rc;
+  if (form == 0) {
+    const size_t NT = (size_t)c.n_text_ctx;
+    std::vector<int> h2(2 * (size_t)rows * NT, 0), dn((size_t)rows, 0);
+    for (int r = 0; r < rows; ++r)
+      for (int i = 0; i < n0; ++i) h2[((size_t)(n0 & 1) * rows + r) * NT + i] = hist[hist_offsets[r] + i];
+    if (done) std::copy(done, done + n_done, dn.begin());
+    int *d_hist, *d_step, *d_done;
+    if ((rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n0, 1)) ||
+        (rc = db.upload(&d_done, dn.data(), dn.size())))
+      return rc;
+    fwd::launch_constrain_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
+  } else {
+    std::vector<fwd::ScoreRow> tab((size_t)rows);
+    for (int r = 0; r < rows; ++r)
+      tab[r] = {(done && done[r]) ? -1 : 0, hist_offsets[r + 1] - hist_offsets[r], hist_offsets[r], r};
+    const size_t n_hist = (size_t)hist_offsets[rows];
+    const int zero = 0;
+    fwd::ScoreRow* d_rows;
+    int* d_hist;
+    if ((rc = db.upload(&d_rows, tab.data(), tab.size())) ||
+        (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
+      return rc;
+    fwd::launch_constrain_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
+  }
+  FW_HIP(hipGetLastError());
+  FW_HIP(hipDeviceSynchronize());
+  return download(logits, d_lg, (size_t)rows * n_vocab);
+}
+
+// the same table walked on the host: no device, no model
+int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                    int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                                    const fw_constraint* constraint) {
+  FW_CHECK_ARG(logits && hist_offsets && constraint && rows >= 1, "bad arguments");
+  if (int rc = constrain_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint)) return rc;
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
+  const int zero = 0;
+  fwd::constrain_rows_host(constraint->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
+                           hist ? hist : &zero, hist_offsets);
+  return FW_OK;
+}
+
+// the compiled table of a constraint list, for the byte-equality the merge rule rests on: *out_words = its size in 32-bit
+// words; `out` (may be NULL) receives min(cap, size) words
+int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, int32_t cap, int32_t* out_words) {
+  FW_CHECK_ARG(constraint && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
+  *out_words = (int32_t)constraint->table.size();
+  std::copy(constraint->table.begin(), constraint->table.begin() + std::min<size_t>((size_t)cap, constraint->table.size()), out);
+  return FW_OK;
+}
+
 // step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together
 int32_t fw_test_graph_captures(const fw_model* fm, int64_t* out) {
   FW_CHECK_ARG(fm && out, "null argument");

@@ -125,6 +125,18 @@ def _boost_keyword(boost) -> dict:
     return {} if boost is None else {"boost": boost}
 
 
+class _BuiltConstraint:
+    """a constraint list that is built already, in the place of transcribe()'s allowed_phrases (as _BuiltBoost)"""
+
+    def __init__(self, constraint):
+        self.constraint = constraint
+
+
+def _constraint_keyword(constraint) -> dict:
+    """the keyword a call passes down for its constraint list — only when it has one (as _boost_keyword)"""
+    return {} if constraint is None else {"constraint": constraint}
+
+
 def _check_trunc_arguments(sampling_top_k, sampling_top_p) -> None:
     """sampling_top_k: an integer >= 0; sampling_top_p: a number in (0, 1] (ValueError) — what fw_generate_trunc accepts,
     checked before anything is decoded"""
@@ -205,6 +217,14 @@ def _check_boost_arguments(boost_phrases, phrase_boost) -> None:
         raise ValueError("boost_phrases must be a sequence of strings, one per phrase")
     if len(boost_phrases) and phrase_boost is None:
         raise ValueError("boost_phrases need phrase_boost: the strength of the boost in logit units has no default")
+
+
+def _check_constraint_arguments(allowed_phrases) -> None:
+    """allowed_phrases: None, or a sequence of strings (ValueError)"""
+    if allowed_phrases is None or isinstance(allowed_phrases, _BuiltConstraint):
+        return
+    if isinstance(allowed_phrases, (str, bytes)) or not all(isinstance(p, str) for p in allowed_phrases):
+        raise ValueError("allowed_phrases must be a sequence of strings, one per phrase")
 
 
 def _per_recording(value, n, name, is_single):
@@ -529,7 +549,8 @@ class WhisperModel:
                    language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                    vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
                    token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
-                   phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0):
+                   phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0,
+                   allowed_phrases: Optional[Sequence[str]] = None):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -549,9 +570,12 @@ class WhisperModel:
         sampling_top_k, sampling_top_p (not in the reference): limits on the sampled attempts of the fallback ladder (the
         rungs with temperature > 0; the attempt at temperature 0 is a beam search and takes none): every draw comes from
         the sampling_top_k most likely tokens, then from the nucleus that holds sampling_top_p of their tempered mass
-        (include/fwamd.h: fw_generate_trunc).  0 / 1.0 (the defaults): the whole distribution, as the reference samples."""
+        (include/fwamd.h: fw_generate_trunc).  0 / 1.0 (the defaults): the whole distribution, as the reference samples.
+        allowed_phrases (not in the reference): see constraint_list_for — every decoded window is then exactly ONE phrase
+        of the list, in every attempt of the fallback ladder.  Composes with boost_phrases."""
         args = dict(locals())               # the call's arguments by name
         _check_boost_arguments(boost_phrases, phrase_boost)
+        _check_constraint_arguments(allowed_phrases)
         _check_trunc_arguments(sampling_top_k, sampling_top_p)
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
@@ -593,6 +617,7 @@ class WhisperModel:
         segments = self.generate_segments(features, tokenizer, options, log_progress, None,
                                           **_value_keywords(token_logprobs, token_alternatives),
                                           **_boost_keyword(self.boost_list_for(boost_phrases, phrase_boost, tokenizer)),
+                                          **_constraint_keyword(self.constraint_list_for(allowed_phrases, tokenizer)),
                                           **_trunc_keywords(sampling_top_k, sampling_top_p),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
@@ -629,11 +654,13 @@ class WhisperModel:
         which recording gets which seed depends on timing.
         boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcribe(), so the
         windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
+        allowed_phrases: likewise ONE constraint list for every recording.
         sampling_top_k / sampling_top_p (not in the reference): transcribe()'s, the same limits for every recording; sampled
         attempts share decode runs whatever their limits.
         An exception in one recording is raised here, after the recordings already started have finished."""
         n = len(audios)
         _check_boost_arguments(transcribe_kwargs.get("boost_phrases"), transcribe_kwargs.get("phrase_boost"))
+        _check_constraint_arguments(transcribe_kwargs.get("allowed_phrases"))
         _check_trunc_arguments(transcribe_kwargs.get("sampling_top_k", 0), transcribe_kwargs.get("sampling_top_p", 1.0))
         if n == 0:
             return []
@@ -642,6 +669,10 @@ class WhisperModel:
             built = self.boost_list_for(transcribe_kwargs["boost_phrases"], transcribe_kwargs.get("phrase_boost"),
                                         self.make_tokenizer())
             transcribe_kwargs = dict(transcribe_kwargs, boost_phrases=None if built is None else _BuiltBoost(built))
+        if transcribe_kwargs.get("allowed_phrases") is not None:
+            built = self.constraint_list_for(transcribe_kwargs["allowed_phrases"], self.make_tokenizer())
+            transcribe_kwargs = dict(transcribe_kwargs,
+                                     allowed_phrases=None if built is None else _BuiltConstraint(built))
         languages = _per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
         prompts = _per_recording(
             initial_prompt, n, "initial_prompt",
@@ -673,7 +704,7 @@ class WhisperModel:
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
                           token_logprobs: bool = False, sampling_seed: Optional[int] = None,
                           token_alternatives: int = 0, boost=None, sampling_top_k: int = 0,
-                          sampling_top_p: float = 1.0):
+                          sampling_top_p: float = 1.0, constraint=None):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -729,7 +760,8 @@ class WhisperModel:
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
                     encoder_output, prompt, tokenizer, options, **_value_keywords(token_logprobs, token_alternatives),
-                    **_boost_keyword(boost), **_trunc_keywords(sampling_top_k, sampling_top_p),
+                    **_boost_keyword(boost), **_constraint_keyword(constraint),
+                    **_trunc_keywords(sampling_top_k, sampling_top_p),
                     **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
@@ -783,7 +815,7 @@ class WhisperModel:
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
                                options: TranscriptionOptions, token_logprobs: bool = False,
                                sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0,
-                               boost=None, sampling_top_k: int = 0, sampling_top_p: float = 1.0):
+                               boost=None, sampling_top_k: int = 0, sampling_top_p: float = 1.0, constraint=None):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
@@ -791,6 +823,7 @@ class WhisperModel:
         sampling_seed: the sampled attempt at rung t gets seed=attempt_seed(sampling_seed, seek, t), `seek` the window's
         first frame; None: no seed is passed, the backend draws one from its call counter.
         boost: the call's boost list (boost_list_for), the same one for every attempt.
+        constraint: the call's constraint list (constraint_list_for), likewise.
         sampling_top_k / sampling_top_p: limits on the draws of the sampled attempts (temperature > 0) only; at 0 / 1.0 no
         keyword is passed to generate.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
@@ -813,6 +846,7 @@ class WhisperModel:
                 max_length=max_length, return_scores=True, return_no_speech_prob=True,
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
                 max_initial_timestamp_index=max_initial_timestamp_index, **mode, **_boost_keyword(boost),
+                **_constraint_keyword(constraint),
                 **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))[0]
             avg_logprob = _avg_logprob(result, options.length_penalty)
             compression_ratio = get_compression_ratio(tokenizer.decode(result.sequences_ids[0]).strip())
@@ -855,6 +889,27 @@ class WhisperModel:
         if not phrases:
             return None
         return self.model.boost_list(phrases, [float(phrase_boost)] * len(phrases))
+
+    def constraint_list_for(self, allowed_phrases, tokenizer: Tokenizer):
+        """The constraint list of a transcribe() call (backend.Whisper.constraint_list), or None without phrases.  Every
+        phrase is encoded as " " + phrase.strip(), as boost_phrases are: ONE variant per phrase, in the caller's casing.
+        Every generate call of the transcription then returns exactly one phrase of the list (its timestamps apart), so
+        EACH DECODED WINDOW IS ONE PHRASE: the keyword is meant for short clips and VAD-cut chunks — voice commands, form
+        fields, re-recognition against an n-best list — not for running speech (a sequence of phrases is out of scope,
+        as are grammars).  The decoding options must leave every phrase reachable, or the first generate call raises
+        ValueError: with the default suppress_tokens=[-1] a phrase that contains a suppressed symbol is one (pass
+        suppress_tokens=[] or drop the phrase), as are no_repeat_ngram_size > 0 and, with suppress_blank, a phrase whose
+        first token is the blank.  The list is built once per call and reused for every window, every attempt of the
+        temperature ladder, every batch and every recording."""
+        _check_constraint_arguments(allowed_phrases)
+        if allowed_phrases is None:
+            return None
+        if isinstance(allowed_phrases, _BuiltConstraint):
+            return allowed_phrases.constraint
+        phrases = [tokenizer.encode(" " + p.strip()) for p in allowed_phrases]
+        if not phrases:
+            return None
+        return self.model.constraint_list(phrases)
 
     def make_tokenizer(self, task="transcribe", language="en") -> Tokenizer:
         return Tokenizer(self.hf_tokenizer, self.model.config, self.model.is_multilingual, task=task, language=language)
@@ -1039,13 +1094,14 @@ class BatchedInferencePipeline:
     # ---- one batch: encode + generate ---------------------------------------------------
     def generate_segment_batched(self, features, tokenizer: Tokenizer, options: TranscriptionOptions,
                                  audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False,
-                                 token_alternatives: int = 0, boost=None):
+                                 token_alternatives: int = 0, boost=None, constraint=None):
         """features: [B, n_mels, 3000] float32, or None when `audio_chunks` is given (fused resident
         PCM -> log-mel -> encoder path; the features never leave HBM).  token_logprobs: every output dict also carries
         the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`);
         token_alternatives=N: those, and the N most likely (id, log-prob) pairs per token (`token_alternatives`) and at
         the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget).  boost: the call's boost list
-        (WhisperModel.boost_list_for), passed to generate when there is one."""
+        (WhisperModel.boost_list_for), passed to generate when there is one; constraint: its constraint list
+        (WhisperModel.constraint_list_for), likewise."""
         m = self.model
         batch_size = len(audio_chunks) if audio_chunks is not None else features.shape[0]
         prompt = m.get_prompt(tokenizer,
@@ -1068,7 +1124,7 @@ class BatchedInferencePipeline:
             length_penalty=options.length_penalty, max_length=max_length, suppress_blank=options.suppress_blank,
             suppress_tokens=options.suppress_tokens, return_scores=True, return_no_speech_prob=True,
             sampling_temperature=options.temperatures[0], repetition_penalty=options.repetition_penalty,
-            no_repeat_ngram_size=options.no_repeat_ngram_size, **_boost_keyword(boost),
+            no_repeat_ngram_size=options.no_repeat_ngram_size, **_boost_keyword(boost), **_constraint_keyword(constraint),
             **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))
         output = []
         for r in results:
@@ -1129,7 +1185,8 @@ class BatchedInferencePipeline:
                    shard: bool = False, fused_features: bool = True, vad_speech_probs=None,
                    token_logprobs: bool = False, token_alternatives: int = 0,
                    boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None,
-                   sampling_top_k: int = 0, sampling_top_p: float = 1.0):
+                   sampling_top_k: int = 0, sampling_top_p: float = 1.0,
+                   allowed_phrases: Optional[Sequence[str]] = None):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1143,11 +1200,14 @@ class BatchedInferencePipeline:
         boost_phrases, phrase_boost (not in the reference): see WhisperModel.boost_list_for — one list for every batch.
         sampling_top_k, sampling_top_p (not in the reference): WhisperModel.transcribe's limits on sampled attempts,
         validated here as there (ValueError).  They apply to the temperature > 0 rungs of the fallback ladder only, and the
-        batched path decodes every chunk once, without sampling (as the reference's does): here they limit nothing."""
+        batched path decodes every chunk once, without sampling (as the reference's does): here they limit nothing.
+        allowed_phrases (not in the reference): see WhisperModel.constraint_list_for — every chunk decodes to exactly one
+        phrase of the list; one list for every batch.  Composes with boost_phrases."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model
         _check_boost_arguments(boost_phrases, phrase_boost)
+        _check_constraint_arguments(allowed_phrases)
         _check_trunc_arguments(sampling_top_k, sampling_top_p)
         if (token_logprobs or token_alternatives) and shard:
             raise ValueError("token_logprobs / token_alternatives are not offered with shard=True: the gathered records "
@@ -1169,7 +1229,8 @@ class BatchedInferencePipeline:
         gen = self._batched_segments_generator(rec.audio_chunks, rec.tokenizer, rec.chunks_metadata, batch_size,
                                                rec.options, log_progress, shard, fused_features,
                                                **_value_keywords(token_logprobs, token_alternatives),
-                                               **_boost_keyword(m.boost_list_for(boost_phrases, phrase_boost, rec.tokenizer)))
+                                               **_boost_keyword(m.boost_list_for(boost_phrases, phrase_boost, rec.tokenizer)),
+                                               **_constraint_keyword(m.constraint_list_for(allowed_phrases, rec.tokenizer)))
         return self._on_recording_time(rec, gen), rec.info
 
     # ---- the steps of transcribe that transcribe_many runs per recording -----------------
@@ -1275,7 +1336,7 @@ class BatchedInferencePipeline:
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
                                     log_progress, shard=False, fused_features=True, token_logprobs=False,
-                                    token_alternatives=0, boost=None):
+                                    token_alternatives=0, boost=None, constraint=None):
         from .sharding import gather_results, partition
         m = self.model
         rank, world, local_rank = 0, 1, 0
@@ -1299,7 +1360,7 @@ class BatchedInferencePipeline:
                 spans = [(lo, mid), (mid, hi)]
             return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
                                             for i0, i1 in spans], shard, fused_features, token_logprobs,
-                                           token_alternatives, boost)
+                                           token_alternatives, boost, constraint)
 
         def emit(results):
             nonlocal seg_idx
@@ -1346,14 +1407,14 @@ class BatchedInferencePipeline:
         self.last_speech_timestamp = 0.0
 
     def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
-                      token_logprobs=False, token_alternatives=0, boost=None):
+                      token_logprobs=False, token_alternatives=0, boost=None, constraint=None):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
         m = self.model
         feats = None if fused_features else m.model.log_mel(chunks)
         enc, outs = self.generate_segment_batched(feats, tokenizer, options,
                                                   audio_chunks=chunks if fused_features else None,
                                                   **_value_keywords(token_logprobs, token_alternatives),
-                                                  **_boost_keyword(boost))
+                                                  **_boost_keyword(boost), **_constraint_keyword(constraint))
         local = aligned = None
         if not shard or options.word_timestamps:
             local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
@@ -1364,7 +1425,7 @@ class BatchedInferencePipeline:
         return outs, local, aligned
 
     def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False, token_alternatives=0,
-                           boost=None):
+                           boost=None, constraint=None):
         """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
         The batches are independent (`condition_on_previous_text=False`): with worker replicas
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
@@ -1373,7 +1434,7 @@ class BatchedInferencePipeline:
         workers = self.model._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
-                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives, boost)
+                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives, boost, constraint)
             return
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
@@ -1381,7 +1442,7 @@ class BatchedInferencePipeline:
             pending = deque()
             for job in jobs:
                 pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs,
-                                           token_alternatives, boost))
+                                           token_alternatives, boost, constraint))
                 if len(pending) >= workers:
                     yield pending.popleft().result()
             while pending:
@@ -1427,6 +1488,7 @@ class BatchedInferencePipeline:
         m = self.model
         n = len(audios)
         _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
+        _check_constraint_arguments(a["allowed_phrases"])
         _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
         if n == 0:
             return []
@@ -1489,9 +1551,10 @@ class BatchedInferencePipeline:
         # ---- route: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
         # (ONE boost list for the batches of every recording and language: the text encoding is the vocabulary's)
         boost = m.boost_list_for(a["boost_phrases"], a["phrase_boost"], next(iter(tokenizers.values())))
+        constraint = m.constraint_list_for(a["allowed_phrases"], next(iter(tokenizers.values())))
         for owner, (_, local, aligned) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
                                                                               a["token_logprobs"],
-                                                                              a["token_alternatives"], boost)):
+                                                                              a["token_alternatives"], boost, constraint)):
             for j, rec in enumerate(owner):
                 rec.decoded.append(local[j])
                 if aligned is not None:

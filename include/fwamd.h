@@ -16,6 +16,8 @@
  *   .align             transcribe.py:1709-1715          -> fw_align
  *   .score             (not in the reference: CTranslate2's score_batch for Whisper) -> fw_score
  *   boost=             (not in the reference: phrase boosting at the logit) -> fw_boost_create, fw_generate_boost, fw_score_boost
+ *   constraint=        (not in the reference: decoding restricted to a phrase list) -> fw_constraint_create,
+ *                      fw_generate_constrain, fw_score_constrain
  *
  * plus the log-mel front end the reference runs in numpy on the host
  * (faster_whisper/feature_extractor.py:198-230, called at
@@ -57,7 +59,9 @@ extern "C" {
  *    fw_vad_forward_audio_batch_dev likewise, fw_generate_lp (fw_generate plus per-token log-probabilities) and
  *    fw_score (teacher-forced log-probs of given transcripts), fw_generate_alt (fw_generate_lp plus the n most
  *    likely tokens at every position), fw_boost_create / fw_boost_free / fw_generate_boost / fw_score_boost (phrases made
- *    more likely by a stated amount, at the logit) */
+ *    more likely by a stated amount, at the logit), fw_generate_trunc (top-k / nucleus limits on the sampled draw),
+ *    fw_constraint_create / fw_constraint_free / fw_generate_constrain / fw_score_constrain (decoding restricted to a
+ *    given phrase list) — new symbols only, each time */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -183,7 +187,8 @@ int32_t fw_model_create_from_blob_dev(const fw_config* cfg, const void* blob_dev
  * next run (up to decode_batch chunks); each caller gets exactly the result it would get alone.  What must agree for two
  * calls to share a run: beam_size, patience, num_hypotheses, length_penalty, repetition_penalty, no_repeat_ngram_size,
  * max_length, max_initial_timestamp_index, suppress_blank, min_new_tokens, the suppress list, the boost list
- * (fw_generate_boost: none on both sides, or byte-equal compiled tables), and the timestamp mode
+ * (fw_generate_boost: none on both sides, or byte-equal compiled tables), the constraint list (fw_generate_constrain: the
+ * same rule), and the timestamp mode
  * (<|notimestamps|> in the prompt or not).  Sampling calls (beam_size 1, sampling_topk 0) merge among themselves, never with
  * beam or greedy calls; their sampling_temperature and seed need NOT agree (every row of a run draws with its own call's,
  * as the row of that call that it is alone), and neither do the top_k / top_p of fw_generate_trunc (a truncating call
@@ -378,6 +383,65 @@ int32_t fw_generate_trunc(fw_model* m, const fw_tensor* enc, const int32_t* prom
                           int32_t* out_alt_ids, float* out_alt_logprobs,
                           int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
 
+/* ---- constrained decoding: the transcript is one of a given phrase list (not in CTranslate2) ----------------
+ * The counterpart of the boost: a boost adds in front of the rules, a constraint REMOVES in front of the rules.  A
+ * constraint list is n_phrases phrases of token ids, laid out as a boost list (tokens, offsets) under limits of its own,
+ * without floats.  Phrase j is p_j[0 .. L_j).  For one logits row let h[0 .. n) be the row's GENERATED history (never the
+ * prompt) and t[0 .. m) be h without its ids >= tok_timestamp_begin.  Then
+ *   M = {j : m <= L_j and p_j[0 .. m) == t},  A = {p_j[m] : j in M, m < L_j},  <eot> is allowed iff some j in M has L_j == m.
+ * What is written, and nothing else:
+ *   - every id v < tok_timestamp_begin keeps its bits if it is in A, or if it is <eot> and <eot> is allowed; otherwise
+ *     logit[v] = -inf;
+ *   - the ids >= tok_timestamp_begin keep their bits when the timestamp rules are on (no <|notimestamps|> in the prompt);
+ *     with <|notimestamps|> they become -inf;
+ *   - nothing is added to any logit.
+ * A history that is a prefix of no phrase has M empty: no text id and no <eot>.  In fw_generate_constrain that arises on
+ * dead beam copies only; in scoring it is a target that left the list, which gets -inf from there on.
+ * Order per step: the boost if there is one, then the constraint, then the rules exactly as always.  Token log-probs,
+ * alternatives, scores and sampled draws are those of the constrained, processed distribution; a position with fewer live
+ * ids than n_alt fills the tail with (0, -inf) as documented at fw_generate_alt.  out_no_speech is unaffected (it is read
+ * before the rules).
+ * THE GUARANTEE: take a returned hypothesis with a finite score and remove its timestamp ids.  If it closed on <eot>, what
+ * remains is a phrase of the list; if it was cut at the budget, what remains is a prefix of a phrase: a proper one,
+ * except where the budget ended on the very step that would have closed a whole phrase with <eot>.
+ * OUT OF SCOPE: a SEQUENCE of phrases (a repeat mode needs per-row automaton state or a prefix-free list), grammars, and
+ * different lists for the calls of one run (a run walks one table).
+ * fw_constraint_create is host code: it needs no device and no model.  FW_EINVAL: n_vocab < 1, a null pointer with
+ * n_phrases > 0, more than FW_CONSTRAIN_MAX_PHRASES phrases, offsets[0] != 0, a phrase of no token or of more than
+ * FW_CONSTRAIN_MAX_LEN, more than FW_CONSTRAIN_MAX_TOKENS tokens in all, an id outside [0, n_vocab).  Duplicate phrases
+ * are valid, and so is a phrase that is a prefix of another (<eot> and the longer phrase's next token are then both
+ * allowed).  An empty list (n_phrases == 0; the pointers may be NULL) is valid and means NO constraint, as with the boost.
+ * The list compiles to one int32 table: the phrases as a set, sorted by their ids, duplicates dropped.  Equal arguments
+ * give byte-equal tables, and so do lists that name the same phrases in another order or more than once. */
+#define FW_CONSTRAIN_MAX_PHRASES 1024
+#define FW_CONSTRAIN_MAX_LEN 32
+#define FW_CONSTRAIN_MAX_TOKENS 4096
+typedef struct fw_constraint fw_constraint;   /* opaque: a validated, compiled list (host memory); any number of calls may read it at once */
+int32_t fw_constraint_create(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
+                             fw_constraint** out);
+void fw_constraint_free(fw_constraint* c);
+/* fw_generate_trunc plus a constraint list.  constraint == NULL (or an empty list) is fw_generate_trunc exactly, bit for
+ * bit.  FW_EINVAL before anything is queued, each message naming the phrase (the caller's index) and the id:
+ *   - the list was built for another n_vocab than the model's;
+ *   - a phrase id is >= tok_eot (phrases are text);
+ *   - a phrase id is in opts' suppress list;
+ *   - opts->suppress_blank is set and a phrase's first id is one of the model's suppress_begin ids;
+ *   - opts->no_repeat_ngram_size > 0;
+ *   - opts->min_new_tokens > 0.
+ * The last four would make a listed phrase unreachable or leave a row without a live id.
+ * Merging: two calls share a decode run only when both have no list or their compiled tables are byte-equal — the rule of
+ * the boost list, beside it; a constrained call never shares a run with a plain one, and every caller gets its solo result
+ * bit for bit.  A constrained run costs one kernel launch per step more (it writes -inf over rows x n_vocab floats); its
+ * table is copied into a buffer of the decode lane at the start of the run (the list may be freed once the call has
+ * returned).  Identity (1) of fw_generate_alt holds unchanged, and (2) with fw_score_constrain in fw_score's place. */
+int32_t fw_generate_constrain(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                              int32_t B, const fw_gen_opts* opts, int32_t top_k, float top_p, int32_t n_alt,
+                              const fw_boost* boost, const fw_constraint* constraint,
+                              int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                              float* out_token_logprobs, float* out_end_logprobs,
+                              int32_t* out_alt_ids, float* out_alt_logprobs,
+                              int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
+
 /* ---- score ---------------------------------------------------------------
  * Teacher-forced log-probs of GIVEN transcripts (CTranslate2 has score_batch for its other model classes): how likely
  * is this text under the model, for text that was not decoded here — a corrected transcript, another system's output,
@@ -410,6 +474,18 @@ int32_t fw_score(fw_model* m, const fw_tensor* enc, const int32_t* prompts, cons
 int32_t fw_score_boost(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
                        const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
                        const fw_boost* boost, float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
+/* fw_score_boost plus a constraint list (constrained decoding, above): on every scored row the boost (if any), then the
+ * constraint with the sequence's own prefix as the generated history, then the rules.  constraint == NULL (or an empty
+ * list) is fw_score_boost exactly; otherwise rules != NULL is needed, and the checks of fw_generate_constrain run against
+ * the rules' fields (FW_EINVAL; min_new_tokens is not read by scoring and not checked).  A target sequence that leaves the
+ * list at position q scores finite before q and -inf from q on, its <eot> entry included.  For a greedy hypothesis of
+ * fw_generate_constrain it returns out_token_logprobs and out_end_logprobs bit for bit, and out_best_ids /
+ * out_best_logprobs are its alternative 0.  Re-recognition against an n-best list larger than max_beam: one constrained
+ * generate call instead of ceil(n / max_beam) scoring calls. */
+int32_t fw_score_constrain(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                           const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                           const fw_gen_opts* rules, const fw_boost* boost, const fw_constraint* constraint,
+                           float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
 
 /* ---- detect_language -------------------------------------------------------
  * ctranslate2.models.Whisper.detect_language: one decoder step on [sot];

@@ -183,6 +183,24 @@ int32_t fw_test_boost_rows(fw_model* m, float* logits, int32_t rows, const int32
  * IN / OUT with ragged histories as above — what fw_boost_create compiled, testable without a GPU */
 int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                                 const fw_boost* boost);
+/* ONE launch of dec_constrain_kernel (constrained decoding, include/fwamd.h) in either row form on caller-provided rows,
+ * with the rows, histories, K, done and form of fw_test_boost_rows above.  The model gives the device, the stream and the
+ * text context only: the vocabulary geometry is the caller's — logits [rows][n_vocab] IN / OUT, returned whole, <eot> =
+ * tok_eot, timestamp ids from tok_ts_begin, with_timestamps 1 (the timestamp rules are on: those ids keep their bits) / 0 —
+ * so a test chooses n_vocab mod 4 and with it the alignment of every row.  Checked before anything is allocated or
+ * launched: what fw_test_boost_rows checks, 0 <= tok_eot < tok_ts_begin <= n_vocab <= 57344, with_timestamps 0 / 1, and
+ * that the list was built for n_vocab.  The ids of the list are NOT checked against tok_eot (fw_generate_constrain's
+ * check): an id >= tok_ts_begin in a phrase allows nothing. */
+int32_t fw_test_constrain_rows(fw_model* m, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                               int32_t tok_ts_begin, int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                               int32_t K, const int32_t* done, int32_t form, const fw_constraint* constraint);
+/* host-only (no device, no model needed): the same table walked in plain C++, ragged histories of any length */
+int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                    int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                                    const fw_constraint* constraint);
+/* host-only: the compiled table of a list (what the merge rule compares).  *out_words = its size in 32-bit words; out
+ * (NULL with cap == 0) receives the first min(cap, size) words */
+int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, int32_t cap, int32_t* out_words);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
