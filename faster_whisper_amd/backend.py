@@ -149,28 +149,22 @@ class WhisperScoringResult:
                 f"end_logprobs={self.end_logprobs})")
 
 
-class BoostList:
-    """A validated, compiled list of phrases to boost (fwamd.h: fw_boost_create): phrases[j] is a sequence of token ids,
-    boosts[j] the float added to the logit of the phrase's next token wherever the generated history ends with the tokens
-    in front of it (the first token: at every step).  Where several phrases ask for one id the largest boost counts, not the
-    sum; the decoding rules run after the boost and still win.  Host-only: needs no device.  Whisper.boost_list builds one
-    for the model's vocabulary; pass it as generate(boost=...) / score(boost=...)."""
+class _PhraseList:
+    """What BoostList and ConstraintList share: the ragged packing of the phrases, the engine's handle and its release, the
+    type check of the keyword that takes the list.  A subclass names its keyword, what the feature is called in messages,
+    and its create / free symbols."""
+    _keyword = _feature = _create = _free = None
 
-    def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]], boosts: Sequence[float]):
-        phrases = [list(p) for p in phrases]
-        boosts = list(boosts)
-        if len(phrases) != len(boosts):
-            raise ValueError(f"got {len(phrases)} phrases and {len(boosts)} boosts")
+    def _compile(self, n_vocab: int, phrases, *per_phrase):
         lib = _lib.load()
-        if not hasattr(lib, "fw_boost_create"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_boost_create: phrase boosting needs a current build")
+        if not hasattr(lib, self._create):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError(f"this libfwamd.so has no {self._create}: {self._feature} needs a current build")
         flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
-        b = np.asarray(boosts, dtype=np.float32).reshape(-1)
         self.n_vocab = int(n_vocab)
         self.n_phrases = len(phrases)
         self._handle = C.c_void_p()
-        _lib.check(lib.fw_boost_create(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
-                                       _lib.as_f32p(b) if b.size else None, C.byref(self._handle)))
+        _lib.check(getattr(lib, self._create)(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
+                                              *per_phrase, C.byref(self._handle)))
 
     def __len__(self):
         return self.n_phrases
@@ -178,21 +172,39 @@ class BoostList:
     def __del__(self):
         if getattr(self, "_handle", None):
             try:
-                _lib.load().fw_boost_free(self._handle)
+                getattr(_lib.load(), self._free)(self._handle)
             except Exception:
                 pass
             self._handle = None
 
+    @classmethod
+    def _handle_of(cls, value):
+        """the handle of a keyword's value: None, or a list of this class (TypeError)"""
+        if value is None:
+            return None
+        if not isinstance(value, cls):
+            raise TypeError(f"{cls._keyword} must be a {cls.__name__} (Whisper.{cls._keyword}_list) or None")
+        return value._handle
 
-def _boost_handle(boost):
-    if boost is None:
-        return None
-    if not isinstance(boost, BoostList):
-        raise TypeError("boost must be a BoostList (Whisper.boost_list) or None")
-    return boost._handle
+
+class BoostList(_PhraseList):
+    """A validated, compiled list of phrases to boost (fwamd.h: fw_boost_create): phrases[j] is a sequence of token ids,
+    boosts[j] the float added to the logit of the phrase's next token wherever the generated history ends with the tokens
+    in front of it (the first token: at every step).  Where several phrases ask for one id the largest boost counts, not the
+    sum; the decoding rules run after the boost and still win.  Host-only: needs no device.  Whisper.boost_list builds one
+    for the model's vocabulary; pass it as generate(boost=...) / score(boost=...)."""
+    _keyword, _feature, _create, _free = "boost", "phrase boosting", "fw_boost_create", "fw_boost_free"
+
+    def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]], boosts: Sequence[float]):
+        phrases = [list(p) for p in phrases]
+        boosts = list(boosts)
+        if len(phrases) != len(boosts):
+            raise ValueError(f"got {len(phrases)} phrases and {len(boosts)} boosts")
+        b = np.asarray(boosts, dtype=np.float32).reshape(-1)
+        self._compile(n_vocab, phrases, _lib.as_f32p(b) if b.size else None)
 
 
-class ConstraintList:
+class ConstraintList(_PhraseList):
     """A validated, compiled list of the phrases a decode may produce (fwamd.h: fw_constraint_create): phrases[j] is a
     sequence of token ids.  At every step the ids that continue no listed phrase after the row's generated text are set to
     -inf in front of the decoding rules, and <eot> is allowed only where a phrase is complete: a hypothesis with a finite
@@ -200,37 +212,55 @@ class ConstraintList:
     of others are valid; the list is a set (order and repeats do not matter).  Host-only: needs no device.
     Whisper.constraint_list builds one for the model's vocabulary; pass it as generate(constraint=...) /
     score(constraint=...).  An empty list constrains nothing."""
+    _keyword, _feature, _create, _free = "constraint", "constrained decoding", "fw_constraint_create", "fw_constraint_free"
 
     def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]]):
-        phrases = [list(p) for p in phrases]
-        lib = _lib.load()
-        if not hasattr(lib, "fw_constraint_create"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_constraint_create: constrained decoding needs a current build")
-        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
-        self.n_vocab = int(n_vocab)
-        self.n_phrases = len(phrases)
-        self._handle = C.c_void_p()
-        _lib.check(lib.fw_constraint_create(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
-                                            C.byref(self._handle)))
-
-    def __len__(self):
-        return self.n_phrases
-
-    def __del__(self):
-        if getattr(self, "_handle", None):
-            try:
-                _lib.load().fw_constraint_free(self._handle)
-            except Exception:
-                pass
-            self._handle = None
+        self._compile(n_vocab, [list(p) for p in phrases])
 
 
-def _constraint_handle(constraint):
-    if constraint is None:
-        return None
-    if not isinstance(constraint, ConstraintList):
-        raise TypeError("constraint must be a ConstraintList (Whisper.constraint_list) or None")
-    return constraint._handle
+def _require_symbols(lib, needs) -> None:
+    """needs: (used, symbol, what it serves) in the order the features were added.  A build loaded through FWAMD_LIB that
+    lacks the symbol of a feature the call uses cannot serve the call (RuntimeError)."""
+    for used, symbol, what in needs:
+        if used and not hasattr(lib, symbol):
+            raise RuntimeError(f"this libfwamd.so has no {symbol}: {what} a current build")
+
+
+def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, constraint_h):
+    """The engine entry point of a generate call and its argument list: the OLDEST symbol that can express the call, so a
+    build that lacks newer ones still serves every call it can.  head: (model, encoder output, prompts, offsets, B, options);
+    outs: (ids, lens, scores, no-speech probabilities); lp: the two log-prob arrays, alt: the four alternative arrays
+    (None where the call does not ask for them).  Every entry's argument order is stated here and nowhere else."""
+    trunc = top_k != 0 or top_p != 1.0   # (NaN included: the engine refuses it)
+    want_lp = lp[0] is not None
+    _require_symbols(lib, ((boost_h is not None, "fw_generate_boost", "phrase boosting needs"),
+                           (constraint_h is not None, "fw_generate_constrain", "constrained decoding needs"),
+                           (trunc, "fw_generate_trunc", "top_k / top_p need"),
+                           (n_alt, "fw_generate_alt", "per-token log-probabilities and alternatives need"),
+                           (want_lp, "fw_generate_lp", "per-token log-probabilities need")))
+    if constraint_h is not None:
+        return lib.fw_generate_constrain, (*head, top_k, top_p, n_alt, boost_h, constraint_h, *outs, *lp, *alt)
+    if trunc:
+        return lib.fw_generate_trunc, (*head, top_k, top_p, n_alt, boost_h, *outs, *lp, *alt)
+    if boost_h is not None:
+        return lib.fw_generate_boost, (*head, n_alt, boost_h, *outs, *lp, *alt)
+    if n_alt:
+        return lib.fw_generate_alt, (*head, n_alt, *outs, *lp, *alt)
+    if want_lp:
+        return lib.fw_generate_lp, (*head, *outs, *lp)
+    return lib.fw_generate, (*head, *outs)
+
+
+def _score_call(lib, head, outs, boost_h, constraint_h):
+    """as _generate_call, for score().  head: (model, encoder output, prompts, offsets, targets, offsets, B, H, rules)"""
+    _require_symbols(lib, ((True, "fw_score", "scoring needs"),
+                           (boost_h is not None, "fw_score_boost", "phrase boosting needs"),
+                           (constraint_h is not None, "fw_score_constrain", "constrained decoding needs")))
+    if constraint_h is not None:
+        return lib.fw_score_constrain, (*head, boost_h, constraint_h, *outs)
+    if boost_h is not None:
+        return lib.fw_score_boost, (*head, boost_h, *outs)
+    return lib.fw_score, (*head, *outs)
 
 
 class _Replica:
@@ -664,16 +694,8 @@ class Whisper:
         min_new_tokens > 0."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
-        boost_h = _boost_handle(boost)
-        if boost_h is not None and not hasattr(self._lib, "fw_generate_boost"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_generate_boost: phrase boosting needs a current build")
-        constraint_h = _constraint_handle(constraint)
-        if constraint_h is not None and not hasattr(self._lib, "fw_generate_constrain"):   # an older build (FWAMD_LIB)
-            raise RuntimeError("this libfwamd.so has no fw_generate_constrain: constrained decoding needs a current build")
+        boost_h, constraint_h = BoostList._handle_of(boost), ConstraintList._handle_of(constraint)
         top_k, top_p = int(top_k), float(top_p)
-        trunc = top_k != 0 or top_p != 1.0   # (NaN included: the engine refuses it)
-        if trunc and not hasattr(self._lib, "fw_generate_trunc"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_generate_trunc: top_k / top_p need a current build")
         n_alt = int(return_alternatives)
         if not 0 <= n_alt <= MAX_ALTERNATIVES:
             raise ValueError(f"return_alternatives must lie in [0, {MAX_ALTERNATIVES}] (got {return_alternatives})")
@@ -708,8 +730,6 @@ class Whisper:
             lens = np.zeros((B, nh), dtype=np.int32)
             scores = np.zeros((B, nh), dtype=np.float32)
             nsp = np.zeros((B,), dtype=np.float32)
-            args = (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o),
-                    _lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp))
             tlp = elp = aid = alp = eid = elps = None
             if return_token_logprobs:
                 tlp = np.zeros((B, nh, ml), dtype=np.float32)
@@ -721,28 +741,11 @@ class Whisper:
                 elps = np.zeros((B, nh, n_alt), dtype=np.float32)
             def f32(a): return _lib.as_f32p(a) if a is not None else None
             def i32(a): return _lib.as_i32p(a) if a is not None else None
-            if constraint_h is not None:
-                _lib.check(self._lib.fw_generate_constrain(*args[:6], top_k, top_p, n_alt, boost_h, constraint_h, *args[6:],
-                                                           f32(tlp), f32(elp), i32(aid), f32(alp), i32(eid), f32(elps)))
-            elif trunc:
-                _lib.check(self._lib.fw_generate_trunc(*args[:6], top_k, top_p, n_alt, boost_h, *args[6:], f32(tlp), f32(elp),
-                                                       i32(aid), f32(alp), i32(eid), f32(elps)))
-            elif boost_h is not None:
-                _lib.check(self._lib.fw_generate_boost(*args[:6], n_alt, boost_h, *args[6:], f32(tlp), f32(elp), i32(aid),
-                                                       f32(alp), i32(eid), f32(elps)))
-            elif return_token_logprobs:
-                need = "fw_generate_alt" if n_alt else "fw_generate_lp"
-                if not hasattr(self._lib, need):   # an older build loaded through FWAMD_LIB
-                    raise RuntimeError(f"this libfwamd.so has no {need}: per-token log-probabilities"
-                                       f"{' and alternatives' if n_alt else ''} need a current build")
-                if n_alt:
-                    _lib.check(self._lib.fw_generate_alt(*args[:6], n_alt, *args[6:], _lib.as_f32p(tlp), _lib.as_f32p(elp),
-                                                         _lib.as_i32p(aid), _lib.as_f32p(alp), _lib.as_i32p(eid),
-                                                         _lib.as_f32p(elps)))
-                else:
-                    _lib.check(self._lib.fw_generate_lp(*args, _lib.as_f32p(tlp), _lib.as_f32p(elp)))
-            else:
-                _lib.check(self._lib.fw_generate(*args))
+            entry, args = _generate_call(
+                self._lib, (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o)),
+                (_lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp)), (f32(tlp), f32(elp)),
+                (i32(aid), f32(alp), i32(eid), f32(elps)), n_alt, top_k, top_p, boost_h, constraint_h)
+            _lib.check(entry(*args))
             out = []
             for b in range(B):
                 seqs = [ids[b, h, :lens[b, h]].tolist() for h in range(nh)]
@@ -829,18 +832,11 @@ class Whisper:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
         if rule_kwargs and not rules:
             raise ValueError(f"{sorted(rule_kwargs)} need rules=True: without it the raw distribution is scored")
-        if not hasattr(self._lib, "fw_score"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_score: scoring needs a current build")
-        boost_h = _boost_handle(boost)
+        boost_h, constraint_h = BoostList._handle_of(boost), ConstraintList._handle_of(constraint)
         if boost_h is not None and not rules:
             raise ValueError("boost needs rules=True: the boost is the first step of the decoding rules")
-        if boost_h is not None and not hasattr(self._lib, "fw_score_boost"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_score_boost: phrase boosting needs a current build")
-        constraint_h = _constraint_handle(constraint)
         if constraint_h is not None and not rules:
             raise ValueError("constraint needs rules=True: the constraint is a step of the decoding rules")
-        if constraint_h is not None and not hasattr(self._lib, "fw_score_constrain"):   # an older build (FWAMD_LIB)
-            raise RuntimeError("this libfwamd.so has no fw_score_constrain: constrained decoding needs a current build")
         enc = self._as_encoded(features)
         if len(prompts) != enc._shape[0] or len(targets) != enc._shape[0]:
             raise ValueError(f"got {len(prompts)} prompts and {len(targets)} targets for a batch of {enc._shape[0]}")
@@ -877,12 +873,8 @@ class Whisper:
             head = (enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs), _lib.as_i32p(tflat),
                     _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None)
             outs = (_lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp))
-            if constraint_h is not None:
-                _lib.check(self._lib.fw_score_constrain(*head, boost_h, constraint_h, *outs))
-            elif boost_h is not None:
-                _lib.check(self._lib.fw_score_boost(*head, boost_h, *outs))
-            else:
-                _lib.check(self._lib.fw_score(*head, *outs))
+            entry, args = _score_call(self._lib, head, outs, boost_h, constraint_h)
+            _lib.check(entry(*args))
             out = []
             for b in range(B):
                 res = WhisperScoringResult([], [], [], [], [])

@@ -51,26 +51,11 @@ static __host__ __device__ __forceinline__ bool boost_of_group(const BoostView& 
 #define BOOST_THREADS 256
 template <bool SCORE>
 __global__ __launch_bounds__(BOOST_THREADS) void dec_boost_kernel(float* __restrict__ logits, const int* __restrict__ boost_tab,
-                                                                  int V, int K, int R, int NT, const int* __restrict__ hist2,
-                                                                  const int* __restrict__ d_step, const int* __restrict__ done,
-                                                                  const fwd::ScoreRow* __restrict__ tab, int tab_stride,
-                                                                  int pos0, int nb, const int* __restrict__ hist_pool) {
+                                                                  int V, int K, int R, int NT, fwd::RowSource src) {
   const int r = blockIdx.x;
   const int* hist;
   int n;
-  if (SCORE) {
-    const int sq = r / nb;
-    const fwd::ScoreRow row = tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
-    if (row.target < 0) return;   // (uniform)
-    n = row.n;
-    hist = hist_pool + row.hist_off;
-  } else {
-    if (done[r / K]) return;
-    const int step = *d_step;
-    n = step;   // tokens generated so far on this row
-    hist = hist2 + ((size_t)(step & 1) * R + r) * NT;
-  }
-  n = n < NT ? n : NT;
+  if (!fwd::row_history<SCORE>(src, r, K, R, NT, hist, n)) return;   // (uniform)
   const fwd::BoostView tv = fwd::boost_view(boost_tab);
   float* lg = logits + (size_t)r * V;
   for (int g = threadIdx.x; g < tv.G; g += BOOST_THREADS) {
@@ -86,15 +71,15 @@ namespace fwd {
 void launch_boost_step(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const int* hist2,
                        const int* d_step, const int* done) {
   if (!boost_tab || gp.R <= 0) return;
-  dec_boost_kernel<false><<<gp.R, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, gp.K, gp.R, gp.n_text_ctx, hist2, d_step,
-                                                         done, nullptr, 0, 0, 1, nullptr);
+  dec_boost_kernel<false><<<gp.R, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, gp.K, gp.R, gp.n_text_ctx,
+                                                         {hist2, d_step, done, nullptr, 0, 0, 1});
 }
 
 void launch_boost_score(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const ScoreRow* tab,
                         int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
   if (!boost_tab || rows <= 0) return;
-  dec_boost_kernel<true><<<rows, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, 1, rows, gp.n_text_ctx, nullptr, nullptr,
-                                                        nullptr, tab, tab_stride, pos0, nb, hist_pool);
+  dec_boost_kernel<true><<<rows, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, 1, rows, gp.n_text_ctx,
+                                                        {hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb});
 }
 
 void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets) {
@@ -109,6 +94,25 @@ void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const
   }
 }
 
+int32_t phrase_list_check(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases, int max_phrases,
+                          int max_len, int max_tokens) {
+  FW_CHECK_ARG(n_vocab >= 1, "n_vocab %d must be positive", n_vocab);
+  FW_CHECK_ARG(n_phrases >= 0 && n_phrases <= max_phrases, "%d phrases not in [0, %d]", n_phrases, max_phrases);
+  if (n_phrases == 0) return FW_OK;
+  FW_CHECK_ARG(tokens && offsets, "null argument");
+  FW_CHECK_ARG(offsets[0] == 0, "offsets must start at 0");
+  for (int j = 0; j < n_phrases; ++j) {
+    // (compared as 64-bit values: offsets that decrease or jump cannot wrap the length)
+    const int64_t len = (int64_t)offsets[j + 1] - offsets[j];
+    FW_CHECK_ARG(len >= 1 && len <= max_len, "phrase %d has %lld tokens, not 1 .. %d", j, (long long)len, max_len);
+    FW_CHECK_ARG(offsets[j + 1] <= max_tokens, "more than %d tokens in all", max_tokens);
+  }
+  for (int j = 0; j < n_phrases; ++j)
+    for (int i = offsets[j]; i < offsets[j + 1]; ++i)
+      FW_CHECK_ARG(tokens[i] >= 0 && tokens[i] < n_vocab, "phrase %d: token %d outside [0, %d)", j, tokens[i], n_vocab);
+  return FW_OK;
+}
+
 }  // namespace fwd
 
 extern "C" {
@@ -117,23 +121,12 @@ int32_t fw_boost_create(int32_t n_vocab, const int32_t* tokens, const int32_t* o
                         const float* boosts, fw_boost** out) {
   FW_CHECK_ARG(out, "null argument");
   *out = nullptr;
-  FW_CHECK_ARG(n_vocab >= 1, "n_vocab %d must be positive", n_vocab);
-  FW_CHECK_ARG(n_phrases >= 0 && n_phrases <= FW_BOOST_MAX_PHRASES, "%d phrases not in [0, %d]", n_phrases, FW_BOOST_MAX_PHRASES);
-  FW_CHECK_ARG(n_phrases == 0 || (tokens && offsets && boosts), "null argument");
-  int T = 0;
-  if (n_phrases > 0) {
-    FW_CHECK_ARG(offsets[0] == 0, "offsets must start at 0");
-    for (int j = 0; j < n_phrases; ++j) {
-      // (compared as 64-bit values: offsets that decrease or jump cannot wrap the length)
-      const int64_t len = (int64_t)offsets[j + 1] - offsets[j];
-      FW_CHECK_ARG(len >= 1 && len <= FW_BOOST_MAX_LEN, "phrase %d has %lld tokens, not 1 .. %d", j, (long long)len, FW_BOOST_MAX_LEN);
-      FW_CHECK_ARG(offsets[j + 1] <= FW_BOOST_MAX_TOKENS, "more than %d tokens in all", FW_BOOST_MAX_TOKENS);
-      FW_CHECK_ARG(std::isfinite(boosts[j]), "the boost of phrase %d is not finite", j);
-    }
-    T = offsets[n_phrases];
-    for (int i = 0; i < T; ++i)
-      FW_CHECK_ARG(tokens[i] >= 0 && tokens[i] < n_vocab, "token %d outside [0, %d)", tokens[i], n_vocab);
-  }
+  if (int rc = fwd::phrase_list_check(n_vocab, tokens, offsets, n_phrases, FW_BOOST_MAX_PHRASES, FW_BOOST_MAX_LEN,
+                                      FW_BOOST_MAX_TOKENS))
+    return rc;
+  FW_CHECK_ARG(n_phrases == 0 || boosts, "null argument");
+  for (int j = 0; j < n_phrases; ++j) FW_CHECK_ARG(std::isfinite(boosts[j]), "the boost of phrase %d is not finite", j);
+  const int T = n_phrases > 0 ? offsets[n_phrases] : 0;
   // entries (j, k) ordered by (target id, j, k): equal arguments give equal bytes
   struct Ent { int id, start, k, bits; };
   std::vector<Ent> ents;

@@ -56,27 +56,14 @@ static __host__ __device__ __forceinline__ unsigned constrain_word_init(int w, i
 template <bool SCORE>
 __global__ __launch_bounds__(CONSTRAIN_THREADS) void dec_constrain_kernel(
     float* __restrict__ logits, const int* __restrict__ ctab, int V, int K, int R, int NT, int eot, int ts_begin, int with_ts,
-    const int* __restrict__ hist2, const int* __restrict__ d_step, const int* __restrict__ done,
-    const fwd::ScoreRow* __restrict__ tab, int tab_stride, int pos0, int nb, const int* __restrict__ hist_pool) {
+    fwd::RowSource src) {
   __shared__ unsigned keep[CONSTRAIN_MASK_WORDS];
   __shared__ int text[FW_CONSTRAIN_MAX_LEN + 1];
   __shared__ int wave_n[CONSTRAIN_WAVES];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int* hist;
   int n;
-  if (SCORE) {
-    const int sq = r / nb;
-    const fwd::ScoreRow row = tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
-    if (row.target < 0) return;   // (uniform)
-    n = row.n;
-    hist = hist_pool + row.hist_off;
-  } else {
-    if (done[r / K]) return;
-    const int step = *d_step;
-    n = step;   // tokens generated so far on this row
-    hist = hist2 + ((size_t)(step & 1) * R + r) * NT;
-  }
-  n = n < NT ? n : NT;
+  if (!fwd::row_history<SCORE>(src, r, K, R, NT, hist, n)) return;   // (uniform, in front of the first barrier)
 
   // 1. the text ids of the history, in order
   int m = 0;
@@ -150,16 +137,16 @@ void launch_constrain_step(hipStream_t st, const GenDev& gp, float* logits, cons
                            const int* d_step, const int* done) {
   if (!ctab || gp.R <= 0 || !constrain_geometry_ok(gp.V, gp.eot, gp.ts_begin)) return;
   dec_constrain_kernel<false><<<gp.R, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot,
-                                                                 gp.ts_begin, gp.with_ts, hist2, d_step, done, nullptr, 0, 0,
-                                                                 1, nullptr);
+                                                                 gp.ts_begin, gp.with_ts,
+                                                                 {hist2, d_step, done, nullptr, 0, 0, 1});
 }
 
 void launch_constrain_score(hipStream_t st, const GenDev& gp, float* logits, const int* ctab, const ScoreRow* tab,
                             int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
   if (!ctab || rows <= 0 || !constrain_geometry_ok(gp.V, gp.eot, gp.ts_begin)) return;
   dec_constrain_kernel<true><<<rows, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, 1, rows, gp.n_text_ctx, gp.eot,
-                                                                gp.ts_begin, gp.with_ts, nullptr, nullptr, nullptr, tab,
-                                                                tab_stride, pos0, nb, hist_pool);
+                                                                gp.ts_begin, gp.with_ts,
+                                                                {hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb});
 }
 
 void constrain_rows_host(const int* ctab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts, const int* hist,
@@ -194,23 +181,9 @@ int32_t fw_constraint_create(int32_t n_vocab, const int32_t* tokens, const int32
                              fw_constraint** out) {
   FW_CHECK_ARG(out, "null argument");
   *out = nullptr;
-  FW_CHECK_ARG(n_vocab >= 1, "n_vocab %d must be positive", n_vocab);
-  FW_CHECK_ARG(n_phrases >= 0 && n_phrases <= FW_CONSTRAIN_MAX_PHRASES, "%d phrases not in [0, %d]", n_phrases,
-               FW_CONSTRAIN_MAX_PHRASES);
-  FW_CHECK_ARG(n_phrases == 0 || (tokens && offsets), "null argument");
-  if (n_phrases > 0) {
-    FW_CHECK_ARG(offsets[0] == 0, "offsets must start at 0");
-    for (int j = 0; j < n_phrases; ++j) {
-      // (compared as 64-bit values: offsets that decrease or jump cannot wrap the length)
-      const int64_t len = (int64_t)offsets[j + 1] - offsets[j];
-      FW_CHECK_ARG(len >= 1 && len <= FW_CONSTRAIN_MAX_LEN, "phrase %d has %lld tokens, not 1 .. %d", j, (long long)len,
-                   FW_CONSTRAIN_MAX_LEN);
-      FW_CHECK_ARG(offsets[j + 1] <= FW_CONSTRAIN_MAX_TOKENS, "more than %d tokens in all", FW_CONSTRAIN_MAX_TOKENS);
-    }
-    for (int j = 0; j < n_phrases; ++j)
-      for (int i = offsets[j]; i < offsets[j + 1]; ++i)
-        FW_CHECK_ARG(tokens[i] >= 0 && tokens[i] < n_vocab, "phrase %d: token %d outside [0, %d)", j, tokens[i], n_vocab);
-  }
+  if (int rc = fwd::phrase_list_check(n_vocab, tokens, offsets, n_phrases, FW_CONSTRAIN_MAX_PHRASES, FW_CONSTRAIN_MAX_LEN,
+                                      FW_CONSTRAIN_MAX_TOKENS))
+    return rc;
   // The list is a SET of phrases: sorted by their ids, duplicates dropped — lists that hold the same phrases give the same
   // bytes in whatever order and however often they name them.  `first` keeps, per compiled phrase, the caller's index of
   // its first occurrence (for messages; not part of the table).

@@ -225,6 +225,39 @@ struct ScoreRow {
   int out;                 // index into out_lp / out_best_id / out_best_lp
 };
 static_assert(sizeof(ScoreRow) == 16, "one 16-byte load per row");
+// row r of a score-form launch: position pos0 + r % nb of sequence r / nb (dec_score_kernel and the score forms of the two
+// pre-pass kernels address their rows through this)
+static __device__ __forceinline__ ScoreRow score_row(const ScoreRow* __restrict__ tab, int tab_stride, int pos0, int nb, int r) {
+  const int sq = r / nb;
+  return tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
+}
+// Where a pre-pass kernel (dec_boost_kernel, dec_constrain_kernel) finds its rows' histories.  Decode-step form: hist is
+// hist2 [2][R][NT], d_step and done are the run's.  Score form: hist is the history pool, tab .. nb address the ScoreRows.
+struct RowSource {
+  const int* hist;
+  const int* d_step;
+  const int* done;
+  const ScoreRow* tab;
+  int tab_stride, pos0, nb;
+};
+// Row r's history hist[0 .. n), n clamped to NT.  False: the row is skipped (its chunk is done / it has no target); the
+// answer is the same for every thread of the workgroup, and the caller returns on it before any barrier.
+template <bool SCORE>
+static __device__ __forceinline__ bool row_history(const RowSource& s, int r, int K, int R, int NT, const int*& hist, int& n) {
+  if (SCORE) {
+    const ScoreRow row = score_row(s.tab, s.tab_stride, s.pos0, s.nb, r);
+    if (row.target < 0) return false;
+    n = row.n;
+    hist = s.hist + row.hist_off;
+  } else {
+    if (s.done[r / K]) return false;
+    const int step = *s.d_step;
+    n = step;   // tokens generated so far on this row
+    hist = s.hist + ((size_t)(step & 1) * R + r) * NT;
+  }
+  n = n < NT ? n : NT;
+  return true;
+}
 // dec_score_kernel over `rows` logits rows in ONE launch: row r is position pos0 + r % nb of sequence r / nb and reads
 // tab[(r / nb) * tab_stride + pos0 + r % nb].  rules: the decoding rules of gp (with_ts, suppress_blank, mits, ngram,
 // rep_pen, the token ids) and sup_bits first, on a greedy row whose history is the ScoreRow's; otherwise the raw
@@ -305,16 +338,29 @@ void constrain_rows_host(const int* constrain_tab, float* logits, int rows, int 
 
 }  // namespace fwd
 
-// what fw_boost_create returns: the list's vocabulary size and its compiled table (above)
-struct fw_boost {
+// What fw_boost and fw_constraint share: the list's vocabulary size and its compiled table (above).  An empty list (first
+// header word 0) is no list, and a decode run walks ONE table per kind: the rules the decode path asks of either kind
+// are stated once here.
+struct fw_phrase_table {
   int32_t n_vocab;
   std::vector<int32_t> table;
 };
+namespace fwd {
+static inline bool phrase_list_live(const fw_phrase_table* t) { return t && t->table[0] > 0; }
+// both none, or one table (the same list, or lists that compiled to the same bytes)
+static inline bool phrase_table_same(const fw_phrase_table* a, const fw_phrase_table* b) {
+  return a == b || (a && b && a->table == b->table);
+}
+// what both *_create functions ask of (n_vocab, tokens, offsets, n_phrases), against the kind's three limits
+int32_t phrase_list_check(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases, int max_phrases,
+                          int max_len, int max_tokens);
+}  // namespace fwd
 
-// what fw_constraint_create returns: the list's vocabulary size, its compiled table (above) and, per compiled phrase, the
-// index the caller gave its first occurrence (for messages only: never compared)
-struct fw_constraint {
-  int32_t n_vocab;
-  std::vector<int32_t> table;
+// what fw_boost_create returns
+struct fw_boost : fw_phrase_table {};
+
+// what fw_constraint_create returns: with, per compiled phrase, the index the caller gave its first occurrence (for
+// messages only: never compared)
+struct fw_constraint : fw_phrase_table {
   std::vector<int32_t> first;
 };

@@ -631,8 +631,7 @@ __global__ __launch_bounds__(LP_THREADS) void dec_score_kernel(fwd::GenDev gp, c
   __shared__ int btok_s[LP_WAVES];
   __shared__ unsigned pen_bits[2 * LP_SUP_WORDS], ng_bits[2 * LP_SUP_WORDS];
   const int r = blockIdx.x;
-  const int sq = r / nb;
-  const fwd::ScoreRow row = tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
+  const fwd::ScoreRow row = fwd::score_row(tab, tab_stride, pos0, nb, r);
   if (row.target < 0) return;   // (uniform)
   const int tid = threadIdx.x;
   const int lane = tid & 63;

@@ -733,6 +733,16 @@ struct GenRequest {
   bool done = false;
 };
 
+// The run's phrase table of one kind into its lane buffer.  The buffer is allocated once, at the kind's largest table
+// (max_words): the pointer a cached step graph holds never changes.
+static int32_t phrase_table_to_lane(GrowBuf<int>& dst, const fw_phrase_table& t, int max_words, const char* what,
+                                    hipStream_t st) {
+  FW_CHECK_ARG(t.table.size() <= (size_t)max_words, "%s table of %zu words", what, t.table.size());
+  if (int rc = dst.ensure(max_words)) return rc;
+  FW_HIP(hipMemcpyAsync(dst.p, t.table.data(), t.table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  return FW_OK;
+}
+
 // calls that may share a decode run: same scalar options (max_length among them), same suppress list, same timestamp
 // mode.  SAMPLING calls share runs among themselves only (their hypotheses are beam-1 rows of their own, num_hypotheses
 // decode chunks per encoder chunk: a beam or greedy call has one); sampling_temperature and seed need NOT agree, every
@@ -744,10 +754,7 @@ struct GenRequest {
 // CONSTRAINT LISTS (fw_generate_constrain) likewise.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
-  if ((a.boost != nullptr) != (b.boost != nullptr)) return false;
-  if (a.boost && a.boost != b.boost && a.boost->table != b.boost->table) return false;
-  if ((a.constraint != nullptr) != (b.constraint != nullptr)) return false;
-  if (a.constraint && a.constraint != b.constraint && a.constraint->table != b.constraint->table) return false;
+  if (!fwd::phrase_table_same(a.boost, b.boost) || !fwd::phrase_table_same(a.constraint, b.constraint)) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -962,18 +969,11 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   FW_HIP(hipMemsetAsync(g->no_speech, 0, Rr * sizeof(float), st));
   const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
-  if (pl.gp.boost) {   // the run's boost table, into the lane's buffer (allocated once, at its maximum size)
-    const std::vector<int32_t>& tab = reqs[0]->boost->table;
-    FW_CHECK_ARG(tab.size() <= (size_t)fwd::BOOST_TABLE_MAX_WORDS, "boost table of %zu words", tab.size());
-    if (int rc = g->boost_tab.ensure(fwd::BOOST_TABLE_MAX_WORDS)) return rc;
-    FW_HIP(hipMemcpyAsync(g->boost_tab.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
-  }
-  if (pl.gp.constrain) {   // the run's constraint table, likewise
-    const std::vector<int32_t>& tab = reqs[0]->constraint->table;
-    FW_CHECK_ARG(tab.size() <= (size_t)fwd::CONSTRAIN_TABLE_MAX_WORDS, "constraint table of %zu words", tab.size());
-    if (int rc = g->constrain_tab.ensure(fwd::CONSTRAIN_TABLE_MAX_WORDS)) return rc;
-    FW_HIP(hipMemcpyAsync(g->constrain_tab.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
-  }
+  if (pl.gp.boost)
+    if (int rc = phrase_table_to_lane(g->boost_tab, *reqs[0]->boost, fwd::BOOST_TABLE_MAX_WORDS, "boost", st)) return rc;
+  if (pl.gp.constrain)
+    if (int rc = phrase_table_to_lane(g->constrain_tab, *reqs[0]->constraint, fwd::CONSTRAIN_TABLE_MAX_WORDS, "constraint", st))
+      return rc;
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
   ptok.assign((size_t)Pmax * Bx, 0);
@@ -1434,7 +1434,7 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
 static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, const fw_gen_opts* o, bool check_min_new) {
   FW_CHECK_ARG(ct->n_vocab == c.n_vocab, "the constraint list was built for a vocabulary of %d ids, the model has %d",
                ct->n_vocab, c.n_vocab);
-  if (ct->table[0] == 0) return FW_OK;   // (an empty list: no constraint, nothing to refuse)
+  if (!fwd::phrase_list_live(ct)) return FW_OK;   // (an empty list: no constraint, nothing to refuse)
   FW_CHECK_ARG(c.tok_eot >= 0 && c.tok_eot < c.tok_timestamp_begin && c.tok_timestamp_begin <= c.n_vocab &&
                    c.n_vocab <= LP_SUP_WORDS * 64,
                "this model's vocabulary layout (<eot> %d, first timestamp %d, %d ids) is not one the constraint kernel takes",
@@ -1536,8 +1536,8 @@ int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_
   req.out_end_alt_ids = out_end_alt_ids; req.out_end_alt_logprobs = out_end_alt_logprobs;
   req.sampling = sampling;
   req.top_k = top_k; req.top_p = top_p;
-  req.boost = (boost && boost->table[0] > 0) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
-  req.constraint = (constraint && constraint->table[0] > 0) ? constraint : nullptr;   // (likewise)
+  req.boost = fwd::phrase_list_live(boost) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
+  req.constraint = fwd::phrase_list_live(constraint) ? constraint : nullptr;   // (likewise)
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -1924,11 +1924,10 @@ extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, cons
   FW_CHECK_ARG(B >= 1 && B <= m->max_batch, "batch %d exceeds max_batch %d", B, m->max_batch);
   FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
                boost ? boost->n_vocab : 0, c.n_vocab);
-  if (boost && boost->table[0] == 0) boost = nullptr;   // (an empty list does nothing)
-  if (constraint) {
+  if (constraint)
     if (int crc = constraint_check(constraint, c, rules, false)) return crc;
-    if (constraint->table[0] == 0) constraint = nullptr;   // (likewise)
-  }
+  if (!fwd::phrase_list_live(boost)) boost = nullptr;   // (an empty list does nothing)
+  if (!fwd::phrase_list_live(constraint)) constraint = nullptr;
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
   FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
   const int Bx = B * H;
@@ -2006,16 +2005,12 @@ extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, cons
       (rc = tmp.alloc(&lp_dev, n_out)))
     return rc;
   if (out_best_ids && ((rc = tmp.alloc(&bid_dev, n_out)) || (rc = tmp.alloc(&blp_dev, n_out)))) return rc;
-  int* boost_dev = nullptr;
-  if (boost) {
-    if ((rc = tmp.alloc(&boost_dev, boost->table.size()))) return rc;
-    FW_HIP_AS(setup_fail, hipMemcpyAsync(boost_dev, boost->table.data(), boost->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  int* constrain_dev = nullptr;
-  if (constraint) {
-    const std::vector<int32_t>& ctab = constraint->table;
-    if ((rc = tmp.alloc(&constrain_dev, ctab.size()))) return rc;
-    FW_HIP_AS(setup_fail, hipMemcpyAsync(constrain_dev, ctab.data(), ctab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  int *boost_dev = nullptr, *constrain_dev = nullptr;
+  const std::pair<const fw_phrase_table*, int**> lists[] = {{boost, &boost_dev}, {constraint, &constrain_dev}};
+  for (const auto& [list, dev] : lists) {   // (null: no list of that kind, its pre-pass is not launched)
+    if (!list) continue;
+    if ((rc = tmp.alloc(dev, list->table.size()))) return rc;
+    FW_HIP_AS(setup_fail, hipMemcpyAsync(*dev, list->table.data(), list->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
   FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));

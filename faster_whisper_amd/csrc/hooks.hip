@@ -1151,18 +1151,16 @@ static int32_t boost_hist_check(int32_t rows, const int32_t* hist, const int32_t
   return FW_OK;
 }
 
-// ONE launch of dec_boost_kernel in either row form (include/fwamd_test.h); everything is checked before anything is
-// allocated or launched.
-int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
-                           int32_t K, const int32_t* done, int32_t form, const fw_boost* boost) {
-  FW_CHECK_ARG(fm && logits && hist_offsets && boost && rows >= 1, "bad arguments");
-  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
-  Model* m = &fm->impl;
-  const fw_config& c = m->cfg;
-  FW_CHECK_ARG(boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
-               boost->n_vocab, c.n_vocab);
+// What fw_test_boost_rows and fw_test_constrain_rows do alike: ONE launch of a pre-pass kernel in either row form
+// (include/fwamd_test.h) over `rows` rows of gp.V logits.  gp holds what the kernel reads beyond the rows (the callers have
+// checked it and the list); B, K and R are set here.  Everything is checked before anything is allocated or launched.
+using PrepassStep = void (*)(hipStream_t, const GenDev&, float*, const int*, const int*, const int*, const int*);
+using PrepassScore = void (*)(hipStream_t, const GenDev&, float*, const int*, const fwd::ScoreRow*, int, int, int, int, const int*);
+static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                            int32_t K, const int32_t* done, int32_t form, const std::vector<int32_t>& table,
+                            PrepassStep launch_step, PrepassScore launch_score) {
   FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
-  if (int rc = boost_hist_check(rows, hist, hist_offsets, c.n_text_ctx, c.n_vocab)) return rc;
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, gp.n_text_ctx, gp.V)) return rc;
   const int n0 = hist_offsets[1];
   if (form == 0)
     for (int r = 0; r < rows; ++r)
@@ -1171,18 +1169,16 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
   if (done)
     for (int b = 0; b < n_done; ++b) FW_CHECK_ARG(done[b] == 0 || done[b] == 1, "done[%d] = %d is not 0 / 1", b, done[b]);
   FW_HIP(hipSetDevice(m->device));
-  GenDev gp;
-  memset(&gp, 0, sizeof(gp));
-  gp.B = rows / K; gp.K = K; gp.R = rows; gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.boost = 1;
+  gp.B = rows / K; gp.K = K; gp.R = rows;
   HookBufs db;
   float* d_lg;
   int* d_tab;
   int rc;
-  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * c.n_vocab)) ||
-      (rc = db.upload(&d_tab, (const int*)boost->table.data(), boost->table.size())))
+  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * gp.V)) ||
+      (rc = db.upload(&d_tab, (const int*)table.data(), table.size())))
     return rc;
   if (form == 0) {
-    const size_t NT = (size_t)c.n_text_ctx;
+    const size_t NT = (size_t)gp.n_text_ctx;
     std::vector<int> h2(2 * (size_t)rows * NT, 0), dn((size_t)rows, 0);
     for (int r = 0; r < rows; ++r)
       for (int i = 0; i < n0; ++i) h2[((size_t)(n0 & 1) * rows + r) * NT + i] = hist[hist_offsets[r] + i];
@@ -1191,7 +1187,7 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
     if ((rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n0, 1)) ||
         (rc = db.upload(&d_done, dn.data(), dn.size())))
       return rc;
-    fwd::launch_boost_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
+    launch_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
   } else {
     std::vector<fwd::ScoreRow> tab((size_t)rows);
     for (int r = 0; r < rows; ++r)
@@ -1203,11 +1199,25 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
     if ((rc = db.upload(&d_rows, tab.data(), tab.size())) ||
         (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
       return rc;
-    fwd::launch_boost_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
+    launch_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
   }
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
-  return download(logits, d_lg, (size_t)rows * c.n_vocab);
+  return download(logits, d_lg, (size_t)rows * gp.V);
+}
+
+int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                           int32_t K, const int32_t* done, int32_t form, const fw_boost* boost) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  const fw_config& c = fm->impl.cfg;
+  FW_CHECK_ARG(boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
+               boost->n_vocab, c.n_vocab);
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.boost = 1;
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, boost->table, fwd::launch_boost_step,
+                      fwd::launch_boost_score);
 }
 
 // the same table walked on the host: no device, no model
@@ -1230,64 +1240,19 @@ static int32_t constrain_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t to
   return FW_OK;
 }
 
-// ONE launch of dec_constrain_kernel in either row form (include/fwamd_test.h); everything is checked before anything is
-// allocated or launched.  The model gives the device and the text context (the stride of the step form's histories) only.
+// The model gives the device and the text context (the stride of the step form's histories) only.
 int32_t fw_test_constrain_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
                                int32_t tok_ts_begin, int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
                                int32_t K, const int32_t* done, int32_t form, const fw_constraint* constraint) {
   FW_CHECK_ARG(fm && logits && hist_offsets && constraint && rows >= 1, "bad arguments");
   FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
-  Model* m = &fm->impl;
-  const fw_config& c = m->cfg;
   if (int rc = constrain_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint)) return rc;
-  FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
-  if (int rc = boost_hist_check(rows, hist, hist_offsets, c.n_text_ctx, n_vocab)) return rc;
-  const int n0 = hist_offsets[1];
-  if (form == 0)
-    for (int r = 0; r < rows; ++r)
-      FW_CHECK_ARG(hist_offsets[r + 1] - hist_offsets[r] == n0, "form 0 takes one n for all rows (row %d)", r);
-  const int n_done = form == 0 ? rows / K : rows;
-  if (done)
-    for (int b = 0; b < n_done; ++b) FW_CHECK_ARG(done[b] == 0 || done[b] == 1, "done[%d] = %d is not 0 / 1", b, done[b]);
-  FW_HIP(hipSetDevice(m->device));
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
-  gp.B = rows / K; gp.K = K; gp.R = rows; gp.V = n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.constrain = 1;
+  gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1; gp.constrain = 1;
   gp.eot = tok_eot; gp.ts_begin = tok_ts_begin; gp.with_ts = with_timestamps;
-  HookBufs db;
-  float* d_lg;
-  int* d_tab;
-  int rc;
-  if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * n_vocab)) ||
-      (rc = db.upload(&d_tab, (const int*)constraint->table.data(), constraint->table.size())))
-    return rc;
-  if (form == 0) {
-    const size_t NT = (size_t)c.n_text_ctx;
-    std::vector<int> h2(2 * (size_t)rows * NT, 0), dn((size_t)rows, 0);
-    for (int r = 0; r < rows; ++r)
-      for (int i = 0; i < n0; ++i) h2[((size_t)(n0 & 1) * rows + r) * NT + i] = hist[hist_offsets[r] + i];
-    if (done) std::copy(done, done + n_done, dn.begin());
-    int *d_hist, *d_step, *d_done;
-    if ((rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n0, 1)) ||
-        (rc = db.upload(&d_done, dn.data(), dn.size())))
-      return rc;
-    fwd::launch_constrain_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
-  } else {
-    std::vector<fwd::ScoreRow> tab((size_t)rows);
-    for (int r = 0; r < rows; ++r)
-      tab[r] = {(done && done[r]) ? -1 : 0, hist_offsets[r + 1] - hist_offsets[r], hist_offsets[r], r};
-    const size_t n_hist = (size_t)hist_offsets[rows];
-    const int zero = 0;
-    fwd::ScoreRow* d_rows;
-    int* d_hist;
-    if ((rc = db.upload(&d_rows, tab.data(), tab.size())) ||
-        (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
-      return rc;
-    fwd::launch_constrain_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
-  }
-  FW_HIP(hipGetLastError());
-  FW_HIP(hipDeviceSynchronize());
-  return download(logits, d_lg, (size_t)rows * n_vocab);
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, constraint->table,
+                      fwd::launch_constrain_step, fwd::launch_constrain_score);
 }
 
 // the same table walked on the host: no device, no model

@@ -103,40 +103,6 @@ def _slice_token_values(subs: List[dict], logprobs: List[float], alternatives: O
         _slice_token_logprobs(subs, alternatives, "token_alternatives")
 
 
-def _value_keywords(token_logprobs: bool, token_alternatives: int, logprobs_key: str = "token_logprobs",
-                    alternatives_key: str = "token_alternatives") -> dict:
-    """the keywords a call passes down for its per-token values — only those it was asked for, so that a layer below that
-    does not know them (a scripted backend, CTranslate2 behind the shim) never sees them otherwise"""
-    if token_alternatives:
-        return {alternatives_key: int(token_alternatives)}
-    return {logprobs_key: True} if token_logprobs else {}
-
-
-class _BuiltBoost:
-    """a boost list that is built already, in the place of transcribe()'s boost_phrases: how transcribe_many hands ONE list
-    to the transcribe() of every recording"""
-
-    def __init__(self, boost):
-        self.boost = boost
-
-
-def _boost_keyword(boost) -> dict:
-    """the keyword a call passes down for its boost list — only when it has one (as _value_keywords)"""
-    return {} if boost is None else {"boost": boost}
-
-
-class _BuiltConstraint:
-    """a constraint list that is built already, in the place of transcribe()'s allowed_phrases (as _BuiltBoost)"""
-
-    def __init__(self, constraint):
-        self.constraint = constraint
-
-
-def _constraint_keyword(constraint) -> dict:
-    """the keyword a call passes down for its constraint list — only when it has one (as _boost_keyword)"""
-    return {} if constraint is None else {"constraint": constraint}
-
-
 def _check_trunc_arguments(sampling_top_k, sampling_top_p) -> None:
     """sampling_top_k: an integer >= 0; sampling_top_p: a number in (0, 1] (ValueError) — what fw_generate_trunc accepts,
     checked before anything is decoded"""
@@ -145,17 +111,6 @@ def _check_trunc_arguments(sampling_top_k, sampling_top_p) -> None:
     if isinstance(sampling_top_p, bool) or not isinstance(sampling_top_p, (int, float, np.integer, np.floating)) \
             or not 0 < sampling_top_p <= 1:
         raise ValueError(f"sampling_top_p must lie in (0, 1] (got {sampling_top_p!r})")
-
-
-def _trunc_keywords(sampling_top_k, sampling_top_p, top_k_key: str = "sampling_top_k",
-                    top_p_key: str = "sampling_top_p") -> dict:
-    """the keywords a call passes down for its sampling limits — only those that limit something (as _value_keywords)"""
-    out = {}
-    if sampling_top_k:
-        out[top_k_key] = int(sampling_top_k)
-    if sampling_top_p != 1:
-        out[top_p_key] = float(sampling_top_p)
-    return out
 
 
 @dataclass
@@ -211,7 +166,7 @@ def _transcription_options(args, tokenizer: "Tokenizer", **derived) -> Transcrip
 
 def _check_boost_arguments(boost_phrases, phrase_boost) -> None:
     """boost_phrases: None, or a sequence of strings; with phrases phrase_boost must be given (ValueError)"""
-    if boost_phrases is None or isinstance(boost_phrases, _BuiltBoost):
+    if boost_phrases is None:
         return
     if isinstance(boost_phrases, (str, bytes)) or not all(isinstance(p, str) for p in boost_phrases):
         raise ValueError("boost_phrases must be a sequence of strings, one per phrase")
@@ -221,10 +176,60 @@ def _check_boost_arguments(boost_phrases, phrase_boost) -> None:
 
 def _check_constraint_arguments(allowed_phrases) -> None:
     """allowed_phrases: None, or a sequence of strings (ValueError)"""
-    if allowed_phrases is None or isinstance(allowed_phrases, _BuiltConstraint):
+    if allowed_phrases is None:
         return
     if isinstance(allowed_phrases, (str, bytes)) or not all(isinstance(p, str) for p in allowed_phrases):
         raise ValueError("allowed_phrases must be a sequence of strings, one per phrase")
+
+
+@dataclass(frozen=True)
+class DecodeExtras:
+    """What a transcription call asks of its decodes beyond the reference's options, carried as ONE value from the entry
+    point to model.generate.  boost / constraint: the call's built lists (boost_list_for / constraint_list_for), the same
+    objects for every window, attempt, batch and recording."""
+    token_logprobs: bool = False
+    token_alternatives: int = 0
+    boost: object = None
+    constraint: object = None
+    sampling_top_k: int = 0
+    sampling_top_p: float = 1.0
+
+    def generate_keywords(self, sampled: bool = False) -> dict:
+        """the keywords of model.generate — only those that are set, so that a backend that does not know them (a scripted
+        backend, CTranslate2 behind the shim) never sees them otherwise.  sampled: a rung with temperature > 0, the only
+        kind of decode the sampling limits apply to."""
+        kw = {}
+        if self.token_alternatives:
+            kw["return_alternatives"] = int(self.token_alternatives)
+        elif self.token_logprobs:
+            kw["return_token_logprobs"] = True
+        if self.boost is not None:
+            kw["boost"] = self.boost
+        if self.constraint is not None:
+            kw["constraint"] = self.constraint
+        if sampled and self.sampling_top_k:
+            kw["top_k"] = int(self.sampling_top_k)
+        if sampled and self.sampling_top_p != 1:
+            kw["top_p"] = float(self.sampling_top_p)
+        return kw
+
+    def keyword(self) -> dict:
+        """the keyword of an internal boundary — none when nothing is set (as generate_keywords)"""
+        return {} if self == DecodeExtras() else {"extras": self}
+
+
+def _decode_extras(model: "WhisperModel", a) -> DecodeExtras:
+    """The DecodeExtras of an entry point's arguments `a` (by name), checked before anything is loaded or decoded
+    (ValueError).  The lists are built here, once per call: the text encoding of a phrase does not depend on task or
+    language, so any tokenizer of the model gives the same ids."""
+    _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
+    _check_constraint_arguments(a["allowed_phrases"])
+    _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
+    tokenizer = model.make_tokenizer() if a["boost_phrases"] or a["allowed_phrases"] else None
+    return DecodeExtras(token_logprobs=a["token_logprobs"], token_alternatives=a["token_alternatives"],
+                        boost=model.boost_list_for(a["boost_phrases"], a["phrase_boost"], tokenizer),
+                        constraint=model.constraint_list_for(a["allowed_phrases"], tokenizer),
+                        sampling_top_k=a["sampling_top_k"], sampling_top_p=a["sampling_top_p"])
 
 
 def _per_recording(value, n, name, is_single):
@@ -574,27 +579,30 @@ class WhisperModel:
         allowed_phrases (not in the reference): see constraint_list_for — every decoded window is then exactly ONE phrase
         of the list, in every attempt of the fallback ladder.  Composes with boost_phrases."""
         args = dict(locals())               # the call's arguments by name
-        _check_boost_arguments(boost_phrases, phrase_boost)
-        _check_constraint_arguments(allowed_phrases)
-        _check_trunc_arguments(sampling_top_k, sampling_top_p)
+        return self._transcribe(args, _decode_extras(self, args))
+
+    def _transcribe(self, a: dict, extras: DecodeExtras):
+        """transcribe() behind its arguments `a` (by name) and their DecodeExtras (transcribe_many builds ONE for all its
+        recordings)"""
         from .vad import VadOptions, collect_chunks, get_speech_timestamps
         from .words import restore_speech_timestamps
         sr = self.feature_extractor.sampling_rate
-        multilingual = self._effective_multilingual(multilingual)
-        audio = self._load_audio(audio)
+        multilingual = self._effective_multilingual(a["multilingual"])
+        audio = self._load_audio(a["audio"])
         duration = audio.shape[0] / sr
         duration_after_vad = duration
         speech_chunks = None
-        if vad_filter and clip_timestamps == "0":
+        vad_parameters, clip_timestamps, language = a["vad_parameters"], a["clip_timestamps"], a["language"]
+        if a["vad_filter"] and clip_timestamps == "0":
             if vad_parameters is None:
                 vad_parameters = VadOptions()
             elif isinstance(vad_parameters, dict):
                 vad_parameters = VadOptions(**vad_parameters)
-            speech_chunks = get_speech_timestamps(audio, vad_parameters, speech_probs=vad_speech_probs)
+            speech_chunks = get_speech_timestamps(audio, vad_parameters, speech_probs=a["vad_speech_probs"])
             audio_chunks, _ = collect_chunks(audio, speech_chunks)
             audio = np.concatenate(audio_chunks, axis=0)
             duration_after_vad = audio.shape[0] / sr
-        features = self.feature_extractor(audio, chunk_length=chunk_length)
+        features = self.feature_extractor(audio, chunk_length=a["chunk_length"])
 
         all_language_probs = None
         if language is None:
@@ -606,19 +614,16 @@ class WhisperModel:
                 at = first * self.frames_per_second
                 seek = int(at) if at < content_frames else 0
                 language, language_probability, all_language_probs = self.detect_language(
-                    features=features[..., seek:], language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold)
+                    features=features[..., seek:], language_detection_segments=a["language_detection_segments"],
+                    language_detection_threshold=a["language_detection_threshold"])
         else:
             language, language_probability = self._effective_language(language), 1
-        tokenizer = self.make_tokenizer(task=task, language=language)
+        tokenizer = self.make_tokenizer(task=a["task"], language=language)
+        temperature, sampling_seed = a["temperature"], a["sampling_seed"]
         options = _transcription_options(
-            args, tokenizer, multilingual=multilingual,
+            a, tokenizer, multilingual=multilingual,
             temperatures=(temperature if isinstance(temperature, (list, tuple)) else [temperature]))
-        segments = self.generate_segments(features, tokenizer, options, log_progress, None,
-                                          **_value_keywords(token_logprobs, token_alternatives),
-                                          **_boost_keyword(self.boost_list_for(boost_phrases, phrase_boost, tokenizer)),
-                                          **_constraint_keyword(self.constraint_list_for(allowed_phrases, tokenizer)),
-                                          **_trunc_keywords(sampling_top_k, sampling_top_p),
+        segments = self.generate_segments(features, tokenizer, options, a["log_progress"], None, **extras.keyword(),
                                           **(dict(sampling_seed=int(sampling_seed)) if sampling_seed is not None else {}))
         if speech_chunks:
             segments = restore_speech_timestamps(segments, speech_chunks, sr)
@@ -652,27 +657,20 @@ class WhisperModel:
         meet in a decode run (they do: sampling calls share runs among themselves) each draw what they draw alone.
         Without sampling_seed the sampled attempts take their seeds from the model's call counter in arrival order, and
         which recording gets which seed depends on timing.
-        boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcribe(), so the
+        boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcription, so the
         windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
         allowed_phrases: likewise ONE constraint list for every recording.
         sampling_top_k / sampling_top_p (not in the reference): transcribe()'s, the same limits for every recording; sampled
         attempts share decode runs whatever their limits.
         An exception in one recording is raised here, after the recordings already started have finished."""
+        import inspect
         n = len(audios)
-        _check_boost_arguments(transcribe_kwargs.get("boost_phrases"), transcribe_kwargs.get("phrase_boost"))
-        _check_constraint_arguments(transcribe_kwargs.get("allowed_phrases"))
-        _check_trunc_arguments(transcribe_kwargs.get("sampling_top_k", 0), transcribe_kwargs.get("sampling_top_p", 1.0))
+        a = inspect.signature(self.transcribe).bind(None, **transcribe_kwargs)     # transcribe's keywords and defaults
+        a.apply_defaults()
+        a = a.arguments
+        extras = _decode_extras(self, a)
         if n == 0:
             return []
-        if transcribe_kwargs.get("boost_phrases") is not None:
-            # (the text encoding does not depend on task or language: any tokenizer of the model gives the same ids)
-            built = self.boost_list_for(transcribe_kwargs["boost_phrases"], transcribe_kwargs.get("phrase_boost"),
-                                        self.make_tokenizer())
-            transcribe_kwargs = dict(transcribe_kwargs, boost_phrases=None if built is None else _BuiltBoost(built))
-        if transcribe_kwargs.get("allowed_phrases") is not None:
-            built = self.constraint_list_for(transcribe_kwargs["allowed_phrases"], self.make_tokenizer())
-            transcribe_kwargs = dict(transcribe_kwargs,
-                                     allowed_phrases=None if built is None else _BuiltConstraint(built))
         languages = _per_recording(language, n, "language", lambda v: v is None or isinstance(v, str))
         prompts = _per_recording(
             initial_prompt, n, "initial_prompt",
@@ -687,9 +685,8 @@ class WhisperModel:
             seeds = _per_recording(sampling_seed, n, "sampling_seed", lambda v: False)
 
         def one(i):
-            segments, info = self.transcribe(audios[i], language=languages[i], initial_prompt=prompts[i],
-                                             **(dict(sampling_seed=seeds[i]) if seeds[i] is not None else {}),
-                                             **transcribe_kwargs)
+            segments, info = self._transcribe(dict(a, audio=audios[i], language=languages[i], initial_prompt=prompts[i],
+                                                   sampling_seed=seeds[i]), extras)
             return list(segments), info
 
         workers = min(n, self._workers())
@@ -702,9 +699,7 @@ class WhisperModel:
 
     def generate_segments(self, features: np.ndarray, tokenizer: Tokenizer, options: TranscriptionOptions,
                           log_progress: bool = False, encoder_output: Optional[StorageView] = None,
-                          token_logprobs: bool = False, sampling_seed: Optional[int] = None,
-                          token_alternatives: int = 0, boost=None, sampling_top_k: int = 0,
-                          sampling_top_p: float = 1.0, constraint=None):
+                          sampling_seed: Optional[int] = None, extras: DecodeExtras = DecodeExtras()):
         """The seek loop (generator of Segment).  For every clip [start, end) of `options.clip_timestamps`
         (frames; an odd count runs to the end of the audio) windows of up to 30 s are decoded at `seek`;
         the timestamps the model emitted (or the last word's end, or a hallucination-silence skip) decide
@@ -759,9 +754,7 @@ class WhisperModel:
                 prompt = self.get_prompt(tokenizer, previous_tokens, without_timestamps=options.without_timestamps,
                                          prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_logprob, temperature, compression_ratio = self.generate_with_fallback(
-                    encoder_output, prompt, tokenizer, options, **_value_keywords(token_logprobs, token_alternatives),
-                    **_boost_keyword(boost), **_constraint_keyword(constraint),
-                    **_trunc_keywords(sampling_top_k, sampling_top_p),
+                    encoder_output, prompt, tokenizer, options, **extras.keyword(),
                     **(dict(sampling_seed=sampling_seed, seek=seek) if sampling_seed is not None else {}))
 
                 if options.no_speech_threshold is not None:
@@ -776,9 +769,9 @@ class WhisperModel:
                 current, seek, single_timestamp_ending = self._split_segments_by_timestamps(
                     tokenizer=tokenizer, tokens=tokens, time_offset=time_offset, segment_size=segment_size,
                     segment_duration=segment_duration, seek=seek)
-                if token_logprobs or token_alternatives:
+                if extras.token_logprobs or extras.token_alternatives:
                     _slice_token_values(current, result.token_logprobs[0],
-                                        result.token_alternatives[0] if token_alternatives else None)
+                                        result.token_alternatives[0] if extras.token_alternatives else None)
 
                 if options.word_timestamps:
                     self.add_word_timestamps([current], tokenizer, encoder_output, segment_size,
@@ -813,19 +806,16 @@ class WhisperModel:
             pbar.close()
 
     def generate_with_fallback(self, encoder_output: StorageView, prompt: List[int], tokenizer: Tokenizer,
-                               options: TranscriptionOptions, token_logprobs: bool = False,
-                               sampling_seed: Optional[int] = None, seek: int = 0, token_alternatives: int = 0,
-                               boost=None, sampling_top_k: int = 0, sampling_top_p: float = 1.0, constraint=None):
+                               options: TranscriptionOptions, sampling_seed: Optional[int] = None, seek: int = 0,
+                               extras: DecodeExtras = DecodeExtras()):
         """Temperature ladder (transcribe.py:1402-1530): beam search at t = 0, `best_of` random samples at
         t > 0; a result is accepted unless it is too repetitive (compression ratio) or too improbable
         (average log-prob) — except when it looks like silence.  If every temperature fails, the most probable
         attempt (preferring those under the compression threshold) is returned with the last temperature.
         sampling_seed: the sampled attempt at rung t gets seed=attempt_seed(sampling_seed, seek, t), `seek` the window's
         first frame; None: no seed is passed, the backend draws one from its call counter.
-        boost: the call's boost list (boost_list_for), the same one for every attempt.
-        constraint: the call's constraint list (constraint_list_for), likewise.
-        sampling_top_k / sampling_top_p: limits on the draws of the sampled attempts (temperature > 0) only; at 0 / 1.0 no
-        keyword is passed to generate.
+        extras: the call's DecodeExtras, the same for every attempt; its sampling limits reach the sampled attempts
+        (temperature > 0) only.
         -> (WhisperGenerationResult, avg_logprob, temperature, compression_ratio)"""
         max_initial_timestamp_index = int(round(options.max_initial_timestamp / self.time_precision))
         max_length = self._max_length_for(prompt, options.max_new_tokens)
@@ -837,7 +827,6 @@ class WhisperModel:
                             sampling_temperature=temperature)
                 if sampling_seed is not None:
                     mode["seed"] = attempt_seed(sampling_seed, seek, rung)
-                mode.update(_trunc_keywords(sampling_top_k, sampling_top_p, "top_k", "top_p"))
             else:
                 mode = dict(beam_size=options.beam_size, patience=options.patience)
             result = self.model.generate(
@@ -845,9 +834,8 @@ class WhisperModel:
                 repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
                 max_length=max_length, return_scores=True, return_no_speech_prob=True,
                 suppress_blank=options.suppress_blank, suppress_tokens=options.suppress_tokens,
-                max_initial_timestamp_index=max_initial_timestamp_index, **mode, **_boost_keyword(boost),
-                **_constraint_keyword(constraint),
-                **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))[0]
+                max_initial_timestamp_index=max_initial_timestamp_index, **mode,
+                **extras.generate_keywords(sampled=temperature > 0))[0]
             avg_logprob = _avg_logprob(result, options.length_penalty)
             compression_ratio = get_compression_ratio(tokenizer.decode(result.sequences_ids[0]).strip())
             attempt = (result, avg_logprob, temperature, compression_ratio)
@@ -883,8 +871,6 @@ class WhisperModel:
         _check_boost_arguments(boost_phrases, phrase_boost)
         if boost_phrases is None:
             return None
-        if isinstance(boost_phrases, _BuiltBoost):
-            return boost_phrases.boost
         phrases = [tokenizer.encode(" " + p.strip()) for p in boost_phrases]
         if not phrases:
             return None
@@ -904,8 +890,6 @@ class WhisperModel:
         _check_constraint_arguments(allowed_phrases)
         if allowed_phrases is None:
             return None
-        if isinstance(allowed_phrases, _BuiltConstraint):
-            return allowed_phrases.constraint
         phrases = [tokenizer.encode(" " + p.strip()) for p in allowed_phrases]
         if not phrases:
             return None
@@ -1093,15 +1077,13 @@ class BatchedInferencePipeline:
 
     # ---- one batch: encode + generate ---------------------------------------------------
     def generate_segment_batched(self, features, tokenizer: Tokenizer, options: TranscriptionOptions,
-                                 audio_chunks: Optional[List[np.ndarray]] = None, token_logprobs: bool = False,
-                                 token_alternatives: int = 0, boost=None, constraint=None):
+                                 audio_chunks: Optional[List[np.ndarray]] = None, extras: DecodeExtras = DecodeExtras()):
         """features: [B, n_mels, 3000] float32, or None when `audio_chunks` is given (fused resident
-        PCM -> log-mel -> encoder path; the features never leave HBM).  token_logprobs: every output dict also carries
-        the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`);
-        token_alternatives=N: those, and the N most likely (id, log-prob) pairs per token (`token_alternatives`) and at
-        the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget).  boost: the call's boost list
-        (WhisperModel.boost_list_for), passed to generate when there is one; constraint: its constraint list
-        (WhisperModel.constraint_list_for), likewise."""
+        PCM -> log-mel -> encoder path; the features never leave HBM).  extras.token_logprobs: every output dict also
+        carries the chunk's per-token log-probs (`token_logprobs`) and that of its closing <eot> (`end_logprob`);
+        extras.token_alternatives=N: those, and the N most likely (id, log-prob) pairs per token (`token_alternatives`) and
+        at the closing <eot> (`end_alternatives`, None when the chunk was cut at the budget).  extras.boost /
+        extras.constraint: the call's lists, passed to generate when there are any."""
         m = self.model
         batch_size = len(audio_chunks) if audio_chunks is not None else features.shape[0]
         prompt = m.get_prompt(tokenizer,
@@ -1124,15 +1106,14 @@ class BatchedInferencePipeline:
             length_penalty=options.length_penalty, max_length=max_length, suppress_blank=options.suppress_blank,
             suppress_tokens=options.suppress_tokens, return_scores=True, return_no_speech_prob=True,
             sampling_temperature=options.temperatures[0], repetition_penalty=options.repetition_penalty,
-            no_repeat_ngram_size=options.no_repeat_ngram_size, **_boost_keyword(boost), **_constraint_keyword(constraint),
-            **_value_keywords(token_logprobs, token_alternatives, "return_token_logprobs", "return_alternatives"))
+            no_repeat_ngram_size=options.no_repeat_ngram_size, **extras.generate_keywords())
         output = []
         for r in results:
             output.append(dict(avg_logprob=_avg_logprob(r, options.length_penalty), no_speech_prob=r.no_speech_prob,
                                tokens=r.sequences_ids[0]))
-            if token_logprobs or token_alternatives:
+            if extras.token_logprobs or extras.token_alternatives:
                 output[-1].update(token_logprobs=r.token_logprobs[0], end_logprob=r.end_logprobs[0])
-            if token_alternatives:
+            if extras.token_alternatives:
                 output[-1].update(token_alternatives=r.token_alternatives[0], end_alternatives=r.end_alternatives[0])
         return encoder_output, output
 
@@ -1206,9 +1187,7 @@ class BatchedInferencePipeline:
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model
-        _check_boost_arguments(boost_phrases, phrase_boost)
-        _check_constraint_arguments(allowed_phrases)
-        _check_trunc_arguments(sampling_top_k, sampling_top_p)
+        extras = _decode_extras(m, args)
         if (token_logprobs or token_alternatives) and shard:
             raise ValueError("token_logprobs / token_alternatives are not offered with shard=True: the gathered records "
                              "carry no per-token values")
@@ -1227,10 +1206,7 @@ class BatchedInferencePipeline:
                 language_detection_threshold=language_detection_threshold)
         self._plan_decode(rec, args, language, multilingual, {})
         gen = self._batched_segments_generator(rec.audio_chunks, rec.tokenizer, rec.chunks_metadata, batch_size,
-                                               rec.options, log_progress, shard, fused_features,
-                                               **_value_keywords(token_logprobs, token_alternatives),
-                                               **_boost_keyword(m.boost_list_for(boost_phrases, phrase_boost, rec.tokenizer)),
-                                               **_constraint_keyword(m.constraint_list_for(allowed_phrases, rec.tokenizer)))
+                                               rec.options, log_progress, shard, fused_features, **extras.keyword())
         return self._on_recording_time(rec, gen), rec.info
 
     # ---- the steps of transcribe that transcribe_many runs per recording -----------------
@@ -1335,8 +1311,7 @@ class BatchedInferencePipeline:
         return restore_speech_timestamps(segments, rec.clips, self.model.feature_extractor.sampling_rate)
 
     def _batched_segments_generator(self, audio_chunks, tokenizer, chunks_metadata, batch_size, options,
-                                    log_progress, shard=False, fused_features=True, token_logprobs=False,
-                                    token_alternatives=0, boost=None, constraint=None):
+                                    log_progress, shard=False, fused_features=True, extras=DecodeExtras()):
         from .sharding import gather_results, partition
         m = self.model
         rank, world, local_rank = 0, 1, 0
@@ -1359,8 +1334,7 @@ class BatchedInferencePipeline:
                 mid = lo + (hi - lo + 1) // 2
                 spans = [(lo, mid), (mid, hi)]
             return self._batches_in_flight([(audio_chunks[i0:i1], chunks_metadata[i0:i1], tokenizer, options)
-                                            for i0, i1 in spans], shard, fused_features, token_logprobs,
-                                           token_alternatives, boost, constraint)
+                                            for i0, i1 in spans], shard, fused_features, **extras.keyword())
 
         def emit(results):
             nonlocal seg_idx
@@ -1407,14 +1381,12 @@ class BatchedInferencePipeline:
         self.last_speech_timestamp = 0.0
 
     def _decode_batch(self, chunks, chunks_metadata, tokenizer, options, shard=False, fused_features=True,
-                      token_logprobs=False, token_alternatives=0, boost=None, constraint=None):
+                      extras=DecodeExtras()):
         """one batch: encode + generate, then the chunk-local post-processing -> (outs, sub-segments, word alignments)"""
         m = self.model
         feats = None if fused_features else m.model.log_mel(chunks)
         enc, outs = self.generate_segment_batched(feats, tokenizer, options,
-                                                  audio_chunks=chunks if fused_features else None,
-                                                  **_value_keywords(token_logprobs, token_alternatives),
-                                                  **_boost_keyword(boost), **_constraint_keyword(constraint))
+                                                  audio_chunks=chunks if fused_features else None, **extras.keyword())
         local = aligned = None
         if not shard or options.word_timestamps:
             local, sizes = self._split_outputs(outs, tokenizer, chunks_metadata)
@@ -1424,8 +1396,7 @@ class BatchedInferencePipeline:
                                         options.append_punctuations)
         return outs, local, aligned
 
-    def _batches_in_flight(self, jobs, shard=False, fused_features=True, token_logprobs=False, token_alternatives=0,
-                           boost=None, constraint=None):
+    def _batches_in_flight(self, jobs, shard=False, fused_features=True, extras=DecodeExtras()):
         """(outs, local, aligned) per job = (chunks, chunks_metadata, tokenizer, options), in order.
         The batches are independent (`condition_on_previous_text=False`): with worker replicas
         (WhisperModel(num_workers=W) -> backend inter_threads) W batches are kept in flight on the GPU — their
@@ -1434,15 +1405,14 @@ class BatchedInferencePipeline:
         workers = self.model._workers()
         if workers <= 1 or len(jobs) <= 1:
             for job in jobs:
-                yield self._decode_batch(*job, shard, fused_features, token_logprobs, token_alternatives, boost, constraint)
+                yield self._decode_batch(*job, shard, fused_features, **extras.keyword())
             return
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=workers) as pool:
             pending = deque()
             for job in jobs:
-                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, token_logprobs,
-                                           token_alternatives, boost, constraint))
+                pending.append(pool.submit(self._decode_batch, *job, shard, fused_features, **extras.keyword()))
                 if len(pending) >= workers:
                     yield pending.popleft().result()
             while pending:
@@ -1487,9 +1457,7 @@ class BatchedInferencePipeline:
         a = a.arguments
         m = self.model
         n = len(audios)
-        _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
-        _check_constraint_arguments(a["allowed_phrases"])
-        _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
+        extras = _decode_extras(m, a)     # (ONE list of either kind for the batches of every recording and language)
         if n == 0:
             return []
         multilingual = m._effective_multilingual(a["multilingual"])
@@ -1549,12 +1517,8 @@ class BatchedInferencePipeline:
                 owners.append([rec for rec, _, _ in part])
 
         # ---- route: every chunk's sub-segments and word alignment back to its recording, in chunk order ----
-        # (ONE boost list for the batches of every recording and language: the text encoding is the vocabulary's)
-        boost = m.boost_list_for(a["boost_phrases"], a["phrase_boost"], next(iter(tokenizers.values())))
-        constraint = m.constraint_list_for(a["allowed_phrases"], next(iter(tokenizers.values())))
         for owner, (_, local, aligned) in zip(owners, self._batches_in_flight(jobs, False, a["fused_features"],
-                                                                              a["token_logprobs"],
-                                                                              a["token_alternatives"], boost, constraint)):
+                                                                              **extras.keyword())):
             for j, rec in enumerate(owner):
                 rec.decoded.append(local[j])
                 if aligned is not None:

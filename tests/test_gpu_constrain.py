@@ -14,7 +14,9 @@ list, 12 new tokens).  A, B, C and the other phrase ids are text ids outside the
      list at position q is finite before q and -inf from q on, the end entry included;
   7. two calls with equal lists built separately share ONE decode run, another list and a plain call do not join;
   8. the call-time ValueErrors;
-  9. with a boost: +1e4 on an unlisted id changes nothing at all; on one listed phrase among several it decides.
+  9. with a boost: +1e4 on an unlisted id changes nothing at all; on one listed phrase among several it decides;
+ 10. score() with a boost AND a constraint list over position blocks (several positions per pass, blocks that start
+     behind position 0, rows without a target) gives the bits of the same call at one position per pass.
 
 UNFILLED SLOTS (test 3, found, not changed): a beam search that is asked for more hypotheses than the list lets finish —
 num_hypotheses=3 with ONE phrase — ends as soon as no live beam is left (-inf candidates are never merged, so a dead beam
@@ -251,6 +253,47 @@ def test_a_target_that_leaves_the_list_scores_minus_infinity_from_there(setup):
                 assert np.all(np.isfinite(lps))
             else:
                 assert np.all(np.isfinite(lps[:q])) and np.all(lps[q:] == -np.inf), (seq, lps)
+
+
+def test_score_with_both_lists_over_position_blocks(setup):
+    """Two chunks x two candidates with targets of 0, 1, 5 and 9 ids behind a prompt of 22 ids: 31 positions, so more than
+    one block whatever the block size (at most 16), the later blocks start behind position 0, and the rows of positions in
+    front of the last prompt token — and of the shorter targets' tails — have no target.  Both pre-pass kernels run on every
+    block.  The reference is the same call with one position per pass (fw_test_knob 4, as tests/test_gpu_score.py compares
+    plain scoring): there every launch is the single-row form that tests/test_gpu_boost_kernel.py and
+    tests/test_gpu_constrain_kernel.py hold against the host walks bit for bit.  (The engine returns no logits rows, so the
+    host walks cannot be applied to the rows of this call directly.)"""
+    from faster_whisper_amd import _lib
+    from faster_whisper_amd.backend import StorageView
+    cfg, model, _ = setup
+    lib = _lib.load()
+    enc = model.encode(StorageView.from_array(model.log_mel([bench_audio(480000, seed=1), bench_audio(200000, seed=2)])))
+    prompt = [cfg.sot_prev] + [10 + (7 * i) % 200 for i in range(17)] + _prompt(cfg)
+    long9 = [B, A, C, 21, A, B, C, A, B]                  # a phrase, then five ids more: it leaves the list at 4
+    targets = [[[], [A]], [[21, 22, 23, 24, 25], long9]]
+    assert [len(t) for ts in targets for t in ts] == [0, 1, 5, 9] and len(prompt) + 9 > 16
+    kw = dict(rules=True, suppress_tokens=_suppress(cfg), repetition_penalty=1.2)
+    lists = dict(constraint=model.constraint_list(PH9), boost=model.boost_list([[A, B], [21, 22, 23]], [1.5, -0.75]))
+
+    def bits(sc):
+        return [[_bits(x).tolist() for x in (s.token_logprobs[h], s.end_logprobs[h], s.best_ids[h], s.best_logprobs[h])]
+                for s in sc for h in range(2)]
+    res = {}
+    try:
+        for on in (0, 1):
+            _lib.check(lib.fw_test_knob(4, on))
+            res[on] = model.score(enc, [prompt] * 2, targets, **kw, **lists)
+    finally:
+        _lib.check(lib.fw_test_knob(4, 1))
+    assert bits(res[0]) == bits(res[1])
+    # both lists did something, and the constraint's pattern is the one the list implies
+    only_c = model.score(enc, [prompt] * 2, targets, constraint=lists["constraint"], **kw)
+    only_b = model.score(enc, [prompt] * 2, targets, boost=lists["boost"], **kw)
+    assert bits(only_c) != bits(res[1]) and bits(only_b) != bits(res[1])
+    lps = [np.asarray(s.token_logprobs[h] + [s.end_logprobs[h]], dtype=np.float32) for s in res[1] for h in range(2)]
+    assert lps[0][0] == -np.inf                           # no phrase is empty: <eot> at once is not allowed
+    assert np.all(np.isfinite(lps[1])) and np.all(np.isfinite(lps[2]))
+    assert np.all(np.isfinite(lps[3][:4])) and np.all(lps[3][4:] == -np.inf)
 
 
 def test_equal_lists_share_a_run_and_others_do_not():
