@@ -96,6 +96,8 @@ SYMBOLS = [
     "fw_generate_trunc", "fw_test_logits_rules_trunc",
     "fw_constraint_create", "fw_constraint_free", "fw_generate_constrain", "fw_score_constrain",
     "fw_test_constrain_rows", "fw_test_constrain_rows_host", "fw_test_constraint_table",
+    "fw_automaton_create", "fw_automaton_free", "fw_generate_automaton", "fw_score_automaton",
+    "fw_test_automaton_rows", "fw_test_automaton_rows_host", "fw_test_automaton_table",
 ]
 
 _lib = None
@@ -264,6 +266,15 @@ def load():
         lib.fw_test_constrain_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
         lib.fw_test_constrain_rows_host.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
         lib.fw_test_constraint_table.argtypes = [vp, vp, i32, i32p]
+    if hasattr(lib, "fw_automaton_create"):         # (absent from an older build loaded through FWAMD_LIB)
+        lib.fw_automaton_create.argtypes = [i32, i32, i32p, i32p, i32p, i32p, C.POINTER(vp)]
+        lib.fw_automaton_free.argtypes = [vp]
+        lib.fw_automaton_free.restype = None
+        lib.fw_generate_automaton.argtypes = lib.fw_generate_constrain.argtypes   # (an automaton in the list's place)
+        lib.fw_score_automaton.argtypes = lib.fw_score_constrain.argtypes
+        lib.fw_test_automaton_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, f32p]
+        lib.fw_test_automaton_rows_host.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+        lib.fw_test_automaton_table.argtypes = [vp, vp, i32, i32p]
     if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

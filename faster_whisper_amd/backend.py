@@ -218,6 +218,41 @@ class ConstraintList(_PhraseList):
         self._compile(n_vocab, [list(p) for p in phrases])
 
 
+class Automaton:
+    """A validated, compiled token automaton (fwamd.h: fw_automaton_create) built from a grammar.Grammar: at every step the
+    ids that label no out-edge of the state the row's generated text leads to are set to -inf in front of the decoding
+    rules, and <eot> is allowed only in an accepting state — a hypothesis with a finite score that closes on <eot> is, its
+    timestamps apart, a string of the grammar's language.  Host-only: needs no device.  Whisper.automaton builds one for
+    the model's vocabulary; pass it as generate(automaton=...) / score(automaton=...)."""
+
+    def __init__(self, n_vocab: int, grammar):
+        lib = _lib.load()
+        if not hasattr(lib, "fw_automaton_create"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_automaton_create: automaton-constrained decoding needs a current build")
+        offsets, tokens, targets, accepting = (np.ascontiguousarray(a, dtype=np.int32) for a in grammar.csr())
+        self.n_vocab = int(n_vocab)
+        self.grammar = grammar
+        self._handle = C.c_void_p()
+        _lib.check(lib.fw_automaton_create(self.n_vocab, len(accepting), _lib.as_i32p(offsets), _lib.as_i32p(tokens),
+                                           _lib.as_i32p(targets), _lib.as_i32p(accepting), C.byref(self._handle)))
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            try:
+                _lib.load().fw_automaton_free(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    @staticmethod
+    def _handle_of(value):
+        if value is None:
+            return None
+        if not isinstance(value, Automaton):
+            raise TypeError("automaton must be an Automaton (Whisper.automaton) or None")
+        return value._handle
+
+
 def _require_symbols(lib, needs) -> None:
     """needs: (used, symbol, what it serves) in the order the features were added.  A build loaded through FWAMD_LIB that
     lacks the symbol of a feature the call uses cannot serve the call (RuntimeError)."""
@@ -226,7 +261,7 @@ def _require_symbols(lib, needs) -> None:
             raise RuntimeError(f"this libfwamd.so has no {symbol}: {what} a current build")
 
 
-def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, constraint_h):
+def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, constraint_h, automaton_h=None):
     """The engine entry point of a generate call and its argument list: the OLDEST symbol that can express the call, so a
     build that lacks newer ones still serves every call it can.  head: (model, encoder output, prompts, offsets, B, options);
     outs: (ids, lens, scores, no-speech probabilities); lp: the two log-prob arrays, alt: the four alternative arrays
@@ -235,9 +270,12 @@ def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, const
     want_lp = lp[0] is not None
     _require_symbols(lib, ((boost_h is not None, "fw_generate_boost", "phrase boosting needs"),
                            (constraint_h is not None, "fw_generate_constrain", "constrained decoding needs"),
+                           (automaton_h is not None, "fw_generate_automaton", "automaton-constrained decoding needs"),
                            (trunc, "fw_generate_trunc", "top_k / top_p need"),
                            (n_alt, "fw_generate_alt", "per-token log-probabilities and alternatives need"),
                            (want_lp, "fw_generate_lp", "per-token log-probabilities need")))
+    if automaton_h is not None:   # (never beside a constraint list: generate() refuses the pair)
+        return lib.fw_generate_automaton, (*head, top_k, top_p, n_alt, boost_h, automaton_h, *outs, *lp, *alt)
     if constraint_h is not None:
         return lib.fw_generate_constrain, (*head, top_k, top_p, n_alt, boost_h, constraint_h, *outs, *lp, *alt)
     if trunc:
@@ -251,11 +289,14 @@ def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, const
     return lib.fw_generate, (*head, *outs)
 
 
-def _score_call(lib, head, outs, boost_h, constraint_h):
+def _score_call(lib, head, outs, boost_h, constraint_h, automaton_h=None):
     """as _generate_call, for score().  head: (model, encoder output, prompts, offsets, targets, offsets, B, H, rules)"""
     _require_symbols(lib, ((True, "fw_score", "scoring needs"),
                            (boost_h is not None, "fw_score_boost", "phrase boosting needs"),
-                           (constraint_h is not None, "fw_score_constrain", "constrained decoding needs")))
+                           (constraint_h is not None, "fw_score_constrain", "constrained decoding needs"),
+                           (automaton_h is not None, "fw_score_automaton", "automaton-constrained decoding needs")))
+    if automaton_h is not None:
+        return lib.fw_score_automaton, (*head, boost_h, automaton_h, *outs)
     if constraint_h is not None:
         return lib.fw_score_constrain, (*head, boost_h, constraint_h, *outs)
     if boost_h is not None:
@@ -669,6 +710,13 @@ class Whisper:
         on, a suppressed id, ...) is checked by that call, against its own rules."""
         return ConstraintList(self._cfg.n_vocab, phrases)
 
+    def automaton(self, grammar) -> Automaton:
+        """An Automaton for this model's vocabulary from a grammar.Grammar over token ids.  ValueError (fwamd.h:
+        FW_AUTOMATON_MAX_STATES / _EDGES): more than 4096 states or 8192 edges, an id outside the vocabulary, a grammar
+        whose language is empty.  What a generate / score call refuses of an automaton (an id from <eot> on, a suppressed
+        id, ...) is checked by that call, against its own rules."""
+        return Automaton(self._cfg.n_vocab, grammar)
+
     # ---- generate -----------------------------------------------------------------------
     def generate(self, features: StorageView, prompts: List[List[int]], *, asynchronous: bool = False,
                  beam_size: int = 5, patience: float = 1, num_hypotheses: int = 1, length_penalty: float = 1,
@@ -679,7 +727,8 @@ class Whisper:
                  sampling_temperature: float = 1, min_new_tokens: int = 0,
                  seed: Optional[int] = None, return_token_logprobs: bool = False,
                  return_alternatives: int = 0, boost: Optional[BoostList] = None, top_k: int = 0,
-                 top_p: float = 1.0, constraint: Optional[ConstraintList] = None) -> List[WhisperGenerationResult]:
+                 top_p: float = 1.0, constraint: Optional[ConstraintList] = None,
+                 automaton: Optional[Automaton] = None) -> List[WhisperGenerationResult]:
         """boost (not in CTranslate2): a BoostList (boost_list()) whose phrases are made more likely at the logit, in front
         of the decoding rules; None or an empty list: the call without it.
         top_k / top_p (not in CTranslate2's generate(); fwamd.h: fw_generate_trunc): limits on the draw of a SAMPLING call
@@ -691,10 +740,16 @@ class Whisper:
         behind the boost and in front of the rules; log-probs, alternatives and scores are those of the constrained
         distribution.  None or an empty list: the call without it.  ValueError: a list for another vocabulary, a phrase id
         from <eot> on or in suppress_tokens, a first id that suppress_blank forbids, no_repeat_ngram_size > 0,
-        min_new_tokens > 0."""
+        min_new_tokens > 0.
+        automaton (not in CTranslate2; fwamd.h: fw_generate_automaton): an Automaton (automaton()) in the constraint's
+        place — every hypothesis is, its timestamps apart, a string the grammar accepts (or a prefix of one when the budget
+        cut it).  The constraint's order, outputs and ValueErrors, edge ids for phrase ids; not together with constraint."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
         boost_h, constraint_h = BoostList._handle_of(boost), ConstraintList._handle_of(constraint)
+        automaton_h = Automaton._handle_of(automaton)
+        if automaton_h is not None and constraint_h is not None:
+            raise ValueError("generate() takes a constraint list or an automaton, not both")
         top_k, top_p = int(top_k), float(top_p)
         n_alt = int(return_alternatives)
         if not 0 <= n_alt <= MAX_ALTERNATIVES:
@@ -744,7 +799,7 @@ class Whisper:
             entry, args = _generate_call(
                 self._lib, (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o)),
                 (_lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp)), (f32(tlp), f32(elp)),
-                (i32(aid), f32(alp), i32(eid), f32(elps)), n_alt, top_k, top_p, boost_h, constraint_h)
+                (i32(aid), f32(alp), i32(eid), f32(elps)), n_alt, top_k, top_p, boost_h, constraint_h, automaton_h)
             _lib.check(entry(*args))
             out = []
             for b in range(B):
@@ -816,7 +871,7 @@ class Whisper:
 
     def score(self, features: StorageView, prompts: List[List[int]], targets, *, rules: bool = False,
               boost: Optional[BoostList] = None, constraint: Optional[ConstraintList] = None,
-              **rule_kwargs) -> List[WhisperScoringResult]:
+              automaton: Optional[Automaton] = None, **rule_kwargs) -> List[WhisperScoringResult]:
         """Teacher-forced log-probs of given transcripts (fwamd.h: fw_score; not in CTranslate2's Whisper class).
         targets[b]: one sequence of ids, or a list of up to max_beam_size sequences, scored against chunk b.
         rules=False: the raw distribution.  rules=True: the distribution generate()'s search ranks by, with generate's
@@ -826,7 +881,9 @@ class Whisper:
         boost: the BoostList of a generate(boost=...) call, added in front of the rules with the sequence's own prefix as the
         generated history; needs rules=True.
         constraint: the ConstraintList of a generate(constraint=...) call, applied behind the boost and in front of the
-        rules; needs rules=True.  A target that leaves the list scores -inf from there on."""
+        rules; needs rules=True.  A target that leaves the list scores -inf from there on.
+        automaton: the Automaton of a generate(automaton=...) call, in the constraint's place (not together with it); needs
+        rules=True.  A target that leaves the language scores -inf from there on."""
         unknown = set(rule_kwargs) - set(self._RULE_DEFAULTS)
         if unknown:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
@@ -837,6 +894,11 @@ class Whisper:
             raise ValueError("boost needs rules=True: the boost is the first step of the decoding rules")
         if constraint_h is not None and not rules:
             raise ValueError("constraint needs rules=True: the constraint is a step of the decoding rules")
+        automaton_h = Automaton._handle_of(automaton)
+        if automaton_h is not None and not rules:
+            raise ValueError("automaton needs rules=True: the automaton is a step of the decoding rules")
+        if automaton_h is not None and constraint_h is not None:
+            raise ValueError("score() takes a constraint list or an automaton, not both")
         enc = self._as_encoded(features)
         if len(prompts) != enc._shape[0] or len(targets) != enc._shape[0]:
             raise ValueError(f"got {len(prompts)} prompts and {len(targets)} targets for a batch of {enc._shape[0]}")
@@ -873,7 +935,7 @@ class Whisper:
             head = (enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs), _lib.as_i32p(tflat),
                     _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None)
             outs = (_lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp))
-            entry, args = _score_call(self._lib, head, outs, boost_h, constraint_h)
+            entry, args = _score_call(self._lib, head, outs, boost_h, constraint_h, automaton_h)
             _lib.check(entry(*args))
             out = []
             for b in range(B):

@@ -26,13 +26,6 @@ static __host__ __device__ __forceinline__ int constrain_next(const ConstrainVie
   return m < L ? p[m] : eot;
 }
 
-// bit v of the row's keep mask as it starts out: the timestamp ids when the timestamp rules are on, nothing else
-static __host__ __device__ __forceinline__ unsigned constrain_word_init(int w, int ts_begin, int with_ts) {
-  const int lo = w * 32;
-  if (!with_ts || lo + 32 <= ts_begin) return 0u;
-  return lo >= ts_begin ? ~0u : ~0u << (ts_begin - lo);
-}
-
 }  // namespace fwd
 
 // ------------------------------------------------------------------------------------
@@ -41,10 +34,8 @@ static __host__ __device__ __forceinline__ unsigned constrain_word_init(int w, i
 //      totals through LDS); only the first FW_CONSTRAIN_MAX_LEN + 1 are kept, m counts on to at least that;
 //   2. a keep mask of one bit per id in LDS: the timestamp ids when the rules want them, then threads stride over the
 //      phrases and OR in what each allows (LDS atomics on a bit: the mask does not depend on the order);
-//   3. -inf over every id whose bit is clear.  The logits are never read: a group of four ids with no bit set takes ONE
-//      16-byte store, a mixed group one 4-byte store per cleared id, a kept id none — its bits are untouched.  The row
-//      starts at r * V floats, 16-, 4-, 8- or 12-byte aligned: up to three ids in front of the first 16-byte boundary and
-//      up to three behind the last are peeled off in plain stores, no store is wider than its alignment.
+//   3. -inf over every id whose bit is clear (fwd::write_neg_inf_row, dec_kernels.h: shared with dec_automaton_kernel).  The
+//      logits are never read; the row starts at r * V floats, 16-, 4-, 8- or 12-byte aligned.
 // SCORE = false, the decode step: the history is the parity half of hist2 that *d_step selects, n = step, rows of done
 // chunks return.  SCORE = true: row r is position pos0 + r % nb of sequence r / nb, as dec_score_kernel addresses it; a row
 // without a target returns.
@@ -99,31 +90,7 @@ __global__ __launch_bounds__(CONSTRAIN_THREADS) void dec_constrain_kernel(
   __syncthreads();
 
   // 3. -inf over the rest
-  const float NEG = -INFINITY;
-  float* lg = logits + (size_t)r * V;
-  int head = (int)(((16u - (unsigned)((uintptr_t)lg & 15u)) & 15u) >> 2);   // ids in front of the first 16-byte boundary
-  head = head < V ? head : V;
-  const int n_vec = (V - head) >> 2, tail0 = head + 4 * n_vec;
-  if (tid < head && !((keep[tid >> 5] >> (tid & 31)) & 1u)) lg[tid] = NEG;
-  {
-    const int v = tail0 + tid;   // tid < 3 at most
-    if (v < V && !((keep[v >> 5] >> (v & 31)) & 1u)) lg[v] = NEG;
-  }
-  const float4 neg4 = make_float4(NEG, NEG, NEG, NEG);
-  for (int i = tid; i < n_vec; i += CONSTRAIN_THREADS) {
-    const int v0 = head + 4 * i;   // v0 + 3 < tail0 <= V
-    const int w = v0 >> 5;
-    const unsigned long long win = ((unsigned long long)keep[w + 1] << 32) | keep[w];
-    const unsigned k4 = (unsigned)(win >> (v0 & 31)) & 15u;
-    if (k4 == 0u) {
-      *reinterpret_cast<float4*>(lg + v0) = neg4;
-    } else if (k4 != 15u) {
-      if (!(k4 & 1u)) lg[v0] = NEG;
-      if (!(k4 & 2u)) lg[v0 + 1] = NEG;
-      if (!(k4 & 4u)) lg[v0 + 2] = NEG;
-      if (!(k4 & 8u)) lg[v0 + 3] = NEG;
-    }
-  }
+  fwd::write_neg_inf_row(logits + (size_t)r * V, V, keep, tid, CONSTRAIN_THREADS);
 }
 
 namespace fwd {

@@ -1,5 +1,8 @@
 // Launch API of the decoder-step kernels (dec_kernels.hip; the kernels that hold one vocabulary row: dec_vocab.hip).
 #pragma once
+#include <math.h>
+#include <stdint.h>
+
 #include <vector>
 
 #include "../../include/fwamd.h"
@@ -49,6 +52,10 @@ struct GenDev {
   // kernel.  0 in every run without a list: the key, the kernels and the graphs of today.  The table's sizes travel in the
   // table's header, not here.
   int constrain;
+  // AUTOMATON (fw_generate_automaton): non-zero when the step launches dec_automaton_kernel between the boost and the rules
+  // kernel: 1 = the kernel's small LDS allocation, 2 = its large one (automaton_lds_class: by the table's size, which
+  // fixes the launch a step graph captures).  0 in every run without an automaton: the key, the kernels and the graphs of today.
+  int automaton;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -258,6 +265,44 @@ static __device__ __forceinline__ bool row_history(const RowSource& s, int r, in
   n = n < NT ? n : NT;
   return true;
 }
+// bit v of a row's keep mask as the constraint and the automaton start it: the timestamp ids when the timestamp rules are on,
+// nothing else
+static __host__ __device__ __forceinline__ unsigned constrain_word_init(int w, int ts_begin, int with_ts) {
+  const int lo = w * 32;
+  if (!with_ts || lo + 32 <= ts_begin) return 0u;
+  return lo >= ts_begin ? ~0u : ~0u << (ts_begin - lo);
+}
+// -inf over every id of logits row lg[0 .. V) whose bit in `keep` (LDS, one bit per id, one word more than the ids need:
+// the 64-bit window of the last group reads it) is clear, by the `nt` threads of a workgroup.  The logits are never read:
+// a group of four ids with no bit set takes ONE 16-byte store, a mixed group one 4-byte store per cleared id, a kept id
+// none — its bits are untouched.  The row is 16-, 4-, 8- or 12-byte aligned: up to three ids in front of the first
+// 16-byte boundary and up to three behind the last are peeled off in plain stores, no store is wider than its alignment.
+static __device__ __forceinline__ void write_neg_inf_row(float* lg, int V, const unsigned* keep, int tid, int nt) {
+  const float NEG = -INFINITY;
+  int head = (int)(((16u - (unsigned)((uintptr_t)lg & 15u)) & 15u) >> 2);   // ids in front of the first 16-byte boundary
+  head = head < V ? head : V;
+  const int n_vec = (V - head) >> 2, tail0 = head + 4 * n_vec;
+  if (tid < head && !((keep[tid >> 5] >> (tid & 31)) & 1u)) lg[tid] = NEG;
+  {
+    const int v = tail0 + tid;   // tid < 3 at most
+    if (v < V && !((keep[v >> 5] >> (v & 31)) & 1u)) lg[v] = NEG;
+  }
+  const float4 neg4 = make_float4(NEG, NEG, NEG, NEG);
+  for (int i = tid; i < n_vec; i += nt) {
+    const int v0 = head + 4 * i;   // v0 + 3 < tail0 <= V
+    const int w = v0 >> 5;
+    const unsigned long long win = ((unsigned long long)keep[w + 1] << 32) | keep[w];
+    const unsigned k4 = (unsigned)(win >> (v0 & 31)) & 15u;
+    if (k4 == 0u) {
+      *reinterpret_cast<float4*>(lg + v0) = neg4;
+    } else if (k4 != 15u) {
+      if (!(k4 & 1u)) lg[v0] = NEG;
+      if (!(k4 & 2u)) lg[v0 + 1] = NEG;
+      if (!(k4 & 4u)) lg[v0 + 2] = NEG;
+      if (!(k4 & 8u)) lg[v0 + 3] = NEG;
+    }
+  }
+}
 // dec_score_kernel over `rows` logits rows in ONE launch: row r is position pos0 + r % nb of sequence r / nb and reads
 // tab[(r / nb) * tab_stride + pos0 + r % nb].  rules: the decoding rules of gp (with_ts, suppress_blank, mits, ngram,
 // rep_pen, the token ids) and sup_bits first, on a greedy row whose history is the ScoreRow's; otherwise the raw
@@ -336,11 +381,56 @@ void launch_constrain_score(hipStream_t st, const GenDev& gp, float* logits, con
 void constrain_rows_host(const int* constrain_tab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts,
                          const int* hist, const int* hist_offsets);
 
+// ---- automaton-constrained decoding (include/fwamd.h: fw_automaton; kernel and table compiler: dec_automaton.hip) ----
+// The compiled table, 32-bit words: a header {S states, E edges, n_vocab, stage_min}, then one RECORD per state, state 0's
+// first, in state order:
+//   {n out-edges, accepting (0 / 1), n pairs (token, offset of the target state's record in this table)}
+// the pairs by ascending token, and AUTOMATON_PAD_WORDS words of -1 behind the last record (two more where that makes the
+// table a whole number of 16-byte groups: automaton_table_words).  A state IS its record's
+// offset: a transition reads one record and needs no second table.  Header, records and pairs all start at even offsets
+// (a pair is one 8-byte load), and 64 lanes may load 64 pairs from the first pair of ANY 64-pair chunk of any record
+// without leaving the table: that is what the padding is for.  stage_min: the kernel stages the table in LDS for a row
+// whose text history has at least that many ids, and walks it where it lies otherwise (automaton_stage_min: a function
+// of the table's size alone, so equal automata still give equal bytes).
+constexpr int AUTOMATON_HDR_WORDS = 4;
+constexpr int AUTOMATON_PAD_WORDS = 128;
+static __host__ __device__ inline int automaton_table_words(int n_states, int n_edges) {
+  return (AUTOMATON_HDR_WORDS + 2 * (n_states + n_edges) + AUTOMATON_PAD_WORDS + 3) & ~3;
+}
+constexpr int AUTOMATON_TABLE_MAX_WORDS =
+    AUTOMATON_HDR_WORDS + 2 * FW_AUTOMATON_MAX_STATES + 2 * FW_AUTOMATON_MAX_EDGES + AUTOMATON_PAD_WORDS;
+static_assert(AUTOMATON_TABLE_MAX_WORDS % 4 == 0, "the largest table is a whole number of 16-byte groups");
+// the kernel's two LDS allocations (GenDev::automaton = 1 / 2): tables of up to AUTOMATON_LDS_SMALL_WORDS words take the
+// small one, which leaves room for three workgroups per CU; the large one holds every table, one workgroup per CU
+constexpr int AUTOMATON_LDS_SMALL_WORDS = 8192;
+static inline int automaton_lds_class(size_t table_words) { return table_words <= (size_t)AUTOMATON_LDS_SMALL_WORDS ? 1 : 2; }
+// the longest history the kernel compacts (its LDS buffer): the launchers refuse a longer text context
+constexpr int AUTOMATON_MAX_HIST = 1024;
+// THE staging rule ("Automaton-constrained decoding", has the measurements behind it)
+int automaton_stage_min(size_t table_words);
+// dec_automaton_kernel, decode-step form, behind launch_boost_step and in front of launch_logits_process, in
+// launch_constrain_step's place and with its row addressing and its contract: every text id (< gp.ts_begin) that labels no
+// out-edge of the state the row's text history leads to becomes -inf, gp.eot included unless that state accepts; a history
+// that leaves the language keeps no text id; the timestamp ids become -inf unless gp.with_ts; every other value keeps its
+// bits, nothing is read.  Reads gp.V, K, R, n_text_ctx, eot, ts_begin, with_ts and gp.automaton (the LDS allocation: the
+// table must fit it).  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS and n_text_ctx <=
+// AUTOMATON_MAX_HIST: the callers check.
+void launch_automaton_step(hipStream_t st, const GenDev& gp, float* logits, const int* automaton_tab, const int* hist2,
+                           const int* d_step, const int* done);
+// ... score form, in front of launch_score, as launch_constrain_score
+void launch_automaton_score(hipStream_t st, const GenDev& gp, float* logits, const int* automaton_tab, const ScoreRow* tab,
+                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// the same walk in plain C++ (fw_test_automaton_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void automaton_rows_host(const int* automaton_tab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts,
+                         const int* hist, const int* hist_offsets);
+// one transition in plain C++: the record offset behind the edge of record `rec` that `token` labels, -1 without one
+int automaton_next_host(const int* automaton_tab, int rec, int token);
+
 }  // namespace fwd
 
-// What fw_boost and fw_constraint share: the list's vocabulary size and its compiled table (above).  An empty list (first
-// header word 0) is no list, and a decode run walks ONE table per kind: the rules the decode path asks of either kind
-// are stated once here.
+// What fw_boost, fw_constraint and fw_automaton share: the vocabulary size and the compiled table (above).  An empty list
+// (first header word 0; an automaton has a state at least) is no list, and a decode run walks ONE table per kind: the
+// rules the decode path asks of either kind are stated once here.
 struct fw_phrase_table {
   int32_t n_vocab;
   std::vector<int32_t> table;
@@ -364,3 +454,6 @@ struct fw_boost : fw_phrase_table {};
 struct fw_constraint : fw_phrase_table {
   std::vector<int32_t> first;
 };
+
+// what fw_automaton_create returns: a third kind of phrase table
+struct fw_automaton : fw_phrase_table {};

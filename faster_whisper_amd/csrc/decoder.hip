@@ -107,6 +107,8 @@ struct GenWorkspace {
   // constrained decoding (fw_generate_constrain): the run's compiled table, held the same way (allocated once, by the first
   // constrained run, at fwd::CONSTRAIN_TABLE_MAX_WORDS)
   GrowBuf<int> constrain_tab;
+  // automaton-constrained decoding (fw_generate_automaton): likewise, at fwd::AUTOMATON_TABLE_MAX_WORDS
+  GrowBuf<int> automaton_tab;
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -590,6 +592,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
     // then the constraint: what the list does not allow is -inf before the rules look
     if (gp.constrain) fwd::launch_constrain_step(st, gp, g->logits, g->constrain_tab.p, g->hist2, g->d_step, g->done);
+    // or the automaton, in the same place (no call carries both)
+    if (gp.automaton) fwd::launch_automaton_step(st, gp, g->logits, g->automaton_tab.p, g->hist2, g->d_step, g->done);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
                                alt ? g->alt_lp.p : nullptr, gp.trunc ? g->trunc_tab : nullptr);
@@ -721,6 +725,7 @@ struct GenRequest {
   float* out_end_alt_logprobs = nullptr;
   const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
   const fw_constraint* constraint = nullptr;   // a non-empty constraint list | null (likewise)
+  const fw_automaton* automaton = nullptr;     // an automaton | null; never beside a constraint list
   // truncated sampling (fw_generate_trunc): the limits on this call's draws, (0, 1) = none.  Like temperature and seed they
   // need NOT agree between the calls of a run: every row reads its call's from the run's TruncRow table.
   int top_k = 0;
@@ -751,10 +756,13 @@ static int32_t phrase_table_to_lane(GrowBuf<int>& dst, const fw_phrase_table& t,
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
 // BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
-// CONSTRAINT LISTS (fw_generate_constrain) likewise.
+// CONSTRAINT LISTS (fw_generate_constrain) likewise, and AUTOMATA (fw_generate_automaton): an automaton call shares a run
+// with neither a plain nor a list-constrained call.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
-  if (!fwd::phrase_table_same(a.boost, b.boost) || !fwd::phrase_table_same(a.constraint, b.constraint)) return false;
+  if (!fwd::phrase_table_same(a.boost, b.boost) || !fwd::phrase_table_same(a.constraint, b.constraint) ||
+      !fwd::phrase_table_same(a.automaton, b.automaton))
+    return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -895,6 +903,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.n_alt = n_alt;
   gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
   gp.constrain = r0.constraint ? 1 : 0;   // (likewise)
+  gp.automaton = r0.automaton ? fwd::automaton_lds_class(r0.automaton->table.size()) : 0;   // (likewise; 1 / 2: the kernel's LDS)
   gp.trunc = (sampling && trunc) ? 1 : 0;   // (a run without a truncating call: today's kernels and graphs)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
@@ -973,6 +982,9 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
     if (int rc = phrase_table_to_lane(g->boost_tab, *reqs[0]->boost, fwd::BOOST_TABLE_MAX_WORDS, "boost", st)) return rc;
   if (pl.gp.constrain)
     if (int rc = phrase_table_to_lane(g->constrain_tab, *reqs[0]->constraint, fwd::CONSTRAIN_TABLE_MAX_WORDS, "constraint", st))
+      return rc;
+  if (pl.gp.automaton)
+    if (int rc = phrase_table_to_lane(g->automaton_tab, *reqs[0]->automaton, fwd::AUTOMATON_TABLE_MAX_WORDS, "automaton", st))
       return rc;
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
@@ -1428,6 +1440,46 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
                                out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
 }
 
+// the model's vocabulary layout, as the two pre-pass kernels that hold a keep mask take it
+static int32_t keep_mask_geometry_check(const fw_config& c, const char* what) {
+  FW_CHECK_ARG(c.tok_eot >= 0 && c.tok_eot < c.tok_timestamp_begin && c.tok_timestamp_begin <= c.n_vocab &&
+                   c.n_vocab <= LP_SUP_WORDS * 64,
+               "this model's vocabulary layout (<eot> %d, first timestamp %d, %d ids) is not one the %s kernel takes",
+               c.tok_eot, c.tok_timestamp_begin, c.n_vocab, what);
+  return FW_OK;
+}
+
+// What fw_generate_automaton and fw_score_automaton refuse (include/fwamd.h), for the reasons constraint_check (below)
+// gives: an automaton for another vocabulary, and rules under which an accepted string cannot be reached or a row is left
+// without a live id.  States are named by their number, as the caller numbered them (records are in state order).
+static int32_t automaton_check(const fw_automaton* at, const fw_config& c, const fw_gen_opts* o, bool check_min_new) {
+  FW_CHECK_ARG(at->n_vocab == c.n_vocab, "the automaton was built for a vocabulary of %d ids, the model has %d", at->n_vocab,
+               c.n_vocab);
+  if (int rc = keep_mask_geometry_check(c, "automaton")) return rc;
+  FW_CHECK_ARG(c.n_text_ctx <= fwd::AUTOMATON_MAX_HIST, "a text context of %d positions is more than the automaton kernel's %d",
+               c.n_text_ctx, fwd::AUTOMATON_MAX_HIST);
+  FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "an automaton does not go with no_repeat_ngram_size %d: an accepted string "
+               "that repeats an n-gram would be unreachable", o->no_repeat_ngram_size);
+  FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "an automaton does not go with min_new_tokens %d: a row in an "
+               "accepting state without out-edges would have no live id", o->min_new_tokens);
+  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
+  const int32_t* tab = at->table.data();
+  int rec = fwd::AUTOMATON_HDR_WORDS;
+  for (int s = 0; s < tab[0]; rec += 2 + 2 * tab[rec], ++s)
+    for (int i = 0; i < tab[rec]; ++i) {
+      const int t = tab[rec + 2 + 2 * i];
+      FW_CHECK_ARG(t < c.tok_eot, "automaton state %d has an edge with id %d: edges are text, ids below <eot> = %d", s, t,
+                   c.tok_eot);
+      FW_CHECK_ARG(!((mask[t >> 6] >> (t & 63)) & 1ull), "automaton state %d has an edge with id %d, which the suppress list "
+                   "forbids", s, t);
+      if (s == 0 && o->suppress_blank)
+        for (int k = 0; k < c.n_suppress_begin; ++k)
+          FW_CHECK_ARG(t != c.suppress_begin[k], "automaton state 0 has an edge with id %d, which suppress_blank forbids at "
+                       "the first step", t);
+    }
+  return FW_OK;
+}
+
 // What fw_generate_constrain and fw_score_constrain refuse (include/fwamd.h): a list for another vocabulary, and rules
 // under which a listed phrase cannot be reached or a row is left without a live id.  `o`: the call's options / the scoring
 // rules; check_min_new: generate only (scoring does not read min_new_tokens).
@@ -1435,10 +1487,7 @@ static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, con
   FW_CHECK_ARG(ct->n_vocab == c.n_vocab, "the constraint list was built for a vocabulary of %d ids, the model has %d",
                ct->n_vocab, c.n_vocab);
   if (!fwd::phrase_list_live(ct)) return FW_OK;   // (an empty list: no constraint, nothing to refuse)
-  FW_CHECK_ARG(c.tok_eot >= 0 && c.tok_eot < c.tok_timestamp_begin && c.tok_timestamp_begin <= c.n_vocab &&
-                   c.n_vocab <= LP_SUP_WORDS * 64,
-               "this model's vocabulary layout (<eot> %d, first timestamp %d, %d ids) is not one the constraint kernel takes",
-               c.tok_eot, c.tok_timestamp_begin, c.n_vocab);
+  if (int rc = keep_mask_geometry_check(c, "constraint")) return rc;
   FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "a constraint list does not go with no_repeat_ngram_size %d: a listed phrase "
                "that repeats an n-gram would be unreachable", o->no_repeat_ngram_size);
   FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "a constraint list does not go with min_new_tokens %d: a row "
@@ -1460,12 +1509,43 @@ static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, con
   return FW_OK;
 }
 
+// One generate call with every extra the entry points know: at most one of `constraint` and `automaton` is given (each
+// entry point takes one of them).
+static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                             int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt, const fw_boost* boost,
+                             const fw_constraint* constraint, const fw_automaton* automaton, int32_t* out_ids,
+                             int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
+                             float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                             float* out_end_alt_logprobs);
+
 int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                               int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt,
                               const fw_boost* boost, const fw_constraint* constraint, int32_t* out_ids, int32_t* out_lens,
                               float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
                               int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
                               float* out_end_alt_logprobs) {
+  return generate_call(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, constraint, nullptr, out_ids,
+                       out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
+                       out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
+}
+
+int32_t fw_generate_automaton(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                              int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt,
+                              const fw_boost* boost, const fw_automaton* automaton, int32_t* out_ids, int32_t* out_lens,
+                              float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
+                              int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                              float* out_end_alt_logprobs) {
+  return generate_call(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, nullptr, automaton, out_ids,
+                       out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
+                       out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
+}
+
+static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                             int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt, const fw_boost* boost,
+                             const fw_constraint* constraint, const fw_automaton* automaton, int32_t* out_ids,
+                             int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
+                             float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                             float* out_end_alt_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
@@ -1486,6 +1566,8 @@ int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_
                boost ? boost->n_vocab : 0, c.n_vocab);
   if (constraint)
     if (int rc = constraint_check(constraint, c, o, true)) return rc;
+  if (automaton)
+    if (int rc = automaton_check(automaton, c, o, true)) return rc;
   const int K = o->beam_size;
   FW_CHECK_ARG(K >= 1 && K <= dm->max_beam, "beam_size %d not in [1, max_beam=%d]", K, dm->max_beam);
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
@@ -1538,6 +1620,7 @@ int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_
   req.top_k = top_k; req.top_p = top_p;
   req.boost = fwd::phrase_list_live(boost) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
   req.constraint = fwd::phrase_list_live(constraint) ? constraint : nullptr;   // (likewise)
+  req.automaton = automaton;
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -1907,14 +1990,39 @@ extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const in
 
 // fw_score with a boost list and / or a constraint list: dec_boost_kernel, then dec_constrain_kernel, on the block's logits
 // (recomputed per block) in front of the scoring kernel
+static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                          const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
+                          const fw_boost* boost, const fw_constraint* constraint, const fw_automaton* automaton,
+                          float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
+
 extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts,
                                       const int32_t* prompt_offsets, const int32_t* targets, const int32_t* target_offsets,
                                       int32_t B, int32_t H, const fw_gen_opts* rules, const fw_boost* boost,
                                       const fw_constraint* constraint, float* out_token_logprobs, int32_t* out_best_ids,
                                       float* out_best_logprobs) {
+  return score_call(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, constraint, nullptr,
+                    out_token_logprobs, out_best_ids, out_best_logprobs);
+}
+
+// ... or an automaton in the list's place: dec_automaton_kernel where dec_constrain_kernel would run
+extern "C" int32_t fw_score_automaton(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts,
+                                      const int32_t* prompt_offsets, const int32_t* targets, const int32_t* target_offsets,
+                                      int32_t B, int32_t H, const fw_gen_opts* rules, const fw_boost* boost,
+                                      const fw_automaton* automaton, float* out_token_logprobs, int32_t* out_best_ids,
+                                      float* out_best_logprobs) {
+  return score_call(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, nullptr, automaton,
+                    out_token_logprobs, out_best_ids, out_best_logprobs);
+}
+
+// (at most one of `constraint` and `automaton`: each entry point takes one of them)
+static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                          const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
+                          const fw_boost* boost, const fw_constraint* constraint, const fw_automaton* automaton,
+                          float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs) {
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
   FW_CHECK_ARG(!boost || rules, "a boost list needs rules: the boost is the first step of the decoding rules");
   FW_CHECK_ARG(!constraint || rules, "a constraint list needs rules: the constraint is a step of the decoding rules");
+  FW_CHECK_ARG(!automaton || rules, "an automaton needs rules: the automaton is a step of the decoding rules");
   FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
   Model* m = decoder_of(&fm->impl);
   const Tensor* enc = &enc_t->impl;
@@ -1926,6 +2034,8 @@ extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, cons
                boost ? boost->n_vocab : 0, c.n_vocab);
   if (constraint)
     if (int crc = constraint_check(constraint, c, rules, false)) return crc;
+  if (automaton)
+    if (int arc = automaton_check(automaton, c, rules, false)) return arc;
   if (!fwd::phrase_list_live(boost)) boost = nullptr;   // (an empty list does nothing)
   if (!fwd::phrase_list_live(constraint)) constraint = nullptr;
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
@@ -2005,8 +2115,10 @@ extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, cons
       (rc = tmp.alloc(&lp_dev, n_out)))
     return rc;
   if (out_best_ids && ((rc = tmp.alloc(&bid_dev, n_out)) || (rc = tmp.alloc(&blp_dev, n_out)))) return rc;
-  int *boost_dev = nullptr, *constrain_dev = nullptr;
-  const std::pair<const fw_phrase_table*, int**> lists[] = {{boost, &boost_dev}, {constraint, &constrain_dev}};
+  int *boost_dev = nullptr, *constrain_dev = nullptr, *automaton_dev = nullptr;
+  const std::pair<const fw_phrase_table*, int**> lists[] = {
+      {boost, &boost_dev}, {constraint, &constrain_dev}, {automaton, &automaton_dev}};
+  if (automaton) gp.automaton = fwd::automaton_lds_class(automaton->table.size());
   for (const auto& [list, dev] : lists) {   // (null: no list of that kind, its pre-pass is not launched)
     if (!list) continue;
     if ((rc = tmp.alloc(dev, list->table.size()))) return rc;
@@ -2033,6 +2145,8 @@ extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, cons
         if (boost_dev) fwd::launch_boost_score(st, gp, g->logits, boost_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         if (constrain_dev)
           fwd::launch_constrain_score(st, gp, g->logits, constrain_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
+        if (automaton_dev)
+          fwd::launch_automaton_score(st, gp, g->logits, automaton_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         fwd::launch_score(st, gp, rules != nullptr, g->logits, g->sup_bits, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev, lp_dev,
                           bid_dev, blp_dev);
       });

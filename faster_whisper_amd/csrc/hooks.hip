@@ -1151,14 +1151,16 @@ static int32_t boost_hist_check(int32_t rows, const int32_t* hist, const int32_t
   return FW_OK;
 }
 
-// What fw_test_boost_rows and fw_test_constrain_rows do alike: ONE launch of a pre-pass kernel in either row form
-// (include/fwamd_test.h) over `rows` rows of gp.V logits.  gp holds what the kernel reads beyond the rows (the callers have
-// checked it and the list); B, K and R are set here.  Everything is checked before anything is allocated or launched.
+// What fw_test_boost_rows, fw_test_constrain_rows and fw_test_automaton_rows do alike: ONE launch of a pre-pass kernel in
+// either row form (include/fwamd_test.h) over `rows` rows of gp.V logits.  gp holds what the kernel reads beyond the rows
+// (the callers have checked it and the list); B, K and R are set here.  Everything is checked before anything is allocated
+// or launched.  us_out != null: `iters` more launches on the same buffers, timed between two events after three untimed
+// ones (a pre-pass kernel that only writes -inf gives the same rows however often it runs); *us_out = microseconds per launch.
 using PrepassStep = void (*)(hipStream_t, const GenDev&, float*, const int*, const int*, const int*, const int*);
 using PrepassScore = void (*)(hipStream_t, const GenDev&, float*, const int*, const fwd::ScoreRow*, int, int, int, int, const int*);
 static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                             int32_t K, const int32_t* done, int32_t form, const std::vector<int32_t>& table,
-                            PrepassStep launch_step, PrepassScore launch_score) {
+                            PrepassStep launch_step, PrepassScore launch_score, int iters = 0, float* us_out = nullptr) {
   FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
   if (int rc = boost_hist_check(rows, hist, hist_offsets, gp.n_text_ctx, gp.V)) return rc;
   const int n0 = hist_offsets[1];
@@ -1188,6 +1190,12 @@ static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, co
         (rc = db.upload(&d_done, dn.data(), dn.size())))
       return rc;
     launch_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
+    if (us_out) {
+      float ms = 0.f;
+      const auto again = [&](int) { launch_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done); return 0; };
+      if ((rc = time_launches(nullptr, 3, iters, again, &ms))) return rc;
+      *us_out = 1000.f * ms / (float)iters;
+    }
   } else {
     std::vector<fwd::ScoreRow> tab((size_t)rows);
     for (int r = 0; r < rows; ++r)
@@ -1200,6 +1208,12 @@ static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, co
         (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
       return rc;
     launch_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
+    if (us_out) {
+      float ms = 0.f;
+      const auto again = [&](int) { launch_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist); return 0; };
+      if ((rc = time_launches(nullptr, 3, iters, again, &ms))) return rc;
+      *us_out = 1000.f * ms / (float)iters;
+    }
   }
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
@@ -1274,6 +1288,60 @@ int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, 
   FW_CHECK_ARG(constraint && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
   *out_words = (int32_t)constraint->table.size();
   std::copy(constraint->table.begin(), constraint->table.begin() + std::min<size_t>((size_t)cap, constraint->table.size()), out);
+  return FW_OK;
+}
+
+// what the automaton hooks check of the caller's vocabulary geometry and automaton
+static int32_t automaton_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, int32_t with_timestamps,
+                                    const fw_automaton* at) {
+  FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
+               "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
+  FW_CHECK_ARG(with_timestamps == 0 || with_timestamps == 1, "with_timestamps %d is not 0 / 1", with_timestamps);
+  FW_CHECK_ARG(at->n_vocab == n_vocab, "the automaton was built for a vocabulary of %d ids, not %d", at->n_vocab, n_vocab);
+  return FW_OK;
+}
+
+// The model gives the device and the text context (the stride of the step form's histories) only.
+int32_t fw_test_automaton_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                               int32_t tok_ts_begin, int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                               int32_t K, const int32_t* done, int32_t form, const fw_automaton* automaton, int32_t staging,
+                               int32_t iters, float* us_out) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && automaton && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  FW_CHECK_ARG(staging >= 0 && staging <= 2, "staging %d is not 0 (the product's rule) / 1 (walk in L2) / 2 (stage in LDS)", staging);
+  FW_CHECK_ARG(!us_out || (iters >= 1 && iters <= 10000), "%d timed launches not in [1, 10000]", iters);
+  if (int rc = automaton_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton)) return rc;
+  FW_CHECK_ARG(fm->impl.cfg.n_text_ctx <= fwd::AUTOMATON_MAX_HIST, "text context of %d positions", fm->impl.cfg.n_text_ctx);
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1;
+  gp.automaton = fwd::automaton_lds_class(automaton->table.size());
+  gp.eot = tok_eot; gp.ts_begin = tok_ts_begin; gp.with_ts = with_timestamps;
+  std::vector<int32_t> table = automaton->table;   // (a copy: a forced staging is its header word 3)
+  if (staging == 1) table[3] = INT32_MAX;
+  if (staging == 2) table[3] = 0;
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, table, fwd::launch_automaton_step,
+                      fwd::launch_automaton_score, iters, us_out);
+}
+
+// the same table walked on the host: no device, no model
+int32_t fw_test_automaton_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                    int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                                    const fw_automaton* automaton) {
+  FW_CHECK_ARG(logits && hist_offsets && automaton && rows >= 1, "bad arguments");
+  if (int rc = automaton_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton)) return rc;
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
+  const int zero = 0;
+  fwd::automaton_rows_host(automaton->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
+                           hist ? hist : &zero, hist_offsets);
+  return FW_OK;
+}
+
+// the compiled table of an automaton, as fw_test_constraint_table
+int32_t fw_test_automaton_table(const fw_automaton* automaton, int32_t* out, int32_t cap, int32_t* out_words) {
+  FW_CHECK_ARG(automaton && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
+  *out_words = (int32_t)automaton->table.size();
+  std::copy(automaton->table.begin(), automaton->table.begin() + std::min<size_t>((size_t)cap, automaton->table.size()), out);
   return FW_OK;
 }
 

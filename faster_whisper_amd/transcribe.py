@@ -182,15 +182,28 @@ def _check_constraint_arguments(allowed_phrases) -> None:
         raise ValueError("allowed_phrases must be a sequence of strings, one per phrase")
 
 
+def _check_grammar_arguments(allowed_grammar, allowed_phrases) -> None:
+    """allowed_grammar: None, or a grammar.Grammar, and then without allowed_phrases (ValueError)"""
+    if allowed_grammar is None:
+        return
+    from .grammar import Grammar
+    if not isinstance(allowed_grammar, Grammar):
+        raise ValueError("allowed_grammar must be a faster_whisper_amd.grammar.Grammar")
+    if allowed_phrases is not None:
+        raise ValueError("allowed_grammar and allowed_phrases exclude each other: a decode takes one constraint "
+                         "(Grammar.phrases(allowed_phrases) is the list as a grammar)")
+
+
 @dataclass(frozen=True)
 class DecodeExtras:
     """What a transcription call asks of its decodes beyond the reference's options, carried as ONE value from the entry
-    point to model.generate.  boost / constraint: the call's built lists (boost_list_for / constraint_list_for), the same
-    objects for every window, attempt, batch and recording."""
+    point to model.generate.  boost / constraint / automaton: the call's built lists and automaton (boost_list_for /
+    constraint_list_for / automaton_for), the same objects for every window, attempt, batch and recording."""
     token_logprobs: bool = False
     token_alternatives: int = 0
     boost: object = None
     constraint: object = None
+    automaton: object = None
     sampling_top_k: int = 0
     sampling_top_p: float = 1.0
 
@@ -207,6 +220,8 @@ class DecodeExtras:
             kw["boost"] = self.boost
         if self.constraint is not None:
             kw["constraint"] = self.constraint
+        if self.automaton is not None:
+            kw["automaton"] = self.automaton
         if sampled and self.sampling_top_k:
             kw["top_k"] = int(self.sampling_top_k)
         if sampled and self.sampling_top_p != 1:
@@ -224,11 +239,13 @@ def _decode_extras(model: "WhisperModel", a) -> DecodeExtras:
     language, so any tokenizer of the model gives the same ids."""
     _check_boost_arguments(a["boost_phrases"], a["phrase_boost"])
     _check_constraint_arguments(a["allowed_phrases"])
+    _check_grammar_arguments(a["allowed_grammar"], a["allowed_phrases"])
     _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
-    tokenizer = model.make_tokenizer() if a["boost_phrases"] or a["allowed_phrases"] else None
+    tokenizer = model.make_tokenizer() if a["boost_phrases"] or a["allowed_phrases"] or a["allowed_grammar"] else None
     return DecodeExtras(token_logprobs=a["token_logprobs"], token_alternatives=a["token_alternatives"],
                         boost=model.boost_list_for(a["boost_phrases"], a["phrase_boost"], tokenizer),
                         constraint=model.constraint_list_for(a["allowed_phrases"], tokenizer),
+                        automaton=model.automaton_for(a["allowed_grammar"], tokenizer),
                         sampling_top_k=a["sampling_top_k"], sampling_top_p=a["sampling_top_p"])
 
 
@@ -555,7 +572,7 @@ class WhisperModel:
                    vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
                    token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
                    phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0,
-                   allowed_phrases: Optional[Sequence[str]] = None):
+                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -577,7 +594,9 @@ class WhisperModel:
         the sampling_top_k most likely tokens, then from the nucleus that holds sampling_top_p of their tempered mass
         (include/fwamd.h: fw_generate_trunc).  0 / 1.0 (the defaults): the whole distribution, as the reference samples.
         allowed_phrases (not in the reference): see constraint_list_for — every decoded window is then exactly ONE phrase
-        of the list, in every attempt of the fallback ladder.  Composes with boost_phrases."""
+        of the list, in every attempt of the fallback ladder.  Composes with boost_phrases.
+        allowed_grammar (not in the reference): see automaton_for — a grammar.Grammar in the list's place: every decoded
+        window is then a string of its language.  ValueError together with allowed_phrases."""
         args = dict(locals())               # the call's arguments by name
         return self._transcribe(args, _decode_extras(self, args))
 
@@ -659,7 +678,7 @@ class WhisperModel:
         which recording gets which seed depends on timing.
         boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcription, so the
         windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
-        allowed_phrases: likewise ONE constraint list for every recording.
+        allowed_phrases: likewise ONE constraint list for every recording, and allowed_grammar ONE automaton.
         sampling_top_k / sampling_top_p (not in the reference): transcribe()'s, the same limits for every recording; sampled
         attempts share decode runs whatever their limits.
         An exception in one recording is raised here, after the recordings already started have finished."""
@@ -894,6 +913,18 @@ class WhisperModel:
         if not phrases:
             return None
         return self.model.constraint_list(phrases)
+
+    def automaton_for(self, allowed_grammar, tokenizer: Tokenizer):
+        """The automaton of a transcribe() call (backend.Whisper.automaton), or None without a grammar.  allowed_grammar is
+        a grammar.Grammar; its text phrases are encoded as " " + phrase.strip(), as allowed_phrases are, per slot element.
+        Every generate call of the transcription then returns a string the grammar accepts (its timestamps apart): a
+        sequence of slots, a repeat — "call" + one of 500 names, four to eight digits — where allowed_phrases takes one
+        flat list.  What constraint_list_for says of the decoding options holds here for the ids on the grammar's edges.
+        Built once per call and reused for every window, attempt of the temperature ladder, batch and recording."""
+        _check_grammar_arguments(allowed_grammar, None)
+        if allowed_grammar is None:
+            return None
+        return self.model.automaton(allowed_grammar.bind(tokenizer.encode))
 
     def make_tokenizer(self, task="transcribe", language="en") -> Tokenizer:
         return Tokenizer(self.hf_tokenizer, self.model.config, self.model.is_multilingual, task=task, language=language)
@@ -1167,7 +1198,7 @@ class BatchedInferencePipeline:
                    token_logprobs: bool = False, token_alternatives: int = 0,
                    boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None,
                    sampling_top_k: int = 0, sampling_top_p: float = 1.0,
-                   allowed_phrases: Optional[Sequence[str]] = None):
+                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1183,7 +1214,9 @@ class BatchedInferencePipeline:
         validated here as there (ValueError).  They apply to the temperature > 0 rungs of the fallback ladder only, and the
         batched path decodes every chunk once, without sampling (as the reference's does): here they limit nothing.
         allowed_phrases (not in the reference): see WhisperModel.constraint_list_for — every chunk decodes to exactly one
-        phrase of the list; one list for every batch.  Composes with boost_phrases."""
+        phrase of the list; one list for every batch.  Composes with boost_phrases.
+        allowed_grammar (not in the reference): see WhisperModel.automaton_for — a grammar.Grammar in the list's place;
+        one automaton for every batch.  ValueError together with allowed_phrases."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model

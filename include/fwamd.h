@@ -18,6 +18,8 @@
  *   boost=             (not in the reference: phrase boosting at the logit) -> fw_boost_create, fw_generate_boost, fw_score_boost
  *   constraint=        (not in the reference: decoding restricted to a phrase list) -> fw_constraint_create,
  *                      fw_generate_constrain, fw_score_constrain
+ *   automaton=         (not in the reference: decoding restricted to the language of a token automaton) ->
+ *                      fw_automaton_create, fw_generate_automaton, fw_score_automaton
  *
  * plus the log-mel front end the reference runs in numpy on the host
  * (faster_whisper/feature_extractor.py:198-230, called at
@@ -61,7 +63,8 @@ extern "C" {
  *    likely tokens at every position), fw_boost_create / fw_boost_free / fw_generate_boost / fw_score_boost (phrases made
  *    more likely by a stated amount, at the logit), fw_generate_trunc (top-k / nucleus limits on the sampled draw),
  *    fw_constraint_create / fw_constraint_free / fw_generate_constrain / fw_score_constrain (decoding restricted to a
- *    given phrase list) — new symbols only, each time */
+ *    given phrase list), fw_automaton_create / fw_automaton_free / fw_generate_automaton / fw_score_automaton (decoding
+ *    restricted to the language of a deterministic token automaton) — new symbols only, each time */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -404,8 +407,8 @@ int32_t fw_generate_trunc(fw_model* m, const fw_tensor* enc, const int32_t* prom
  * THE GUARANTEE: take a returned hypothesis with a finite score and remove its timestamp ids.  If it closed on <eot>, what
  * remains is a phrase of the list; if it was cut at the budget, what remains is a prefix of a phrase: a proper one,
  * except where the budget ended on the very step that would have closed a whole phrase with <eot>.
- * OUT OF SCOPE: a SEQUENCE of phrases (a repeat mode needs per-row automaton state or a prefix-free list), grammars, and
- * different lists for the calls of one run (a run walks one table).
+ * OUT OF SCOPE here: a SEQUENCE of phrases, repeats, grammars — those are the automaton's (below) — and different lists
+ * for the calls of one run (a run walks one table).
  * fw_constraint_create is host code: it needs no device and no model.  FW_EINVAL: n_vocab < 1, a null pointer with
  * n_phrases > 0, more than FW_CONSTRAIN_MAX_PHRASES phrases, offsets[0] != 0, a phrase of no token or of more than
  * FW_CONSTRAIN_MAX_LEN, more than FW_CONSTRAIN_MAX_TOKENS tokens in all, an id outside [0, n_vocab).  Duplicate phrases
@@ -437,6 +440,72 @@ void fw_constraint_free(fw_constraint* c);
 int32_t fw_generate_constrain(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
                               int32_t B, const fw_gen_opts* opts, int32_t top_k, float top_p, int32_t n_alt,
                               const fw_boost* boost, const fw_constraint* constraint,
+                              int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                              float* out_token_logprobs, float* out_end_logprobs,
+                              int32_t* out_alt_ids, float* out_alt_logprobs,
+                              int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
+
+/* ---- automaton-constrained decoding: the transcript is a string of a regular language (not in CTranslate2) ----
+ * The constraint list's big sibling: where a list says "exactly one of these phrases", a deterministic token automaton
+ * says "a digit string of 4 to 8 digits", "call + one of 500 names", "one to three items of a menu".  The automaton is
+ * given in CSR form: n_states states, state 0 the start state; the out-edges of state s are entries
+ * edge_offsets[s] .. edge_offsets[s + 1]) of edge_tokens (the id that labels the edge) and edge_targets (the state it
+ * leads to); accepting[s] != 0 marks the states in which the transcript may end.  delta(s, v) is the target of the
+ * out-edge of s labelled v, undefined without one; delta*(s, t) follows a whole string and is undefined as soon as one
+ * step is.  For one logits row let h[0 .. n) be the row's GENERATED history (never the prompt), t[0 .. m) be h without its
+ * ids >= tok_timestamp_begin, and s = delta*(0, t).  What is written, and nothing else — the constraint's contract:
+ *   - every id v < tok_timestamp_begin keeps its bits if s is defined and v labels an out-edge of s, or if v is <eot>
+ *     and s is defined and accepting; otherwise logit[v] = -inf;
+ *   - the ids >= tok_timestamp_begin keep their bits when the timestamp rules are on (no <|notimestamps|> in the prompt);
+ *     with <|notimestamps|> they become -inf;
+ *   - nothing is added to any logit.
+ * If s is undefined (the history has left the language) no text id and no <eot> survive.  In fw_generate_automaton that
+ * arises on dead beam copies only; in scoring it is a target that left the language, which gets -inf from there on.
+ * Order per step: the boost if there is one, then the automaton, then the rules exactly as always.  Token log-probs,
+ * alternatives, scores and sampled draws are those of the constrained, processed distribution, as under a list.
+ * THE GUARANTEE: take a returned hypothesis with a finite score and remove its timestamp ids.  If it closed on <eot>, the
+ * automaton accepts what remains; if it was cut at the budget, what remains is a prefix of an accepted string.
+ * No state is kept between steps: s is a function of the row's history, recomputed by one kernel (dec_automaton.hip) per
+ * step, so beam reordering needs nothing and a merged run gives every caller its solo bits.
+ * OUT OF SCOPE: non-regular grammars, weights on edges, an automaton AND a constraint list in one call (no entry point
+ * takes both), different automata for the calls of one run (a run walks one table).
+ * fw_automaton_create is host code: it needs no device and no model.  FW_EINVAL, the message naming the state and the id:
+ * n_vocab < 1, a null pointer, n_states < 1 or > FW_AUTOMATON_MAX_STATES, more than FW_AUTOMATON_MAX_EDGES edges,
+ * edge_offsets[0] != 0 or offsets that decrease, a state whose tokens are not strictly ascending (what makes the
+ * automaton deterministic), an id outside [0, n_vocab), a target outside [0, n_states), a state that cannot be reached
+ * from state 0, a state from which no accepting state can be reached.  The automaton must be TRIM: that is what keeps a
+ * live row from ever running out of live ids.  It compiles to one int32 table, one record per state; equal arguments give
+ * byte-equal tables. */
+#define FW_AUTOMATON_MAX_STATES 4096
+#define FW_AUTOMATON_MAX_EDGES 8192
+typedef struct fw_automaton fw_automaton;   /* opaque: a validated, compiled automaton (host memory); any number of calls may read it at once */
+int32_t fw_automaton_create(int32_t n_vocab, int32_t n_states, const int32_t* edge_offsets, const int32_t* edge_tokens,
+                            const int32_t* edge_targets, const int32_t* accepting, fw_automaton** out);
+void fw_automaton_free(fw_automaton* a);
+/* fw_generate_trunc plus an automaton: fw_generate_constrain with the automaton in the list's place.  automaton == NULL is
+ * fw_generate_trunc exactly, bit for bit.  FW_EINVAL before anything is queued, each message naming the state and the id:
+ *   - the automaton was built for another n_vocab than the model's;
+ *   - an edge token is >= tok_eot (edges are text);
+ *   - an edge token is in opts' suppress list;
+ *   - opts->suppress_blank is set and an edge of state 0 carries one of the model's suppress_begin ids;
+ *   - opts->no_repeat_ngram_size > 0;
+ *   - opts->min_new_tokens > 0.
+ * The last four would make an accepted string unreachable or leave a row without a live id.
+ * Merging: two calls share a decode run only when both have no automaton or their compiled tables are byte-equal; an
+ * automaton call never shares a run with a plain or a list-constrained one, and every caller gets its solo result bit for
+ * bit.  The table is copied into a buffer of the decode lane at the start of the run (the automaton may be freed once the
+ * call has returned); a run without an automaton launches exactly what it launched before.
+ * COST: one kernel launch per step more, whose time is the walk of the row's text history, one table fetch per id.
+ * Measured on an MI355X, large-v3, kernel time: for the constraint's full list (128 phrases x 32 ids) as a grammar, 22.5 us
+ * per step at 80 rows averaged over the 32 steps (14 us at an empty history, 31 us at 31 ids) where dec_constrain_kernel
+ * takes 15.7 us, and 54 us against 31.5 us at 640 rows: 1.4 x / 1.7 x the list kernel - a plain phrase list is cheaper
+ * as a list.  Long histories (eager launches, event timing): about 0.16 us per id with the table staged in LDS (0.27 us
+ * walked in L2: short histories, the kernel picks per row), 87 us at 447 ids on a table at both limits, 263 us at a full
+ * lane of 640 rows.  That worst case is a
+ * noticeable share of a decode step (about 3 % at 80 rows); histories of a few dozen ids stay below 1 %. */
+int32_t fw_generate_automaton(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                              int32_t B, const fw_gen_opts* opts, int32_t top_k, float top_p, int32_t n_alt,
+                              const fw_boost* boost, const fw_automaton* automaton,
                               int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
                               float* out_token_logprobs, float* out_end_logprobs,
                               int32_t* out_alt_ids, float* out_alt_logprobs,
@@ -485,6 +554,17 @@ int32_t fw_score_boost(fw_model* m, const fw_tensor* enc, const int32_t* prompts
 int32_t fw_score_constrain(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
                            const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
                            const fw_gen_opts* rules, const fw_boost* boost, const fw_constraint* constraint,
+                           float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
+
+/* fw_score_boost plus an automaton (automaton-constrained decoding, above): fw_score_constrain with the automaton in the
+ * list's place.  automaton == NULL is fw_score_boost exactly; otherwise rules != NULL is needed, and the checks of
+ * fw_generate_automaton run against the rules' fields (FW_EINVAL; min_new_tokens is not read by scoring and not checked).
+ * A target sequence that leaves the language at position q scores finite before q and -inf from q on, its <eot> entry
+ * included.  For a greedy hypothesis of fw_generate_automaton it returns out_token_logprobs and out_end_logprobs bit for
+ * bit, and out_best_ids / out_best_logprobs are its alternative 0. */
+int32_t fw_score_automaton(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                           const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                           const fw_gen_opts* rules, const fw_boost* boost, const fw_automaton* automaton,
                            float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
 
 /* ---- detect_language -------------------------------------------------------

@@ -201,6 +201,22 @@ int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab
 /* host-only: the compiled table of a list (what the merge rule compares).  *out_words = its size in 32-bit words; out
  * (NULL with cap == 0) receives the first min(cap, size) words */
 int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, int32_t cap, int32_t* out_words);
+/* ONE launch of dec_automaton_kernel (automaton-constrained decoding, include/fwamd.h) in either row form, with the
+ * arguments and the checks of fw_test_constrain_rows above and an automaton in the list's place (its edge ids are NOT
+ * checked against tok_eot: an id >= tok_ts_begin on an edge allows nothing).  staging: 0 the product's rule (the stage_min
+ * in the table's header), 1 every row walks the table where it lies (L2), 2 every row stages it in LDS first — the same
+ * bits all three.  us_out != NULL: after the launch whose rows are returned, `iters` (1 .. 10000) more on the same buffers
+ * between two events; *us_out = microseconds per launch. */
+int32_t fw_test_automaton_rows(fw_model* m, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                               int32_t tok_ts_begin, int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                               int32_t K, const int32_t* done, int32_t form, const fw_automaton* automaton, int32_t staging,
+                               int32_t iters, float* us_out);
+/* host-only (no device, no model needed): the same table walked in plain C++, ragged histories of any length */
+int32_t fw_test_automaton_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                    int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
+                                    const fw_automaton* automaton);
+/* host-only: the compiled table of an automaton (what the merge rule compares), as fw_test_constraint_table */
+int32_t fw_test_automaton_table(const fw_automaton* automaton, int32_t* out, int32_t cap, int32_t* out_words);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
