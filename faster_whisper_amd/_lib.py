@@ -98,6 +98,8 @@ SYMBOLS = [
     "fw_test_constrain_rows", "fw_test_constrain_rows_host", "fw_test_constraint_table",
     "fw_automaton_create", "fw_automaton_free", "fw_generate_automaton", "fw_score_automaton",
     "fw_test_automaton_rows", "fw_test_automaton_rows_host", "fw_test_automaton_table",
+    "fw_ngram_create", "fw_ngram_free", "fw_generate_lm", "fw_score_lm",
+    "fw_test_ngram_rows", "fw_test_ngram_rows_host", "fw_test_ngram_table",
 ]
 
 _lib = None
@@ -275,6 +277,18 @@ def load():
         lib.fw_test_automaton_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, i32, f32p]
         lib.fw_test_automaton_rows_host.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
         lib.fw_test_automaton_table.argtypes = [vp, vp, i32, i32p]
+    if hasattr(lib, "fw_ngram_create"):             # (absent from an older build loaded through FWAMD_LIB)
+        f32 = C.c_float
+        lib.fw_ngram_create.argtypes = [i32, i32, i32p, i32p, f32p, f32p, f32, f32, f32, i32, C.POINTER(vp)]
+        lib.fw_ngram_free.argtypes = [vp]
+        lib.fw_ngram_free.restype = None
+        a = lib.fw_generate_constrain.argtypes      # (.. boost, constraint | automaton, lm, outputs ..)
+        lib.fw_generate_lm.argtypes = a[:11] + [vp, vp] + a[11:]
+        a = lib.fw_score_constrain.argtypes
+        lib.fw_score_lm.argtypes = a[:11] + [vp, vp] + a[11:]
+        lib.fw_test_ngram_rows.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, f32p]
+        lib.fw_test_ngram_rows_host.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+        lib.fw_test_ngram_table.argtypes = [vp, vp, i32, i32p]
     if hasattr(lib, "fw_test_blob_check"):          # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_test_blob_check.argtypes = [vp, i64]
     lib.fw_vad_create.argtypes = [C.POINTER(FwVadWeights), C.POINTER(vp)]

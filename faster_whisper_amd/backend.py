@@ -253,6 +253,40 @@ class Automaton:
         return value._handle
 
 
+class NgramFusion:
+    """A validated, compiled n-gram language model with its fusion strength (fwamd.h: fw_ngram_create), built from an
+    ngram.NgramLM: at every step scale * log P(id | the row's last order - 1 text ids) + bonus is added to the logit of every
+    text id and <eot>, behind the boost and in front of the constraint / automaton and the decoding rules.  Host-only: needs
+    no device.  Whisper.ngram_lm builds one for the model's vocabulary; pass it as generate(lm=...) / score(lm=...)."""
+
+    def __init__(self, n_vocab: int, eos_id: int, lm, scale: float, bonus: float = 0.0):
+        lib = _lib.load()
+        if not hasattr(lib, "fw_ngram_create"):   # an older build loaded through FWAMD_LIB
+            raise RuntimeError("this libfwamd.so has no fw_ngram_create: language-model fusion needs a current build")
+        counts, ids, lp, bo = lm.arrays(n_vocab, eos_id)
+        self.n_vocab, self.lm, self.scale, self.bonus = int(n_vocab), lm, float(scale), float(bonus)
+        self._handle = C.c_void_p()
+        _lib.check(lib.fw_ngram_create(self.n_vocab, lm.order, _lib.as_i32p(counts), _lib.as_i32p(ids), _lib.as_f32p(lp),
+                                       _lib.as_f32p(bo), float(lm.unk_logprob), self.scale, self.bonus, int(eos_id),
+                                       C.byref(self._handle)))
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            try:
+                _lib.load().fw_ngram_free(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    @staticmethod
+    def _handle_of(value):
+        if value is None:
+            return None
+        if not isinstance(value, NgramFusion):
+            raise TypeError("lm must be an NgramFusion (Whisper.ngram_lm) or None")
+        return value._handle
+
+
 def _require_symbols(lib, needs) -> None:
     """needs: (used, symbol, what it serves) in the order the features were added.  A build loaded through FWAMD_LIB that
     lacks the symbol of a feature the call uses cannot serve the call (RuntimeError)."""
@@ -261,7 +295,7 @@ def _require_symbols(lib, needs) -> None:
             raise RuntimeError(f"this libfwamd.so has no {symbol}: {what} a current build")
 
 
-def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, constraint_h, automaton_h=None):
+def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, constraint_h, automaton_h=None, lm_h=None):
     """The engine entry point of a generate call and its argument list: the OLDEST symbol that can express the call, so a
     build that lacks newer ones still serves every call it can.  head: (model, encoder output, prompts, offsets, B, options);
     outs: (ids, lens, scores, no-speech probabilities); lp: the two log-prob arrays, alt: the four alternative arrays
@@ -271,9 +305,12 @@ def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, const
     _require_symbols(lib, ((boost_h is not None, "fw_generate_boost", "phrase boosting needs"),
                            (constraint_h is not None, "fw_generate_constrain", "constrained decoding needs"),
                            (automaton_h is not None, "fw_generate_automaton", "automaton-constrained decoding needs"),
+                           (lm_h is not None, "fw_generate_lm", "language-model fusion needs"),
                            (trunc, "fw_generate_trunc", "top_k / top_p need"),
                            (n_alt, "fw_generate_alt", "per-token log-probabilities and alternatives need"),
                            (want_lp, "fw_generate_lp", "per-token log-probabilities need")))
+    if lm_h is not None:
+        return lib.fw_generate_lm, (*head, top_k, top_p, n_alt, boost_h, constraint_h, automaton_h, lm_h, *outs, *lp, *alt)
     if automaton_h is not None:   # (never beside a constraint list: generate() refuses the pair)
         return lib.fw_generate_automaton, (*head, top_k, top_p, n_alt, boost_h, automaton_h, *outs, *lp, *alt)
     if constraint_h is not None:
@@ -289,12 +326,15 @@ def _generate_call(lib, head, outs, lp, alt, n_alt, top_k, top_p, boost_h, const
     return lib.fw_generate, (*head, *outs)
 
 
-def _score_call(lib, head, outs, boost_h, constraint_h, automaton_h=None):
+def _score_call(lib, head, outs, boost_h, constraint_h, automaton_h=None, lm_h=None):
     """as _generate_call, for score().  head: (model, encoder output, prompts, offsets, targets, offsets, B, H, rules)"""
     _require_symbols(lib, ((True, "fw_score", "scoring needs"),
                            (boost_h is not None, "fw_score_boost", "phrase boosting needs"),
                            (constraint_h is not None, "fw_score_constrain", "constrained decoding needs"),
-                           (automaton_h is not None, "fw_score_automaton", "automaton-constrained decoding needs")))
+                           (automaton_h is not None, "fw_score_automaton", "automaton-constrained decoding needs"),
+                           (lm_h is not None, "fw_score_lm", "language-model fusion needs")))
+    if lm_h is not None:
+        return lib.fw_score_lm, (*head, boost_h, constraint_h, automaton_h, lm_h, *outs)
     if automaton_h is not None:
         return lib.fw_score_automaton, (*head, boost_h, automaton_h, *outs)
     if constraint_h is not None:
@@ -717,6 +757,14 @@ class Whisper:
         id, ...) is checked by that call, against its own rules."""
         return Automaton(self._cfg.n_vocab, grammar)
 
+    def ngram_lm(self, lm, scale: float, bonus: float = 0.0) -> NgramFusion:
+        """An NgramFusion for this model's vocabulary from an ngram.NgramLM: </s> is the model's <eot>, scale the weight of
+        the model's natural-log probabilities at the logit, bonus the insertion bonus every text id gets (without it the
+        text ids lose ground to the timestamp ids, which receive nothing).  ValueError (fwamd.h: fw_ngram_create): an id
+        outside the vocabulary, a duplicate n-gram, </s> inside a context, a value that is not finite, more than 2^20
+        n-grams of order 2 and above.  An n-gram id above <eot> is refused by the generate / score call."""
+        return NgramFusion(self._cfg.n_vocab, self._cfg.eot, lm, scale, bonus)
+
     # ---- generate -----------------------------------------------------------------------
     def generate(self, features: StorageView, prompts: List[List[int]], *, asynchronous: bool = False,
                  beam_size: int = 5, patience: float = 1, num_hypotheses: int = 1, length_penalty: float = 1,
@@ -728,7 +776,8 @@ class Whisper:
                  seed: Optional[int] = None, return_token_logprobs: bool = False,
                  return_alternatives: int = 0, boost: Optional[BoostList] = None, top_k: int = 0,
                  top_p: float = 1.0, constraint: Optional[ConstraintList] = None,
-                 automaton: Optional[Automaton] = None) -> List[WhisperGenerationResult]:
+                 automaton: Optional[Automaton] = None,
+                 lm: Optional[NgramFusion] = None) -> List[WhisperGenerationResult]:
         """boost (not in CTranslate2): a BoostList (boost_list()) whose phrases are made more likely at the logit, in front
         of the decoding rules; None or an empty list: the call without it.
         top_k / top_p (not in CTranslate2's generate(); fwamd.h: fw_generate_trunc): limits on the draw of a SAMPLING call
@@ -743,11 +792,14 @@ class Whisper:
         min_new_tokens > 0.
         automaton (not in CTranslate2; fwamd.h: fw_generate_automaton): an Automaton (automaton()) in the constraint's
         place — every hypothesis is, its timestamps apart, a string the grammar accepts (or a prefix of one when the budget
-        cut it).  The constraint's order, outputs and ValueErrors, edge ids for phrase ids; not together with constraint."""
+        cut it).  The constraint's order, outputs and ValueErrors, edge ids for phrase ids; not together with constraint.
+        lm (not in CTranslate2; fwamd.h: fw_generate_lm): an NgramFusion (ngram_lm()) — shallow fusion with an n-gram
+        language model, behind the boost and in front of the constraint / automaton; log-probs, alternatives and scores are
+        those of the fused distribution.  ValueError: a model for another vocabulary, an n-gram id above <eot>."""
         if asynchronous or return_logits_vocab:
             raise ValueError("asynchronous / return_logits_vocab are not supported (unused by faster-whisper)")
         boost_h, constraint_h = BoostList._handle_of(boost), ConstraintList._handle_of(constraint)
-        automaton_h = Automaton._handle_of(automaton)
+        automaton_h, lm_h = Automaton._handle_of(automaton), NgramFusion._handle_of(lm)
         if automaton_h is not None and constraint_h is not None:
             raise ValueError("generate() takes a constraint list or an automaton, not both")
         top_k, top_p = int(top_k), float(top_p)
@@ -799,7 +851,8 @@ class Whisper:
             entry, args = _generate_call(
                 self._lib, (enc._owner.handle, enc._handle, _lib.as_i32p(flat), _lib.as_i32p(offs), B, C.byref(o)),
                 (_lib.as_i32p(ids), _lib.as_i32p(lens), _lib.as_f32p(scores), _lib.as_f32p(nsp)), (f32(tlp), f32(elp)),
-                (i32(aid), f32(alp), i32(eid), f32(elps)), n_alt, top_k, top_p, boost_h, constraint_h, automaton_h)
+                (i32(aid), f32(alp), i32(eid), f32(elps)), n_alt, top_k, top_p, boost_h, constraint_h, automaton_h,
+                lm_h)
             _lib.check(entry(*args))
             out = []
             for b in range(B):
@@ -871,7 +924,8 @@ class Whisper:
 
     def score(self, features: StorageView, prompts: List[List[int]], targets, *, rules: bool = False,
               boost: Optional[BoostList] = None, constraint: Optional[ConstraintList] = None,
-              automaton: Optional[Automaton] = None, **rule_kwargs) -> List[WhisperScoringResult]:
+              automaton: Optional[Automaton] = None, lm: Optional[NgramFusion] = None,
+              **rule_kwargs) -> List[WhisperScoringResult]:
         """Teacher-forced log-probs of given transcripts (fwamd.h: fw_score; not in CTranslate2's Whisper class).
         targets[b]: one sequence of ids, or a list of up to max_beam_size sequences, scored against chunk b.
         rules=False: the raw distribution.  rules=True: the distribution generate()'s search ranks by, with generate's
@@ -883,7 +937,8 @@ class Whisper:
         constraint: the ConstraintList of a generate(constraint=...) call, applied behind the boost and in front of the
         rules; needs rules=True.  A target that leaves the list scores -inf from there on.
         automaton: the Automaton of a generate(automaton=...) call, in the constraint's place (not together with it); needs
-        rules=True.  A target that leaves the language scores -inf from there on."""
+        rules=True.  A target that leaves the language scores -inf from there on.
+        lm: the NgramFusion of a generate(lm=...) call, fused behind the boost; needs rules=True."""
         unknown = set(rule_kwargs) - set(self._RULE_DEFAULTS)
         if unknown:
             raise TypeError(f"score() got unexpected keyword arguments {sorted(unknown)}")
@@ -894,7 +949,9 @@ class Whisper:
             raise ValueError("boost needs rules=True: the boost is the first step of the decoding rules")
         if constraint_h is not None and not rules:
             raise ValueError("constraint needs rules=True: the constraint is a step of the decoding rules")
-        automaton_h = Automaton._handle_of(automaton)
+        automaton_h, lm_h = Automaton._handle_of(automaton), NgramFusion._handle_of(lm)
+        if lm_h is not None and not rules:
+            raise ValueError("lm needs rules=True: the fusion is a step of the decoding rules")
         if automaton_h is not None and not rules:
             raise ValueError("automaton needs rules=True: the automaton is a step of the decoding rules")
         if automaton_h is not None and constraint_h is not None:
@@ -935,7 +992,7 @@ class Whisper:
             head = (enc._owner.handle, enc._handle, _lib.as_i32p(pflat), _lib.as_i32p(poffs), _lib.as_i32p(tflat),
                     _lib.as_i32p(toffs), B, H, C.byref(o) if o is not None else None)
             outs = (_lib.as_f32p(lp), _lib.as_i32p(bid), _lib.as_f32p(blp))
-            entry, args = _score_call(self._lib, head, outs, boost_h, constraint_h, automaton_h)
+            entry, args = _score_call(self._lib, head, outs, boost_h, constraint_h, automaton_h, lm_h)
             _lib.check(entry(*args))
             out = []
             for b in range(B):

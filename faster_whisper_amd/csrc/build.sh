@@ -6,7 +6,7 @@ OUT=../libfwamd.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable"
 mkdir -p build
 pids=()
-for f in logmel gemm rowops attn_enc engine decoder dec_kernels dec_vocab dec_trunc dec_boost dec_constrain dec_automaton vad resample hooks; do
+for f in logmel gemm rowops attn_enc engine decoder dec_kernels dec_vocab dec_trunc dec_boost dec_constrain dec_automaton dec_ngram vad resample hooks; do
   if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ kernels.h -nt build/$f.o ] || [ engine.h -nt build/$f.o ] || [ dec_kernels.h -nt build/$f.o ] || [ ../../include/fwamd.h -nt build/$f.o ] || [ ../../include/fwamd_test.h -nt build/$f.o ] || [ vad_model.h -nt build/$f.o ] || [ build.sh -nt build/$f.o ] || { [ $f = dec_trunc ] && [ dec_vocab.hip -nt build/$f.o ]; }; then
     # attn_enc: MFMA accumulators in VGPRs (-amdgpu-mfma-vgpr-form): the softmax reads every score and rescales the output
     # accumulators, which with AGPR accumulators costs 191 v_accvgpr moves per 64-key tile of a vector-bound kernel (548 ->
@@ -19,6 +19,9 @@ for f in logmel gemm rowops attn_enc engine decoder dec_kernels dec_vocab dec_tr
     # the optimiser (16 VGPRs / 42 SGPRs with it, 28 / 62 without; the mask-init loop is not vectorised), so whoever
     # drops it re-runs tests/test_gpu_automaton*.py and profiles/automaton_*.py on the plain build (profiles/NOTES.md).
     if [ $f = dec_automaton ]; then EXTRA="-Xclang -target-feature -Xclang -packed-fp32-ops"; fi
+    # dec_ngram likewise, and here the switch does something: the dense pass adds to four floats at a time, and with it
+    # off those are four v_fma_f32 / v_add_f32 and no v_pk_* — the unit's tests and timings are of this build.
+    if [ $f = dec_ngram ]; then EXTRA="-Xclang -target-feature -Xclang -packed-fp32-ops"; fi
     hipcc $FLAGS $EXTRA -c $f.hip -o build/$f.o &
     pids+=($!)
   fi

@@ -56,6 +56,10 @@ struct GenDev {
   // kernel: 1 = the kernel's small LDS allocation, 2 = its large one (automaton_lds_class: by the table's size, which
   // fixes the launch a step graph captures).  0 in every run without an automaton: the key, the kernels and the graphs of today.
   int automaton;
+  // LM (fw_generate_lm): 1 when the step launches dec_ngram_kernel between the boost and the constraint / automaton.  0 in
+  // every run without a language model: the key, the kernels and the graphs of today.  Order, scale and bonus travel in the
+  // table's header, not here.
+  int lm;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -426,9 +430,51 @@ void automaton_rows_host(const int* automaton_tab, float* logits, int rows, int 
 // one transition in plain C++: the record offset behind the edge of record `rec` that `token` labels, -1 without one
 int automaton_next_host(const int* automaton_tab, int rec, int token);
 
+// ---- n-gram language-model fusion (include/fwamd.h: fw_ngram; kernel, table compiler and host walk: dec_ngram.hip) ----
+// The compiled table, 32-bit words: a header
+//   {order N, nodes, n_vocab, eos_id, bits of scale, bits of bonus, largest id of any n-gram (BOS apart), offset of the root}
+// then the UNIGRAM level, dense: float [eos_id + 1], unk_logprob where an id has no unigram, zero-padded to a whole number
+// of 16-byte groups (every id of every row reads it); then one RECORD per context, the root (the empty context) first.
+// The records are a trie over REVERSED contexts: the child of a node along id w is the context that puts w in FRONT of
+// the node's context, so one walk from the root along the history's last id, the one before it, ... meets the whole
+// back-off chain c_1, c_2, .. c_K in at most N - 1 transitions.  A record:
+//   {n child pairs, n successor pairs, bits of the context's back-off weight, 0,
+//    child pairs (id, offset of the child's record), ascending by id,
+//    successor pairs (id v, bits of p(context, v)), ascending by id}
+// BOS is the id n_vocab, and by that the last child of its node.  A context that exists only as a path to a longer one
+// has back-off 0 and no successors; a context with back-off 0, no successor and no child has no record at all (that is
+// what its absence means).  Every field sits at an even offset (a pair is one 8-byte load), and NGRAM_PAD_WORDS words of
+// -1 behind the last record let 64 lanes load 64 pairs from ANY pair of any record without leaving the table.
+constexpr int NGRAM_HDR_WORDS = 8;
+constexpr int NGRAM_REC_WORDS = 4;
+constexpr int NGRAM_PAD_WORDS = 128;
+static __host__ __device__ inline int ngram_unigram_words(int eos_id) { return (eos_id + 1 + 3) & ~3; }
+static __host__ __device__ inline float ngram_bits_float(int bits) {
+  union { int i; float f; } u;
+  u.i = bits;
+  return u.f;
+}
+// dec_ngram_kernel, decode-step form, behind launch_boost_step and in front of the constraint / automaton: row r of gp.R
+// rows reads its history from the parity half of hist2 that *d_step selects (n = step), rows of chunks with
+// done[r / gp.K] are skipped.  logits [gp.R][gp.V] IN / OUT: logits[r][v] += scale * score(v) + bonus for every id
+// v <= gp.eot (include/fwamd.h states score), each written once; the ids above gp.eot keep their bits.  Reads gp.V, K, R,
+// n_text_ctx, eot, ts_begin.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS, the table's
+// eos_id is gp.eot and none of its ids lies above it: the callers check.
+void launch_ngram_step(hipStream_t st, const GenDev& gp, float* logits, const int* ngram_tab, const int* hist2,
+                       const int* d_step, const int* done);
+// ... score form, in front of launch_score, as launch_boost_score
+void launch_ngram_score(hipStream_t st, const GenDev& gp, float* logits, const int* ngram_tab, const ScoreRow* tab,
+                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// the same walk in plain C++ (fw_test_ngram_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void ngram_rows_host(const int* ngram_tab, float* logits, int rows, int V, int eot, int ts_begin, const int* hist,
+                     const int* hist_offsets);
+// whether a table goes with a vocabulary of V ids whose <eot> is `eot` and whose first timestamp is `ts_begin`: what both
+// launchers ask, what fw_generate_lm / fw_score_lm and the hooks turn into their messages
+bool ngram_geometry_ok(const int* ngram_tab, int V, int eot, int ts_begin);
+
 }  // namespace fwd
 
-// What fw_boost, fw_constraint and fw_automaton share: the vocabulary size and the compiled table (above).  An empty list
+// What fw_boost, fw_constraint, fw_automaton and fw_ngram share: the vocabulary size and the compiled table (above).  An empty list
 // (first header word 0; an automaton has a state at least) is no list, and a decode run walks ONE table per kind: the
 // rules the decode path asks of either kind are stated once here.
 struct fw_phrase_table {
@@ -457,3 +503,6 @@ struct fw_constraint : fw_phrase_table {
 
 // what fw_automaton_create returns: a third kind of phrase table
 struct fw_automaton : fw_phrase_table {};
+
+// what fw_ngram_create returns: a fourth kind (its table is never empty: word 0 is the order)
+struct fw_ngram : fw_phrase_table {};

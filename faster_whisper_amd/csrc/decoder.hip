@@ -109,6 +109,10 @@ struct GenWorkspace {
   GrowBuf<int> constrain_tab;
   // automaton-constrained decoding (fw_generate_automaton): likewise, at fwd::AUTOMATON_TABLE_MAX_WORDS
   GrowBuf<int> automaton_tab;
+  // language-model fusion (fw_generate_lm): the run's compiled table.  It can be megabytes, so it is sized by the largest
+  // model so far (run_lm_ensure) and not by the kind's limit.  A step graph holds the pointer by value: growing the buffer
+  // drops the graphs that fuse.
+  GrowBuf<int> lm_tab;
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -590,6 +594,8 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
     const bool alt = gp.n_alt > 0;   // (run_alt_ensure has sized the buffers for this run)
     // the boost comes first: the rules below see the boosted logits (run_init_state has filled the table for this run)
     if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
+    // then the language model: what is constrained and ranked below is the fused distribution
+    if (gp.lm) fwd::launch_ngram_step(st, gp, g->logits, g->lm_tab.p, g->hist2, g->d_step, g->done);
     // then the constraint: what the list does not allow is -inf before the rules look
     if (gp.constrain) fwd::launch_constrain_step(st, gp, g->logits, g->constrain_tab.p, g->hist2, g->d_step, g->done);
     // or the automaton, in the same place (no call carries both)
@@ -726,6 +732,7 @@ struct GenRequest {
   const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
   const fw_constraint* constraint = nullptr;   // a non-empty constraint list | null (likewise)
   const fw_automaton* automaton = nullptr;     // an automaton | null; never beside a constraint list
+  const fw_ngram* lm = nullptr;                // a language model to fuse | null
   // truncated sampling (fw_generate_trunc): the limits on this call's draws, (0, 1) = none.  Like temperature and seed they
   // need NOT agree between the calls of a run: every row reads its call's from the run's TruncRow table.
   int top_k = 0;
@@ -757,11 +764,12 @@ static int32_t phrase_table_to_lane(GrowBuf<int>& dst, const fw_phrase_table& t,
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
 // BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
 // CONSTRAINT LISTS (fw_generate_constrain) likewise, and AUTOMATA (fw_generate_automaton): an automaton call shares a run
-// with neither a plain nor a list-constrained call.
+// with neither a plain nor a list-constrained call.  LANGUAGE MODELS (fw_generate_lm) likewise: scale and bonus are part
+// of the table.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
   if (!fwd::phrase_table_same(a.boost, b.boost) || !fwd::phrase_table_same(a.constraint, b.constraint) ||
-      !fwd::phrase_table_same(a.automaton, b.automaton))
+      !fwd::phrase_table_same(a.automaton, b.automaton) || !fwd::phrase_table_same(a.lm, b.lm))
     return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
@@ -904,6 +912,7 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
   gp.constrain = r0.constraint ? 1 : 0;   // (likewise)
   gp.automaton = r0.automaton ? fwd::automaton_lds_class(r0.automaton->table.size()) : 0;   // (likewise; 1 / 2: the kernel's LDS)
+  gp.lm = r0.lm ? 1 : 0;   // (likewise)
   gp.trunc = (sampling && trunc) ? 1 : 0;   // (a run without a truncating call: today's kernels and graphs)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
@@ -934,6 +943,18 @@ static int run_alt_ensure(DecodeLane* lane, const RunPlan& pl) {
     if ((rc = g->alt_tok.ensure(n_alt)) || (rc = g->alt_lp.ensure(n_alt)) || (rc = g->fin_path.ensure(n_path))) return rc;
   }
   return FW_OK;
+}
+
+// Language-model fusion: the lane's table buffer holds `words` words, grown by replacement as the alternatives' buffers
+// are (the lane is idle) — the step graphs that fuse hold the old pointer and go with it.  FW_ENOMEM when the device has no
+// room: the calls of the run get it.  Runs without a model allocate nothing and touch nothing here.
+static int lm_table_ensure(DecodeLane* lane, size_t words) {
+  GenWorkspace* g = lane->gen;
+  if ((int64_t)words <= g->lm_tab.cap) return FW_OK;
+  FW_HIP(hipStreamSynchronize(lane->stream));
+  for (GraphSlot& gs : g->graphs)
+    if (gs.exec && gs.key.lm) { (void)hipGraphExecDestroy(gs.exec); gs.exec = nullptr; gs.stamp = 0; }
+  return g->lm_tab.ensure((int64_t)words);
 }
 
 // Phase 2: the run's blocks of the cross-attention pool (all at once; `hold` keeps them to the end of the run), the
@@ -986,6 +1007,10 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   if (pl.gp.automaton)
     if (int rc = phrase_table_to_lane(g->automaton_tab, *reqs[0]->automaton, fwd::AUTOMATON_TABLE_MAX_WORDS, "automaton", st))
       return rc;
+  if (pl.gp.lm) {   // (generate_run has sized the buffer: lm_table_ensure)
+    const std::vector<int32_t>& t = reqs[0]->lm->table;
+    FW_HIP(hipMemcpyAsync(g->lm_tab.p, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
   ptok.assign((size_t)Pmax * Bx, 0);
@@ -1228,6 +1253,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   PoolHold hold{m->xpool, {}, lane->stream};
   std::vector<int> slots, ptok;
   if ((rc = run_alt_ensure(lane, pl))) return rc;
+  if (pl.gp.lm && (rc = lm_table_ensure(lane, reqs[0]->lm->table.size()))) return rc;
   if ((rc = run_acquire_blocks(m, lane, reqs, hold, slots))) return rc;
   if ((rc = run_init_state(m, lane, reqs, pl, slots, ptok))) return rc;
   if ((rc = run_prompt_forward(m, lane, pl, ptok))) return rc;
@@ -1509,14 +1535,17 @@ static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, con
   return FW_OK;
 }
 
-// One generate call with every extra the entry points know: at most one of `constraint` and `automaton` is given (each
-// entry point takes one of them).
-static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
-                             int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt, const fw_boost* boost,
-                             const fw_constraint* constraint, const fw_automaton* automaton, int32_t* out_ids,
-                             int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
-                             float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
-                             float* out_end_alt_logprobs);
+// What fw_generate_lm and fw_score_lm refuse of a language model (include/fwamd.h): one for another vocabulary, or whose
+// end-of-sentence id or n-gram ids do not fit the model's text ids — the kernel adds to the ids up to <eot> and no further.
+static int32_t ngram_check(const fw_ngram* lm, const fw_config& c) {
+  FW_CHECK_ARG(lm->n_vocab == c.n_vocab, "the language model was built for a vocabulary of %d ids, the model has %d",
+               lm->n_vocab, c.n_vocab);
+  if (int rc = keep_mask_geometry_check(c, "language-model")) return rc;
+  FW_CHECK_ARG(lm->table[3] == c.tok_eot, "the language model's eos_id is %d, the model's <eot> is %d", lm->table[3], c.tok_eot);
+  FW_CHECK_ARG(lm->table[6] <= c.tok_eot, "the language model holds an n-gram with id %d: n-grams are text, ids up to <eot> = %d",
+               lm->table[6], c.tok_eot);
+  return FW_OK;
+}
 
 int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                               int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt,
@@ -1524,9 +1553,9 @@ int32_t fw_generate_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_
                               float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
                               int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
                               float* out_end_alt_logprobs) {
-  return generate_call(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, constraint, nullptr, out_ids,
-                       out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
-                       out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
+  return fw_generate_lm(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, constraint, nullptr, nullptr,
+                        out_ids, out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
+                        out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
 }
 
 int32_t fw_generate_automaton(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
@@ -1535,17 +1564,19 @@ int32_t fw_generate_automaton(fw_model* fm, const fw_tensor* enc_t, const int32_
                               float* out_scores, float* out_no_speech, float* out_token_logprobs, float* out_end_logprobs,
                               int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
                               float* out_end_alt_logprobs) {
-  return generate_call(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, nullptr, automaton, out_ids,
-                       out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
-                       out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
+  return fw_generate_lm(fm, enc_t, prompts, prompt_offsets, B, o, top_k, top_p, n_alt, boost, nullptr, automaton, nullptr,
+                        out_ids, out_lens, out_scores, out_no_speech, out_token_logprobs, out_end_logprobs, out_alt_ids,
+                        out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
 }
 
-static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
-                             int32_t B, const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt, const fw_boost* boost,
-                             const fw_constraint* constraint, const fw_automaton* automaton, int32_t* out_ids,
-                             int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
-                             float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
-                             float* out_end_alt_logprobs) {
+// One generate call with every extra: what every other generate entry point calls.
+int32_t fw_generate_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets, int32_t B,
+                       const fw_gen_opts* o, int32_t top_k, float top_p, int32_t n_alt, const fw_boost* boost,
+                       const fw_constraint* constraint, const fw_automaton* automaton, const fw_ngram* lm, int32_t* out_ids,
+                       int32_t* out_lens, float* out_scores, float* out_no_speech, float* out_token_logprobs,
+                       float* out_end_logprobs, int32_t* out_alt_ids, float* out_alt_logprobs, int32_t* out_end_alt_ids,
+                       float* out_end_alt_logprobs) {
+  FW_CHECK_ARG(!constraint || !automaton, "a call takes a constraint list or an automaton, not both");
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && o && out_ids && out_lens && out_scores && out_no_speech,
                "null argument");
   FW_CHECK_ARG(n_alt >= 0 && n_alt <= FW_MAX_ALTERNATIVES, "n_alt %d not in [0, %d]", n_alt, FW_MAX_ALTERNATIVES);
@@ -1568,6 +1599,8 @@ static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t
     if (int rc = constraint_check(constraint, c, o, true)) return rc;
   if (automaton)
     if (int rc = automaton_check(automaton, c, o, true)) return rc;
+  if (lm)
+    if (int rc = ngram_check(lm, c)) return rc;
   const int K = o->beam_size;
   FW_CHECK_ARG(K >= 1 && K <= dm->max_beam, "beam_size %d not in [1, max_beam=%d]", K, dm->max_beam);
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
@@ -1621,6 +1654,7 @@ static int32_t generate_call(fw_model* fm, const fw_tensor* enc_t, const int32_t
   req.boost = fwd::phrase_list_live(boost) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
   req.constraint = fwd::phrase_list_live(constraint) ? constraint : nullptr;   // (likewise)
   req.automaton = automaton;
+  req.lm = lm;
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -1988,20 +2022,14 @@ extern "C" int32_t fw_score_boost(fw_model* fm, const fw_tensor* enc_t, const in
                             out_token_logprobs, out_best_ids, out_best_logprobs);
 }
 
-// fw_score with a boost list and / or a constraint list: dec_boost_kernel, then dec_constrain_kernel, on the block's logits
-// (recomputed per block) in front of the scoring kernel
-static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
-                          const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
-                          const fw_boost* boost, const fw_constraint* constraint, const fw_automaton* automaton,
-                          float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
-
+// fw_score with a boost list and / or a constraint list: fw_score_lm (below) without the rest
 extern "C" int32_t fw_score_constrain(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts,
                                       const int32_t* prompt_offsets, const int32_t* targets, const int32_t* target_offsets,
                                       int32_t B, int32_t H, const fw_gen_opts* rules, const fw_boost* boost,
                                       const fw_constraint* constraint, float* out_token_logprobs, int32_t* out_best_ids,
                                       float* out_best_logprobs) {
-  return score_call(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, constraint, nullptr,
-                    out_token_logprobs, out_best_ids, out_best_logprobs);
+  return fw_score_lm(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, constraint, nullptr,
+                     nullptr, out_token_logprobs, out_best_ids, out_best_logprobs);
 }
 
 // ... or an automaton in the list's place: dec_automaton_kernel where dec_constrain_kernel would run
@@ -2010,16 +2038,20 @@ extern "C" int32_t fw_score_automaton(fw_model* fm, const fw_tensor* enc_t, cons
                                       int32_t B, int32_t H, const fw_gen_opts* rules, const fw_boost* boost,
                                       const fw_automaton* automaton, float* out_token_logprobs, int32_t* out_best_ids,
                                       float* out_best_logprobs) {
-  return score_call(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, nullptr, automaton,
-                    out_token_logprobs, out_best_ids, out_best_logprobs);
+  return fw_score_lm(fm, enc_t, prompts, prompt_offsets, targets, target_offsets, B, H, rules, boost, nullptr, automaton,
+                     nullptr, out_token_logprobs, out_best_ids, out_best_logprobs);
 }
 
-// (at most one of `constraint` and `automaton`: each entry point takes one of them)
-static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
-                          const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H, const fw_gen_opts* rules,
-                          const fw_boost* boost, const fw_constraint* constraint, const fw_automaton* automaton,
-                          float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs) {
+// One score call with every extra: dec_boost_kernel, dec_ngram_kernel, then dec_constrain_kernel or dec_automaton_kernel, on
+// the block's logits (recomputed per block) in front of the scoring kernel.  What every other score entry point calls.
+extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
+                               const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                               const fw_gen_opts* rules, const fw_boost* boost, const fw_constraint* constraint,
+                               const fw_automaton* automaton, const fw_ngram* lm, float* out_token_logprobs,
+                               int32_t* out_best_ids, float* out_best_logprobs) {
+  FW_CHECK_ARG(!constraint || !automaton, "a call takes a constraint list or an automaton, not both");
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
+  FW_CHECK_ARG(!lm || rules, "a language model needs rules: the fusion is a step of the decoding rules");
   FW_CHECK_ARG(!boost || rules, "a boost list needs rules: the boost is the first step of the decoding rules");
   FW_CHECK_ARG(!constraint || rules, "a constraint list needs rules: the constraint is a step of the decoding rules");
   FW_CHECK_ARG(!automaton || rules, "an automaton needs rules: the automaton is a step of the decoding rules");
@@ -2036,6 +2068,8 @@ static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
     if (int crc = constraint_check(constraint, c, rules, false)) return crc;
   if (automaton)
     if (int arc = automaton_check(automaton, c, rules, false)) return arc;
+  if (lm)
+    if (int lrc = ngram_check(lm, c)) return lrc;
   if (!fwd::phrase_list_live(boost)) boost = nullptr;   // (an empty list does nothing)
   if (!fwd::phrase_list_live(constraint)) constraint = nullptr;
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
@@ -2119,6 +2153,10 @@ static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
   const std::pair<const fw_phrase_table*, int**> lists[] = {
       {boost, &boost_dev}, {constraint, &constrain_dev}, {automaton, &automaton_dev}};
   if (automaton) gp.automaton = fwd::automaton_lds_class(automaton->table.size());
+  if (lm) {   // (into the lane's buffer, as a decode run's: the lane is this call's until it returns)
+    if ((rc = lm_table_ensure(lane, lm->table.size()))) return rc;
+    FW_HIP_AS(setup_fail, hipMemcpyAsync(g->lm_tab.p, lm->table.data(), lm->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
   for (const auto& [list, dev] : lists) {   // (null: no list of that kind, its pre-pass is not launched)
     if (!list) continue;
     if ((rc = tmp.alloc(dev, list->table.size()))) return rc;
@@ -2143,6 +2181,7 @@ static int32_t score_call(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
         if (pos + nb - 1 < P - 1) return;
         ProfScope ps(lane->prof, PF_DEC_MISC, 0, 4.0 * Bx * nb * (double)c.n_vocab, st);
         if (boost_dev) fwd::launch_boost_score(st, gp, g->logits, boost_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
+        if (lm) fwd::launch_ngram_score(st, gp, g->logits, g->lm_tab.p, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         if (constrain_dev)
           fwd::launch_constrain_score(st, gp, g->logits, constrain_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
         if (automaton_dev)

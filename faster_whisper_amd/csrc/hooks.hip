@@ -1151,11 +1151,12 @@ static int32_t boost_hist_check(int32_t rows, const int32_t* hist, const int32_t
   return FW_OK;
 }
 
-// What fw_test_boost_rows, fw_test_constrain_rows and fw_test_automaton_rows do alike: ONE launch of a pre-pass kernel in
+// What fw_test_boost_rows, fw_test_constrain_rows, fw_test_automaton_rows and fw_test_ngram_rows do alike: ONE launch of a pre-pass kernel in
 // either row form (include/fwamd_test.h) over `rows` rows of gp.V logits.  gp holds what the kernel reads beyond the rows
 // (the callers have checked it and the list); B, K and R are set here.  Everything is checked before anything is allocated
 // or launched.  us_out != null: `iters` more launches on the same buffers, timed between two events after three untimed
-// ones (a pre-pass kernel that only writes -inf gives the same rows however often it runs); *us_out = microseconds per launch.
+// ones (a pre-pass kernel that only writes -inf gives the same rows however often it runs; one that adds does not, and its
+// timed rows serve no comparison); *us_out = microseconds per launch.
 using PrepassStep = void (*)(hipStream_t, const GenDev&, float*, const int*, const int*, const int*, const int*);
 using PrepassScore = void (*)(hipStream_t, const GenDev&, float*, const int*, const fwd::ScoreRow*, int, int, int, int, const int*);
 static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
@@ -1342,6 +1343,51 @@ int32_t fw_test_automaton_table(const fw_automaton* automaton, int32_t* out, int
   FW_CHECK_ARG(automaton && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
   *out_words = (int32_t)automaton->table.size();
   std::copy(automaton->table.begin(), automaton->table.begin() + std::min<size_t>((size_t)cap, automaton->table.size()), out);
+  return FW_OK;
+}
+
+// what the language-model hooks check of the caller's vocabulary geometry and model
+static int32_t ngram_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, const fw_ngram* lm) {
+  FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
+               "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
+  FW_CHECK_ARG(fwd::ngram_geometry_ok(lm->table.data(), n_vocab, tok_eot, tok_ts_begin),
+               "the language model (%d ids, eos_id %d, largest n-gram id %d) does not go with %d ids and <eot> %d", lm->table[2],
+               lm->table[3], lm->table[6], n_vocab, tok_eot);
+  return FW_OK;
+}
+
+// The model gives the device and the text context (the stride of the step form's histories) only.
+int32_t fw_test_ngram_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                           const int32_t* hist, const int32_t* hist_offsets, int32_t K, const int32_t* done, int32_t form,
+                           const fw_ngram* lm, int32_t iters, float* us_out) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && lm && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  FW_CHECK_ARG(!us_out || (iters >= 1 && iters <= 10000), "%d timed launches not in [1, 10000]", iters);
+  if (int rc = ngram_hook_check(n_vocab, tok_eot, tok_ts_begin, lm)) return rc;
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1; gp.lm = 1;
+  gp.eot = tok_eot; gp.ts_begin = tok_ts_begin;
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, lm->table, fwd::launch_ngram_step,
+                      fwd::launch_ngram_score, iters, us_out);
+}
+
+// the same table walked on the host: no device, no model
+int32_t fw_test_ngram_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                const int32_t* hist, const int32_t* hist_offsets, const fw_ngram* lm) {
+  FW_CHECK_ARG(logits && hist_offsets && lm && rows >= 1, "bad arguments");
+  if (int rc = ngram_hook_check(n_vocab, tok_eot, tok_ts_begin, lm)) return rc;
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
+  const int zero = 0;
+  fwd::ngram_rows_host(lm->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, hist ? hist : &zero, hist_offsets);
+  return FW_OK;
+}
+
+// the compiled table of a language model, as fw_test_constraint_table
+int32_t fw_test_ngram_table(const fw_ngram* lm, int32_t* out, int32_t cap, int32_t* out_words) {
+  FW_CHECK_ARG(lm && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
+  *out_words = (int32_t)lm->table.size();
+  std::copy(lm->table.begin(), lm->table.begin() + std::min<size_t>((size_t)cap, lm->table.size()), out);
   return FW_OK;
 }
 

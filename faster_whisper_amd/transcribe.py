@@ -194,16 +194,31 @@ def _check_grammar_arguments(allowed_grammar, allowed_phrases) -> None:
                          "(Grammar.phrases(allowed_phrases) is the list as a grammar)")
 
 
+def _check_lm_arguments(language_model, lm_scale, lm_bonus) -> None:
+    """language_model: None, or an ngram.NgramLM, and then lm_scale must be given (ValueError)"""
+    if language_model is None:
+        if lm_scale is not None or lm_bonus:
+            raise ValueError("lm_scale / lm_bonus need a language_model")
+        return
+    from .ngram import NgramLM
+    if not isinstance(language_model, NgramLM):
+        raise ValueError("language_model must be a faster_whisper_amd.ngram.NgramLM")
+    if lm_scale is None:
+        raise ValueError("language_model needs lm_scale: the weight of the language model at the logit has no default")
+
+
 @dataclass(frozen=True)
 class DecodeExtras:
     """What a transcription call asks of its decodes beyond the reference's options, carried as ONE value from the entry
-    point to model.generate.  boost / constraint / automaton: the call's built lists and automaton (boost_list_for /
-    constraint_list_for / automaton_for), the same objects for every window, attempt, batch and recording."""
+    point to model.generate.  boost / constraint / automaton / lm: the call's built lists, automaton and language model
+    (boost_list_for / constraint_list_for / automaton_for / lm_for), the same objects for every window, attempt, batch and
+    recording."""
     token_logprobs: bool = False
     token_alternatives: int = 0
     boost: object = None
     constraint: object = None
     automaton: object = None
+    lm: object = None
     sampling_top_k: int = 0
     sampling_top_p: float = 1.0
 
@@ -222,6 +237,8 @@ class DecodeExtras:
             kw["constraint"] = self.constraint
         if self.automaton is not None:
             kw["automaton"] = self.automaton
+        if self.lm is not None:
+            kw["lm"] = self.lm
         if sampled and self.sampling_top_k:
             kw["top_k"] = int(self.sampling_top_k)
         if sampled and self.sampling_top_p != 1:
@@ -241,11 +258,13 @@ def _decode_extras(model: "WhisperModel", a) -> DecodeExtras:
     _check_constraint_arguments(a["allowed_phrases"])
     _check_grammar_arguments(a["allowed_grammar"], a["allowed_phrases"])
     _check_trunc_arguments(a["sampling_top_k"], a["sampling_top_p"])
+    _check_lm_arguments(a["language_model"], a["lm_scale"], a["lm_bonus"])
     tokenizer = model.make_tokenizer() if a["boost_phrases"] or a["allowed_phrases"] or a["allowed_grammar"] else None
     return DecodeExtras(token_logprobs=a["token_logprobs"], token_alternatives=a["token_alternatives"],
                         boost=model.boost_list_for(a["boost_phrases"], a["phrase_boost"], tokenizer),
                         constraint=model.constraint_list_for(a["allowed_phrases"], tokenizer),
                         automaton=model.automaton_for(a["allowed_grammar"], tokenizer),
+                        lm=model.lm_for(a["language_model"], a["lm_scale"], a["lm_bonus"]),
                         sampling_top_k=a["sampling_top_k"], sampling_top_p=a["sampling_top_p"])
 
 
@@ -572,7 +591,8 @@ class WhisperModel:
                    vad_speech_probs=None, token_logprobs: bool = False, sampling_seed: Optional[int] = None,
                    token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
                    phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0,
-                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None):
+                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None, language_model=None,
+                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -596,7 +616,9 @@ class WhisperModel:
         allowed_phrases (not in the reference): see constraint_list_for — every decoded window is then exactly ONE phrase
         of the list, in every attempt of the fallback ladder.  Composes with boost_phrases.
         allowed_grammar (not in the reference): see automaton_for — a grammar.Grammar in the list's place: every decoded
-        window is then a string of its language.  ValueError together with allowed_phrases."""
+        window is then a string of its language.  ValueError together with allowed_phrases.
+        language_model, lm_scale, lm_bonus (not in the reference): see lm_for — shallow fusion with an n-gram language model
+        (ngram.NgramLM) in every window and every attempt of the fallback ladder.  lm_scale has no default."""
         args = dict(locals())               # the call's arguments by name
         return self._transcribe(args, _decode_extras(self, args))
 
@@ -678,7 +700,8 @@ class WhisperModel:
         which recording gets which seed depends on timing.
         boost_phrases / phrase_boost: ONE boost list is built here and handed to every recording's transcription, so the
         windows of different recordings keep sharing decode runs (calls share a run only with an equal list).
-        allowed_phrases: likewise ONE constraint list for every recording, and allowed_grammar ONE automaton.
+        allowed_phrases: likewise ONE constraint list for every recording, allowed_grammar ONE automaton and language_model
+        ONE compiled model.
         sampling_top_k / sampling_top_p (not in the reference): transcribe()'s, the same limits for every recording; sampled
         attempts share decode runs whatever their limits.
         An exception in one recording is raised here, after the recordings already started have finished."""
@@ -925,6 +948,20 @@ class WhisperModel:
         if allowed_grammar is None:
             return None
         return self.model.automaton(allowed_grammar.bind(tokenizer.encode))
+
+    def lm_for(self, language_model, lm_scale, lm_bonus=0.0):
+        """The compiled language model of a transcribe() call (backend.Whisper.ngram_lm), or None without one.
+        language_model is an ngram.NgramLM over the model's token ids (NgramLM.from_arpa, NgramLM.train); at every step
+        lm_scale * log P(id | the last ids) + lm_bonus is added to the logit of every text id and of <eot> — a graded
+        preference for the domain's text where boost_phrases only raises listed phrases.  lm_scale has no default, as
+        phrase_boost has none: a model without it is a ValueError.  lm_bonus (default 0) is the insertion bonus that keeps
+        the text ids level with the timestamp ids, which receive nothing.  Composes with boost_phrases, allowed_phrases
+        and allowed_grammar.  Built once per call and reused for every window, attempt of the temperature ladder, batch and
+        recording."""
+        _check_lm_arguments(language_model, lm_scale, lm_bonus)
+        if language_model is None:
+            return None
+        return self.model.ngram_lm(language_model, float(lm_scale), float(lm_bonus))
 
     def make_tokenizer(self, task="transcribe", language="en") -> Tokenizer:
         return Tokenizer(self.hf_tokenizer, self.model.config, self.model.is_multilingual, task=task, language=language)
@@ -1198,7 +1235,8 @@ class BatchedInferencePipeline:
                    token_logprobs: bool = False, token_alternatives: int = 0,
                    boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None,
                    sampling_top_k: int = 0, sampling_top_p: float = 1.0,
-                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None):
+                   allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None, language_model=None,
+                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1216,7 +1254,9 @@ class BatchedInferencePipeline:
         allowed_phrases (not in the reference): see WhisperModel.constraint_list_for — every chunk decodes to exactly one
         phrase of the list; one list for every batch.  Composes with boost_phrases.
         allowed_grammar (not in the reference): see WhisperModel.automaton_for — a grammar.Grammar in the list's place;
-        one automaton for every batch.  ValueError together with allowed_phrases."""
+        one automaton for every batch.  ValueError together with allowed_phrases.
+        language_model, lm_scale, lm_bonus (not in the reference): see WhisperModel.lm_for — one compiled model for every
+        batch.  lm_scale has no default."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model

@@ -20,6 +20,8 @@
  *                      fw_generate_constrain, fw_score_constrain
  *   automaton=         (not in the reference: decoding restricted to the language of a token automaton) ->
  *                      fw_automaton_create, fw_generate_automaton, fw_score_automaton
+ *   lm=                (not in the reference: shallow fusion with an n-gram language model) -> fw_ngram_create,
+ *                      fw_generate_lm, fw_score_lm
  *
  * plus the log-mel front end the reference runs in numpy on the host
  * (faster_whisper/feature_extractor.py:198-230, called at
@@ -64,7 +66,8 @@ extern "C" {
  *    more likely by a stated amount, at the logit), fw_generate_trunc (top-k / nucleus limits on the sampled draw),
  *    fw_constraint_create / fw_constraint_free / fw_generate_constrain / fw_score_constrain (decoding restricted to a
  *    given phrase list), fw_automaton_create / fw_automaton_free / fw_generate_automaton / fw_score_automaton (decoding
- *    restricted to the language of a deterministic token automaton) — new symbols only, each time */
+ *    restricted to the language of a deterministic token automaton), fw_ngram_create / fw_ngram_free / fw_generate_lm /
+ *    fw_score_lm (shallow fusion with a back-off n-gram language model) — new symbols only, each time */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -511,6 +514,93 @@ int32_t fw_generate_automaton(fw_model* m, const fw_tensor* enc, const int32_t* 
                               int32_t* out_alt_ids, float* out_alt_logprobs,
                               int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
 
+/* ---- shallow fusion with an n-gram language model: a graded preference for some text over other text (not in CTranslate2) ----
+ * The boost raises listed phrases, the constraint and the automaton remove ids; a back-off n-gram model — a weighted
+ * automaton with failure arcs, the "weights on edges" the automaton leaves out — adds a context-dependent value to EVERY
+ * text id: the usual way to adapt a Whisper engine to a domain's vocabulary.
+ * An n-gram model of order N has explicit n-grams of orders 1 to N, with 1 <= N <= FW_NGRAM_MAX_ORDER = 5.  Ids lie in
+ * [0, n_vocab).  One extra symbol, FW_NGRAM_BOS (= n_vocab), may appear only as the first id of an n-gram.  Every n-gram
+ * has a natural-log probability p.  Every n-gram of order below N also has a natural-log back-off weight bo.
+ * unk_logprob is the value of an id with no unigram.  eos_id is the id that stands for end of sentence.
+ * For one logits row:
+ *   - h is the generated history, never the prompt.
+ *   - t[0 .. m) is h without its ids >= tok_timestamp_begin.
+ *   - s = [BOS] + t.
+ *   - c_k is the last k symbols of s.
+ *   - K = min(N - 1, m + 1).
+ *   score(v): acc = 0.0f
+ *             for k = K .. 1:  if (c_k, v) is an explicit n-gram: return acc + p(c_k, v)
+ *                              acc += bo(c_k)          (0 when c_k is not an n-gram)
+ *             return acc + (p(v) if v has a unigram else unk_logprob)
+ * The arithmetic is float32, in the order written.
+ * Every id v <= tok_eot gets logit[v] += scale * score(v) + bonus, with score(eot) taken at eos_id.
+ *   - Each id is written exactly once.
+ *   - Whether scale * score + bonus is fused is the implementation's choice.
+ *   - Ids above tok_eot (specials and timestamps) keep their bits.
+ *   - A -inf logit stays -inf.
+ * bonus is the insertion bonus.  Without it, text ids lose ground to the timestamp ids, which receive nothing.
+ * Order within a step: boost, then the language model, then the constraint or the automaton, then the rules exactly as
+ * today.  Log-probs, alternatives, scores and sampled draws are those of the fused, processed distribution.
+ * No state is kept between steps: the context is a function of the row's history, found again by one kernel
+ * (dec_ngram.hip) per step, so beam reordering needs nothing and a merged run gives every caller its solo bits.
+ *
+ * fw_ngram_create is host code and needs no device and no model.  Its inputs:
+ *   - n_vocab and order.
+ *   - counts[order].
+ *   - ids: the ids of all n-grams, back to back, order by order (counts[0] ids, then 2 * counts[1], ...).
+ *   - logprobs and backoffs laid out the same way, one entry per n-gram.  Back-offs of order N are ignored, and so is the
+ *     back-off of an n-gram that ends in eos_id (no history holds it).
+ *   - unk_logprob, scale, bonus, eos_id.
+ * The context [BOS] gets its back-off weight from the unigram BOS, which has no probability — BOS is never predicted:
+ * its logprobs entry must be 0.
+ * It returns FW_EINVAL, with a message that names the order and the n-gram's index, for any of these:
+ *   - a null pointer where a count is positive;
+ *   - an order outside [1, 5];
+ *   - more than FW_NGRAM_MAX_GRAMS (2^20) n-grams of order >= 2;
+ *   - an id outside [0, n_vocab];
+ *   - BOS anywhere but the first position, or BOS as a unigram with a probability;
+ *   - a duplicate n-gram;
+ *   - eos_id inside an n-gram's context;
+ *   - a value that is not finite.  p, bo, unk_logprob, scale and bonus must be finite, and -inf is refused.  A fused row
+ *     must never lose its last live id.
+ * An n-gram whose context is itself not an n-gram is valid.  That context has back-off 0.
+ * The model compiles to one int32 table, and equal arguments give byte-equal tables.  scale and bonus sit in the table's
+ * header, so two calls that fuse with different strengths do not share a run.
+ * fw_ngram_free frees the object. */
+#define FW_NGRAM_MAX_ORDER 5
+#define FW_NGRAM_MAX_GRAMS (1 << 20)
+#define FW_NGRAM_BOS(n_vocab) (n_vocab)
+typedef struct fw_ngram fw_ngram;   /* opaque: a validated, compiled model (host memory); any number of calls may read it at once */
+int32_t fw_ngram_create(int32_t n_vocab, int32_t order, const int32_t* counts, const int32_t* ids, const float* logprobs,
+                        const float* backoffs, float unk_logprob, float scale, float bonus, int32_t eos_id, fw_ngram** out);
+void fw_ngram_free(fw_ngram* lm);
+/* fw_generate_constrain and fw_generate_automaton in one, plus a language model: `constraint` and `automaton` exclude each
+ * other (giving both is FW_EINVAL), and each is checked as its own entry point checks it.  lm == NULL is the existing
+ * entry point exactly, bit for bit; the existing entry points are calls of this one.
+ * FW_EINVAL before anything is queued:
+ *   - the model's n_vocab differs from the one the object was built for;
+ *   - eos_id != tok_eot;
+ *   - an n-gram id is above tok_eot.
+ * Merging follows the rule of the other kinds: two calls share a decode run only when both have no model, or their tables
+ * are byte-equal (scale and bonus included).  Every caller gets its solo bits.  A run without a model launches exactly what
+ * it launched before.
+ * The table can be megabytes: it does not go into a fixed per-lane buffer but into a device buffer of the lane that the
+ * first run needing it allocates and that grows when a larger table arrives (the model may be freed once the call has
+ * returned).  The calls of that run get FW_ENOMEM if that fails.
+ * COST: one kernel launch per step more, which reads and writes rows x (tok_eot + 1) floats where the mask writers only
+ * write.  Measured on an MI355X at large-v3's vocabulary (python profiles/ngram_cost.py: kernel time, eager launches,
+ * event timing, a trigram model of 2^20 - 8 n-grams of order 2 and 3, 5.6 M table words): 17.4 us per step at 80 rows and an
+ * empty history, 19.1 us at a history of 32 ids (the walk at full depth, two sparse levels), where dec_constrain_kernel
+ * takes 15.7 us; 42.7 us / 45.2 us at 640 rows against its 31.5 us — 1.1 x - 1.2 x and 1.4 x the list kernel. */
+int32_t fw_generate_lm(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                       int32_t B, const fw_gen_opts* opts, int32_t top_k, float top_p, int32_t n_alt,
+                       const fw_boost* boost, const fw_constraint* constraint, const fw_automaton* automaton,
+                       const fw_ngram* lm,
+                       int32_t* out_ids, int32_t* out_lens, float* out_scores, float* out_no_speech,
+                       float* out_token_logprobs, float* out_end_logprobs,
+                       int32_t* out_alt_ids, float* out_alt_logprobs,
+                       int32_t* out_end_alt_ids, float* out_end_alt_logprobs);
+
 /* ---- score ---------------------------------------------------------------
  * Teacher-forced log-probs of GIVEN transcripts (CTranslate2 has score_batch for its other model classes): how likely
  * is this text under the model, for text that was not decoded here — a corrected transcript, another system's output,
@@ -566,6 +656,17 @@ int32_t fw_score_automaton(fw_model* m, const fw_tensor* enc, const int32_t* pro
                            const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
                            const fw_gen_opts* rules, const fw_boost* boost, const fw_automaton* automaton,
                            float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
+
+/* fw_score_constrain and fw_score_automaton in one, plus a language model (shallow fusion, above): on every scored row the
+ * boost (if any), then the model with the sequence's own prefix as the generated history, then the constraint or the
+ * automaton (giving both is FW_EINVAL), then the rules.  lm == NULL is the existing entry point exactly; otherwise
+ * rules != NULL is needed and the checks of fw_generate_lm run (FW_EINVAL).  For a greedy hypothesis of fw_generate_lm it
+ * returns out_token_logprobs and out_end_logprobs bit for bit, and out_best_ids / out_best_logprobs are its alternative 0. */
+int32_t fw_score_lm(fw_model* m, const fw_tensor* enc, const int32_t* prompts, const int32_t* prompt_offsets,
+                    const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
+                    const fw_gen_opts* rules, const fw_boost* boost, const fw_constraint* constraint,
+                    const fw_automaton* automaton, const fw_ngram* lm,
+                    float* out_token_logprobs, int32_t* out_best_ids, float* out_best_logprobs);
 
 /* ---- detect_language -------------------------------------------------------
  * ctranslate2.models.Whisper.detect_language: one decoder step on [sot];

@@ -217,6 +217,19 @@ int32_t fw_test_automaton_rows_host(float* logits, int32_t rows, int32_t n_vocab
                                     const fw_automaton* automaton);
 /* host-only: the compiled table of an automaton (what the merge rule compares), as fw_test_constraint_table */
 int32_t fw_test_automaton_table(const fw_automaton* automaton, int32_t* out, int32_t cap, int32_t* out_words);
+/* ONE launch of dec_ngram_kernel (shallow fusion, include/fwamd.h) in either row form on caller-provided rows, with the row
+ * arguments and the checks of fw_test_constrain_rows above.  The geometry (n_vocab, tok_eot, tok_ts_begin) is the caller's
+ * and must be the one the model was built for: lm's n_vocab and eos_id, no n-gram id above tok_eot (FW_EINVAL).  us_out !=
+ * NULL: after the launch, `iters` (1 .. 10000) more on the same buffers between two events; *us_out = microseconds per
+ * launch — the kernel ADDS, so the rows that come back have then been fused 4 + iters times and serve no comparison. */
+int32_t fw_test_ngram_rows(fw_model* m, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                           const int32_t* hist, const int32_t* hist_offsets, int32_t K, const int32_t* done, int32_t form,
+                           const fw_ngram* lm, int32_t iters, float* us_out);
+/* host-only (no device, no model needed): the same table walked in plain C++, ragged histories of any length */
+int32_t fw_test_ngram_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                const int32_t* hist, const int32_t* hist_offsets, const fw_ngram* lm);
+/* host-only: the compiled table of a language model (what the merge rule compares), as fw_test_constraint_table */
+int32_t fw_test_ngram_table(const fw_ngram* lm, int32_t* out, int32_t cap, int32_t* out_words);
 /* one launch of the token + position embedding (K12: launch_embed): tok [rows] (in [0, V): checked), emb [V][d], pos_emb
  * [NT][d] (rounded to fp16 by the hook) -> x [rows][d] and x_frag [ceil(rows / 16) * 16][d], the fragment-major copy
  * un-permuted on the host; its device buffer starts as `sentinel`, so the padding rows of the last tile stay visible.
