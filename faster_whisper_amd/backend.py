@@ -149,25 +149,19 @@ class WhisperScoringResult:
                 f"end_logprobs={self.end_logprobs})")
 
 
-class _PhraseList:
-    """What BoostList and ConstraintList share: the ragged packing of the phrases, the engine's handle and its release, the
-    type check of the keyword that takes the list.  A subclass names its keyword, what the feature is called in messages,
-    and its create / free symbols."""
-    _keyword = _feature = _create = _free = None
+class _Compiled:
+    """What BoostList, ConstraintList, Automaton and NgramFusion share: the engine's handle and its release, and the type
+    check of the keyword that takes one.  A subclass names its keyword, how a value of it is spoken of, what the feature is
+    called in messages, and its create / free symbols."""
+    _keyword = _a = _feature = _create = _free = None
 
-    def _compile(self, n_vocab: int, phrases, *per_phrase):
+    def _create_handle(self, *args):
+        """self._handle from the class's create symbol, which takes args and the handle's address"""
         lib = _lib.load()
         if not hasattr(lib, self._create):   # an older build loaded through FWAMD_LIB
             raise RuntimeError(f"this libfwamd.so has no {self._create}: {self._feature} needs a current build")
-        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
-        self.n_vocab = int(n_vocab)
-        self.n_phrases = len(phrases)
         self._handle = C.c_void_p()
-        _lib.check(getattr(lib, self._create)(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases),
-                                              *per_phrase, C.byref(self._handle)))
-
-    def __len__(self):
-        return self.n_phrases
+        _lib.check(getattr(lib, self._create)(*args, C.byref(self._handle)))
 
     def __del__(self):
         if getattr(self, "_handle", None):
@@ -179,12 +173,25 @@ class _PhraseList:
 
     @classmethod
     def _handle_of(cls, value):
-        """the handle of a keyword's value: None, or a list of this class (TypeError)"""
+        """the handle of a keyword's value: None, or an object of this class (TypeError)"""
         if value is None:
             return None
         if not isinstance(value, cls):
-            raise TypeError(f"{cls._keyword} must be a {cls.__name__} (Whisper.{cls._keyword}_list) or None")
+            raise TypeError(f"{cls._keyword} must be {cls._a} or None")
         return value._handle
+
+
+class _PhraseList(_Compiled):
+    """What BoostList and ConstraintList share beyond that: the ragged packing of the phrases."""
+
+    def _compile(self, n_vocab: int, phrases, *per_phrase):
+        flat, offs = _ragged([np.asarray(p, dtype=np.int32) for p in phrases], np.int32, np.int32)
+        self.n_vocab = int(n_vocab)
+        self.n_phrases = len(phrases)
+        self._create_handle(self.n_vocab, _lib.as_i32p(flat), _lib.as_i32p(offs), len(phrases), *per_phrase)
+
+    def __len__(self):
+        return self.n_phrases
 
 
 class BoostList(_PhraseList):
@@ -193,7 +200,8 @@ class BoostList(_PhraseList):
     in front of it (the first token: at every step).  Where several phrases ask for one id the largest boost counts, not the
     sum; the decoding rules run after the boost and still win.  Host-only: needs no device.  Whisper.boost_list builds one
     for the model's vocabulary; pass it as generate(boost=...) / score(boost=...)."""
-    _keyword, _feature, _create, _free = "boost", "phrase boosting", "fw_boost_create", "fw_boost_free"
+    _keyword, _a, _feature = "boost", "a BoostList (Whisper.boost_list)", "phrase boosting"
+    _create, _free = "fw_boost_create", "fw_boost_free"
 
     def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]], boosts: Sequence[float]):
         phrases = [list(p) for p in phrases]
@@ -212,79 +220,43 @@ class ConstraintList(_PhraseList):
     of others are valid; the list is a set (order and repeats do not matter).  Host-only: needs no device.
     Whisper.constraint_list builds one for the model's vocabulary; pass it as generate(constraint=...) /
     score(constraint=...).  An empty list constrains nothing."""
-    _keyword, _feature, _create, _free = "constraint", "constrained decoding", "fw_constraint_create", "fw_constraint_free"
+    _keyword, _a, _feature = "constraint", "a ConstraintList (Whisper.constraint_list)", "constrained decoding"
+    _create, _free = "fw_constraint_create", "fw_constraint_free"
 
     def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]]):
         self._compile(n_vocab, [list(p) for p in phrases])
 
 
-class Automaton:
+class Automaton(_Compiled):
     """A validated, compiled token automaton (fwamd.h: fw_automaton_create) built from a grammar.Grammar: at every step the
     ids that label no out-edge of the state the row's generated text leads to are set to -inf in front of the decoding
     rules, and <eot> is allowed only in an accepting state — a hypothesis with a finite score that closes on <eot> is, its
     timestamps apart, a string of the grammar's language.  Host-only: needs no device.  Whisper.automaton builds one for
     the model's vocabulary; pass it as generate(automaton=...) / score(automaton=...)."""
+    _keyword, _a, _feature = "automaton", "an Automaton (Whisper.automaton)", "automaton-constrained decoding"
+    _create, _free = "fw_automaton_create", "fw_automaton_free"
 
     def __init__(self, n_vocab: int, grammar):
-        lib = _lib.load()
-        if not hasattr(lib, "fw_automaton_create"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_automaton_create: automaton-constrained decoding needs a current build")
         offsets, tokens, targets, accepting = (np.ascontiguousarray(a, dtype=np.int32) for a in grammar.csr())
         self.n_vocab = int(n_vocab)
         self.grammar = grammar
-        self._handle = C.c_void_p()
-        _lib.check(lib.fw_automaton_create(self.n_vocab, len(accepting), _lib.as_i32p(offsets), _lib.as_i32p(tokens),
-                                           _lib.as_i32p(targets), _lib.as_i32p(accepting), C.byref(self._handle)))
-
-    def __del__(self):
-        if getattr(self, "_handle", None):
-            try:
-                _lib.load().fw_automaton_free(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-
-    @staticmethod
-    def _handle_of(value):
-        if value is None:
-            return None
-        if not isinstance(value, Automaton):
-            raise TypeError("automaton must be an Automaton (Whisper.automaton) or None")
-        return value._handle
+        self._create_handle(self.n_vocab, len(accepting), _lib.as_i32p(offsets), _lib.as_i32p(tokens), _lib.as_i32p(targets),
+                            _lib.as_i32p(accepting))
 
 
-class NgramFusion:
+class NgramFusion(_Compiled):
     """A validated, compiled n-gram language model with its fusion strength (fwamd.h: fw_ngram_create), built from an
     ngram.NgramLM: at every step scale * log P(id | the row's last order - 1 text ids) + bonus is added to the logit of every
     text id and <eot>, behind the boost and in front of the constraint / automaton and the decoding rules.  Host-only: needs
     no device.  Whisper.ngram_lm builds one for the model's vocabulary; pass it as generate(lm=...) / score(lm=...)."""
+    _keyword, _a, _feature = "lm", "an NgramFusion (Whisper.ngram_lm)", "language-model fusion"
+    _create, _free = "fw_ngram_create", "fw_ngram_free"
 
     def __init__(self, n_vocab: int, eos_id: int, lm, scale: float, bonus: float = 0.0):
-        lib = _lib.load()
-        if not hasattr(lib, "fw_ngram_create"):   # an older build loaded through FWAMD_LIB
-            raise RuntimeError("this libfwamd.so has no fw_ngram_create: language-model fusion needs a current build")
         counts, ids, lp, bo = lm.arrays(n_vocab, eos_id)
         self.n_vocab, self.lm, self.scale, self.bonus = int(n_vocab), lm, float(scale), float(bonus)
-        self._handle = C.c_void_p()
-        _lib.check(lib.fw_ngram_create(self.n_vocab, lm.order, _lib.as_i32p(counts), _lib.as_i32p(ids), _lib.as_f32p(lp),
-                                       _lib.as_f32p(bo), float(lm.unk_logprob), self.scale, self.bonus, int(eos_id),
-                                       C.byref(self._handle)))
-
-    def __del__(self):
-        if getattr(self, "_handle", None):
-            try:
-                _lib.load().fw_ngram_free(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-
-    @staticmethod
-    def _handle_of(value):
-        if value is None:
-            return None
-        if not isinstance(value, NgramFusion):
-            raise TypeError("lm must be an NgramFusion (Whisper.ngram_lm) or None")
-        return value._handle
+        self._create_handle(self.n_vocab, lm.order, _lib.as_i32p(counts), _lib.as_i32p(ids), _lib.as_f32p(lp),
+                            _lib.as_f32p(bo), float(lm.unk_logprob), self.scale, self.bonus, int(eos_id))
 
 
 def _require_symbols(lib, needs) -> None:

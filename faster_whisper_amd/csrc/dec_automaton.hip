@@ -169,28 +169,22 @@ static bool automaton_geometry_ok(int V, int eot, int ts_begin, int n_text_ctx) 
 // near 16 ids for the phrase-list table and between 16 and 64 for the largest: 8 ids plus one per 1024 table words.
 int automaton_stage_min(size_t table_words) { return 8 + (int)(table_words / 1024); }
 
-void launch_automaton_step(hipStream_t st, const GenDev& gp, float* logits, const int* atab, const int* hist2,
-                           const int* d_step, const int* done) {
-  if (!atab || gp.R <= 0 || !automaton_geometry_ok(gp.V, gp.eot, gp.ts_begin, gp.n_text_ctx)) return;
-  const RowSource src{hist2, d_step, done, nullptr, 0, 0, 1};
+template <bool SCORE>
+static void launch_automaton_form(hipStream_t st, const GenDev& gp, float* logits, const int* atab, const RowSource& src,
+                                  int K, int R) {
   if (gp.automaton == 1)
-    dec_automaton_kernel<false, AUTOMATON_LDS_SMALL_WORDS><<<gp.R, AUTOMATON_THREADS, 0, st>>>(
-        logits, atab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
+    dec_automaton_kernel<SCORE, AUTOMATON_LDS_SMALL_WORDS><<<R, AUTOMATON_THREADS, 0, st>>>(
+        logits, atab, gp.V, K, R, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
   else
-    dec_automaton_kernel<false, AUTOMATON_LDS_LARGE_WORDS><<<gp.R, AUTOMATON_THREADS, 0, st>>>(
-        logits, atab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
+    dec_automaton_kernel<SCORE, AUTOMATON_LDS_LARGE_WORDS><<<R, AUTOMATON_THREADS, 0, st>>>(
+        logits, atab, gp.V, K, R, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
 }
 
-void launch_automaton_score(hipStream_t st, const GenDev& gp, float* logits, const int* atab, const ScoreRow* tab,
-                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
-  if (!atab || rows <= 0 || !automaton_geometry_ok(gp.V, gp.eot, gp.ts_begin, gp.n_text_ctx)) return;
-  const RowSource src{hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb};
-  if (gp.automaton == 1)
-    dec_automaton_kernel<true, AUTOMATON_LDS_SMALL_WORDS><<<rows, AUTOMATON_THREADS, 0, st>>>(
-        logits, atab, gp.V, 1, rows, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
-  else
-    dec_automaton_kernel<true, AUTOMATON_LDS_LARGE_WORDS><<<rows, AUTOMATON_THREADS, 0, st>>>(
-        logits, atab, gp.V, 1, rows, gp.n_text_ctx, gp.eot, gp.ts_begin, gp.with_ts, src);
+void launch_automaton(hipStream_t st, const GenDev& gp, float* logits, const int* atab, const RowSource& src, int rows) {
+  const bool step = src.tab == nullptr;
+  if (!atab || (step ? gp.R : rows) <= 0 || !automaton_geometry_ok(gp.V, gp.eot, gp.ts_begin, gp.n_text_ctx)) return;
+  if (step) launch_automaton_form<false>(st, gp, logits, atab, src, gp.K, gp.R);
+  else launch_automaton_form<true>(st, gp, logits, atab, src, 1, rows);
 }
 
 int automaton_next_host(const int* tab, int rec, int token) {

@@ -68,18 +68,13 @@ __global__ __launch_bounds__(BOOST_THREADS) void dec_boost_kernel(float* __restr
 
 namespace fwd {
 
-void launch_boost_step(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const int* hist2,
-                       const int* d_step, const int* done) {
-  if (!boost_tab || gp.R <= 0) return;
-  dec_boost_kernel<false><<<gp.R, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, gp.K, gp.R, gp.n_text_ctx,
-                                                         {hist2, d_step, done, nullptr, 0, 0, 1});
-}
-
-void launch_boost_score(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const ScoreRow* tab,
-                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
-  if (!boost_tab || rows <= 0) return;
-  dec_boost_kernel<true><<<rows, BOOST_THREADS, 0, st>>>(logits, boost_tab, gp.V, 1, rows, gp.n_text_ctx,
-                                                        {hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb});
+void launch_boost(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows) {
+  const bool step = src.tab == nullptr;
+  if (!tab || (step ? gp.R : rows) <= 0) return;
+  if (step)
+    dec_boost_kernel<false><<<gp.R, BOOST_THREADS, 0, st>>>(logits, tab, gp.V, gp.K, gp.R, gp.n_text_ctx, src);
+  else
+    dec_boost_kernel<true><<<rows, BOOST_THREADS, 0, st>>>(logits, tab, gp.V, 1, rows, gp.n_text_ctx, src);
 }
 
 void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets) {

@@ -100,20 +100,15 @@ static bool constrain_geometry_ok(int V, int eot, int ts_begin) {
   return V >= 1 && V <= LP_SUP_WORDS * 64 && eot >= 0 && eot < ts_begin && ts_begin <= V;
 }
 
-void launch_constrain_step(hipStream_t st, const GenDev& gp, float* logits, const int* ctab, const int* hist2,
-                           const int* d_step, const int* done) {
-  if (!ctab || gp.R <= 0 || !constrain_geometry_ok(gp.V, gp.eot, gp.ts_begin)) return;
-  dec_constrain_kernel<false><<<gp.R, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot,
-                                                                 gp.ts_begin, gp.with_ts,
-                                                                 {hist2, d_step, done, nullptr, 0, 0, 1});
-}
-
-void launch_constrain_score(hipStream_t st, const GenDev& gp, float* logits, const int* ctab, const ScoreRow* tab,
-                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
-  if (!ctab || rows <= 0 || !constrain_geometry_ok(gp.V, gp.eot, gp.ts_begin)) return;
-  dec_constrain_kernel<true><<<rows, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, 1, rows, gp.n_text_ctx, gp.eot,
-                                                                gp.ts_begin, gp.with_ts,
-                                                                {hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb});
+void launch_constrain(hipStream_t st, const GenDev& gp, float* logits, const int* ctab, const RowSource& src, int rows) {
+  const bool step = src.tab == nullptr;
+  if (!ctab || (step ? gp.R : rows) <= 0 || !constrain_geometry_ok(gp.V, gp.eot, gp.ts_begin)) return;
+  if (step)
+    dec_constrain_kernel<false><<<gp.R, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot,
+                                                                   gp.ts_begin, gp.with_ts, src);
+  else
+    dec_constrain_kernel<true><<<rows, CONSTRAIN_THREADS, 0, st>>>(logits, ctab, gp.V, 1, rows, gp.n_text_ctx, gp.eot,
+                                                                  gp.ts_begin, gp.with_ts, src);
 }
 
 void constrain_rows_host(const int* ctab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts, const int* hist,

@@ -236,14 +236,14 @@ struct ScoreRow {
   int out;                 // index into out_lp / out_best_id / out_best_lp
 };
 static_assert(sizeof(ScoreRow) == 16, "one 16-byte load per row");
-// row r of a score-form launch: position pos0 + r % nb of sequence r / nb (dec_score_kernel and the score forms of the two
+// row r of a score-form launch: position pos0 + r % nb of sequence r / nb (dec_score_kernel and the score forms of the
 // pre-pass kernels address their rows through this)
 static __device__ __forceinline__ ScoreRow score_row(const ScoreRow* __restrict__ tab, int tab_stride, int pos0, int nb, int r) {
   const int sq = r / nb;
   return tab[(size_t)sq * tab_stride + pos0 + (r - sq * nb)];
 }
-// Where a pre-pass kernel (dec_boost_kernel, dec_constrain_kernel) finds its rows' histories.  Decode-step form: hist is
-// hist2 [2][R][NT], d_step and done are the run's.  Score form: hist is the history pool, tab .. nb address the ScoreRows.
+// Where a pre-pass kernel finds its rows' histories.  Decode-step form (tab == null): hist is hist2 [2][R][NT], d_step and
+// done are the run's.  Score form: hist is the history pool, tab .. nb address the ScoreRows.
 struct RowSource {
   const int* hist;
   const int* d_step;
@@ -251,6 +251,12 @@ struct RowSource {
   const ScoreRow* tab;
   int tab_stride, pos0, nb;
 };
+static inline RowSource step_rows(const int* hist2, const int* d_step, const int* done) {
+  return {hist2, d_step, done, nullptr, 0, 0, 1};
+}
+static inline RowSource score_rows(const int* hist_pool, const ScoreRow* tab, int tab_stride, int pos0, int nb) {
+  return {hist_pool, nullptr, nullptr, tab, tab_stride, pos0, nb};
+}
 // Row r's history hist[0 .. n), n clamped to NT.  False: the row is skipped (its chunk is done / it has no target); the
 // answer is the same for every thread of the workgroup, and the caller returns on it before any barrier.
 template <bool SCORE>
@@ -338,15 +344,9 @@ static __host__ __device__ inline BoostView boost_view(const int* tab) {
   v.tok = v.ent + 3 * v.E;
   return v;
 }
-// dec_boost_kernel, decode-step form, in front of launch_logits_process: row r of gp.R rows reads its history from the
-// parity half of hist2 that *d_step selects (n = step), rows of chunks with done[r / gp.K] are skipped.  logits [gp.R][gp.V]
-// IN / OUT: logits[r][v] += boost(v) for the ids with a matching pair, every other value keeps its bits.
-void launch_boost_step(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const int* hist2,
-                       const int* d_step, const int* done);
-// ... score form, in front of launch_score, same row addressing: rows without a target (target < 0) are skipped, the
-// history is the ScoreRow's.  Every n <= n_text_ctx, every table built by fw_boost_create for gp.V: the caller's to guarantee.
-void launch_boost_score(hipStream_t st, const GenDev& gp, float* logits, const int* boost_tab, const ScoreRow* tab,
-                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// dec_boost_kernel (row forms: launch_prepasses, below).  logits IN / OUT: logits[r][v] += boost(v) for the ids with a
+// matching pair, every other value keeps its bits.  Every table built by fw_boost_create for gp.V: the caller's to guarantee.
+void launch_boost(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
 // the same walk in plain C++ (fw_test_boost_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
 
@@ -369,18 +369,12 @@ static __host__ __device__ inline ConstrainView constrain_view(const int* tab) {
   v.tok = v.off + v.P + 1;
   return v;
 }
-// dec_constrain_kernel, decode-step form, behind launch_boost_step and in front of launch_logits_process: row r of gp.R
-// rows reads its history from the parity half of hist2 that *d_step selects (n = step), rows of chunks with
-// done[r / gp.K] are skipped.  logits [gp.R][gp.V] IN / OUT: every text id (< gp.ts_begin) that no phrase allows after the
-// row's history (include/fwamd.h) becomes -inf, gp.eot included unless the history is a whole phrase; the timestamp ids
-// become -inf unless gp.with_ts; every other value keeps its bits, nothing is read.  Reads gp.V, K, R, n_text_ctx, eot,
-// ts_begin, with_ts.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS: the callers check.
-void launch_constrain_step(hipStream_t st, const GenDev& gp, float* logits, const int* constrain_tab, const int* hist2,
-                           const int* d_step, const int* done);
-// ... score form, in front of launch_score, same row addressing: rows without a target (target < 0) are skipped, the
-// history is the ScoreRow's.  Every n <= n_text_ctx, a table built by fw_constraint_create: the caller's to guarantee.
-void launch_constrain_score(hipStream_t st, const GenDev& gp, float* logits, const int* constrain_tab, const ScoreRow* tab,
-                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+// dec_constrain_kernel (row forms: launch_prepasses, below).  logits IN / OUT: every text id (< gp.ts_begin) that no phrase
+// allows after the row's history (include/fwamd.h) becomes -inf, gp.eot included unless the history is a whole phrase; the
+// timestamp ids become -inf unless gp.with_ts; every other value keeps its bits, nothing is read.  Reads gp.V, K, R,
+// n_text_ctx, eot, ts_begin, with_ts.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS: the callers
+// check.  A table built by fw_constraint_create: the caller's to guarantee.
+void launch_constrain(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
 // the same walk in plain C++ (fw_test_constrain_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void constrain_rows_host(const int* constrain_tab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts,
                          const int* hist, const int* hist_offsets);
@@ -412,18 +406,13 @@ static inline int automaton_lds_class(size_t table_words) { return table_words <
 constexpr int AUTOMATON_MAX_HIST = 1024;
 // THE staging rule ("Automaton-constrained decoding", has the measurements behind it)
 int automaton_stage_min(size_t table_words);
-// dec_automaton_kernel, decode-step form, behind launch_boost_step and in front of launch_logits_process, in
-// launch_constrain_step's place and with its row addressing and its contract: every text id (< gp.ts_begin) that labels no
+// dec_automaton_kernel, in launch_constrain's place and with its contract: every text id (< gp.ts_begin) that labels no
 // out-edge of the state the row's text history leads to becomes -inf, gp.eot included unless that state accepts; a history
 // that leaves the language keeps no text id; the timestamp ids become -inf unless gp.with_ts; every other value keeps its
 // bits, nothing is read.  Reads gp.V, K, R, n_text_ctx, eot, ts_begin, with_ts and gp.automaton (the LDS allocation: the
 // table must fit it).  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS and n_text_ctx <=
 // AUTOMATON_MAX_HIST: the callers check.
-void launch_automaton_step(hipStream_t st, const GenDev& gp, float* logits, const int* automaton_tab, const int* hist2,
-                           const int* d_step, const int* done);
-// ... score form, in front of launch_score, as launch_constrain_score
-void launch_automaton_score(hipStream_t st, const GenDev& gp, float* logits, const int* automaton_tab, const ScoreRow* tab,
-                            int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+void launch_automaton(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
 // the same walk in plain C++ (fw_test_automaton_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void automaton_rows_host(const int* automaton_tab, float* logits, int rows, int V, int eot, int ts_begin, int with_ts,
                          const int* hist, const int* hist_offsets);
@@ -454,23 +443,45 @@ static __host__ __device__ inline float ngram_bits_float(int bits) {
   u.i = bits;
   return u.f;
 }
-// dec_ngram_kernel, decode-step form, behind launch_boost_step and in front of the constraint / automaton: row r of gp.R
-// rows reads its history from the parity half of hist2 that *d_step selects (n = step), rows of chunks with
-// done[r / gp.K] are skipped.  logits [gp.R][gp.V] IN / OUT: logits[r][v] += scale * score(v) + bonus for every id
-// v <= gp.eot (include/fwamd.h states score), each written once; the ids above gp.eot keep their bits.  Reads gp.V, K, R,
-// n_text_ctx, eot, ts_begin.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS, the table's
+// dec_ngram_kernel (row forms: launch_prepasses, below).  logits IN / OUT: logits[r][v] += scale * score(v) + bonus for
+// every id v <= gp.eot (include/fwamd.h states score), each written once; the ids above gp.eot keep their bits.  Reads gp.V,
+// K, R, n_text_ctx, eot, ts_begin.  Nothing is launched unless 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS, the table's
 // eos_id is gp.eot and none of its ids lies above it: the callers check.
-void launch_ngram_step(hipStream_t st, const GenDev& gp, float* logits, const int* ngram_tab, const int* hist2,
-                       const int* d_step, const int* done);
-// ... score form, in front of launch_score, as launch_boost_score
-void launch_ngram_score(hipStream_t st, const GenDev& gp, float* logits, const int* ngram_tab, const ScoreRow* tab,
-                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool);
+void launch_ngram(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
 // the same walk in plain C++ (fw_test_ngram_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void ngram_rows_host(const int* ngram_tab, float* logits, int rows, int V, int eot, int ts_begin, const int* hist,
                      const int* hist_offsets);
-// whether a table goes with a vocabulary of V ids whose <eot> is `eot` and whose first timestamp is `ts_begin`: what both
-// launchers ask, what fw_generate_lm / fw_score_lm and the hooks turn into their messages
+// whether a table goes with a vocabulary of V ids whose <eot> is `eot` and whose first timestamp is `ts_begin`: what the
+// launcher asks, what fw_generate_lm / fw_score_lm and the hooks turn into their messages
 bool ngram_geometry_ok(const int* ngram_tab, int V, int eot, int ts_begin);
+
+// ---- the logit pre-passes: the kernels above, which rewrite the logits in front of the rules kernel (decode steps) or the
+//      scoring kernel (fw_score) ----
+// THE statement of the kinds and of the order they are applied in.  The boost comes first: everything below sees the boosted
+// logits.  Then the language model: what is constrained and ranked below is the fused distribution.  Then the constraint
+// list: what it does not allow is -inf before the rules look — or the automaton, in the same place (no call carries both).
+enum PrePass { PRE_BOOST, PRE_LM, PRE_CONSTRAIN, PRE_AUTOMATON, PRE_KINDS };
+// One launcher per kind, in either ROW FORM.  src.tab == null, the decode step: gp.R rows, row r reads its history from
+// the parity half of hist2 that *src.d_step selects (n = step), rows of chunks with src.done[r / gp.K] are skipped; `rows`
+// is not read.  Otherwise the score form, in front of launch_score and with its row addressing: `rows` rows, rows without a
+// target (target < 0) are skipped, the history is the ScoreRow's; every n <= n_text_ctx is the caller's to guarantee.
+// logits [rows of the form][gp.V].  A null table, no rows, or a geometry the kernel does not take: nothing is launched.
+using PrePassLaunch = void (*)(hipStream_t, const GenDev&, float*, const int*, const RowSource&, int);
+static inline PrePassLaunch prepass_launcher(int kind) {
+  switch (kind) {
+    case PRE_BOOST: return launch_boost;
+    case PRE_LM: return launch_ngram;
+    case PRE_CONSTRAIN: return launch_constrain;
+    case PRE_AUTOMATON: return launch_automaton;
+  }
+  return nullptr;
+}
+// every kind with a table, in the order of the enum; a null table: the kind is not part of this run / call
+static inline void launch_prepasses(hipStream_t st, const GenDev& gp, float* logits, const int* const tabs[PRE_KINDS],
+                                    const RowSource& src, int rows) {
+  for (int k = 0; k < PRE_KINDS; ++k)
+    if (tabs[k]) prepass_launcher(k)(st, gp, logits, tabs[k], src, rows);
+}
 
 }  // namespace fwd
 

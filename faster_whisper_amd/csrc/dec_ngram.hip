@@ -187,18 +187,13 @@ bool ngram_geometry_ok(const int* tab, int V, int eot, int ts_begin) {
   return ngram_gp_ok(V, eot, ts_begin) && tab[2] == V && tab[3] == eot && tab[6] <= eot;
 }
 
-void launch_ngram_step(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const int* hist2, const int* d_step,
-                       const int* done) {
-  if (!tab || gp.R <= 0 || !ngram_gp_ok(gp.V, gp.eot, gp.ts_begin)) return;
-  const RowSource src{hist2, d_step, done, nullptr, 0, 0, 1};
-  dec_ngram_kernel<false><<<gp.R, NGRAM_THREADS, 0, st>>>(logits, tab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot, gp.ts_begin, src);
-}
-
-void launch_ngram_score(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const ScoreRow* rows_tab,
-                        int tab_stride, int pos0, int nb, int rows, const int* hist_pool) {
-  if (!tab || rows <= 0 || !ngram_gp_ok(gp.V, gp.eot, gp.ts_begin)) return;
-  const RowSource src{hist_pool, nullptr, nullptr, rows_tab, tab_stride, pos0, nb};
-  dec_ngram_kernel<true><<<rows, NGRAM_THREADS, 0, st>>>(logits, tab, gp.V, 1, rows, gp.n_text_ctx, gp.eot, gp.ts_begin, src);
+void launch_ngram(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows) {
+  const bool step = src.tab == nullptr;
+  if (!tab || (step ? gp.R : rows) <= 0 || !ngram_gp_ok(gp.V, gp.eot, gp.ts_begin)) return;
+  if (step)
+    dec_ngram_kernel<false><<<gp.R, NGRAM_THREADS, 0, st>>>(logits, tab, gp.V, gp.K, gp.R, gp.n_text_ctx, gp.eot, gp.ts_begin, src);
+  else
+    dec_ngram_kernel<true><<<rows, NGRAM_THREADS, 0, st>>>(logits, tab, gp.V, 1, rows, gp.n_text_ctx, gp.eot, gp.ts_begin, src);
 }
 
 // one transition in plain C++: a binary search over the node's child pairs

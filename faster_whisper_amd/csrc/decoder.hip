@@ -34,6 +34,35 @@ namespace fw {
 
 using fwd::FIN_CAP;
 using fwd::GenDev;
+using fwd::PRE_KINDS;
+
+// What the host code knows of a pre-pass kind (dec_kernels.h: PrePass), one entry per kind in the order of the enum.
+struct PreKind {
+  fwd::PrePass kind;
+  const char* name;          // in messages
+  const char* the;           // ... with its article
+  const char* needs_rules;   // what fw_score_lm answers without rules
+  int max_words;             // the lane's buffer is allocated once, at this size; 0: sized by the table, grown by replacement
+  int GenDev::*flag;         // non-zero in a run whose step launches the kind's kernel: part of the step graph's key
+};
+static constexpr PreKind kPreKinds[] = {
+    {fwd::PRE_BOOST, "boost", "the boost list", "a boost list needs rules: the boost is the first step of the decoding rules",
+     fwd::BOOST_TABLE_MAX_WORDS, &GenDev::boost},
+    // (a language model can be megabytes: its buffer is sized by the largest model so far, not by a limit of the kind)
+    {fwd::PRE_LM, "language-model", "the language model",
+     "a language model needs rules: the fusion is a step of the decoding rules", 0, &GenDev::lm},
+    {fwd::PRE_CONSTRAIN, "constraint", "the constraint list",
+     "a constraint list needs rules: the constraint is a step of the decoding rules", fwd::CONSTRAIN_TABLE_MAX_WORDS,
+     &GenDev::constrain},
+    {fwd::PRE_AUTOMATON, "automaton", "the automaton", "an automaton needs rules: the automaton is a step of the decoding rules",
+     fwd::AUTOMATON_TABLE_MAX_WORDS, &GenDev::automaton},
+};
+constexpr bool pre_kinds_follow_the_enum() {
+  for (int k = 0; k < PRE_KINDS; ++k)
+    if (kPreKinds[k].kind != k) return false;
+  return true;
+}
+static_assert(sizeof(kPreKinds) / sizeof(kPreKinds[0]) == PRE_KINDS && pre_kinds_follow_the_enum(), "one entry per kind");
 
 // rows of a merged decode run above which a second, nearly empty round of workgroups starts (dec_kernels.hip)
 #define DEC_RUN_MAX_ROWS 1600
@@ -100,19 +129,14 @@ struct GenWorkspace {
   GrowBuf<int> alt_out_tok;              // the gather's output: [returned hypotheses][budget + 1][n_alt]
   GrowBuf<float> alt_out_lp;
   GrowBuf<fwd::AltHyp> alt_hyps;
-  // phrase boosting (fw_generate_boost): the run's compiled table.  Nothing until the first boosted run, which allocates it
-  // at its maximum size (fwd::BOOST_TABLE_MAX_WORDS): the pointer never changes afterwards, so a cached step graph stays
-  // valid whatever list the next run brings — the sizes travel in the table's header — and no graph holds a caller's pointer.
-  GrowBuf<int> boost_tab;
-  // constrained decoding (fw_generate_constrain): the run's compiled table, held the same way (allocated once, by the first
-  // constrained run, at fwd::CONSTRAIN_TABLE_MAX_WORDS)
-  GrowBuf<int> constrain_tab;
-  // automaton-constrained decoding (fw_generate_automaton): likewise, at fwd::AUTOMATON_TABLE_MAX_WORDS
-  GrowBuf<int> automaton_tab;
-  // language-model fusion (fw_generate_lm): the run's compiled table.  It can be megabytes, so it is sized by the largest
-  // model so far (run_lm_ensure) and not by the kind's limit.  A step graph holds the pointer by value: growing the buffer
-  // drops the graphs that fuse.
-  GrowBuf<int> lm_tab;
+  // the logit pre-passes: the compiled table of each kind the run — or, on lane 0, the fw_score_lm call — brings
+  // (pre_tables_to_lane).  Nothing until the first run with a table of the kind.  A kind with PreKind::max_words is then
+  // allocated at that size: the pointer never changes afterwards, so a cached step graph stays valid whatever table the next
+  // run brings — the sizes travel in the table's header — and no graph holds a caller's pointer.  A kind without is sized
+  // by its largest table so far: a step graph holds the pointer by value, and growing the buffer drops the graphs with the
+  // kind's flag.  The contents are the last user's: whoever holds the lane writes its own tables before it reads them, and
+  // walks the buffers of those kinds only (run_step) — so scoring and decode runs share the buffers of lane 0.
+  GrowBuf<int> pre_tab[PRE_KINDS];
   int *done = nullptr, *n_done = nullptr, *n_fin = nullptr, *fin_tok = nullptr, *fin_len = nullptr;
   float *fin_score = nullptr, *fin_cum = nullptr;
   int* d_step = nullptr;
@@ -592,14 +616,10 @@ static int run_step(Model* m, DecodeLane* lane, const GenDev& gp, const StepCfg&
   if (s.beam_tail) {
     ProfScope ps(lane->prof, PF_DEC_SAMPLE, 0, 8.0 * rows * c.n_vocab, st);
     const bool alt = gp.n_alt > 0;   // (run_alt_ensure has sized the buffers for this run)
-    // the boost comes first: the rules below see the boosted logits (run_init_state has filled the table for this run)
-    if (gp.boost) fwd::launch_boost_step(st, gp, g->logits, g->boost_tab.p, g->hist2, g->d_step, g->done);
-    // then the language model: what is constrained and ranked below is the fused distribution
-    if (gp.lm) fwd::launch_ngram_step(st, gp, g->logits, g->lm_tab.p, g->hist2, g->d_step, g->done);
-    // then the constraint: what the list does not allow is -inf before the rules look
-    if (gp.constrain) fwd::launch_constrain_step(st, gp, g->logits, g->constrain_tab.p, g->hist2, g->d_step, g->done);
-    // or the automaton, in the same place (no call carries both)
-    if (gp.automaton) fwd::launch_automaton_step(st, gp, g->logits, g->automaton_tab.p, g->hist2, g->d_step, g->done);
+    // the pre-passes of this run (generate_run has filled their tables; a buffer left from another run is not walked)
+    const int* pre_tabs[PRE_KINDS];
+    for (int k = 0; k < PRE_KINDS; ++k) pre_tabs[k] = gp.*kPreKinds[k].flag ? g->pre_tab[k].p : nullptr;
+    fwd::launch_prepasses(st, gp, g->logits, pre_tabs, fwd::step_rows(g->hist2, g->d_step, g->done), 0);
     fwd::launch_logits_process(st, gp, g->logits, g->sup_bits, g->hist2, g->cum2, g->d_step, g->done, g->cand_val,
                                g->cand_tok, g->cand_lp, g->smp_tab, alt ? g->alt_tok.p : nullptr,
                                alt ? g->alt_lp.p : nullptr, gp.trunc ? g->trunc_tab : nullptr);
@@ -729,10 +749,9 @@ struct GenRequest {
   float* out_alt_logprobs = nullptr;
   int32_t* out_end_alt_ids = nullptr;    // [B, num_hypotheses, n_alt]
   float* out_end_alt_logprobs = nullptr;
-  const fw_boost* boost = nullptr;       // a non-empty boost list | null (fw_generate_boost turns an empty list into null)
-  const fw_constraint* constraint = nullptr;   // a non-empty constraint list | null (likewise)
-  const fw_automaton* automaton = nullptr;     // an automaton | null; never beside a constraint list
-  const fw_ngram* lm = nullptr;                // a language model to fuse | null
+  // per pre-pass kind: the call's table | null without one or with an empty list (prepass_check); never both a constraint
+  // list and an automaton
+  const fw_phrase_table* pre[PRE_KINDS] = {};
   // truncated sampling (fw_generate_trunc): the limits on this call's draws, (0, 1) = none.  Like temperature and seed they
   // need NOT agree between the calls of a run: every row reads its call's from the run's TruncRow table.
   int top_k = 0;
@@ -745,13 +764,27 @@ struct GenRequest {
   bool done = false;
 };
 
-// The run's phrase table of one kind into its lane buffer.  The buffer is allocated once, at the kind's largest table
-// (max_words): the pointer a cached step graph holds never changes.
-static int32_t phrase_table_to_lane(GrowBuf<int>& dst, const fw_phrase_table& t, int max_words, const char* what,
-                                    hipStream_t st) {
-  FW_CHECK_ARG(t.table.size() <= (size_t)max_words, "%s table of %zu words", what, t.table.size());
-  if (int rc = dst.ensure(max_words)) return rc;
-  FW_HIP(hipMemcpyAsync(dst.p, t.table.data(), t.table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+// The tables of a decode run, or of a score call, into the buffers of its lane (GenWorkspace::pre_tab).  The lane is idle:
+// its mutex is held.  A buffer that has to grow is replaced, as the alternatives' buffers are (run_alt_ensure): the stream
+// is waited for, and the step graphs with the kind's flag hold the old pointer and go with it.  FW_ENOMEM when the device
+// has no room.  Kinds without a table allocate nothing and touch nothing.
+static int pre_tables_to_lane(DecodeLane* lane, const fw_phrase_table* const pre[PRE_KINDS], const HipFail& fail) {
+  GenWorkspace* g = lane->gen;
+  for (int k = 0; k < PRE_KINDS; ++k) {
+    if (!pre[k]) continue;
+    const PreKind& kind = kPreKinds[k];
+    const std::vector<int32_t>& t = pre[k]->table;
+    FW_CHECK_ARG(!kind.max_words || t.size() <= (size_t)kind.max_words, "%s table of %zu words", kind.name, t.size());
+    GrowBuf<int>& buf = g->pre_tab[k];
+    const int64_t words = kind.max_words ? kind.max_words : (int64_t)t.size();
+    if (words > buf.cap) {
+      FW_HIP_AS(fail, hipStreamSynchronize(lane->stream));
+      for (GraphSlot& gs : g->graphs)
+        if (gs.exec && gs.key.*kind.flag) { (void)hipGraphExecDestroy(gs.exec); gs.exec = nullptr; gs.stamp = 0; }
+      if (int rc = buf.ensure(words)) return rc;
+    }
+    FW_HIP_AS(fail, hipMemcpyAsync(buf.p, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice, lane->stream));
+  }
   return FW_OK;
 }
 
@@ -768,9 +801,8 @@ static int32_t phrase_table_to_lane(GrowBuf<int>& dst, const fw_phrase_table& t,
 // of the table.
 static bool mergeable(const GenRequest& a, const GenRequest& b, int n_text_ctx) {
   if (a.sampling != b.sampling) return false;
-  if (!fwd::phrase_table_same(a.boost, b.boost) || !fwd::phrase_table_same(a.constraint, b.constraint) ||
-      !fwd::phrase_table_same(a.automaton, b.automaton) || !fwd::phrase_table_same(a.lm, b.lm))
-    return false;
+  for (int k = 0; k < PRE_KINDS; ++k)
+    if (!fwd::phrase_table_same(a.pre[k], b.pre[k])) return false;
   const fw_gen_opts &x = *a.o, &y = *b.o;
   // a call whose prompt already fills max_length decodes nothing (and may lie beyond the run's cache extent): it shares
   // a run only with calls of its own prompt length and <sot> position, as before
@@ -909,10 +941,9 @@ static int run_plan(const Model* m, const GenWorkspace* g, const std::vector<Gen
   gp.ragged = ragged ? 1 : 0; gp.reach = ragged ? reach : 0;   // (part of the step graph's key)
   gp.sample = sampling ? 1 : 0;
   gp.n_alt = n_alt;
-  gp.boost = r0.boost ? 1 : 0;   // (mergeable calls agree on the list)
-  gp.constrain = r0.constraint ? 1 : 0;   // (likewise)
-  gp.automaton = r0.automaton ? fwd::automaton_lds_class(r0.automaton->table.size()) : 0;   // (likewise; 1 / 2: the kernel's LDS)
-  gp.lm = r0.lm ? 1 : 0;   // (likewise)
+  for (int k = 0; k < PRE_KINDS; ++k) gp.*kPreKinds[k].flag = r0.pre[k] ? 1 : 0;   // (mergeable calls agree on the tables)
+  if (r0.pre[fwd::PRE_AUTOMATON])   // (1 / 2: the kernel's LDS allocation)
+    gp.automaton = fwd::automaton_lds_class(r0.pre[fwd::PRE_AUTOMATON]->table.size());
   gp.trunc = (sampling && trunc) ? 1 : 0;   // (a run without a truncating call: today's kernels and graphs)
   // temperature and seed are per CALL: a sampling run reads them from g->smp_tab (filled below), a run of one call
   // included, and they stay out of the step graph's key — sampling runs of one size share a graph whatever their seeds
@@ -943,18 +974,6 @@ static int run_alt_ensure(DecodeLane* lane, const RunPlan& pl) {
     if ((rc = g->alt_tok.ensure(n_alt)) || (rc = g->alt_lp.ensure(n_alt)) || (rc = g->fin_path.ensure(n_path))) return rc;
   }
   return FW_OK;
-}
-
-// Language-model fusion: the lane's table buffer holds `words` words, grown by replacement as the alternatives' buffers
-// are (the lane is idle) — the step graphs that fuse hold the old pointer and go with it.  FW_ENOMEM when the device has no
-// room: the calls of the run get it.  Runs without a model allocate nothing and touch nothing here.
-static int lm_table_ensure(DecodeLane* lane, size_t words) {
-  GenWorkspace* g = lane->gen;
-  if ((int64_t)words <= g->lm_tab.cap) return FW_OK;
-  FW_HIP(hipStreamSynchronize(lane->stream));
-  for (GraphSlot& gs : g->graphs)
-    if (gs.exec && gs.key.lm) { (void)hipGraphExecDestroy(gs.exec); gs.exec = nullptr; gs.stamp = 0; }
-  return g->lm_tab.ensure((int64_t)words);
 }
 
 // Phase 2: the run's blocks of the cross-attention pool (all at once; `hold` keeps them to the end of the run), the
@@ -999,18 +1018,6 @@ static int run_init_state(Model* m, DecodeLane* lane, const std::vector<GenReque
   FW_HIP(hipMemsetAsync(g->no_speech, 0, Rr * sizeof(float), st));
   const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
   FW_HIP(hipMemcpyAsync(g->sup_bits, mask.data(), mask.size() * sizeof(mask[0]), hipMemcpyHostToDevice, st));
-  if (pl.gp.boost)
-    if (int rc = phrase_table_to_lane(g->boost_tab, *reqs[0]->boost, fwd::BOOST_TABLE_MAX_WORDS, "boost", st)) return rc;
-  if (pl.gp.constrain)
-    if (int rc = phrase_table_to_lane(g->constrain_tab, *reqs[0]->constraint, fwd::CONSTRAIN_TABLE_MAX_WORDS, "constraint", st))
-      return rc;
-  if (pl.gp.automaton)
-    if (int rc = phrase_table_to_lane(g->automaton_tab, *reqs[0]->automaton, fwd::AUTOMATON_TABLE_MAX_WORDS, "automaton", st))
-      return rc;
-  if (pl.gp.lm) {   // (generate_run has sized the buffer: lm_table_ensure)
-    const std::vector<int32_t>& t = reqs[0]->lm->table;
-    FW_HIP(hipMemcpyAsync(g->lm_tab.p, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
   // prompt tokens transposed to [pos][bx]; first-step tokens replicated per beam.  Ragged: positions at and beyond a
   // chunk's last prompt token are padded with that token (see the prompt forward)
   ptok.assign((size_t)Pmax * Bx, 0);
@@ -1253,7 +1260,7 @@ static int generate_run(Model* m, DecodeLane* lane, const std::vector<GenRequest
   PoolHold hold{m->xpool, {}, lane->stream};
   std::vector<int> slots, ptok;
   if ((rc = run_alt_ensure(lane, pl))) return rc;
-  if (pl.gp.lm && (rc = lm_table_ensure(lane, reqs[0]->lm->table.size()))) return rc;
+  if ((rc = pre_tables_to_lane(lane, reqs[0]->pre, HipFail{FW_ENODEV, "decode run: table upload"}))) return rc;
   if ((rc = run_acquire_blocks(m, lane, reqs, hold, slots))) return rc;
   if ((rc = run_init_state(m, lane, reqs, pl, slots, ptok))) return rc;
   if ((rc = run_prompt_forward(m, lane, pl, ptok))) return rc;
@@ -1466,7 +1473,14 @@ int32_t fw_generate_trunc(fw_model* fm, const fw_tensor* enc_t, const int32_t* p
                                out_alt_logprobs, out_end_alt_ids, out_end_alt_logprobs);
 }
 
-// the model's vocabulary layout, as the two pre-pass kernels that hold a keep mask take it
+// a table of kind k goes with the model's vocabulary
+static int32_t pre_vocab_check(int k, const fw_phrase_table* t, const fw_config& c) {
+  FW_CHECK_ARG(t->n_vocab == c.n_vocab, "%s was built for a vocabulary of %d ids, the model has %d", kPreKinds[k].the, t->n_vocab,
+               c.n_vocab);
+  return FW_OK;
+}
+
+// the model's vocabulary layout, as the pre-pass kernels that hold a keep mask take it
 static int32_t keep_mask_geometry_check(const fw_config& c, const char* what) {
   FW_CHECK_ARG(c.tok_eot >= 0 && c.tok_eot < c.tok_timestamp_begin && c.tok_timestamp_begin <= c.n_vocab &&
                    c.n_vocab <= LP_SUP_WORDS * 64,
@@ -1475,75 +1489,102 @@ static int32_t keep_mask_geometry_check(const fw_config& c, const char* what) {
   return FW_OK;
 }
 
-// What fw_generate_automaton and fw_score_automaton refuse (include/fwamd.h), for the reasons constraint_check (below)
-// gives: an automaton for another vocabulary, and rules under which an accepted string cannot be reached or a row is left
-// without a live id.  States are named by their number, as the caller numbered them (records are in state order).
+// What a constraint list and an automaton refuse alike (include/fwamd.h): rules under which a string of theirs cannot be
+// reached or a row is left without a live id.  `o`: the call's options / the scoring rules.  The words of the messages:
+namespace {
+struct KeepNoun {
+  const char *a, *string, *stuck;   // "a constraint list", what it lists, the row that min_new_tokens would leave dead
+  const char *unit, *holds, *starts, *ids;   // "constraint phrase" <n> "holds" | "starts with" an id; "phrases" are text
+};
+static const KeepNoun kListNoun = {"a constraint list", "a listed phrase", "a row whose phrase is complete",
+                                   "constraint phrase", "holds", "starts with", "phrases"};
+static const KeepNoun kAutomatonNoun = {"an automaton", "an accepted string", "a row in an accepting state without out-edges",
+                                        "automaton state", "has an edge with", "has an edge with", "edges"};
+struct KeepCheck {
+  const KeepNoun& w;
+  const fw_config& c;
+  const fw_gen_opts* o;
+  std::vector<unsigned long long> mask;
+  // check_min_new: generate only (scoring does not read min_new_tokens)
+  int32_t options(bool check_min_new) {
+    FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "%s does not go with no_repeat_ngram_size %d: %s that repeats an n-gram would "
+                 "be unreachable", w.a, o->no_repeat_ngram_size, w.string);
+    FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "%s does not go with min_new_tokens %d: %s would have no live id",
+                 w.a, o->min_new_tokens, w.stuck);
+    mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
+    return FW_OK;
+  }
+  // id t of unit `unit` (a phrase, a state); first: an id a string can start with
+  int32_t token(int unit, int t, bool first) const {
+    FW_CHECK_ARG(t < c.tok_eot, "%s %d %s id %d: %s are text, ids below <eot> = %d", w.unit, unit, w.holds, t, w.ids, c.tok_eot);
+    FW_CHECK_ARG(!((mask[t >> 6] >> (t & 63)) & 1ull), "%s %d %s id %d, which the suppress list forbids", w.unit, unit, w.holds, t);
+    if (first && o->suppress_blank)
+      for (int k = 0; k < c.n_suppress_begin; ++k)
+        FW_CHECK_ARG(t != c.suppress_begin[k], "%s %d %s id %d, which suppress_blank forbids at the first step", w.unit, unit,
+                     w.starts, t);
+    return FW_OK;
+  }
+};
+}  // namespace
+
+// What fw_generate_automaton and fw_score_automaton refuse: an automaton for another vocabulary, and what KeepCheck
+// refuses.  States are named by their number, as the caller numbered them (records are in state order).
 static int32_t automaton_check(const fw_automaton* at, const fw_config& c, const fw_gen_opts* o, bool check_min_new) {
-  FW_CHECK_ARG(at->n_vocab == c.n_vocab, "the automaton was built for a vocabulary of %d ids, the model has %d", at->n_vocab,
-               c.n_vocab);
-  if (int rc = keep_mask_geometry_check(c, "automaton")) return rc;
+  if (int rc = pre_vocab_check(fwd::PRE_AUTOMATON, at, c)) return rc;
+  if (int rc = keep_mask_geometry_check(c, kPreKinds[fwd::PRE_AUTOMATON].name)) return rc;
   FW_CHECK_ARG(c.n_text_ctx <= fwd::AUTOMATON_MAX_HIST, "a text context of %d positions is more than the automaton kernel's %d",
                c.n_text_ctx, fwd::AUTOMATON_MAX_HIST);
-  FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "an automaton does not go with no_repeat_ngram_size %d: an accepted string "
-               "that repeats an n-gram would be unreachable", o->no_repeat_ngram_size);
-  FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "an automaton does not go with min_new_tokens %d: a row in an "
-               "accepting state without out-edges would have no live id", o->min_new_tokens);
-  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
+  KeepCheck kc{kAutomatonNoun, c, o, {}};
+  if (int rc = kc.options(check_min_new)) return rc;
   const int32_t* tab = at->table.data();
   int rec = fwd::AUTOMATON_HDR_WORDS;
   for (int s = 0; s < tab[0]; rec += 2 + 2 * tab[rec], ++s)
-    for (int i = 0; i < tab[rec]; ++i) {
-      const int t = tab[rec + 2 + 2 * i];
-      FW_CHECK_ARG(t < c.tok_eot, "automaton state %d has an edge with id %d: edges are text, ids below <eot> = %d", s, t,
-                   c.tok_eot);
-      FW_CHECK_ARG(!((mask[t >> 6] >> (t & 63)) & 1ull), "automaton state %d has an edge with id %d, which the suppress list "
-                   "forbids", s, t);
-      if (s == 0 && o->suppress_blank)
-        for (int k = 0; k < c.n_suppress_begin; ++k)
-          FW_CHECK_ARG(t != c.suppress_begin[k], "automaton state 0 has an edge with id %d, which suppress_blank forbids at "
-                       "the first step", t);
-    }
+    for (int i = 0; i < tab[rec]; ++i)
+      if (int rc = kc.token(s, tab[rec + 2 + 2 * i], s == 0)) return rc;
   return FW_OK;
 }
 
-// What fw_generate_constrain and fw_score_constrain refuse (include/fwamd.h): a list for another vocabulary, and rules
-// under which a listed phrase cannot be reached or a row is left without a live id.  `o`: the call's options / the scoring
-// rules; check_min_new: generate only (scoring does not read min_new_tokens).
+// What fw_generate_constrain and fw_score_constrain refuse: a list for another vocabulary, and what KeepCheck refuses.
+// Phrases are named by the index the caller gave them.
 static int32_t constraint_check(const fw_constraint* ct, const fw_config& c, const fw_gen_opts* o, bool check_min_new) {
-  FW_CHECK_ARG(ct->n_vocab == c.n_vocab, "the constraint list was built for a vocabulary of %d ids, the model has %d",
-               ct->n_vocab, c.n_vocab);
+  if (int rc = pre_vocab_check(fwd::PRE_CONSTRAIN, ct, c)) return rc;
   if (!fwd::phrase_list_live(ct)) return FW_OK;   // (an empty list: no constraint, nothing to refuse)
-  if (int rc = keep_mask_geometry_check(c, "constraint")) return rc;
-  FW_CHECK_ARG(o->no_repeat_ngram_size <= 0, "a constraint list does not go with no_repeat_ngram_size %d: a listed phrase "
-               "that repeats an n-gram would be unreachable", o->no_repeat_ngram_size);
-  FW_CHECK_ARG(!check_min_new || o->min_new_tokens <= 0, "a constraint list does not go with min_new_tokens %d: a row "
-               "whose phrase is complete would have no live id", o->min_new_tokens);
-  const std::vector<unsigned long long> mask = fwd::suppress_mask(o->suppress_tokens, o->n_suppress_tokens, c.n_vocab);
+  if (int rc = keep_mask_geometry_check(c, kPreKinds[fwd::PRE_CONSTRAIN].name)) return rc;
+  KeepCheck kc{kListNoun, c, o, {}};
+  if (int rc = kc.options(check_min_new)) return rc;
   const fwd::ConstrainView cv = fwd::constrain_view(ct->table.data());
   for (int j = 0; j < cv.P; ++j)
-    for (int i = cv.off[j]; i < cv.off[j + 1]; ++i) {
-      const int t = cv.tok[i];
-      FW_CHECK_ARG(t < c.tok_eot, "constraint phrase %d holds id %d: phrases are text, ids below <eot> = %d", ct->first[j], t,
-                   c.tok_eot);
-      FW_CHECK_ARG(!((mask[t >> 6] >> (t & 63)) & 1ull), "constraint phrase %d holds id %d, which the suppress list forbids",
-                   ct->first[j], t);
-      if (i == cv.off[j] && o->suppress_blank)
-        for (int k = 0; k < c.n_suppress_begin; ++k)
-          FW_CHECK_ARG(t != c.suppress_begin[k], "constraint phrase %d starts with id %d, which suppress_blank forbids at "
-                       "the first step", ct->first[j], t);
-    }
+    for (int i = cv.off[j]; i < cv.off[j + 1]; ++i)
+      if (int rc = kc.token(ct->first[j], cv.tok[i], i == cv.off[j])) return rc;
   return FW_OK;
 }
 
 // What fw_generate_lm and fw_score_lm refuse of a language model (include/fwamd.h): one for another vocabulary, or whose
 // end-of-sentence id or n-gram ids do not fit the model's text ids — the kernel adds to the ids up to <eot> and no further.
 static int32_t ngram_check(const fw_ngram* lm, const fw_config& c) {
-  FW_CHECK_ARG(lm->n_vocab == c.n_vocab, "the language model was built for a vocabulary of %d ids, the model has %d",
-               lm->n_vocab, c.n_vocab);
-  if (int rc = keep_mask_geometry_check(c, "language-model")) return rc;
+  if (int rc = pre_vocab_check(fwd::PRE_LM, lm, c)) return rc;
+  if (int rc = keep_mask_geometry_check(c, kPreKinds[fwd::PRE_LM].name)) return rc;
   FW_CHECK_ARG(lm->table[3] == c.tok_eot, "the language model's eos_id is %d, the model's <eot> is %d", lm->table[3], c.tok_eot);
   FW_CHECK_ARG(lm->table[6] <= c.tok_eot, "the language model holds an n-gram with id %d: n-grams are text, ids up to <eot> = %d",
                lm->table[6], c.tok_eot);
+  return FW_OK;
+}
+
+// The extras of a call, pre[kind] as the caller passed them (null: none), against the model and the call's options / the
+// scoring rules (`o`; check_min_new: generate only): what fw_generate_lm and fw_score_lm refuse of them.  An empty list
+// does nothing: its entry becomes null, and the call is one without it.  ("a constraint list or an automaton, not both" is
+// the first thing either entry point checks, in front of its null arguments.)
+static int32_t prepass_check(const fw_config& c, const fw_gen_opts* o, bool check_min_new, const fw_phrase_table* pre[PRE_KINDS]) {
+  if (pre[fwd::PRE_BOOST])
+    if (int rc = pre_vocab_check(fwd::PRE_BOOST, pre[fwd::PRE_BOOST], c)) return rc;
+  if (pre[fwd::PRE_CONSTRAIN])
+    if (int rc = constraint_check(static_cast<const fw_constraint*>(pre[fwd::PRE_CONSTRAIN]), c, o, check_min_new)) return rc;
+  if (pre[fwd::PRE_AUTOMATON])
+    if (int rc = automaton_check(static_cast<const fw_automaton*>(pre[fwd::PRE_AUTOMATON]), c, o, check_min_new)) return rc;
+  if (pre[fwd::PRE_LM])
+    if (int rc = ngram_check(static_cast<const fw_ngram*>(pre[fwd::PRE_LM]), c)) return rc;
+  for (int k = 0; k < PRE_KINDS; ++k)
+    if (!fwd::phrase_list_live(pre[k])) pre[k] = nullptr;   // (an automaton has a state, a model an order: never empty)
   return FW_OK;
 }
 
@@ -1593,14 +1634,10 @@ int32_t fw_generate_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   FW_CHECK_ARG(decoder_of(*enc) == dm, "encoder output belongs to a different model");
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= dm->max_batch, "batch %d exceeds max_batch %d", B, dm->max_batch);
-  FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
-               boost ? boost->n_vocab : 0, c.n_vocab);
-  if (constraint)
-    if (int rc = constraint_check(constraint, c, o, true)) return rc;
-  if (automaton)
-    if (int rc = automaton_check(automaton, c, o, true)) return rc;
-  if (lm)
-    if (int rc = ngram_check(lm, c)) return rc;
+  GenRequest req;
+  req.pre[fwd::PRE_BOOST] = boost; req.pre[fwd::PRE_LM] = lm;
+  req.pre[fwd::PRE_CONSTRAIN] = constraint; req.pre[fwd::PRE_AUTOMATON] = automaton;
+  if (int rc = prepass_check(c, o, true, req.pre)) return rc;
   const int K = o->beam_size;
   FW_CHECK_ARG(K >= 1 && K <= dm->max_beam, "beam_size %d not in [1, max_beam=%d]", K, dm->max_beam);
   // random sampling (the sequential path's temperature fallback, transcribe.py:1433-1439): beam_size 1,
@@ -1643,7 +1680,6 @@ int32_t fw_generate_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
     std::fill(out_end_alt_logprobs, out_end_alt_logprobs + n_end, 0.f);
   }
 
-  GenRequest req;
   req.enc = enc; req.prompts = prompts; req.prompt_offsets = prompt_offsets; req.B = B; req.P = P; req.o = o;
   req.out_ids = out_ids; req.out_lens = out_lens; req.out_scores = out_scores; req.out_no_speech = out_no_speech;
   req.out_token_logprobs = out_token_logprobs; req.out_end_logprobs = out_end_logprobs;
@@ -1651,10 +1687,6 @@ int32_t fw_generate_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   req.out_end_alt_ids = out_end_alt_ids; req.out_end_alt_logprobs = out_end_alt_logprobs;
   req.sampling = sampling;
   req.top_k = top_k; req.top_p = top_p;
-  req.boost = fwd::phrase_list_live(boost) ? boost : nullptr;   // (an empty list does nothing: the call is a plain one)
-  req.constraint = fwd::phrase_list_live(constraint) ? constraint : nullptr;   // (likewise)
-  req.automaton = automaton;
-  req.lm = lm;
   for (int b = 0; b < B; ++b) {
     // every prompt of the call must agree on what switches the decoding rules (true for every call site of the
     // reference: one prompt per batch, language token swapped in place)
@@ -2042,8 +2074,8 @@ extern "C" int32_t fw_score_automaton(fw_model* fm, const fw_tensor* enc_t, cons
                      nullptr, out_token_logprobs, out_best_ids, out_best_logprobs);
 }
 
-// One score call with every extra: dec_boost_kernel, dec_ngram_kernel, then dec_constrain_kernel or dec_automaton_kernel, on
-// the block's logits (recomputed per block) in front of the scoring kernel.  What every other score entry point calls.
+// One score call with every extra: the pre-passes (dec_kernels.h: PrePass) on the block's logits (recomputed per block) in
+// front of the scoring kernel.  What every other score entry point calls.
 extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prompts, const int32_t* prompt_offsets,
                                const int32_t* targets, const int32_t* target_offsets, int32_t B, int32_t H,
                                const fw_gen_opts* rules, const fw_boost* boost, const fw_constraint* constraint,
@@ -2051,10 +2083,9 @@ extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32
                                int32_t* out_best_ids, float* out_best_logprobs) {
   FW_CHECK_ARG(!constraint || !automaton, "a call takes a constraint list or an automaton, not both");
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
-  FW_CHECK_ARG(!lm || rules, "a language model needs rules: the fusion is a step of the decoding rules");
-  FW_CHECK_ARG(!boost || rules, "a boost list needs rules: the boost is the first step of the decoding rules");
-  FW_CHECK_ARG(!constraint || rules, "a constraint list needs rules: the constraint is a step of the decoding rules");
-  FW_CHECK_ARG(!automaton || rules, "an automaton needs rules: the automaton is a step of the decoding rules");
+  const fw_phrase_table* pre[PRE_KINDS];
+  pre[fwd::PRE_BOOST] = boost; pre[fwd::PRE_LM] = lm; pre[fwd::PRE_CONSTRAIN] = constraint; pre[fwd::PRE_AUTOMATON] = automaton;
+  for (int k = 0; k < PRE_KINDS; ++k) FW_CHECK_ARG(!pre[k] || rules, "%s", kPreKinds[k].needs_rules);
   FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
   Model* m = decoder_of(&fm->impl);
   const Tensor* enc = &enc_t->impl;
@@ -2062,16 +2093,7 @@ extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32
   FW_CHECK_ARG(decoder_of(*enc) == m, "encoder output belongs to a different model");
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= m->max_batch, "batch %d exceeds max_batch %d", B, m->max_batch);
-  FW_CHECK_ARG(!boost || boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
-               boost ? boost->n_vocab : 0, c.n_vocab);
-  if (constraint)
-    if (int crc = constraint_check(constraint, c, rules, false)) return crc;
-  if (automaton)
-    if (int arc = automaton_check(automaton, c, rules, false)) return arc;
-  if (lm)
-    if (int lrc = ngram_check(lm, c)) return lrc;
-  if (!fwd::phrase_list_live(boost)) boost = nullptr;   // (an empty list does nothing)
-  if (!fwd::phrase_list_live(constraint)) constraint = nullptr;
+  if (int prc = prepass_check(c, rules, false, pre)) return prc;
   FW_CHECK_ARG(H >= 1 && H <= m->max_beam, "%d candidates per chunk not in [1, max_beam=%d]", H, m->max_beam);
   FW_CHECK_ARG(c.n_vocab <= LP_SUP_WORDS * 64 && c.n_text_ctx <= 1024, "model too large for the scoring kernel");
   const int Bx = B * H;
@@ -2149,19 +2171,11 @@ extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32
       (rc = tmp.alloc(&lp_dev, n_out)))
     return rc;
   if (out_best_ids && ((rc = tmp.alloc(&bid_dev, n_out)) || (rc = tmp.alloc(&blp_dev, n_out)))) return rc;
-  int *boost_dev = nullptr, *constrain_dev = nullptr, *automaton_dev = nullptr;
-  const std::pair<const fw_phrase_table*, int**> lists[] = {
-      {boost, &boost_dev}, {constraint, &constrain_dev}, {automaton, &automaton_dev}};
   if (automaton) gp.automaton = fwd::automaton_lds_class(automaton->table.size());
-  if (lm) {   // (into the lane's buffer, as a decode run's: the lane is this call's until it returns)
-    if ((rc = lm_table_ensure(lane, lm->table.size()))) return rc;
-    FW_HIP_AS(setup_fail, hipMemcpyAsync(g->lm_tab.p, lm->table.data(), lm->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  for (const auto& [list, dev] : lists) {   // (null: no list of that kind, its pre-pass is not launched)
-    if (!list) continue;
-    if ((rc = tmp.alloc(dev, list->table.size()))) return rc;
-    FW_HIP_AS(setup_fail, hipMemcpyAsync(*dev, list->table.data(), list->table.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
+  // (into the lane's buffers, as a decode run's: the lane is this call's until it returns)
+  if ((rc = pre_tables_to_lane(lane, pre, setup_fail))) return rc;
+  const int* pre_tabs[PRE_KINDS];   // (null: no table of that kind, its pre-pass is not launched)
+  for (int k = 0; k < PRE_KINDS; ++k) pre_tabs[k] = pre[k] ? g->pre_tab[k].p : nullptr;
   FW_HIP_AS(setup_fail, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice, st));
   if (n_tgt) FW_HIP_AS(setup_fail, hipMemcpyAsync(hist_dev, targets + off0, n_tgt * sizeof(int), hipMemcpyHostToDevice, st));
   FW_HIP_AS(setup_fail, hipMemcpyAsync(g->prompt_dev, ptok.data(), ptok.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -2180,12 +2194,7 @@ extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32
       [&](int pos, int nb) {
         if (pos + nb - 1 < P - 1) return;
         ProfScope ps(lane->prof, PF_DEC_MISC, 0, 4.0 * Bx * nb * (double)c.n_vocab, st);
-        if (boost_dev) fwd::launch_boost_score(st, gp, g->logits, boost_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
-        if (lm) fwd::launch_ngram_score(st, gp, g->logits, g->lm_tab.p, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
-        if (constrain_dev)
-          fwd::launch_constrain_score(st, gp, g->logits, constrain_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
-        if (automaton_dev)
-          fwd::launch_automaton_score(st, gp, g->logits, automaton_dev, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev);
+        fwd::launch_prepasses(st, gp, g->logits, pre_tabs, fwd::score_rows(hist_dev, tab_dev, n_pos, pos, nb), Bx * nb);
         fwd::launch_score(st, gp, rules != nullptr, g->logits, g->sup_bits, tab_dev, n_pos, pos, nb, Bx * nb, hist_dev, lp_dev,
                           bid_dev, blp_dev);
       });

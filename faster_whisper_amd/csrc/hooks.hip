@@ -1157,11 +1157,9 @@ static int32_t boost_hist_check(int32_t rows, const int32_t* hist, const int32_t
 // or launched.  us_out != null: `iters` more launches on the same buffers, timed between two events after three untimed
 // ones (a pre-pass kernel that only writes -inf gives the same rows however often it runs; one that adds does not, and its
 // timed rows serve no comparison); *us_out = microseconds per launch.
-using PrepassStep = void (*)(hipStream_t, const GenDev&, float*, const int*, const int*, const int*, const int*);
-using PrepassScore = void (*)(hipStream_t, const GenDev&, float*, const int*, const fwd::ScoreRow*, int, int, int, int, const int*);
 static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                             int32_t K, const int32_t* done, int32_t form, const std::vector<int32_t>& table,
-                            PrepassStep launch_step, PrepassScore launch_score, int iters = 0, float* us_out = nullptr) {
+                            fwd::PrePassLaunch launch, int iters = 0, float* us_out = nullptr) {
   FW_CHECK_ARG(form == 0 ? (K >= 1 && K <= 16 && rows % K == 0) : K == 1, "bad K %d for form %d and %d rows", K, form, rows);
   if (int rc = boost_hist_check(rows, hist, hist_offsets, gp.n_text_ctx, gp.V)) return rc;
   const int n0 = hist_offsets[1];
@@ -1180,6 +1178,7 @@ static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, co
   if ((rc = db.upload(&d_lg, (const float*)logits, (size_t)rows * gp.V)) ||
       (rc = db.upload(&d_tab, (const int*)table.data(), table.size())))
     return rc;
+  fwd::RowSource src;
   if (form == 0) {
     const size_t NT = (size_t)gp.n_text_ctx;
     std::vector<int> h2(2 * (size_t)rows * NT, 0), dn((size_t)rows, 0);
@@ -1190,13 +1189,7 @@ static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, co
     if ((rc = db.upload(&d_hist, h2.data(), h2.size())) || (rc = db.upload(&d_step, &n0, 1)) ||
         (rc = db.upload(&d_done, dn.data(), dn.size())))
       return rc;
-    launch_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done);
-    if (us_out) {
-      float ms = 0.f;
-      const auto again = [&](int) { launch_step(nullptr, gp, d_lg, d_tab, d_hist, d_step, d_done); return 0; };
-      if ((rc = time_launches(nullptr, 3, iters, again, &ms))) return rc;
-      *us_out = 1000.f * ms / (float)iters;
-    }
+    src = fwd::step_rows(d_hist, d_step, d_done);
   } else {
     std::vector<fwd::ScoreRow> tab((size_t)rows);
     for (int r = 0; r < rows; ++r)
@@ -1208,13 +1201,14 @@ static int32_t prepass_rows(Model* m, GenDev gp, float* logits, int32_t rows, co
     if ((rc = db.upload(&d_rows, tab.data(), tab.size())) ||
         (rc = db.upload(&d_hist, n_hist ? hist : &zero, std::max<size_t>(1, n_hist))))
       return rc;
-    launch_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist);
-    if (us_out) {
-      float ms = 0.f;
-      const auto again = [&](int) { launch_score(nullptr, gp, d_lg, d_tab, d_rows, 1, 0, 1, rows, d_hist); return 0; };
-      if ((rc = time_launches(nullptr, 3, iters, again, &ms))) return rc;
-      *us_out = 1000.f * ms / (float)iters;
-    }
+    src = fwd::score_rows(d_hist, d_rows, 1, 0, 1);
+  }
+  launch(nullptr, gp, d_lg, d_tab, src, rows);
+  if (us_out) {
+    float ms = 0.f;
+    const auto again = [&](int) { launch(nullptr, gp, d_lg, d_tab, src, rows); return 0; };
+    if ((rc = time_launches(nullptr, 3, iters, again, &ms))) return rc;
+    *us_out = 1000.f * ms / (float)iters;
   }
   FW_HIP(hipGetLastError());
   FW_HIP(hipDeviceSynchronize());
@@ -1231,8 +1225,7 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.boost = 1;
-  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, boost->table, fwd::launch_boost_step,
-                      fwd::launch_boost_score);
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, boost->table, fwd::launch_boost);
 }
 
 // the same table walked on the host: no device, no model
@@ -1245,13 +1238,26 @@ int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist
   return FW_OK;
 }
 
-// what both constraint hooks check of the caller's vocabulary geometry and list
-static int32_t constrain_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, int32_t with_timestamps,
-                                    const fw_constraint* ct) {
+// what the constraint, automaton and language-model hooks check of the caller's vocabulary geometry (the keep mask's)
+static int32_t keep_geometry_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin) {
   FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
                "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
+  return FW_OK;
+}
+// ... and, the constraint and automaton hooks, of with_timestamps and of their table (`the`: "the constraint list")
+static int32_t keep_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, int32_t with_timestamps,
+                               const fw_phrase_table* t, const char* the) {
+  if (int rc = keep_geometry_hook_check(n_vocab, tok_eot, tok_ts_begin)) return rc;
   FW_CHECK_ARG(with_timestamps == 0 || with_timestamps == 1, "with_timestamps %d is not 0 / 1", with_timestamps);
-  FW_CHECK_ARG(ct->n_vocab == n_vocab, "the constraint list was built for a vocabulary of %d ids, not %d", ct->n_vocab, n_vocab);
+  FW_CHECK_ARG(t->n_vocab == n_vocab, "%s was built for a vocabulary of %d ids, not %d", the, t->n_vocab, n_vocab);
+  return FW_OK;
+}
+// the compiled table of a constraint list, an automaton or a language model, for the byte-equality the merge rule rests on:
+// *out_words = its size in 32-bit words; `out` (may be NULL) receives min(cap, size) words
+static int32_t table_words_out(const fw_phrase_table* t, int32_t* out, int32_t cap, int32_t* out_words) {
+  FW_CHECK_ARG(t && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
+  *out_words = (int32_t)t->table.size();
+  std::copy(t->table.begin(), t->table.begin() + std::min<size_t>((size_t)cap, t->table.size()), out);
   return FW_OK;
 }
 
@@ -1261,13 +1267,13 @@ int32_t fw_test_constrain_rows(fw_model* fm, float* logits, int32_t rows, int32_
                                int32_t K, const int32_t* done, int32_t form, const fw_constraint* constraint) {
   FW_CHECK_ARG(fm && logits && hist_offsets && constraint && rows >= 1, "bad arguments");
   FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
-  if (int rc = constrain_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint)) return rc;
+  if (int rc = keep_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint, "the constraint list")) return rc;
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1; gp.constrain = 1;
   gp.eot = tok_eot; gp.ts_begin = tok_ts_begin; gp.with_ts = with_timestamps;
   return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, constraint->table,
-                      fwd::launch_constrain_step, fwd::launch_constrain_score);
+                      fwd::launch_constrain);
 }
 
 // the same table walked on the host: no device, no model
@@ -1275,7 +1281,7 @@ int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab
                                     int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
                                     const fw_constraint* constraint) {
   FW_CHECK_ARG(logits && hist_offsets && constraint && rows >= 1, "bad arguments");
-  if (int rc = constrain_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint)) return rc;
+  if (int rc = keep_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, constraint, "the constraint list")) return rc;
   if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
   const int zero = 0;
   fwd::constrain_rows_host(constraint->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
@@ -1283,23 +1289,8 @@ int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab
   return FW_OK;
 }
 
-// the compiled table of a constraint list, for the byte-equality the merge rule rests on: *out_words = its size in 32-bit
-// words; `out` (may be NULL) receives min(cap, size) words
 int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, int32_t cap, int32_t* out_words) {
-  FW_CHECK_ARG(constraint && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
-  *out_words = (int32_t)constraint->table.size();
-  std::copy(constraint->table.begin(), constraint->table.begin() + std::min<size_t>((size_t)cap, constraint->table.size()), out);
-  return FW_OK;
-}
-
-// what the automaton hooks check of the caller's vocabulary geometry and automaton
-static int32_t automaton_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, int32_t with_timestamps,
-                                    const fw_automaton* at) {
-  FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
-               "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
-  FW_CHECK_ARG(with_timestamps == 0 || with_timestamps == 1, "with_timestamps %d is not 0 / 1", with_timestamps);
-  FW_CHECK_ARG(at->n_vocab == n_vocab, "the automaton was built for a vocabulary of %d ids, not %d", at->n_vocab, n_vocab);
-  return FW_OK;
+  return table_words_out(constraint, out, cap, out_words);
 }
 
 // The model gives the device and the text context (the stride of the step form's histories) only.
@@ -1311,7 +1302,7 @@ int32_t fw_test_automaton_rows(fw_model* fm, float* logits, int32_t rows, int32_
   FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
   FW_CHECK_ARG(staging >= 0 && staging <= 2, "staging %d is not 0 (the product's rule) / 1 (walk in L2) / 2 (stage in LDS)", staging);
   FW_CHECK_ARG(!us_out || (iters >= 1 && iters <= 10000), "%d timed launches not in [1, 10000]", iters);
-  if (int rc = automaton_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton)) return rc;
+  if (int rc = keep_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton, "the automaton")) return rc;
   FW_CHECK_ARG(fm->impl.cfg.n_text_ctx <= fwd::AUTOMATON_MAX_HIST, "text context of %d positions", fm->impl.cfg.n_text_ctx);
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
@@ -1321,8 +1312,8 @@ int32_t fw_test_automaton_rows(fw_model* fm, float* logits, int32_t rows, int32_
   std::vector<int32_t> table = automaton->table;   // (a copy: a forced staging is its header word 3)
   if (staging == 1) table[3] = INT32_MAX;
   if (staging == 2) table[3] = 0;
-  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, table, fwd::launch_automaton_step,
-                      fwd::launch_automaton_score, iters, us_out);
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, table, fwd::launch_automaton, iters,
+                      us_out);
 }
 
 // the same table walked on the host: no device, no model
@@ -1330,7 +1321,7 @@ int32_t fw_test_automaton_rows_host(float* logits, int32_t rows, int32_t n_vocab
                                     int32_t with_timestamps, const int32_t* hist, const int32_t* hist_offsets,
                                     const fw_automaton* automaton) {
   FW_CHECK_ARG(logits && hist_offsets && automaton && rows >= 1, "bad arguments");
-  if (int rc = automaton_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton)) return rc;
+  if (int rc = keep_hook_check(n_vocab, tok_eot, tok_ts_begin, with_timestamps, automaton, "the automaton")) return rc;
   if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
   const int zero = 0;
   fwd::automaton_rows_host(automaton->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
@@ -1338,18 +1329,13 @@ int32_t fw_test_automaton_rows_host(float* logits, int32_t rows, int32_t n_vocab
   return FW_OK;
 }
 
-// the compiled table of an automaton, as fw_test_constraint_table
 int32_t fw_test_automaton_table(const fw_automaton* automaton, int32_t* out, int32_t cap, int32_t* out_words) {
-  FW_CHECK_ARG(automaton && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
-  *out_words = (int32_t)automaton->table.size();
-  std::copy(automaton->table.begin(), automaton->table.begin() + std::min<size_t>((size_t)cap, automaton->table.size()), out);
-  return FW_OK;
+  return table_words_out(automaton, out, cap, out_words);
 }
 
 // what the language-model hooks check of the caller's vocabulary geometry and model
 static int32_t ngram_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, const fw_ngram* lm) {
-  FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
-               "bad vocabulary geometry: %d ids, <eot> %d, first timestamp %d", n_vocab, tok_eot, tok_ts_begin);
+  if (int rc = keep_geometry_hook_check(n_vocab, tok_eot, tok_ts_begin)) return rc;
   FW_CHECK_ARG(fwd::ngram_geometry_ok(lm->table.data(), n_vocab, tok_eot, tok_ts_begin),
                "the language model (%d ids, eos_id %d, largest n-gram id %d) does not go with %d ids and <eot> %d", lm->table[2],
                lm->table[3], lm->table[6], n_vocab, tok_eot);
@@ -1368,8 +1354,8 @@ int32_t fw_test_ngram_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_
   memset(&gp, 0, sizeof(gp));
   gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1; gp.lm = 1;
   gp.eot = tok_eot; gp.ts_begin = tok_ts_begin;
-  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, lm->table, fwd::launch_ngram_step,
-                      fwd::launch_ngram_score, iters, us_out);
+  return prepass_rows(&fm->impl, gp, logits, rows, hist, hist_offsets, K, done, form, lm->table, fwd::launch_ngram, iters,
+                      us_out);
 }
 
 // the same table walked on the host: no device, no model
@@ -1383,12 +1369,8 @@ int32_t fw_test_ngram_rows_host(float* logits, int32_t rows, int32_t n_vocab, in
   return FW_OK;
 }
 
-// the compiled table of a language model, as fw_test_constraint_table
 int32_t fw_test_ngram_table(const fw_ngram* lm, int32_t* out, int32_t cap, int32_t* out_words) {
-  FW_CHECK_ARG(lm && out_words && cap >= 0 && (out || cap == 0), "bad arguments");
-  *out_words = (int32_t)lm->table.size();
-  std::copy(lm->table.begin(), lm->table.begin() + std::min<size_t>((size_t)cap, lm->table.size()), out);
-  return FW_OK;
+  return table_words_out(lm, out, cap, out_words);
 }
 
 // step graphs the model's decode group has captured (and instantiated) since the model was created, all lanes together

@@ -1,6 +1,7 @@
 """generate(..., lm=) and score(..., lm=) end to end on the GPU, on the setup of tests/test_gpu_constrain.py (the micro model
 of seed 11, three chunks, 12 new tokens; A, B, C are text ids outside the suppress list): lm=NULL against the existing
-entry point, scoring, run sharing, steering by a unigram model, the constraint behind the fusion, and the call-time
+entry point, scoring (with the model alone and with every kind of extra at once), the lane buffers that scoring and decode
+runs share, run sharing, steering by a unigram model, the constraint behind the fusion, and the call-time
 ValueErrors."""
 import numpy as np
 import pytest
@@ -40,14 +41,7 @@ def test_no_model_is_the_existing_entry_point(setup, mode, monkeypatch):
     _same(model.generate(enc, [_prompt(cfg)] * 3, **kw), want, alternatives=True)
 
 
-def test_score_reproduces_greedy(setup):
-    cfg, model, enc = setup
-    prompt, lm = _prompt(cfg), model.ngram_lm(TRI, 10.0, 0.5)      # (strong enough to close every hypothesis on </s>)
-    kw = _kw_text(cfg, "greedy")
-    res = model.generate(enc, [prompt] * 3, lm=lm, return_alternatives=2, **kw)
-    plain = model.generate(enc, [prompt] * 3, **kw)
-    assert [r.sequences_ids for r in res] != [r.sequences_ids for r in plain]          # the fusion does something
-    sc = model.score(enc, [prompt] * 3, [r.sequences_ids[0] for r in res], rules=True, lm=lm, suppress_tokens=kw["suppress_tokens"])
+def _assert_score_is_the_call(res, sc):
     for r, s in zip(res, sc):
         assert len(r.sequences_ids[0]) < NEW
         assert np.array_equal(_bits(s.token_logprobs[0]), _bits(r.token_logprobs[0]))
@@ -55,6 +49,50 @@ def test_score_reproduces_greedy(setup):
         alt0 = [a[0] for a in r.token_alternatives[0]] + [r.end_alternatives[0][0]]
         assert s.best_ids[0] == [i for i, _ in alt0]
         assert np.array_equal(_bits(s.best_logprobs[0]), _bits([v for _, v in alt0]))
+
+
+@pytest.mark.parametrize("kinds", ["lm", "every kind"])
+def test_score_reproduces_greedy(setup, kinds):
+    """every kind: a boost list, the model and PH9 as a constraint list, then as the automaton of the same phrases in the
+    list's place — a path that drops a kind or uploads another kind's table cannot give the other path's bits"""
+    cfg, model, enc = setup
+    prompt, lm = _prompt(cfg), model.ngram_lm(TRI, 10.0, 0.5)      # (strong enough to close every hypothesis on </s>)
+    kw = _kw_text(cfg, "greedy")
+    plain = model.generate(enc, [prompt] * 3, **kw)
+    extras = [dict(lm=lm)]
+    if kinds == "every kind":
+        boost = model.boost_list([[A, B], [C]], [2.0, 1.5])
+        extras = [dict(lm=lm, boost=boost, constraint=model.constraint_list(PH9)),
+                  dict(lm=lm, boost=boost, automaton=model.automaton(Grammar.phrases(PH9)))]
+    ids = []
+    for ex in extras:
+        res = model.generate(enc, [prompt] * 3, return_alternatives=2, **ex, **kw)
+        ids.append([r.sequences_ids for r in res])
+        assert ids[-1] != [r.sequences_ids for r in plain]                             # the extras do something
+        sc = model.score(enc, [prompt] * 3, [r.sequences_ids[0] for r in res], rules=True, suppress_tokens=kw["suppress_tokens"], **ex)
+        _assert_score_is_the_call(res, sc)
+    assert all(i == ids[0] for i in ids)                   # the list and its automaton allow the same strings
+
+
+# larger than every other model of this file: the lane's table buffer has to grow for it
+BIG = NgramLM([{(BOS,): (0.0, -0.4), (EOS,): (-1.5, 0.0), **{(v,): (-1.0 - 0.01 * v, -0.3) for v in range(10, 60)}},
+               {(v, v + 1): (-0.2, 0.0) for v in range(10, 59)}], unk_logprob=-9.0)
+
+
+def test_scoring_and_runs_share_the_lane_buffers(setup):
+    """score() keeps its tables where a decode run keeps its own: a score call with another boost list and a larger model
+    (the buffer is replaced) between two equal generate calls changes nothing in the second, and the other way round"""
+    cfg, model, enc = setup
+    prompt, kw = _prompt(cfg), _kw_text(cfg, "greedy")
+    gen = dict(kw, return_alternatives=2, boost=model.boost_list([[A, B]], [2.0]),
+               lm=model.ngram_lm(NgramLM([{(A,): (-1.0, 0.0), (EOS,): (-1.5, 0.0)}], unk_logprob=-9.0), 2.0, 0.5))
+    score = dict(rules=True, suppress_tokens=kw["suppress_tokens"], boost=model.boost_list([[B], [C, A]], [1.0, 3.0]),
+                 lm=model.ngram_lm(BIG, 1.0))
+    want = model.generate(enc, [prompt] * 3, **gen)
+    sc = model.score(enc, [prompt] * 3, [[B, C]] * 3, **score)
+    _same(model.generate(enc, [prompt] * 3, **gen), want, alternatives=True)
+    for s, t in zip(model.score(enc, [prompt] * 3, [[B, C]] * 3, **score), sc):
+        assert np.array_equal(_bits(s.token_logprobs[0]), _bits(t.token_logprobs[0])) and s.best_ids == t.best_ids
 
 
 def test_equal_models_share_a_run_and_others_do_not():
