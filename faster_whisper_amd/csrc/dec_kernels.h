@@ -60,6 +60,9 @@ struct GenDev {
   // every run without a language model: the key, the kernels and the graphs of today.  Order, scale and bonus travel in the
   // table's header, not here.
   int lm;
+  // BOOST_TRIE (a list built by fw_boost_create_large): 1 when the step launches dec_boost_trie_kernel in dec_boost_kernel's
+  // place.  0 in every run without a large list: the key, the kernels and the graphs of today.
+  int boost_trie;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -350,6 +353,28 @@ void launch_boost(hipStream_t st, const GenDev& gp, float* logits, const int* ta
 // the same walk in plain C++ (fw_test_boost_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void boost_rows_host(const int* boost_tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
 
+// ---- phrase boosting, the LARGE form (include/fwamd.h: fw_boost_create_large; kernel, trie compiler and host walk:
+//      dec_boost_trie.hip) ----
+// The compiled table, 32-bit words: a header
+//   {edges of the trie, records, n_vocab, BOOST_TRIE_FORM_MARK, offset of the root's record, 0, 0, 0}
+// (fw_boost_create's header holds n_vocab >= 1 where this one holds the mark), then one RECORD per trie node that has
+// children, the root's first (an empty list has that one record and no edge), in the trie's pre-order:
+//   {n children, 0, n pairs (id, offset of the child's record; 0 when the child has no children),
+//                   n pairs (id, bits of the largest boost of the phrases through that edge)}
+// both pair lists ascending by id.  A node IS its record's offset.  Every field sits at an even offset (a pair is one 8-byte
+// load), and BOOST_TRIE_PAD_WORDS words of -1 behind the last record let 64 lanes load 64 pairs from ANY pair of any record
+// without leaving the table.  The table is a function of the SET of (phrase, boost) pairs: order and repeats do not show.
+constexpr int BOOST_TRIE_HDR_WORDS = 8;
+constexpr int BOOST_TRIE_REC_WORDS = 2;
+constexpr int BOOST_TRIE_PAD_WORDS = 128;
+constexpr int BOOST_TRIE_FORM_MARK = -1;
+constexpr int BOOST_TRIE_MAX_DEPTH = FW_BOOST_MAX_LEN - 1;   // the deepest node that still has an edge
+// dec_boost_trie_kernel, in launch_boost's place and with its contract and its bits.  A table built by
+// fw_boost_create_large for gp.V: the caller's to guarantee (no id >= gp.V is touched whatever the table holds).
+void launch_boost_trie(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
+// the same walk in plain C++ (fw_test_boost_trie_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void boost_trie_rows_host(const int* tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
+
 // ---- constrained decoding (include/fwamd.h: fw_constraint; kernel and table compiler: dec_constrain.hip) ----
 // The compiled table, 32-bit words: a header {P phrases, T phrase tokens, n_vocab, 0}, then
 //   off [P + 1]     phrase j is tok[off[j] .. off[j + 1]), off[0] = 0
@@ -460,7 +485,8 @@ bool ngram_geometry_ok(const int* ngram_tab, int V, int eot, int ts_begin);
 // THE statement of the kinds and of the order they are applied in.  The boost comes first: everything below sees the boosted
 // logits.  Then the language model: what is constrained and ranked below is the fused distribution.  Then the constraint
 // list: what it does not allow is -inf before the rules look — or the automaton, in the same place (no call carries both).
-enum PrePass { PRE_BOOST, PRE_LM, PRE_CONSTRAIN, PRE_AUTOMATON, PRE_KINDS };
+// (PRE_BOOST_TRIE is the boost in its large form: a call's fw_boost goes into the slot of its form, never both)
+enum PrePass { PRE_BOOST, PRE_BOOST_TRIE, PRE_LM, PRE_CONSTRAIN, PRE_AUTOMATON, PRE_KINDS };
 // One launcher per kind, in either ROW FORM.  src.tab == null, the decode step: gp.R rows, row r reads its history from
 // the parity half of hist2 that *src.d_step selects (n = step), rows of chunks with src.done[r / gp.K] are skipped; `rows`
 // is not read.  Otherwise the score form, in front of launch_score and with its row addressing: `rows` rows, rows without a
@@ -470,6 +496,7 @@ using PrePassLaunch = void (*)(hipStream_t, const GenDev&, float*, const int*, c
 static inline PrePassLaunch prepass_launcher(int kind) {
   switch (kind) {
     case PRE_BOOST: return launch_boost;
+    case PRE_BOOST_TRIE: return launch_boost_trie;
     case PRE_LM: return launch_ngram;
     case PRE_CONSTRAIN: return launch_constrain;
     case PRE_AUTOMATON: return launch_automaton;
@@ -503,8 +530,14 @@ int32_t phrase_list_check(int32_t n_vocab, const int32_t* tokens, const int32_t*
                           int max_len, int max_tokens);
 }  // namespace fwd
 
-// what fw_boost_create returns
-struct fw_boost : fw_phrase_table {};
+// what fw_boost_create and fw_boost_create_large return; large: the table is the trie (PRE_BOOST_TRIE), not the entry list
+struct fw_boost : fw_phrase_table {
+  bool large = false;
+};
+namespace fwd {
+// the slot of a call's boost list among the pre-pass kinds
+static inline int boost_kind(const fw_boost* b) { return b && b->large ? PRE_BOOST_TRIE : PRE_BOOST; }
+}  // namespace fwd
 
 // what fw_constraint_create returns: with, per compiled phrase, the index the caller gave its first occurrence (for
 // messages only: never compared)

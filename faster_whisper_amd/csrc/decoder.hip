@@ -48,6 +48,9 @@ struct PreKind {
 static constexpr PreKind kPreKinds[] = {
     {fwd::PRE_BOOST, "boost", "the boost list", "a boost list needs rules: the boost is the first step of the decoding rules",
      fwd::BOOST_TABLE_MAX_WORDS, &GenDev::boost},
+    // (a large list compiles to megabytes at its limits: sized by the largest so far, as the language model's)
+    {fwd::PRE_BOOST_TRIE, "boost", "the boost list", "a boost list needs rules: the boost is the first step of the decoding rules",
+     0, &GenDev::boost_trie},
     // (a language model can be megabytes: its buffer is sized by the largest model so far, not by a limit of the kind)
     {fwd::PRE_LM, "language-model", "the language model",
      "a language model needs rules: the fusion is a step of the decoding rules", 0, &GenDev::lm},
@@ -1575,8 +1578,9 @@ static int32_t ngram_check(const fw_ngram* lm, const fw_config& c) {
 // does nothing: its entry becomes null, and the call is one without it.  ("a constraint list or an automaton, not both" is
 // the first thing either entry point checks, in front of its null arguments.)
 static int32_t prepass_check(const fw_config& c, const fw_gen_opts* o, bool check_min_new, const fw_phrase_table* pre[PRE_KINDS]) {
-  if (pre[fwd::PRE_BOOST])
-    if (int rc = pre_vocab_check(fwd::PRE_BOOST, pre[fwd::PRE_BOOST], c)) return rc;
+  for (int k : {fwd::PRE_BOOST, fwd::PRE_BOOST_TRIE})
+    if (pre[k])
+      if (int rc = pre_vocab_check(k, pre[k], c)) return rc;
   if (pre[fwd::PRE_CONSTRAIN])
     if (int rc = constraint_check(static_cast<const fw_constraint*>(pre[fwd::PRE_CONSTRAIN]), c, o, check_min_new)) return rc;
   if (pre[fwd::PRE_AUTOMATON])
@@ -1635,7 +1639,7 @@ int32_t fw_generate_lm(fw_model* fm, const fw_tensor* enc_t, const int32_t* prom
   FW_CHECK_ARG(B == enc->B, "batch %d does not match the encoder output batch %d", B, enc->B);
   FW_CHECK_ARG(B >= 1 && B <= dm->max_batch, "batch %d exceeds max_batch %d", B, dm->max_batch);
   GenRequest req;
-  req.pre[fwd::PRE_BOOST] = boost; req.pre[fwd::PRE_LM] = lm;
+  req.pre[fwd::boost_kind(boost)] = boost; req.pre[fwd::PRE_LM] = lm;
   req.pre[fwd::PRE_CONSTRAIN] = constraint; req.pre[fwd::PRE_AUTOMATON] = automaton;
   if (int rc = prepass_check(c, o, true, req.pre)) return rc;
   const int K = o->beam_size;
@@ -2083,8 +2087,8 @@ extern "C" int32_t fw_score_lm(fw_model* fm, const fw_tensor* enc_t, const int32
                                int32_t* out_best_ids, float* out_best_logprobs) {
   FW_CHECK_ARG(!constraint || !automaton, "a call takes a constraint list or an automaton, not both");
   FW_CHECK_ARG(fm && enc_t && prompts && prompt_offsets && targets && target_offsets && out_token_logprobs, "null argument");
-  const fw_phrase_table* pre[PRE_KINDS];
-  pre[fwd::PRE_BOOST] = boost; pre[fwd::PRE_LM] = lm; pre[fwd::PRE_CONSTRAIN] = constraint; pre[fwd::PRE_AUTOMATON] = automaton;
+  const fw_phrase_table* pre[PRE_KINDS] = {};
+  pre[fwd::boost_kind(boost)] = boost; pre[fwd::PRE_LM] = lm; pre[fwd::PRE_CONSTRAIN] = constraint; pre[fwd::PRE_AUTOMATON] = automaton;
   for (int k = 0; k < PRE_KINDS; ++k) FW_CHECK_ARG(!pre[k] || rules, "%s", kPreKinds[k].needs_rules);
   FW_CHECK_ARG((out_best_ids == nullptr) == (out_best_logprobs == nullptr), "out_best_ids and out_best_logprobs go together");
   Model* m = decoder_of(&fm->impl);

@@ -1238,6 +1238,42 @@ int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist
   return FW_OK;
 }
 
+// the large form (dec_boost_trie.hip).  The vocabulary is the list's; the model gives the device and the text context.
+static GenDev boost_trie_gp(const fw_model* fm, const fw_boost* boost) {
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.V = boost->n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1;
+  (boost->large ? gp.boost_trie : gp.boost) = 1;
+  return gp;
+}
+
+int32_t fw_test_boost_trie_rows(fw_model* fm, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                int32_t K, const int32_t* done, int32_t form, const fw_boost* boost) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  FW_CHECK_ARG(boost->large, "the boost list was not built by fw_boost_create_large");
+  return prepass_rows(&fm->impl, boost_trie_gp(fm, boost), logits, rows, hist, hist_offsets, K, done, form, boost->table,
+                      fwd::launch_boost_trie);
+}
+
+int32_t fw_test_boost_trie_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                     const fw_boost* boost) {
+  FW_CHECK_ARG(logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(boost->large, "the boost list was not built by fw_boost_create_large");
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, boost->n_vocab)) return rc;
+  const int zero = 0;
+  fwd::boost_trie_rows_host(boost->table.data(), logits, rows, boost->n_vocab, hist ? hist : &zero, hist_offsets);
+  return FW_OK;
+}
+
+int32_t fw_test_boost_cost(fw_model* fm, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                           int32_t K, const fw_boost* boost, int32_t iters, float* us_out) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && us_out && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(iters >= 1 && iters <= 10000, "%d timed launches not in [1, 10000]", iters);
+  return prepass_rows(&fm->impl, boost_trie_gp(fm, boost), logits, rows, hist, hist_offsets, K, nullptr, 0, boost->table,
+                      boost->large ? fwd::launch_boost_trie : fwd::launch_boost, iters, us_out);
+}
+
 // what the constraint, automaton and language-model hooks check of the caller's vocabulary geometry (the keep mask's)
 static int32_t keep_geometry_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin) {
   FW_CHECK_ARG(n_vocab >= 1 && n_vocab <= LP_SUP_WORDS * 64 && tok_eot >= 0 && tok_eot < tok_ts_begin && tok_ts_begin <= n_vocab,
@@ -1287,6 +1323,10 @@ int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab
   fwd::constrain_rows_host(constraint->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
                            hist ? hist : &zero, hist_offsets);
   return FW_OK;
+}
+
+int32_t fw_test_boost_table(const fw_boost* boost, int32_t* out, int32_t cap, int32_t* out_words) {
+  return table_words_out(boost, out, cap, out_words);
 }
 
 int32_t fw_test_constraint_table(const fw_constraint* constraint, int32_t* out, int32_t cap, int32_t* out_words) {

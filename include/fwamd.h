@@ -67,7 +67,8 @@ extern "C" {
  *    fw_constraint_create / fw_constraint_free / fw_generate_constrain / fw_score_constrain (decoding restricted to a
  *    given phrase list), fw_automaton_create / fw_automaton_free / fw_generate_automaton / fw_score_automaton (decoding
  *    restricted to the language of a deterministic token automaton), fw_ngram_create / fw_ngram_free / fw_generate_lm /
- *    fw_score_lm (shallow fusion with a back-off n-gram language model) — new symbols only, each time */
+ *    fw_score_lm (shallow fusion with a back-off n-gram language model), fw_boost_create_large (boost lists of up to
+ *    65 536 phrases, taken by every entry point that takes an fw_boost) — new symbols only, each time */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -343,6 +344,27 @@ typedef struct fw_boost fw_boost;   /* opaque: a validated, compiled boost list 
 int32_t fw_boost_create(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
                         const float* boosts, fw_boost** out);
 void fw_boost_free(fw_boost* b);
+/* ---- boost lists at catalogue scale ----
+ * fw_boost_create with larger limits: the same arguments, the same FW_EINVAL cases against FW_BOOST_LARGE_MAX_PHRASES and
+ * FW_BOOST_LARGE_MAX_TOKENS (a phrase still holds at most FW_BOOST_MAX_LEN tokens), the same definition of the boost above,
+ * and for every list that fw_boost_create takes as well the same bits in every output of every call.  What differs is the
+ * compiled form and the kernel that walks it: a prefix trie over the phrases (a node is a phrase prefix, an edge holds the
+ * largest boost of the phrases through it), in which the matching pairs of a row are the nodes that equal a suffix of its
+ * history — the root and at most 31 more, found from the row's last 31 ids.  The object is an fw_boost: fw_boost_free
+ * frees it, and fw_generate_boost / _trunc / _constrain / _automaton / _lm and fw_score_boost / _constrain / _automaton / _lm
+ * take it wherever they take a list of fw_boost_create.  The table is a function of the SET of (phrase, boost) pairs:
+ * lists that name the same pairs in another order, or some of them twice, compile to equal bytes and share decode runs.  A
+ * list in this form and a list of fw_boost_create never share a run, whatever they hold.
+ * COST (dec_boost_trie_kernel alone, MI355X, large-v3's 51 866 ids, 80 / 640 rows, eager launches between two events,
+ * history of 0 - 31 ids; DESIGN.md, "Phrase boosting", has the table and profiles/boost_trie_cost.py made it): 2.6 - 5.0 /
+ * 2.8 - 5.3 us with 16 phrases (dec_boost_kernel: 2.6 - 2.8 / 2.7 - 2.9), 4.5 - 10.5 / 17 - 24 us with 1 024 phrases of 4
+ * (dec_boost_kernel: 19 - 25 / 38 - 44), 45 - 70 / 73 - 118 us with 65 536 phrases of 8 that start with 31 700 different ids,
+ * 2.6 - 6.8 / 2.7 - 16 us with 65 536 phrases of 8 that start with 64: the time follows the number of distinct FIRST tokens,
+ * the history and the rows, not the size of the list.  At a handful of phrases fw_boost_create's form is the faster one. */
+#define FW_BOOST_LARGE_MAX_PHRASES 65536
+#define FW_BOOST_LARGE_MAX_TOKENS 524288
+int32_t fw_boost_create_large(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
+                              const float* boosts, fw_boost** out);
 /* fw_generate_alt plus a boost list.  boost == NULL (or an empty list) is fw_generate_alt exactly; FW_EINVAL when the list
  * was built for another n_vocab than the model's.  Identity (1) of fw_generate_alt holds unchanged on boosted calls, and
  * (2) with fw_score_boost in fw_score's place.  Two calls share a decode run only when both have no list or their compiled

@@ -183,6 +183,23 @@ int32_t fw_test_boost_rows(fw_model* m, float* logits, int32_t rows, const int32
  * IN / OUT with ragged histories as above — what fw_boost_create compiled, testable without a GPU */
 int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                                 const fw_boost* boost);
+/* ONE launch of dec_boost_trie_kernel (fw_boost_create_large, include/fwamd.h) with the arguments, the row forms and the
+ * checks of fw_test_boost_rows above, except that the vocabulary is the LIST's: logits [rows][n_vocab of the list] — so a
+ * test chooses n_vocab mod 4 and with it the alignment of every row; the model gives the device and the text context.
+ * FW_EINVAL for a list of fw_boost_create. */
+int32_t fw_test_boost_trie_rows(fw_model* m, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                int32_t K, const int32_t* done, int32_t form, const fw_boost* boost);
+/* host-only (no device, no model needed): the trie walked in plain C++, as fw_test_boost_rows_host walks the entry list */
+int32_t fw_test_boost_trie_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                                     const fw_boost* boost);
+/* host-only: the compiled table of a boost list of either form (what the merge rule compares), as fw_test_constraint_table */
+int32_t fw_test_boost_table(const fw_boost* boost, int32_t* out, int32_t cap, int32_t* out_words);
+/* What one launch of a boost kernel costs: the step form of fw_test_boost_rows / fw_test_boost_trie_rows (by the list's
+ * form) over logits [rows][n_vocab of the list], then `iters` (1 .. 10000) more launches on the same buffers between two
+ * events after three untimed ones; *us_out = microseconds per launch.  The rows returned have been added to iters + 4
+ * times: they serve no comparison. */
+int32_t fw_test_boost_cost(fw_model* m, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
+                           int32_t K, const fw_boost* boost, int32_t iters, float* us_out);
 /* ONE launch of dec_constrain_kernel (constrained decoding, include/fwamd.h) in either row form on caller-provided rows,
  * with the rows, histories, K, done and form of fw_test_boost_rows above.  The model gives the device, the stream and the
  * text context only: the vocabulary geometry is the caller's — logits [rows][n_vocab] IN / OUT, returned whole, <eot> =
