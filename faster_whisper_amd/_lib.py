@@ -95,6 +95,7 @@ SYMBOLS = [
     "fw_test_boost_rows", "fw_test_boost_rows_host",
     "fw_boost_create_large", "fw_test_boost_trie_rows", "fw_test_boost_trie_rows_host", "fw_test_boost_table",
     "fw_test_boost_cost",
+    "fw_boost_create_revocable", "fw_test_boost_graph_rows", "fw_test_boost_graph_rows_host", "fw_test_boost_graph_cost",
     "fw_generate_trunc", "fw_test_logits_rules_trunc",
     "fw_constraint_create", "fw_constraint_free", "fw_generate_constrain", "fw_score_constrain",
     "fw_test_constrain_rows", "fw_test_constrain_rows_host", "fw_test_constraint_table",
@@ -260,6 +261,11 @@ def load():
         lib.fw_test_boost_trie_rows_host.argtypes = lib.fw_test_boost_rows_host.argtypes
         lib.fw_test_boost_table.argtypes = [vp, vp, i32, i32p]
         lib.fw_test_boost_cost.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, C.POINTER(C.c_float)]
+    if hasattr(lib, "fw_boost_create_revocable"):
+        lib.fw_boost_create_revocable.argtypes = lib.fw_boost_create.argtypes
+        lib.fw_test_boost_graph_rows.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
+        lib.fw_test_boost_graph_rows_host.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+        lib.fw_test_boost_graph_cost.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, C.POINTER(C.c_float)]
     if hasattr(lib, "fw_generate_trunc"):           # (absent from an older build loaded through FWAMD_LIB)
         lib.fw_generate_trunc.argtypes = [vp, vp, i32p, i32p, i32, C.POINTER(FwGenOpts), i32, C.c_float, i32, vp, i32p, i32p,
                                           f32p, f32p, f32p, f32p, i32p, f32p, i32p, f32p]

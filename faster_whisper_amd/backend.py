@@ -202,21 +202,30 @@ class BoostList(_PhraseList):
     for the model's vocabulary; pass it as generate(boost=...) / score(boost=...).
     A list of more than MAX_PHRASES phrases or MAX_TOKENS tokens (fw_boost_create's limits) is compiled by
     fw_boost_create_large — a prefix trie, up to 65 536 phrases and 524 288 tokens, the same boosts bit for bit; a list
-    inside those limits keeps fw_boost_create's table, and with it the lists it shares decode runs with."""
+    inside those limits keeps fw_boost_create's table, and with it the lists it shares decode runs with.
+    revocable=True (fw_boost_create_revocable, any size up to the large limits) changes the semantics: the bonus of a partial
+    match is taken back when the match breaks and kept when the phrase completes, and a phrase's first token is no longer
+    raised on rows that sit inside another match — fwamd.h states the contract.  Phrase ids must then lie below <eot>
+    (ValueError at generate / score).  A revocable list shares decode runs with equal revocable lists only."""
     _keyword, _a, _feature = "boost", "a BoostList (Whisper.boost_list)", "phrase boosting"
     _create, _free = "fw_boost_create", "fw_boost_free"
     MAX_PHRASES, MAX_TOKENS = 1024, 4096
 
     def __init__(self, n_vocab: int, phrases: Sequence[Sequence[int]], boosts: Sequence[float],
-                 large: Optional[bool] = None):
-        """large: None — by the list's size; True — fw_boost_create_large whatever the size"""
+                 large: Optional[bool] = None, revocable: bool = False):
+        """large: None — by the list's size; True — fw_boost_create_large whatever the size.  revocable: the third form,
+        whatever the size (large is then not read)"""
         phrases = [list(p) for p in phrases]
         boosts = list(boosts)
         if len(phrases) != len(boosts):
             raise ValueError(f"got {len(phrases)} phrases and {len(boosts)} boosts")
         b = np.asarray(boosts, dtype=np.float32).reshape(-1)
-        self.large = bool(large) or len(phrases) > self.MAX_PHRASES or sum(len(p) for p in phrases) > self.MAX_TOKENS
-        if self.large:
+        self.revocable = bool(revocable)
+        self.large = not self.revocable and (bool(large) or len(phrases) > self.MAX_PHRASES or
+                                             sum(len(p) for p in phrases) > self.MAX_TOKENS)
+        if self.revocable:
+            self._create = "fw_boost_create_revocable"
+        elif self.large:
             self._create = "fw_boost_create_large"
         self._compile(n_vocab, phrases, _lib.as_f32p(b) if b.size else None)
 
@@ -717,13 +726,14 @@ class Whisper:
         return out
 
     # ---- phrase boosting ----------------------------------------------------------------
-    def boost_list(self, phrases: Sequence[Sequence[int]], boosts: Sequence[float]) -> BoostList:
+    def boost_list(self, phrases: Sequence[Sequence[int]], boosts: Sequence[float], revocable: bool = False) -> BoostList:
         """A BoostList for this model's vocabulary: phrases[j] a sequence of token ids, boosts[j] its strength in logit
         units.  ValueError (fwamd.h: FW_BOOST_LARGE_MAX_PHRASES / FW_BOOST_MAX_LEN / FW_BOOST_LARGE_MAX_TOKENS): more than
         65536 phrases, a phrase of no token or more than 32, more than 524288 tokens in all, an id outside the vocabulary, a
         boost that is not finite.  Up to 1024 phrases and 4096 tokens the list takes fw_boost_create's form, beyond either
-        fw_boost_create_large's (BoostList)."""
-        return BoostList(self._cfg.n_vocab, phrases, boosts)
+        fw_boost_create_large's (BoostList).  revocable=True: fw_boost_create_revocable's form, whose bonus is taken back when
+        a match breaks (BoostList)."""
+        return BoostList(self._cfg.n_vocab, phrases, boosts, revocable=revocable)
 
     # ---- constrained decoding -----------------------------------------------------------
     def constraint_list(self, phrases: Sequence[Sequence[int]]) -> ConstraintList:

@@ -63,6 +63,9 @@ struct GenDev {
   // BOOST_TRIE (a list built by fw_boost_create_large): 1 when the step launches dec_boost_trie_kernel in dec_boost_kernel's
   // place.  0 in every run without a large list: the key, the kernels and the graphs of today.
   int boost_trie;
+  // BOOST_GRAPH (a list built by fw_boost_create_revocable): 1 when the step launches dec_boost_graph_kernel in
+  // dec_boost_kernel's place.  0 in every run without such a list: the key, the kernels and the graphs of today.
+  int boost_graph;
 };
 
 // GenDev::mits from the caller's max_initial_timestamp_index (unbounded there: CTranslate2 takes a size_t).  The rules
@@ -375,6 +378,30 @@ void launch_boost_trie(hipStream_t st, const GenDev& gp, float* logits, const in
 // the same walk in plain C++ (fw_test_boost_trie_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
 void boost_trie_rows_host(const int* tab, float* logits, int rows, int V, const int* hist, const int* hist_offsets);
 
+// ---- phrase boosting, the REVOCABLE form (include/fwamd.h: fw_boost_create_revocable; kernel, context-graph compiler and
+//      host walk: dec_boost_graph.hip) ----
+// The compiled table, 32-bit words: a header
+//   {edges of the trie, nodes, n_vocab, BOOST_GRAPH_FORM_MARK, offset of the root's record, largest id of any phrase, 0, 0}
+// then one RECORD per trie node — leaves too: a row's state can be one —, the root's first, in the trie's pre-order:
+//   {n children, offset of fail(u)'s record, bits of G(u), 0,
+//    n pairs (id, offset of the child's record), n pairs (id, bits of val(child))}
+// both pair lists ascending by id.  A node IS its record's offset; 0 is no node.  Every field sits at an even offset (a
+// pair is one 8-byte load).  The table is a function of the SET of (phrase, boost) pairs: order and repeats do not show.
+constexpr int BOOST_GRAPH_HDR_WORDS = 8;
+constexpr int BOOST_GRAPH_REC_WORDS = 4;
+constexpr int BOOST_GRAPH_FORM_MARK = -2;
+constexpr int BOOST_GRAPH_MAX_DEPTH = FW_BOOST_MAX_LEN;   // the deepest node: a whole phrase of the longest kind
+// dec_boost_graph_kernel (row forms: launch_prepasses, below).  logits IN / OUT: every id v <= gp.eot gets what
+// include/fwamd.h states, each written at most once; the ids above gp.eot keep their bits.  Reads gp.V, K, R, n_text_ctx,
+// eot, ts_begin.  Nothing is launched unless boost_graph_geometry_ok: the callers check.  A table built by
+// fw_boost_create_revocable: the caller's to guarantee (no id > gp.eot is touched whatever the table holds).
+void launch_boost_graph(hipStream_t st, const GenDev& gp, float* logits, const int* tab, const RowSource& src, int rows);
+// the same walk in plain C++ (fw_test_boost_graph_rows_host): row r's history is hist[hist_offsets[r] .. hist_offsets[r + 1])
+void boost_graph_rows_host(const int* tab, float* logits, int rows, int V, int eot, int ts_begin, const int* hist,
+                           const int* hist_offsets);
+// the vocabulary layout the kernel's claim mask takes: 0 <= eot < ts_begin <= V <= 64 * LP_SUP_WORDS
+bool boost_graph_geometry_ok(int V, int eot, int ts_begin);
+
 // ---- constrained decoding (include/fwamd.h: fw_constraint; kernel and table compiler: dec_constrain.hip) ----
 // The compiled table, 32-bit words: a header {P phrases, T phrase tokens, n_vocab, 0}, then
 //   off [P + 1]     phrase j is tok[off[j] .. off[j + 1]), off[0] = 0
@@ -485,8 +512,9 @@ bool ngram_geometry_ok(const int* ngram_tab, int V, int eot, int ts_begin);
 // THE statement of the kinds and of the order they are applied in.  The boost comes first: everything below sees the boosted
 // logits.  Then the language model: what is constrained and ranked below is the fused distribution.  Then the constraint
 // list: what it does not allow is -inf before the rules look — or the automaton, in the same place (no call carries both).
-// (PRE_BOOST_TRIE is the boost in its large form: a call's fw_boost goes into the slot of its form, never both)
-enum PrePass { PRE_BOOST, PRE_BOOST_TRIE, PRE_LM, PRE_CONSTRAIN, PRE_AUTOMATON, PRE_KINDS };
+// (PRE_BOOST_TRIE is the boost in its large form, PRE_BOOST_GRAPH in its revocable form: a call's fw_boost goes into the slot
+// of its form, never two)
+enum PrePass { PRE_BOOST, PRE_BOOST_TRIE, PRE_BOOST_GRAPH, PRE_LM, PRE_CONSTRAIN, PRE_AUTOMATON, PRE_KINDS };
 // One launcher per kind, in either ROW FORM.  src.tab == null, the decode step: gp.R rows, row r reads its history from
 // the parity half of hist2 that *src.d_step selects (n = step), rows of chunks with src.done[r / gp.K] are skipped; `rows`
 // is not read.  Otherwise the score form, in front of launch_score and with its row addressing: `rows` rows, rows without a
@@ -497,6 +525,7 @@ static inline PrePassLaunch prepass_launcher(int kind) {
   switch (kind) {
     case PRE_BOOST: return launch_boost;
     case PRE_BOOST_TRIE: return launch_boost_trie;
+    case PRE_BOOST_GRAPH: return launch_boost_graph;
     case PRE_LM: return launch_ngram;
     case PRE_CONSTRAIN: return launch_constrain;
     case PRE_AUTOMATON: return launch_automaton;
@@ -530,13 +559,18 @@ int32_t phrase_list_check(int32_t n_vocab, const int32_t* tokens, const int32_t*
                           int max_len, int max_tokens);
 }  // namespace fwd
 
-// what fw_boost_create and fw_boost_create_large return; large: the table is the trie (PRE_BOOST_TRIE), not the entry list
+// what fw_boost_create, fw_boost_create_large and fw_boost_create_revocable return; large: the table is the trie
+// (PRE_BOOST_TRIE), revocable: the context graph (PRE_BOOST_GRAPH), neither: the entry list.  top_phrase (revocable only;
+// for messages, never compared): the first phrase that holds the list's largest id.
 struct fw_boost : fw_phrase_table {
-  bool large = false;
+  bool large = false, revocable = false;
+  int32_t top_phrase = -1;
 };
 namespace fwd {
 // the slot of a call's boost list among the pre-pass kinds
-static inline int boost_kind(const fw_boost* b) { return b && b->large ? PRE_BOOST_TRIE : PRE_BOOST; }
+static inline int boost_kind(const fw_boost* b) {
+  return b && b->revocable ? PRE_BOOST_GRAPH : b && b->large ? PRE_BOOST_TRIE : PRE_BOOST;
+}
 }  // namespace fwd
 
 // what fw_constraint_create returns: with, per compiled phrase, the index the caller gave its first occurrence (for

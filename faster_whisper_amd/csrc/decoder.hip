@@ -51,6 +51,9 @@ static constexpr PreKind kPreKinds[] = {
     // (a large list compiles to megabytes at its limits: sized by the largest so far, as the language model's)
     {fwd::PRE_BOOST_TRIE, "boost", "the boost list", "a boost list needs rules: the boost is the first step of the decoding rules",
      0, &GenDev::boost_trie},
+    // (a revocable list: a record per phrase prefix, megabytes at its limits too)
+    {fwd::PRE_BOOST_GRAPH, "boost", "the boost list", "a boost list needs rules: the boost is the first step of the decoding rules",
+     0, &GenDev::boost_graph},
     // (a language model can be megabytes: its buffer is sized by the largest model so far, not by a limit of the kind)
     {fwd::PRE_LM, "language-model", "the language model",
      "a language model needs rules: the fusion is a step of the decoding rules", 0, &GenDev::lm},
@@ -798,7 +801,8 @@ static int pre_tables_to_lane(DecodeLane* lane, const fw_phrase_table* const pre
 // table): a truncating call shares runs with sampling calls that truncate otherwise or not at all.  The PROMPT LENGTH and
 // the <|startoftranscript|> position need not agree: a run whose calls differ in either is a RAGGED run (generate_run),
 // every chunk at its own position with its own budget min(max_length, n_text_ctx) - P.
-// BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table).
+// BOOST LISTS must agree: both calls have none, or their compiled tables are byte-equal (the run walks ONE table); a list's form (entry
+// list, trie, revocable context graph) is a kind of its own, so lists of two forms never meet.
 // CONSTRAINT LISTS (fw_generate_constrain) likewise, and AUTOMATA (fw_generate_automaton): an automaton call shares a run
 // with neither a plain nor a list-constrained call.  LANGUAGE MODELS (fw_generate_lm) likewise: scale and bonus are part
 // of the table.
@@ -1573,6 +1577,18 @@ static int32_t ngram_check(const fw_ngram* lm, const fw_config& c) {
   return FW_OK;
 }
 
+// What the entry points refuse of a revocable boost list (include/fwamd.h: fw_boost_create_revocable): one for another
+// vocabulary, or one that holds an id from <eot> up — the row's state is read off its history without the timestamps, which
+// such an id never enters, and the kernel writes the ids up to <eot> and no further.
+static int32_t boost_graph_check(const fw_boost* b, const fw_config& c) {
+  if (int rc = pre_vocab_check(fwd::PRE_BOOST_GRAPH, b, c)) return rc;
+  if (!fwd::phrase_list_live(b)) return FW_OK;   // (an empty list: no boost, nothing to refuse)
+  if (int rc = keep_mask_geometry_check(c, kPreKinds[fwd::PRE_BOOST_GRAPH].name)) return rc;
+  FW_CHECK_ARG(b->table[5] < c.tok_eot, "boost phrase %d holds id %d: the phrases of a revocable list are text, ids below <eot> = %d",
+               b->top_phrase, b->table[5], c.tok_eot);
+  return FW_OK;
+}
+
 // The extras of a call, pre[kind] as the caller passed them (null: none), against the model and the call's options / the
 // scoring rules (`o`; check_min_new: generate only): what fw_generate_lm and fw_score_lm refuse of them.  An empty list
 // does nothing: its entry becomes null, and the call is one without it.  ("a constraint list or an automaton, not both" is
@@ -1581,6 +1597,8 @@ static int32_t prepass_check(const fw_config& c, const fw_gen_opts* o, bool chec
   for (int k : {fwd::PRE_BOOST, fwd::PRE_BOOST_TRIE})
     if (pre[k])
       if (int rc = pre_vocab_check(k, pre[k], c)) return rc;
+  if (pre[fwd::PRE_BOOST_GRAPH])
+    if (int rc = boost_graph_check(static_cast<const fw_boost*>(pre[fwd::PRE_BOOST_GRAPH]), c)) return rc;
   if (pre[fwd::PRE_CONSTRAIN])
     if (int rc = constraint_check(static_cast<const fw_constraint*>(pre[fwd::PRE_CONSTRAIN]), c, o, check_min_new)) return rc;
   if (pre[fwd::PRE_AUTOMATON])

@@ -1222,6 +1222,7 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
   const fw_config& c = fm->impl.cfg;
   FW_CHECK_ARG(boost->n_vocab == c.n_vocab, "the boost list was built for a vocabulary of %d ids, the model has %d",
                boost->n_vocab, c.n_vocab);
+  FW_CHECK_ARG(!boost->revocable, "a revocable boost list: fw_test_boost_graph_rows / _rows_host walk its table");
   GenDev gp;
   memset(&gp, 0, sizeof(gp));
   gp.V = c.n_vocab; gp.n_text_ctx = c.n_text_ctx; gp.kv_div = 1; gp.boost = 1;
@@ -1232,6 +1233,7 @@ int32_t fw_test_boost_rows(fw_model* fm, float* logits, int32_t rows, const int3
 int32_t fw_test_boost_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                                 const fw_boost* boost) {
   FW_CHECK_ARG(logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(!boost->revocable, "a revocable boost list: fw_test_boost_graph_rows / _rows_host walk its table");
   if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, boost->n_vocab)) return rc;
   const int zero = 0;
   fwd::boost_rows_host(boost->table.data(), logits, rows, boost->n_vocab, hist ? hist : &zero, hist_offsets);
@@ -1270,6 +1272,7 @@ int32_t fw_test_boost_cost(fw_model* fm, float* logits, int32_t rows, const int3
                            int32_t K, const fw_boost* boost, int32_t iters, float* us_out) {
   FW_CHECK_ARG(fm && logits && hist_offsets && boost && us_out && rows >= 1, "bad arguments");
   FW_CHECK_ARG(iters >= 1 && iters <= 10000, "%d timed launches not in [1, 10000]", iters);
+  FW_CHECK_ARG(!boost->revocable, "a revocable boost list: fw_test_boost_graph_cost times its kernel");
   return prepass_rows(&fm->impl, boost_trie_gp(fm, boost), logits, rows, hist, hist_offsets, K, nullptr, 0, boost->table,
                       boost->large ? fwd::launch_boost_trie : fwd::launch_boost, iters, us_out);
 }
@@ -1323,6 +1326,58 @@ int32_t fw_test_constrain_rows_host(float* logits, int32_t rows, int32_t n_vocab
   fwd::constrain_rows_host(constraint->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, with_timestamps,
                            hist ? hist : &zero, hist_offsets);
   return FW_OK;
+}
+
+// the revocable form (dec_boost_graph.hip): what its hooks check of the caller's vocabulary geometry and list — the
+// call-time check of fw_generate_boost on a model with this layout
+static int32_t boost_graph_hook_check(int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin, const fw_boost* boost) {
+  if (int rc = keep_geometry_hook_check(n_vocab, tok_eot, tok_ts_begin)) return rc;
+  FW_CHECK_ARG(boost->revocable, "the boost list was not built by fw_boost_create_revocable");
+  FW_CHECK_ARG(boost->n_vocab == n_vocab, "the boost list was built for a vocabulary of %d ids, not %d", boost->n_vocab, n_vocab);
+  FW_CHECK_ARG(boost->table[5] < tok_eot, "boost phrase %d holds id %d: the phrases of a revocable list are text, ids below <eot> = %d",
+               boost->top_phrase, boost->table[5], tok_eot);
+  return FW_OK;
+}
+
+static GenDev boost_graph_gp(const fw_model* fm, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin) {
+  GenDev gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.V = n_vocab; gp.n_text_ctx = fm->impl.cfg.n_text_ctx; gp.kv_div = 1; gp.boost_graph = 1;
+  gp.eot = tok_eot; gp.ts_begin = tok_ts_begin;
+  return gp;
+}
+
+// The model gives the device and the text context (the stride of the step form's histories) only.
+int32_t fw_test_boost_graph_rows(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                                 int32_t tok_ts_begin, const int32_t* hist, const int32_t* hist_offsets, int32_t K,
+                                 const int32_t* done, int32_t form, const fw_boost* boost) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(form == 0 || form == 1, "form %d is not 0 (decode step) / 1 (scoring)", form);
+  if (int rc = boost_graph_hook_check(n_vocab, tok_eot, tok_ts_begin, boost)) return rc;
+  return prepass_rows(&fm->impl, boost_graph_gp(fm, n_vocab, tok_eot, tok_ts_begin), logits, rows, hist, hist_offsets, K, done,
+                      form, boost->table, fwd::launch_boost_graph);
+}
+
+// the same table walked on the host: no device, no model
+int32_t fw_test_boost_graph_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                      const int32_t* hist, const int32_t* hist_offsets, const fw_boost* boost) {
+  FW_CHECK_ARG(logits && hist_offsets && boost && rows >= 1, "bad arguments");
+  if (int rc = boost_graph_hook_check(n_vocab, tok_eot, tok_ts_begin, boost)) return rc;
+  if (int rc = boost_hist_check(rows, hist, hist_offsets, -1, n_vocab)) return rc;
+  const int zero = 0;
+  fwd::boost_graph_rows_host(boost->table.data(), logits, rows, n_vocab, tok_eot, tok_ts_begin, hist ? hist : &zero,
+                             hist_offsets);
+  return FW_OK;
+}
+
+int32_t fw_test_boost_graph_cost(fw_model* fm, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                                 int32_t tok_ts_begin, const int32_t* hist, const int32_t* hist_offsets, int32_t K,
+                                 const fw_boost* boost, int32_t iters, float* us_out) {
+  FW_CHECK_ARG(fm && logits && hist_offsets && boost && us_out && rows >= 1, "bad arguments");
+  FW_CHECK_ARG(iters >= 1 && iters <= 10000, "%d timed launches not in [1, 10000]", iters);
+  if (int rc = boost_graph_hook_check(n_vocab, tok_eot, tok_ts_begin, boost)) return rc;
+  return prepass_rows(&fm->impl, boost_graph_gp(fm, n_vocab, tok_eot, tok_ts_begin), logits, rows, hist, hist_offsets, K,
+                      nullptr, 0, boost->table, fwd::launch_boost_graph, iters, us_out);
 }
 
 int32_t fw_test_boost_table(const fw_boost* boost, int32_t* out, int32_t cap, int32_t* out_words) {

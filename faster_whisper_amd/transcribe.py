@@ -261,7 +261,8 @@ def _decode_extras(model: "WhisperModel", a) -> DecodeExtras:
     _check_lm_arguments(a["language_model"], a["lm_scale"], a["lm_bonus"])
     tokenizer = model.make_tokenizer() if a["boost_phrases"] or a["allowed_phrases"] or a["allowed_grammar"] else None
     return DecodeExtras(token_logprobs=a["token_logprobs"], token_alternatives=a["token_alternatives"],
-                        boost=model.boost_list_for(a["boost_phrases"], a["phrase_boost"], tokenizer),
+                        boost=model.boost_list_for(a["boost_phrases"], a["phrase_boost"], tokenizer,
+                                                   a["phrase_boost_revocable"]),
                         constraint=model.constraint_list_for(a["allowed_phrases"], tokenizer),
                         automaton=model.automaton_for(a["allowed_grammar"], tokenizer),
                         lm=model.lm_for(a["language_model"], a["lm_scale"], a["lm_bonus"]),
@@ -592,7 +593,7 @@ class WhisperModel:
                    token_alternatives: int = 0, boost_phrases: Optional[Sequence[str]] = None,
                    phrase_boost: Optional[float] = None, sampling_top_k: int = 0, sampling_top_p: float = 1.0,
                    allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None, language_model=None,
-                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0):
+                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0, phrase_boost_revocable: bool = False):
         """Sequential (seek-loop) transcription: 30 s windows decoded one after the other, each conditioned on
         the text before it, with the temperature-fallback ladder.  Same arguments / defaults / return value
         as the reference's WhisperModel.transcribe; `vad_speech_probs` (not in the reference) feeds
@@ -618,7 +619,8 @@ class WhisperModel:
         allowed_grammar (not in the reference): see automaton_for — a grammar.Grammar in the list's place: every decoded
         window is then a string of its language.  ValueError together with allowed_phrases.
         language_model, lm_scale, lm_bonus (not in the reference): see lm_for — shallow fusion with an n-gram language model
-        (ngram.NgramLM) in every window and every attempt of the fallback ladder.  lm_scale has no default."""
+        (ngram.NgramLM) in every window and every attempt of the fallback ladder.  lm_scale has no default.
+        phrase_boost_revocable (not in the reference): boost_phrases in the revocable form — see boost_list_for."""
         args = dict(locals())               # the call's arguments by name
         return self._transcribe(args, _decode_extras(self, args))
 
@@ -902,21 +904,25 @@ class WhisperModel:
             chosen = (best[0], best[1], temperature, best[3])   # last temperature drives the prompt reset
         return chosen
 
-    def boost_list_for(self, boost_phrases, phrase_boost, tokenizer: Tokenizer):
+    def boost_list_for(self, boost_phrases, phrase_boost, tokenizer: Tokenizer, revocable: bool = False):
         """The boost list of a transcribe() call (backend.Whisper.boost_list), or None without phrases.  Every phrase is
         encoded as " " + phrase.strip(), the form `hotwords` uses: ONE variant per phrase — the word as it stands after a
         space, in the caller's casing; a caller who wants the capitalised or the sentence-initial form boosted lists it as
         a phrase of its own.  All phrases get the strength phrase_boost (logit units; where phrases share a prefix the
         boost counts once: the list takes the maximum, not the sum).  phrase_boost has no default: no measurement on real
         speech stands behind any value, so phrases without a strength are a ValueError.  The list is built once per call
-        and reused for every window, every attempt of the temperature ladder and every batch."""
+        and reused for every window, every attempt of the temperature ladder and every batch.
+        revocable (transcribe's phrase_boost_revocable): the list in fw_boost_create_revocable's form — phrase_boost is
+        then earned token by token, taken back from a hypothesis that leaves a phrase unfinished and kept by one that
+        completes it; the backend is handed the argument only when it is set."""
         _check_boost_arguments(boost_phrases, phrase_boost)
         if boost_phrases is None:
             return None
         phrases = [tokenizer.encode(" " + p.strip()) for p in boost_phrases]
         if not phrases:
             return None
-        return self.model.boost_list(phrases, [float(phrase_boost)] * len(phrases))
+        form = {"revocable": True} if revocable else {}
+        return self.model.boost_list(phrases, [float(phrase_boost)] * len(phrases), **form)
 
     def constraint_list_for(self, allowed_phrases, tokenizer: Tokenizer):
         """The constraint list of a transcribe() call (backend.Whisper.constraint_list), or None without phrases.  Every
@@ -1236,7 +1242,7 @@ class BatchedInferencePipeline:
                    boost_phrases: Optional[Sequence[str]] = None, phrase_boost: Optional[float] = None,
                    sampling_top_k: int = 0, sampling_top_p: float = 1.0,
                    allowed_phrases: Optional[Sequence[str]] = None, allowed_grammar=None, language_model=None,
-                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0):
+                   lm_scale: Optional[float] = None, lm_bonus: float = 0.0, phrase_boost_revocable: bool = False):
         """Same contract as the reference (transcribe.py:254-578): returns (segment generator, info).
         token_logprobs=True (not in the reference): every segment is a ScoredSegment carrying the log-prob of each of
         its tokens; every other field is what the call without the keyword yields (not offered with shard=True).
@@ -1256,7 +1262,9 @@ class BatchedInferencePipeline:
         allowed_grammar (not in the reference): see WhisperModel.automaton_for — a grammar.Grammar in the list's place;
         one automaton for every batch.  ValueError together with allowed_phrases.
         language_model, lm_scale, lm_bonus (not in the reference): see WhisperModel.lm_for — one compiled model for every
-        batch.  lm_scale has no default."""
+        batch.  lm_scale has no default.
+        phrase_boost_revocable (not in the reference): boost_phrases in the revocable form — see
+        WhisperModel.boost_list_for."""
         args = dict(locals())               # the call's arguments by name
         from .vad import get_speech_timestamps
         m = self.model

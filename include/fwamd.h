@@ -68,7 +68,8 @@ extern "C" {
  *    given phrase list), fw_automaton_create / fw_automaton_free / fw_generate_automaton / fw_score_automaton (decoding
  *    restricted to the language of a deterministic token automaton), fw_ngram_create / fw_ngram_free / fw_generate_lm /
  *    fw_score_lm (shallow fusion with a back-off n-gram language model), fw_boost_create_large (boost lists of up to
- *    65 536 phrases, taken by every entry point that takes an fw_boost) — new symbols only, each time */
+ *    65 536 phrases, taken by every entry point that takes an fw_boost), fw_boost_create_revocable (a boost that is
+ *    taken back when a match breaks, likewise an fw_boost) — new symbols only, each time */
 #define FW_ABI_VERSION 2
 
 /* compute types (the reference passes the CTranslate2 strings, transcribe.py:626) */
@@ -365,6 +366,50 @@ void fw_boost_free(fw_boost* b);
 #define FW_BOOST_LARGE_MAX_TOKENS 524288
 int32_t fw_boost_create_large(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
                               const float* boosts, fw_boost** out);
+/* ---- revocable phrase boosting: an Aho-Corasick context graph ----
+ * The two forms above are STICKY: a hypothesis that starts a listed phrase keeps the boosts of the tokens it matched even
+ * when the phrase never completes, and every phrase's first token is raised at every step.  fw_boost_create_revocable takes
+ * the arguments, limits and FW_EINVAL cases of fw_boost_create_large and returns an fw_boost in a third compiled form, whose
+ * bonus is earned token by token, TAKEN BACK when the match breaks and kept for good when a phrase completes (the context
+ * graphs of k2 / sherpa, WeNet's hotwords).  fw_boost_free frees it, and fw_generate_boost / _trunc / _constrain /
+ * _automaton / _lm and fw_score_boost / _constrain / _automaton / _lm take it unchanged.  Host code: no device, no model.
+ * An empty list is valid and does nothing.
+ * THE TRIE.  A node is a phrase prefix, the root the empty one.  w(u) = the largest boosts[j] over the phrases through the
+ * edge into u (the large form's edge value); term(u): some phrase ends at u.
+ * NODE VALUES, float32, every operation in the order written:
+ *   G(root) = 0;  G(u) = 0 if term(u), else G(parent(u)) + w(u)        the bonus a partial match currently holds
+ *   C(u) = G(parent(u)) + w(u) if term(u), else 0                      the bonus banked by a completion
+ *   fail(u) = the node of the longest proper suffix of u's string that is a node (Aho-Corasick)
+ *   E(root) = 0;  E(u) = C(u) + E(fail(u))                             shorter phrases that end here as suffixes bank too
+ *   val(u) = G(u) + E(u)
+ * ROW STATE.  h is the row's generated history (never the prompt), t is h without its ids >= tok_timestamp_begin
+ * (timestamps are transparent, as for the constraint and the language model), and the row's state s is the deepest node
+ * whose string is a suffix of t — a function of the last 32 ids of t, a phrase holding at most 32 tokens.  No state is kept
+ * between steps: beam reordering needs nothing, and a merged run gives every caller its solo bits.
+ * UPDATE.  For every id v <= tok_eot: u' = the child by v of the deepest node among s, fail(s), fail(fail(s)), .. root that
+ * has an out-edge v, u' = root when none has one.  If u' == root and G(s) == 0 the id keeps its bits; otherwise
+ * logit[v] += (val(u') - G(s)): one fp32 subtract, one fp32 add, each id written once.  So:
+ *   - <eot> continues no phrase: on a row that sits mid-phrase it gets -G(s), the partial bonus is taken back at the end;
+ *   - ids above tok_eot keep their bits, and a -inf logit stays -inf;
+ *   - on a row whose state holds nothing (G(s) == 0) only the ids that continue a phrase are touched;
+ *   - along any hypothesis the deltas of its own tokens add up to the banked completions plus G of its last state.
+ * ORDER within a step is unchanged: the boost (in this form) first, then the language model, then the constraint or the
+ * automaton, then the rules.  CALL TIME: FW_EINVAL before anything is queued when the list was built for another n_vocab,
+ * or when a phrase holds an id >= tok_eot — it can never match a stripped history; the message names the phrase and the id.
+ * MERGING.  The compiled table is a function of the SET of (phrase, boost) pairs: equal sets compile to byte-equal tables
+ * and share decode runs.  A list in this form never shares a run with a list of another form, or with a plain call.
+ * COST (dec_boost_graph_kernel alone, MI355X, large-v3's 51 866 ids, 80 / 640 rows, eager launches between two events;
+ * DESIGN.md, "Phrase boosting", has the table and profiles/boost_graph_cost.py made it).  Rows whose state holds nothing
+ * (no history, or one that ends in no phrase) cost what dec_boost_trie_kernel costs on the same list or a little less: 2.6 -
+ * 3.2 / 2.7 - 3.4 us with 16 phrases, 4.2 - 5.6 / 17 - 19 us with 1 024 phrases of 4, 40 - 42 / 67 - 71 us with 65 536 phrases
+ * of 8 that start with 31 700 different ids (the trie kernel: 45 - 47 / 74 - 77), 2.3 - 3.4 / 2.6 - 3.5 us with 65 536 phrases of
+ * 8 that start with 64.  Rows that sit mid-phrase also pay the dense take-back pass, which reads and writes every id up to
+ * <eot> as dec_ngram_kernel does (17.1 / 42.0 us): 18 / 44 us with 16 phrases, 24 / 61 us with 1 024 x 4, 68 / 135 us at
+ * the limits with 31 700 first ids, 21 / 51 us with 64 — the n-gram kernel's time PLUS the sparse pass over the root, which a
+ * workgroup barrier keeps in front of the dense pass.  The sticky forms have no such pass: a row mid-phrase costs them 5 -
+ * 66 / 5 - 110 us on these lists. */
+int32_t fw_boost_create_revocable(int32_t n_vocab, const int32_t* tokens, const int32_t* offsets, int32_t n_phrases,
+                                  const float* boosts, fw_boost** out);
 /* fw_generate_alt plus a boost list.  boost == NULL (or an empty list) is fw_generate_alt exactly; FW_EINVAL when the list
  * was built for another n_vocab than the model's.  Identity (1) of fw_generate_alt holds unchanged on boosted calls, and
  * (2) with fw_score_boost in fw_score's place.  Two calls share a decode run only when both have no list or their compiled

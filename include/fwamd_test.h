@@ -192,7 +192,7 @@ int32_t fw_test_boost_trie_rows(fw_model* m, float* logits, int32_t rows, const 
 /* host-only (no device, no model needed): the trie walked in plain C++, as fw_test_boost_rows_host walks the entry list */
 int32_t fw_test_boost_trie_rows_host(float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                                      const fw_boost* boost);
-/* host-only: the compiled table of a boost list of either form (what the merge rule compares), as fw_test_constraint_table */
+/* host-only: the compiled table of a boost list of any of the three forms (what the merge rule compares), as fw_test_constraint_table */
 int32_t fw_test_boost_table(const fw_boost* boost, int32_t* out, int32_t cap, int32_t* out_words);
 /* What one launch of a boost kernel costs: the step form of fw_test_boost_rows / fw_test_boost_trie_rows (by the list's
  * form) over logits [rows][n_vocab of the list], then `iters` (1 .. 10000) more launches on the same buffers between two
@@ -200,6 +200,23 @@ int32_t fw_test_boost_table(const fw_boost* boost, int32_t* out, int32_t cap, in
  * times: they serve no comparison. */
 int32_t fw_test_boost_cost(fw_model* m, float* logits, int32_t rows, const int32_t* hist, const int32_t* hist_offsets,
                            int32_t K, const fw_boost* boost, int32_t iters, float* us_out);
+/* ONE launch of dec_boost_graph_kernel (fw_boost_create_revocable, include/fwamd.h) in either row form on caller-provided
+ * rows, with the rows, histories, K, done and form of fw_test_boost_rows above and the geometry arguments and checks of
+ * fw_test_constrain_rows below: logits [rows][n_vocab] IN / OUT, returned whole, <eot> = tok_eot, the timestamp ids from
+ * tok_ts_begin on; the model gives the device and the text context only.  FW_EINVAL: 0 <= tok_eot < tok_ts_begin <= n_vocab
+ * violated, a list of another creator or another n_vocab, a phrase id >= tok_eot (the call-time check of the entry points). */
+int32_t fw_test_boost_graph_rows(fw_model* m, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                                 int32_t tok_ts_begin, const int32_t* hist, const int32_t* hist_offsets, int32_t K,
+                                 const int32_t* done, int32_t form, const fw_boost* boost);
+/* host-only (no device, no model needed): the context graph walked in plain C++, same arguments and checks */
+int32_t fw_test_boost_graph_rows_host(float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot, int32_t tok_ts_begin,
+                                      const int32_t* hist, const int32_t* hist_offsets, const fw_boost* boost);
+/* What one launch of dec_boost_graph_kernel costs, in the manner of fw_test_boost_cost: the step form of
+ * fw_test_boost_graph_rows, then `iters` (1 .. 10000) more launches on the same buffers between two events after three
+ * untimed ones; *us_out = microseconds per launch.  The rows returned serve no comparison. */
+int32_t fw_test_boost_graph_cost(fw_model* m, float* logits, int32_t rows, int32_t n_vocab, int32_t tok_eot,
+                                 int32_t tok_ts_begin, const int32_t* hist, const int32_t* hist_offsets, int32_t K,
+                                 const fw_boost* boost, int32_t iters, float* us_out);
 /* ONE launch of dec_constrain_kernel (constrained decoding, include/fwamd.h) in either row form on caller-provided rows,
  * with the rows, histories, K, done and form of fw_test_boost_rows above.  The model gives the device, the stream and the
  * text context only: the vocabulary geometry is the caller's — logits [rows][n_vocab] IN / OUT, returned whole, <eot> =
